@@ -35,6 +35,11 @@ The JSON line also carries
                `fallback_calls` must stay 0 (no range-policy replay hidden in the figure)
   cpu_baseline oracle/sr3_oracle_aten.py (the build's restatement on torch's CPU operators — what the
                reference's CPU path runs on) timed on this host on a bounded sample ("port-aten").
+
+`--dump-outputs DIR` writes what the timed path returned after its last timed step — the images sr3_sample_end hands
+the caller (all ranks' images, gathered, with N > 1) — to DIR/images.npy in float32. The inputs are seeded, so two
+builds run with the same arguments can be compared output for output. Beyond 64 MB a fixed, seeded sample of the
+images is written instead, with their batch indices in DIR/images_index.npy.
 """
 import argparse
 import importlib
@@ -77,7 +82,33 @@ def parse():
     ap.add_argument("--no-full-loop", action="store_true", help="skip the timed whole-loop sr3_sample call (N=1 only)")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-steps", type=int, default=32)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the images of the last timed step to DIR/images.npy (float32, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, images):
+    """--dump-outputs: `images` [N,3,r,r] as DIR/images.npy (float32). Over DUMP_BYTES, a fixed, seeded sample of the
+    images (ascending batch index) is written, and its indices as DIR/images_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(images, dtype=np.float32)
+    files = {}
+    if a.nbytes > DUMP_BYTES:
+        n = a.shape[0]
+        keep = (DUMP_BYTES - 8 * n) // a[0].nbytes       # room for the index file
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        a = a[idx]
+        np.save(os.path.join(path, "images_index.npy"), idx.astype(np.float64))
+        files["images_index"] = [int(idx.shape[0])]
+    np.save(os.path.join(path, "images.npy"), a)
+    files["images"] = list(a.shape)
+    return files
 
 
 def cpu_baseline(cfg, sd, sched_opt, args, synth):
@@ -315,6 +346,9 @@ def main():
         if world == 1 and rank == 0 and backend == "nccl":
             assert torch.equal(gathered, out), "world-size-1 all-gather must be the identity"
     sec_per_step = dt / K
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, (gathered if collective else out).cpu().numpy())
 
     # ---- per-mode blocks (rank 0): the headline mode first, then the other arithmetic modes of the same library
     def roofline_block(precision, steps, t_from, sec_step):
@@ -416,6 +450,8 @@ def main():
             for m in alts:
                 alts[m]["parity"] = gpu_parity(eng, torch, sample, args, m, B)
         res["fallback_calls"] = eng.fallback_calls()
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(res, allow_nan=False) + "\n").encode())
     if collective:
