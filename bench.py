@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: SR images/sec for the full SR3 p_sample_loop (16->128) on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is ONE p_sample step (UNet forward + DDPM update, reference diffusion.py:182-187) over
@@ -15,11 +15,14 @@ Inputs are resident in HBM before the timed region. Multi-GPU: the batch is shar
 scaling, 64 images per GPU), no collective inside the loop, one RCCL all-gather of the finished
 images at the end of the timed region.
 
-The headline (`value`, `ms_per_step`, `dtype`, `roofline`) is measured in the REFERENCE's arithmetic: fp32 operands,
-fp32 accumulation (`--precision f32`, v_mfma_f32_32x32x2_f32; reference unet.py:235-265 / diffusion.py:164-187 compute
-in plain fp32). The library's faster split-f16 arithmetics are reported next to it, never as `value`.
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` if asked and prints the JSON line: the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and the workload's `config`. The
+headline is measured in the REFERENCE's arithmetic: fp32 operands, fp32 accumulation (`--precision f32`,
+v_mfma_f32_32x32x2_f32; reference unet.py:235-265 / diffusion.py:164-187 compute in plain fp32). The library's faster
+split-f16 arithmetics are reported next to it under `--full`, never as `value`.
 
-The JSON line also carries
+`--full` runs everything else after the timed region and adds to the line (`--no-alt`, `--no-cpu-baseline`,
+`--no-full-loop` leave parts out)
   roofline     the conv implicit-GEMM kernel family of the headline mode: algorithmic FLOPs / HIP-event time per
                launch against the dense MFMA peak of the mode's instruction — 157.3 TFLOP/s (f32-input MFMA) for f32,
                2500 TFLOP/s (f16 MFMA) for the split-f16 modes (f16f8 is priced against the f16 peak too) — plus
@@ -35,6 +38,7 @@ The JSON line also carries
                `fallback_calls` must stay 0 (no range-policy replay hidden in the figure)
   cpu_baseline oracle/sr3_oracle_aten.py (the build's restatement on torch's CPU operators — what the
                reference's CPU path runs on) timed on this host on a bounded sample ("port-aten").
+None of it touches the timed steps, `value` or what `--dump-outputs` writes.
 
 `--dump-outputs DIR` writes what the timed path returned after its last timed step — the images sr3_sample_end hands
 the caller (all ranks' images, gathered, with N > 1) — to DIR/images.npy in float32. The inputs are seeded, so two
@@ -76,10 +80,13 @@ def parse():
     ap.add_argument("--image-size", type=int, default=224, help="UNet image_size key: 224 = yml-literal, 128 = 6 attention modules")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16x3", "f16f8"],
                     help="arithmetic of the HEADLINE: f32 = the reference's (default); the split-f16 modes are "
-                         "reported as alt_precisions")
-    ap.add_argument("--no-alt", action="store_true", help="skip the measurement of the other arithmetic modes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-full-loop", action="store_true", help="skip the timed whole-loop sr3_sample call (N=1 only)")
+                         "reported as alt_precisions (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline pass, the other arithmetic modes, the whole-loop "
+                         "call, the CPU baseline and the GPU-vs-CPU parity (a plain run measures the headline only)")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the measurement of the other arithmetic modes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity")
+    ap.add_argument("--no-full-loop", action="store_true", help="with --full: skip the timed whole-loop sr3_sample call (N=1 only)")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-steps", type=int, default=32)
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
@@ -403,9 +410,9 @@ def main():
 
     roof = None
     alts = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         t_next, roof = roofline_block(args.precision, K, t_next, sec_per_step)
-    if rank == 0 and not args.no_alt:
+    if rank == 0 and args.full and not args.no_alt:
         t_a = t_next
         for other in [m for m in ("f32", "f16x3", "f16f8") if m != args.precision]:
             eng.set_precision(other)
@@ -435,15 +442,16 @@ def main():
                                           "PyTorch encoder; FLAME assets and loguru absent): SR stage only"),
                        "parallelism": f"batch-sharded x{world}, one all-gather at the end" +
                                       (" (SR3_FORCE_COLLECTIVE: world-size-1 RCCL all-gather executed)" if collective and world == 1 else "")},
-            "roofline": roof,
-            "alt_precisions": alts,
         }
-        if world == 1 and not args.no_full_loop:
+        if args.full:
+            res["roofline"] = roof
+            res["alt_precisions"] = alts
+        if args.full and world == 1 and not args.no_full_loop:
             res["full_loop"] = full_loop(eng, torch, B, r, T, cond, sec_per_step, args.precision)
             if alts:
                 fastest = min(alts, key=lambda m: alts[m]["ms_per_step"])
                 alts[fastest]["full_loop"] = full_loop(eng, torch, B, r, T, cond, alts[fastest]["ms_per_step"] * 1e-3, fastest)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             base, sample = cpu_baseline(cfg, sd, sched_opt, args, synth)
             res["cpu_baseline"] = base
             res["parity"] = dict(gpu_parity(eng, torch, sample, args, args.precision, B), precision=args.precision)
