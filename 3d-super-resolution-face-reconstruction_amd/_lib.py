@@ -69,6 +69,7 @@ PROTOTYPES = {
     "sr3_weights_missing": (_I, [_P]),
     "sr3_unet_forward": (_I, [_P, _F, _F, _I, _I, _I, _F]),
     "sr3_set_schedule": (_I, [_P, _I, _F, _F, _F, _F, _F, _F]),
+    "sr3_set_sampler_schedule": (_I, [_P, _I, _F, _F, _F, _F, _F, _F, _F, _I]),
     "sr3_sample": (_I, [_P, _F, _I, _I, _I, _F, _U64, _U64, _F, _F]),
     "sr3_num_frames": (_I, [_P]),
     "sr3_max_batch": (_I, [_P, _I, _I]),

@@ -1393,6 +1393,8 @@ __global__ void init_state_kernel(const TDesc state, int xoff, int C, const floa
 
 // One p_sample tail (reference diffusion.py:144-151 predict_start_from_noise, :175-176 clamp,
 // :153-162 q_posterior, :182-187 p_sample), element-wise in the reference's operation order.
+// The few-step samplers reuse it with their own coefficients: DDIM fits c1, c2, sigma as they are;
+// DPM-Solver++(2M) adds c3 times the previous step's clamped x0 (StepArgs::hist, UpdateParams::hist).
 // One thread per (image, channel, pixel) in NCHW order (a thread per pixel with its three Philox / Box-Muller
 // evaluations in sequence measured 1.5x slower: the kernel is bound by that arithmetic, not by its accesses).
 __global__ void ddpm_update_kernel(const UpdateParams u, size_t total) {
@@ -1412,6 +1414,10 @@ __global__ void ddpm_update_kernel(const UpdateParams u, size_t total) {
     float x0 = __fsub_rn(__fmul_rn(sa.a, x), __fmul_rn(sa.b, e));
     x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
     float v = __fadd_rn(__fmul_rn(sa.c1, x0), __fmul_rn(sa.c2, x));
+    if (sa.hist) {                      // multistep samplers: never taken on the DDPM path (sr3_set_schedule)
+        if (sa.hist == 2) v = __fadd_rn(v, __fmul_rn(sa.c3, u.hist[i]));
+        u.hist[i] = x0;                 // (same element, same thread: read before the overwrite)
+    }
     if (sa.sigma != 0.f) {
         const float z = sa.noise ? sa.noise[i]
                                  : philox_normal(sa.seed, sa.image_offset + n, sa.draw, (uint32_t)(c * HW + pp));

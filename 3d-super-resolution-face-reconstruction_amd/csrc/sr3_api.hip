@@ -7,6 +7,7 @@
 #include "sr3_internal.h"
 
 #include <math.h>
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -165,6 +166,7 @@ struct sr3_ctx {
     float *x0p = nullptr;       // packed split-f16 state for conv_in_kernel (null: shape not supported); kept in
                                 // step with x0 by launch_pack_state / the DDPM update
     TDesc eps;                  // [B][H][W][out_channel]
+    float *xhist = nullptr;     // NCHW [B][out_channel][H][W]: x0 history of the multistep samplers (UpdateParams::hist)
     TDesc final_act;            // activated input of final_conv
     float *qkvb = nullptr, *aob = nullptr, *vtb = nullptr;   // attention: qkv, core output, v^T scratch (split-f16 core)
     float *part = nullptr;      // split-K partial sums (small-M convs)
@@ -172,9 +174,11 @@ struct sr3_ctx {
     float *temb = nullptr, *cbias = nullptr;
     int cb_stride = 0;          // row stride of cbias: nf_total, or 0 when one noise level serves the whole batch (sampler steps)
 
-    // schedule
-    int T = 0;
-    std::vector<float> s_nl, s_a, s_b, s_lv, s_c1, s_c2;
+    // sampler schedule (sr3_set_schedule: the reference's DDPM loop; sr3_set_sampler_schedule: S of its levels)
+    int T = 0;              // steps of one call: T of the DDPM schedule, or S
+    std::vector<float> s_nl, s_a, s_b, s_c1, s_c2, s_c3, s_sig;   // s_nl [T+1], the others [T], indexed by step t
+    bool uses_hist = false; // the update keeps the clamped x0 of the previous step (xhist)
+    bool hist_valid = false;// xhist holds the x0 of an earlier step of the current call (reset by sr3_sample_begin)
     float *d_nl = nullptr;  // [T+1]
 
     // sampler state
@@ -601,6 +605,7 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     const uint64_t o_te = cv.take((uint64_t)B * g.inner_channel);
     const uint64_t o_cb = cv.take((uint64_t)B * c->nf_total);
     const uint64_t o_eps = cv.take((uint64_t)B * HW * g.out_channel);
+    const uint64_t o_hist = cv.take((uint64_t)B * HW * g.out_channel);
     HIP_OK(hipMalloc(&c->arena, cv.off));
     c->arena_bytes = cv.off;
     // zero everything once: the 1-pixel borders and the pad channels of x0 stay zero for the
@@ -643,6 +648,7 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     c->x0s = desc(o_x0s, c->in_pad, H, W, 1);
     c->x0p = ci_ok ? at(o_x0p) : nullptr;
     c->eps = desc(o_eps, g.out_channel, H, W, 0);
+    c->xhist = at(o_hist);
     c->final_act = desc(o_fa, c->final_gn.C, H, W, 1);
     c->qkvb = at(o_qkv); c->aob = at(o_ao); c->vtb = at(o_vt);
     c->part = max_part ? at(o_part) : nullptr;
@@ -1142,6 +1148,7 @@ void enqueue_step(sr3_ctx *c) {
     u.eps = c->eps;
     u.args = c->d_step;
     u.ovf = c->prec ? c->d_ovf : nullptr;       // (the packed copy is only read in split-f16 mode)
+    u.hist = c->xhist;                          // constant per workspace: the captured graph stays valid
     c->pbegin(F_MISC);
     launch_ddpm_update(u, B, c->stream);
     c->pend();
@@ -1161,9 +1168,12 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     StepArgs &sa = c->h_ring[c->step_count % sr3_ctx::kRing];
     ++c->step_count;
     sa.nl = c->s_nl[t + 1];
-    sa.a = c->s_a[t]; sa.b = c->s_b[t]; sa.c1 = c->s_c1[t]; sa.c2 = c->s_c2[t];
-    sa.sigma = t > 0 ? expf(0.5f * c->s_lv[t]) : 0.f;
+    sa.a = c->s_a[t]; sa.b = c->s_b[t]; sa.c1 = c->s_c1[t]; sa.c2 = c->s_c2[t]; sa.c3 = c->s_c3[t];
+    sa.sigma = c->s_sig[t];
     sa.draw = (uint32_t)(c->T - t); sa.pad_ = 0;
+    // the first step after sr3_sample_begin has no previous x0: it only stores its own
+    sa.hist = c->uses_hist ? (c->hist_valid ? 2u : 1u) : 0u;
+    if (c->uses_hist) c->hist_valid = true;
     sa.noise = noise_slab; sa.frame = frame;
     sa.seed = c->seed; sa.image_offset = c->image_offset;
     HIP_OK(hipMemcpyAsync(c->d_step, &sa, sizeof(StepArgs), hipMemcpyHostToDevice, c->stream));
@@ -1456,24 +1466,46 @@ int sr3_unet_forward(sr3_ctx *c, const float *x_dev, const float *noise_level_de
     return warn_fallback(c, "sr3_unet_forward", "the forward pass");
 }
 
+static int set_step_tables(sr3_ctx *c, int T, const float *noise_level, const float *a, const float *b,
+                           const float *c1, const float *c2, const float *c3, const std::vector<float> &sigma,
+                           bool uses_hist) {
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    c->T = T;
+    c->s_nl.assign(noise_level, noise_level + T + 1);
+    c->s_a.assign(a, a + T);
+    c->s_b.assign(b, b + T);
+    c->s_c1.assign(c1, c1 + T);
+    c->s_c2.assign(c2, c2 + T);
+    if (c3) c->s_c3.assign(c3, c3 + T);
+    else c->s_c3.assign((size_t)T, 0.f);
+    c->s_sig = sigma;
+    c->uses_hist = uses_hist;
+    if (c->d_nl) HIP_OK(hipFree(c->d_nl));
+    HIP_OK(hipMalloc(&c->d_nl, (size_t)(T + 1) * sizeof(float)));
+    HIP_OK(hipMemcpy(c->d_nl, noise_level, (size_t)(T + 1) * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
 int sr3_set_schedule(sr3_ctx *c, int T, const float *noise_level, const float *recip, const float *recipm1,
                      const float *logvar, const float *coef1, const float *coef2) {
     if (!c) return fail("null context");
     if (T < 1 || !noise_level || !recip || !recipm1 || !logvar || !coef1 || !coef2)
         return fail("sr3_set_schedule: invalid argument");
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    c->T = T;
-    c->s_nl.assign(noise_level, noise_level + T + 1);
-    c->s_a.assign(recip, recip + T);
-    c->s_b.assign(recipm1, recipm1 + T);
-    c->s_lv.assign(logvar, logvar + T);
-    c->s_c1.assign(coef1, coef1 + T);
-    c->s_c2.assign(coef2, coef2 + T);
-    if (c->d_nl) HIP_OK(hipFree(c->d_nl));
-    HIP_OK(hipMalloc(&c->d_nl, (size_t)(T + 1) * sizeof(float)));
-    HIP_OK(hipMemcpy(c->d_nl, noise_level, (size_t)(T + 1) * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    std::vector<float> sigma((size_t)T);
+    for (int t = 0; t < T; ++t) sigma[t] = t > 0 ? expf(0.5f * logvar[t]) : 0.f;
+    return set_step_tables(c, T, noise_level, recip, recipm1, coef1, coef2, nullptr, sigma, false);
+}
+
+int sr3_set_sampler_schedule(sr3_ctx *c, int S, const float *noise_level, const float *a, const float *b,
+                             const float *c1, const float *c2, const float *c3, const float *sigma, int uses_history) {
+    if (!c) return fail("null context");
+    if (S < 1 || !noise_level || !a || !b || !c1 || !c2 || !c3 || !sigma)
+        return fail("sr3_set_sampler_schedule: invalid argument");
+    for (int i = 0; i < S; ++i)
+        if (!std::isfinite(c1[i]) || !std::isfinite(c2[i]) || !std::isfinite(c3[i]) || !std::isfinite(sigma[i]) || sigma[i] < 0.f)
+            return fail("sr3_set_sampler_schedule: coefficients of step %d are not finite (or sigma < 0)", i);
+    return set_step_tables(c, S, noise_level, a, b, c1, c2, c3, std::vector<float>(sigma, sigma + S), uses_history != 0);
 }
 
 int sr3_max_batch(sr3_ctx *c, int H, int W) {
@@ -1502,6 +1534,7 @@ int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, con
     if (ensure_workspace(c, B, H, W)) return -1;
     c->seed = seed;
     c->image_offset = image_offset;
+    c->hist_valid = false;
     if (range_reset(c)) return -1;
     c->pbegin(F_MISC);
     if (cond_dev) launch_nchw_to_nhwc(cond_dev, B, nc, c->x0, 0, c->stream);
@@ -1558,24 +1591,43 @@ int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const flo
     //    arithmetic, whatever the policy.
     const bool guard = c->prec == 1;
     const int seg = std::max(1, T / 10);
-    if (guard && c->ckpt_floats < slab) {
+    // a multistep sampler's update also reads the previous step's x0: the checkpoint holds that history too
+    const size_t ck_floats = c->uses_hist ? 2 * slab : slab;
+    if (guard && c->ckpt_floats < ck_floats) {
         if (c->ckpt) HIP_OK(hipFree(c->ckpt));
         c->ckpt = nullptr; c->ckpt_floats = 0;
-        HIP_OK(hipMalloc(&c->ckpt, slab * sizeof(float)));
-        c->ckpt_floats = slab;
+        HIP_OK(hipMalloc(&c->ckpt, ck_floats * sizeof(float)));
+        c->ckpt_floats = ck_floats;
     }
-    auto save = [&]() { launch_nhwc_to_nchw(c->x0, nc, B, C, c->ckpt, c->stream); };
-    auto restore = [&]() {
+    // save / restore: 0, or -1 with the error set
+    bool ck_hist_valid = false;
+    auto save = [&]() -> int {
+        launch_nhwc_to_nchw(c->x0, nc, B, C, c->ckpt, c->stream);
+        ck_hist_valid = c->hist_valid;
+        if (c->uses_hist) {
+            const hipError_t e = hipMemcpyAsync(c->ckpt + slab, c->xhist, slab * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+            if (e != hipSuccess) return fail("sr3_sample: checkpoint of the x0 history: %s", hipGetErrorString(e));
+        }
+        return 0;
+    };
+    auto restore = [&]() -> int {
         launch_init_state(c->x0, nc, C, c->ckpt, seed, image_offset, B, c->stream);
         if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
+        c->hist_valid = ck_hist_valid;
+        if (c->uses_hist) {
+            const hipError_t e = hipMemcpyAsync(c->xhist, c->ckpt + slab, slab * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+            if (e != hipSuccess) return fail("sr3_sample: restore of the x0 history: %s", hipGetErrorString(e));
+        }
+        return 0;
     };
     // back to the last clean boundary, one arithmetic down from here on: f16f8 -> f16x3 (the fp8 operands have the
     // narrower range; the guard stays on) -> exact f32 (the mode is restored before the call returns)
     const bool f8_was = c->f8corr;
-    auto fall_back = [&]() {
-        restore();
+    auto fall_back = [&]() -> int {
+        if (restore()) return -1;
         if (c->f8corr) c->f8corr = false;
         else c->prec = 0;
+        return 0;
     };
     int t_ck = T - 1, f_ck = 0;          // the checkpoint holds the state BEFORE step t_ck; f_ck frames were written by then
     bool fell_back = false;              // exact f32 from here on: no more checks
@@ -1586,7 +1638,7 @@ int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const flo
         if (r < 0) return -1;
         if (r == 1 && c->strict_range) return range_fail(c, "sr3_sample");
         if (r == 1) { c->prec = 0; fell_back = any_fallback = true; }
-        else save();
+        else if (save()) return -1;
     }
     int f = 0;
     // boundary check: 0 = clean (checkpoint taken by the caller), 1 = rewound to the checkpoint, -1 = error (rc set)
@@ -1594,9 +1646,14 @@ int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const flo
         const int r = range_read(c);
         if (r < 0) { rc = -1; return -1; }
         if (r == 0) return 0;
-        if (r == 2) { restore(); replayed = true; return 1; }
+        if (r == 2) {
+            if (restore()) { rc = -1; return -1; }
+            replayed = true;
+            return 1;
+        }
         if (c->strict_range) { rc = range_fail(c, "sr3_sample"); return -1; }
-        fall_back(); fell_back = c->prec == 0; any_fallback = true;
+        if (fall_back()) { rc = -1; return -1; }
+        fell_back = c->prec == 0; any_fallback = true;
         return 1;
     };
     for (int t = T - 1; t >= 0; --t) {
@@ -1604,7 +1661,8 @@ int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const flo
             const int b = boundary();
             if (b < 0) break;
             if (b == 1) { t = t_ck; f = f_ck; }
-            else { save(); t_ck = t; f_ck = f; }
+            else if (save()) { rc = -1; break; }
+            else { t_ck = t; f_ck = f; }
         }
         const float *nz = (noise_dev && t > 0) ? noise_dev + (size_t)(T - t) * slab : nullptr;
         float *fr = (frames_dev && (t % si == 0)) ? frames_dev + (size_t)(f++) * slab : nullptr;

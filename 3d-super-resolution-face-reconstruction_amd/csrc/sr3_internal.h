@@ -298,7 +298,10 @@ void launch_nhwc_to_nchw(const TDesc &src, int coff, int B, int C, float *out, h
 struct StepArgs {
     float nl;                   // noise level fed to the embedding (diffusion.py:166-167)
     float a, b, c1, c2, sigma;  // recip, recipm1, coef1, coef2, exp(0.5*logvar) (0 at t == 0)
-    uint32_t draw, pad_;
+    float c3;                   // weight of the previous step's x0 (multistep samplers, hist == 2)
+    uint32_t draw;
+    uint32_t hist;              // x0 history: 0 untouched (DDPM / DDIM), 1 store x0, 2 read the previous x0, then store
+    uint32_t pad_;
     const float *noise;         // NCHW [B][C][HW] or null -> Philox
     float *frame;               // NCHW [B][C][HW] or null: copy of the updated image
     uint64_t seed, image_offset;
@@ -310,6 +313,7 @@ struct UpdateParams {
     TDesc eps;          // eps.C >= C
     const StepArgs *args;
     int *ovf = nullptr; // range check of the packed copy (ConvParams::ovf contract)
+    float *hist = nullptr;  // NCHW [B][C][H][W] clamped x0 of the previous step (StepArgs::hist)
 };
 void launch_ddpm_update(const UpdateParams &p, int B, hipStream_t s);
 // x <- noise (NCHW buffer or Philox draw 0) into state channels

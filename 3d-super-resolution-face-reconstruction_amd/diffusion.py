@@ -11,6 +11,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import samplers as _samplers
 from . import schedule as _schedule
 from ._lib import Sr3Error
 
@@ -27,6 +28,7 @@ class GaussianDiffusion(nn.Module):
         self.num_timesteps = 0
         self._sched_np = None
         self._sched_pushed = None   # engine id the schedule was pushed to
+        self._sampler = ("ddpm", None, 0.0)   # set_sampler(); not part of state_dict()
 
     # ---- reference surface that is configuration only -----------------------------------------
     def set_loss(self, device=None):
@@ -53,6 +55,28 @@ class GaussianDiffusion(nn.Module):
         self._sched_np = bufs
         self._sched_pushed = None
 
+    def set_sampler(self, kind="ddpm", steps=None, eta=0.0):
+        """Sampling algorithm of every sampling entry point (super_resolution, sample, p_sample_loop, sample_batch,
+        super_resolution_batch; validation.validate_batch and the dist.sharded_* helpers through them), DESIGN.md §3.5:
+
+          "ddpm"      the reference's ancestral loop over all T steps (default)
+          "ddim"      DDIM over `steps` (S) of the schedule's levels; eta = 0 deterministic, eta = 1 with S = T is DDPM
+          "dpmpp_2m"  DPM-Solver++(2M), deterministic, second order
+
+        steps=None means S = T. The setting survives set_new_noise_schedule (the tables are re-derived from the new
+        schedule) and adds nothing to state_dict(). p_sample / p_mean_variance / q_posterior stay the reference's
+        single DDPM step whatever the setting."""
+        # (without a schedule yet, S <= T is checked when the tables are derived)
+        _samplers.check_sampler(kind, steps, eta, self.num_timesteps if self._sched_np is not None else None)
+        self._sampler = (kind, None if steps is None or kind == "ddpm" else int(steps), float(eta))
+        self._sched_pushed = None
+
+    @property
+    def num_sampling_steps(self) -> int:
+        """S: UNet evaluations of one sampling call (num_timesteps = T for the default "ddpm" sampler)."""
+        kind, steps, _ = self._sampler
+        return self.num_timesteps if steps is None else int(steps)
+
     def _engine(self):
         eng = self.denoise_fn.engine()
         if self._sched_np is None:
@@ -60,15 +84,31 @@ class GaussianDiffusion(nn.Module):
         # like the reference, sample with whatever the registered buffers hold now (a checkpoint's
         # load_state_dict may have replaced them, diffusion.py:144-162 reads self.<buffer>[t]); the
         # noise levels come from the config-derived float64 array (diffusion.py:108-109,166-167)
-        sig = (id(eng),) + tuple((self._buffers[k].data_ptr(), self._buffers[k]._version)
-                                 for k in _schedule.ENGINE_BUFFERS)
+        sig = (id(eng), self._sampler) + tuple((self._buffers[k].data_ptr(), self._buffers[k]._version)
+                                               for k in _schedule.ENGINE_BUFFERS)
         if self._sched_pushed != sig:
             bufs = {"noise_level": self._sched_np["noise_level"]}
             for k in _schedule.ENGINE_BUFFERS:
                 bufs[k] = self._buffers[k].detach().to("cpu", torch.float32).numpy()
-            eng.set_schedule(bufs)
+            kind, steps, eta = self._sampler
+            if kind == "ddpm":
+                eng.set_schedule(bufs)
+            else:
+                bufs["sqrt_alphas_cumprod_prev"] = self._sched_np["sqrt_alphas_cumprod_prev"]
+                eng.set_sampler_schedule(_samplers.sampler_tables(bufs, kind, steps, eta))
             self._sched_pushed = sig
         return eng
+
+    def _ddpm_engine(self):
+        """The engine with the reference's DDPM schedule (p_sample: one reference step whatever set_sampler chose)."""
+        if self._sampler[0] == "ddpm":
+            return self._engine()
+        keep = self._sampler
+        try:
+            self._sampler = ("ddpm", None, 0.0)
+            return self._engine()
+        finally:
+            self._sampler = keep
 
     # ---- sampling ------------------------------------------------------------------------------
     @staticmethod
@@ -93,8 +133,9 @@ class GaussianDiffusion(nn.Module):
         """p_sample_loop for a whole batch (diffusion.py:189-215).
 
         x_in: conditioning [B,3,H,W] (conditional) or a shape tuple (unconditional, :193-201).
-        noise: optional [T,B,C,H,W] tensor replacing the RNG (slab 0 = initial image, slab k = the
-        randn_like of step t=T-k). Returns [B,C,H,W], or (final, frames [n,B,C,H,W]) if continous.
+        noise: optional [S,B,C,H,W] tensor replacing the RNG (slab 0 = initial image, slab k = the
+        randn_like of step t=S-k; S = num_sampling_steps, = T for the default sampler). Returns [B,C,H,W], or
+        (final, frames [n,B,C,H,W]) if continous.
 
         Batches above the library's per-call limit (4 GiB per activation tensor: ~250 images at 128x128) — the
         reference's validation loop is 15 samples x N images (lib/trainer_temp.py:441-446), BASELINE configs[3] is 512
@@ -110,7 +151,7 @@ class GaussianDiffusion(nn.Module):
             B, _, H, W = tuple(x_in)
             dev, x = next(self.denoise_fn.parameters()).device, None
         C = self.channels
-        T = self.num_timesteps
+        T = self.num_sampling_steps
         out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
         frames = None
         if continous:
@@ -204,7 +245,7 @@ class GaussianDiffusion(nn.Module):
         """One reverse step (diffusion.py:182-187) on the device."""
         if not clip_denoised:
             raise NotImplementedError("clip_denoised=False is never used by the reference")
-        eng = self._engine()
+        eng = self._ddpm_engine()
         x = x.to(torch.float32).contiguous()
         B, _, H, W = x.shape
         cond = condition_x.to(torch.float32).contiguous() if condition_x is not None else None

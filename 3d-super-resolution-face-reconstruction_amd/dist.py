@@ -100,6 +100,7 @@ def sharded_p_sample_loop(netG, x_full: torch.Tensor, continous: bool = False, s
       continous=True  -> `ret_img` = cat([x_in, frame_0, ..., frame_9]) on dim 0, [(1 + n_frames) * N, 3, H, W], the
                          conditioning batch first (:203-204), then the whole batch after every recorded step (:209-211)
 
+    The sampler is netG's setting (GaussianDiffusion.set_sampler); with S steps there are len(frame_steps(S)) frames.
     Two collectives at most: the final images (N/world x 3 x r x r per rank) and, if continous, the frames (n_frames
     times as much: 126 MB per rank for 256 images at 128x128 — still one call). `seed` must be the same on every rank
     (Philox streams are keyed by the global image index)."""

@@ -178,6 +178,23 @@ class Engine:
         _lib.check(self.lib.sr3_set_schedule(self.ctx, T, *[a.ctypes.data for a in arrs]))
         self.T = T
 
+    def set_sampler_schedule(self, tables: Dict) -> None:
+        """A sampler's per-step tables (samplers.sampler_tables): S steps from then on. "ddpm" tables go through
+        sr3_set_schedule, the reference's loop exactly."""
+        S = int(tables["S"])
+        if tables.get("kind") == "ddpm":
+            self.set_schedule({"noise_level": tables["noise_level"], "sqrt_recip_alphas_cumprod": tables["a"],
+                               "sqrt_recipm1_alphas_cumprod": tables["b"], "posterior_log_variance_clipped": tables["logvar"],
+                               "posterior_mean_coef1": tables["c1"], "posterior_mean_coef2": tables["c2"]})
+            return
+        nl = _host_f32(tables["noise_level"])
+        arrs = [_host_f32(tables[k]) for k in ("a", "b", "c1", "c2", "c3", "sigma")]
+        if nl.size != S + 1 or any(a.size != S for a in arrs):
+            raise ValueError("sampler tables: noise_level needs S+1 entries, the coefficients S")
+        _lib.check(self.lib.sr3_set_sampler_schedule(self.ctx, S, nl.ctypes.data, *[a.ctypes.data for a in arrs],
+                                                     1 if tables["uses_history"] else 0))
+        self.T = S
+
     def num_frames(self) -> int:
         n = self.lib.sr3_num_frames(self.ctx)
         if n < 0:

@@ -126,6 +126,19 @@ int sr3_set_schedule(sr3_ctx *ctx, int T, const float *noise_level, const float 
                      const float *recipm1, const float *logvar, const float *coef1,
                      const float *coef2);
 
+/* A few-step sampler over the same noise schedule (DDIM, DPM-Solver++(2M)), replacing the one
+ * sr3_set_schedule set. S steps; step i (S-1 down to 0, like the reference's t) runs the UNet at noise_level[i+1] and
+ * updates x0 = clamp(a[i] x - b[i] eps, -1, 1), x' = c1[i] x0 + c2[i] x + c3[i] x0_prev + sigma[i] z, where x0_prev is
+ * the clamped x0 of the previous step (used only with uses_history != 0; the first step after sr3_sample_begin, whatever
+ * its t, stores its x0 without reading one. The library keeps it next to the sampler state and in the checkpoints of
+ * sr3_sample). sigma is the standard deviation
+ * itself (not a log-variance). Afterwards S is the step count of sr3_sample, sr3_sample_step (t in [0, S)),
+ * sr3_num_frames and of the injected noise ([S, B, C, H, W]). sr3_set_schedule returns to the reference's DDPM loop
+ * (c3 = 0, no history). */
+int sr3_set_sampler_schedule(sr3_ctx *ctx, int S, const float *noise_level, const float *a, const float *b,
+                             const float *c1, const float *c2, const float *c3, const float *sigma,
+                             int uses_history);
+
 /* replaces: p_sample_loop (diffusion.py:189-215) for a whole batch.
  *   cond_dev   [B,3,H,W] conditioning image (x_in) or NULL for the unconditional branch (:193-201)
  *   noise_dev  NULL -> device Philox4x32-10 + Box-Muller keyed by (seed, image index+image_offset,
