@@ -123,6 +123,15 @@ __device__ __forceinline__ ConvParams phase_params(const ConvParams &in, int ph)
     return p;
 }
 
+// kernel-side view of GEMM batch z (ZB instantiations: the position GEMMs of a Winograd conv, ConvParams::zbatch)
+__device__ __forceinline__ ConvParams batch_params(const ConvParams &in, int z) {
+    ConvParams p = in;
+    p.in0.p = in.in0.p + (size_t)z * in.batch_in_stride;
+    p.w = in.w + (size_t)z * in.phase_w_stride;
+    p.out.p = in.out.p + (size_t)z * in.batch_out_stride;
+    return p;
+}
+
 // residual element o (= pixel * C + channel) of a tensor stored in the split-f16 format: hi + lo
 __device__ __forceinline__ float load_split(const float *base, unsigned o) {
     const _Float16 *hp = reinterpret_cast<const _Float16 *>(base + (o & ~31u)) + (o & 31u);
@@ -677,9 +686,9 @@ __device__ __forceinline__ void gnf_producer_tail(const ConvParams &p, float *sm
 // PREC 0: exact f32 (v_mfma_f32_32x32x2_f32); PREC 1: split-f16, 3 x v_mfma_f32_32x32x16_f16
 // NS: LDS pipeline stages (power of two or 3); the DMA of tile k+NS-1 is issued while tile k is
 // multiplied, so NS-2 tiles stay in flight across a barrier (counted vmcnt + raw s_barrier)
-template <int BM, int BN, int WGM, int WGN, int KS, int PREC, int NS>
+template <int BM, int BN, int WGM, int WGN, int KS, int PREC, int NS, bool ZB = false>
 __global__ __launch_bounds__(512, (((BM + BN) * ROWF * 4 * NS + 8 * BM) * 3 <= 160 * 1024 ? 6 : 4)) void conv_igemm_dma_f32(const ConvParams p_in) {
-    const ConvParams p = phase_params(p_in, blockIdx.z);
+    const ConvParams p = ZB ? batch_params(p_in, blockIdx.z) : phase_params(p_in, blockIdx.z);
     static_assert(WGM * WGN == 4, "4 consumer waves per block");
     constexpr bool DMA_BUF = !(BM == 64 && BN == 64);   // (see dma16s)
     constexpr int WM = BM / WGM, WN = BN / WGN;
@@ -2267,11 +2276,11 @@ static bool halo_ok(const ConvParams &p, int BM, int segmin, int bn, bool split_
     return (M % BM) == 0 && (p.out.C % bn) == 0 && (!p.in2.p || (p.in2.C % 32) == 0) && (!p.in2b.p || (p.in2b.C % 32) == 0);
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, int PREC, int NS>
+template <int BM, int BN, int WGM, int WGN, int KS, int PREC, int NS, bool ZB = false>
 void launch_inst2(const ConvParams &p, hipStream_t s) {
     static bool attr_set = false;
     constexpr size_t lds = ((size_t)NS * (BM + BN) * ROWF + 2 * BM) * sizeof(float);
-    auto kern = conv_igemm_dma_f32<BM, BN, WGM, WGN, KS, PREC, NS>;
+    auto kern = conv_igemm_dma_f32<BM, BN, WGM, WGN, KS, PREC, NS, ZB>;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2279,7 +2288,7 @@ void launch_inst2(const ConvParams &p, hipStream_t s) {
     }
     const int M = p.B * p.Hout * p.Wout;
     const int tilesM = (M + BM - 1) / BM, tilesN = (p.out.C + BN - 1) / BN;
-    hipLaunchKernelGGL(kern, dim3(tilesM * tilesN, p.splits > 1 ? p.splits : 1, p.phases), dim3(512), lds, s, p);
+    hipLaunchKernelGGL(kern, dim3(tilesM * tilesN, p.splits > 1 ? p.splits : 1, ZB ? p.zbatch : p.phases), dim3(512), lds, s, p);
 }
 
 template <int BM, int BN, int WGM, int WGN, int KS, int PREC>
@@ -2531,8 +2540,25 @@ bool conv_gnf_supported(const ConvParams &p, int groups) { return gnf_kernel_cho
 static thread_local const char *g_conv_error = nullptr;
 const char *conv_take_error() { const char *e = g_conv_error; g_conv_error = nullptr; return e; }
 
+void launch_wino_gemm(const ConvParams &p_in, hipStream_t s) {
+    ConvParams p = p_in;
+    const long M = (long)p.B * p.Hout * p.Wout;
+    auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
+    p.hw_shift = lg(p.Hout * p.Wout);
+    p.w_shift = lg(p.Wout);
+    p.splits = 1; p.part = nullptr; p.tile_cnt = nullptr; p.stats = nullptr; p.phases = 1;
+    // the zbatch GEMMs fill the chip together: the tile is chosen for their combined rows
+    switch (conv_tile_choice(M * p.zbatch, p.out.C)) {
+    case 0: launch_inst2<128, 32, 4, 1, 1, 0, 2, true>(p, s); break;
+    case 1: launch_inst2<128, 64, 2, 2, 1, 0, 2, true>(p, s); break;
+    case 2: launch_inst2<64, 64, 2, 2, 1, 0, 4, true>(p, s); break;
+    default: launch_inst2<128, 128, 2, 2, 1, 0, 2, true>(p, s); break;
+    }
+}
+
 void launch_conv(const ConvParams &p_in, hipStream_t s) {
     if (p_in.up2) { launch_conv_up2(p_in, s); return; }     // weights must be in phase form (make_up2_phase_weights)
+    if (conv_wino_taken(p_in)) { launch_conv_wino(p_in, s); return; }
     ConvParams p = p_in;
     p.dbg = exp_int("SR3_CONV_DBG", 0);
     const long M = (long)p.B * p.Hout * p.Wout;

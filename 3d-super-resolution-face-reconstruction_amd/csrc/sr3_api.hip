@@ -52,6 +52,7 @@ struct Param {
     float *dev = nullptr;                        // device storage (kernel layout)
     float *dev_split = nullptr;                  // P_CONV: split-f16 copy (prec 1), same size
     float *dev_f8 = nullptr;                     // P_CONV 3x3: F8C copy of dev_split ("f16f8" mode; made on demand)
+    float *dev_wino = nullptr;                   // P_CONV 3x3 (wino_weights): G g G^T [16][cout][cin_pad] for prec 0
     float w_unscale = 1.0f;
     bool keep_host = false;                      // part of a fused (conv2 + res_conv) launch
     bool up_phase = false;                       // Upsample conv: stored as 4 sub-pixel phases x 2x2 taps
@@ -170,6 +171,7 @@ struct sr3_ctx {
     TDesc final_act;            // activated input of final_conv
     float *qkvb = nullptr, *aob = nullptr, *vtb = nullptr;   // attention: qkv, core output, v^T scratch (split-f16 core)
     float *part = nullptr;      // split-K partial sums (small-M convs)
+    float *wino_ws = nullptr;   // transformed input and products of the Winograd convs (conv_wino_ws_floats)
     float *gscale = nullptr, *gshift = nullptr, *gpart = nullptr;
     float *temb = nullptr, *cbias = nullptr;
     int cb_stride = 0;          // row stride of cbias: nf_total, or 0 when one noise level serves the whole batch (sampler steps)
@@ -382,6 +384,11 @@ int build_graph(sr3_ctx *c) {
     return 0;
 }
 
+// 3x3 conv weights that may run in Winograd form (conv_wino_supported: the batch and resolution decide per launch)
+bool wino_weights(const Param &p) {
+    return p.kind == P_CONV && p.ks == 3 && !p.up_phase && p.cin_pad >= WINO_MIN_CIN && (p.cin_pad % 32) == 0 && (p.cout % 64) == 0;
+}
+
 int alloc_weights(sr3_ctx *c) {
     const int inner = c->cfg.inner_channel;
     HIP_OK(hipMalloc(&c->nfw, (size_t)c->nf_total * inner * sizeof(float)));
@@ -422,6 +429,10 @@ int alloc_weights(sr3_ctx *c) {
         if (p.kind == P_CONV) {
             HIP_OK(hipMalloc(&p.dev_split, n * sizeof(float)));
             c->weight_bytes += n * sizeof(float);
+        }
+        if (wino_weights(p)) {
+            HIP_OK(hipMalloc(&p.dev_wino, (size_t)16 * p.cout * p.cin_pad * sizeof(float)));
+            c->weight_bytes += (size_t)16 * p.cout * p.cin_pad * sizeof(float);
         }
     }
     return 0;
@@ -504,7 +515,7 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
         twin[i] = skip || (nx && (nx->kind == M_DOWN || nx->kind == M_UP || (nx->kind == M_RES && nx->rb.has_res)));
     }
     std::vector<int> s_slices(nm, 0), s_out(nm, 0), s_h1(nm, 0);
-    uint64_t max_qkv = 0, max_ao = 0, max_part = 0, max_vt = 0;
+    uint64_t max_qkv = 0, max_ao = 0, max_part = 0, max_vt = 0, max_wino = 0;
     int h = H, w = W;
     int cur_c = c->in_pad;
     std::vector<int> feat_c;
@@ -546,6 +557,9 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
             };
             if (m.kind == M_RES) {
                 want(oc, m.rb.cin); want(oc, oc);
+                for (const ConvRef *cr : {&m.rb.c1, &m.rb.c2})      // Winograd workspace of the block's 3x3 convs
+                    if (wino_weights(c->params[cr->w]) && conv_wino_supported(B, h, w, cr->cin_pad, cr->cout))
+                        max_wino = std::max<uint64_t>(max_wino, conv_wino_ws_floats(B, h, w, cr->cin_pad, cr->cout));
                 if (m.rb.attn) { want(3 * oc, oc); want(oc, oc); }
             } else if (m.kind == M_UP) {
                 const long Ml = Mo / 4;                       // each sub-pixel phase is a conv over the low-res pixels
@@ -599,6 +613,7 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     const uint64_t o_x0p = ci_ok ? cv.take((uint64_t)B * (H + 2) * (W + 2) * 8 + 16) : 0;   // + slack: the last A fragment reads one pixel on
     const uint64_t o_qkv = cv.take(max_qkv), o_ao = cv.take(max_ao), o_vt = cv.take(max_vt);
     const uint64_t o_part = cv.take(max_part);
+    const uint64_t o_wino = cv.take(max_wino);
     const uint64_t o_gs = cv.take((uint64_t)B * c->c_max), o_gh = cv.take((uint64_t)B * c->c_max);
     const uint64_t o_gab = cv.take((uint64_t)B * c->c_max * 2);
     const uint64_t o_gp = cv.take(gn_workspace_floats(B, c->c_max));
@@ -652,6 +667,7 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     c->final_act = desc(o_fa, c->final_gn.C, H, W, 1);
     c->qkvb = at(o_qkv); c->aob = at(o_ao); c->vtb = at(o_vt);
     c->part = max_part ? at(o_part) : nullptr;
+    c->wino_ws = max_wino ? at(o_wino) : nullptr;
     c->gscale = at(o_gs); c->gshift = at(o_gh); c->gpart = at(o_gp);
     c->gnf_ab = at(o_gab);
     c->temb = at(o_te); c->cbias = at(o_cb);
@@ -714,6 +730,7 @@ void run_conv(sr3_ctx *c, const TDesc &a, const TDesc &b, const ConvRef &cv, int
     p.ks = cv.ks; p.stride = stride; p.up2 = up2;
     p.prec = activated ? c->prec : 0;
     p.w = p.prec ? c->params[cv.w].dev_split : c->params[cv.w].dev;
+    if (!p.prec && cv.cin_pad == a.C + (b.p ? b.C : 0)) { p.w_wino = c->params[cv.w].dev_wino; p.wino_ws = c->wino_ws; }
     if (f8 && p.prec) { p.f8 = 1; p.w = c->params[cv.w].dev_f8; }
     p.w_unscale = c->params[cv.w].w_unscale;
     p.bias = bias_override ? bias_override : (cv.b >= 0 ? c->params[cv.b].dev : nullptr);
@@ -1267,6 +1284,7 @@ void sr3_destroy(sr3_ctx *c) {
         if (p.owns && p.dev) (void)hipFree(p.dev);
         if (p.dev_split) (void)hipFree(p.dev_split);
         if (p.dev_f8) (void)hipFree(p.dev_f8);
+        if (p.dev_wino) (void)hipFree(p.dev_wino);
     }
     if (c->final_wq) (void)hipFree(c->final_wq);
     if (c->ci_w) (void)hipFree(c->ci_w);
@@ -1387,6 +1405,11 @@ int sr3_load_weight(sr3_ctx *c, const char *name, const float *host, const int64
                 rows = (size_t)16 * p.cout;
             }
             HIP_OK(hipMemcpy(p.dev, packed.data(), p.dev_floats * sizeof(float), hipMemcpyHostToDevice));
+            if (p.dev_wino) {
+                std::vector<float> wv((size_t)16 * p.cout * p.cin_pad);
+                make_wino_weights(packed.data(), p.cout, p.cin_pad, wv.data());
+                HIP_OK(hipMemcpy(p.dev_wino, wv.data(), wv.size() * sizeof(float), hipMemcpyHostToDevice));
+            }
             if (p.keep_host) p.host = packed;
             std::vector<float> sp(p.dev_floats);
             p.w_unscale = split_conv_weight(packed.data(), rows, p.cin_pad, sp.data());
@@ -1771,6 +1794,15 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
         packed.swap(ph);
         rows = (size_t)16 * Cout;
     }
+    // Winograd form where the engine would take it for this shape (launch_conv decides per launch)
+    float *dww = nullptr, *dws = nullptr;
+    if (!c->prec && ks == 3 && stride == 1 && !up2 && Cin >= WINO_MIN_CIN && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
+        std::vector<float> wv((size_t)16 * Cout * Cin);
+        make_wino_weights(packed.data(), Cout, Cin, wv.data());
+        HIP_OK(hipMalloc(&dww, wv.size() * sizeof(float)));
+        HIP_OK(hipMemcpy(dww, wv.data(), wv.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_OK(hipMalloc(&dws, conv_wino_ws_floats(B, Hin, Win, Cin, Cout) * sizeof(float)));
+    }
     if (c->prec) {
         std::vector<float> sp(packed.size());
         w_unscale = split_conv_weight(packed.data(), rows, Cin, sp.data());
@@ -1816,6 +1848,7 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     p.in_fm = ws ? 1 : 0;
     if (ws) p.tile_cnt = c->tile_cnt;       // (the experiment's tile counters)
     p.w = dw; p.bias = db; p.chan_bias = chan_bias_dev; p.chan_bias_stride = Cout;
+    p.w_wino = dww; p.wino_ws = dws;
     p.out = unpadded(out_dev, Cout, p.Hout, p.Wout);
     p.ovf = c->d_ovf;            // (range bits of twin stores and the 'wait gave up' bit of the in-place split-K)
     if (resid_dev) p.resid = unpadded(const_cast<float *>(resid_dev), Cout, p.Hout, p.Wout);
@@ -1852,6 +1885,8 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     HIP_OK(hipFree(act));
     if (db) HIP_OK(hipFree(db));
     if (part) HIP_OK(hipFree(part));
+    if (dww) HIP_OK(hipFree(dww));
+    if (dws) HIP_OK(hipFree(dws));
     if (rc) return rc;
     return replayed ? warn_replay(c, "sr3_op_conv2d", "the conv") : 0;
 }
@@ -1900,6 +1935,13 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     if (with_resid) p.resid = res;
     p.out = out;
     p.ovf = c->d_ovf;
+    float *wino_w = nullptr, *wino_ws = nullptr;      // Winograd form where the engine would take it (random weights)
+    if (!c->prec && ks == 3 && stride == 1 && !up2 && Cin >= WINO_MIN_CIN && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
+        HIP_OK(hipMalloc(&wino_w, (size_t)16 * Cout * Cin * 4));
+        HIP_OK(hipMalloc(&wino_ws, conv_wino_ws_floats(B, Hin, Win, Cin, Cout) * 4));
+        rnd(wino_w, (size_t)16 * Cout * Cin, 10);
+        p.w_wino = wino_w; p.wino_ws = wino_ws;
+    }
     // split-K exactly as the engine would choose it for this problem (partials on a scratch buffer)
     float *part = nullptr;
     {
@@ -1928,7 +1970,7 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     HIP_OK(hipEventElapsedTime(&ms, e1, e2));
     if (apply_ms) *apply_ms = ms / iters;
     HIP_OK(hipEventDestroy(e0)); HIP_OK(hipEventDestroy(e1)); HIP_OK(hipEventDestroy(e2));
-    for (float *q : {i0.p, i1.p, act.p, out.p, res.p, w, bias, sc, sh, cb, part})
+    for (float *q : {i0.p, i1.p, act.p, out.p, res.p, w, bias, sc, sh, cb, part, wino_w, wino_ws})
         if (q) HIP_OK(hipFree(q));
     HIP_OK(hipGetLastError());
     return 0;

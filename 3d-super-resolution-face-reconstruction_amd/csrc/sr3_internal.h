@@ -13,6 +13,7 @@ namespace sr3 {
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
 //   SR3_HALO_SPLITS=0|2|4   in-place split-K of deep-K convs on 128x128 x-halo tiles: off / forced
 //   SR3_NO_INPLACE_SPLIT=1  split-K always as conv + reduce kernel
+//   SR3_NO_WINOGRAD=1       exact-f32 3x3 convs always on the direct implicit-GEMM kernel (conv_wino_supported)
 // Everything else is an A/B switch of the development build (-DSR3_EXPERIMENTS, build.py --experiments): the product
 // library does not read those variables at all, so a stray one cannot change kernels or numerics.
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
@@ -134,6 +135,15 @@ struct ConvParams {
     float *gnf_ab = nullptr;           // [B][Cout][2] scale | shift
     int gnf_band = 0;                  // > 0: M-tiles of an image per XCD (band block order, set by launch_conv)
     int dbg = 0;            // timing experiments only (tools/conv_bench.py); 0 in product code
+    // Winograd F(2x2, 3x3) form of this conv (prec 0 only; launch_conv takes it where conv_wino_supported says so and
+    // the conv uses nothing the Winograd path does not handle): transformed weights [16][Cout][CinPad]
+    // (make_wino_weights) and a workspace of conv_wino_ws_floats() floats; either null: direct kernel
+    const float *w_wino = nullptr;
+    float *wino_ws = nullptr;
+    // GEMM batch (launch_wino_gemm only): blockIdx.z = z multiplies in0.p + z * batch_in_stride by
+    // w + z * phase_w_stride into out.p + z * batch_out_stride
+    int zbatch = 1;
+    size_t batch_in_stride = 0, batch_out_stride = 0;
 };
 // bit raised in *ConvParams::ovf when a bounded inter-block wait gives up (in-place split-K of the x-halo kernel; the
 // producer-side GroupNorm experiment): the launch's result is invalid; the API replays the work with
@@ -203,6 +213,23 @@ void launch_conv_ws(const ConvParams &p, hipStream_t s);
 void launch_conv_up2(const ConvParams &p, hipStream_t s);
 // packed [9][Cout][CinPad] -> [py*2+px][dy2*2+dx2][Cout][CinPad]
 void make_up2_phase_weights(const float *packed9, int Cout, int CinPad, float *dst);
+// ---- Winograd F(2x2, 3x3) for the exact-f32 3x3 convs of the deep levels (kernels_wino.hip) ----------------------
+// Y = A^T [ (G g G^T) . (B^T d B) ] A per 2x2 output tile: the 16 positions of the transformed 4x4 window are 16
+// independent GEMMs [B*H/2*W/2][Cin] x [Cin][Cout] on the f32 implicit-GEMM kernel (4 instead of 9 MACs per output
+// pixel and channel pair); the input transform and the output transform (+ bias, FeatureWiseAffine bias, residual,
+// fused 1x1 term, fused GroupNorm statistics) are separate passes.
+constexpr int WINO_MIN_CIN = 128;      // narrower inputs: the transforms' memory passes cost more than the MACs saved
+constexpr int WINO_MIN_TILES = 1024;   // fewer 2x2 output tiles per launch (B * H/2 * W/2): the direct kernel (latency)
+// shape rule of the dispatch (3x3 / stride 1 / prec 0 convs): false also under SR3_NO_WINOGRAD=1
+bool conv_wino_supported(int B, int H, int W, int Cin, int Cout);
+size_t conv_wino_ws_floats(int B, int H, int W, int Cin, int Cout);     // U [16][B*H*W/4][Cin] + M [16][B*H*W/4][Cout]
+// host helper: packed [9][Cout][CinPad] -> G g G^T as [16][Cout][CinPad] (fp64, rounded once to fp32)
+void make_wino_weights(const float *packed9, int Cout, int CinPad, float *dst);
+// true when launch_conv runs this conv in Winograd form (p.w_wino / p.wino_ws set, as launch_conv would see it)
+bool conv_wino_taken(const ConvParams &p);
+void launch_conv_wino(const ConvParams &p, hipStream_t s);
+// the 16 position GEMMs of one Winograd conv on conv_igemm_dma_f32 (kernels_conv.hip); p as described at zbatch
+void launch_wino_gemm(const ConvParams &p, hipStream_t s);
 // BM of the tile launch_conv will use for this problem (so callers can size / enable fused stats)
 int conv_tile_m(long M, int Cout);
 // number of K-splits launch_conv wants for this problem (1 = none); Cin per tap, multiple of 32

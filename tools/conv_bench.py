@@ -25,6 +25,8 @@ MAIN = [
     (64, 64, 64, 128, 0, 128, 3, 1, 1, 0, 0, 0),
     (64, 128, 128, 64, 0, 3, 3, 1, 0, 2, 0, 0),
     (64, 128, 128, 32, 0, 64, 3, 1, 0, 0, 0, 0),
+    (64, 16, 16, 1024, 0, 512, 3, 1, 0, 0, 0, 0),
+    (64, 32, 32, 768, 0, 256, 3, 1, 0, 0, 0, 0),
 ]
 
 if __name__ == "__main__":
