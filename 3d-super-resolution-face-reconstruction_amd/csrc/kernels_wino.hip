@@ -7,7 +7,7 @@
 //         | 0 -1  1  0 |         | 1/2 -1/2  1/2|
 //         | 0  1  0 -1 |         | 0    0    1  |
 //
-// Three passes per conv, all on one stream:
+// At <= 32x32 pixels, three passes per conv, all on one stream (64x64 and up: wino_fused_kernel, one pass):
 //   1. wino_input_kernel: U[pos][tile][Cin] = (B^T d B)[pos] over the zero-bordered input (window origins (2ty, 2tx)
 //      in padded coordinates, so the borders are already zero and nothing is masked); in0 || in1 concatenated here.
 //   2. launch_wino_gemm: M[pos] = U[pos] x V[pos] for the 16 positions, on the f32 implicit-GEMM kernel
@@ -18,10 +18,12 @@
 // first (with the conv's residual); the output transform then adds it as the residual.
 // The operands and the accumulation stay fp32; the data transforms use only +-1, the weight transform (1/2) runs in fp64.
 #include "sr3_internal.h"
+#include <type_traits>
 
 namespace sr3 {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -127,6 +129,245 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const ConvParams p, co
     }
 }
 
+// ---- one-pass form for the 64x64- and 128x128-pixel levels ----------------------------------------------------------
+// Block = one strip of WF_T = 32 tiles along a tile row x WF_BN = 64 output channels; wave a (0..3) owns row a of the
+// 4x4 positions (4a + b, b = 0..3), so U and M never leave the CU:
+//   * the strip's 4 x 66 padded input pixels x 32 channels are staged per K-step by LDS-DMA (two stages, 16-B chunk c
+//     of pixel column x at c ^ ((x >> 1) & 7));
+//   * lane (li, h) of wave a reads the two window rows that (B^T d)[a] needs for tile li and 4 channels (same +-1 adds as
+//     wino_input_kernel) and forms U[4a + b] for b = 0..3: exactly its A operands of v_mfma_f32_32x32x2_f32
+//     (lane half h, element j -> channel 8kk + 4h + j, as in conv_igemm_dma_f32);
+//   * the B operand comes straight from the transformed weights [16][Cout][CinPad] (one 16-B load per lane, L2-resident):
+//     the four waves multiply DIFFERENT positions, so a B tile staged in LDS would be read by one wave only, and the
+//     16 positions x 64 channels x 32 input channels of one K-step (128 KiB) do not fit next to the input stages;
+//   * epilogue: each wave folds its row over the columns of A (t_c = M[a] A[:, c]) in registers, the four rows meet in
+//     LDS, y = A^T t, then the direct kernel's epilogue order (bias, residual, FeatureWiseAffine bias), the store and the
+//     fused GroupNorm statistics (per tile in LDS, then per slice in tile order; spb slices per strip).
+// Registers: 4 positions x 2 N-fragments x 16 accumulators = 128, plus two sets of B fragments (64): 2 waves per SIMD.
+// A 64-tile or 128-channel block doubles the accumulators (256: 1 wave per SIMD, nothing left for operands).
+// One input tensor only (conv_wino_taken): the engine writes x || skip as one tensor in the GroupNorm apply pass.
+constexpr int WF_T = 32;                    // 2x2 output tiles per block (one strip of a tile row)
+constexpr int WF_BN = 64;                   // output channels per block
+constexpr int WF_WX = 2 * WF_T + 2;         // padded input columns of a strip's windows
+constexpr int WF_ROWS = 4 * WF_WX;          // pixel rows of 32 floats per LDS stage
+constexpr int WF_STAGE = WF_ROWS * 32;      // floats per stage
+constexpr int WF_DMA = WF_ROWS / 8;         // LDS-DMA instructions per stage (64 lanes x 16 B each)
+constexpr int WF_DMA_PER_WAVE = (WF_DMA + 3) / 4;
+static_assert(WF_ROWS % 8 == 0, "whole DMA instructions per stage");
+constexpr size_t WF_LDS = (size_t)2 * WF_STAGE * sizeof(float);
+static_assert(WF_LDS >= (size_t)4 * 2 * WF_T * WF_BN * sizeof(float), "epilogue exchange fits in the stages");
+
+template <int N, class F>
+__device__ __forceinline__ void wf_static_for(F &&f) {
+    if constexpr (N > 0) {
+        wf_static_for<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+
+// 64 lanes x 16 B from a wave-uniform base + per-lane byte offset into LDS at lds (wave-uniform) + lane * 16
+__device__ __forceinline__ void wf_dma16(const char *sbase, unsigned voff, float *lds) {
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(sbase), 0, -1, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)lds, 16, (int)voff, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, int spb) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int Cin = p.in0.C;                             // (one input tensor: conv_wino_taken)
+    const int Cout = p.out.C, th = p.Hout >> 1, tw = p.Wout >> 1;
+    const int spr = tw / WF_T, spi = th * spr;           // strips per tile row / per image
+    const int nbl = Cout / WF_BN;
+    int bid = blockIdx.x;
+    {   // XCD-aware remap (as conv_igemm_dma_f32): the channel blocks of one strip share an L2
+        const int nwg = gridDim.x;
+        const int xcd = bid & 7, loc = bid >> 3;
+        const int qq = nwg >> 3, rr = nwg & 7;
+        bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + loc;
+    }
+    const int nb = bid % nbl, strip = bid / nbl;
+    const int n = strip / spi, si = strip - n * spi;
+    const int ty = si / spr, tx0 = (si - ty * spr) * WF_T;
+    const int n0 = nb * WF_BN;
+    const int a = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const int Wp = p.in0.Wp();
+    const size_t pix0 = ((size_t)n * p.in0.Hp() + 2 * ty) * Wp + 2 * tx0;     // window origin of the strip
+    const char *src0 = reinterpret_cast<const char *>(p.in0.p + pix0 * Cin);
+
+    // LDS-DMA: wave a issues instructions i = a + 4m; lane -> pixel row 8i + (lane >> 3) (window row r, column x),
+    // stored chunk lane & 7 (offsets recomputed per K-step: a few VALU operations, no registers held across the loop)
+    auto issue = [&](int c0, int stage) {
+        const char *sb = src0 + (size_t)c0 * 4;
+        const unsigned cs4 = (unsigned)Cin * 4u;
+        float *dst = smem + stage * WF_STAGE;
+        wf_static_for<WF_DMA_PER_WAVE>([&](auto mc) {
+            constexpr int m = decltype(mc)::value;
+            if (a + 4 * m < WF_DMA) {
+                int q = 8 * (a + 4 * m) + (lane >> 3);
+                asm volatile("" : "+v"(q));      // (kept in the loop: hoisted, the per-instruction offsets would be held in registers)
+                const int r = q / WF_WX, x = q - r * WF_WX;
+                const unsigned voff = (unsigned)(r * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16);
+                wf_dma16(sb, voff, dst + (a + 4 * m) * 256);
+            }
+        });
+    };
+
+    // B fragments: lane (li, h) loads channels c0 + 8kk + 4h .. +3 of output channel n0 + 32ni + li, position 4a + b
+    // (buffer loads: a wave-uniform descriptor over the wave's 4 position planes, the uniform part of the offset in
+    // soffset, the lane part in one VGPR — no 64-bit address arithmetic per load)
+    const unsigned wlane = ((unsigned)(n0 + li) * (unsigned)Cin + 4u * h) * 4u;
+    const size_t plane = (size_t)Cout * Cin;
+    const __amdgpu_buffer_rsrc_t wrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w_wino + (size_t)(4 * a) * plane), 0, -1, 0x00020000);
+    auto loadB = [&](f32x4 (&bf)[4][2], int c0, int kk) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                const int soff = (int)(((size_t)b * plane + (size_t)ni * 32 * Cin + c0 + 8 * kk) * 4);
+                bf[b][ni] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (int)wlane, soff, 0));
+            }
+    };
+
+    // rows of the 4x4 window that (B^T d)[a] combines: e = d[ra] + sg * d[rb]
+    const int ra = a == 0 ? 0 : (a == 2 ? 2 : 1);
+    const int rb = a == 0 ? 2 : (a == 1 ? 2 : (a == 2 ? 1 : 3));
+    const float sg = a == 1 ? 1.f : -1.f;
+    int aoff[2][4];          // float offsets of the lane's window pixels (rows ra, rb; columns 0..3) in a stage
+    int asw[4];              // swizzle of those columns
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+        aoff[0][x] = (ra * WF_WX + 2 * li + x) * 32;
+        aoff[1][x] = (rb * WF_WX + 2 * li + x) * 32;
+        asw[x] = (li + (x >> 1)) & 7;
+    }
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[b][ni][r] = 0.f;
+
+    const int nk = Cin / 32;
+    f32x4 bf[2][4][2];
+    issue(0, 0);
+    loadB(bf[0], 0, 0);
+    __syncthreads();                          // (waits for this wave's DMA; the barrier publishes everybody's)
+    for (int kt = 0; kt < nk; ++kt) {
+        const int c0 = kt * 32;
+        if (kt + 1 < nk) issue(c0 + 32, (kt + 1) & 1);   // stage free since the barrier that ended step kt - 1
+        const float *st = smem + (kt & 1) * WF_STAGE;
+        wf_static_for<4>([&](auto kc) {
+            constexpr int kk = decltype(kc)::value;
+            if constexpr (kk < 3) loadB(bf[(kk + 1) & 1], c0, kk + 1);
+            else if (kt + 1 < nk) loadB(bf[0], c0 + 32, 0);
+            const int ch = 2 * kk + h;
+            f32x4 e[4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                const f32x4 d0 = *reinterpret_cast<const f32x4 *>(st + aoff[0][x] + ((ch ^ asw[x]) << 2));
+                const f32x4 d1 = *reinterpret_cast<const f32x4 *>(st + aoff[1][x] + ((ch ^ asw[x]) << 2));
+                e[x] = d0 + sg * d1;
+            }
+            f32x4 u[4];
+            u[0] = e[0] - e[2];
+            u[1] = e[1] + e[2];
+            u[2] = e[2] - e[1];
+            u[3] = e[1] - e[3];
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int ni = 0; ni < 2; ++ni)
+                        acc[b][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[b][j], bf[kk & 1][b][ni][j], acc[b][ni], 0, 0, 0);
+        });
+        __syncthreads();                      // DMA of step kt + 1 landed; every read of stage kt & 1 done
+    }
+
+    // epilogue operands from memory first: their latency overlaps the exchange of the rows through LDS
+    const int q = threadIdx.x & 15, c = n0 + q * 4;
+    f32x4 bias = {0.f, 0.f, 0.f, 0.f}, cb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (p.bias) bias[j] = p.bias[c + j];
+        if (p.chan_bias) cb[j] = p.chan_bias[(size_t)n * p.chan_bias_stride + c + j];
+    }
+    f32x4 rv[2][2][2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) {
+                const int tl = (threadIdx.x >> 4) + 16 * u;
+                rv[u][r][cc] = p.resid.p ? *reinterpret_cast<const f32x4 *>(p.resid.p + p.resid.pix(n, 2 * ty + r, 2 * (tx0 + tl) + cc) * Cout + c)
+                                         : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+
+    // t[c] = M[a] A[:, c] per (tile, channel) into LDS: tb[a][c][tile][channel]
+    float *tb = smem;
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int tile = (r & 3) + 8 * (r >> 2) + 4 * h, col = ni * 32 + li;
+            const float m0 = acc[0][ni][r], m1 = acc[1][ni][r], m2 = acc[2][ni][r], m3 = acc[3][ni][r];
+            tb[((a * 2 + 0) * WF_T + tile) * WF_BN + col] = m0 + m1 + m2;
+            tb[((a * 2 + 1) * WF_T + tile) * WF_BN + col] = m1 - m2 - m3;
+        }
+    __syncthreads();
+
+    double s1[2][4], s2[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int tl = (threadIdx.x >> 4) + 16 * u;
+        f32x4 t[4][2];
+#pragma unroll
+        for (int aa = 0; aa < 4; ++aa)
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) t[aa][cc] = *reinterpret_cast<const f32x4 *>(tb + ((aa * 2 + cc) * WF_T + tl) * WF_BN + q * 4);
+        f32x4 y[2][2];
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            y[0][cc] = t[0][cc] + t[1][cc] + t[2][cc];
+            y[1][cc] = t[1][cc] - t[2][cc] - t[3][cc];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { s1[u][j] = 0.0; s2[u][j] = 0.0; }
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) {
+                const int oy = 2 * ty + r, ox = 2 * (tx0 + tl) + cc;
+                f32x4 add = bias;   // (the direct kernel's epilogue order: bias, residual, FeatureWiseAffine bias)
+                if (p.resid.p) add += rv[u][r][cc];
+                if (p.chan_bias) add += cb;
+                const f32x4 o = y[r][cc] + add;
+                *reinterpret_cast<f32x4 *>(p.out.p + p.out.pix(n, oy, ox) * Cout + c) = o;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { s1[u][j] += (double)o[j]; s2[u][j] = fma((double)o[j], (double)o[j], s2[u][j]); }
+            }
+    }
+    if (p.stats == nullptr) return;
+    __syncthreads();                          // every read of tb done: its space holds the per-tile sums
+    double2 *red = reinterpret_cast<double2 *>(smem);     // [tile][channel]
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) red[((threadIdx.x >> 4) + 16 * u) * WF_BN + q * 4 + j] = make_double2(s1[u][j], s2[u][j]);
+    __syncthreads();
+    if ((int)threadIdx.x < spb * WF_BN) {
+        const int sl = threadIdx.x / WF_BN, col = threadIdx.x % WF_BN, tps = WF_T / spb;
+        double sa = 0, sq = 0;
+        for (int k = 0; k < tps; ++k) { const double2 t2 = red[(sl * tps + k) * WF_BN + col]; sa += t2.x; sq += t2.y; }
+        double *o = p.stats + (((size_t)n * p.stats_slices + si * spb + sl) * Cout + n0 + col) * 2;
+        o[0] = sa; o[1] = sq;
+    }
+}
+
 int out_slices(const ConvParams &p) {
     const int tiles = (p.Hout >> 1) * (p.Wout >> 1);
     if (p.stats) return p.stats_slices;
@@ -135,9 +376,19 @@ int out_slices(const ConvParams &p) {
 
 } // namespace
 
+// one-pass kernel (wino_fused_kernel): 64x64 pixels and up, whole strips per tile row, whole channel blocks, and enough
+// blocks to fill the chip (fewer: the direct kernel, whose smaller tiles spread further)
+static bool wino_fused_shape(int B, int H, int W, int Cin, int Cout) {
+    if (H * W < 4096 || (H & 1) || (W % (2 * WF_T)) || Cin < WINO_FUSED_CIN || (Cin % 32) || (Cout % WF_BN)) return false;
+    const uint64_t blocks = (uint64_t)B * (H / 2) * (W / (2 * WF_T)) * (Cout / WF_BN);
+    return blocks >= WINO_FUSED_MIN_BLOCKS;
+}
+
 bool conv_wino_supported(int B, int H, int W, int Cin, int Cout) {
     static const bool off = env_int("SR3_NO_WINOGRAD", 0) != 0;    // product switch (read once)
-    if (off || B <= 0 || (H & 1) || (W & 1) || H * W > 1024 || Cin < WINO_MIN_CIN || (Cin % 32) || (Cout % 64)) return false;
+    if (off || B <= 0) return false;
+    if (wino_fused_shape(B, H, W, Cin, Cout)) return true;
+    if ((H & 1) || (W & 1) || H * W > 1024 || Cin < WINO_MIN_CIN || (Cin % 32) || (Cout % 64)) return false;
     // few tiles (a single 128x128 image: 256 at its 32x32 level): the three dependent passes cost more latency than the
     // MACs they save (B = 1 step 1.99 -> 2.27 ms with every level in Winograd form); B = 64 at 8x8 is 1024 tiles and gains
     const uint64_t tiles = (uint64_t)B * (H / 2) * (W / 2);
@@ -147,17 +398,31 @@ bool conv_wino_supported(int B, int H, int W, int Cin, int Cout) {
 }
 
 size_t conv_wino_ws_floats(int B, int H, int W, int Cin, int Cout) {
+    if (wino_fused_shape(B, H, W, Cin, Cout)) return 0;           // U and M never leave the CU
     return (size_t)16 * B * (H / 2) * (W / 2) * (Cin + Cout);
 }
 
 bool conv_wino_taken(const ConvParams &p) {
-    if (!p.w_wino || !p.wino_ws || p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.in_fm || p.f8)
+    if (!p.w_wino || p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.in_fm || p.f8)
         return false;
     if (p.gnf_gamma || p.out_split.p || !p.out_f32 || p.resid_split) return false;
     if (p.in0.pad != 1 || p.in0.H != p.Hout || p.in0.W != p.Wout) return false;
     if (p.in1.p && (p.in1.pad != 1 || p.in1.H != p.Hout || p.in1.W != p.Wout)) return false;
     if (p.in2.p && !p.w2) return false;
-    if (!conv_wino_supported(p.B, p.Hout, p.Wout, p.in0.C + (p.in1.p ? p.in1.C : 0), p.out.C)) return false;
+    const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
+    if (!conv_wino_supported(p.B, p.Hout, p.Wout, Cin, p.out.C)) return false;
+    if (wino_fused_shape(p.B, p.Hout, p.Wout, Cin, p.out.C)) {
+        // one input tensor: the engine concatenates x || skip in the GroupNorm apply pass that writes the conv's input,
+        // so no caller hands these convs a second tensor (one that does gets the direct kernel)
+        if (p.in1.p) return false;
+        // the statistics slices must be whole strips or 2 | 4 equal parts of one
+        const int spi = (p.Hout / 2) * (p.Wout / (2 * WF_T));
+        if (p.stats == nullptr) return true;
+        if (p.stats_slices <= 0 || (p.stats_slices % spi)) return false;
+        const int spb = p.stats_slices / spi;
+        return spb == 1 || spb == 2 || spb == 4;
+    }
+    if (!p.wino_ws) return false;
     const int tiles = (p.Hout >> 1) * (p.Wout >> 1);
     return p.stats == nullptr || (p.stats_slices > 0 && (tiles % p.stats_slices) == 0);
 }
@@ -180,6 +445,34 @@ void make_wino_weights(const float *w9, int Cout, int CinPad, float *dst) {
 void launch_conv_wino(const ConvParams &p, hipStream_t s) {
     const int H = p.Hout, W = p.Wout, Cout = p.out.C;
     const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
+    ConvParams o = p;
+    if (p.in2.p) {
+        // fused 1x1 term: a 1x1 conv over in2 || in2b (+ the residual) into the output, added back as the residual
+        ConvParams r;
+        r.in0 = p.in2; r.in1 = p.in2b;
+        r.B = p.B; r.Hout = H; r.Wout = W;
+        r.ks = 1; r.prec = 0;
+        r.w = p.w2;
+        r.resid = p.resid;
+        r.out = p.out;
+        r.ovf = p.ovf;
+        launch_conv(r, s);
+        o.resid = p.out;
+    }
+    if (wino_fused_shape(p.B, H, W, Cin, Cout)) {
+        const int spi = (H / 2) * (W / (2 * WF_T));
+        const int spb = o.stats ? o.stats_slices / spi : 1;
+        const unsigned blocks = (unsigned)((size_t)p.B * spi * (Cout / WF_BN));
+        static bool attr_set = false;          // (more than 64 KiB of dynamic LDS)
+        if (!attr_set) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wino_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)WF_LDS);
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(wino_fused_kernel, dim3(blocks), dim3(256), WF_LDS, s, o, spb);
+        return;
+    }
+
     const size_t tiles = (size_t)p.B * (H / 2) * (W / 2);
     float *U = p.wino_ws, *Mw = p.wino_ws + 16 * tiles * Cin;
     const size_t items = tiles * (Cin / 4);
@@ -197,20 +490,6 @@ void launch_conv_wino(const ConvParams &p, hipStream_t s) {
     g.batch_out_stride = tiles * Cout;
     launch_wino_gemm(g, s);
 
-    ConvParams o = p;
-    if (p.in2.p) {
-        // fused 1x1 term: a 1x1 conv over in2 || in2b (+ the residual) into the output, added back as the residual
-        ConvParams r;
-        r.in0 = p.in2; r.in1 = p.in2b;
-        r.B = p.B; r.Hout = H; r.Wout = W;
-        r.ks = 1; r.prec = 0;
-        r.w = p.w2;
-        r.resid = p.resid;
-        r.out = p.out;
-        r.ovf = p.ovf;
-        launch_conv(r, s);
-        o.resid = p.out;
-    }
     const int sl = out_slices(o);
     hipLaunchKernelGGL(wino_output_kernel, dim3(Cout / 64, sl, p.B), dim3(256), 0, s, o, Mw, sl);
 }

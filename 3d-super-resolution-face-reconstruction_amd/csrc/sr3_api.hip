@@ -384,9 +384,12 @@ int build_graph(sr3_ctx *c) {
     return 0;
 }
 
-// 3x3 conv weights that may run in Winograd form (conv_wino_supported: the batch and resolution decide per launch)
+// 3x3 conv weights that may run in Winograd form (conv_wino_supported: the batch and resolution decide per launch).
+// The parameter does not know its level: a conv with 64 <= Cin < 128 gets the transformed copy (16/9 of its 3x3
+// weights) even where it only ever runs at 32x32 or below, where only Cin >= 128 is taken (none in the yml UNet).
 bool wino_weights(const Param &p) {
-    return p.kind == P_CONV && p.ks == 3 && !p.up_phase && p.cin_pad >= WINO_MIN_CIN && (p.cin_pad % 32) == 0 && (p.cout % 64) == 0;
+    return p.kind == P_CONV && p.ks == 3 && !p.up_phase && p.cin_pad >= std::min(WINO_MIN_CIN, WINO_FUSED_CIN) && (p.cin_pad % 32) == 0 &&
+           (p.cout % 64) == 0;
 }
 
 int alloc_weights(sr3_ctx *c) {
@@ -1796,12 +1799,12 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     }
     // Winograd form where the engine would take it for this shape (launch_conv decides per launch)
     float *dww = nullptr, *dws = nullptr;
-    if (!c->prec && ks == 3 && stride == 1 && !up2 && Cin >= WINO_MIN_CIN && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
+    if (!c->prec && ks == 3 && stride == 1 && !up2 && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
         std::vector<float> wv((size_t)16 * Cout * Cin);
         make_wino_weights(packed.data(), Cout, Cin, wv.data());
         HIP_OK(hipMalloc(&dww, wv.size() * sizeof(float)));
         HIP_OK(hipMemcpy(dww, wv.data(), wv.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_OK(hipMalloc(&dws, conv_wino_ws_floats(B, Hin, Win, Cin, Cout) * sizeof(float)));
+        if (const size_t wsf = conv_wino_ws_floats(B, Hin, Win, Cin, Cout)) HIP_OK(hipMalloc(&dws, wsf * sizeof(float)));
     }
     if (c->prec) {
         std::vector<float> sp(packed.size());
@@ -1936,9 +1939,9 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     p.out = out;
     p.ovf = c->d_ovf;
     float *wino_w = nullptr, *wino_ws = nullptr;      // Winograd form where the engine would take it (random weights)
-    if (!c->prec && ks == 3 && stride == 1 && !up2 && Cin >= WINO_MIN_CIN && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
+    if (!c->prec && ks == 3 && stride == 1 && !up2 && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
         HIP_OK(hipMalloc(&wino_w, (size_t)16 * Cout * Cin * 4));
-        HIP_OK(hipMalloc(&wino_ws, conv_wino_ws_floats(B, Hin, Win, Cin, Cout) * 4));
+        if (const size_t wsf = conv_wino_ws_floats(B, Hin, Win, Cin, Cout)) HIP_OK(hipMalloc(&wino_ws, wsf * 4));
         rnd(wino_w, (size_t)16 * Cout * Cin, 10);
         p.w_wino = wino_w; p.wino_ws = wino_ws;
     }

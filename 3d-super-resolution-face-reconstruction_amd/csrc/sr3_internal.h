@@ -220,9 +220,14 @@ void make_up2_phase_weights(const float *packed9, int Cout, int CinPad, float *d
 // fused 1x1 term, fused GroupNorm statistics) are separate passes.
 constexpr int WINO_MIN_CIN = 128;      // narrower inputs: the transforms' memory passes cost more than the MACs saved
 constexpr int WINO_MIN_TILES = 1024;   // fewer 2x2 output tiles per launch (B * H/2 * W/2): the direct kernel (latency)
+// 64x64 pixels and up: ONE kernel per conv (U and M stay on chip; kernels_wino.hip, wino_fused_kernel), taken from this
+// many blocks of 32 tiles x 64 output channels (4 per CU) — fewer: the direct kernel
+constexpr int WINO_FUSED_CIN = 64;
+constexpr int WINO_FUSED_MIN_BLOCKS = 1024;
 // shape rule of the dispatch (3x3 / stride 1 / prec 0 convs): false also under SR3_NO_WINOGRAD=1
 bool conv_wino_supported(int B, int H, int W, int Cin, int Cout);
-size_t conv_wino_ws_floats(int B, int H, int W, int Cin, int Cout);     // U [16][B*H*W/4][Cin] + M [16][B*H*W/4][Cout]
+// U [16][B*H*W/4][Cin] + M [16][B*H*W/4][Cout] for the three-pass form, 0 for the one-pass kernel
+size_t conv_wino_ws_floats(int B, int H, int W, int Cin, int Cout);
 // host helper: packed [9][Cout][CinPad] -> G g G^T as [16][Cout][CinPad] (fp64, rounded once to fp32)
 void make_wino_weights(const float *packed9, int Cout, int CinPad, float *dst);
 // true when launch_conv runs this conv in Winograd form (p.w_wino / p.wino_ws set, as launch_conv would see it)

@@ -27,6 +27,12 @@ MAIN = [
     (64, 128, 128, 32, 0, 64, 3, 1, 0, 0, 0, 0),
     (64, 16, 16, 1024, 0, 512, 3, 1, 0, 0, 0, 0),
     (64, 32, 32, 768, 0, 256, 3, 1, 0, 0, 0, 0),
+    # the remaining 3x3 stride-1 shapes of the 64x64 and 128x128 levels (Winograd one-pass kernel; x || skip inputs)
+    (64, 128, 128, 128, 0, 64, 3, 1, 0, 2, 0, 1),
+    (64, 64, 64, 64, 0, 128, 3, 1, 0, 2, 0, 1),
+    (64, 64, 64, 128, 64, 128, 3, 1, 0, 2, 0, 1),
+    (64, 64, 64, 128, 128, 128, 3, 1, 0, 2, 0, 1),
+    (64, 64, 64, 256, 128, 128, 3, 1, 0, 2, 0, 1),
 ]
 
 if __name__ == "__main__":
