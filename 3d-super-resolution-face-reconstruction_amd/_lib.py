@@ -88,6 +88,7 @@ PROTOTYPES = {
     "sr3_profile_get": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "sr3_profile_dump_csv": (_I, [_P, C.c_char_p]),
     "sr3_bench_conv": (_I, [_P] + [_I] * 13 + [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sr3_wino_weights_host": (_I, [_F, _I, _I, _I, _F]),
     "sr3_op_conv2d": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F]),
     "sr3_op_groupnorm_affine": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _F]),
     "sr3_op_attention": (_I, [_P, _F, _I, _I, _I, _F]),

@@ -137,7 +137,10 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const ConvParams p, co
 //   * lane (li, h) of wave a reads the two window rows that (B^T d)[a] needs for tile li and 4 channels (same +-1 adds as
 //     wino_input_kernel) and forms U[4a + b] for b = 0..3: exactly its A operands of v_mfma_f32_32x32x2_f32
 //     (lane half h, element j -> channel 8kk + 4h + j, as in conv_igemm_dma_f32);
-//   * the B operand comes straight from the transformed weights [16][Cout][CinPad] (one 16-B load per lane, L2-resident):
+//   * the B operand comes straight from the fragment-major copy of the transformed weights [16][CinPad/8][Cout][8]
+//     (make_wino_weights_frag; one 16-B load per lane, L2-resident): the 64 lanes of one load read 32 output channels
+//     x 8 input channels = 1 KiB of contiguous memory, whole 128-B lines (in the [16][Cout][CinPad] layout of the
+//     three-pass path the same load touches 32 rows of 32 B each, half of every L2 request);
 //     the four waves multiply DIFFERENT positions, so a B tile staged in LDS would be read by one wave only, and the
 //     16 positions x 64 channels x 32 input channels of one K-step (128 KiB) do not fit next to the input stages;
 //   * epilogue: each wave folds its row over the columns of A (t_c = M[a] A[:, c]) in registers, the four rows meet in
@@ -212,19 +215,20 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
         });
     };
 
-    // B fragments: lane (li, h) loads channels c0 + 8kk + 4h .. +3 of output channel n0 + 32ni + li, position 4a + b
+    // B fragments: lane (li, h) loads channels c0 + 8kk + 4h .. +3 of output channel n0 + 32ni + li, position 4a + b,
+    // from w_wino_f[4a + b][(c0 + 8kk) / 8][n0 + 32ni + li][4h .. 4h + 3]
     // (buffer loads: a wave-uniform descriptor over the wave's 4 position planes, the uniform part of the offset in
     // soffset, the lane part in one VGPR — no 64-bit address arithmetic per load)
-    const unsigned wlane = ((unsigned)(n0 + li) * (unsigned)Cin + 4u * h) * 4u;
+    const unsigned wlane = ((unsigned)(n0 + li) * 8u + 4u * h) * 4u;
     const size_t plane = (size_t)Cout * Cin;
     const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w_wino + (size_t)(4 * a) * plane), 0, -1, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w_wino_f + (size_t)(4 * a) * plane), 0, -1, 0x00020000);
     auto loadB = [&](f32x4 (&bf)[4][2], int c0, int kk) {
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
-                const int soff = (int)(((size_t)b * plane + (size_t)ni * 32 * Cin + c0 + 8 * kk) * 4);
+                const int soff = (int)(((size_t)b * plane + ((size_t)(c0 / 8 + kk) * Cout + (size_t)ni * 32) * 8) * 4);
                 bf[b][ni] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (int)wlane, soff, 0));
             }
     };
@@ -402,8 +406,12 @@ size_t conv_wino_ws_floats(int B, int H, int W, int Cin, int Cout) {
     return (size_t)16 * B * (H / 2) * (W / 2) * (Cin + Cout);
 }
 
+bool conv_wino_fused(int B, int H, int W, int Cin, int Cout) {
+    return conv_wino_supported(B, H, W, Cin, Cout) && wino_fused_shape(B, H, W, Cin, Cout);
+}
+
 bool conv_wino_taken(const ConvParams &p) {
-    if (!p.w_wino || p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.in_fm || p.f8)
+    if (p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.in_fm || p.f8)
         return false;
     if (p.gnf_gamma || p.out_split.p || !p.out_f32 || p.resid_split) return false;
     if (p.in0.pad != 1 || p.in0.H != p.Hout || p.in0.W != p.Wout) return false;
@@ -412,6 +420,7 @@ bool conv_wino_taken(const ConvParams &p) {
     const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
     if (!conv_wino_supported(p.B, p.Hout, p.Wout, Cin, p.out.C)) return false;
     if (wino_fused_shape(p.B, p.Hout, p.Wout, Cin, p.out.C)) {
+        if (!p.w_wino_f) return false;
         // one input tensor: the engine concatenates x || skip in the GroupNorm apply pass that writes the conv's input,
         // so no caller hands these convs a second tensor (one that does gets the direct kernel)
         if (p.in1.p) return false;
@@ -422,7 +431,7 @@ bool conv_wino_taken(const ConvParams &p) {
         const int spb = p.stats_slices / spi;
         return spb == 1 || spb == 2 || spb == 4;
     }
-    if (!p.wino_ws) return false;
+    if (!p.w_wino || !p.wino_ws) return false;
     const int tiles = (p.Hout >> 1) * (p.Wout >> 1);
     return p.stats == nullptr || (p.stats_slices > 0 && (tiles % p.stats_slices) == 0);
 }
@@ -440,6 +449,35 @@ void make_wino_weights(const float *w9, int Cout, int CinPad, float *dst) {
                 dst[(size_t)(a * 4 + b) * plane + i] = (float)(gg[0] * G[b][0] + gg[1] * G[b][1] + gg[2] * G[b][2]);
         }
     }
+}
+
+void make_wino_weights_frag(const float *wino, int Cout, int CinPad, float *dst) {
+    const int groups = CinPad / 8;
+    for (int ps = 0; ps < 16; ++ps)
+        for (int g = 0; g < groups; ++g)
+            for (int n = 0; n < Cout; ++n)
+                for (int j = 0; j < 8; ++j)
+                    dst[(((size_t)ps * groups + g) * Cout + n) * 8 + j] = wino[((size_t)ps * Cout + n) * CinPad + 8 * g + j];
+}
+
+namespace {
+// the same permutation on the device: one thread per 8-float group (two 16-B loads, two 16-B stores)
+__global__ __launch_bounds__(256) void wino_frag_kernel(const float *__restrict__ wino, int Cout, int CinPad, float *__restrict__ dst) {
+    const int groups = CinPad / 8;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;          // destination group ((ps, g), n)
+    if (i >= (size_t)16 * groups * Cout) return;
+    const size_t n = i % (size_t)Cout, pg = i / (size_t)Cout;
+    const size_t ps = pg / (size_t)groups, g = pg - ps * groups;
+    const f32x4 *s = reinterpret_cast<const f32x4 *>(wino + (ps * Cout + n) * CinPad + 8 * g);
+    f32x4 *d = reinterpret_cast<f32x4 *>(dst + i * 8);
+    d[0] = s[0];
+    d[1] = s[1];
+}
+} // namespace
+
+void launch_wino_frag(const float *wino, int Cout, int CinPad, float *dst, hipStream_t s) {
+    const size_t n = (size_t)16 * (CinPad / 8) * Cout;
+    hipLaunchKernelGGL(wino_frag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wino, Cout, CinPad, dst);
 }
 
 void launch_conv_wino(const ConvParams &p, hipStream_t s) {

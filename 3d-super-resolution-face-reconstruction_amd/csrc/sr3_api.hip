@@ -53,6 +53,8 @@ struct Param {
     float *dev_split = nullptr;                  // P_CONV: split-f16 copy (prec 1), same size
     float *dev_f8 = nullptr;                     // P_CONV 3x3: F8C copy of dev_split ("f16f8" mode; made on demand)
     float *dev_wino = nullptr;                   // P_CONV 3x3 (wino_weights): G g G^T [16][cout][cin_pad] for prec 0
+    float *dev_wino_f = nullptr;                 // the same in fragment-major order [16][cin_pad/8][cout][8] for the
+                                                 // one-pass kernel: made when a workspace plan runs the conv there
     float w_unscale = 1.0f;
     bool keep_host = false;                      // part of a fused (conv2 + res_conv) launch
     bool up_phase = false;                       // Upsample conv: stored as 4 sub-pixel phases x 2x2 taps
@@ -392,6 +394,20 @@ bool wino_weights(const Param &p) {
            (p.cout % 64) == 0;
 }
 
+// the one-pass Winograd kernel's fragment-major copy of a parameter's transformed weights, made from dev_wino on the
+// device the first time a workspace plan runs the conv at a one-pass shape (a parameter does not know its level; only
+// the 64x64 and 128x128 levels' convs get one). sr3_load_weight refreshes it with dev_wino.
+int ensure_wino_frag(sr3_ctx *c, Param &p) {
+    if (p.dev_wino_f) return 0;
+    const size_t n = (size_t)16 * p.cout * p.cin_pad;
+    HIP_OK(hipMalloc(&p.dev_wino_f, n * sizeof(float)));
+    c->weight_bytes += n * sizeof(float);
+    launch_wino_frag(p.dev_wino, p.cout, p.cin_pad, p.dev_wino_f, c->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int alloc_weights(sr3_ctx *c) {
     const int inner = c->cfg.inner_channel;
     HIP_OK(hipMalloc(&c->nfw, (size_t)c->nf_total * inner * sizeof(float)));
@@ -560,9 +576,11 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
             };
             if (m.kind == M_RES) {
                 want(oc, m.rb.cin); want(oc, oc);
-                for (const ConvRef *cr : {&m.rb.c1, &m.rb.c2})      // Winograd workspace of the block's 3x3 convs
-                    if (wino_weights(c->params[cr->w]) && conv_wino_supported(B, h, w, cr->cin_pad, cr->cout))
-                        max_wino = std::max<uint64_t>(max_wino, conv_wino_ws_floats(B, h, w, cr->cin_pad, cr->cout));
+                for (const ConvRef *cr : {&m.rb.c1, &m.rb.c2}) {    // Winograd workspace of the block's 3x3 convs
+                    if (!wino_weights(c->params[cr->w]) || !conv_wino_supported(B, h, w, cr->cin_pad, cr->cout)) continue;
+                    max_wino = std::max<uint64_t>(max_wino, conv_wino_ws_floats(B, h, w, cr->cin_pad, cr->cout));
+                    if (conv_wino_fused(B, h, w, cr->cin_pad, cr->cout) && ensure_wino_frag(c, c->params[cr->w])) return -1;
+                }
                 if (m.rb.attn) { want(3 * oc, oc); want(oc, oc); }
             } else if (m.kind == M_UP) {
                 const long Ml = Mo / 4;                       // each sub-pixel phase is a conv over the low-res pixels
@@ -733,7 +751,9 @@ void run_conv(sr3_ctx *c, const TDesc &a, const TDesc &b, const ConvRef &cv, int
     p.ks = cv.ks; p.stride = stride; p.up2 = up2;
     p.prec = activated ? c->prec : 0;
     p.w = p.prec ? c->params[cv.w].dev_split : c->params[cv.w].dev;
-    if (!p.prec && cv.cin_pad == a.C + (b.p ? b.C : 0)) { p.w_wino = c->params[cv.w].dev_wino; p.wino_ws = c->wino_ws; }
+    if (!p.prec && cv.cin_pad == a.C + (b.p ? b.C : 0)) {
+        p.w_wino = c->params[cv.w].dev_wino; p.w_wino_f = c->params[cv.w].dev_wino_f; p.wino_ws = c->wino_ws;
+    }
     if (f8 && p.prec) { p.f8 = 1; p.w = c->params[cv.w].dev_f8; }
     p.w_unscale = c->params[cv.w].w_unscale;
     p.bias = bias_override ? bias_override : (cv.b >= 0 ? c->params[cv.b].dev : nullptr);
@@ -1288,6 +1308,7 @@ void sr3_destroy(sr3_ctx *c) {
         if (p.dev_split) (void)hipFree(p.dev_split);
         if (p.dev_f8) (void)hipFree(p.dev_f8);
         if (p.dev_wino) (void)hipFree(p.dev_wino);
+        if (p.dev_wino_f) (void)hipFree(p.dev_wino_f);
     }
     if (c->final_wq) (void)hipFree(c->final_wq);
     if (c->ci_w) (void)hipFree(c->ci_w);
@@ -1348,6 +1369,16 @@ int sr3_set_precision(sr3_ctx *c, int prec) {
 }
 
 int sr3_conv_f8_supported(int B, int H, int W, int Cout, int Cin) { return conv_f8_supported(B, H, W, Cout, Cin) ? 1 : 0; }
+
+int sr3_wino_weights_host(const float *packed_host, int Cout, int CinPad, int frag, float *dst_host) {
+    if (!packed_host || !dst_host || Cout <= 0 || CinPad <= 0 || (CinPad % 8))
+        return fail("sr3_wino_weights_host: Cout > 0 and CinPad a positive multiple of 8");
+    if (!frag) { make_wino_weights(packed_host, Cout, CinPad, dst_host); return 0; }
+    std::vector<float> wv((size_t)16 * Cout * CinPad);
+    make_wino_weights(packed_host, Cout, CinPad, wv.data());
+    make_wino_weights_frag(wv.data(), Cout, CinPad, dst_host);
+    return 0;
+}
 
 int sr3_synchronize(sr3_ctx *c) {
     if (!c) return fail("null context");
@@ -1412,6 +1443,11 @@ int sr3_load_weight(sr3_ctx *c, const char *name, const float *host, const int64
                 std::vector<float> wv((size_t)16 * p.cout * p.cin_pad);
                 make_wino_weights(packed.data(), p.cout, p.cin_pad, wv.data());
                 HIP_OK(hipMemcpy(p.dev_wino, wv.data(), wv.size() * sizeof(float), hipMemcpyHostToDevice));
+                if (p.dev_wino_f) {
+                    std::vector<float> wf(wv.size());
+                    make_wino_weights_frag(wv.data(), p.cout, p.cin_pad, wf.data());
+                    HIP_OK(hipMemcpy(p.dev_wino_f, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
+                }
             }
             if (p.keep_host) p.host = packed;
             std::vector<float> sp(p.dev_floats);
@@ -1799,9 +1835,15 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     }
     // Winograd form where the engine would take it for this shape (launch_conv decides per launch)
     float *dww = nullptr, *dws = nullptr;
+    bool wfrag = false;            // dww in the one-pass kernel's fragment-major order (w_wino_f)
     if (!c->prec && ks == 3 && stride == 1 && !up2 && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
         std::vector<float> wv((size_t)16 * Cout * Cin);
         make_wino_weights(packed.data(), Cout, Cin, wv.data());
+        if ((wfrag = conv_wino_fused(B, Hin, Win, Cin, Cout))) {
+            std::vector<float> wf(wv.size());
+            make_wino_weights_frag(wv.data(), Cout, Cin, wf.data());
+            wv.swap(wf);
+        }
         HIP_OK(hipMalloc(&dww, wv.size() * sizeof(float)));
         HIP_OK(hipMemcpy(dww, wv.data(), wv.size() * sizeof(float), hipMemcpyHostToDevice));
         if (const size_t wsf = conv_wino_ws_floats(B, Hin, Win, Cin, Cout)) HIP_OK(hipMalloc(&dws, wsf * sizeof(float)));
@@ -1851,7 +1893,8 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     p.in_fm = ws ? 1 : 0;
     if (ws) p.tile_cnt = c->tile_cnt;       // (the experiment's tile counters)
     p.w = dw; p.bias = db; p.chan_bias = chan_bias_dev; p.chan_bias_stride = Cout;
-    p.w_wino = dww; p.wino_ws = dws;
+    (wfrag ? p.w_wino_f : p.w_wino) = dww;
+    p.wino_ws = dws;
     p.out = unpadded(out_dev, Cout, p.Hout, p.Wout);
     p.ovf = c->d_ovf;            // (range bits of twin stores and the 'wait gave up' bit of the in-place split-K)
     if (resid_dev) p.resid = unpadded(const_cast<float *>(resid_dev), Cout, p.Hout, p.Wout);
@@ -1943,7 +1986,8 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
         HIP_OK(hipMalloc(&wino_w, (size_t)16 * Cout * Cin * 4));
         if (const size_t wsf = conv_wino_ws_floats(B, Hin, Win, Cin, Cout)) HIP_OK(hipMalloc(&wino_ws, wsf * 4));
         rnd(wino_w, (size_t)16 * Cout * Cin, 10);
-        p.w_wino = wino_w; p.wino_ws = wino_ws;
+        (conv_wino_fused(B, Hin, Win, Cin, Cout) ? p.w_wino_f : p.w_wino) = wino_w;   // (either layout: random values)
+        p.wino_ws = wino_ws;
     }
     // split-K exactly as the engine would choose it for this problem (partials on a scratch buffer)
     float *part = nullptr;

@@ -140,6 +140,9 @@ struct ConvParams {
     // (make_wino_weights) and a workspace of conv_wino_ws_floats() floats; either null: direct kernel
     const float *w_wino = nullptr;
     float *wino_ws = nullptr;
+    // the one-pass kernel's copy of w_wino in fragment-major order [16][CinPad/8][Cout][8] (make_wino_weights_frag);
+    // null: a conv of the one-pass shapes runs on the direct kernel
+    const float *w_wino_f = nullptr;
     // GEMM batch (launch_wino_gemm only): blockIdx.z = z multiplies in0.p + z * batch_in_stride by
     // w + z * phase_w_stride into out.p + z * batch_out_stride
     int zbatch = 1;
@@ -230,6 +233,11 @@ bool conv_wino_supported(int B, int H, int W, int Cin, int Cout);
 size_t conv_wino_ws_floats(int B, int H, int W, int Cin, int Cout);
 // host helper: packed [9][Cout][CinPad] -> G g G^T as [16][Cout][CinPad] (fp64, rounded once to fp32)
 void make_wino_weights(const float *packed9, int Cout, int CinPad, float *dst);
+// conv_wino_supported and of the one-pass shapes (wino_fused_kernel, which reads ConvParams::w_wino_f)
+bool conv_wino_fused(int B, int H, int W, int Cin, int Cout);
+// host helper: [16][Cout][CinPad] (make_wino_weights) -> [16][CinPad/8][Cout][8]; launch_wino_frag: the same on the device
+void make_wino_weights_frag(const float *wino, int Cout, int CinPad, float *dst);
+void launch_wino_frag(const float *wino, int Cout, int CinPad, float *dst, hipStream_t s);
 // true when launch_conv runs this conv in Winograd form (p.w_wino / p.wino_ws set, as launch_conv would see it)
 bool conv_wino_taken(const ConvParams &p);
 void launch_conv_wino(const ConvParams &p, hipStream_t s);

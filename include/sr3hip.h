@@ -219,6 +219,12 @@ int sr3_bench_conv(sr3_ctx *ctx, int B, int Hin, int Win, int C0, int C1, int Co
                    int up2, int mode, int with_resid, int with_chan_bias, int iters, float *avg_ms,
                    float *apply_ms);
 
+/* Host-side weight layouts of the exact-f32 Winograd convs (no GPU involved): packed_host is the
+ * kernel layout [9][Cout][CinPad] of a 3x3 conv; dst receives 16 * Cout * CinPad floats of
+ * G g G^T as [16][Cout][CinPad] (frag = 0, the three-pass path) or [16][CinPad/8][Cout][8]
+ * (frag = 1, the one-pass kernel). CinPad a multiple of 8. */
+int sr3_wino_weights_host(const float *packed_host, int Cout, int CinPad, int frag, float *dst_host);
+
 /* ---- single ops through the same kernels (parity tests call these) ------------------------ */
 
 /* Conv2d over NHWC device tensors. in1_dev may be NULL (C1 = 0); channel order is in0 ‖ in1
