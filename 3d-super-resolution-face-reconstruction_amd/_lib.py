@@ -92,6 +92,7 @@ PROTOTYPES = {
     "sr3_op_conv2d": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F]),
     "sr3_op_groupnorm_affine": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _F]),
     "sr3_op_attention": (_I, [_P, _F, _I, _I, _I, _F]),
+    "sr3_op_attention_stream": (_I, [_P, _F, _I, _I, _I, _F]),
     "sr3_op_noise_embed": (_I, [_P, _F, _I, _F, _F]),
     "sr3_chan_bias_total": (_I, [_P]),
     "sr3_op_nchw_to_nhwc": (_I, [_P, _F, _I, _I, _I, _I, _F]),

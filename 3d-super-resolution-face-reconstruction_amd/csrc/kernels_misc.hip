@@ -1242,6 +1242,200 @@ double launch_attention(const float *qkv, int B, int N, int C, float *out, hipSt
     return 4.0 * (double)B * N * N * C;
 }
 
+// -------------------------------------------------------------------------------------------------
+// Streaming form of the f32 core for any token count: online softmax over tiles of KT = 32 * KB keys,
+// the N x N scores never stored. One block = 32 query rows of one image, 4 waves; the C / 32 channel
+// groups of 32 go round-robin to the waves (group g = wave + 4 a, a < NA), and a wave keeps its groups
+// of q in registers (16 floats per group and lane) and the 32 x 32 output accumulator of each.
+// Per key tile:
+//   1. every wave multiplies its q channels with the same channels of the tile's keys: a partial score
+//      tile over its share of C (v_mfma_f32_32x32x2_f32), written to its own LDS slot;
+//   2. softmax step, 8 lanes per query row: sum the partials, / sqrt(C), keys >= N to -inf, new
+//      running max m, p = exp(s - m), alpha = exp(m_old - m), l = alpha l + sum p; p and alpha to LDS;
+//   3. every wave scales its accumulators by alpha and adds P v over its own channels.
+// K and v are each read once per block (each wave its own channels). Two barriers per tile: the P
+// buffer is separate from the partial slots, so a wave may start the next tile's scores while another
+// still reads P. The MFMA k index of lane half lh in step m is 8 (m / 4) + 4 lh + m % 4 (channels for
+// the scores, keys for P v), so both operands of a step come as float4 runs.
+// -------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kStreamMaxC = 512;
+
+template <int NA, int KB>
+__global__ __launch_bounds__(256, 2) void attention_stream_kernel(const float *__restrict__ qkv, int N, int C,
+                                                               float *__restrict__ out) {
+    constexpr int NW = 4, KT = 32 * KB, LD = KT + 8;       // LD: the 8 lanes of 4 rows hit 32 distinct banks
+    __shared__ __attribute__((aligned(16))) float Ps[NW][32][LD];   // partial scores of each wave
+    __shared__ __attribute__((aligned(16))) float Pb[32][LD];       // probabilities of the tile
+    __shared__ float s_alpha[32], s_l[32];
+    const int q0 = blockIdx.x * 32, b = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const int G = C >> 5, nact = min(NW, G);
+    const size_t rs = (size_t)3 * C;
+    const float *base = qkv + (size_t)b * N * rs;
+    const float sdiv = sqrtf((float)C);
+
+    // q of this wave's channel groups (rows past N read row N - 1: their results are never written)
+    float qr[NA][16];
+    {
+        const float *qp = base + (size_t)min(q0 + li, N - 1) * rs + 4 * lh;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            const int g = wid + NW * a;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (g < G) t = *reinterpret_cast<const float4 *>(qp + g * 32 + 8 * i);
+                qr[a][4 * i] = t.x; qr[a][4 * i + 1] = t.y; qr[a][4 * i + 2] = t.z; qr[a][4 * i + 3] = t.w;
+            }
+        }
+    }
+    f32x16 o[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[a][r] = 0.f;
+    const int srow = tid >> 3, sub = tid & 7;       // softmax: 8 lanes per query row
+    float m_run = -INFINITY, l_run = 0.f;
+
+    for (int t0 = 0; t0 < N; t0 += KT) {
+        // ---- 1. partial scores over this wave's channels ----
+        if (wid < nact) {
+            f32x16 sc[KB];
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sc[kb][r] = 0.f;
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) {
+                // keys past N read row N - 1; the softmax gives them probability 0
+                const float *kp = base + (size_t)min(t0 + kb * 32 + li, N - 1) * rs + C + 4 * lh;
+#pragma unroll
+                for (int a = 0; a < NA; ++a) {
+                    const int g = wid + NW * a;
+                    if (g >= G) continue;
+                    float4 kv[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) kv[i] = *reinterpret_cast<const float4 *>(kp + g * 32 + 8 * i);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        sc[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[a][4 * i], kv[i].x, sc[kb], 0, 0, 0);
+                        sc[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[a][4 * i + 1], kv[i].y, sc[kb], 0, 0, 0);
+                        sc[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[a][4 * i + 2], kv[i].z, sc[kb], 0, 0, 0);
+                        sc[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(qr[a][4 * i + 3], kv[i].w, sc[kb], 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Ps[wid][(r & 3) + 8 * (r >> 2) + 4 * lh][kb * 32 + li] = sc[kb][r];
+        }
+        __syncthreads();
+
+        // ---- 2. online softmax of the tile ----
+        {
+            float sv[KT / 8];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < KT / 8; ++j) {
+                const int c = sub + 8 * j;
+                float v = Ps[0][srow][c];
+                for (int w = 1; w < nact; ++w) v += Ps[w][srow][c];
+                v = (t0 + c < N) ? v / sdiv : -INFINITY;
+                sv[j] = v;
+                mx = fmaxf(mx, v);
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 1));
+            mx = fmaxf(mx, __shfl_xor(mx, 2));
+            mx = fmaxf(mx, __shfl_xor(mx, 4));
+            const float m_new = fmaxf(m_run, mx);     // finite: key 0 of the first tile always exists
+            float sum = 0.f;
+#pragma unroll
+            for (int j = 0; j < KT / 8; ++j) {
+                const float p = expf(sv[j] - m_new);
+                Pb[srow][sub + 8 * j] = p;
+                sum += p;
+            }
+            sum += __shfl_xor(sum, 1);
+            sum += __shfl_xor(sum, 2);
+            sum += __shfl_xor(sum, 4);
+            const float alpha = expf(m_run - m_new);  // 0 on the first tile
+            l_run = l_run * alpha + sum;
+            m_run = m_new;
+            if (sub == 0) s_alpha[srow] = alpha;
+        }
+        __syncthreads();
+
+        // ---- 3. rescale, then o += P v over this wave's channels ----
+        if (wid < nact) {
+            float al[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) al[r] = s_alpha[(r & 3) + 8 * (r >> 2) + 4 * lh];
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                const int g = wid + NW * a;
+                if (g >= G) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[a][r] *= al[r];
+            }
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int kk = kb * 32 + 8 * i + 4 * lh;      // this lane half's 4 keys of the step group
+                    const float4 pa = *reinterpret_cast<const float4 *>(&Pb[li][kk]);
+                    const float *vp[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) vp[j] = base + (size_t)min(t0 + kk + j, N - 1) * rs + 2 * C + li;
+#pragma unroll
+                    for (int a = 0; a < NA; ++a) {
+                        const int g = wid + NW * a;
+                        if (g >= G) continue;
+                        float v[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[j] = vp[j][g * 32];
+                        o[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa.x, v[0], o[a], 0, 0, 0);
+                        o[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa.y, v[1], o[a], 0, 0, 0);
+                        o[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa.z, v[2], o[a], 0, 0, 0);
+                        o[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa.w, v[3], o[a], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+
+    if (sub == 0) s_l[srow] = l_run;
+    __syncthreads();
+    if (wid >= nact) return;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        const int g = wid + NW * a;
+        if (g >= G) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (q0 + row < N) out[((size_t)b * N + q0 + row) * C + g * 32 + li] = o[a][r] / s_l[row];
+        }
+    }
+}
+
+} // namespace
+
+bool attention_stream_supported(int C) { return C >= 32 && C <= kStreamMaxC && (C % 32) == 0; }
+
+double launch_attention_stream(const float *qkv, int B, int N, int C, float *out, hipStream_t s) {
+    const dim3 grid((N + 31) / 32, B), block(256);
+    const int G = C / 32;
+    // channel groups per wave NA; key tile 32 KB: 4 (NA, KB) fragments of MFMA work per wave and tile
+    if (G <= 4) hipLaunchKernelGGL((attention_stream_kernel<1, 2>), grid, block, 0, s, qkv, N, C, out);
+    else if (G <= 8) hipLaunchKernelGGL((attention_stream_kernel<2, 2>), grid, block, 0, s, qkv, N, C, out);
+    else hipLaunchKernelGGL((attention_stream_kernel<4, 1>), grid, block, 0, s, qkv, N, C, out);
+    return 4.0 * (double)B * N * N * C;
+}
+
 // =================================================================================================
 // Noise-level embedding (reference unet.py:18-31 PositionalEncoding, :179-184 noise_level_mlp,
 // :34-50 FeatureWiseAffine linears of every ResnetBlock, concatenated in module order).

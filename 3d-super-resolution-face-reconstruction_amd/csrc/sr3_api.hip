@@ -498,6 +498,8 @@ int max_batch(const sr3_ctx *c, int H, int W) {
         else if (m.kind == M_UP) { h *= 2; w *= 2; }
         uint64_t ch = m.kind == M_RES ? (uint64_t)m.rb.cout : (uint64_t)m.conv.cout;
         if (m.kind == M_RES) ch = std::max<uint64_t>(ch, std::max<uint64_t>(m.rb.attn ? 3ull * m.rb.cout : 0ull, (uint64_t)m.rb.cin));
+        // attention over more than 1024 tokens runs on the streaming core, which has a channel bound (ensure_workspace)
+        if (m.kind == M_RES && m.rb.attn && (long)h * w > 1024 && !attention_stream_supported(m.rb.cout)) return -1;
         per = std::max(per, (uint64_t)(h + 2) * (w + 2) * ch);
     }
     const uint64_t by_bytes = ((1ull << 32) - 1) / (per * sizeof(float));
@@ -563,8 +565,10 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
                 const uint64_t nu = (uint64_t)B * h * w * oc;
                 if (3 * nu > max_qkv) max_qkv = 3 * nu;
                 if (nu > max_ao) max_ao = nu;
-                max_vt = std::max<uint64_t>(max_vt, attention_vt_floats(B, h * w, oc));
-                if ((long)h * w > 1024) return fail("attention over %d tokens exceeds the 1024-token LDS tile", h * w);
+                if (attention_split_supported(h * w, oc)) max_vt = std::max<uint64_t>(max_vt, attention_vt_floats(B, h * w, oc));
+                // over 1024 tokens the streaming core runs (no N x N tile): only its channel bound remains
+                if ((long)h * w > 1024 && !attention_stream_supported(oc))
+                    return fail("attention over %d tokens at %d channels: the streaming core takes at most 512 channels", h * w, oc);
             }
         }
         m.oc = oc; m.oh = h; m.ow = w;
@@ -869,7 +873,9 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
         } else {
             run_conv(c, m.act2, kNone, rb.qkv, B, 1, 0, nullptr, kNone, qkv, true);
             c->pbegin(F_ATTN);
-            const double fl = launch_attention(c->qkvb, B, h * w, rb.cout, c->aob, c->stream);
+            // over 1024 tokens the 32 x N score tile no longer fits in LDS: the online-softmax core (every mode)
+            const double fl = h * w > 1024 ? launch_attention_stream(c->qkvb, B, h * w, rb.cout, c->aob, c->stream)
+                                           : launch_attention(c->qkvb, B, h * w, rb.cout, c->aob, c->stream);
             c->pend(fl);
             run_conv(c, unpadded(c->aob, rb.cout, h, w), kNone, rb.aout, B, 1, 0, nullptr, m.rb_out, m.out, false, kNone,
                      nullptr, nullptr, m.st_out, m.out_s);
@@ -1573,7 +1579,8 @@ int sr3_set_sampler_schedule(sr3_ctx *c, int S, const float *noise_level, const 
 int sr3_max_batch(sr3_ctx *c, int H, int W) {
     if (!c) return fail("null context");
     const int b = max_batch(c, H, W);
-    if (b <= 0) return fail("unsupported shape H=%d W=%d: H and W must be multiples of %d", H, W, 1 << (c->cfg.n_mults - 1));
+    if (b < 0) return fail("unsupported shape H=%d W=%d: attention over more than 1024 tokens at more than 512 channels", H, W);
+    if (b == 0) return fail("unsupported shape H=%d W=%d: H and W must be multiples of %d", H, W, 1 << (c->cfg.n_mults - 1));
     return b;
 }
 
@@ -2048,7 +2055,9 @@ int sr3_op_groupnorm_affine(sr3_ctx *c, const float *in0_dev, int C0, const floa
 
 int sr3_op_attention(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev) {
     if (!c || !qkv_dev || !out_dev) return fail("sr3_op_attention: null argument");
-    if (C % 32 || N < 1 || N > 1024) return fail("sr3_op_attention: need C %% 32 == 0 and 1 <= N <= 1024");
+    if (C % 32 || N < 1) return fail("sr3_op_attention: need C %% 32 == 0 and N >= 1");
+    if (N > 1024 && !attention_stream_supported(C))
+        return fail("sr3_op_attention: over 1024 tokens the streaming core takes at most 512 channels (C = %d)", C);
     HIP_OK(hipSetDevice(c->device));
     if (c->prec && attention_split_supported(N, C)) {
         // split-f16 mode: the engine's own sequence — q, k, v in the split operand format, fp32 result
@@ -2063,7 +2072,19 @@ int sr3_op_attention(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, floa
         HIP_OK(hipGetLastError());
         return range_check(c, "sr3_op_attention");
     }
-    launch_attention(qkv_dev, B, N, C, out_dev, c->stream);
+    if (N > 1024) launch_attention_stream(qkv_dev, B, N, C, out_dev, c->stream);
+    else launch_attention(qkv_dev, B, N, C, out_dev, c->stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int sr3_op_attention_stream(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev) {
+    if (!c || !qkv_dev || !out_dev) return fail("sr3_op_attention_stream: null argument");
+    if (B < 1 || B > 65535 || N < 1 || !attention_stream_supported(C))
+        return fail("sr3_op_attention_stream: need 1 <= B <= 65535, N >= 1 and C a multiple of 32 in [32, 512] (B=%d N=%d C=%d)",
+                    B, N, C);
+    HIP_OK(hipSetDevice(c->device));
+    launch_attention_stream(qkv_dev, B, N, C, out_dev, c->stream);
     HIP_OK(hipGetLastError());
     return 0;
 }

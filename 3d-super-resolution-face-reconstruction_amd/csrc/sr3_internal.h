@@ -307,6 +307,10 @@ float split_conv_weight_k(const float *packed, size_t rows, int CinPad, int k, f
 
 // ---- attention core ----------------------------------------------------------------------------
 double launch_attention(const float *qkv, int B, int N, int C, float *out, hipStream_t s);
+// streaming form (online softmax, any N >= 1, no N x N score tile): same operands and result as launch_attention;
+// C a multiple of 32 up to 512 (attention_stream_supported)
+bool attention_stream_supported(int C);
+double launch_attention_stream(const float *qkv, int B, int N, int C, float *out, hipStream_t s);
 // split-f16 form: qkv in the conv's split operand format ([B][N][3C], 32-channel chunks of hi | lo halfs);
 // out (fp32 [B][N][C]) and / or out_split (the same tensor in the split format) may be null
 bool attention_split_supported(int N, int C);

@@ -362,12 +362,14 @@ class Engine:
             b.ctypes.data, sc.ptr, sh.ptr))
         return sc.download((B, C)), sh.download((B, C))
 
-    def op_attention(self, qkv) -> np.ndarray:
+    def op_attention(self, qkv, streaming: bool = False) -> np.ndarray:
+        """streaming=True runs the online-softmax core at any N (otherwise it runs only above 1024 tokens)."""
         qkv = _host_f32(qkv)
         B, N, C3 = qkv.shape
         d = self.to_device(qkv)
         out = self.buffer(B * N * (C3 // 3))
-        _lib.check(self.lib.sr3_op_attention(self.ctx, d.ptr, B, N, C3 // 3, out.ptr))
+        fn = self.lib.sr3_op_attention_stream if streaming else self.lib.sr3_op_attention
+        _lib.check(fn(self.ctx, d.ptr, B, N, C3 // 3, out.ptr))
         return out.download((B, N, C3 // 3))
 
     def op_noise_embed(self, noise_level) -> Tuple[np.ndarray, np.ndarray]:

@@ -244,8 +244,13 @@ int sr3_op_groupnorm_affine(sr3_ctx *ctx, const float *in0_dev, int C0, const fl
                             int C1, int B, int H, int W, int groups, const float *gamma_host,
                             const float *beta_host, float *scale_dev, float *shift_dev);
 /* SelfAttention core (unet.py:132-139): qkv_dev [B, N, 3C] (q|k|v along the last axis) -> out
- * [B, N, C]; softmax(q.k / sqrt(C)) v, one head. */
+ * [B, N, C]; softmax(q.k / sqrt(C)) v, one head. Any N >= 1, C a multiple of 32: up to 1024 tokens the
+ * engine's cores for the precision mode run (32 x N score tile in LDS); above, the exact-f32 streaming
+ * core (online softmax, C <= 512) runs in every mode. */
 int sr3_op_attention(sr3_ctx *ctx, const float *qkv_dev, int B, int N, int C, float *out_dev);
+/* The streaming core alone, at any N >= 1 (C a multiple of 32 in [32, 512]), whatever the precision
+ * mode: for comparing it with the tiled core on the same shape. */
+int sr3_op_attention_stream(sr3_ctx *ctx, const float *qkv_dev, int B, int N, int C, float *out_dev);
 /* noise_level_mlp + every FeatureWiseAffine linear (unet.py:23-31,179-184,39,49): noise_level_dev
  * [B] -> chan_bias_dev [B, total] where total = sr3_chan_bias_total(ctx) (blocks in module order). */
 int sr3_op_noise_embed(sr3_ctx *ctx, const float *noise_level_dev, int B, float *temb_dev,
