@@ -100,6 +100,7 @@ PROTOTYPES = {
     "sr3_preprocess_bicubic": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "sr3_postprocess_u8": (_I, [_P, _F, _I, _I, _I, _I, _I, _P, _P, _F, _F]),
     "sr3_postprocess_tensor_blob": (_I, [_P, _F, _I, _I, _I, _I, _F]),
+    "sr3_metrics_psnr_ssim": (_I, [_P, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sr3_dev_malloc": (_I, [_P, _U64, C.POINTER(_P)]),
     "sr3_dev_free": (_I, [_P, _P]),
     "sr3_memcpy_h2d": (_I, [_P, _P, _P, _U64]),

@@ -21,13 +21,6 @@ namespace {
 constexpr int COEF_BITS = 11;                 // INTER_RESIZE_COEF_BITS
 constexpr int COEF_ONE = 1 << COEF_BITS;      // INTER_RESIZE_COEF_SCALE
 
-// tensor2img for one value: clamp(-1,1) -> (v+1)/2 -> *255 -> round half to even -> u8
-__device__ __forceinline__ uint8_t to_u8(float v) {
-    v = fminf(fmaxf(v, -1.f), 1.f);
-    const float t = __fmul_rn(__fdiv_rn(__fadd_rn(v, 1.f), 2.f), 255.f);
-    return (uint8_t)(int)rintf(t);
-}
-
 // [B][3][H][W] fp32 -> [B][H][W][3] u8
 __global__ void tensor2img_kernel(const float *__restrict__ in, int HW, uint8_t *__restrict__ out, size_t total) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // over B*HW pixels

@@ -151,6 +151,8 @@ struct sr3_ctx {
     int fallback_calls = 0;             // calls finished by the f32 fallback since sr3_create
     float *ckpt = nullptr;              // sr3_sample: NCHW copy of the sampler state at the last clean checkpoint
     size_t ckpt_floats = 0;
+    double *metrics_ws = nullptr;       // sr3_metrics_psnr_ssim: per-block SSIM partial sums (grows on demand)
+    size_t metrics_ws_n = 0;
     unsigned *tile_cnt = nullptr;       // ConvParams::tile_cnt: arrival counters of the in-place split-K convs (zero between launches)
     // Set (for the rest of the context's life) when a bounded inter-block wait of the in-place split-K on x-halo tiles
     // gave up — a co-tenant kernel held the CU slots its sibling blocks needed (range_read): every conv then runs on a
@@ -1326,6 +1328,7 @@ void sr3_destroy(sr3_ctx *c) {
     drop_graphs(c);
     if (c->d_ovf) (void)hipFree(c->d_ovf);
     if (c->ckpt) (void)hipFree(c->ckpt);
+    if (c->metrics_ws) (void)hipFree(c->metrics_ws);
     if (c->tile_cnt) (void)hipFree(c->tile_cnt);
     if (c->gnf_cnt) (void)hipFree(c->gnf_cnt);
     if (c->h_ovf) (void)hipHostFree(c->h_ovf);
@@ -2216,6 +2219,30 @@ int sr3_postprocess_tensor_blob(sr3_ctx *c, const float *sr, int B, int H, int W
     if (B <= 0 || H <= 0 || W <= 0 || blob <= 0) return fail("sr3_postprocess_tensor_blob: bad size");
     HIP_OK(hipSetDevice(c->device));
     launch_tensor_blob(sr, B, H, W, blob, blob, arcface, c->stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- validation metrics ------------------------------------------------------------------------
+int sr3_metrics_psnr_ssim(sr3_ctx *c, const float *sr, const float *hr, int B, int N, int row_offset, int H, int W,
+                          const double *gauss11, int64_t *ssd, double *ssim) {
+    if (!c || !sr || !hr || !gauss11 || !ssd || !ssim) return fail("sr3_metrics_psnr_ssim: null argument");
+    if (B <= 0 || N <= 0 || row_offset < 0 || H <= 0 || W <= 0)
+        return fail("sr3_metrics_psnr_ssim: bad size (B=%d N=%d row_offset=%d H=%d W=%d)", B, N, row_offset, H, W);
+    if (H < 11 || W < 11)
+        return fail("sr3_metrics_psnr_ssim: %dx%d images are smaller than the 11x11 window of the SSIM (core/metrics.py:88-93)", H, W);
+    const long long blocks = metrics_blocks(B, H, W);
+    if (blocks > 0x7fffffffll) return fail("sr3_metrics_psnr_ssim: B=%d at %dx%d needs %lld blocks, more than one launch takes", B, H, W, blocks);
+    HIP_OK(hipSetDevice(c->device));
+    const size_t need = (size_t)blocks;                        // one fp64 partial per block
+    if (c->metrics_ws_n < need) {
+        if (c->metrics_ws) HIP_OK(hipFree(c->metrics_ws));   // (hipFree waits for the kernels still reading it)
+        c->metrics_ws = nullptr; c->metrics_ws_n = 0;
+        HIP_OK(hipMalloc(&c->metrics_ws, need * sizeof(double)));
+        c->metrics_ws_n = need;
+    }
+    HIP_OK(hipMemsetAsync(ssd, 0, (size_t)B * sizeof(int64_t), c->stream));   // the blocks ADD their shares
+    launch_metrics(sr, hr, B, N, row_offset, H, W, gauss11, c->metrics_ws, ssd, ssim, c->stream);
     HIP_OK(hipGetLastError());
     return 0;
 }

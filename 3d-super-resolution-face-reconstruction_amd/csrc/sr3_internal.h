@@ -401,6 +401,14 @@ void launch_resample_h(const uint8_t *in, int B, int H, int Win, int Wout, const
 void launch_resample_v(const uint8_t *in, int B, int Hin, int Hout, int W, const int *bounds, const int *kk,
                        int ksize, float *out_nchw, uint8_t *out_u8, hipStream_t s);
 
+// ---- tensor2img for one value (core/metrics.py:16-42): clamp(-1,1) -> (v+1)/2 -> *255 -> round half to even -> u8;
+// shared by the post-processing chain (kernels_post.hip) and the validation metrics (kernels_metrics.hip)
+__device__ __forceinline__ uint8_t to_u8(float v) {
+    v = fminf(fmaxf(v, -1.f), 1.f);
+    const float t = __fmul_rn(__fdiv_rn(__fadd_rn(v, 1.f), 2.f), 255.f);
+    return (uint8_t)(int)rintf(t);
+}
+
 // ---- post-processing: tensor2img / cv2-style 8-bit linear resize / ArcFace blob (kernels_post.hip) ----
 void cv_linear_coeffs(int in_size, int out_size, bool horizontal, std::vector<int> &ofs, std::vector<int> &ab);
 void launch_tensor2img(const float *in_nchw, int B, int H, int W, uint8_t *out_hwc, hipStream_t s);
@@ -410,5 +418,14 @@ void launch_resize_linear_u8(const uint8_t *src, int B, int Hs, int Ws, int Hd, 
 // src is f x the blob size (f = 1 | 2); out [B][3][Hb][Wb], channels swapped, (avg - mean) * scale
 void launch_blob(const uint8_t *src, int B, int Hb, int Wb, int f, float mean, float scale, float *out, hipStream_t s);
 void launch_tensor_blob(const float *in_nchw, int B, int H, int W, int Hb, int Wb, float *out, hipStream_t s);
+
+// ---- validation metrics: PSNR sums and SSIM of uint8-quantised image pairs (kernels_metrics.hip) ----
+// row b of sr [B][3][H][W] is scored against hr[(row_offset + b) % N] ([N][3][H][W]); H, W >= 11 (the 11x11 window).
+// ssd[b] += sum of squared uint8 differences (exact; the caller zeroes ssd on the stream first), ssim[b] =
+// core/metrics.py:84-125 in fp64; taps = the 11 normalised Gaussian weights (host). ws: one double per block. Bitwise
+// reproducible (no floating-point atomics).
+long long metrics_blocks(int B, int H, int W);           // blocks of the tile kernel (the caller bounds them by INT_MAX)
+void launch_metrics(const float *sr, const float *hr, int B, int N, int row_offset, int H, int W, const double *taps,
+                    double *ws, int64_t *ssd, double *ssim, hipStream_t s);
 
 } // namespace sr3

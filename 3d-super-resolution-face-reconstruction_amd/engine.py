@@ -267,6 +267,16 @@ class Engine:
     def postprocess_tensor_blob(self, sr_ptr: int, B: int, H: int, W: int, blob: int, arcface_ptr: int) -> None:
         _lib.check(self.lib.sr3_postprocess_tensor_blob(self.ctx, sr_ptr, B, H, W, blob, arcface_ptr))
 
+    # ---- validation metrics ----------------------------------------------
+    def metrics(self, sr_ptr: int, hr_ptr: int, B: int, N: int, row_offset: int, H: int, W: int,
+                ssd_ptr: int, ssim_ptr: int) -> None:
+        """Row b of sr fp32 [B,3,H,W] against hr[(row_offset + b) % N] (fp32 [N,3,H,W]): exact sum of squared uint8
+        differences -> int64 [B] at ssd_ptr, SSIM -> fp64 [B] at ssim_ptr (sr3_metrics_psnr_ssim; stream-ordered)."""
+        from .validation import gaussian_kernel
+        taps = np.ascontiguousarray(gaussian_kernel(11, 1.5), dtype=np.float64)
+        _lib.check(self.lib.sr3_metrics_psnr_ssim(self.ctx, sr_ptr, hr_ptr, B, N, row_offset, H, W,
+                                                  taps.ctypes.data, ssd_ptr, ssim_ptr))
+
     def postprocess_np(self, sr: np.ndarray, up: int = 224, blob: int = 112) -> Dict[str, np.ndarray]:
         """Host-array convenience (tests): fp32 [B,3,H,W] -> dict(img_u8, up_u8, images, arcface,
         tensor_arcface)."""

@@ -8,6 +8,9 @@ with an 11x11 window is exactly the 'valid' correlation with that window, and
 `cv2.getGaussianKernel(11, 1.5)` is the normalised exp(-(i-5)^2 / (2*1.5^2)). cv2 is not available
 in the build container, so this file's SSIM is checked against an independent scipy evaluation,
 not against cv2 itself (parity unpinned for the cv2 call, formula-level faithful).
+
+The host functions are the default and the yardstick. `validate_batch(metrics="device")` / `device_scores` compute the
+same scores on the device (sr3_metrics_psnr_ssim, csrc/kernels_metrics.hip) so that only two numbers per image leave it.
 """
 from __future__ import annotations
 
@@ -62,8 +65,55 @@ def calculate_ssim(img1: np.ndarray, img2: np.ndarray) -> float:
     raise ValueError("Wrong input image dimensions.")
 
 
+def scores_from_sums(ssd, n_values: int) -> np.ndarray:
+    """PSNR (core/metrics.py:74-81) from exact sums of squared uint8 differences over `n_values` values each:
+    20*log10(255/sqrt(ssd/n)), inf where ssd == 0. Bit-equal to `metrics.psnr` on the same images: a sum of integer
+    squares below 2^53 is exact in float64 whatever the order, and the rest is the same libm calls."""
+    ssd = np.asarray(ssd)
+    out = np.empty(ssd.shape, dtype=np.float64)
+    flat = out.reshape(-1)
+    for j, v in enumerate(ssd.reshape(-1)):
+        mse = float(np.float64(int(v)) / np.float64(int(n_values)))
+        flat[j] = math.inf if mse == 0 else 20 * math.log10(255.0 / math.sqrt(mse))
+    return out
+
+
+def device_scores(netG, images: "torch.Tensor", hr: "torch.Tensor", row_offset: int = 0) -> Dict[str, np.ndarray]:
+    """PSNR / SSIM of `images` [B,3,H,W] (CUDA, any range) against `hr` [N,3,H,W] (CUDA) on the device
+    (sr3_metrics_psnr_ssim): row b is scored against hr[(row_offset + b) % N], so `hr` is never replicated. Same scores as
+    `metrics.psnr` / `calculate_ssim` on `metrics.tensor2img` of both (PSNR bit-equal, SSIM to ~1e-14). Only the 2 x B
+    results cross to the host. Returns {"psnr": float64 [B], "ssim": float64 [B]} (numpy)."""
+    import torch
+    from .postprocess import _check, _unet
+
+    sr, hr = _check(images), _check(hr)
+    if hr.device != sr.device or hr.shape[2:] != sr.shape[2:]:
+        raise RuntimeError(f"images {tuple(sr.shape)} on {sr.device} and hr {tuple(hr.shape)} on {hr.device} do not match")
+    B, _, H, W = sr.shape
+    ssd = torch.empty(B, dtype=torch.int64, device=sr.device)
+    ss = torch.empty(B, dtype=torch.float64, device=sr.device)
+    unet = _unet(netG)
+    eng = unet.engine()
+    unet.ready()
+    eng.metrics(sr.data_ptr(), hr.data_ptr(), B, hr.shape[0], int(row_offset), H, W, ssd.data_ptr(), ss.data_ptr())
+    unet.finish()
+    return {"psnr": scores_from_sums(ssd.cpu().numpy(), 3 * H * W), "ssim": ss.cpu().numpy()}
+
+
+def _gather_rows(local: "torch.Tensor", n_total: int, gpu: "torch.device") -> "torch.Tensor":
+    """dist.all_gather_images for a tensor on any device: the collective runs where the backend has one — host memory
+    for gloo, the rank's GPU `gpu` for nccl (RCCL) — and the result comes back on `local`'s device."""
+    import torch
+    from . import dist as _dist
+    if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
+        return local
+    where = torch.device("cpu") if torch.distributed.get_backend() == "gloo" else gpu
+    return _dist.all_gather_images(local.to(where), n_total).to(local.device)
+
+
 def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 1,
-                   seed: Optional[int] = None, sharded: bool = False) -> Dict[str, np.ndarray]:
+                   seed: Optional[int] = None, sharded: bool = False, metrics: str = "host",
+                   keep_images: bool = True) -> Dict[str, np.ndarray]:
     """Runs `samples` independent SR3 chains per conditioning image as one batch of N*samples
     images (sample k of image i is batch row k*N + i) and scores them against `hr`.
 
@@ -74,7 +124,15 @@ def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 
     Returns per (sample, image) PSNR / SSIM arrays and their means. The reference's running
     `avg / idx * sample` (lib/trainer_temp.py:445-446) multiplies by `sample` instead of dividing —
     the plain means are reported here.
+
+    metrics="host" (default): every image is copied to the host and scored there (metrics.psnr, calculate_ssim).
+    metrics="device": the images are scored where they are (device_scores); with sharded=True every rank scores its
+    own shard (dist.shard_bounds; a rank left without rows samples nothing) and the ranks exchange the two score
+    arrays — on the GPU with nccl / RCCL, through host memory with gloo; the images are gathered only if keep_images.
+    keep_images=False: "images" is None in the result.
     """
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
     import torch
     from . import dist as _dist
 
@@ -88,19 +146,35 @@ def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 
             box = [seed]
             torch.distributed.broadcast_object_list(box, src=0)
             seed = int(box[0])
-    if sharded:
-        out = _dist.sharded_super_resolution(
-            lambda xs, off: netG.super_resolution_batch(xs, seed=seed, image_offset=off), x)
+    if metrics == "device":
+        a, b = 0, samples * N
+        if sharded and torch.distributed.is_available() and torch.distributed.is_initialized():
+            a, b = _dist.shard_bounds(samples * N, torch.distributed.get_world_size(), torch.distributed.get_rank())
+        if b > a:
+            out = netG.super_resolution_batch(x[a:b], seed=seed, image_offset=a)
+            sc = device_scores(netG, out, hr.to(out.device), row_offset=a)
+        else:       # more ranks than rows: this rank has nothing to sample and contributes nothing to the gather
+            out = torch.empty((0,) + tuple(x.shape[1:]), dtype=torch.float32, device=next(netG.parameters()).device)
+            sc = {"psnr": np.empty(0), "ssim": np.empty(0)}
+        if sharded:
+            both = _gather_rows(torch.from_numpy(np.stack([sc["psnr"], sc["ssim"]], axis=1)), samples * N, out.device).numpy()
+            sc = {"psnr": both[:, 0], "ssim": both[:, 1]}
+            out = _gather_rows(out, samples * N, out.device) if keep_images else None
+        ps, ss = sc["psnr"].reshape(samples, N).copy(), sc["ssim"].reshape(samples, N).copy()
     else:
-        out = netG.super_resolution_batch(x, seed=seed)
-    out_np, hr_np = out.float().cpu().numpy(), hr.float().cpu().numpy()
-    ps = np.zeros((samples, N)); ss = np.zeros((samples, N))
-    for k in range(samples):
-        for i in range(N):
-            a, b = tensor2img(out_np[k * N + i]), tensor2img(hr_np[i])
-            ps[k, i] = psnr(a, b)
-            ss[k, i] = calculate_ssim(a, b)
+        if sharded:
+            out = _dist.sharded_super_resolution(
+                lambda xs, off: netG.super_resolution_batch(xs, seed=seed, image_offset=off), x)
+        else:
+            out = netG.super_resolution_batch(x, seed=seed)
+        out_np, hr_np = out.float().cpu().numpy(), hr.float().cpu().numpy()
+        ps = np.zeros((samples, N)); ss = np.zeros((samples, N))
+        for k in range(samples):
+            for i in range(N):
+                a, b = tensor2img(out_np[k * N + i]), tensor2img(hr_np[i])
+                ps[k, i] = psnr(a, b)
+                ss[k, i] = calculate_ssim(a, b)
     finite = np.isfinite(ps)
-    return {"psnr": ps, "ssim": ss, "images": out,
+    return {"psnr": ps, "ssim": ss, "images": out if keep_images else None,
             "mean_psnr": float(ps[finite].mean()) if finite.any() else math.inf,
             "mean_ssim": float(ss.mean())}

@@ -296,6 +296,26 @@ int sr3_postprocess_u8(sr3_ctx *ctx, const float *sr_nchw_dev, int B, int H, int
 int sr3_postprocess_tensor_blob(sr3_ctx *ctx, const float *sr_nchw_dev, int B, int H, int W, int blob,
                                 float *arcface_dev);
 
+/* ---- validation metrics behind the sampler -------------------------------------------------- */
+
+/* replaces the host scoring of the validation loop (lib/trainer_temp.py:441-446 ->
+ * model/sr3d/model.py:368-433), per row b of the batch against hr[(row_offset + b) % N]:
+ *   a, b    = Metrics.tensor2img(SR[b]), Metrics.tensor2img(HR[..])    core/metrics.py:16-42
+ *   ssd[b]  = sum((a - b)^2) over all 3*H*W uint8 pairs, exact          core/metrics.py:74-81
+ *             (calculate_psnr = 20*log10(255/sqrt(ssd / (3*H*W))), inf for ssd == 0: left to the host)
+ *   ssim[b] = Metrics.calculate_ssim(a, b)                               core/metrics.py:84-125
+ *             (fp64; 11x11 Gaussian, sigma 1.5; 'valid' region (H-10) x (W-10); C1 = 6.5025,
+ *             C2 = 58.5225; mean of the map per channel, mean of the three channels)
+ * sr_nchw: fp32 [B,3,H,W], any range (the sampler's output); hr_nchw: fp32 [N,3,H,W], never
+ * replicated: sample k of image i is row k*N + i of a validation batch, a shard of it starts at
+ * row_offset. gauss11_host: the 11 normalised taps of cv2.getGaussianKernel(11, 1.5) in fp64 (host
+ * memory; the device evaluates no exp). ssd_dev [B] int64, ssim_dev [B] fp64: device pointers.
+ * H, W >= 11 (the formula has no value below the window size). Two calls on the same inputs return
+ * bitwise equal results (no floating-point atomics). Asynchronous on the context's stream. */
+int sr3_metrics_psnr_ssim(sr3_ctx *ctx, const float *sr_nchw_dev, const float *hr_nchw_dev, int B, int N,
+                          int row_offset, int H, int W, const double *gauss11_host, int64_t *ssd_dev,
+                          double *ssim_dev);
+
 /* ---- device memory helpers (so hosts without torch can drive the library) ---------------- */
 int sr3_dev_malloc(sr3_ctx *ctx, uint64_t bytes, void **out_dev);
 int sr3_dev_free(sr3_ctx *ctx, void *dev);
