@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# SR3_LIB: another build of the same C-ABI (development: the -DSR3_EXPERIMENTS library of build.py --experiments)
+# SR3_LIB: another build of the same C-ABI (development: an A/B of two builds of the library, tools/ab_bench.sh)
 LIB_PATH = os.environ.get("SR3_LIB") or os.path.join(HERE, "libsr3hip.so")
 
 SR3_MAX_MULTS = 8

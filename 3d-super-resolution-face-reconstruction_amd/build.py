@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsr3hip.so")
-SOURCES = ["sr3_api.hip", "kernels_conv.hip", "kernels_conv_ws.hip", "kernels_wino.hip", "kernels_misc.hip", "kernels_edge.hip", "kernels_pre.hip", "kernels_post.hip", "kernels_metrics.hip"]
+SOURCES = ["sr3_api.hip", "kernels_conv.hip", "kernels_wino.hip", "kernels_misc.hip", "kernels_edge.hip", "kernels_pre.hip", "kernels_post.hip", "kernels_metrics.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-source flags: the fp32 VALU contraction of kernels_edge.hip must stay scalar v_fma_f32 (the SLP
 # vectoriser packs it into v_pk_fma_f32 pairs: register-pair shuffles, 2 KB of scratch per lane)
@@ -33,17 +33,9 @@ def _stale(out: str, deps: list[str]) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_library(force: bool = False, verbose: bool = False, experiments: bool = False) -> str:
-    """experiments=True builds libsr3hip_exp.so with -DSR3_EXPERIMENTS: the timing switches of
-    tools/conv_bench.py (SR3_CONV_DBG) exist only there, never in the product library."""
+def build_library(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
-    # SR3_EXP_TAG / SR3_EXP_DEFINES (experiments only): several variant libraries side by side, e.g.
-    #   SR3_EXP_TAG=v1 SR3_EXP_DEFINES="-DSR3_GA_VARIANT=1" python build.py --experiments  -> libsr3hip_exp_v1.so
-    tag = os.environ.get("SR3_EXP_TAG", "") if experiments else ""
-    extra = os.environ.get("SR3_EXP_DEFINES", "").split() if experiments else []
-    objdir = os.path.join(HERE, ("build_exp" + ("_" + tag if tag else "")) if experiments else "build")
-    lib = os.path.join(HERE, "libsr3hip_exp%s.so" % ("_" + tag if tag else "")) if experiments else LIB
-    flags = FLAGS + (["-DSR3_EXPERIMENTS"] + extra if experiments else [])
+    objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "sr3_internal.h"),
                os.path.join(HERE, "..", "include", "sr3hip.h")]
@@ -54,7 +46,7 @@ def build_library(force: bool = False, verbose: bool = False, experiments: bool 
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(obj)
         if force or _stale(obj, [sp] + headers):
-            jobs.append([hipcc, *flags, *EXTRA_FLAGS.get(src, []), "-c", sp, "-o", obj])
+            jobs.append([hipcc, *FLAGS, *EXTRA_FLAGS.get(src, []), "-c", sp, "-o", obj])
 
     def run(cmd):
         if verbose:
@@ -66,10 +58,10 @@ def build_library(force: bool = False, verbose: bool = False, experiments: bool 
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(run, jobs))
-    if force or jobs or _stale(lib, objs):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs])
-    return lib
+    if force or jobs or _stale(LIB, objs):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
+    return LIB
 
 
 if __name__ == "__main__":
-    print(build_library(force="--force" in sys.argv, verbose=True, experiments="--experiments" in sys.argv))
+    print(build_library(force="--force" in sys.argv, verbose=True))

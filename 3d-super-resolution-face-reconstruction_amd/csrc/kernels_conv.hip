@@ -48,14 +48,6 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-// timing experiments (tools/conv_bench.py) exist only in builds with -DSR3_EXPERIMENTS: the product
-// library ignores SR3_CONV_DBG and carries no experiment branches in its kernels
-#ifdef SR3_EXPERIMENTS
-#define SR3_DBG(p) ((p).dbg)
-#else
-#define SR3_DBG(p) 0
-#endif
-
 constexpr int BK = 32;            // channels per K-step
 constexpr int ROWF = 32;          // floats per LDS row (128 B, unpadded)
 
@@ -251,17 +243,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams &p, f32x16 (&acc)
 // epilogue's critical path): bias + FeatureWiseAffine bias when the whole tile lies in one image
 // (one_img: the flag the producers leave behind the table); otherwise bias only and the per-image part is
 // gathered per row. BN may be a column slice of the block's tile (in-place split-K: n0 and colbias advanced by it).
-// QRED (persistent kernel): the four row groups of a wave are added by lane exchange first, only lanes q == 0
-// write [wm][column] entries (a quarter of the staging space) and the caller does the barrier
-// GNF (producer-side GroupNorm of the output, ConvParams::gnf_*): the column statistics go out FIRST (phase 6 moves in
-// front of the stores), the wave then sits through the four barriers of gnf_producer_tail, picks up scale / shift of its
-// columns from LDS, applies swish(scale * v + shift) to the accumulators and stores them as the split-f16 tensor only.
-template <int BM, int BN, int WGM, int WGN, int MT, int NT, bool QRED = false, bool GNF = false>
+template <int BM, int BN, int WGM, int WGN, int MT, int NT>
 __device__ __forceinline__ void conv_epilogue16(const ConvParams &p, f32x4 (&acc)[MT][NT], float *smem,
                                                 const int *rowpix, const int *rowimg, int m0, int n0, int M, int wm,
                                                 int wn, int l16, int q, const float *colbias, const bool one_img) {
     constexpr int WM = BM / WGM, WN = BN / WGN;
-    static_assert(!(GNF && QRED), "the persistent experiment has no producer-side GroupNorm");
     const unsigned Cout = (unsigned)p.out.C;
     const unsigned ncol = (unsigned)(n0 + wn * WN + l16);       // column of nt = 0; + 16 per nt
     // element offset of (row, column 0) for this lane's 4 rows of every row tile
@@ -321,52 +307,14 @@ __device__ __forceinline__ void conv_epilogue16(const ConvParams &p, f32x4 (&acc
             }
         }
     }
-    if constexpr (GNF) {
-        // 6'. statistics of the values block2's GroupNorm sees (bias and FeatureWiseAffine bias included), then the
-        //     hand-off (gnf_producer_tail: barriers A, A2, A3, Y, X1) and the normalisation in registers
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            double st1 = 0.0, st2 = 0.0;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const double v = (double)acc[mt][nt][j];
-                    st1 += v; st2 = fma(v, v, st2);
-                }
-            reinterpret_cast<double2 *>(smem)[(wm * 4 + q) * BN + wn * WN + nt * 16 + l16] = make_double2(st1, st2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads();        // A: column sums staged
-        __syncthreads();        // A2: this block's slice is on its way to memory
-        __syncthreads();        // A3: arrival counted
-        __syncthreads();        // Y: (last block: slices folded | others: group ready)
-        __syncthreads();        // X1: scale / shift of this N-tile in LDS
-        const float2 *ab_lds = reinterpret_cast<const float2 *>(smem + WGM * 4 * BN * 4);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const float2 ab = ab_lds[wn * WN + nt * 16 + l16];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float x = fmaf(ab.x, acc[mt][nt][j], ab.y);
-                    acc[mt][nt][j] = x * __frcp_rn(1.0f + __expf(-x));      // Swish (unet.py:53-55), as gn_apply does it
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
     // The statistics phase (6) runs in FRONT of the stores (4, 5): the producer threads' tail (adding the staged column sums,
     // writing the slice) then runs under the consumers' store phase instead of after it, and the block leaves its CU
-    // slot that much earlier: 16.887 -> 16.780 ms per B = 64 step (three alternating pairs, -DSR3_EARLY_STATS=0 | 1
-    // builds of the same source; profiles/README.md finding 61)
-#ifndef SR3_EARLY_STATS
-#define SR3_EARLY_STATS 1
-#endif
-    constexpr bool EARLY = SR3_EARLY_STATS && !QRED && !GNF;
-    auto stats_phase = [&]() {
+    // slot that much earlier: 16.887 -> 16.780 ms per B = 64 step (three alternating pairs; profiles/README.md finding 61)
     // 6. fused GroupNorm statistics of the stored values: fp64 column sums, handed to the producers
-        if (!GNF && p.stats != nullptr) {
+    // (a lambda called once: written inline, the 8-pixel-segment split-K instantiation comes out with 114 instead of
+    // 115 VGPRs, i.e. as different, unmeasured code)
+    auto stats_phase = [&]() {
+        if (p.stats != nullptr) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 double st1 = 0.0, st2 = 0.0;
@@ -377,21 +325,15 @@ __device__ __forceinline__ void conv_epilogue16(const ConvParams &p, f32x4 (&acc
                         const double v = (double)acc[mt][nt][j];
                         st1 += v; st2 = fma(v, v, st2);
                     }
-                if (QRED) {
-                    st1 += __shfl_xor(st1, 16); st2 += __shfl_xor(st2, 16);
-                    st1 += __shfl_xor(st1, 32); st2 += __shfl_xor(st2, 32);
-                    if (q == 0) reinterpret_cast<double2 *>(smem)[wm * BN + wn * WN + nt * 16 + l16] = make_double2(st1, st2);
-                } else {
-                    reinterpret_cast<double2 *>(smem)[(wm * 4 + q) * BN + wn * WN + nt * 16 + l16] = make_double2(st1, st2);
-                }
+                reinterpret_cast<double2 *>(smem)[(wm * 4 + q) * BN + wn * WN + nt * 16 + l16] = make_double2(st1, st2);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (!QRED) __syncthreads();
+            __syncthreads();
         }
     };
-    if constexpr (EARLY) stats_phase();
+    stats_phase();
     // 4. fp32 output (32-bit byte offsets: every tensor is < 4 GiB)
-    if (!GNF && p.out_f32) {
+    if (p.out_f32) {
         char *obase = reinterpret_cast<char *>(p.out.p);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -428,7 +370,6 @@ __device__ __forceinline__ void conv_epilogue16(const ConvParams &p, f32x4 (&acc
         }
         if (p.ovf != nullptr && split_range_overflow(range_bits)) *p.ovf = 1;
     }
-    if constexpr (!EARLY) stats_phase();
 }
 
 // conv_epilogue16's phase structure for 32x32 accumulator tiles (the F8C consumers of the x-halo kernel): C/D map
@@ -565,124 +506,6 @@ __device__ __forceinline__ void producer_stats_tail(const ConvParams &p, const f
     }
 }
 
-// Producer side of the producer-side GroupNorm (ConvParams::gnf_*), run by the block's 256 producer threads while the
-// consumer waves sit in the matching barriers of conv_epilogue16<..., GNF>. NSL = staged entries per column.
-// Hand-off forms (MI355X_MICROARCH.md, inter-workgroup visibility): every byte that crosses blocks is written by a
-// write-through (sc1) store and read by a cache-bypassing (sc1) global load; every storing wave waits vmcnt(0), then a
-// workgroup barrier, then ONE lane adds to the group's counter (agent scope). The counter of a group of G blocks runs
-// 0 -> G (arrivals; the add that returns G - 1 marks the last block) -> 2G (the last block's "ready", after its
-// scale / shift stores have completed) -> 3G (departures: every block adds 1 after it has fetched scale / shift; the
-// add that returns 3G - 1 stores 0, ready for the next launch — nobody polls any more by then).
-// No wait can hang by construction: a block only waits for blocks of its own group, which launch_conv orders so that
-// they are dispatched together (see conv_gnf_supported); should the hardware ever dispatch differently, the poll gives
-// up after SR3_WAIT_TICKS of the 100 MHz real-time counter (5 ms), raises SR3_FLAG_GNF_TIMEOUT in *ovf and the grid drains.
-typedef unsigned __attribute__((address_space(1))) *gnf_cnt_ptr;
-typedef const double __attribute__((address_space(1))) *gnf_cdbl_ptr;
-typedef double __attribute__((address_space(1))) *gnf_dbl_ptr;
-typedef const float __attribute__((address_space(1))) *gnf_cflt_ptr;
-typedef float __attribute__((address_space(1))) *gnf_flt_ptr;
-template <int BM, int BN, int NSL>
-__device__ __forceinline__ void gnf_producer_tail(const ConvParams &p, float *smem, int m0, int n0, int HWo, int tid) {
-    const double2 *red = reinterpret_cast<const double2 *>(smem);
-    float2 *ab_lds = reinterpret_cast<float2 *>(smem + NSL * BN * 4);                  // [BN]
-    double2 *fin = reinterpret_cast<double2 *>(smem + NSL * BN * 4 + 2 * BN);          // [256 / BN][BN]
-    const int Cout = p.out.C;
-    const int img = m0 / HWo, TMI = HWo / BM, slice = (m0 - img * HWo) / BM;
-    const int tilesN = Cout / BN, ntile = n0 / BN;
-    const unsigned G = (unsigned)TMI;
-    // counter and ready word of the group on cache lines of their own (the pollers' loads must not queue in front of
-    // the other blocks' arrival adds)
-    gnf_cnt_ptr cnt = (gnf_cnt_ptr)(p.gnf_cnt + ((size_t)img * tilesN + ntile) * 64);
-    gnf_cnt_ptr rdy = cnt + 32;
-    __syncthreads();                                    // A: the consumers' column sums are staged
-    if (tid < BN) {
-        double a = 0, b = 0;
-#pragma unroll
-        for (int j = 0; j < NSL; ++j) { const double2 v = red[j * BN + tid]; a += v.x; b += v.y; }
-        gnf_dbl_ptr o = (gnf_dbl_ptr)(p.stats + (((size_t)img * TMI + slice) * Cout + n0 + tid) * 2);
-        __hip_atomic_store(o, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(o + 1, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the slice has reached the coherence point ...
-    __syncthreads();                                    // A2: ... in every storing wave
-    if (tid == 0) {
-        const unsigned old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == G - 1u) {
-            // last arrival: every block of the group counted itself after its slice had completed
-            __hip_atomic_store(rdy, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-            while (__hip_atomic_load(rdy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-                __builtin_amdgcn_s_sleep(16);
-                if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > SR3_WAIT_TICKS) {     // 5 ms: never in a healthy run
-                    if (p.ovf != nullptr) atomicOr(p.ovf, SR3_FLAG_GNF_TIMEOUT);
-                    break;
-                }
-            }
-        }
-    }
-    __syncthreads();                                    // A3: all G slices of this image are complete
-    // EVERY block folds the G slices of its N-tile's channels itself (in slice order: the same bits in every block):
-    // thread (channel c, part) adds slices part, part + PARTS, ... with all its loads in flight at once. One hop less
-    // than "the last block folds and publishes" (no second flag, no scale / shift round trip).
-    constexpr int PARTS = 256 / BN;
-    {
-        const int c = tid % BN, part = tid / BN;
-        gnf_cdbl_ptr base = (gnf_cdbl_ptr)(p.stats + ((size_t)img * TMI * Cout + n0 + c) * 2);
-        const size_t sstride = (size_t)Cout * 2;
-        double sa = 0, sb = 0;
-        int sidx = part;
-        for (; sidx + 15 * PARTS < TMI; sidx += 16 * PARTS) {
-            double va[16], vb[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                va[u] = __hip_atomic_load(base + (size_t)(sidx + u * PARTS) * sstride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                vb[u] = __hip_atomic_load(base + (size_t)(sidx + u * PARTS) * sstride + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (int u = 0; u < 16; ++u) { sa += va[u]; sb += vb[u]; }
-        }
-        for (; sidx + 3 * PARTS < TMI; sidx += 4 * PARTS) {
-            double va[4], vb[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                va[u] = __hip_atomic_load(base + (size_t)(sidx + u * PARTS) * sstride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                vb[u] = __hip_atomic_load(base + (size_t)(sidx + u * PARTS) * sstride + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { sa += va[u]; sb += vb[u]; }
-        }
-        for (; sidx < TMI; sidx += PARTS) {
-            sa += __hip_atomic_load(base + (size_t)sidx * sstride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sb += __hip_atomic_load(base + (size_t)sidx * sstride + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        fin[part * BN + c] = make_double2(sa, sb);
-    }
-    __syncthreads();                                    // Y
-    if (tid < BN) {
-        // whole groups lie inside an N-tile: channel tid adds its group's channels and parts in a fixed order
-        const int cg = Cout / p.gnf_groups, g0 = (tid / cg) * cg;
-        double sa = 0, sb = 0;
-        for (int cc = 0; cc < cg; ++cc)
-#pragma unroll
-            for (int pt = 0; pt < PARTS; ++pt) { const double2 v = fin[pt * BN + g0 + cc]; sa += v.x; sb += v.y; }
-        const double count = (double)cg * HWo;
-        const double mean = sa / count;
-        const double var = fmax(sb / count - mean * mean, 0.0);
-        const float rstd = 1.0f / sqrtf((float)var + p.gnf_eps);
-        const float sc = rstd * p.gnf_gamma[n0 + tid];
-        ab_lds[tid] = make_float2(sc, p.gnf_beta[n0 + tid] - (float)mean * sc);
-    }
-    __syncthreads();                                    // X1: scale / shift of this N-tile in LDS
-    if (tid == 0) {
-        const unsigned old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // departed
-        if (old == 2u * G - 1u) {       // every block of the group has read the slices: ready for the next launch
-            __hip_atomic_store(rdy, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
 // PREC 0: exact f32 (v_mfma_f32_32x32x2_f32); PREC 1: split-f16, 3 x v_mfma_f32_32x32x16_f16
 // NS: LDS pipeline stages (power of two or 3); the DMA of tile k+NS-1 is issued while tile k is
 // multiplied, so NS-2 tiles stay in flight across a barrier (counted vmcnt + raw s_barrier)
@@ -801,26 +624,23 @@ __global__ __launch_bounds__(512, (((BM + BN) * ROWF * 4 * NS + 8 * BM) * 3 <= 1
                 constexpr int dy = tap / KS, dx = tap % KS;
                 float *Ad = smem + (k % NS) * STAGE + w * 256;
                 float *Bd = Ad + BM * ROWF;
-                if (!(SR3_DBG(p) & 1) || k == 0) {
-                    const char *ab = abase + (size_t)(dy * Wp + dx) * Cs * 4;
-                    if (SR3_DBG(p) & 2) ab = reinterpret_cast<const char *>(p.in0.p);   // experiment: cache-hot source
-                    if (first) {
-                        static_for<AR>([&](auto ic) {
-                            constexpr int i = decltype(ic)::value;
-                            dma16s<DMA_BUF>(ab, vA0[i], Ad + i * 1024);
-                        });
-                    } else {
-                        static_for<AR>([&](auto ic) {
-                            constexpr int i = decltype(ic)::value;
-                            dma16s<DMA_BUF>(ab, vA1[i], Ad + i * 1024);
-                        });
-                    }
-                    const char *wb = (SR3_DBG(p) & 2) ? reinterpret_cast<const char *>(p.w) : wbase + (size_t)tap * tapstride * 4;
-                    static_for<BR>([&](auto ic) {
+                const char *ab = abase + (size_t)(dy * Wp + dx) * Cs * 4;
+                if (first) {
+                    static_for<AR>([&](auto ic) {
                         constexpr int i = decltype(ic)::value;
-                        dma16s<DMA_BUF>(wb, vB[i], Bd + i * 1024);
+                        dma16s<DMA_BUF>(ab, vA0[i], Ad + i * 1024);
+                    });
+                } else {
+                    static_for<AR>([&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        dma16s<DMA_BUF>(ab, vA1[i], Ad + i * 1024);
                     });
                 }
+                const char *wb = wbase + (size_t)tap * tapstride * 4;
+                static_for<BR>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value;
+                    dma16s<DMA_BUF>(wb, vB[i], Bd + i * 1024);
+                });
                 if (k >= NS - 2) producer_sync<(NS - 2) * (AR + BR)>();
                 ++k;
             });
@@ -1078,15 +898,13 @@ __global__ __launch_bounds__(512, (((BM + BN) * ROWF * 4 * NS + 8 * BM) * 3 <= 1
 // =================================================================================================
 // MS: MFMA shape of the consumers, 32 (v_mfma_f32_32x32x16_f16) or 16 (v_mfma_f32_16x16x32_f16: same
 // FLOP per cycle, but the chip holds a higher clock on it under load — MI355X_MICROARCH.md, DVFS (7))
-// GNF: producer-side GroupNorm of the output (ConvParams::gnf_*; MS == 16 only)
 // SPK: in-place split-K instantiation (ConvParams::splits > 1; MS == 16, KS == 3). A template parameter, not a run-time
 // branch: with the split code compiled into the one kernel the register allocation of the unsplit K loop changed
 // (scratch 76 -> 430 bytes per lane) and EVERY x-halo conv ran 20 % slower (same box: 16.35 -> 19.29 ms per B = 64 step).
-template <int BM, int BN, int WGM, int WGN, int SEGMIN, int KS, int MS, bool GNF = false, bool SPK = false, bool F8C = false>
+template <int BM, int BN, int WGM, int WGN, int SEGMIN, int KS, int MS, bool SPK = false, bool F8C = false>
 __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) void conv3x3_halo_h3(const ConvParams p_in) {
-    static_assert(!F8C || (MS == 32 && KS == 3 && !GNF && !SPK), "fp8 correction products: 3x3 convs on the 32x32 consumers");
-    static_assert(!GNF || (MS == 16 && KS == 3), "producer-side GroupNorm: 3x3 convs on the 16x16x32 consumers");
-    static_assert(!SPK || (MS == 16 && KS == 3 && !GNF), "in-place split-K: 3x3 convs on the 16x16x32 consumers");
+    static_assert(!F8C || (MS == 32 && KS == 3 && !SPK), "fp8 correction products: 3x3 convs on the 32x32 consumers");
+    static_assert(!SPK || (MS == 16 && KS == 3), "in-place split-K: 3x3 convs on the 16x16x32 consumers");
     const ConvParams p = phase_params(p_in, blockIdx.z);
     static_assert(WGM * WGN == 4, "4 consumer waves per block");
     constexpr int WM = BM / WGM, WN = BN / WGN;
@@ -1117,27 +935,7 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
     const int tilesN = (Cout + BN - 1) / BN;
     const int nsplit = SPK ? p.splits : 1;     // in-place split-K (end of the consumer path)
     int bid = blockIdx.x;
-    if (GNF) {
-        // Block order of the producer-side GroupNorm: the blocks of one image must be dispatched together (they wait
-        // for each other), whole images per XCD so that no group straddles two XCDs' dispatch sequences.
-        //  band == 0 (an image is at most 32 blocks): XCD x = blockIdx.x & 7 takes images x, x + 8, ... one after the
-        //    other (the grid is padded to whole rounds of eight images; surplus blocks leave at once);
-        //  band > 0 (128x128-pixel level: 128 M-tiles per image): XCD x takes M-tiles [x * band, (x + 1) * band) of
-        //    EVERY image, images in order — an image is spread over the eight XCDs, band x tilesN blocks on each, and
-        //    neighbouring image rows still share an L2.
-        const int xcd = bid & 7, loc = bid >> 3, TMI = HWo / BM;
-        if (p.gnf_band > 0) {
-            const int per = p.gnf_band * tilesN;
-            const int image = loc / per, r = loc - image * per;
-            const int j = r / tilesN;
-            bid = (image * TMI + xcd * p.gnf_band + j) * tilesN + (r - j * tilesN);
-        } else {
-            const int per = TMI * tilesN;
-            const int image = (loc / per) * 8 + xcd;
-            if (image >= p.B) return;
-            bid = image * per + (loc % per);
-        }
-    } else if (SPK) {
+    if (SPK) {
         // split-K: the grid is (tiles padded to a multiple of 8) x splits in ONE dimension; XCD x = blockIdx.x & 7 takes
         // tiles [x * tpx, (x + 1) * tpx), the splits of a tile adjacent in its dispatch sequence — the blocks that wait
         // for each other at the end of the kernel are always dispatched together, whatever the tile count
@@ -1171,39 +969,30 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
 
     if (wid >= 4) {
         // ------------------------------- producer waves -------------------------------------
-#if defined(SR3_CONV_VARIANT) && SR3_CONV_VARIANT == 3
-        __builtin_amdgcn_s_setprio(1);      // experiment: the DMA waves win issue arbitration
-#endif
         const int w = wid - 4;
         const int tid = threadIdx.x - 256;
-        // Epilogue tables (row -> output pixel / image, column bias). They are not read before the epilogue, and the
-        // bias loads have a memory round trip of their own: with SR3_LATE_TABLES they are set up behind the DMAs of
-        // K-step 0 instead of in front of the first DMA (profiles/README.md finding 61).
-#ifndef SR3_LATE_TABLES
-#define SR3_LATE_TABLES 0
-#endif
-        auto setup_tables = [&]() {
-            if (tid < BM) {
-                const int m = min(m0 + tid, M - 1);
-                const int n = div_hw(p, m, HWo);
-                const int rem = m - n * HWo;
-                const int oy = div_w(p, rem, W);
-                rowpix[tid] = (int)p.out.pix(n, oy * p.out_step + p.out_oy, (rem - oy * W) * p.out_step + p.out_ox);
-                rowimg[tid] = n;
+        // Epilogue tables (row -> output pixel / image, column bias), set up in front of the first DMA: they are not read
+        // before the epilogue, but setting them up behind the DMAs of K-step 0 measured no faster (profiles/README.md
+        // finding 61).
+        if (tid < BM) {
+            const int m = min(m0 + tid, M - 1);
+            const int n = div_hw(p, m, HWo);
+            const int rem = m - n * HWo;
+            const int oy = div_w(p, rem, W);
+            rowpix[tid] = (int)p.out.pix(n, oy * p.out_step + p.out_oy, (rem - oy * W) * p.out_step + p.out_ox);
+            rowimg[tid] = n;
+        }
+        if constexpr (MS == 16 || F8C) {    // column bias of the epilogue, fetched now, read from LDS later
+            const int img_a = div_hw(p, m0, HWo), img_b = div_hw(p, min(m0 + BM - 1, M - 1), HWo);
+            const bool one = img_a == img_b;
+            if (tid < BN) {
+                const int nc = min(n0 + tid, Cout - 1);
+                float v = p.bias ? p.bias[nc] : 0.f;
+                if (p.chan_bias != nullptr && one) v += p.chan_bias[(size_t)img_a * p.chan_bias_stride + nc];
+                colbias[tid] = v;
             }
-            if constexpr (MS == 16 || F8C) {    // column bias of the epilogue, fetched now, read from LDS later
-                const int img_a = div_hw(p, m0, HWo), img_b = div_hw(p, min(m0 + BM - 1, M - 1), HWo);
-                const bool one = img_a == img_b;
-                if (tid < BN) {
-                    const int nc = min(n0 + tid, Cout - 1);
-                    float v = p.bias ? p.bias[nc] : 0.f;
-                    if (p.chan_bias != nullptr && one) v += p.chan_bias[(size_t)img_a * p.chan_bias_stride + nc];
-                    colbias[tid] = v;
-                }
-                if (tid == 0) reinterpret_cast<int *>(colbias)[BN] = one ? 1 : 0;
-            }
-        };
-        if constexpr (!SR3_LATE_TABLES) setup_tables();
+            if (tid == 0) reinterpret_cast<int *>(colbias)[BN] = one ? 1 : 0;
+        }
         const int rsub = lane >> 3;
         const unsigned schunk16 = (unsigned)(((lane & 7) ^ ((((w & 1) << 2) | (lane >> 4)) & 7)) * 16);
         const int Hp = p.in0.Hp(), Wp = p.in0.Wp();
@@ -1276,24 +1065,17 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
             static_for<TAPS>([&](auto tc) {
                 constexpr int tap = decltype(tc)::value;
                 constexpr int dy = tap / KS, dx = tap % KS;
-                const bool feed = !(SR3_DBG(p) & 1) || k == 0;      // experiment: operands only for the first K-step
-                // experiment bit 7 (timing only, results wrong): every other block issues no weight DMA after its first K-step —
-                // what the launch would cost if co-resident blocks SHARED their weight tiles (37 % fewer L2 bytes on a 128x128
-                // tile) without being tied to each other's barriers (profiles/README.md finding 72)
-                const bool feed_b = feed && (!(SR3_DBG(p) & 128) || !(blockIdx.x & 1) || k == 0);
                 // The B tile of this K-step goes out FIRST: the consumers wait for it at the very next barrier. The A
                 // halo group issued at dx == 1 is not read before the K-step after next, so it goes out behind the B
                 // tile and stays in flight across this K-step's barrier (counted wait: the wave's nh youngest DMAs).
                 float *Bd = Bring + (k & 1) * BSTG + w * 256;
                 const char *wb = wbase + (size_t)tap * tapstride * 4;
-                if (feed_b) {
-                    static_for<BR>([&](auto ic) {
-                        constexpr int i = decltype(ic)::value;
-                        dma16s<true>(wb, vB[i], Bd + i * 1024);
-                    });
-                }
+                static_for<BR>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value;
+                    dma16s<true>(wb, vB[i], Bd + i * 1024);
+                });
                 bool halo_now = false;
-                if (dx == 1 && feed) {  // the stage of group g-1 is free once K-step KS*g - 1 has been read
+                if (dx == 1) {  // the stage of group g-1 is free once K-step KS*g - 1 has been read
                     if (dy < KS - 1) {
                         SR3_ISSUE_HALO(c0, dy + 1)
                         halo_now = true;
@@ -1302,37 +1084,12 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
                         halo_now = true;
                     }
                 }
-#ifdef SR3_EXPERIMENTS
-                {   // experiment (profiles/README.md, GroupNorm-apply fusion): bits 8..15 = N dummy vector operations per
-                    // K-step in every producer lane (every 8th one a v_exp_f32), the VALU load an in-kernel
-                    // a*x+b / Swish / hi-lo split of the A tile would add next to the f16 MFMAs
-                    // eight independent chains (the real work has that much parallelism: ~17 elements per lane)
-                    const int nv = (p.dbg >> 8) & 0xFF;
-                    float z[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) z[u] = (float)(lane + u);
-                    for (int i = 0; i < nv; i += 8) {
-#pragma unroll
-                        for (int u = 0; u < 7; ++u) asm volatile("v_fma_f32 %0, %0, %1, %1" : "+v"(z[u]) : "v"(1.000001f));
-                        z[7] = __expf(z[7] * 1e-6f);
-                    }
-                    float zs = 0.f;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) zs += z[u];
-                    if (zs == 1234.5f) rowimg[0] = 1;     // keep the chains alive
-                }
-#endif
-                if constexpr (SR3_LATE_TABLES && tap == 0) {
-                    if (c0 == cb) setup_tables();
-                }
-                if (!(SR3_DBG(p) & 8)) {                            // experiment bit 3: no barriers (timing only)
-                    if (dx == 1 && halo_now) {
-                        static_for<ARH + 1>([&](auto nc) {
-                            if (nh == decltype(nc)::value) producer_sync<decltype(nc)::value>();
-                        });
-                    } else {
-                        producer_sync<0>();
-                    }
+                if (dx == 1 && halo_now) {
+                    static_for<ARH + 1>([&](auto nc) {
+                        if (nh == decltype(nc)::value) producer_sync<decltype(nc)::value>();
+                    });
+                } else {
+                    producer_sync<0>();
                 }
                 ++k;
             });
@@ -1365,10 +1122,6 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
             ++ga;
         }
         __syncthreads();
-        if constexpr (GNF) {
-            gnf_producer_tail<BM, BN, WGM * 4>(p, smem, m0, n0, HWo, tid);
-            return;
-        }
         // (in-place split-K: the consumer waves of the tile's last block write the statistics themselves)
         if (p.stats != nullptr && nsplit == 1) producer_stats_tail<BM, BN, WGM, MS == 16 ? 4 : 2>(p, smem, m0, n0, HWo);
         return;
@@ -1402,13 +1155,7 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
             rhalo[mt] = rplain[mt] + HALO * (rplain[mt] / SEG);
         }
         h16x8 ah[MT], al[MT], bqh[2], bql[2];
-#ifndef SR3_CONV_VARIANT
-#define SR3_CONV_VARIANT 1
-#endif
-#if SR3_CONV_VARIANT == 2
-        __builtin_amdgcn_s_setprio(1);      // consumers win issue arbitration against the DMA waves
-#endif
-        const float *aptr_h[MT], *aptr_l[MT];   // variant >= 1: fragment addresses of the NEXT K-step, computed early
+        const float *aptr_h[MT], *aptr_l[MT];   // fragment addresses of the NEXT K-step, computed early
         // ONESEG: the WM rows of a wave lie in one row segment (SEG is a power of two >= SEGMIN), so row tile mt
         // is tile 0 + 16 * mt ring rows with the same swizzle term: one address pair per K-step, the other row
         // tiles are constant offsets of the reads (half the address arithmetic, two registers less)
@@ -1459,15 +1206,7 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) SR3_AREAD(mt, 0)
         SR3_BREAD(0, 0, 0)
-#ifdef SR3_EXPERIMENTS
-        // timing experiments (results are wrong): bit 2 no fragment reads after the first K-step,
-        // bit 3 no barriers, bit 4 no MFMAs
-        const bool x_rd = !(p.dbg & 4), x_bar = !(p.dbg & 8), x_mma = !(p.dbg & 16);
-#else
-        constexpr bool x_rd = true, x_bar = true, x_mma = true;
-#endif
         int kt = 0;
-#if SR3_CONV_VARIANT >= 1
         if constexpr (ONESEG) {
             // Halo-phase K loop WITHOUT address arithmetic. The fragment addresses of K-step kt = KS g + dx depend on kt
             // through (B stage kt & 1, A stage g & 1, row shift dx) only: a pattern of period 2 KS. The loop is unrolled
@@ -1527,10 +1266,8 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
             // pattern loop at all; same box, three alternating pairs each.)
             for (; kt + PER < nkh; kt += PER) static_for<PER>([&](auto uc) { kstep(uc); });
         }
-#endif
         for (; kt < nk; ++kt) {
             const int kn = min(kt + 1, nk - 1);     // after the last K-step: re-read, unused
-#if SR3_CONV_VARIANT >= 1
             // the next K-step's A addresses are computed in the shadow of the first columns' MFMAs and
             // the reads are pinned right behind the last MFMA that uses each fragment (left to itself
             // the scheduler sinks address arithmetic and reads to the top of the next iteration, in
@@ -1555,21 +1292,6 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
                 SR3_AREAD2(mt)
                 __builtin_amdgcn_sched_barrier(0);
             }
-#else
-#pragma unroll
-            for (int nt = 0; nt < NT - 1; ++nt) {
-                if (x_rd) SR3_BREAD((nt + 1) & 1, nt + 1, kt)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) if (x_mma) SR3_MMA16(mt, nt, nt & 1)
-            }
-            if (x_bar) __syncthreads();             // every read of K-step kt has been issued and waited
-            if (x_rd) SR3_BREAD(0, 0, kn)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                if (x_mma) SR3_MMA16(mt, NT - 1, (NT - 1) & 1)
-                if (x_rd) SR3_AREAD(mt, kn)
-            }
-#endif
         }
 #undef SR3_AREAD
 #undef SR3_AREAD2
@@ -1614,7 +1336,7 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
                     while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)nsplit) {
                         __builtin_amdgcn_s_sleep(8);
                         if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > SR3_WAIT_TICKS) {
-                            if (p.ovf != nullptr) atomicOr(p.ovf, SR3_FLAG_GNF_TIMEOUT);
+                            if (p.ovf != nullptr) atomicOr(p.ovf, SR3_FLAG_WAIT_TIMEOUT);
                             break;
                         }
                     }
@@ -1694,8 +1416,8 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[mt][nt][r] *= p.w_unscale;
-        conv_epilogue16<BM, BN, WGM, WGN, MT, NT, false, GNF>(p, acc, smem, rowpix, rowimg, m0, n0, M, wm, wn, l16, q, colbias,
-                                                              reinterpret_cast<const int *>(colbias)[BN] != 0);
+        conv_epilogue16<BM, BN, WGM, WGN, MT, NT>(p, acc, smem, rowpix, rowimg, m0, n0, M, wm, wn, l16, q, colbias,
+                                                  reinterpret_cast<const int *>(colbias)[BN] != 0);
         return;
     }
     const int li = lane & 31, lh = lane >> 5;
@@ -1818,418 +1540,12 @@ __global__ __launch_bounds__(512, (BN == 64 && MS == 16 && BM == 128) ? 6 : 4) v
         conv_epilogue<BM, BN, WGM, WGN, MI, NI>(p, acc, smem, rowpix, rowimg, m0, n0, M, wm, wn, li, lh, 0, 1);
 }
 
-#ifdef SR3_EXPERIMENTS
-// =================================================================================================
-// EXPERIMENT (libsr3hip_exp.so only, SR3_PERSIST=1; results are correct — the conv / UNet / sampler GPU tests
-// pass with it — but it is 1.4x SLOWER than the one-tile kernel: 0.35 vs 0.25 ms on the 128x128-pixel
-// 64-channel conv, +1.0 ms per B=64 step; profiles/README.md finding 38). Kept as the measured record of
-// the "hide the tile prologue behind the previous epilogue" idea.
-// Persistent form of the x-halo kernel (16x16x32 consumers, four waves stacked along M): a block walks
-// over tiles v = blockIdx.x, + gridDim.x, ... . What it buys: while the consumer waves run the epilogue
-// of tile i, the producer waves set up tile i + 1 (tables, addresses) and put its first A halo group
-// and first B tile in flight — the LDS rings are free once the last K-step of tile i has been read —
-// so a tile's launch / set-up / first-DMA latency (10 % of a 128x128-pixel, 64-channel conv) hides
-// behind the previous epilogue. What makes it fit the same registers and LDS as the one-tile kernel:
-// the consumer state is tile independent (fragment row offsets depend on the lane only), the per-tile
-// tables are double-buffered (1.3 KB), and the statistics hand-off is reduced over the four row groups
-// of a wave by lane exchange, so it fits B stage 1 (free between two tiles) instead of a region of its own.
-// Barriers per tile, identical on both sides: nk K-step barriers + F (end of K loop) + E (statistics
-// staged; only with fused statistics). The consumers' first barrier of a tile is the producers' K-step-0
-// barrier of that tile.
-// =================================================================================================
-template <int BM, int BN, int SEGMIN, int KS>
-__global__ __launch_bounds__(512, (BN == 64) ? 6 : 4) void conv3x3_halo_pt(const ConvParams p_in, const int ntiles,
-                                                                             const int stagger) {
-    const ConvParams p = phase_params(p_in, blockIdx.z);
-    // Resident blocks of a CU that start together and walk over equal tiles stay in lockstep: all in their K
-    // loops, then all in their epilogues (MI355X_MICROARCH.md, "try a stagger"). The k-th wave of blocks
-    // (blockIdx.x / stagger_group) starts k * stagger shader cycles late so the phases interleave.
-    if (stagger > 0) {
-        const int late = (blockIdx.x / (gridDim.x / 3 > 0 ? gridDim.x / 3 : 1)) * stagger;
-        const long long t0 = __builtin_amdgcn_s_memtime();
-        while (__builtin_amdgcn_s_memtime() - t0 < late) __builtin_amdgcn_s_sleep(16);
-    }
-    constexpr int WGM = 4, WGN = 1;
-    constexpr int WM = BM / WGM, WN = BN / WGN;
-    constexpr int AR = BM / 32, BR = BN / 32;
-    constexpr int HALO = KS - 1, TAPS = KS * KS;
-    constexpr int RA = (BM + HALO * (BM / SEGMIN) + 7) / 8 * 8;
-    constexpr int ARH = (RA / 8 + 3) / 4;
-    constexpr int ASTG = RA * ROWF, BSTG = BN * ROWF;
-    constexpr int MT = WM / 16, NT = WN / 16;
-    constexpr int TBL = 2 * BM + BN + 4;            // ints / floats of the epilogue tables: rowpix | rowimg | colbias + flag
-    static_assert((NT % 2) == 0 && (RA % 8) == 0, "tile shape");
-    static_assert((size_t)WGM * BN * sizeof(double2) <= (size_t)BSTG * sizeof(float), "statistics staging fits one B stage");
-
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *Aring = smem;                    // [2][RA][32]
-    float *Bring = smem + 2 * ASTG;         // [2][BN][32]
-    float *tables = smem + 2 * ASTG + 2 * BSTG;     // [TBL], ONE set (a second one would cost the third block per CU: LDS is
-                                                    // allocated in 1280-B granules): written by the producers right behind a
-                                                    // tile's K-step-0 barrier, when every consumer has left the previous epilogue
-    float *stat_stage = Bring + BSTG;       // B stage 1: free from the end of a tile's K loop to K-step 1 of the next
-
-    const int C0 = p.in0.C, C1 = p.in1.p ? p.in1.C : 0;
-    const int Cin = C0 + C1;
-    const int Cout = p.out.C;
-    const int W = p.Wout;
-    const int HWo = p.Hout * W;
-    const int M = p.B * HWo;
-    const int tilesN = Cout / BN;
-    const int SEG = min(W, BM), SEGP = SEG + HALO, nseg = BM / SEG;
-    const int rows_a = nseg * SEGP;
-    const int nkh = TAPS * (Cin / BK);
-    const int C2a = p.in2.p ? p.in2.C : 0, C2 = C2a + (p.in2b.p ? p.in2b.C : 0);
-    const int nk = nkh + C2 / BK;
-    const int G = nkh / KS;
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const bool has_stats = p.stats != nullptr;
-    // XCD-aware order of the virtual tile ids (speed only): ids v and v + 8 run on one XCD
-    auto tile_of = [&](int v, int &m0, int &n0) {
-        const int xcd = v & 7, loc = v >> 3, qq = ntiles >> 3, rr = ntiles & 7;
-        const int bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + loc;
-        m0 = (bid / tilesN) * BM;
-        n0 = (bid % tilesN) * BN;
-    };
-
-    if (wid >= 4) {
-        // ------------------------------- producer waves -------------------------------------
-        const int w = wid - 4;
-        const int tid = threadIdx.x - 256;
-        const int rsub = lane >> 3;
-        const unsigned schunk16 = (unsigned)(((lane & 7) ^ ((((w & 1) << 2) | (lane >> 4)) & 7)) * 16);
-        const int Hp = p.in0.Hp(), Wp = p.in0.Wp();
-        const size_t tapstride = (size_t)Cout * Cin;
-        unsigned vH0[ARH], vH1[ARH], vB[BR], vB2[BR], vA2[AR], vA2b[AR];
-        int m0 = 0, n0 = 0;
-        // epilogue tables of tile (tm0, tn0)
-        auto setup_tables = [&](int tm0, int tn0) {
-            int *rowpix = reinterpret_cast<int *>(tables);
-            int *rowimg = rowpix + BM;
-            float *colbias = reinterpret_cast<float *>(rowimg + BM);
-            const int m0 = tm0, n0 = tn0;
-            if (tid < BM) {
-                const int m = min(m0 + tid, M - 1);
-                const int n = div_hw(p, m, HWo);
-                const int rem = m - n * HWo;
-                const int oy = div_w(p, rem, W);
-                rowpix[tid] = (int)p.out.pix(n, oy * p.out_step + p.out_oy, (rem - oy * W) * p.out_step + p.out_ox);
-                rowimg[tid] = n;
-            }
-            {
-                const int img_a = div_hw(p, m0, HWo), img_b = div_hw(p, min(m0 + BM - 1, M - 1), HWo);
-                const bool one = img_a == img_b;
-                if (tid < BN) {
-                    const int nc = min(n0 + tid, Cout - 1);
-                    float v = p.bias ? p.bias[nc] : 0.f;
-                    if (p.chan_bias != nullptr && one) v += p.chan_bias[(size_t)img_a * p.chan_bias_stride + nc];
-                    colbias[tid] = v;
-                }
-                if (tid == 0) reinterpret_cast<int *>(colbias)[BN] = one ? 1 : 0;
-            }
-        };
-        // DMA addresses of tile (m0, n0)
-        auto setup = [&]() {
-            static_for<ARH>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                const int R = (4 * i + w) * 8 + rsub;
-                int sg = R / SEGP, jx = R - sg * SEGP;
-                if (sg >= nseg) { sg = nseg - 1; jx = 0; }
-                const int m = m0 + sg * SEG;
-                const int n = div_hw(p, m, HWo);
-                const int rem = m - n * HWo;
-                const int y = div_w(p, rem, W), x0 = rem - y * W;
-                const unsigned pix = (unsigned)((n * Hp + y + p.org_y) * Wp + x0 + jx + p.org_x);
-                vH0[i] = pix * (unsigned)C0 * 4u + schunk16;
-                vH1[i] = pix * (unsigned)C1 * 4u + schunk16;
-            });
-            static_for<BR>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                const int n = min(n0 + (4 * i + w) * 8 + rsub, Cout - 1);
-                vB[i] = (unsigned)n * (unsigned)Cin * 4u + schunk16;
-                vB2[i] = (unsigned)n * (unsigned)C2 * 4u + schunk16;
-            });
-            static_for<AR>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                const int m = min(m0 + (4 * i + w) * 8 + rsub, M - 1);
-                const int n = div_hw(p, m, HWo);
-                const int rem = m - n * HWo;
-                const int oy = div_w(p, rem, W);
-                vA2[i] = C2 ? (unsigned)p.in2.pix(n, oy, rem - oy * W) * (unsigned)C2a * 4u + schunk16 : 0u;
-                vA2b[i] = C2 > C2a ? (unsigned)p.in2b.pix(n, oy, rem - oy * W) * (unsigned)(C2 - C2a) * 4u + schunk16 : 0u;
-            });
-        };
-        int ga = 0;
-#define SR3_ISSUE_HALO(C0A, DY)                                                                    \
-    {                                                                                              \
-        const int c0a_ = (C0A);                                                                    \
-        const bool first_ = c0a_ < C0;                                                             \
-        const int Cs_ = first_ ? C0 : C1;                                                          \
-        const char *ab_ = reinterpret_cast<const char *>((first_ ? p.in0.p : p.in1.p) + (first_ ? c0a_ : c0a_ - C0)) + \
-                          (size_t)(DY) * Wp * Cs_ * 4;                                             \
-        float *Ad_ = Aring + (ga & 1) * ASTG + w * 256;                                            \
-        /* (a uniform branch instead of a per-lane select of the offset in front of every DMA) */   \
-        if (first_) {                                                                              \
-            static_for<ARH>([&](auto ic) {                                                         \
-                constexpr int i = decltype(ic)::value;                                             \
-                if ((4 * i + w) * 8 < rows_a) dma16s<true>(ab_, vH0[i], Ad_ + i * 1024);                 \
-            });                                                                                    \
-        } else {                                                                                   \
-            static_for<ARH>([&](auto ic) {                                                         \
-                constexpr int i = decltype(ic)::value;                                             \
-                if ((4 * i + w) * 8 < rows_a) dma16s<true>(ab_, vH1[i], Ad_ + i * 1024);                 \
-            });                                                                                    \
-        }                                                                                          \
-        ++ga;                                                                                      \
-    }
-        // first operands of a tile: halo group (chunk 0, dy 0) into A stage 0, B tile of K-step 0 into B stage 0
-        auto issue_first = [&]() {
-            ga = 0;
-            SR3_ISSUE_HALO(0, 0)
-            const char *wb = reinterpret_cast<const char *>(p.w);
-            float *Bd = Bring + w * 256;
-            static_for<BR>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                dma16s<true>(wb, vB[i], Bd + i * 1024);
-            });
-        };
-        int v = blockIdx.x;
-        if (v < ntiles) {
-            tile_of(v, m0, n0);
-            setup();
-            issue_first();
-        }
-        for (; v < ntiles; v += gridDim.x) {
-            const int m0_cur = m0, n0_cur = n0;
-            int k = 0;
-            for (int c0 = 0; c0 < Cin; c0 += BK) {
-                const char *wbase = reinterpret_cast<const char *>(p.w + c0);
-                static_for<TAPS>([&](auto tc) {
-                    constexpr int tap = decltype(tc)::value;
-                    constexpr int dy = tap / KS, dx = tap % KS;
-                    if (dx == 1) {          // the stage of group g-1 is free once K-step KS*g - 1 has been read
-                        if (dy < KS - 1) {
-                            SR3_ISSUE_HALO(c0, dy + 1)
-                        } else if (c0 + BK < Cin) {
-                            SR3_ISSUE_HALO(c0 + BK, 0)
-                        }
-                    }
-                    if (k > 0) {            // (K-step 0's B tile went out with the tile's first operands)
-                        float *Bd = Bring + (k & 1) * BSTG + w * 256;
-                        const char *wb = wbase + (size_t)tap * tapstride * 4;
-                        static_for<BR>([&](auto ic) {
-                            constexpr int i = decltype(ic)::value;
-                            dma16s<true>(wb, vB[i], Bd + i * 1024);
-                        });
-                    }
-                    producer_sync<0>();
-                    if (k == 0) setup_tables(m0_cur, n0_cur);
-                    ++k;
-                });
-            }
-            // fused 1x1 term: plain BM-row A tiles continue in the A ring
-            for (int c0 = 0; c0 < C2; c0 += BK) {
-                float *Ad = Aring + (ga & 1) * ASTG + w * 256;
-                float *Bd = Bring + (k & 1) * BSTG + w * 256;
-                const bool first2 = c0 < C2a;
-                const char *ab = reinterpret_cast<const char *>(first2 ? p.in2.p + c0 : p.in2b.p + (c0 - C2a));
-                const char *wb = reinterpret_cast<const char *>(p.w2 + c0);
-                if (first2) {
-                    static_for<AR>([&](auto ic) {
-                        constexpr int i = decltype(ic)::value;
-                        dma16s<true>(ab, vA2[i], Ad + i * 1024);
-                    });
-                } else {
-                    static_for<AR>([&](auto ic) {
-                        constexpr int i = decltype(ic)::value;
-                        dma16s<true>(ab, vA2b[i], Ad + i * 1024);
-                    });
-                }
-                static_for<BR>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value;
-                    dma16s<true>(wb, vB2[i], Bd + i * 1024);
-                });
-                producer_sync<0>();
-                ++k;
-                ++ga;
-            }
-            producer_sync<0>();             // F: the consumers have read the last K-step
-            // next tile: tables, addresses and first operands while the consumers run this tile's epilogue
-            const int vn = v + gridDim.x;
-            if (vn < ntiles) {
-                tile_of(vn, m0, n0);
-                setup();
-                issue_first();
-            }
-            if (has_stats) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();               // E: this tile's column sums are staged (not a DMA wait)
-                const double2 *red = reinterpret_cast<const double2 *>(stat_stage);
-                if (tid < BN) {
-                    double a = 0, b = 0;
-#pragma unroll
-                    for (int j = 0; j < WGM; ++j) { const double2 t2 = red[j * BN + tid]; a += t2.x; b += t2.y; }
-                    const int n = m0_cur / HWo, slice = p.stats_slice0 + (m0_cur - n * HWo) / BM;
-                    double *o = p.stats + (((size_t)n * p.stats_slices + slice) * Cout + n0_cur + tid) * 2;
-                    o[0] = a; o[1] = b;
-                }
-            }
-        }
-#undef SR3_ISSUE_HALO
-        return;
-    }
-
-    // ----------------------------------- consumer waves -----------------------------------------
-    const int l16 = lane & 15, q = lane >> 4;
-    const int wm = wid, wn = 0;
-    const int swzB = (l16 >> 1) & 7;
-    const float *Bbase = Bring + (wn * WN + l16) * ROWF;
-    const int bho = ((q ^ swzB) & 7) * 4, blo = (((4 + q) ^ swzB) & 7) * 4;
-    static_assert(SEGMIN % WM == 0, "a wave's rows lie in one row segment");
-    const int rplain0 = wm * WM + l16;
-    const int rhalo0 = rplain0 + HALO * (rplain0 / SEG);
-    for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
-        int m0, n0;
-        tile_of(v, m0, n0);
-        f32x4 acc[MT][NT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[mt][nt][r] = 0.f;
-        h16x8 ah[MT], al[MT], bqh[2], bql[2];
-        const float *aptr_h, *aptr_l;
-        // (SEGMIN >= WM: the WM rows of a wave lie in one row segment, so row tile mt is tile 0 + 16 * mt ring
-        // rows with the same swizzle term — one address pair per K-step, the other tiles are constant offsets)
-#define SR3_AADDR(MTI, KT)                                                                         \
-    if ((MTI) == 0) {                                                                              \
-        const int kt_ = (KT);                                                                      \
-        const bool halo_ = kt_ < nkh;                                                              \
-        const int g_ = kt_ / KS;                                                                   \
-        const int astage_ = halo_ ? (g_ & 1) : ((G + kt_ - nkh) & 1);                              \
-        const int R_ = halo_ ? rhalo0 + (kt_ - KS * g_) : rplain0;                                 \
-        const int sw_ = (R_ >> 1) & 7;                                                             \
-        const float *Ar_ = Aring + astage_ * ASTG + R_ * ROWF;                                     \
-        aptr_h = Ar_ + ((q ^ sw_) & 7) * 4;                                                        \
-        aptr_l = Ar_ + (((4 + q) ^ sw_) & 7) * 4;                                                  \
-    }
-#define SR3_AREAD2(MTI)                                                                            \
-    {                                                                                              \
-        ah[MTI] = *reinterpret_cast<const h16x8 *>(aptr_h + (MTI) * 16 * ROWF);                    \
-        al[MTI] = *reinterpret_cast<const h16x8 *>(aptr_l + (MTI) * 16 * ROWF);                    \
-    }
-#define SR3_BREAD(BUF, NTI, KT)                                                                    \
-    {                                                                                              \
-        const float *Bb_ = Bbase + ((KT) & 1) * BSTG + (NTI) * 16 * ROWF;                          \
-        bqh[BUF] = *reinterpret_cast<const h16x8 *>(Bb_ + bho);                                    \
-        bql[BUF] = *reinterpret_cast<const h16x8 *>(Bb_ + blo);                                    \
-    }
-#define SR3_MMA16(MTI, NTI, BUF)                                                                   \
-    {                                                                                              \
-        acc[MTI][NTI] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[MTI], bqh[BUF], acc[MTI][NTI], 0, 0, 0); \
-        acc[MTI][NTI] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[MTI], bql[BUF], acc[MTI][NTI], 0, 0, 0); \
-        acc[MTI][NTI] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[MTI], bqh[BUF], acc[MTI][NTI], 0, 0, 0); \
-    }
-        __syncthreads();                            // K-step 0 of this tile has landed
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) { SR3_AADDR(mt, 0) SR3_AREAD2(mt) }
-        SR3_BREAD(0, 0, 0)
-        for (int kt = 0; kt < nk; ++kt) {
-            const int kn = min(kt + 1, nk - 1);     // after the last K-step: re-read, unused
-#pragma unroll
-            for (int nt = 0; nt < NT - 1; ++nt) {
-                SR3_BREAD((nt + 1) & 1, nt + 1, kt)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) SR3_MMA16(mt, nt, nt & 1)
-                if (nt == 0) {
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) SR3_AADDR(mt, kn)
-                }
-            }
-            __syncthreads();
-            SR3_BREAD(0, 0, kn)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                SR3_MMA16(mt, NT - 1, (NT - 1) & 1)
-                __builtin_amdgcn_sched_barrier(0);
-                SR3_AREAD2(mt)
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#undef SR3_AADDR
-#undef SR3_AREAD2
-#undef SR3_BREAD
-#undef SR3_MMA16
-        // The epilogue re-reads its parameters from the kernel-argument segment through a pointer the optimiser
-        // cannot see through: otherwise ~15 pointers / scalars are hoisted out of the tile loop, stay live across
-        // the K loop, and the 80-register budget of this tile shape spills inside the K loop. (KS == 3: no
-        // sub-pixel phases, so the phase-adjusted copy equals the argument itself.)
-        typedef const unsigned __attribute__((address_space(4))) *KArgW;
-        typedef unsigned __attribute__((may_alias)) AliasWord;      // (the copy is read back as floats and pointers)
-        KArgW pq = (KArgW)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(pq));
-        ConvParams pl;
-        static_assert(sizeof(ConvParams) % 4 == 0, "word copy");
-#pragma unroll
-        for (int i = 0; i < (int)(sizeof(ConvParams) / 4); ++i) reinterpret_cast<AliasWord *>(&pl)[i] = pq[i];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[mt][nt][r] *= pl.w_unscale;
-        const int *rowpix = reinterpret_cast<const int *>(tables);
-        const int *rowimg = rowpix + BM;
-        const float *colbias = reinterpret_cast<const float *>(rowimg + BM);
-        // (same for the lane-derived offsets of the epilogue: made opaque per tile so they are recomputed here
-        // instead of being carried through the K loop)
-        int l16e = l16, qe = q;
-        asm volatile("" : "+v"(l16e), "+v"(qe));
-        conv_epilogue16<BM, BN, WGM, WGN, MT, NT, true>(pl, acc, stat_stage, rowpix, rowimg, m0, n0, M, wm, wn, l16e, qe, colbias,
-                                                        reinterpret_cast<const int *>(colbias)[BN] != 0);
-        if (has_stats) __syncthreads();             // E: column sums staged for the producer threads
-    }
-}
-
-template <int BM, int BN, int SEGMIN, int KS>
-void launch_halo_pt(const ConvParams &p, hipStream_t s) {
-    static bool attr_set = false;
-    static int cus = 0;
-    constexpr int RA = (BM + (KS - 1) * (BM / SEGMIN) + 7) / 8 * 8;
-    constexpr size_t lds = ((size_t)2 * RA * ROWF + 2 * BN * ROWF + 2 * BM + BN + 4) * sizeof(float);
-    auto kern = conv3x3_halo_pt<BM, BN, SEGMIN, KS>;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int dev = 0;
-        hipDeviceProp_t prop;
-        (void)hipGetDevice(&dev);
-        cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        attr_set = true;
-    }
-    const int M = p.B * p.Hout * p.Wout;
-    const int ntiles = (M / BM) * (p.out.C / BN);
-    // resident blocks per CU: LDS comes in 1280-byte granules (160 KiB = 128 of them)
-    const int granules = ((int)lds + 1279) / 1280;
-    const int per_cu = std::min(128 / granules, BN == 64 ? 3 : 2);
-    int grid = cus * per_cu;
-    if (grid > ntiles) grid = ntiles;
-    static const int stagger = exp_int("SR3_PT_STAGGER", 0);
-    hipLaunchKernelGGL(kern, dim3(grid, 1, p.phases), dim3(512), lds, s, p, ntiles, stagger);
-}
-
-#endif  // SR3_EXPERIMENTS
-
-template <int BM, int BN, int WGM, int WGN, int SEGMIN, int KS, int MS, bool GNF = false, bool SPK = false, bool F8C = false>
+template <int BM, int BN, int WGM, int WGN, int SEGMIN, int KS, int MS, bool SPK = false, bool F8C = false>
 void launch_halo(const ConvParams &p, hipStream_t s) {
     static bool attr_set = false;
     constexpr int RA = (BM + (KS - 1) * (BM / SEGMIN) + 7) / 8 * 8;
     constexpr size_t lds = ((size_t)2 * RA * ROWF + 2 * BN * ROWF + 2 * BM + BN + 4) * sizeof(float);
-    // (the GroupNorm hand-off stages its sums, scale / shift and the fold scratch in the rings, free after the K loop)
-    static_assert(!GNF || ((size_t)WGM * 4 * BN * 16 + BN * 8 + 4096 + 16 <= ((size_t)2 * RA * ROWF + 2 * BN * ROWF) * sizeof(float)), "GNF staging fits the rings");
-    auto kern = conv3x3_halo_h3<BM, BN, WGM, WGN, SEGMIN, KS, MS, GNF, SPK, F8C>;
+    auto kern = conv3x3_halo_h3<BM, BN, WGM, WGN, SEGMIN, KS, MS, SPK, F8C>;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2237,26 +1553,9 @@ void launch_halo(const ConvParams &p, hipStream_t s) {
     }
     const int M = p.B * p.Hout * p.Wout;
     int grid = (M / BM) * ((p.out.C + BN - 1) / BN);
-    if (GNF && p.gnf_band == 0) grid = (p.B + 7) / 8 * 8 * ((p.Hout * p.Wout) / BM) * (p.out.C / BN);   // whole rounds of eight images
     if (SPK) grid = (grid + 7) / 8 * 8 * p.splits;     // in-place split-K: see the kernel's block order
     hipLaunchKernelGGL(kern, dim3(grid, 1, p.phases), dim3(512), lds, s, p);
 }
-
-// consumer MFMA shape of the halo kernels: 16x16x32 with the four consumer waves stacked along M
-// (wave tile 32 x BN: all A fragments of a K-step are 4 registers x 4, the B columns stream through
-// two buffers); SR3_MFMA16=0 selects the 32x32x16 consumers (2 x 2 wave grid) for A/B measurements
-static bool halo_mfma16() {
-    static const int v = exp_int("SR3_MFMA16", 1);
-    return v != 0;
-}
-
-#ifdef SR3_EXPERIMENTS
-// persistent-tile form of the halo kernel (conv3x3_halo_pt, experiment): SR3_PERSIST=1
-static bool halo_persistent() {
-    static const int v = exp_int("SR3_PERSIST", 0);
-    return v != 0;
-}
-#endif
 
 // SR3_NO_HALO=1 (product safety switch): no x-halo kernel anywhere — and therefore no F8C path and no halo split-K
 static bool halo_off() {
@@ -2407,8 +1706,6 @@ int splitk_stats_slices(int HWo, int Cout) {
 
 // tile choice: 0 = 128x32, 1 = 128x64, 2 = 64x64, 3 = 128x128
 static int conv_tile_choice(long M, int Cout) {
-    static const int force = exp_int("SR3_CONV_TILE", -1);   // experiments build only
-    if (force >= 0) return force;
     auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((Cout + bn - 1) / bn); };
     const long want = 512;  // 256 CUs x 2 resident blocks
     if (Cout <= 32) return 0;
@@ -2420,15 +1717,13 @@ static int conv_tile_choice(long M, int Cout) {
 int conv_tile_m(long M, int Cout) { return conv_tile_choice(M, Cout) == 2 ? 64 : 128; }
 
 int conv_splits(long M, int Cout, int Cin) {
-    static const int off = exp_int("SR3_NO_SPLITK", 0);
-    if (off || (Cout & 3)) return 1;
-    if (const int f = exp_int("SR3_FORCE_SPLITS", 0)) return f;
+    if (Cout & 3) return 1;
     static const int bm[4] = {128, 128, 64, 128}, bn[4] = {32, 64, 64, 128};
     const int t = conv_tile_choice(M, Cout);
     const long tiles = ((M + bm[t] - 1) / bm[t]) * ((Cout + bn[t] - 1) / bn[t]);
     const int nchunk = Cin / BK;
     // (tuned on B = 1 at 128x128 and config 1, with the in-place fix-up: profiles/README.md finding 42)
-    const int tmin = exp_int("SR3_SPLIT_TMIN", 256), target = exp_int("SR3_SPLIT_TARGET", 256), chmin = exp_int("SR3_SPLIT_CHMIN", 2);
+    constexpr int tmin = 256, target = 256, chmin = 2;
     if (tiles >= tmin || nchunk < 2 * chmin) return 1;
     int s = 2;
     while (s * 2 <= nchunk / chmin && tiles * s * 2 <= target && s < 16) s *= 2;
@@ -2443,7 +1738,7 @@ int conv_splits(long M, int Cout, int Cin) {
 // Assumes ks 3, stride 1, prec 1, pad 1 (launch_conv checks them); sr3_api.hip sizes the partial buffer with it.
 int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
     static const int force = env_int("SR3_HALO_SPLITS", -1);    // product switch: 0 off, 2 | 4 forced
-    if (force == 0 || halo_off() || !halo_mfma16()) return 0;
+    if (force == 0 || halo_off()) return 0;
     const int HWo = H * W;
     if (W < 8 || (M % 128) || (Cout % 128) || (Cin % 32)) return 0;
     const int seg = W < 128 ? W : 128;
@@ -2464,12 +1759,11 @@ int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
 // 14-20 % faster than the f16x3 kernel (profiles/README.md finding 64); the 64x64- and 128x128-pixel levels are bound by
 // operand movement and gain nothing. Mirrors launch_conv's choice: callers format the conv's input accordingly.
 bool conv_f8_supported(int B, int H, int W, int Cout, int Cin) {
-    static const int off = exp_int("SR3_NO_F8C", 0);
-    static const int maxhw = exp_int("SR3_F8C_MAX_HW", 1024);
+    constexpr int maxhw = 1024;         // pixels of one image: the 32x32 level and below
     if (halo_off()) return false;            // (the F8C consumers exist in the x-halo kernel only)
     const long M = (long)B * H * W;
     const int HWo = H * W;
-    if (off || (Cin % 32) || (Cout % 128) || (M % 128) || HWo > maxhw || HWo < 128 || (HWo % 128)) return false;
+    if ((Cin % 32) || (Cout % 128) || (M % 128) || HWo > maxhw || HWo < 128 || (HWo % 128)) return false;
     const int seg = W < 128 ? W : 128;
     if (seg < 8 || (W % seg) || (128 % seg)) return false;
     if (conv_tile_choice(M, Cout) != 3) return false;
@@ -2486,54 +1780,6 @@ bool conv_split_inplace(long M, int HWo, int Cout, int Cin, int phases) {
     // (nothing is masked in the fix-up), and a counter for every tile
     return t == 2 && (HWo % bm[t]) == 0 && (Cout % bn[t]) == 0 && tiles * phases <= CONV_TILE_COUNTERS;
 }
-
-// Producer-side GroupNorm (ConvParams::gnf_*): which halo kernel would run it — 0 none, 1 the 128x64 tile, 2 the 128x128
-// tile with row segments of 32+ pixels, 3 the 128x128 tile with shorter segments.
-// EXPERIMENT (libsr3hip_exp.so, SR3_GNF=1 [SR3_GNF_MAX_HW=pixels]): correct (all sampler / UNet / full-size tests pass with
-// it) but it does not pay — the cross-CU hand-off costs a block about what the saved apply pass costs the chip
-// (profiles/README.md finding 54), and its liveness rests on the observed dispatch order. The product library never
-// takes this path.
-static int gnf_kernel_choice(const ConvParams &p, int groups) {
-#ifndef SR3_EXPERIMENTS
-    (void)p; (void)groups;
-    return 0;
-#else
-    static const int on = exp_int("SR3_GNF", 0);
-    if (!on || !halo_mfma16() || p.prec != 1 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases > 1 || groups <= 0) return 0;
-    if (p.resid.p != nullptr || p.in2.p != nullptr || p.stats == nullptr) return 0;
-    const int Cout = p.out.C, HWo = p.Hout * p.Wout;
-    const long M = (long)p.B * HWo;
-    if ((Cout % groups) != 0 || (HWo % 128) != 0) return 0;             // whole 128-row tiles inside one image
-    const int cg = Cout / groups;
-    const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
-    if (conv_splits(M, Cout, Cin) > 1) return 0;
-    int which = 0, bn = 0;
-    switch (conv_tile_choice(M, Cout)) {
-    case 1: if (halo_ok(p, 128, 32, 64)) { which = 1; bn = 64; } break;
-    case 3:
-        if (halo_ok(p, 128, 32, 128)) { which = 2; bn = 128; }
-        else if (halo_ok(p, 128, 8, 128)) { which = 3; bn = 128; }
-        break;
-    default: break;
-    }
-    if (!which || (bn % cg) != 0 || p.stats_slices != HWo / 128) return 0;
-    if ((long)p.B * (Cout / bn) > CONV_GNF_COUNTERS) return 0;
-    static const int max_hw = exp_int("SR3_GNF_MAX_HW", 1 << 30);   // A/B: only images of at most this many pixels
-    if (HWo > max_hw) return 0;
-    // every (image, N-tile) group of TMI blocks must be able to be resident together: the standard block order keeps an
-    // image's TMI x tilesN blocks on one XCD (32 CUs x 2 blocks at least); larger images use the band order, which
-    // needs TMI to divide over the eight XCDs and a grid the round-robin deals evenly
-    const int TMI = HWo / 128, tilesN = Cout / bn;
-    if (TMI * tilesN > 32 && (TMI % 8) != 0) return 0;
-    if (TMI * tilesN > 32 && (TMI / 8) * tilesN > 32) return 0;
-    return which;
-#endif
-}
-static int gnf_band_for(const ConvParams &p, int which) {
-    const int HWo = p.Hout * p.Wout, TMI = HWo / 128, tilesN = p.out.C / (which == 1 ? 64 : 128);
-    return TMI * tilesN > 32 ? TMI / 8 : 0;
-}
-bool conv_gnf_supported(const ConvParams &p, int groups) { return gnf_kernel_choice(p, groups) != 0; }
 
 // first launch request of this thread that could not be honoured (nothing was launched for it); the API entry points
 // turn it into an error return (conv_take_error)
@@ -2560,7 +1806,6 @@ void launch_conv(const ConvParams &p_in, hipStream_t s) {
     if (p_in.up2) { launch_conv_up2(p_in, s); return; }     // weights must be in phase form (make_up2_phase_weights)
     if (conv_wino_taken(p_in)) { launch_conv_wino(p_in, s); return; }
     ConvParams p = p_in;
-    p.dbg = exp_int("SR3_CONV_DBG", 0);
     const long M = (long)p.B * p.Hout * p.Wout;
     {
         auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
@@ -2568,23 +1813,15 @@ void launch_conv(const ConvParams &p_in, hipStream_t s) {
         p.w_shift = lg(p.Wout);
     }
     if (p.part == nullptr) p.splits = 1;
-    if (p.in_fm) {
-        // the caller wrote this conv's input fragment-major (it asked conv_ws_shape_ok): 64 -> 64 channels over many
-        // 128-pixel tiles — the weights-stationary persistent kernel, and no other kernel can read that layout
-        p.splits = 1;
-        if (conv_ws_supported(p)) launch_conv_ws(p, s);
-        else g_conv_error = "internal: fragment-major input handed to a conv the weights-stationary kernel does not support";
-        return;
-    }
     if (p.prec == 1 && p.ks == 3 && p.stride == 1 && !p.up2 && p.phases == 1 && p.part != nullptr && p.tile_cnt != nullptr &&
-        p.in0.pad == 1 && p.in0.W == p.Wout && p.in0.H == p.Hout && p.gnf_gamma == nullptr && !p.no_halo_split) {
+        p.in0.pad == 1 && p.in0.W == p.Wout && p.in0.H == p.Hout && !p.no_halo_split) {
         const int hs = conv_halo_splits(M, p.Hout, p.Wout, p.out.C, p.in0.C + (p.in1.p ? p.in1.C : 0));
         const int HWo = p.Hout * p.Wout;
         const bool stats_ok = p.stats == nullptr || p.stats_slices == (HWo >= 128 ? HWo / 128 : 1);
         if (hs > 1 && stats_ok) {
             p.splits = hs;
-            if (halo_ok(p, 128, 32, 128, true)) { launch_halo<128, 128, 4, 1, 32, 3, 16, false, true>(p, s); return; }
-            if (halo_ok(p, 128, 8, 128, true)) { launch_halo<128, 128, 4, 1, 8, 3, 16, false, true>(p, s); return; }
+            if (halo_ok(p, 128, 32, 128, true)) { launch_halo<128, 128, 4, 1, 32, 3, 16, true>(p, s); return; }
+            if (halo_ok(p, 128, 8, 128, true)) { launch_halo<128, 128, 4, 1, 8, 3, 16, true>(p, s); return; }
             p.splits = p_in.splits;
         }
     }
@@ -2599,18 +1836,6 @@ void launch_conv(const ConvParams &p_in, hipStream_t s) {
         if (p.stats && splitk_stats_slices(HWo, p.out.C) > 0) reduce_stats = p.stats;
         p.stats = nullptr;
     }
-#ifdef SR3_EXPERIMENTS
-    if (p.gnf_gamma != nullptr) {
-        // producer-side GroupNorm: the caller asked conv_gnf_supported() first
-        const int which = gnf_kernel_choice(p, p.gnf_groups);
-        if (which == 0) { g_conv_error = "internal: producer-side GroupNorm requested for an unsupported conv"; return; }
-        p.gnf_band = gnf_band_for(p, which);
-        if (which == 1) launch_halo<128, 64, 4, 1, 32, 3, 16, true>(p, s);
-        else if (which == 2) launch_halo<128, 128, 4, 1, 32, 3, 16, true>(p, s);
-        else launch_halo<128, 128, 4, 1, 8, 3, 16, true>(p, s);
-        return;
-    }
-#endif
     if (p.f8) {
         // the caller asked conv_f8_supported() first and wrote the input / passes the weights in the F8C format
         // (conv_f8_supported is the single source of truth; a mismatch is a library bug, reported through the API's
@@ -2619,30 +1844,24 @@ void launch_conv(const ConvParams &p_in, hipStream_t s) {
             g_conv_error = "internal: fp8 correction products requested for a conv the F8C kernel does not support";
             return;
         }
-        launch_halo<128, 128, 2, 2, 8, 3, 32, false, false, true>(p, s);
+        launch_halo<128, 128, 2, 2, 8, 3, 32, false, true>(p, s);
         return;
     }
     switch (conv_tile_choice(M, p.out.C)) {
     case 0: launch_cfg<128, 32, 4, 1>(p, s); break;
     case 1:
         if (halo_ok(p, 128, 32, 64)) {
-#ifdef SR3_EXPERIMENTS
-            if (halo_mfma16() && halo_persistent() && p.ks == 3) launch_halo_pt<128, 64, 32, 3>(p, s);
-            else
-#endif
-            if (halo_mfma16()) { if (p.ks == 3) launch_halo<128, 64, 4, 1, 32, 3, 16>(p, s); else launch_halo<128, 64, 4, 1, 32, 2, 16>(p, s); }
-            else { if (p.ks == 3) launch_halo<128, 64, 2, 2, 32, 3, 32>(p, s); else launch_halo<128, 64, 2, 2, 32, 2, 32>(p, s); }
+            if (p.ks == 3) launch_halo<128, 64, 4, 1, 32, 3, 16>(p, s); else launch_halo<128, 64, 4, 1, 32, 2, 16>(p, s);
         }
         else launch_cfg<128, 64, 2, 2>(p, s);
         break;
     case 2: launch_cfg<64, 64, 2, 2>(p, s); break;
     default:
-        if (halo_mfma16() && halo_ok(p, 128, 32, 128)) {   // rows of 32+ pixels: one row segment per wave (ONESEG)
+        if (halo_ok(p, 128, 32, 128)) {   // rows of 32+ pixels: one row segment per wave (ONESEG)
             if (p.ks == 3) launch_halo<128, 128, 4, 1, 32, 3, 16>(p, s); else launch_halo<128, 128, 4, 1, 32, 2, 16>(p, s);
         }
         else if (halo_ok(p, 128, 8, 128)) {
-            if (halo_mfma16()) { if (p.ks == 3) launch_halo<128, 128, 4, 1, 8, 3, 16>(p, s); else launch_halo<128, 128, 4, 1, 8, 2, 16>(p, s); }
-            else { if (p.ks == 3) launch_halo<128, 128, 2, 2, 8, 3, 32>(p, s); else launch_halo<128, 128, 2, 2, 8, 2, 32>(p, s); }
+            if (p.ks == 3) launch_halo<128, 128, 4, 1, 8, 3, 16>(p, s); else launch_halo<128, 128, 4, 1, 8, 2, 16>(p, s);
         }
         else launch_cfg<128, 128, 2, 2>(p, s);
         break;
@@ -2709,7 +1928,7 @@ __global__ __launch_bounds__(256) void make_f8_weights_kernel(const float *__res
 #pragma unroll
     for (int u = 0; u < 4; ++u) { h[u] = (float)src[j + u]; l[u] = (float)src[32 + j + u]; dh[j + u] = src[j + u]; }
     const float sh = ldexpf(1.0f, SR3_F8_WH), sl = ldexpf(1.0f, SR3_F8_WL);
-    auto cl = [](float v) { return __builtin_fminf(__builtin_fmaxf(v, -448.f), 448.f); };
+    auto cl = [](float v) { return fminf(fmaxf(v, -448.f), 448.f); };
     int wh = __builtin_amdgcn_cvt_pk_fp8_f32(cl(h[0] * sh), cl(h[1] * sh), 0, false);
     wh = __builtin_amdgcn_cvt_pk_fp8_f32(cl(h[2] * sh), cl(h[3] * sh), wh, true);
     int wl = __builtin_amdgcn_cvt_pk_fp8_f32(cl(l[0] * sl), cl(l[1] * sl), 0, false);

@@ -302,30 +302,6 @@ __device__ __forceinline__ void store8(float *dst, int c, const float (&f)[8], f
     }
 }
 
-// SPLIT 3: split-f16 halfs in the fragment-major layout (sr3_internal.h fm_*): hi octet at the lane slot of its pixel,
-// lo octet 1 KB behind it
-__device__ __forceinline__ void store8_fm(const TDesc &out, int n, int y, int x, int c, const float (&f)[8], float &absmax) {
-    h16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float g = f[j];
-        absmax = fmaxf(absmax, fabsf(g));
-        hi[j] = (_Float16)g;
-        lo[j] = (_Float16)(g - (float)hi[j]);
-    }
-    const int yp = y + 1, xp = x + 1;
-    const size_t blk = (((size_t)n * (out.H + 2) + yp) * fm_groups(out.W) + (xp >> 4)) * (out.C >> 5) + (c >> 5);
-    char *d = reinterpret_cast<char *>(out.p) + blk * 2048 + ((c & 31) >> 3) * 256 + (xp & 15) * 16;
-    *reinterpret_cast<h16x8 *>(d) = hi;
-    *reinterpret_cast<h16x8 *>(d + 1024) = lo;
-}
-
-template <int SPLIT>
-__device__ __forceinline__ void store_out(const TDesc &out, int n, int y, int x, int C, int c, const float (&f)[8], float &absmax) {
-    if constexpr (SPLIT == 3) store8_fm(out, n, y, x, c, f, absmax);
-    else store8<SPLIT>(out.p + out.pix(n, y, x) * C, c, f, absmax);
-}
-
 // Where the per-(image, channel) GroupNorm statistics of an apply pass come from: fp64 {sum, sum of
 // squares} partials per (image, slice, channel) of one or two source tensors (the halves of a
 // concatenation; written by conv epilogues or by gn_partial_kernel), folded with gamma / beta.
@@ -475,7 +451,7 @@ __global__ __launch_bounds__(GA_T) void gn_apply_kernel(const TDesc in0, const T
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = swish_fast(f[j]);
             }
-            store_out<SPLIT>(out, n, y, x, C, c, f, absmax);
+            store8<SPLIT>(out.p + out.pix(n, y, x) * C, c, f, absmax);
         };
         int pix = pix0 + pl;
         int y = pix / W, x = pix - y * W;
@@ -516,9 +492,7 @@ __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const TDesc in0, con
     const int Hh = out.H / NR;
     const int n = blockIdx.y / Hh, y0 = blockIdx.y - n * Hh;
     const int item = blockIdx.x * 256 + threadIdx.x;
-    // (SPLIT 3: the launcher guarantees C == 64 and W % 32 == 0 — whole blocks, every thread reaches the barrier)
-    __shared__ h16x8 fm_stage[SPLIT == 3 ? NR * 8 * 2 * 32 : 1];
-    if (SPLIT != 3 && item >= out.W * C8) return;
+    if (item >= out.W * C8) return;
     const int x = item / C8;
     const int c = (item - x * C8) << 3;
     const bool first = c < C0;
@@ -569,39 +543,7 @@ __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const TDesc in0, con
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = swish_fast(f[j]);
         }
-        if constexpr (SPLIT == 3) {
-            // Fragment-major output (C == 64, W % 32 == 0: a block is 32 consecutive pixels x 8 octets). Written straight
-            // from this thread mapping every quad would store four 16-byte pieces 256 B apart (+50 % on the whole pass:
-            // profiles/README.md finding 66), so the pieces go through LDS: thread (pixel pl, octet j) leaves hi | lo in
-            // slot [row][j][h][pl]; after the barrier thread t picks up (j = t >> 5, pl = t & 31) — a quad then writes
-            // 64 consecutive bytes of one (chunk, h, q) run of the FM block.
-            h16x8 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float g = f[j];
-                absmax = fmaxf(absmax, fabsf(g));
-                hi[j] = (_Float16)g;
-                lo[j] = (_Float16)(g - (float)hi[j]);
-            }
-            const int pl = threadIdx.x >> 3, jo = threadIdx.x & 7;
-            fm_stage[((r * 8 + jo) * 2 + 0) * 32 + pl] = hi;
-            fm_stage[((r * 8 + jo) * 2 + 1) * 32 + pl] = lo;
-        } else {
-            store_out<SPLIT>(out, n, y, x, C, c, f, absmax);
-        }
-    }
-    if constexpr (SPLIT == 3) {
-        __syncthreads();
-        const int jo = threadIdx.x >> 5, pl = threadIdx.x & 31;
-        const int xq = blockIdx.x * 32 + pl + 1;                    // padded x of this thread's output pixel
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const int yp = y0 + r * Hh + 1;
-            const size_t blk = (((size_t)n * (out.H + 2) + yp) * fm_groups(out.W) + (xq >> 4)) * 2 + (jo >> 2);
-            char *d = reinterpret_cast<char *>(out.p) + blk * 2048 + (jo & 3) * 256 + (xq & 15) * 16;
-            *reinterpret_cast<h16x8 *>(d) = fm_stage[((r * 8 + jo) * 2 + 0) * 32 + pl];
-            *reinterpret_cast<h16x8 *>(d + 1024) = fm_stage[((r * 8 + jo) * 2 + 1) * 32 + pl];
-        }
+        store8<SPLIT>(out.p + out.pix(n, y, x) * C, c, f, absmax);
     }
     if (SPLIT && ovf != nullptr && (absmax > (SPLIT == 2 ? SPLIT_F8_MAX : SPLIT_F16_MAX) || absmax_raw > SPLIT_F16_MAX)) *ovf = 1;
 }
@@ -617,11 +559,6 @@ void launch_gn_apply_rows(const TDesc &in0, const TDesc &in1, int B, const float
         if (nr == 2) hipLaunchKernelGGL((gn_apply_rows_kernel<M, S, 2>), grid, dim3(256), 0, s, in0, in1, scale, shift, out, raw, in_split, ovf); \
         else hipLaunchKernelGGL((gn_apply_rows_kernel<M, S, 1>), grid, dim3(256), 0, s, in0, in1, scale, shift, out, raw, in_split, ovf);         \
     }
-#ifdef SR3_EXPERIMENTS      // fragment-major output: the weights-stationary conv experiment only (profiles/README.md finding 66)
-    if (split == 3) {
-        if (mode == 0) SR3_GR(0, 3) else if (mode == 1) SR3_GR(1, 3) else SR3_GR(2, 3)
-    } else
-#endif
     if (split == 2) {
         if (mode == 0) SR3_GR(0, 2) else if (mode == 1) SR3_GR(1, 2) else SR3_GR(2, 2)
     } else if (split) {
@@ -635,7 +572,7 @@ void launch_gn_apply_rows(const TDesc &in0, const TDesc &in1, int B, const float
 // pixels per block: enough blocks to keep every CU streaming (>= ~4 blocks of 512 threads per CU over
 // the whole grid), at least two items per thread
 static int ga_pixels_per_block(int B, int HW, int C8) {
-    const int total = exp_int("SR3_GN_BLOCKS", 1024);       // (experiments build reads the variable)
+    constexpr int total = 1024;                         // blocks of the whole grid wanted
     int P = (total + B - 1) / B;                        // blocks per image wanted
     const int maxP = (HW * C8 + 2 * GA_T - 1) / (2 * GA_T);
     if (P > maxP) P = maxP;
@@ -663,11 +600,6 @@ static void launch_gn_apply_impl(const TDesc &in0, const TDesc &in1, int B, cons
         hipLaunchKernelGGL((gn_apply_kernel<M, S>), grid, dim3(GA_T), lds, s, in0, in1, scale, shift, st, out, raw, \
                            in_split, ovf, ppb);                                                                    \
     }
-#ifdef SR3_EXPERIMENTS
-    if (split == 3) {
-        if (mode == 0) SR3_GA(0, 3) else if (mode == 1) SR3_GA(1, 3) else SR3_GA(2, 3)
-    } else
-#endif
     if (split == 2) {
         if (mode == 0) SR3_GA(0, 2) else if (mode == 1) SR3_GA(1, 2) else SR3_GA(2, 2)
     } else if (split) {
@@ -911,12 +843,9 @@ __global__ __launch_bounds__(256) void attention_vt_kernel(const float *__restri
 template <int NTW, int NTC, int MTQ, int NWAVES, int NCH = 0, int NKS = 0>
 __global__ __launch_bounds__(NWAVES * 64) void attention_split_kernel(const float *__restrict__ qkv, const float *__restrict__ vt,
                                                               int N, int C, float *__restrict__ out,
-                                                              float *__restrict__ out_split, int *ovf, int dbg) {
+                                                              float *__restrict__ out_split, int *ovf) {
     extern __shared__ __attribute__((aligned(16))) float S[];   // [QB][ld]: fp32 scores, then P as [hi8|lo8] groups
     constexpr int QB = MTQ * 16;
-#ifndef SR3_EXPERIMENTS
-    dbg = 0;        // timing experiments only (SR3_ATTN_DBG in the experiments build): 1 no scores, 2 no softmax, 4 no P v
-#endif
     const int Np = (N + 31) & ~31;
     const int ld = Np + 8;
     // XCD-aware block order (speed only): blocks b and b + 8 share an XCD, so every XCD gets a contiguous
@@ -989,7 +918,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attention_split_kernel(const floa
             for (int mt = 0; mt < MTQ; ++mt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[i][mt][r] = 0.f;
-        if (wid * NTW < nkt && !(dbg & 1)) {
+        if (wid * NTW < nkt) {
             // the fragments of chunk ch + 1 are in flight while chunk ch multiplies (two register sets; rows of
             // tiles past the end are clamped duplicates whose scores are never stored)
             if constexpr (STATIC) {
@@ -1068,7 +997,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attention_split_kernel(const floa
     __syncthreads();
 
     // ---- softmax over keys (fp32, 8 lanes per query row), then P -> [8 hi halfs | 8 lo halfs] per 8 keys, in place ----
-    if (!(dbg & 2)) {
+    {
         constexpr int RPP = NWAVES * 8, NRP = QB / RPP;     // query rows per pass of the block, passes
         const int sub = tid & 7;
         float sums[NRP];
@@ -1163,7 +1092,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attention_split_kernel(const floa
                 }
         };
         if constexpr (STATIC) attn_ring_static<NKS, NSETV>(fetch, mult);
-        else if (!(dbg & 4)) attn_ring2(nks, fetch, mult);
+        else attn_ring2(nks, fetch, mult);
     }
     // C/D map: col = l16 (channel), row = 4 q4 + j (query)
 #pragma unroll
@@ -1202,12 +1131,10 @@ double launch_attention_split(const float *qkv_split, float *vt, int B, int N, i
     hipLaunchKernelGGL(attention_vt_kernel, dim3(Np / 32, (C + 127) / 128, B), dim3(256), 0, s, qkv_split, N, C, vt);
     // 64 queries x 8 waves per block where that still leaves a block for every CU (config 3: B = 64, 256 tokens);
     // else 32 queries x 4 waves
-    static const int q64 = exp_int("SR3_ATTN_Q64", 1);
-    const bool big = q64 && (Np % 64) == 0 && (long)B * (Np / 64) >= 256 && (Np / 16 + 7) / 8 <= 2 && (C / 16 + 7) / 8 <= 4;
+    const bool big = (Np % 64) == 0 && (long)B * (Np / 64) >= 256 && (Np / 16 + 7) / 8 <= 2 && (C / 16 + 7) / 8 <= 4;
     const int QB = big ? 64 : 32, NW = big ? 8 : 4;
     const size_t lds = std::max((size_t)QB * (Np + 8) * sizeof(float), big ? (size_t)QB * (C * 4 + 32) : (size_t)0);
     const int ntw = (Np / 16 + NW - 1) / NW, ntc = (C / 16 + NW - 1) / NW;
-    const int dbg = exp_int("SR3_ATTN_DBG", 0);
 #define SR3_AT(A, B_, MQ, W_, CH_, KS_)                                                                            \
     {                                                                                                              \
         static size_t attr = 0;                                                                                    \
@@ -1217,10 +1144,9 @@ double launch_attention_split(const float *qkv_split, float *vt, int B, int N, i
             attr = lds;                                                                                            \
         }                                                                                                          \
         hipLaunchKernelGGL((attention_split_kernel<A, B_, MQ, W_, CH_, KS_>), dim3((Np / QB) * B), dim3(W_ * 64), lds, s, \
-                           qkv_split, vt, N, C, out, out_split, ovf, dbg);                                         \
+                           qkv_split, vt, N, C, out, out_split, ovf);                                              \
     }
-    static const int attn_static = exp_int("SR3_ATTN_STATIC", 1);    // A/B (experiments build): rolled two-set rings
-    if (big && attn_static && C == 512 && Np == 256 && dbg == 0) SR3_AT(2, 4, 4, 8, 16, 8)     // config 3: unrolled, deep rings
+    if (big && C == 512 && Np == 256) SR3_AT(2, 4, 4, 8, 16, 8)     // config 3: unrolled, deep rings
     else if (big) SR3_AT(2, 4, 4, 8, 0, 0)       // (at most 256 tokens: 2 key tiles per wave)
     else if (ntw <= 2 && ntc <= 2) SR3_AT(2, 2, 2, 4, 0, 0)
     else if (ntw <= 4 && ntc <= 8) SR3_AT(4, 8, 2, 4, 0, 0)

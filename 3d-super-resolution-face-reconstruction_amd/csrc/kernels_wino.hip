@@ -411,9 +411,9 @@ bool conv_wino_fused(int B, int H, int W, int Cin, int Cout) {
 }
 
 bool conv_wino_taken(const ConvParams &p) {
-    if (p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.in_fm || p.f8)
+    if (p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.f8)
         return false;
-    if (p.gnf_gamma || p.out_split.p || !p.out_f32 || p.resid_split) return false;
+    if (p.out_split.p || !p.out_f32 || p.resid_split) return false;
     if (p.in0.pad != 1 || p.in0.H != p.Hout || p.in0.W != p.Wout) return false;
     if (p.in1.p && (p.in1.pad != 1 || p.in1.H != p.Hout || p.in1.W != p.Wout)) return false;
     if (p.in2.p && !p.w2) return false;

@@ -96,9 +96,6 @@ struct Module {
     TDesc up_in;            // M_UP / M_DOWN: split-f16 copy of the raw input (prec 1)
     int slices_default = 0; // st_out.slices when the generic conv produces the statistics (conv_in_kernel: HW / 256)
     TDesc raw1;             // has_res: un-normalised x ‖ skip in the conv input format (fused res_conv)
-    // fragment-major copies of act1 / act2 (sr3_internal.h fm_*): the input layout of the weights-stationary kernel, used in
-    // split-f16 mode where conv_ws_shape_ok says this block's 64 -> 64 channel convs run on it (p == null: not for this block)
-    TDesc fm1, fm2;
     // fused GroupNorm statistics written by the conv that produces out / rb_out / h1 (p == null:
     // the tile does not divide the image, fall back to the statistics kernel)
     StatsRef st_out, st_rb, st_h1;
@@ -139,7 +136,6 @@ struct sr3_ctx {
     bool f8corr = false;
     bool f8_dirty = true;      // dev_f8 copies are stale (weights loaded / re-split since they were made)
     bool fused_dirty = true;   // fused bias / common weight scales need (re)building
-    bool no_fused_stats = false;   // SR3_NO_FUSED_STATS=1: always run the statistics kernel (A/B testing)
     bool all_fused = false;        // every GroupNorm of the current workspace gets its statistics from a conv epilogue
     // split-f16 range check: kernels set *d_ovf when a value stored in the split format exceeds the
     // fp16 range (|v| > 65504); sr3_unet_forward / sr3_sample_end / sr3_range_check read it and fail
@@ -159,8 +155,6 @@ struct sr3_ctx {
     // path whose blocks never wait for each other. Captured step graphs are rebuilt.
     bool halo_split_off = false;
     int replay_calls = 0;               // calls (or segments) replayed for that reason since sr3_create
-    unsigned *gnf_cnt = nullptr;        // ConvParams::gnf_cnt: group counters of the producer-side GroupNorm (zero between launches)
-    float *gnf_ab = nullptr;            // ConvParams::gnf_ab: [B][c_max][2] (workspace)
 
     // workspace for one (B, H, W)
     int wB = 0, wH = 0, wW = 0;
@@ -524,15 +518,11 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     // dry run over the graph for sizes
     Carver cv;
     ShapePool acts, h1s, raws;
-    std::map<std::pair<int, int>, uint64_t> fm_off;      // one fragment-major buffer per (h, w) level with 64-channel convs
-    std::vector<uint64_t> fm_at(c->mods.size(), 0);
-    std::vector<char> fm_use(c->mods.size(), 0);       // bit 0: conv1, bit 1: conv2 of the block
     const size_t nm = c->mods.size();
     std::vector<uint64_t> out_off(nm), rb_off(nm), a1_off(nm), a2_off(nm), h1_off(nm), raw_off(nm);
     std::vector<uint64_t> so_off(nm), sr_off(nm), sh_off(nm), tw_off(nm);
     std::vector<char> twin(nm, 0);
-    static const int no_twin = exp_int("SR3_NO_TWIN", 0);   // A/B (experiments build): old copy / raw passes
-    for (size_t i = 0; i < nm && !no_twin; ++i) {
+    for (size_t i = 0; i < nm; ++i) {
         const bool skip = (int)i < c->n_downs;                       // consumed raw by an up-path res_conv
         const Module *nx = i + 1 < nm ? &c->mods[i + 1] : nullptr;
         twin[i] = skip || (nx && (nx->kind == M_DOWN || nx->kind == M_UP || (nx->kind == M_RES && nx->rb.has_res)));
@@ -554,15 +544,6 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
             a2_off[i] = acts.get(cv, B, oc, h, w);
             h1_off[i] = h1s.get(cv, B, oc, h, w);
             if (m.rb.has_res) raw_off[i] = raws.get(cv, B, m.rb.cin, h, w);
-            {
-                const bool ws1 = conv_ws_shape_ok(B, h, w, m.rb.cin, oc), ws2 = conv_ws_shape_ok(B, h, w, oc, oc);
-                if (ws1 || ws2) {
-                    auto key = std::make_pair(h, w);
-                    if (!fm_off.count(key)) fm_off[key] = cv.take(fm_floats(B, 64, h, w));
-                    fm_at[i] = fm_off[key];
-                    fm_use[i] = (char)((ws1 ? 1 : 0) | (ws2 ? 2 : 0));
-                }
-            }
             if (m.rb.attn) {
                 const uint64_t nu = (uint64_t)B * h * w * oc;
                 if (3 * nu > max_qkv) max_qkv = 3 * nu;
@@ -642,7 +623,6 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     const uint64_t o_part = cv.take(max_part);
     const uint64_t o_wino = cv.take(max_wino);
     const uint64_t o_gs = cv.take((uint64_t)B * c->c_max), o_gh = cv.take((uint64_t)B * c->c_max);
-    const uint64_t o_gab = cv.take((uint64_t)B * c->c_max * 2);
     const uint64_t o_gp = cv.take(gn_workspace_floats(B, c->c_max));
     const uint64_t o_te = cv.take((uint64_t)B * g.inner_channel);
     const uint64_t o_cb = cv.take((uint64_t)B * c->nf_total);
@@ -682,8 +662,6 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
             m.act2 = desc(a2_off[i], m.oc, m.oh, m.ow, 1);
             m.h1 = desc(h1_off[i], m.oc, m.oh, m.ow, 1);
             if (m.rb.has_res) m.raw1 = desc(raw_off[i], m.rb.cin, m.oh, m.ow, 1);
-            m.fm1 = (fm_use[i] & 1) ? desc(fm_at[i], m.rb.cin, m.oh, m.ow, 1) : TDesc();
-            m.fm2 = (fm_use[i] & 2) ? desc(fm_at[i], m.oc, m.oh, m.ow, 1) : TDesc();
         }
     }
     c->x0 = desc(o_x0, c->in_pad, H, W, 1);
@@ -696,7 +674,6 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     c->part = max_part ? at(o_part) : nullptr;
     c->wino_ws = max_wino ? at(o_wino) : nullptr;
     c->gscale = at(o_gs); c->gshift = at(o_gh); c->gpart = at(o_gp);
-    c->gnf_ab = at(o_gab);
     c->temb = at(o_te); c->cbias = at(o_cb);
     c->all_fused = all_fused;
     c->wB = B; c->wH = H; c->wW = W;
@@ -711,26 +688,24 @@ const TDesc kNone{};
 // GroupNorm statistics + apply (+Swish) (+concat) -> activated, zero-bordered conv input
 // f8: the consumer conv takes the F8C operand format (f8_conv() said so)
 void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int B, int mode, const TDesc &act,
-                const StatsRef &sa, const StatsRef &sb, const TDesc &raw = TDesc(), int in_split = 0, bool f8 = false,
-                bool fm = false) {
-    // fm: `act` is a fragment-major buffer (the consumer conv runs on the weights-stationary kernel; split-f16 mode only)
-    const int fmt = c->prec ? (fm ? 3 : (f8 ? 2 : 1)) : 0;
+                const StatsRef &sa, const StatsRef &sb, const TDesc &raw = TDesc(), int in_split = 0, bool f8 = false) {
+    const int fmt = c->prec ? (f8 ? 2 : 1) : 0;
     c->pbegin(F_GN);
     const float *gamma = c->params[g.gamma].dev, *beta = c->params[g.beta].dev;
     // bytes the pass moves (read + write, 4 B per element each way): above ~200 MB the one-item-per-thread
     // streaming kernel behind a separate finalize launch is faster than the folded form (A/B on one box,
     // profiles/README.md); below it the launch saved and the shorter critical path win
     const double pass_bytes = 8.0 * B * a.H * a.W * (a.C + (b.p ? b.C : 0));
-    static const double fold_max = exp_double("SR3_GN_FOLD_MAX_MB", 200.0) * 1e6;
+    constexpr double fold_max = 200.0 * 1e6;
     // few images with many statistics slices (a single 128x128 image on 64x64 tiles leaves 256): the folded form's
     // prologue walks them in 12-16 dependent round trips in EVERY block (12-23 us per apply at B = 1); the
     // per-(image, group) finalize launch takes one round trip
     const bool many_slices = (long)B * 4 < 128 && std::max(sa.slices, b.p ? sb.slices : 0) >= 64;
-    if (sa.p && (!b.p || sb.p) && !c->no_fused_stats && (pass_bytes > fold_max || many_slices)) {
+    if (sa.p && (!b.p || sb.p) && (pass_bytes > fold_max || many_slices)) {
         launch_groupnorm_finalize(sa, a.C, sb, b.p ? b.C : 0, B, a.H * a.W, c->cfg.norm_groups, gamma, beta, 1e-5f,
                                   c->gscale, c->gshift, c->stream);
         launch_gn_apply_rows(a, b, B, c->gscale, c->gshift, mode, fmt, act, c->stream, raw, in_split, c->d_ovf);
-    } else if (sa.p && (!b.p || sb.p) && !c->no_fused_stats) {
+    } else if (sa.p && (!b.p || sb.p)) {
         // statistics came out of the producing convs' epilogues: finalize + apply are ONE launch
         launch_gn_fold_apply(a, b, B, sa, sb, c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream, raw,
                              in_split, c->d_ovf);
@@ -749,10 +724,8 @@ void run_conv(sr3_ctx *c, const TDesc &a, const TDesc &b, const ConvRef &cv, int
               const float *chan_bias, const TDesc &resid, const TDesc &out, bool activated = false,
               const TDesc &in2 = TDesc(), const ConvRef *cv2 = nullptr, const float *bias_override = nullptr,
               const StatsRef &stats = StatsRef(), const TDesc &out_split = TDesc(), const TDesc &in2b = TDesc(),
-              bool out_f32 = true, bool resid_split = false, const float *w2_raw = nullptr, const GNRef *gnf = nullptr,
-              bool *gnf_done = nullptr, bool f8 = false, bool in_fm = false) {
+              bool out_f32 = true, bool resid_split = false, const float *w2_raw = nullptr, bool f8 = false) {
     ConvParams p;
-    p.in_fm = in_fm ? 1 : 0;
     p.in0 = a; p.in1 = b; p.B = B; p.Hout = out.H; p.Wout = out.W;
     p.ks = cv.ks; p.stride = stride; p.up2 = up2;
     p.prec = activated ? c->prec : 0;
@@ -768,7 +741,7 @@ void run_conv(sr3_ctx *c, const TDesc &a, const TDesc &b, const ConvRef &cv, int
     if (c->prec) p.out_split = out_split;
     p.out_f32 = (out_f32 || !p.out_split.p) ? 1 : 0;
     p.resid_split = resid_split ? 1 : 0;
-    if (stats.p && !c->no_fused_stats) { p.stats = const_cast<double *>(stats.p); p.stats_slices = stats.slices; }
+    if (stats.p) { p.stats = const_cast<double *>(stats.p); p.stats_slices = stats.slices; }
     p.splits = p.f8 ? 1 : conv_splits((long)B * out.H * out.W, cv.cout, a.C + (b.p ? b.C : 0));
     p.part = c->part;
     p.tile_cnt = c->tile_cnt;
@@ -781,17 +754,6 @@ void run_conv(sr3_ctx *c, const TDesc &a, const TDesc &b, const ConvRef &cv, int
         p.in2 = in2;                    // identity skip as extra K-steps (ResBlock::ident_w)
         p.w2 = w2_raw;
     }
-    bool use_gnf = false;
-    if (gnf && p.prec == 1 && !p.f8 && p.out_split.p && conv_gnf_supported(p, c->cfg.norm_groups)) {
-        // producer-side GroupNorm: the conv normalises its own output and writes swish(scale * h + shift) as out_split
-        p.gnf_gamma = c->params[gnf->gamma].dev; p.gnf_beta = c->params[gnf->beta].dev;
-        p.gnf_groups = c->cfg.norm_groups; p.gnf_eps = 1e-5f;
-        p.gnf_cnt = c->gnf_cnt; p.gnf_ab = c->gnf_ab;
-        p.out_f32 = 0;
-        use_gnf = true;
-    }
-    if (gnf_done) *gnf_done = use_gnf;
-    if (gnf && !use_gnf) { p.out_split = TDesc(); p.out_f32 = 1; }   // the caller runs the apply pass on the fp32 output
     c->pbegin(F_CONV);
     if (up2) launch_conv_up2(p, c->stream);
     else launch_conv(p, c->stream);
@@ -799,7 +761,7 @@ void run_conv(sr3_ctx *c, const TDesc &a, const TDesc &b, const ConvRef &cv, int
         char tag[160];
         snprintf(tag, sizeof tag, "conv k%d s%d u%d %dx%d cin%d(%d+%d) cout%d res%d fused1x1:%d prec%d%s", cv.ks, stride,
                  up2, out.H, out.W, cv.cin, a.C, b.p ? b.C : 0, cv.cout, resid.p ? 1 : 0, cv2 ? cv2->cin : 0, p.prec,
-                 use_gnf ? " +gn" : (p.f8 ? " f8c" : (p.in_fm ? " ws" : "")));
+                 p.f8 ? " f8c" : "");
         c->pend(2.0 * (double)B * out.H * out.W * cv.cout * ((double)(cv.ks * cv.ks) * cv.cin + (cv2 ? cv2->cin : 0)), tag);
     }
 }
@@ -825,43 +787,32 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     const int h = m.oh, w = m.ow;
     // block1: GN+Swish(x ‖ skip) -> conv3x3 + bias + FeatureWiseAffine bias; the same pass stores
     // the raw concatenation for the fused res_conv
-    static const bool no_ident = exp_int("SR3_NO_IDENT", 0) != 0;   // A/B (experiments build): epilogue gather
     const bool direct = rb.has_res && xr.p && (!skip.p || skr.p);
     // (conv2's fused 1x1 K-steps read x / skip — or the raw concatenation — in 32-channel chunks of the plain split format)
     const bool fused_ok = !rb.has_res || (direct ? ((xr.C % 32) == 0 && (!skip.p || (skr.C % 32) == 0)) : (rb.cin % 32) == 0);
     const bool f8a = f8_conv(c, rb.c1, B, h, w), f8b = fused_ok && f8_conv(c, rb.c2, B, h, w);
-    // 64 -> 64 channel convs of the full-resolution level: weights-stationary kernel on a fragment-major input (the epilogue
-    // residual is the one thing it does not do: such a conv2 stays on the x-halo kernel)
-    const bool wsa = c->prec == 1 && m.fm1.p != nullptr && !skip.p && !f8a;
-    const bool ws2_resid = !rb.has_res && !(rb.ident_w && xr.p && !no_ident);
-    const bool wsb = c->prec == 1 && m.fm2.p != nullptr && !f8b && !ws2_resid;
-    const TDesc &a1 = wsa ? m.fm1 : m.act1, &a2 = wsb ? m.fm2 : m.act2;
-    run_gn_act(c, x_so ? xr : x, (skip.p && sk_so) ? skr : skip, rb.gn1, B, 2, a1, sx, ss,
-               rb.has_res && !direct ? m.raw1 : kNone, (x_so ? 1 : 0) | (skip.p && sk_so ? 2 : 0), f8a, wsa);
-    // block1's conv + FeatureWiseAffine bias, then block2's GroupNorm + Swish: inside the conv where the producer-side
-    // form applies (h1 then never exists: the conv writes act2), else as the apply pass over the fp32 h1
-    bool gn2_done = false;
-    const bool want_gnf = c->prec && !c->no_fused_stats;     // (only then may the conv write act2 itself: h1 is never range-checked as a twin otherwise)
-    run_conv(c, a1, kNone, rb.c1, B, 1, 0, c->cbias + rb.nf_off, kNone, m.h1, true, kNone, nullptr, nullptr, m.st_h1,
-             want_gnf ? m.act2 : kNone, kNone, true, false, nullptr, want_gnf ? &rb.gn2 : nullptr, &gn2_done, f8a, wsa);
-    if (!gn2_done) run_gn_act(c, m.h1, kNone, rb.gn2, B, 2, a2, m.st_h1, StatsRef(), TDesc(), 0, f8b, wsb);
+    run_gn_act(c, x_so ? xr : x, (skip.p && sk_so) ? skr : skip, rb.gn1, B, 2, m.act1, sx, ss,
+               rb.has_res && !direct ? m.raw1 : kNone, (x_so ? 1 : 0) | (skip.p && sk_so ? 2 : 0), f8a);
+    // block1's conv + FeatureWiseAffine bias writes the fp32 h1, then block2's GroupNorm + Swish as the apply pass over it
+    run_conv(c, m.act1, kNone, rb.c1, B, 1, 0, c->cbias + rb.nf_off, kNone, m.h1, true, kNone, nullptr, nullptr, m.st_h1,
+             kNone, kNone, true, false, nullptr, f8a);
+    run_gn_act(c, m.h1, kNone, rb.gn2, B, 2, m.act2, m.st_h1, StatsRef(), TDesc(), 0, f8b);
     // block2 + skip path in one launch: conv3x3(act2) [+ res_conv 1x1 (raw x ‖ skip) as extra
     // K-steps | + x as residual when the block keeps its width]
     const TDesc tw = rb.attn ? kNone : m.out_s;      // with attention the out-projection writes the module output
     if (rb.has_res)
-        run_conv(c, a2, kNone, rb.c2, B, 1, 0, nullptr, kNone, m.rb_out, true, direct ? xr : m.raw1, &rb.res,
-                 rb.fused_bias, m.st_rb, tw, direct && skip.p ? skr : kNone, !out_so, false, nullptr, nullptr, nullptr, f8b, wsb);
-    else if (c->prec && rb.ident_w && xr.p && !no_ident)
-        run_conv(c, a2, kNone, rb.c2, B, 1, 0, nullptr, kNone, m.rb_out, true, xr, nullptr, nullptr, m.st_rb,
-                 tw, kNone, !out_so, false, rb.ident_w, nullptr, nullptr, f8b, wsb);
+        run_conv(c, m.act2, kNone, rb.c2, B, 1, 0, nullptr, kNone, m.rb_out, true, direct ? xr : m.raw1, &rb.res,
+                 rb.fused_bias, m.st_rb, tw, direct && skip.p ? skr : kNone, !out_so, false, nullptr, f8b);
+    else if (c->prec && rb.ident_w && xr.p)
+        run_conv(c, m.act2, kNone, rb.c2, B, 1, 0, nullptr, kNone, m.rb_out, true, xr, nullptr, nullptr, m.st_rb,
+                 tw, kNone, !out_so, false, rb.ident_w, f8b);
     else
-        run_conv(c, a2, kNone, rb.c2, B, 1, 0, nullptr, x_so ? xr : x, m.rb_out, true, kNone, nullptr, nullptr, m.st_rb,
-                 tw, kNone, !out_so, x_so, nullptr, nullptr, nullptr, f8b, wsb);
+        run_conv(c, m.act2, kNone, rb.c2, B, 1, 0, nullptr, x_so ? xr : x, m.rb_out, true, kNone, nullptr, nullptr, m.st_rb,
+                 tw, kNone, !out_so, x_so, nullptr, f8b);
     if (rb.attn) {
         run_gn_act(c, m.rb_out, kNone, rb.agn, B, 1, m.act2, m.st_rb, StatsRef());
         const TDesc qkv = unpadded(c->qkvb, 3 * rb.cout, h, w);
-        static const bool attn_f32 = exp_int("SR3_ATTN_F32", 0) != 0;   // A/B (experiments build): f32-MFMA core in f16x3 mode
-        if (c->prec && !attn_f32 && attention_split_supported(h * w, rb.cout)) {
+        if (c->prec && attention_split_supported(h * w, rb.cout)) {
             // split-f16 mode: the qkv projection writes ONLY the split twin of its output, the attention core
             // multiplies hi/lo halfs (3 x v_mfma_f32_16x16x32_f16 per product) and hands its result to the out
             // projection in the same format
@@ -894,25 +845,21 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
     // split-only mode: a module output that has a twin is written ONLY as the twin (4 instead of 8
     // bytes per element); GroupNorm apply and residual adds read hi + lo. Needs every GroupNorm to get
     // its statistics from a conv epilogue (the fallback statistics kernel reads fp32 tensors).
-    static const bool so_off = exp_int("SR3_NO_SPLIT_ONLY", 0) != 0;
-    const bool so_mode = c->prec && c->all_fused && !c->no_fused_stats && !so_off;
+    const bool so_mode = c->prec && c->all_fused;
     const int n_pre = c->n_downs + c->n_mid;
-    static const bool no_direct = exp_int("SR3_NO_TWIN", 0) != 0;   // A/B (experiments build): raw-concatenation pass
-    static const bool no_edge = exp_int("SR3_NO_EDGE", 0) != 0;     // A/B (experiments build): generic kernels for downs.0 / final_conv
     for (int i = 0; i < (int)c->mods.size(); ++i) {
         Module &m = c->mods[i];
         const bool is_up_path = i >= n_pre;
         switch (m.kind) {
         case M_CONV_IN:
             m.st_out.slices = m.slices_default;
-            if (c->prec && c->x0p && !no_edge) {
+            if (c->prec && c->x0p) {
                 // downs.0 on the packed split-f16 state (kernels_edge.hip): 3 K-steps of 24 live k-values instead
                 // of 9 K-steps of 32 mostly-zero channels, no split copy of the state tensor
                 if (m.st_out.p) m.st_out.slices = H * W / 256;       // one statistics slice per 256-pixel block
-                const bool st = m.st_out.p && !c->no_fused_stats;
                 c->pbegin(F_CONV);
                 launch_conv_in(c->x0p, c->ci_w, m.conv.b >= 0 ? c->params[m.conv.b].dev : nullptr, c->ci_unscale, B, m.out,
-                               m.out_s, !(so_mode && m.out_s.p), st ? const_cast<double *>(m.st_out.p) : nullptr,
+                               m.out_s, !(so_mode && m.out_s.p), const_cast<double *>(m.st_out.p),
                                m.st_out.slices, c->d_ovf, c->stream);
                 if (c->prof) {
                     char tag[160];
@@ -952,11 +899,11 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
                 feats.pop_back();
                 if (c->prec) run_res(c, m, cur, scur, sk.out, sk.st_out, B, cur_s, sk.out_s, cur_so, sk.so_now,
                                      so_mode && m.out_s.p && !m.rb.attn);
-                else run_res(c, m, cur, scur, sk.out, sk.st_out, B, no_direct ? kNone : cur, sk.out);
+                else run_res(c, m, cur, scur, sk.out, sk.st_out, B, cur, sk.out);
             } else {
                 if (c->prec) run_res(c, m, cur, scur, kNone, StatsRef(), B, cur_s, kNone, cur_so, false,
                                      so_mode && m.out_s.p && !m.rb.attn);
-                else run_res(c, m, cur, scur, kNone, StatsRef(), B, no_direct ? kNone : cur, kNone);
+                else run_res(c, m, cur, scur, kNone, StatsRef(), B, cur, kNone);
             }
             break;
         }
@@ -967,12 +914,12 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
         scur = m.st_out;
         if (i < c->n_downs) feats.push_back(i);
     }
-    if (c->final_wq && !cur_so && !no_edge) {
+    if (c->final_wq && !cur_so) {
         // final_conv (unet.py:229,263): GroupNorm + Swish + Conv3x3(C -> 3) as ONE fp32 VALU kernel behind the
         // statistics finalize — no activated copy of the 128x128 tensor, no MFMA tile that is 29/32 padding
         const GNRef &g = c->final_gn;
         c->pbegin(F_GN);
-        if (scur.p && !c->no_fused_stats)
+        if (scur.p)
             launch_groupnorm_finalize(scur, cur.C, StatsRef(), 0, B, cur.H * cur.W, c->cfg.norm_groups, c->params[g.gamma].dev,
                                       c->params[g.beta].dev, 1e-5f, c->gscale, c->gshift, c->stream);
         else
@@ -980,8 +927,7 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
                                     c->gpart, c->gscale, c->gshift, c->stream);
         c->pend();
         c->pbegin(F_CONV);
-        static const bool final_valu = exp_int("SR3_FINAL_VALU", 0) != 0;   // A/B (experiments build): fp32 VALU form in f16x3 mode
-        const bool mfma = c->prec && c->final_wm && !final_valu;
+        const bool mfma = c->prec && c->final_wm;
         if (mfma)
             launch_final_conv_mfma(cur, B, c->gscale, c->gshift, c->final_wm, c->final_unscale, c->params[c->final_conv.b].dev,
                                    c->eps, c->stream, c->d_ovf);
@@ -1093,7 +1039,7 @@ int range_reset(sr3_ctx *c) {
 // fp16 range in the split-f16 format (such a value would otherwise corrupt the residual stream
 // silently). The flag is cleared either way.
 // synchronises, reads and clears the flag: 0 in range, 1 overflow, -1 HIP error, and
-// 2: a bounded inter-block wait of the in-place split-K on x-halo tiles gave up (SR3_FLAG_GNF_TIMEOUT) — some other kernel
+// 2: a bounded inter-block wait of the in-place split-K on x-halo tiles gave up (SR3_FLAG_WAIT_TIMEOUT) — some other kernel
 //    held the CU slots the tile's sibling blocks needed. Everything computed since the last reset is invalid (the flag may
 //    carry a bogus overflow bit from the incomplete sums as well). The context is switched to the conv path whose blocks
 //    never wait for each other (halo_split_off; captured graphs dropped) and the CALLER REPLAYS the work: the call still
@@ -1104,7 +1050,7 @@ int range_read(sr3_ctx *c) {
     if (*c->h_ovf == 0) return 0;
     const int v = *c->h_ovf;
     HIP_OK(hipMemsetAsync(c->d_ovf, 0, sizeof(int), c->stream));
-    if (v & SR3_FLAG_GNF_TIMEOUT) {
+    if (v & SR3_FLAG_WAIT_TIMEOUT) {
         c->halo_split_off = true;
         drop_graphs(c);
         // (every block still counts its arrival and departure, so the counters return to zero by themselves; the stream
@@ -1283,7 +1229,6 @@ int sr3_create(const sr3_unet_cfg *cfg, int device, sr3_ctx **out) {
     sr3_ctx *c = new sr3_ctx();
     c->cfg = *cfg;
     c->device = device;
-    c->no_fused_stats = exp_int("SR3_NO_FUSED_STATS", 0) != 0;      // experiments build only
     c->no_graph = env_int("SR3_NO_GRAPH", 0) != 0;                  // product switch
     if (build_graph(c)) { delete c; return -1; }
     if (alloc_weights(c)) { sr3_destroy(c); return -1; }
@@ -1292,8 +1237,6 @@ int sr3_create(const sr3_unet_cfg *cfg, int device, sr3_ctx **out) {
     if (hipMalloc(&c->d_ovf, sizeof(int)) != hipSuccess || hipMemset(c->d_ovf, 0, sizeof(int)) != hipSuccess ||
         hipMalloc(&c->tile_cnt, CONV_TILE_COUNTERS * sizeof(unsigned)) != hipSuccess ||
         hipMemset(c->tile_cnt, 0, CONV_TILE_COUNTERS * sizeof(unsigned)) != hipSuccess ||
-        hipMalloc(&c->gnf_cnt, (size_t)CONV_GNF_COUNTERS * 64 * sizeof(unsigned)) != hipSuccess ||
-        hipMemset(c->gnf_cnt, 0, (size_t)CONV_GNF_COUNTERS * 64 * sizeof(unsigned)) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void **>(&c->h_ovf), sizeof(int), hipHostMallocDefault) != hipSuccess) {
         sr3_destroy(c);
         return fail("allocating the range-check flag failed");
@@ -1330,7 +1273,6 @@ void sr3_destroy(sr3_ctx *c) {
     if (c->ckpt) (void)hipFree(c->ckpt);
     if (c->metrics_ws) (void)hipFree(c->metrics_ws);
     if (c->tile_cnt) (void)hipFree(c->tile_cnt);
-    if (c->gnf_cnt) (void)hipFree(c->gnf_cnt);
     if (c->h_ovf) (void)hipHostFree(c->h_ovf);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     if (c->d_step) (void)hipFree(c->d_step);
@@ -1882,17 +1824,14 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     }
     // the engine's own sequence: (GroupNorm apply | copy) + concat into a zero-bordered tensor, then conv
     TDesc a; a.C = Cin; a.H = Hin; a.W = Win; a.pad = 1;
-    // 64 -> 64 channels over many tiles: fragment-major input + the weights-stationary kernel, as run_res does it
-    const bool ws = c->prec == 1 && !f8 && ks == 3 && stride == 1 && !up2 && C1 == 0 && !resid_dev &&
-                    conv_ws_shape_ok(B, Hin, Win, Cin, Cout);
-    const size_t act_floats = ws ? std::max(a.floats(B), fm_floats(B, Cin, Hin, Win)) : a.floats(B);
+    const size_t act_floats = a.floats(B);
     HIP_OK(hipMalloc(&act, act_floats * sizeof(float)));
     HIP_OK(hipMemsetAsync(act, 0, act_floats * sizeof(float), c->stream));
     a.p = act;
     const TDesc i0 = unpadded(const_cast<float *>(in0_dev), C0, Hin, Win);
     const TDesc i1 = in1_dev ? unpadded(const_cast<float *>(in1_dev), C1, Hin, Win) : kNone;
     if (range_reset(c)) return -1;
-    launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, gn_scale_dev ? (swish ? 2 : 1) : 0, ws ? 3 : (f8 ? 2 : c->prec), a,
+    launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, gn_scale_dev ? (swish ? 2 : 1) : 0, f8 ? 2 : c->prec, a,
                     c->stream, TDesc(), 0, c->d_ovf);
     const int pad = ks / 2, Hv = Hin << up2, Wv = Win << up2;
     ConvParams p;
@@ -1900,8 +1839,6 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     p.Hout = (Hv + 2 * pad - ks) / stride + 1; p.Wout = (Wv + 2 * pad - ks) / stride + 1;
     p.ks = ks; p.stride = stride; p.up2 = up2;
     p.prec = c->prec; p.w_unscale = w_unscale; p.f8 = f8 ? 1 : 0;
-    p.in_fm = ws ? 1 : 0;
-    if (ws) p.tile_cnt = c->tile_cnt;       // (the experiment's tile counters)
     p.w = dw; p.bias = db; p.chan_bias = chan_bias_dev; p.chan_bias_stride = Cout;
     (wfrag ? p.w_wino_f : p.w_wino) = dww;
     p.wino_ws = dws;
@@ -1965,9 +1902,7 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     float *w, *bias, *sc, *sh, *cb;
     HIP_OK(hipMalloc(&i0.p, i0.floats(B) * 4));
     if (C1) HIP_OK(hipMalloc(&i1.p, i1.floats(B) * 4));
-    const bool ws_probe = c->prec == 1 && !(c->f8corr && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin)) &&
-                          ks == 3 && stride == 1 && !up2 && C1 == 0 && !with_resid && conv_ws_shape_ok(B, Hin, Win, Cin, Cout);
-    HIP_OK(hipMalloc(&act.p, std::max(act.floats(B), ws_probe ? fm_floats(B, Cin, Hin, Win) : (size_t)0) * 4));
+    HIP_OK(hipMalloc(&act.p, act.floats(B) * 4));
     HIP_OK(hipMalloc(&out.p, out.floats(B) * 4));
     HIP_OK(hipMalloc(&res.p, res.floats(B) * 4));
     HIP_OK(hipMalloc(&w, n_w * 4));
@@ -1985,8 +1920,6 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     p.prec = c->prec;
     const bool f8 = c->prec == 1 && c->f8corr && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin);
     p.f8 = f8 ? 1 : 0;       // (timing: the operand bytes are random either way)
-    p.in_fm = ws_probe ? 1 : 0;
-    if (ws_probe) p.tile_cnt = c->tile_cnt;
     p.chan_bias = with_chan_bias ? cb : nullptr; p.chan_bias_stride = Cout;
     if (with_resid) p.resid = res;
     p.out = out;
@@ -2018,7 +1951,7 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     HIP_OK(hipEventRecord(e0, c->stream));
     for (int i = 0; i < iters; ++i) go();
     HIP_OK(hipEventRecord(e1, c->stream));
-    for (int i = 0; i < iters; ++i) launch_gn_apply(i0, C1 ? i1 : kNone, B, sc, sh, mode, ws_probe ? 3 : (f8 ? 2 : c->prec), act, c->stream);
+    for (int i = 0; i < iters; ++i) launch_gn_apply(i0, C1 ? i1 : kNone, B, sc, sh, mode, f8 ? 2 : c->prec, act, c->stream);
     HIP_OK(hipEventRecord(e2, c->stream));
     HIP_OK(hipEventSynchronize(e2));
     float ms = 0.f;

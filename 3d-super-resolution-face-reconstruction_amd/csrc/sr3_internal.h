@@ -8,22 +8,14 @@
 namespace sr3 {
 
 // ---- environment switches ---------------------------------------------------------------------------
-// PRODUCT switches (INTEGRATION.md lists them; each is read once per process and then baked into captured graphs):
+// Everything the library reads from the environment (INTEGRATION.md lists the same five; each is read once per process
+// and then baked into captured graphs):
 //   SR3_NO_GRAPH=1          every kernel launched individually, no hipGraph replay (hosts that cannot capture)
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
 //   SR3_HALO_SPLITS=0|2|4   in-place split-K of deep-K convs on 128x128 x-halo tiles: off / forced
 //   SR3_NO_INPLACE_SPLIT=1  split-K always as conv + reduce kernel
 //   SR3_NO_WINOGRAD=1       exact-f32 3x3 convs always on the direct implicit-GEMM kernel (conv_wino_supported)
-// Everything else is an A/B switch of the development build (-DSR3_EXPERIMENTS, build.py --experiments): the product
-// library does not read those variables at all, so a stray one cannot change kernels or numerics.
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-#ifdef SR3_EXPERIMENTS
-inline int exp_int(const char *name, int dflt) { return env_int(name, dflt); }
-inline double exp_double(const char *name, double dflt) { const char *e = getenv(name); return e ? atof(e) : dflt; }
-#else
-inline int exp_int(const char *, int dflt) { return dflt; }
-inline double exp_double(const char *, double dflt) { return dflt; }
-#endif
 
 // Activation tensor: NHWC fp32 with an optional 1-pixel zero border ("pad") stored around every
 // image, so a 3x3 window never needs a bounds check: pixel (n, y, x) lives at
@@ -108,33 +100,12 @@ struct ConvParams {
     // nullptr: always the two-kernel form.
     unsigned *tile_cnt = nullptr;
     // 1: never the in-place split-K of the 128x128 x-halo tile (conv_halo_splits) — set for the rest of a context's
-    // life once one of its bounded inter-block waits gave up (SR3_FLAG_GNF_TIMEOUT): the conv then runs unsplit on the
+    // life once one of its bounded inter-block waits gave up (SR3_FLAG_WAIT_TIMEOUT): the conv then runs unsplit on the
     // generic 64x64 tile, whose blocks never wait for each other
     int no_halo_split = 0;
-    // 1: in0 is stored FRAGMENT-MAJOR (fm_* below) — the input layout of the weights-stationary kernel
-    // (kernels_conv_ws.hip); launch_conv runs such a conv on that kernel or reports an error, never on another one
-    int in_fm = 0;
     // split-f16 range check: any value stored in the split format (out_split) with |v| > 65504 (or
     // non-finite) sets *ovf = 1; the API call that ran the launch then fails (never a silent clamp)
     int *ovf = nullptr;
-    // Producer-side GroupNorm of the OUTPUT (gnf_gamma != nullptr): the output h of a ResnetBlock's first conv is read
-    // by nothing but block2's GroupNorm + Swish (unet.py:105-110, 84-87), so the conv normalises it ITSELF and stores
-    // swish(scale * h + shift) straight in the next conv's operand format (out_split = that conv's activated input,
-    // out_f32 = 0): h never reaches memory and no apply pass runs. Inside the launch the blocks of one (image, N-tile)
-    // group — they hold whole GroupNorm groups of that image between them — publish their fp64 partial statistics
-    // (ConvParams::stats, one slice per M-tile, write-through stores), count themselves on gnf_cnt[image * tilesN + nt];
-    // the block that arrives last folds the slices in slice order (bit-identical whichever block it is), publishes
-    // scale / shift in gnf_ab and signals; the others poll the counter (one lane, s_sleep) and fetch gnf_ab.
-    // Requirements (conv_gnf_supported): split-f16 x-halo kernel with 16x16x32 consumers, whole 128-row tiles inside one
-    // image, whole groups inside an N-tile, no split-K, and every group's blocks co-resident on their XCD (the block
-    // order is chosen for it: gnf_band).
-    const float *gnf_gamma = nullptr, *gnf_beta = nullptr;   // [Cout] of the GroupNorm that FOLLOWS this conv
-    int gnf_groups = 0;
-    float gnf_eps = 1e-5f;
-    unsigned *gnf_cnt = nullptr;       // per (image, N-tile) 64 words: [0] counter, [32] ready word (two cache lines), zero between launches
-    float *gnf_ab = nullptr;           // [B][Cout][2] scale | shift
-    int gnf_band = 0;                  // > 0: M-tiles of an image per XCD (band block order, set by launch_conv)
-    int dbg = 0;            // timing experiments only (tools/conv_bench.py); 0 in product code
     // Winograd F(2x2, 3x3) form of this conv (prec 0 only; launch_conv takes it where conv_wino_supported says so and
     // the conv uses nothing the Winograd path does not handle): transformed weights [16][Cout][CinPad]
     // (make_wino_weights) and a workspace of conv_wino_ws_floats() floats; either null: direct kernel
@@ -148,11 +119,11 @@ struct ConvParams {
     int zbatch = 1;
     size_t batch_in_stride = 0, batch_out_stride = 0;
 };
-// bit raised in *ConvParams::ovf when a bounded inter-block wait gives up (in-place split-K of the x-halo kernel; the
-// producer-side GroupNorm experiment): the launch's result is invalid; the API replays the work with
+// bit raised in *ConvParams::ovf when the bounded inter-block wait of the in-place split-K on x-halo tiles gives up (the
+// only such wait in the library): the launch's result is invalid; the API replays the work with
 // ConvParams::no_halo_split set (sr3_api.hip: range_read)
-constexpr int SR3_FLAG_GNF_TIMEOUT = 2;
-// bound of such a wait in ticks of s_memrealtime (constant 100 MHz on gfx950, MI355X_MICROARCH.md): 2^19 = 5.2 ms — the
+constexpr int SR3_FLAG_WAIT_TIMEOUT = 2;
+// bound of that wait in ticks of s_memrealtime (constant 100 MHz on gfx950, MI355X_MICROARCH.md): 2^19 = 5.2 ms — the
 // blocks of one tile are dispatched back to back and the whole conv takes < 0.1 ms on an idle chip
 constexpr long long SR3_WAIT_TICKS = 1ll << 19;
 // largest magnitude the split-f16 format (hi + lo, both fp16) can hold
@@ -191,22 +162,6 @@ void launch_conv(const ConvParams &p, hipStream_t s);
 // launch_conv never aborts the process: a request it cannot honour (a caller / library bug) launches nothing and leaves
 // a message here; returns it once (nullptr if none) — the C-ABI entry points fail the call with it
 const char *conv_take_error();
-// Weights-stationary kernel for the 64 -> 64 channel 3x3 convs of the full-resolution level (kernels_conv_ws.hip). Its
-// waves load their MFMA A fragments straight from memory, so the activated input is stored FRAGMENT-MAJOR ("FM"): the
-// zero-bordered tensor [B][H + 2][W + 2][C] regrouped per padded row into groups of 16 consecutive pixels, per group and
-// 32-channel chunk one 2 KB block  [hi | lo][q = 0..3][pixel 0..15][16 B]  — the 16 bytes (8 halfs of channel octet q) that
-// lane (pixel, q) of a 16x16x32 MFMA holds, so one fragment of 16 pixels is 1 KB of consecutive memory (a wave's load is
-// lane-linear: perfectly coalesced; the pixel-major layout costs the texture path 2.4x, profiles/README.md finding 66).
-// Rows are padded to whole groups; borders and group padding stay zero like every activation border.
-//   byte offset of (n, padded y, padded x, channel c), hi half of its octet:
-//     ((((n * (H + 2) + yp) * G + (xp >> 4)) * (C / 32) + (c >> 5)) * 2048 + ((c & 31) >> 3) * 256 + (xp & 15) * 16,  lo: + 1024
-__host__ __device__ inline int fm_groups(int W) { return (W + 2 + 15) >> 4; }                      // G: 16-pixel groups per padded row
-inline size_t fm_floats(int B, int C, int H, int W) { return (size_t)B * (H + 2) * fm_groups(W) * (C / 32) * 512; }
-// shape test shared by the engine (which writes the conv's input in FM form) and launch_conv: 3x3 / stride 1 / split-f16
-// conv of this shape runs on the weights-stationary kernel when its input is FM (ConvParams::in_fm)
-bool conv_ws_shape_ok(int B, int H, int W, int Cin, int Cout);
-bool conv_ws_supported(const ConvParams &p);
-void launch_conv_ws(const ConvParams &p, hipStream_t s);
 // Upsample (nearest x2) + conv3x3 (unet.py:58-65) as four sub-pixel phases: output pixels of
 // parity (py, px) see only a 2x2 window of the low-resolution input, with the 3x3 taps that land
 // on the same source pixel pre-added (make_up2_phase_weights) — 16 instead of 36 MACs per
@@ -250,10 +205,6 @@ int conv_splits(long M, int Cout, int Cin);
 // true when a split conv of this shape adds its partials in place (ConvParams::tile_cnt given): its fused statistics
 // then have the unsplit layout, HWo / conv_tile_m() slices per image; HWo = pixels of one image (and phase)
 bool conv_split_inplace(long M, int HWo, int Cout, int Cin, int phases = 1);
-// true when launch_conv can run this 3x3 / stride-1 / split-f16 conv with the producer-side GroupNorm of its output
-// (ConvParams::gnf_*): p as it will be launched, without the gnf fields
-bool conv_gnf_supported(const ConvParams &p, int groups);
-constexpr int CONV_GNF_COUNTERS = 8192;     // capacity of ConvParams::gnf_cnt (images x N-tiles of one launch)
 // K-splits of the 128x128 x-halo tile for deep-K 3x3 / stride-1 split-f16 convs over few tiles (kernels_conv.hip); <= 1: none
 int conv_halo_splits(long M, int H, int W, int Cout, int Cin);
 constexpr int CONV_TILE_COUNTERS = 8192;    // capacity of ConvParams::tile_cnt (tiles x phases of one launch)
@@ -280,8 +231,7 @@ void launch_groupnorm_finalize(const StatsRef &s0, int C0, const StatsRef &s1, i
 // out[n,y,x,:] = act(concat(in0,in1)[n,y,x,:] * scale[n,:] + shift[n,:]); mode 0 copy, 1 affine,
 // 2 affine + Swish. out.C == in0.C + in1.C; writes the interior only. split = 1 stores every
 // 32-channel chunk as 32 hi halfs | 32 lo halfs (the conv's prec 1 input format), split = 2 as
-// 32 hi halfs | 32 x e4m3(lo * 2^SR3_F8_XL) | 32 x e4m3(hi * 2^SR3_F8_XH) (ConvParams::f8; `raw` stays format 1),
-// split = 3 as format 1 in the fragment-major layout (fm_*: out.p must hold fm_floats(); ConvParams::in_fm).
+// 32 hi halfs | 32 x e4m3(lo * 2^SR3_F8_XL) | 32 x e4m3(hi * 2^SR3_F8_XH) (ConvParams::f8; `raw` stays format 1).
 // raw (optional, p != nullptr): additionally stores the un-normalised concatenation in the same
 // format (the input of a fused res_conv).
 // in_split: bit 0 / bit 1 = in0 / in1 is itself stored in the split-f16 format (split-only tensors)

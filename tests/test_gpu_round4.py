@@ -416,9 +416,7 @@ def test_conv_64_to_64_full_resolution_vs_oracle(case):
     """3x3 / stride 1 / 64 -> 64 channels over >= 2048 tiles of 128 pixels (unet.py:80-91 `Block` conv at the 128x128
     level: 2.1 ms of the B = 64 step, the shapes furthest below the roofline). With bias and the per-image
     FeatureWiseAffine bias (unet.py:34-50), GroupNorm + Swish in front as the engine runs it; f16x3 bar as for every
-    split-f16 conv: 2e-5 on O(1) outputs. The product library runs them on the x-halo kernel; the experiments build with
-    SR3_WS=1 on the weights-stationary persistent kernel of profiles/README.md finding 66 (kernels_conv_ws.hip) — the same
-    cases are its parity test (SR3_LIB=.../libsr3hip_exp.so SR3_WS=1 pytest -k conv_64_to_64)."""
+    split-f16 conv: 2e-5 on O(1) outputs. The library runs them on the x-halo kernel."""
     B, H, W = case
     e = pkg("engine").Engine(synth.tiny_unet_config(), 0)
     e.load_state_dict(synth.synth_state_dict(e.cfg, 11))

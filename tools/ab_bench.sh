@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of the B = 64 sampler step: alternating runs of bench.py under two environments.
-#   [PREC=f16f8] tools/ab_bench.sh "<env A>" "<env B>" [pairs] [extra bench args]     (e.g. "SR3_NO_F8C=1" "")
+#   [PREC=f16f8] tools/ab_bench.sh "<env A>" "<env B>" [pairs] [extra bench args]     (e.g. "SR3_LIB=/path/to/another/libsr3hip.so" "": another build of the library against this one)
 # PREC = arithmetic mode measured (default f16f8, the fastest; bench.py itself defaults to the reference's f32).
 # Prints ms_per_step and the per-family split of every run; run on the GPU box (gpurun).
 A="$1"; B="$2"; N="${3:-3}"; shift 3 || true

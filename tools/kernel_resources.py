@@ -2,7 +2,7 @@
 """Registers / LDS / occupancy of every kernel of one HIP source, from hipcc's own report
 (-Rpass-analysis=kernel-resource-usage). Cross-compiles, needs no GPU.
 
-    python tools/kernel_resources.py kernels_conv.hip [-DSR3_EXPERIMENTS]
+    python tools/kernel_resources.py kernels_conv.hip [extra hipcc flags]
 """
 import os
 import re
@@ -32,7 +32,7 @@ def main():
         dn = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         dn = dn.replace("sr3::(anonymous namespace)::", "").replace("(sr3::ConvParams)", "")
         print("%-72s vgpr %4s agpr %3s sgpr %3s spill %3s scratch %4s occ %2s lds %s" % (
-            dn[:72], field(b, "VGPRs"), field(b, "AGPRs"), field(b, "SGPRs"), field(b, "VGPR Spill"),
+            dn[:72], field(b, "VGPRs"), field(b, "AGPRs"), field(b, "SGPRs"), field(b, "VGPRs Spill"),
             field(b, "ScratchSize [bytes/lane]"), field(b, "Occupancy [waves/SIMD]"), field(b, "LDS Size [bytes/block]")))
 
 
