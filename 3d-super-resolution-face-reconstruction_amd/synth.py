@@ -48,6 +48,15 @@ def synth_noise(T: int, B: int, C: int, H: int, W: int, seed: int = 0) -> np.nda
     return np.random.RandomState(seed ^ 0xA015E).standard_normal((T, B, C, H, W)).astype(np.float32)
 
 
+def synth_unet_input(cfg: UNetConfig, B: int, H: int, W: int, seed: int = 0):
+    """Input of one UNet forward: x [B,in_channel,H,W] ~ N(0,1) and per-image noise levels [B,1] in [0.05, 1): the
+    stream tests/golden/make_golden.py::gen_unet draws from (fixtures that do not store `x` regenerate it here)."""
+    rs = np.random.RandomState(seed + 77)
+    x = rs.standard_normal((B, cfg.in_channel, H, W)).astype(np.float32)
+    nl = rs.uniform(0.05, 1.0, (B, 1)).astype(np.float32)
+    return x, nl
+
+
 # the reference's yml UNet (config/*.yml:35-48,60-63); image_size 224 is what every yml says,
 # 128 is BASELINE.json's "attention-heavy" reading (SURVEY.md §0)
 def yml_unet_config(image_size: int = 224) -> UNetConfig:
@@ -59,6 +68,26 @@ def yml_unet_config(image_size: int = 224) -> UNetConfig:
 def tiny_unet_config() -> UNetConfig:
     return UNetConfig(in_channel=6, out_channel=3, inner_channel=32, norm_groups=32,
                       channel_mults=(1, 2), attn_res=(8,), res_blocks=1, dropout=0.0, image_size=16)
+
+
+# Configurations off the yml ladder (tests/golden/unet_cfg{A,B,D}.npz are reference-made forwards of A, B and D):
+#   A  norm_groups 8, ladder 32/64/96: 160- and 96+64-channel concatenations whose 20-channel groups straddle the two
+#      sources, 96-channel attention at two levels
+#   B  inner_channel 96, norm_groups 16 (groups of 6 and 12 channels), 192-channel attention, one ResnetBlock per level
+#   C  repeated multipliers (identity-skip ResnetBlocks on the down path), five levels, three ResnetBlocks per level
+#   D  unconditional (in_channel == out_channel), 128/256/512 channels
+def sweep_unet_config(name: str) -> UNetConfig:
+    table = {
+        "A": dict(in_channel=6, out_channel=3, inner_channel=32, norm_groups=8, channel_mults=(1, 2, 3),
+                  attn_res=(24, 12), res_blocks=2, image_size=48),
+        "B": dict(in_channel=6, out_channel=3, inner_channel=96, norm_groups=16, channel_mults=(1, 2),
+                  attn_res=(16,), res_blocks=1, image_size=32),
+        "C": dict(in_channel=6, out_channel=3, inner_channel=64, norm_groups=32, channel_mults=(1, 1, 2, 2, 4),
+                  attn_res=(16,), res_blocks=3, image_size=64),
+        "D": dict(in_channel=3, out_channel=3, inner_channel=128, norm_groups=32, channel_mults=(1, 2, 4),
+                  attn_res=(8,), res_blocks=2, image_size=32),
+    }
+    return UNetConfig(dropout=0.0, **table[name])
 
 
 def yml_opt(l: int, r: int, n_timestep: int, image_size: int = 224, phase: str = "val") -> dict:

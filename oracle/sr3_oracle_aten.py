@@ -28,8 +28,9 @@ noise_schedule = _np_oracle.noise_schedule
 unet_plan = _np_oracle.unet_plan
 
 
-def to_torch_state(sd: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
-    return {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}
+def to_torch_state(sd: Dict[str, np.ndarray], dtype: torch.dtype = torch.float32) -> Dict[str, torch.Tensor]:
+    """dtype=torch.float64: the same (float32) weights widened exactly, for the float64 run of unet_forward."""
+    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(dtype) for k, v in sd.items()}
 
 
 def swish(x):                                                                    # unet.py:53-55
@@ -71,10 +72,13 @@ def self_attention(sd, p, x, groups):                                           
 
 
 def unet_forward(sd: Dict[str, torch.Tensor], cfg, x, noise_level, prefix: str = "",
-                 taps: Optional[dict] = None) -> torch.Tensor:
-    """UNet.forward, unet.py:235-265; NCHW torch tensors, sd from to_torch_state()."""
+                 taps: Optional[dict] = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """UNet.forward, unet.py:235-265; NCHW torch tensors, sd from to_torch_state().
+    dtype=torch.float64 (with sd from to_torch_state(sd, torch.float64)) computes the same network on the same float32
+    inputs and weights, widened exactly, in float64 throughout: the high-precision yardstick of the GPU tests."""
     g = cfg.norm_groups
-    t = positional_encoding(noise_level.reshape(-1).to(torch.float32), cfg.inner_channel)
+    x = x.to(dtype)
+    t = positional_encoding(noise_level.reshape(-1).to(dtype), cfg.inner_channel)
     t = swish(F.linear(t, sd[prefix + "noise_level_mlp.1.weight"], sd[prefix + "noise_level_mlp.1.bias"]))
     temb = F.linear(t, sd[prefix + "noise_level_mlp.3.weight"], sd[prefix + "noise_level_mlp.3.bias"])
     downs, mid, ups = unet_plan(cfg)

@@ -36,7 +36,8 @@ def opt_from_cfg(cfg, sched, conditional=True):
     return {"phase": "val", "sr": {"model": {
         "which_model_G": "sr3",
         "unet": {"in_channel": cfg.in_channel, "out_channel": cfg.out_channel,
-                 "inner_channel": cfg.inner_channel, "channel_multiplier": list(cfg.channel_mults),
+                 "inner_channel": cfg.inner_channel, "norm_groups": cfg.norm_groups,
+                 "channel_multiplier": list(cfg.channel_mults),
                  "attn_res": list(cfg.attn_res), "res_blocks": cfg.res_blocks, "dropout": cfg.dropout},
         "beta_schedule": {"train": dict(sched), "val": dict(sched)},
         "diffusion": {"image_size": cfg.image_size, "channels": 3, "conditional": conditional}}}}
@@ -106,14 +107,15 @@ def gen_schedules():
     save("schedules.npz", **out)
 
 
-def gen_unet(name, cfg, B, r, seed, with_taps=False):
+def gen_unet(name, cfg, B, r, seed, with_taps=False, store_x=True):
+    """r: side of a square input, or (H, W). store_x=False keeps the fixture small: the tests regenerate the input with
+    synth.synth_unet_input (the same frozen stream)."""
+    H, W = (r, r) if isinstance(r, int) else r
     t0 = time.time()
     sched = {"schedule": "linear", "n_timestep": 10, "linear_start": 1e-4, "linear_end": 2e-2}
     netG = build_ref(cfg, sched, seed)
-    rs = np.random.RandomState(seed + 77)
-    x = rs.standard_normal((B, cfg.in_channel, r, r)).astype(np.float32)
-    nl = rs.uniform(0.05, 1.0, (B, 1)).astype(np.float32)
-    arrs = {"x": x, "noise_level": nl}
+    x, nl = synth.synth_unet_input(cfg, B, H, W, seed)
+    arrs = {"x": x, "noise_level": nl} if store_x else {"noise_level": nl}
     unet = netG.denoise_fn
     if with_taps:
         hooks = []
@@ -194,6 +196,12 @@ if __name__ == "__main__":
         # BASELINE.json config 3 ("attention-heavy"): image_size=128 puts attention at the 16x16 level
         # (N = 256 tokens x 5 modules + mid), reference placement logic unet.py:192-207
         print("unet 128-variant r=128"); gen_unet("unet_yml128_r128.npz", synth.yml_unet_config(128), B=1, r=128, seed=8)
+    # configurations off the yml ladder (synth.sweep_unet_config): norm_groups 8 / 16, 96- and 160-channel tensors,
+    # non-square inputs, the unconditional form
+    for tag, B, hw, seed in (("A", 3, (48, 80), 12), ("B", 5, (24, 40), 13), ("D", 4, (32, 32), 14)):
+        if only(f"unet_cfg{tag}.npz"):
+            print(f"unet config {tag}"); gen_unet(f"unet_cfg{tag}.npz", synth.sweep_unet_config(tag), B=B, r=hw, seed=seed,
+                                                     store_x=False)
     if only("sampler_tiny.npz"):
         s20 = {"schedule": "linear", "n_timestep": 20, "linear_start": 1e-4, "linear_end": 2e-2}
         print("sampler tiny"); gen_sampler("sampler_tiny.npz", tiny, s20, B=2, r=16, l=8, seed=5)

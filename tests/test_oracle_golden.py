@@ -110,6 +110,49 @@ def test_aten_unet_forward_matches_reference(name, tol):
     np.testing.assert_allclose(eps, g["eps"], atol=tol, rtol=0)
 
 
+@pytest.mark.parametrize("tag", ["A", "B", "D"])
+def test_sweep_configs_match_reference(tag):
+    """Configurations off the yml ladder (synth.sweep_unet_config: norm_groups 8 / 16, 96- and 160-channel tensors,
+    non-square inputs, the unconditional form), reference-made by make_golden.py with norm_groups passed through
+    (model/sr/networks.py:89-94). Both float32 oracles at this file's forward bar; the float64 run of the aten oracle
+    (the yardstick of tests/test_gpu_config_sweep.py) is no further from the reference than the float32 one + 1e-6."""
+    import torch
+    g = load_golden(f"unet_cfg{tag}.npz")
+    m = g["meta"]
+    cfg = cfg_from_meta(m)
+    assert cfg == synth.sweep_unet_config(tag)
+    H, W = m["r"]
+    x, nl = synth.synth_unet_input(cfg, m["B"], H, W, m["seed"])
+    np.testing.assert_array_equal(nl, g["noise_level"])
+    assert g["eps"].shape == (m["B"], cfg.out_channel, H, W)
+    sd = synth.synth_state_dict(cfg, m["seed"])
+    e_np = np.abs(oracle.unet_forward(sd, cfg, x, nl) - g["eps"]).max()
+    with torch.no_grad():
+        y32 = aten.unet_forward(aten.to_torch_state(sd), cfg, torch.from_numpy(x), torch.from_numpy(nl))
+        y64 = aten.unet_forward(aten.to_torch_state(sd, torch.float64), cfg, torch.from_numpy(x), torch.from_numpy(nl),
+                                dtype=torch.float64)
+    assert y32.dtype == torch.float32 and y64.dtype == torch.float64
+    e32 = np.abs(y32.numpy() - g["eps"]).max()
+    e64 = np.abs(y64.numpy() - g["eps"]).max()
+    print(f"config {tag}: numpy {e_np:.2e}  aten f32 {e32:.2e}  aten f64 {e64:.2e} vs reference")
+    assert e_np <= 2e-5 and e32 <= 2e-5
+    assert e64 <= e32 + 1e-6
+
+
+def test_float64_oracle_runs_config_C():
+    """Config C (repeated multipliers: identity-skip blocks on the down path; five levels) has no reference-made
+    fixture; its float64 oracle run is held to the float32 numpy oracle, an independent restatement."""
+    import torch
+    cfg = synth.sweep_unet_config("C")
+    sd = synth.synth_state_dict(cfg, 15)
+    x, nl = synth.synth_unet_input(cfg, 1, 32, 48, 15)
+    with torch.no_grad():
+        y64 = aten.unet_forward(aten.to_torch_state(sd, torch.float64), cfg, torch.from_numpy(x), torch.from_numpy(nl),
+                                dtype=torch.float64).numpy()
+    assert y64.dtype == np.float64
+    assert np.abs(oracle.unet_forward(sd, cfg, x, nl) - y64).max() <= 2e-5
+
+
 @pytest.mark.parametrize("name", ["sampler_tiny.npz", "sampler_uncond_tiny.npz", "sampler_cfg1_8_16.npz"])
 def test_aten_sampler_matches_reference(name):
     g = load_golden(name)
