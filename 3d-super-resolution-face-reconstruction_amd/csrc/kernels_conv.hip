@@ -97,7 +97,7 @@ __device__ __forceinline__ void dma16s(const char *sbase, unsigned voff, float *
     }
 }
 
-// KS: 1 | 2 | 3 (the tap loop is unrolled); nearest x2 upsampling never reaches the kernel (launch_conv_up2)
+// KS: 1 | 2 | 3 (the tap loop is unrolled); nearest x2 upsampling never reaches the kernel (launch_conv: phase_form)
 // m / (Hout*Wout) and rem / Wout of the tile address set-up: shifts when the sizes are powers of two
 __device__ __forceinline__ int div_hw(const ConvParams &p, int m, int HWo) { return p.hw_shift >= 0 ? (m >> p.hw_shift) : m / HWo; }
 __device__ __forceinline__ int div_w(const ConvParams &p, int rem, int W) { return p.w_shift >= 0 ? (rem >> p.w_shift) : rem / W; }
@@ -1557,22 +1557,11 @@ void launch_halo(const ConvParams &p, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3(grid, 1, p.phases), dim3(512), lds, s, p);
 }
 
-// SR3_NO_HALO=1 (product safety switch): no x-halo kernel anywhere — and therefore no F8C path and no halo split-K
-static bool halo_off() {
-    static const int off = env_int("SR3_NO_HALO", 0);
-    return off != 0;
-}
-
-// preconditions of the x-halo kernel for tile height BM
-static bool halo_ok(const ConvParams &p, int BM, int segmin, int bn, bool split_ok = false) {
-    if (halo_off() || p.prec != 1 || (p.ks != 3 && p.ks != 2) || p.stride != 1 || p.up2 || (p.splits > 1 && !split_ok) || p.in0.pad != 1) return false;
-    const int W = p.Wout;
-    if (p.in0.W != W || p.in0.H != p.Hout) return false;
-    const int seg = W < BM ? W : BM;
-    if (seg < segmin || (W % seg) || (BM % seg)) return false;
-    const long M = (long)p.B * p.Hout * W;
-    // no masking anywhere in the halo kernels: whole tiles in M and (for the tile width bn the caller picks) in N
-    return (M % BM) == 0 && (p.out.C % bn) == 0 && (!p.in2.p || (p.in2.C % 32) == 0) && (!p.in2b.p || (p.in2b.C % 32) == 0);
+// the 128-row x-halo tile of width BN: 3x3 | the 2x2 window of an upsample phase; spk: in-place split-K (3x3, BN 128 only)
+template <int BN, int SEGMIN>
+void launch_halo_tile(const ConvParams &p, bool spk, hipStream_t s) {
+    if constexpr (BN == 128) { if (spk) return launch_halo<128, 128, 4, 1, SEGMIN, 3, 16, true>(p, s); }
+    if (p.ks == 3) launch_halo<128, BN, 4, 1, SEGMIN, 3, 16>(p, s); else launch_halo<128, BN, 4, 1, SEGMIN, 2, 16>(p, s);
 }
 
 template <int BM, int BN, int WGM, int WGN, int KS, int PREC, int NS, bool ZB = false>
@@ -1590,25 +1579,20 @@ void launch_inst2(const ConvParams &p, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3(tilesM * tilesN, p.splits > 1 ? p.splits : 1, ZB ? p.zbatch : p.phases), dim3(512), lds, s, p);
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, int PREC>
-void launch_inst(const ConvParams &p, hipStream_t s) {
+template <int BM, int BN, int WGM, int WGN>
+void launch_cfg(const ConvParams &p, hipStream_t s) {
     // stages per tile shape (A/B in profiles/README.md): the 64x64 tile is used where few blocks
     // are resident (small M), so it gets a 4-deep ring (2 blocks/CU); the larger tiles run 2-3
     // blocks per CU with 2 stages (3 stages x 2 blocks measured the same or slower)
     constexpr int NS = (BM + BN) <= 128 ? 4 : 2;
-    launch_inst2<BM, BN, WGM, WGN, KS, PREC, NS>(p, s);
-}
-
-template <int BM, int BN, int WGM, int WGN>
-void launch_cfg(const ConvParams &p, hipStream_t s) {
     if (p.prec == 0) {
-        if (p.ks == 1) launch_inst<BM, BN, WGM, WGN, 1, 0>(p, s);
-        else if (p.ks == 2) launch_inst<BM, BN, WGM, WGN, 2, 0>(p, s);
-        else launch_inst<BM, BN, WGM, WGN, 3, 0>(p, s);
+        if (p.ks == 1) launch_inst2<BM, BN, WGM, WGN, 1, 0, NS>(p, s);
+        else if (p.ks == 2) launch_inst2<BM, BN, WGM, WGN, 2, 0, NS>(p, s);
+        else launch_inst2<BM, BN, WGM, WGN, 3, 0, NS>(p, s);
     } else {
-        if (p.ks == 1) launch_inst<BM, BN, WGM, WGN, 1, 1>(p, s);
-        else if (p.ks == 2) launch_inst<BM, BN, WGM, WGN, 2, 1>(p, s);
-        else launch_inst<BM, BN, WGM, WGN, 3, 1>(p, s);
+        if (p.ks == 1) launch_inst2<BM, BN, WGM, WGN, 1, 1, NS>(p, s);
+        else if (p.ks == 2) launch_inst2<BM, BN, WGM, WGN, 2, 1, NS>(p, s);
+        else launch_inst2<BM, BN, WGM, WGN, 3, 1, NS>(p, s);
     }
 }
 
@@ -1697,30 +1681,32 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParam
 }
 
 // pixels per block of the split-K reduce (at most 64 statistics slices per image and phase)
-int splitk_reduce_tp(int HWo) { const int tp = HWo / 64; return tp < 1 ? 1 : tp; }
-// 0: the reduce pass cannot produce the statistics of this shape (the caller's statistics kernel runs)
-int splitk_stats_slices(int HWo, int Cout) {
+static int splitk_reduce_tp(int HWo) { const int tp = HWo / 64; return tp < 1 ? 1 : tp; }
+// a split conv's fused GroupNorm statistics come out of its reduce pass: slices per image (and per sub-pixel phase)
+// for an output of HWo pixels; 0: the reduce pass cannot produce the statistics of this shape
+static int splitk_stats_slices(int HWo, int Cout) {
     const int tp = splitk_reduce_tp(HWo);
     return ((HWo % tp) == 0 && Cout <= 1024 && (Cout & 3) == 0) ? HWo / tp : 0;
 }
 
-// tile choice: 0 = 128x32, 1 = 128x64, 2 = 64x64, 3 = 128x128
-static int conv_tile_choice(long M, int Cout) {
+// ---- the dispatch plan ---------------------------------------------------------------------------------------------
+// tile of the generic kernel (and of the x-halo kernel that replaces it where its preconditions hold)
+struct Tile { ConvKernel generic; int bm, bn; };
+static Tile conv_tile_choice(long M, int Cout) {
     auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((Cout + bn - 1) / bn); };
     const long want = 512;  // 256 CUs x 2 resident blocks
-    if (Cout <= 32) return 0;
-    if (Cout <= 64 || (Cout % 128) != 0) return blocks(128, 64) >= want ? 1 : 2;
-    if (blocks(128, 128) >= want) return 3;
-    return blocks(128, 64) >= want ? 1 : 2;
+    const Tile t32 = {CK_GENERIC_128x32, 128, 32}, t64 = {CK_GENERIC_128x64, 128, 64}, t6464 = {CK_GENERIC_64x64, 64, 64};
+    if (Cout <= 32) return t32;
+    if (Cout <= 64 || (Cout % 128) != 0) return blocks(128, 64) >= want ? t64 : t6464;
+    if (blocks(128, 128) >= want) return Tile{CK_GENERIC_128x128, 128, 128};
+    return blocks(128, 64) >= want ? t64 : t6464;
 }
+static long tile_count(const Tile &t, long M, int Cout) { return ((M + t.bm - 1) / t.bm) * ((Cout + t.bn - 1) / t.bn); }
 
-int conv_tile_m(long M, int Cout) { return conv_tile_choice(M, Cout) == 2 ? 64 : 128; }
-
-int conv_splits(long M, int Cout, int Cin) {
+// K-splits of the generic kernel for small problems (1 = none); Cin per tap, multiple of 32
+static int conv_splits(long M, int Cout, int Cin) {
     if (Cout & 3) return 1;
-    static const int bm[4] = {128, 128, 64, 128}, bn[4] = {32, 64, 64, 128};
-    const int t = conv_tile_choice(M, Cout);
-    const long tiles = ((M + bm[t] - 1) / bm[t]) * ((Cout + bn[t] - 1) / bn[t]);
+    const long tiles = tile_count(conv_tile_choice(M, Cout), M, Cout);
     const int nchunk = Cin / BK;
     // (tuned on B = 1 at 128x128 and config 1, with the in-place fix-up: profiles/README.md finding 42)
     constexpr int tmin = 256, target = 256, chmin = 2;
@@ -1730,13 +1716,19 @@ int conv_splits(long M, int Cout, int Cin) {
     return s;
 }
 
+// SR3_NO_HALO=1 (product safety switch): no x-halo kernel anywhere — and therefore no F8C path and no halo split-K
+static bool halo_off() {
+    static const int off = env_int("SR3_NO_HALO", 0);
+    return off != 0;
+}
+
 // Deep-K 3x3 / stride-1 split-f16 convs over FEW output tiles (the 8x8 level at B = 64: M = 4096 pixels, 512 channels):
 // instead of 64x64 tiles of the generic kernel (LDS traffic per MFMA twice that of a 128x128 tile) they run on the
 // 128x128 x-halo tile with the K range split over `return value` blocks per tile, added IN PLACE by the block that
 // arrives last (conv3x3_halo_h3, end of the consumer path) — no reduce pass, statistics in the unsplit layout (one
 // slice per 128-row tile, or one per image where a tile covers several whole images). 0 or 1: not for this shape.
-// Assumes ks 3, stride 1, prec 1, pad 1 (launch_conv checks them); sr3_api.hip sizes the partial buffer with it.
-int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
+// Assumes ks 3, stride 1, prec 1, pad 1 (conv_plan checks them).
+static int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
     static const int force = env_int("SR3_HALO_SPLITS", -1);    // product switch: 0 off, 2 | 4 forced
     if (force == 0 || halo_off()) return 0;
     const int HWo = H * W;
@@ -1744,7 +1736,7 @@ int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
     const int seg = W < 128 ? W : 128;
     if ((W % seg) || (128 % seg)) return 0;
     if (HWo >= 128 ? (HWo % 128) != 0 : ((128 % HWo) != 0 || (HWo % 32) != 0)) return 0;
-    if (conv_tile_choice(M, Cout) != 2) return 0;                  // enough 128-row tiles already: no split needed
+    if (conv_tile_choice(M, Cout).generic != CK_GENERIC_64x64) return 0;   // enough 128-row tiles already: no split needed
     const long tiles = (M / 128) * (Cout / 128);
     const int nchunk = Cin / 32;
     if (tiles < 64 || tiles > CONV_TILE_COUNTERS || nchunk < 8) return 0;
@@ -1754,31 +1746,177 @@ int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
     return sp;
 }
 
+// preconditions of the x-halo kernel for tile height BM: p after the phase transform, splits = the plan's
+static bool halo_ok(const ConvParams &p, int splits, int BM, int segmin, int bn, bool split_ok = false) {
+    if (halo_off() || p.prec != 1 || (p.ks != 3 && p.ks != 2) || p.stride != 1 || p.up2 || (splits > 1 && !split_ok) || p.in0.pad != 1) return false;
+    const int W = p.Wout;
+    if (p.in0.W != W || p.in0.H != p.Hout) return false;
+    const int seg = W < BM ? W : BM;
+    if (seg < segmin || (W % seg) || (BM % seg)) return false;
+    const long M = (long)p.B * p.Hout * W;
+    // no masking anywhere in the halo kernels: whole tiles in M and (for the tile width bn the caller picks) in N
+    return (M % BM) == 0 && (p.out.C % bn) == 0 && (!p.in2.p || (p.in2.C % 32) == 0) && (!p.in2b.p || (p.in2b.C % 32) == 0);
+}
+
+// ---- Winograd gates (the kernels are in kernels_wino.hip) ----
+// one-pass kernel: 64x64 pixels and up, whole strips per tile row, whole channel blocks, and enough blocks to fill the
+// chip (fewer: the direct kernel, whose smaller tiles spread further)
+static bool wino_fused_shape(int B, int H, int W, int Cin, int Cout) {
+    if (H * W < 4096 || (H & 1) || (W % (2 * WINO_FUSED_TILES)) || Cin < WINO_FUSED_CIN || (Cin % 32) || (Cout % WINO_FUSED_BN)) return false;
+    const uint64_t blocks = (uint64_t)B * (H / 2) * (W / (2 * WINO_FUSED_TILES)) * (Cout / WINO_FUSED_BN);
+    return blocks >= WINO_FUSED_MIN_BLOCKS;
+}
+
+// shape rule (3x3 / stride 1 / prec 0 convs): false also under SR3_NO_WINOGRAD=1
+static bool wino_shape(int B, int H, int W, int Cin, int Cout) {
+    static const bool off = env_int("SR3_NO_WINOGRAD", 0) != 0;    // product switch (read once)
+    if (off || B <= 0) return false;
+    if (wino_fused_shape(B, H, W, Cin, Cout)) return true;
+    if ((H & 1) || (W & 1) || H * W > 1024 || Cin < WINO_MIN_CIN || (Cin % 32) || (Cout % 64)) return false;
+    // few tiles (a single 128x128 image: 256 at its 32x32 level): the three dependent passes cost more latency than the
+    // MACs they save (B = 1 step 1.99 -> 2.27 ms with every level in Winograd form); B = 64 at 8x8 is 1024 tiles and gains
+    const uint64_t tiles = (uint64_t)B * (H / 2) * (W / 2);
+    if (tiles < WINO_MIN_TILES) return false;
+    // the LDS-DMA and epilogue addressing of the position GEMMs uses 32-bit byte offsets inside one position's plane
+    return tiles * (uint64_t)(Cin > Cout ? Cin : Cout) * 4 < (1ull << 32);
+}
+
+// the Winograd form this conv runs in, CK_COUNT: none (the direct kernels)
+static ConvKernel wino_form(const ConvParams &p) {
+    if (p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.f8) return CK_COUNT;
+    if (p.out_split.p || !p.out_f32 || p.resid_split) return CK_COUNT;
+    if (p.in0.pad != 1 || p.in0.H != p.Hout || p.in0.W != p.Wout) return CK_COUNT;
+    if (p.in1.p && (p.in1.pad != 1 || p.in1.H != p.Hout || p.in1.W != p.Wout)) return CK_COUNT;
+    if (p.in2.p && !p.w2) return CK_COUNT;
+    const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
+    if (!wino_shape(p.B, p.Hout, p.Wout, Cin, p.out.C)) return CK_COUNT;
+    if (wino_fused_shape(p.B, p.Hout, p.Wout, Cin, p.out.C)) {
+        // one input tensor: the engine concatenates x || skip in the GroupNorm apply pass that writes the conv's input,
+        // so no caller hands these convs a second tensor (one that does gets the direct kernel)
+        if (!p.w_wino_f || p.in1.p) return CK_COUNT;
+        // the statistics slices must be whole strips or 2 | 4 equal parts of one
+        const int spi = (p.Hout / 2) * (p.Wout / (2 * WINO_FUSED_TILES));
+        if (p.stats == nullptr) return CK_WINO_ONE_PASS;
+        if (p.stats_slices <= 0 || (p.stats_slices % spi)) return CK_COUNT;
+        const int spb = p.stats_slices / spi;
+        return (spb == 1 || spb == 2 || spb == 4) ? CK_WINO_ONE_PASS : CK_COUNT;
+    }
+    if (!p.w_wino || !p.wino_ws) return CK_COUNT;
+    const int tiles = (p.Hout >> 1) * (p.Wout >> 1);
+    return (p.stats == nullptr || (p.stats_slices > 0 && (tiles % p.stats_slices) == 0)) ? CK_WINO_THREE_PASS : CK_COUNT;
+}
+
+// p as the kernels see it: an upsample conv becomes its four sub-pixel phases over the low-resolution pixels (one
+// launch: blockIdx.z picks (py, px)); splits / phase_slices / phase_part_stride are the plan's to fill
+static ConvParams phase_form(const ConvParams &p_in) {
+    ConvParams p = p_in;
+    if (!p.up2) return p;
+    p.ks = 2; p.stride = 1; p.up2 = 0;
+    p.Hout = p_in.Hout / 2; p.Wout = p_in.Wout / 2;
+    p.out_step = 2;
+    p.phases = 4;
+    p.phase_w_stride = (size_t)4 * p.out.C * (p.in0.C + (p.in1.p ? p.in1.C : 0));
+    return p;
+}
+
+const char *conv_kernel_name(ConvKernel k) {
+    static const char *const names[CK_COUNT] = {"wino_one_pass", "wino_three_pass", "halo_f8c", "halo_128x128_seg32", "halo_128x128_seg8",
+                                                "halo_128x64", "generic_128x32", "generic_128x64", "generic_64x64", "generic_128x128"};
+    return (unsigned)k < (unsigned)CK_COUNT ? names[k] : "?";
+}
+
+ConvPlan conv_plan(const ConvParams &p_in) {
+    const ConvParams p = phase_form(p_in);
+    const int Cout = p.out.C, Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
+    const int HWo = p.Hout * p.Wout;                 // pixels of one image (and phase)
+    const long M = (long)p.B * HWo;
+    const Tile t = conv_tile_choice(M, Cout);
+    ConvPlan plan;
+    plan.phases = p.phases;
+    plan.tile_m = t.bm; plan.tile_n = t.bn;
+    // split-K of the generic kernel: in place on the 64x64 tile where every tile has a counter, whole tiles per image (the
+    // statistics slices are per M-tile of an image) and in N (nothing is masked in the fix-up); else conv + reduce kernel
+    static const int no_inplace = env_int("SR3_NO_INPLACE_SPLIT", 0);
+    const int gs = p.part ? conv_splits(M, Cout, Cin) : 1;
+    const bool inplace = gs > 1 && p.tile_cnt && !no_inplace && t.generic == CK_GENERIC_64x64 && (HWo % t.bm) == 0 && (Cout % t.bn) == 0 &&
+                         tile_count(t, M, Cout) * p.phases <= CONV_TILE_COUNTERS;
+    // fused statistics: one slice per M-tile of an image (an in-place split conv leaves the same slices as an unsplit
+    // one; every kernel of one output shape uses the same tile height), a two-kernel split one slice per reduce block
+    plan.stats_slices = p.phases * ((gs > 1 && !inplace) ? splitk_stats_slices(HWo, Cout) : (HWo % t.bm) == 0 ? HWo / t.bm : 0);
+
+    const ConvKernel wino = wino_form(p);
+    if (wino != CK_COUNT) {
+        plan.kernel = wino;
+        plan.needs_wino_frag = wino == CK_WINO_ONE_PASS;       // (U and M never leave the CU)
+        if (wino == CK_WINO_THREE_PASS) plan.wino_ws_floats = (size_t)16 * p.B * (p.Hout / 2) * (p.Wout / 2) * (Cin + Cout);
+        return plan;
+    }
+    auto split = [&](ConvSplit kind, int splits) {
+        plan.split = kind; plan.splits = splits;
+        plan.part_floats = (size_t)p.phases * splits * M * Cout;
+        plan.needs_counters = kind != CS_REDUCE;
+    };
+    if (p.prec == 1 && p.ks == 3 && p.stride == 1 && p.phases == 1 && p.part != nullptr && p.tile_cnt != nullptr && p.in0.pad == 1 &&
+        p.in0.W == p.Wout && p.in0.H == p.Hout && !p.no_halo_split) {
+        const int hs = conv_halo_splits(M, p.Hout, p.Wout, Cout, Cin);
+        const bool stats_ok = p.stats == nullptr || p.stats_slices == (HWo >= 128 ? HWo / 128 : 1);
+        const bool seg32 = halo_ok(p, hs, 128, 32, 128, true);
+        if (hs > 1 && stats_ok && (seg32 || halo_ok(p, hs, 128, 8, 128, true))) {
+            plan.kernel = seg32 ? CK_HALO_128x128_SEG32 : CK_HALO_128x128_SEG8;
+            plan.tile_m = plan.tile_n = 128;
+            split(CS_INPLACE_HALO, hs);
+            return plan;
+        }
+    }
+    if (gs > 1) split(inplace ? CS_INPLACE : CS_REDUCE, gs);
+    if (p.f8) {
+        // the caller asked conv_f8_supported() first and wrote the input / passes the weights in the F8C format
+        // (conv_f8_supported is this plan's answer; a mismatch is a library bug, reported through the API's error
+        // path — nothing is launched, the process is never aborted)
+        if (!(p.prec == 1 && p.ks == 3 && p.phases == 1 && gs <= 1 && halo_ok(p, gs, 128, 8, 128)))
+            plan.error = "internal: fp8 correction products requested for a conv the F8C kernel does not support";
+        plan.kernel = CK_HALO_F8C;
+        plan.tile_m = plan.tile_n = 128;
+        return plan;
+    }
+    plan.kernel = t.generic;
+    if (t.generic == CK_GENERIC_128x64 && halo_ok(p, gs, 128, 32, 64)) plan.kernel = CK_HALO_128x64;
+    else if (t.generic == CK_GENERIC_128x128 && halo_ok(p, gs, 128, 32, 128)) plan.kernel = CK_HALO_128x128_SEG32;   // rows of 32+ pixels: one row segment per wave (ONESEG)
+    else if (t.generic == CK_GENERIC_128x128 && halo_ok(p, gs, 128, 8, 128)) plan.kernel = CK_HALO_128x128_SEG8;
+    return plan;
+}
+
+ConvPlan conv_plan_offered(int B, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int prec, bool f8, bool stats) {
+    static float buf;                    // (never dereferenced: a plan only asks whether a buffer is offered)
+    static unsigned cnt;
+    static double st;
+    const int pad = ks / 2, Hv = H << up2, Wv = W << up2;
+    ConvParams p;
+    p.in0.p = &buf; p.in0.C = Cin; p.in0.H = H; p.in0.W = W; p.in0.pad = 1;
+    p.B = B; p.ks = ks; p.stride = stride; p.up2 = up2; p.prec = prec; p.f8 = f8 ? 1 : 0;
+    p.Hout = (Hv + 2 * pad - ks) / stride + 1; p.Wout = (Wv + 2 * pad - ks) / stride + 1;
+    p.out.p = &buf; p.out.C = Cout; p.out.H = p.Hout; p.out.W = p.Wout;
+    p.w = p.w_wino = p.w_wino_f = &buf;
+    p.part = p.wino_ws = &buf;
+    p.tile_cnt = &cnt;
+    if (stats) {
+        p.stats_slices = conv_plan(p).stats_slices;       // (the layout does not depend on what is offered beyond part / tile_cnt)
+        if (p.stats_slices) p.stats = &st;
+    }
+    return conv_plan(p);
+}
+
 // F8C ("f16f8" mode): 3x3 / stride-1 split-f16 convs that run on the 128x128 x-halo tile without split-K at the 32x32- and
 // 16x16-pixel levels — the MFMA-bound shapes, where the 32x32 consumers with the corrections on the fp8 path measured
 // 14-20 % faster than the f16x3 kernel (profiles/README.md finding 64); the 64x64- and 128x128-pixel levels are bound by
-// operand movement and gain nothing. Mirrors launch_conv's choice: callers format the conv's input accordingly.
+// operand movement and gain nothing. Callers format the conv's input accordingly.
 bool conv_f8_supported(int B, int H, int W, int Cout, int Cin) {
     constexpr int maxhw = 1024;         // pixels of one image: the 32x32 level and below
-    if (halo_off()) return false;            // (the F8C consumers exist in the x-halo kernel only)
-    const long M = (long)B * H * W;
     const int HWo = H * W;
-    if ((Cin % 32) || (Cout % 128) || (M % 128) || HWo > maxhw || HWo < 128 || (HWo % 128)) return false;
-    const int seg = W < 128 ? W : 128;
-    if (seg < 8 || (W % seg) || (128 % seg)) return false;
-    if (conv_tile_choice(M, Cout) != 3) return false;
-    return conv_halo_splits(M, H, W, Cout, Cin) <= 1;
-}
-
-bool conv_split_inplace(long M, int HWo, int Cout, int Cin, int phases) {
-    static const int off = env_int("SR3_NO_INPLACE_SPLIT", 0);
-    if (off || conv_splits(M, Cout, Cin) <= 1) return false;
-    static const int bm[4] = {128, 128, 64, 128}, bn[4] = {32, 64, 64, 128};
-    const int t = conv_tile_choice(M, Cout);
-    const long tiles = ((M + bm[t] - 1) / bm[t]) * ((Cout + bn[t] - 1) / bn[t]);
-    // the 64x64-tile kernel only; whole tiles per image (the statistics slices are per M-tile of an image) and in N
-    // (nothing is masked in the fix-up), and a counter for every tile
-    return t == 2 && (HWo % bm[t]) == 0 && (Cout % bn[t]) == 0 && tiles * phases <= CONV_TILE_COUNTERS;
+    if ((Cin % 32) || HWo > maxhw || HWo < 128 || (HWo % 128)) return false;
+    // where the f16x3 plan runs the conv unsplit on a 128x128 x-halo tile, the F8C kernel can take its place
+    const ConvPlan f16 = conv_plan_offered(B, H, W, Cin, Cout, 3, 1, 0, 1, false, false);
+    return f16.split == CS_NONE && (f16.kernel == CK_HALO_128x128_SEG32 || f16.kernel == CK_HALO_128x128_SEG8);
 }
 
 // first launch request of this thread that could not be honoured (nothing was launched for it); the API entry points
@@ -1786,109 +1924,60 @@ bool conv_split_inplace(long M, int HWo, int Cout, int Cin, int phases) {
 static thread_local const char *g_conv_error = nullptr;
 const char *conv_take_error() { const char *e = g_conv_error; g_conv_error = nullptr; return e; }
 
+static int log2_exact(int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; }
+
 void launch_wino_gemm(const ConvParams &p_in, hipStream_t s) {
     ConvParams p = p_in;
     const long M = (long)p.B * p.Hout * p.Wout;
-    auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-    p.hw_shift = lg(p.Hout * p.Wout);
-    p.w_shift = lg(p.Wout);
+    p.hw_shift = log2_exact(p.Hout * p.Wout);
+    p.w_shift = log2_exact(p.Wout);
     p.splits = 1; p.part = nullptr; p.tile_cnt = nullptr; p.stats = nullptr; p.phases = 1;
     // the zbatch GEMMs fill the chip together: the tile is chosen for their combined rows
-    switch (conv_tile_choice(M * p.zbatch, p.out.C)) {
-    case 0: launch_inst2<128, 32, 4, 1, 1, 0, 2, true>(p, s); break;
-    case 1: launch_inst2<128, 64, 2, 2, 1, 0, 2, true>(p, s); break;
-    case 2: launch_inst2<64, 64, 2, 2, 1, 0, 4, true>(p, s); break;
+    switch (conv_tile_choice(M * p.zbatch, p.out.C).generic) {
+    case CK_GENERIC_128x32: launch_inst2<128, 32, 4, 1, 1, 0, 2, true>(p, s); break;
+    case CK_GENERIC_128x64: launch_inst2<128, 64, 2, 2, 1, 0, 2, true>(p, s); break;
+    case CK_GENERIC_64x64: launch_inst2<64, 64, 2, 2, 1, 0, 4, true>(p, s); break;
     default: launch_inst2<128, 128, 2, 2, 1, 0, 2, true>(p, s); break;
     }
 }
 
 void launch_conv(const ConvParams &p_in, hipStream_t s) {
-    if (p_in.up2) { launch_conv_up2(p_in, s); return; }     // weights must be in phase form (make_up2_phase_weights)
-    if (conv_wino_taken(p_in)) { launch_conv_wino(p_in, s); return; }
-    ConvParams p = p_in;
-    const long M = (long)p.B * p.Hout * p.Wout;
-    {
-        auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-        p.hw_shift = lg(p.Hout * p.Wout);
-        p.w_shift = lg(p.Wout);
+    const ConvPlan plan = conv_plan(p_in);
+    if (plan.error) { g_conv_error = plan.error; return; }
+    if (plan.kernel == CK_WINO_ONE_PASS || plan.kernel == CK_WINO_THREE_PASS) { launch_conv_wino(p_in, plan.kernel, s); return; }
+    ConvParams p = phase_form(p_in);     // up2: the weights must be in phase form (make_up2_phase_weights)
+    const int HWo = p.Hout * p.Wout;
+    const long M = (long)p.B * HWo;
+    p.hw_shift = log2_exact(HWo);
+    p.w_shift = log2_exact(p.Wout);
+    p.splits = plan.splits;
+    if (p.phases > 1) {
+        p.phase_slices = HWo / plan.tile_m;
+        p.phase_part_stride = plan.splits > 1 ? (size_t)plan.splits * M * p.out.C : 0;
     }
-    if (p.part == nullptr) p.splits = 1;
-    if (p.prec == 1 && p.ks == 3 && p.stride == 1 && !p.up2 && p.phases == 1 && p.part != nullptr && p.tile_cnt != nullptr &&
-        p.in0.pad == 1 && p.in0.W == p.Wout && p.in0.H == p.Hout && !p.no_halo_split) {
-        const int hs = conv_halo_splits(M, p.Hout, p.Wout, p.out.C, p.in0.C + (p.in1.p ? p.in1.C : 0));
-        const int HWo = p.Hout * p.Wout;
-        const bool stats_ok = p.stats == nullptr || p.stats_slices == (HWo >= 128 ? HWo / 128 : 1);
-        if (hs > 1 && stats_ok) {
-            p.splits = hs;
-            if (halo_ok(p, 128, 32, 128, true)) { launch_halo<128, 128, 4, 1, 32, 3, 16, true>(p, s); return; }
-            if (halo_ok(p, 128, 8, 128, true)) { launch_halo<128, 128, 4, 1, 8, 3, 16, true>(p, s); return; }
-            p.splits = p_in.splits;
-        }
-    }
-    const bool inplace = p.splits > 1 && p.tile_cnt != nullptr &&
-                         conv_split_inplace(M, p.Hout * p.Wout, p.out.C, p.in0.C + (p.in1.p ? p.in1.C : 0), p.phases);
-    if (!inplace) p.tile_cnt = nullptr;
+    if (!plan.needs_counters) p.tile_cnt = nullptr;
     // split-K, two-kernel form: the blocks hold partial sums, the statistics come out of the reduce pass (one slice
     // per TP pixels); they need whole tiles per image and at most 1024 channels, else the caller's statistics kernel runs
-    double *reduce_stats = nullptr;
-    if (p.splits > 1 && !inplace) {
-        const int HWo = p.Hout * p.Wout;
-        if (p.stats && splitk_stats_slices(HWo, p.out.C) > 0) reduce_stats = p.stats;
-        p.stats = nullptr;
+    double *const stats = p.stats;
+    if (plan.split == CS_REDUCE) p.stats = nullptr;
+    const bool spk = plan.split == CS_INPLACE_HALO;
+    switch (plan.kernel) {
+    case CK_HALO_F8C: launch_halo<128, 128, 2, 2, 8, 3, 32, false, true>(p, s); break;
+    case CK_HALO_128x128_SEG32: launch_halo_tile<128, 32>(p, spk, s); break;
+    case CK_HALO_128x128_SEG8: launch_halo_tile<128, 8>(p, spk, s); break;
+    case CK_HALO_128x64: launch_halo_tile<64, 32>(p, false, s); break;
+    case CK_GENERIC_128x32: launch_cfg<128, 32, 4, 1>(p, s); break;
+    case CK_GENERIC_128x64: launch_cfg<128, 64, 2, 2>(p, s); break;
+    case CK_GENERIC_64x64: launch_cfg<64, 64, 2, 2>(p, s); break;
+    default: launch_cfg<128, 128, 2, 2>(p, s); break;
     }
-    if (p.f8) {
-        // the caller asked conv_f8_supported() first and wrote the input / passes the weights in the F8C format
-        // (conv_f8_supported is the single source of truth; a mismatch is a library bug, reported through the API's
-        // error path — nothing is launched, the process is never aborted)
-        if (!(p.prec == 1 && p.ks == 3 && p.phases == 1 && p.splits <= 1 && halo_ok(p, 128, 8, 128))) {
-            g_conv_error = "internal: fp8 correction products requested for a conv the F8C kernel does not support";
-            return;
-        }
-        launch_halo<128, 128, 2, 2, 8, 3, 32, false, true>(p, s);
-        return;
-    }
-    switch (conv_tile_choice(M, p.out.C)) {
-    case 0: launch_cfg<128, 32, 4, 1>(p, s); break;
-    case 1:
-        if (halo_ok(p, 128, 32, 64)) {
-            if (p.ks == 3) launch_halo<128, 64, 4, 1, 32, 3, 16>(p, s); else launch_halo<128, 64, 4, 1, 32, 2, 16>(p, s);
-        }
-        else launch_cfg<128, 64, 2, 2>(p, s);
-        break;
-    case 2: launch_cfg<64, 64, 2, 2>(p, s); break;
-    default:
-        if (halo_ok(p, 128, 32, 128)) {   // rows of 32+ pixels: one row segment per wave (ONESEG)
-            if (p.ks == 3) launch_halo<128, 128, 4, 1, 32, 3, 16>(p, s); else launch_halo<128, 128, 4, 1, 32, 2, 16>(p, s);
-        }
-        else if (halo_ok(p, 128, 8, 128)) {
-            if (p.ks == 3) launch_halo<128, 128, 4, 1, 8, 3, 16>(p, s); else launch_halo<128, 128, 4, 1, 8, 2, 16>(p, s);
-        }
-        else launch_cfg<128, 128, 2, 2>(p, s);
-        break;
-    }
-    if (p.splits > 1 && !inplace) {
-        const int HWo = p.Hout * p.Wout, TP = splitk_reduce_tp(HWo);
-        p.stats = reduce_stats;
-        if (reduce_stats) p.phase_slices = splitk_stats_slices(HWo, p.out.C);   // slices of one sub-pixel phase (phases > 1)
+    if (plan.split == CS_REDUCE) {
+        const int TP = splitk_reduce_tp(HWo), slices = splitk_stats_slices(HWo, p.out.C);
+        p.stats = slices > 0 ? stats : nullptr;
+        if (p.stats) p.phase_slices = slices;      // slices of one sub-pixel phase (phases > 1)
         hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((M + TP - 1) / TP), p.phases), dim3(256), 0, s, p,
                            (int)M, HWo, TP);
     }
-}
-
-void launch_conv_up2(const ConvParams &p_in, hipStream_t s) {
-    const int H = p_in.Hout / 2, W = p_in.Wout / 2, Cout = p_in.out.C;
-    const int Cin = p_in.in0.C + (p_in.in1.p ? p_in.in1.C : 0);
-    const long Ml = (long)p_in.B * H * W;
-    ConvParams p = p_in;            // the four phases are one launch: blockIdx.z picks (py, px)
-    p.ks = 2; p.stride = 1; p.up2 = 0;
-    p.Hout = H; p.Wout = W;
-    p.out_step = 2;
-    p.phases = 4;
-    p.phase_w_stride = (size_t)4 * Cout * Cin;
-    p.phase_slices = (H * W) / conv_tile_m(Ml, Cout);
-    p.splits = p.part ? conv_splits(Ml, Cout, Cin) : 1;
-    p.phase_part_stride = p.splits > 1 ? (size_t)p.splits * Ml * Cout : 0;
-    launch_conv(p, s);
 }
 
 void make_up2_phase_weights(const float *w9, int Cout, int CinPad, float *dst) {

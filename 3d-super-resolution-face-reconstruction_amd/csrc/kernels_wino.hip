@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const ConvParams p, co
 //     fused GroupNorm statistics (per tile in LDS, then per slice in tile order; spb slices per strip).
 // Registers: 4 positions x 2 N-fragments x 16 accumulators = 128, plus two sets of B fragments (64): 2 waves per SIMD.
 // A 64-tile or 128-channel block doubles the accumulators (256: 1 wave per SIMD, nothing left for operands).
-// One input tensor only (conv_wino_taken): the engine writes x || skip as one tensor in the GroupNorm apply pass.
+// One input tensor only (conv_plan): the engine writes x || skip as one tensor in the GroupNorm apply pass.
 constexpr int WF_T = 32;                    // 2x2 output tiles per block (one strip of a tile row)
 constexpr int WF_BN = 64;                   // output channels per block
 constexpr int WF_WX = 2 * WF_T + 2;         // padded input columns of a strip's windows
@@ -380,61 +380,7 @@ int out_slices(const ConvParams &p) {
 
 } // namespace
 
-// one-pass kernel (wino_fused_kernel): 64x64 pixels and up, whole strips per tile row, whole channel blocks, and enough
-// blocks to fill the chip (fewer: the direct kernel, whose smaller tiles spread further)
-static bool wino_fused_shape(int B, int H, int W, int Cin, int Cout) {
-    if (H * W < 4096 || (H & 1) || (W % (2 * WF_T)) || Cin < WINO_FUSED_CIN || (Cin % 32) || (Cout % WF_BN)) return false;
-    const uint64_t blocks = (uint64_t)B * (H / 2) * (W / (2 * WF_T)) * (Cout / WF_BN);
-    return blocks >= WINO_FUSED_MIN_BLOCKS;
-}
-
-bool conv_wino_supported(int B, int H, int W, int Cin, int Cout) {
-    static const bool off = env_int("SR3_NO_WINOGRAD", 0) != 0;    // product switch (read once)
-    if (off || B <= 0) return false;
-    if (wino_fused_shape(B, H, W, Cin, Cout)) return true;
-    if ((H & 1) || (W & 1) || H * W > 1024 || Cin < WINO_MIN_CIN || (Cin % 32) || (Cout % 64)) return false;
-    // few tiles (a single 128x128 image: 256 at its 32x32 level): the three dependent passes cost more latency than the
-    // MACs they save (B = 1 step 1.99 -> 2.27 ms with every level in Winograd form); B = 64 at 8x8 is 1024 tiles and gains
-    const uint64_t tiles = (uint64_t)B * (H / 2) * (W / 2);
-    if (tiles < WINO_MIN_TILES) return false;
-    // the LDS-DMA and epilogue addressing of the position GEMMs uses 32-bit byte offsets inside one position's plane
-    return tiles * (uint64_t)(Cin > Cout ? Cin : Cout) * 4 < (1ull << 32);
-}
-
-size_t conv_wino_ws_floats(int B, int H, int W, int Cin, int Cout) {
-    if (wino_fused_shape(B, H, W, Cin, Cout)) return 0;           // U and M never leave the CU
-    return (size_t)16 * B * (H / 2) * (W / 2) * (Cin + Cout);
-}
-
-bool conv_wino_fused(int B, int H, int W, int Cin, int Cout) {
-    return conv_wino_supported(B, H, W, Cin, Cout) && wino_fused_shape(B, H, W, Cin, Cout);
-}
-
-bool conv_wino_taken(const ConvParams &p) {
-    if (p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.f8)
-        return false;
-    if (p.out_split.p || !p.out_f32 || p.resid_split) return false;
-    if (p.in0.pad != 1 || p.in0.H != p.Hout || p.in0.W != p.Wout) return false;
-    if (p.in1.p && (p.in1.pad != 1 || p.in1.H != p.Hout || p.in1.W != p.Wout)) return false;
-    if (p.in2.p && !p.w2) return false;
-    const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
-    if (!conv_wino_supported(p.B, p.Hout, p.Wout, Cin, p.out.C)) return false;
-    if (wino_fused_shape(p.B, p.Hout, p.Wout, Cin, p.out.C)) {
-        if (!p.w_wino_f) return false;
-        // one input tensor: the engine concatenates x || skip in the GroupNorm apply pass that writes the conv's input,
-        // so no caller hands these convs a second tensor (one that does gets the direct kernel)
-        if (p.in1.p) return false;
-        // the statistics slices must be whole strips or 2 | 4 equal parts of one
-        const int spi = (p.Hout / 2) * (p.Wout / (2 * WF_T));
-        if (p.stats == nullptr) return true;
-        if (p.stats_slices <= 0 || (p.stats_slices % spi)) return false;
-        const int spb = p.stats_slices / spi;
-        return spb == 1 || spb == 2 || spb == 4;
-    }
-    if (!p.w_wino || !p.wino_ws) return false;
-    const int tiles = (p.Hout >> 1) * (p.Wout >> 1);
-    return p.stats == nullptr || (p.stats_slices > 0 && (tiles % p.stats_slices) == 0);
-}
+static_assert(WF_T == WINO_FUSED_TILES && WF_BN == WINO_FUSED_BN, "conv_plan gates the one-pass kernel on its block shape");
 
 void make_wino_weights(const float *w9, int Cout, int CinPad, float *dst) {
     static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
@@ -480,7 +426,7 @@ void launch_wino_frag(const float *wino, int Cout, int CinPad, float *dst, hipSt
     hipLaunchKernelGGL(wino_frag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wino, Cout, CinPad, dst);
 }
 
-void launch_conv_wino(const ConvParams &p, hipStream_t s) {
+void launch_conv_wino(const ConvParams &p, ConvKernel form, hipStream_t s) {
     const int H = p.Hout, W = p.Wout, Cout = p.out.C;
     const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
     ConvParams o = p;
@@ -497,7 +443,7 @@ void launch_conv_wino(const ConvParams &p, hipStream_t s) {
         launch_conv(r, s);
         o.resid = p.out;
     }
-    if (wino_fused_shape(p.B, H, W, Cin, Cout)) {
+    if (form == CK_WINO_ONE_PASS) {
         const int spi = (H / 2) * (W / (2 * WF_T));
         const int spb = o.stats ? o.stats_slices / spi : 1;
         const unsigned blocks = (unsigned)((size_t)p.B * spi * (Cout / WF_BN));

@@ -99,7 +99,8 @@ struct Module {
     // fused GroupNorm statistics written by the conv that produces out / rb_out / h1 (p == null:
     // the tile does not divide the image, fall back to the statistics kernel)
     StatsRef st_out, st_rb, st_h1;
-    int oc = 0, oh = 0, ow = 0;
+    int oc = 0, oh = 0, ow = 0;     // output channels and resolution
+    int ih = 0, iw = 0;             // input resolution
 };
 
 enum Family { F_CONV = 0, F_GN = 1, F_ATTN = 2, F_EMBED = 3, F_MISC = 4 };
@@ -169,7 +170,7 @@ struct sr3_ctx {
     TDesc final_act;            // activated input of final_conv
     float *qkvb = nullptr, *aob = nullptr, *vtb = nullptr;   // attention: qkv, core output, v^T scratch (split-f16 core)
     float *part = nullptr;      // split-K partial sums (small-M convs)
-    float *wino_ws = nullptr;   // transformed input and products of the Winograd convs (conv_wino_ws_floats)
+    float *wino_ws = nullptr;   // transformed input and products of the Winograd convs (ConvPlan::wino_ws_floats)
     float *gscale = nullptr, *gshift = nullptr, *gpart = nullptr;
     float *temb = nullptr, *cbias = nullptr;
     int cb_stride = 0;          // row stride of cbias: nf_total, or 0 when one noise level serves the whole batch (sampler steps)
@@ -382,7 +383,7 @@ int build_graph(sr3_ctx *c) {
     return 0;
 }
 
-// 3x3 conv weights that may run in Winograd form (conv_wino_supported: the batch and resolution decide per launch).
+// 3x3 conv weights that may run in Winograd form (conv_plan: the batch and resolution decide per launch).
 // The parameter does not know its level: a conv with 64 <= Cin < 128 gets the transformed copy (16/9 of its 3x3
 // weights) even where it only ever runs at 32x32 or below, where only Cin >= 128 is taken (none in the yml UNet).
 bool wino_weights(const Param &p) {
@@ -530,14 +531,30 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     std::vector<int> s_slices(nm, 0), s_out(nm, 0), s_h1(nm, 0);
     uint64_t max_qkv = 0, max_ao = 0, max_part = 0, max_vt = 0, max_wino = 0;
     int h = H, w = W;
-    int cur_c = c->in_pad;
     std::vector<int> feat_c;
+    // What one conv asks of the shared buffers: its plan with everything offered, in either arithmetic (the exact-f32
+    // repeat of the range check runs on the same workspace) and with or without fused statistics (a shape that has none
+    // runs without). Returns the statistics slices per image of its output (the same in all four plans).
+    bool frag_ok = true;
+    auto want = [&](const ConvRef &cr, int ih, int iw, int stride, int up2) {
+        int slices = 0;
+        for (int v = 0; v < 4; ++v) {
+            const ConvPlan pl = conv_plan_offered(B, ih, iw, cr.cin_pad, cr.cout, cr.ks, stride, up2, v & 1, false, (v & 2) != 0);
+            max_part = std::max<uint64_t>(max_part, pl.part_floats);
+            slices = pl.stats_slices;
+            if (!wino_weights(c->params[cr.w])) continue;
+            max_wino = std::max<uint64_t>(max_wino, pl.wino_ws_floats);
+            if (pl.needs_wino_frag && ensure_wino_frag(c, c->params[cr.w])) frag_ok = false;
+        }
+        return slices;
+    };
     for (size_t i = 0; i < nm; ++i) {
         Module &m = c->mods[i];
+        const int ih = h, iw = w;                 // the module's input resolution
         int oc;
         if (m.kind == M_CONV_IN) { oc = m.conv.cout; }
-        else if (m.kind == M_DOWN) { oc = m.conv.cout; a1_off[i] = acts.get(cv, B, m.conv.cin, h, w); a2_off[i] = h * 65536 + w; h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
-        else if (m.kind == M_UP) { oc = m.conv.cout; a1_off[i] = acts.get(cv, B, m.conv.cin, h, w); a2_off[i] = h * 65536 + w; h *= 2; w *= 2; }
+        else if (m.kind == M_DOWN) { oc = m.conv.cout; a1_off[i] = acts.get(cv, B, m.conv.cin, h, w); h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+        else if (m.kind == M_UP) { oc = m.conv.cout; a1_off[i] = acts.get(cv, B, m.conv.cin, h, w); h *= 2; w *= 2; }
         else {
             oc = m.rb.cout;
             a1_off[i] = acts.get(cv, B, m.rb.cin, h, w);
@@ -554,57 +571,29 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
                     return fail("attention over %d tokens at %d channels: the streaming core takes at most 512 channels", h * w, oc);
             }
         }
-        m.oc = oc; m.oh = h; m.ow = w;
-        {   // split-K partial buffer: largest splits * M * Cout over the convs of this module
-            const long Mo = (long)B * h * w;
-            auto want = [&](int cout, int cin) {
-                const int sp = std::max(conv_splits(Mo, cout, cin), conv_halo_splits(Mo, h, w, cout, cin));
-                if (sp > 1) max_part = std::max<uint64_t>(max_part, (uint64_t)sp * Mo * cout);
-            };
-            if (m.kind == M_RES) {
-                want(oc, m.rb.cin); want(oc, oc);
-                for (const ConvRef *cr : {&m.rb.c1, &m.rb.c2}) {    // Winograd workspace of the block's 3x3 convs
-                    if (!wino_weights(c->params[cr->w]) || !conv_wino_supported(B, h, w, cr->cin_pad, cr->cout)) continue;
-                    max_wino = std::max<uint64_t>(max_wino, conv_wino_ws_floats(B, h, w, cr->cin_pad, cr->cout));
-                    if (conv_wino_fused(B, h, w, cr->cin_pad, cr->cout) && ensure_wino_frag(c, c->params[cr->w])) return -1;
-                }
-                if (m.rb.attn) { want(3 * oc, oc); want(oc, oc); }
-            } else if (m.kind == M_UP) {
-                const long Ml = Mo / 4;                       // each sub-pixel phase is a conv over the low-res pixels
-                const int sp = conv_splits(Ml, oc, m.conv.cin_pad);
-                if (sp > 1) max_part = std::max<uint64_t>(max_part, (uint64_t)4 * sp * Ml * oc);   // 4 phases in one launch
-            } else {
-                want(oc, m.conv.cin_pad);
-            }
+        m.oc = oc; m.oh = h; m.ow = w; m.ih = ih; m.iw = iw;
+        // split-K partials, Winograd workspace and fused statistics: a conv writing an [oc, h, w] tensor leaves one slice
+        // per M-tile of an image (every such conv uses the same tile height), a split-K conv one per block of its reduce pass
+        if (m.kind == M_RES) {
+            s_h1[i] = want(m.rb.c1, h, w, 1, 0);
+            s_out[i] = want(m.rb.c2, h, w, 1, 0);
+            if (m.rb.attn) { want(m.rb.qkv, h, w, 1, 0); want(m.rb.aout, h, w, 1, 0); }
+        } else {
+            s_out[i] = want(m.conv, ih, iw, m.kind == M_DOWN ? 2 : 1, m.kind == M_UP ? 1 : 0);
         }
-        {   // fused statistics: a conv writing an [oc, h, w] tensor leaves one slice per M-tile of an image (every
-            // such conv uses the same tile height), a split-K conv one slice per block of its reduce pass
-            const bool up = m.kind == M_UP;                   // 4 phases, each tiled over the low-res image
-            const int hw = up ? (h * w) / 4 : h * w;
-            const int bm = conv_tile_m((long)B * hw, oc);
-            auto slices_for = [&](int cin) {
-                // (an in-place split conv leaves the same slices as an unsplit one)
-                if (conv_splits((long)B * hw, oc, cin) > 1 && !conv_split_inplace((long)B * hw, hw, oc, cin, up ? 4 : 1))
-                    return (up ? 4 : 1) * splitk_stats_slices(hw, oc);
-                return (hw % bm == 0) ? (up ? 4 : 1) * (hw / bm) : 0;
-            };
-            s_out[i] = slices_for(m.kind == M_RES ? oc : m.conv.cin_pad);
-            s_h1[i] = m.kind == M_RES ? slices_for(m.rb.cin) : 0;
-            s_slices[i] = std::max(s_out[i], s_h1[i]);
-            if (s_slices[i]) {
-                const uint64_t sf = (uint64_t)B * s_slices[i] * oc * 4;   // 2 doubles per channel
-                so_off[i] = cv.take(sf);
-                sr_off[i] = cv.take(sf);
-                sh_off[i] = cv.take(sf);
-            }
+        if (!frag_ok) return -1;
+        s_slices[i] = std::max(s_out[i], s_h1[i]);
+        if (s_slices[i]) {
+            const uint64_t sf = (uint64_t)B * s_slices[i] * oc * 4;   // 2 doubles per channel
+            so_off[i] = cv.take(sf);
+            sr_off[i] = cv.take(sf);
+            sh_off[i] = cv.take(sf);
         }
         const uint64_t n = (uint64_t)B * (h + 2) * (w + 2) * oc;
         out_off[i] = cv.take(n);
         if (twin[i]) tw_off[i] = cv.take(n);
         rb_off[i] = (m.kind == M_RES && m.rb.attn) ? cv.take(n) : out_off[i];
-        cur_c = oc;
     }
-    (void)cur_c;
     if (h != H || w != W) return fail("internal: UNet does not return to the input resolution");
     {   // the conv's LDS-DMA addressing uses 32-bit byte offsets inside one tensor
         const int bmax = max_batch(c, H, W);
@@ -656,7 +645,7 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
             if (!(m.kind == M_RES && m.rb.attn)) m.st_rb = m.st_out;   // rb_out aliases out
         }
         if (!m.st_out.p || (m.kind == M_RES && (!m.st_h1.p || !m.st_rb.p))) all_fused = false;
-        if (m.kind == M_UP || m.kind == M_DOWN) m.up_in = desc(a1_off[i], m.conv.cin, (int)(a2_off[i] >> 16), (int)(a2_off[i] & 65535), 1);
+        if (m.kind == M_UP || m.kind == M_DOWN) m.up_in = desc(a1_off[i], m.conv.cin, m.ih, m.iw, 1);
         if (m.kind == M_RES) {
             m.act1 = desc(a1_off[i], m.rb.cin, m.oh, m.ow, 1);
             m.act2 = desc(a2_off[i], m.oc, m.oh, m.ow, 1);
@@ -719,50 +708,67 @@ void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int 
     c->pend();
 }
 
-// `activated`: the input was written by launch_gn_apply and is in the context's precision format
-void run_conv(sr3_ctx *c, const TDesc &a, const TDesc &b, const ConvRef &cv, int B, int stride, int up2,
-              const float *chan_bias, const TDesc &resid, const TDesc &out, bool activated = false,
-              const TDesc &in2 = TDesc(), const ConvRef *cv2 = nullptr, const float *bias_override = nullptr,
-              const StatsRef &stats = StatsRef(), const TDesc &out_split = TDesc(), const TDesc &in2b = TDesc(),
-              bool out_f32 = true, bool resid_split = false, const float *w2_raw = nullptr, bool f8 = false) {
+// One conv of the engine, by name (defaults = what most convs want)
+struct ConvCall {
+    TDesc in;                           // (a concatenation x ‖ skip is written as one tensor by the GroupNorm pass)
+    const ConvRef *conv = nullptr;
+    int B = 0, stride = 1, up2 = 0;
+    bool activated = false;             // the input was written by launch_gn_apply and is in the context's precision format
+    bool f8 = false;                    // ... in the F8C operand format (f8_conv() said so)
+    const float *chan_bias = nullptr;   // FeatureWiseAffine bias rows
+    const float *bias_override = nullptr;
+    TDesc resid;                        // added to the output
+    bool resid_split = false;           // ... which is stored in the split-f16 format
+    TDesc out;
+    StatsRef stats;                     // fused GroupNorm statistics of the output
+    TDesc out_split;                    // split-f16 twin of the output (prec 1)
+    bool out_f32 = true;                // false: only the twin is written (where there is one)
+    // fused 1x1 term over in2 ‖ in2b: a res_conv, or (ident_w, prec 1) the identity skip as extra K-steps (ResBlock::ident_w)
+    TDesc in2, in2b;
+    const ConvRef *fused1x1 = nullptr;
+    const float *ident_w = nullptr;
+};
+
+void run_conv(sr3_ctx *c, const ConvCall &k) {
+    const ConvRef &cv = *k.conv;
+    const TDesc &a = k.in, &out = k.out;
+    const int B = k.B;
     ConvParams p;
-    p.in0 = a; p.in1 = b; p.B = B; p.Hout = out.H; p.Wout = out.W;
-    p.ks = cv.ks; p.stride = stride; p.up2 = up2;
-    p.prec = activated ? c->prec : 0;
+    p.in0 = a; p.B = B; p.Hout = out.H; p.Wout = out.W;
+    p.ks = cv.ks; p.stride = k.stride; p.up2 = k.up2;
+    p.prec = k.activated ? c->prec : 0;
     p.w = p.prec ? c->params[cv.w].dev_split : c->params[cv.w].dev;
-    if (!p.prec && cv.cin_pad == a.C + (b.p ? b.C : 0)) {
+    if (!p.prec && cv.cin_pad == a.C) {
         p.w_wino = c->params[cv.w].dev_wino; p.w_wino_f = c->params[cv.w].dev_wino_f; p.wino_ws = c->wino_ws;
     }
-    if (f8 && p.prec) { p.f8 = 1; p.w = c->params[cv.w].dev_f8; }
+    if (k.f8 && p.prec) { p.f8 = 1; p.w = c->params[cv.w].dev_f8; }
     p.w_unscale = c->params[cv.w].w_unscale;
-    p.bias = bias_override ? bias_override : (cv.b >= 0 ? c->params[cv.b].dev : nullptr);
-    p.chan_bias = chan_bias; p.chan_bias_stride = c->cb_stride;
-    p.resid = resid; p.out = out;
-    if (c->prec) p.out_split = out_split;
-    p.out_f32 = (out_f32 || !p.out_split.p) ? 1 : 0;
-    p.resid_split = resid_split ? 1 : 0;
-    if (stats.p) { p.stats = const_cast<double *>(stats.p); p.stats_slices = stats.slices; }
-    p.splits = p.f8 ? 1 : conv_splits((long)B * out.H * out.W, cv.cout, a.C + (b.p ? b.C : 0));
+    p.bias = k.bias_override ? k.bias_override : (cv.b >= 0 ? c->params[cv.b].dev : nullptr);
+    p.chan_bias = k.chan_bias; p.chan_bias_stride = c->cb_stride;
+    p.resid = k.resid; p.out = out;
+    if (c->prec) p.out_split = k.out_split;
+    p.out_f32 = (k.out_f32 || !p.out_split.p) ? 1 : 0;
+    p.resid_split = k.resid_split ? 1 : 0;
+    if (k.stats.p) { p.stats = const_cast<double *>(k.stats.p); p.stats_slices = k.stats.slices; }
     p.part = c->part;
     p.tile_cnt = c->tile_cnt;
     p.no_halo_split = c->halo_split_off ? 1 : 0;
     p.ovf = c->d_ovf;
-    if (cv2) {
-        p.in2 = in2; p.in2b = in2b;
-        p.w2 = p.prec ? c->params[cv2->w].dev_split : c->params[cv2->w].dev;
-    } else if (w2_raw && p.prec) {
-        p.in2 = in2;                    // identity skip as extra K-steps (ResBlock::ident_w)
-        p.w2 = w2_raw;
+    if (k.fused1x1) {
+        p.in2 = k.in2; p.in2b = k.in2b;
+        p.w2 = p.prec ? c->params[k.fused1x1->w].dev_split : c->params[k.fused1x1->w].dev;
+    } else if (k.ident_w && p.prec) {
+        p.in2 = k.in2;
+        p.w2 = k.ident_w;
     }
     c->pbegin(F_CONV);
-    if (up2) launch_conv_up2(p, c->stream);
-    else launch_conv(p, c->stream);
+    launch_conv(p, c->stream);
     if (c->prof) {
         char tag[160];
-        snprintf(tag, sizeof tag, "conv k%d s%d u%d %dx%d cin%d(%d+%d) cout%d res%d fused1x1:%d prec%d%s", cv.ks, stride,
-                 up2, out.H, out.W, cv.cin, a.C, b.p ? b.C : 0, cv.cout, resid.p ? 1 : 0, cv2 ? cv2->cin : 0, p.prec,
-                 p.f8 ? " f8c" : "");
-        c->pend(2.0 * (double)B * out.H * out.W * cv.cout * ((double)(cv.ks * cv.ks) * cv.cin + (cv2 ? cv2->cin : 0)), tag);
+        const int cin2 = k.fused1x1 ? k.fused1x1->cin : 0;
+        snprintf(tag, sizeof tag, "conv k%d s%d u%d %dx%d cin%d(%d+%d) cout%d res%d fused1x1:%d prec%d%s", cv.ks, k.stride,
+                 k.up2, out.H, out.W, cv.cin, a.C, 0, cv.cout, k.resid.p ? 1 : 0, cin2, p.prec, p.f8 ? " f8c" : "");
+        c->pend(2.0 * (double)B * out.H * out.W * cv.cout * ((double)(cv.ks * cv.ks) * cv.cin + cin2), tag);
     }
 }
 
@@ -794,45 +800,53 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     run_gn_act(c, x_so ? xr : x, (skip.p && sk_so) ? skr : skip, rb.gn1, B, 2, m.act1, sx, ss,
                rb.has_res && !direct ? m.raw1 : kNone, (x_so ? 1 : 0) | (skip.p && sk_so ? 2 : 0), f8a);
     // block1's conv + FeatureWiseAffine bias writes the fp32 h1, then block2's GroupNorm + Swish as the apply pass over it
-    run_conv(c, m.act1, kNone, rb.c1, B, 1, 0, c->cbias + rb.nf_off, kNone, m.h1, true, kNone, nullptr, nullptr, m.st_h1,
-             kNone, kNone, true, false, nullptr, f8a);
+    ConvCall k1;
+    k1.in = m.act1; k1.conv = &rb.c1; k1.B = B; k1.activated = true; k1.f8 = f8a;
+    k1.chan_bias = c->cbias + rb.nf_off;
+    k1.out = m.h1; k1.stats = m.st_h1;
+    run_conv(c, k1);
     run_gn_act(c, m.h1, kNone, rb.gn2, B, 2, m.act2, m.st_h1, StatsRef(), TDesc(), 0, f8b);
     // block2 + skip path in one launch: conv3x3(act2) [+ res_conv 1x1 (raw x ‖ skip) as extra
     // K-steps | + x as residual when the block keeps its width]
-    const TDesc tw = rb.attn ? kNone : m.out_s;      // with attention the out-projection writes the module output
-    if (rb.has_res)
-        run_conv(c, m.act2, kNone, rb.c2, B, 1, 0, nullptr, kNone, m.rb_out, true, direct ? xr : m.raw1, &rb.res,
-                 rb.fused_bias, m.st_rb, tw, direct && skip.p ? skr : kNone, !out_so, false, nullptr, f8b);
-    else if (c->prec && rb.ident_w && xr.p)
-        run_conv(c, m.act2, kNone, rb.c2, B, 1, 0, nullptr, kNone, m.rb_out, true, xr, nullptr, nullptr, m.st_rb,
-                 tw, kNone, !out_so, false, rb.ident_w, f8b);
-    else
-        run_conv(c, m.act2, kNone, rb.c2, B, 1, 0, nullptr, x_so ? xr : x, m.rb_out, true, kNone, nullptr, nullptr, m.st_rb,
-                 tw, kNone, !out_so, x_so, nullptr, f8b);
+    ConvCall k2;
+    k2.in = m.act2; k2.conv = &rb.c2; k2.B = B; k2.activated = true; k2.f8 = f8b;
+    k2.out = m.rb_out; k2.stats = m.st_rb; k2.out_f32 = !out_so;
+    k2.out_split = rb.attn ? kNone : m.out_s;      // with attention the out-projection writes the module output
+    if (rb.has_res) {
+        k2.in2 = direct ? xr : m.raw1; k2.in2b = direct && skip.p ? skr : kNone;
+        k2.fused1x1 = &rb.res; k2.bias_override = rb.fused_bias;
+    } else if (c->prec && rb.ident_w && xr.p) {
+        k2.in2 = xr; k2.ident_w = rb.ident_w;
+    } else {
+        k2.resid = x_so ? xr : x; k2.resid_split = x_so;
+    }
+    run_conv(c, k2);
     if (rb.attn) {
         run_gn_act(c, m.rb_out, kNone, rb.agn, B, 1, m.act2, m.st_rb, StatsRef());
-        const TDesc qkv = unpadded(c->qkvb, 3 * rb.cout, h, w);
-        if (c->prec && attention_split_supported(h * w, rb.cout)) {
+        const bool split_attn = c->prec && attention_split_supported(h * w, rb.cout);
+        ConvCall kq, ko;
+        kq.in = m.act2; kq.conv = &rb.qkv; kq.B = B; kq.activated = true;
+        kq.out = unpadded(c->qkvb, 3 * rb.cout, h, w);
+        ko.in = unpadded(c->aob, rb.cout, h, w); ko.conv = &rb.aout; ko.B = B; ko.activated = split_attn;
+        ko.resid = m.rb_out; ko.out = m.out; ko.stats = m.st_out; ko.out_split = m.out_s;
+        if (split_attn) {
             // split-f16 mode: the qkv projection writes ONLY the split twin of its output, the attention core
             // multiplies hi/lo halfs (3 x v_mfma_f32_16x16x32_f16 per product) and hands its result to the out
             // projection in the same format
-            run_conv(c, m.act2, kNone, rb.qkv, B, 1, 0, nullptr, kNone, qkv, true, kNone, nullptr, nullptr, StatsRef(), qkv,
-                     kNone, false);
+            kq.out_split = kq.out; kq.out_f32 = false;
+            run_conv(c, kq);
             c->pbegin(F_ATTN);
             const double fl = launch_attention_split(c->qkvb, c->vtb, B, h * w, rb.cout, nullptr, c->aob, c->d_ovf, c->stream);
             c->pend(fl);
-            run_conv(c, unpadded(c->aob, rb.cout, h, w), kNone, rb.aout, B, 1, 0, nullptr, m.rb_out, m.out, true, kNone,
-                     nullptr, nullptr, m.st_out, m.out_s);
         } else {
-            run_conv(c, m.act2, kNone, rb.qkv, B, 1, 0, nullptr, kNone, qkv, true);
+            run_conv(c, kq);
             c->pbegin(F_ATTN);
             // over 1024 tokens the 32 x N score tile no longer fits in LDS: the online-softmax core (every mode)
             const double fl = h * w > 1024 ? launch_attention_stream(c->qkvb, B, h * w, rb.cout, c->aob, c->stream)
                                            : launch_attention(c->qkvb, B, h * w, rb.cout, c->aob, c->stream);
             c->pend(fl);
-            run_conv(c, unpadded(c->aob, rb.cout, h, w), kNone, rb.aout, B, 1, 0, nullptr, m.rb_out, m.out, false, kNone,
-                     nullptr, nullptr, m.st_out, m.out_s);
         }
+        run_conv(c, ko);
     }
 }
 
@@ -850,9 +864,12 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
     for (int i = 0; i < (int)c->mods.size(); ++i) {
         Module &m = c->mods[i];
         const bool is_up_path = i >= n_pre;
+        ConvCall k;                       // the module's own conv (conv_in, Downsample, Upsample)
+        k.conv = &m.conv; k.B = B; k.out = m.out; k.stats = m.st_out; k.out_split = m.out_s;     // (the twin: prec 1 only)
         switch (m.kind) {
         case M_CONV_IN:
             m.st_out.slices = m.slices_default;
+            k.stats = m.st_out;
             if (c->prec && c->x0p) {
                 // downs.0 on the packed split-f16 state (kernels_edge.hip): 3 K-steps of 24 live k-values instead
                 // of 9 K-steps of 32 mostly-zero channels, no split copy of the state tensor
@@ -871,26 +888,27 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
                 c->pbegin(F_GN);
                 launch_gn_apply_rows(cur, kNone, B, nullptr, nullptr, 0, 1, c->x0s, c->stream, TDesc(), 0, c->d_ovf);
                 c->pend();
-                run_conv(c, c->x0s, kNone, m.conv, B, 1, 0, nullptr, kNone, m.out, true, kNone, nullptr, nullptr, m.st_out, m.out_s,
-                         kNone, !(so_mode && m.out_s.p));
+                k.in = c->x0s; k.activated = true; k.out_f32 = !(so_mode && m.out_s.p);
+                run_conv(c, k);
             } else {
-                run_conv(c, cur, kNone, m.conv, B, 1, 0, nullptr, kNone, m.out, false, kNone, nullptr, nullptr, m.st_out, m.out_s);
+                k.in = cur;
+                run_conv(c, k);
             }
             break;
         case M_DOWN:
         case M_UP: {
-            const int stride = m.kind == M_DOWN ? 2 : 1, up2 = m.kind == M_UP ? 1 : 0;
+            k.stride = m.kind == M_DOWN ? 2 : 1; k.up2 = m.kind == M_UP ? 1 : 0;
             if (c->prec && cur_s.p) {           // the producer left a split-f16 twin: read it directly
-                run_conv(c, cur_s, kNone, m.conv, B, stride, up2, nullptr, kNone, m.out, true, kNone, nullptr, nullptr, m.st_out, m.out_s,
-                         kNone, !(so_mode && m.out_s.p));
+                k.in = cur_s; k.activated = true; k.out_f32 = !(so_mode && m.out_s.p);
             } else if (c->prec) {               // no twin: re-store the raw input in split-f16 form first
                 c->pbegin(F_GN);
                 launch_gn_apply(cur, kNone, B, nullptr, nullptr, 0, 1, m.up_in, c->stream, TDesc(), 0, c->d_ovf);
                 c->pend();
-                run_conv(c, m.up_in, kNone, m.conv, B, stride, up2, nullptr, kNone, m.out, true, kNone, nullptr, nullptr, m.st_out, m.out_s);
+                k.in = m.up_in; k.activated = true;
             } else {
-                run_conv(c, cur, kNone, m.conv, B, stride, up2, nullptr, kNone, m.out, false, kNone, nullptr, nullptr, m.st_out);
+                k.in = cur;
             }
+            run_conv(c, k);
             break;
         }
         case M_RES:
@@ -942,7 +960,9 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
         return;
     }
     run_gn_act(c, cur, kNone, c->final_gn, B, 2, c->final_act, scur, StatsRef());
-    run_conv(c, c->final_act, kNone, c->final_conv, B, 1, 0, nullptr, kNone, c->eps, true);
+    ConvCall k;
+    k.in = c->final_act; k.conv = &c->final_conv; k.B = B; k.activated = true; k.out = c->eps;
+    run_conv(c, k);
 }
 
 void run_embed(sr3_ctx *c, const float *nl, int stride, int B) {
@@ -1201,6 +1221,102 @@ int step_checked(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     return 0;
 }
 
+// ---- one conv on scratch buffers (sr3_op_conv2d, sr3_bench_conv) ------------------------------------------------
+// device memory of one call: freed on every return
+struct DevBuf {
+    float *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    ~DevBuf() { (void)hipFree(p); }            // (a null pointer is a no-op)
+    int alloc(size_t floats) { HIP_OK(hipMalloc(&p, floats * sizeof(float))); return 0; }
+    int upload(const float *host, size_t floats) {
+        if (alloc(floats)) return -1;
+        HIP_OK(hipMemcpy(p, host, floats * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+
+void fill_random(sr3_ctx *c, float *q, size_t n, int seed) {
+    launch_philox_normal(seed, 0, 0, (int)std::min<size_t>(n, 1u << 30), q, c->stream);
+}
+
+// A single conv as the engine runs this shape: the plan of the shape with every buffer offered (no fused statistics)
+// names the weight layouts and scratch buffers; p comes back with input, weights, partials and Winograd workspace
+// filled in — output, bias, residual and FeatureWiseAffine bias are the caller's.
+struct ScratchConv {
+    ConvPlan plan;
+    bool f8 = false;                // "f16f8" mode and the shape takes the F8C operand format
+    DevBuf act, w, wino_w, wino_ws, part;
+    ConvParams p;
+
+    // weight_host: OIHW weights, nullptr: random values (timing). The activated input `act` (zero-bordered, Cin
+    // channels) is allocated and left for the caller to fill.
+    int setup(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout, int ks, int stride, int up2, const float *weight_host) {
+        const int Cin = C0 + C1;
+        f8 = c->prec == 1 && c->f8corr && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin);
+        plan = conv_plan_offered(B, Hin, Win, Cin, Cout, ks, stride, up2, c->prec, f8, false);
+        const bool wino = plan.kernel == CK_WINO_ONE_PASS || plan.kernel == CK_WINO_THREE_PASS;
+        const size_t n_w = (size_t)(up2 ? 16 : ks * ks) * Cout * Cin;     // up2: 4 phases x 2x2 taps
+        const size_t n_wino = (size_t)16 * Cout * Cin;
+        if (weight_host) {
+            std::vector<float> packed((size_t)ks * ks * Cout * Cin), tmp;
+            pack_conv_weight(weight_host, Cout, Cin, ks, Cin, packed.data());
+            if (up2) {
+                tmp.resize(n_w);
+                make_up2_phase_weights(packed.data(), Cout, Cin, tmp.data());
+                packed.swap(tmp);
+            }
+            if (wino) {
+                std::vector<float> wv(n_wino);
+                make_wino_weights(packed.data(), Cout, Cin, wv.data());
+                if (plan.needs_wino_frag) {
+                    tmp.resize(n_wino);
+                    make_wino_weights_frag(wv.data(), Cout, Cin, tmp.data());
+                    wv.swap(tmp);
+                }
+                if (wino_w.upload(wv.data(), n_wino)) return -1;
+            }
+            if (c->prec) {
+                tmp.resize(n_w);
+                p.w_unscale = split_conv_weight(packed.data(), n_w / Cin, Cin, tmp.data());
+                packed.swap(tmp);
+            }
+            if (w.upload(packed.data(), n_w)) return -1;
+            if (f8) {
+                DevBuf w8;
+                if (w8.alloc(n_w)) return -1;
+                launch_make_f8_weights(w.p, w8.p, n_w / 32, c->stream);
+                HIP_OK(hipStreamSynchronize(c->stream));
+                std::swap(w.p, w8.p);
+            }
+        } else {
+            if (w.alloc(n_w)) return -1;
+            fill_random(c, w.p, n_w, 3);
+            if (wino) {
+                if (wino_w.alloc(n_wino)) return -1;
+                fill_random(c, wino_w.p, n_wino, 10);       // (either layout: random values)
+            }
+        }
+        if (plan.wino_ws_floats && wino_ws.alloc(plan.wino_ws_floats)) return -1;
+        if (plan.part_floats && part.alloc(plan.part_floats)) return -1;
+        TDesc a; a.C = Cin; a.H = Hin; a.W = Win; a.pad = 1;
+        if (act.alloc(a.floats(B))) return -1;
+        a.p = act.p;
+        const int pad = ks / 2, Hv = Hin << up2, Wv = Win << up2;
+        p.in0 = a; p.B = B;
+        p.Hout = (Hv + 2 * pad - ks) / stride + 1; p.Wout = (Wv + 2 * pad - ks) / stride + 1;
+        p.ks = ks; p.stride = stride; p.up2 = up2;
+        p.prec = c->prec; p.f8 = f8 ? 1 : 0;
+        p.w = w.p;
+        (plan.needs_wino_frag ? p.w_wino_f : p.w_wino) = wino_w.p;
+        p.wino_ws = wino_ws.p;
+        p.part = part.p;
+        if (part.p) p.tile_cnt = c->tile_cnt;
+        p.ovf = c->d_ovf;            // (range bits of twin stores and the 'wait gave up' bit of the in-place split-K)
+        return 0;
+    }
+};
+
 } // namespace
 
 // =================================================================================================
@@ -1320,6 +1436,22 @@ int sr3_set_precision(sr3_ctx *c, int prec) {
 }
 
 int sr3_conv_f8_supported(int B, int H, int W, int Cout, int Cin) { return conv_f8_supported(B, H, W, Cout, Cin) ? 1 : 0; }
+
+int sr3_conv_plan(int B, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int precision, int with_stats,
+                  int64_t *out12, char *kernel_name, int name_cap) {
+    if (!out12) return fail("sr3_conv_plan: null argument");
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % 32) || !(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) ||
+        (up2 & ~1) || (up2 && (ks != 3 || stride != 1)) || precision < 0 || precision > 2)
+        return fail("sr3_conv_plan: unsupported conv (Cin a multiple of 32, ks 1 | 3, stride 1 | 2, up2 with ks 3 / stride 1, precision 0..2)");
+    const bool f8 = precision == 2 && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, H, W, Cout, Cin);
+    const ConvPlan pl = conv_plan_offered(B, H, W, Cin, Cout, ks, stride, up2, precision ? 1 : 0, f8, with_stats != 0);
+    if (pl.error) return fail("sr3_conv_plan: %s", pl.error);
+    const int64_t v[12] = {pl.kernel, pl.tile_m, pl.tile_n, pl.split, pl.splits, pl.phases, (int64_t)pl.part_floats,
+                           pl.needs_counters, pl.stats_slices, (int64_t)pl.wino_ws_floats, pl.needs_wino_frag, f8};
+    std::copy(v, v + 12, out12);
+    if (kernel_name && name_cap > 0) snprintf(kernel_name, (size_t)name_cap, "%s", conv_kernel_name(pl.kernel));
+    return 0;
+}
 
 int sr3_wino_weights_host(const float *packed_host, int Cout, int CinPad, int frag, float *dst_host) {
     if (!packed_host || !dst_host || Cout <= 0 || CinPad <= 0 || (CinPad % 8))
@@ -1771,116 +1903,39 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     if ((C0 % 32) || (C1 % 32) || C0 <= 0 || C1 < 0) return fail("sr3_op_conv2d: C0=%d C1=%d must be multiples of 32", C0, C1);
     if (!(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (up2 & ~1)) return fail("sr3_op_conv2d: bad ks/stride/up2");
     if ((gn_scale_dev == nullptr) != (gn_shift_dev == nullptr)) return fail("sr3_op_conv2d: scale and shift go together");
+    if (up2 && (ks != 3 || stride != 1)) return fail("sr3_op_conv2d: up2 needs ks 3, stride 1");
     HIP_OK(hipSetDevice(c->device));
     if (!in1_dev) C1 = 0;
-    const int Cin = C0 + C1, taps = ks * ks;
-    std::vector<float> packed((size_t)taps * Cout * Cin);
-    pack_conv_weight(weight_host, Cout, Cin, ks, Cin, packed.data());
-    float w_unscale = 1.0f;
-    size_t rows = (size_t)taps * Cout;
-    if (up2) {
-        if (ks != 3 || stride != 1) return fail("sr3_op_conv2d: up2 needs ks 3, stride 1");
-        std::vector<float> ph((size_t)16 * Cout * Cin);
-        make_up2_phase_weights(packed.data(), Cout, Cin, ph.data());
-        packed.swap(ph);
-        rows = (size_t)16 * Cout;
-    }
-    // Winograd form where the engine would take it for this shape (launch_conv decides per launch)
-    float *dww = nullptr, *dws = nullptr;
-    bool wfrag = false;            // dww in the one-pass kernel's fragment-major order (w_wino_f)
-    if (!c->prec && ks == 3 && stride == 1 && !up2 && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
-        std::vector<float> wv((size_t)16 * Cout * Cin);
-        make_wino_weights(packed.data(), Cout, Cin, wv.data());
-        if ((wfrag = conv_wino_fused(B, Hin, Win, Cin, Cout))) {
-            std::vector<float> wf(wv.size());
-            make_wino_weights_frag(wv.data(), Cout, Cin, wf.data());
-            wv.swap(wf);
-        }
-        HIP_OK(hipMalloc(&dww, wv.size() * sizeof(float)));
-        HIP_OK(hipMemcpy(dww, wv.data(), wv.size() * sizeof(float), hipMemcpyHostToDevice));
-        if (const size_t wsf = conv_wino_ws_floats(B, Hin, Win, Cin, Cout)) HIP_OK(hipMalloc(&dws, wsf * sizeof(float)));
-    }
-    if (c->prec) {
-        std::vector<float> sp(packed.size());
-        w_unscale = split_conv_weight(packed.data(), rows, Cin, sp.data());
-        packed.swap(sp);
-    }
-    float *dw = nullptr, *db = nullptr, *act = nullptr;
-    HIP_OK(hipMalloc(&dw, packed.size() * sizeof(float)));
-    HIP_OK(hipMemcpy(dw, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    // "f16f8" mode: the conv runs as the engine would run it for this shape (F8C operands where conv_f8_supported)
-    const bool f8 = c->prec == 1 && c->f8corr && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin);
-    if (f8) {
-        float *dw8 = nullptr;
-        HIP_OK(hipMalloc(&dw8, packed.size() * sizeof(float)));
-        launch_make_f8_weights(dw, dw8, packed.size() / 32, c->stream);
-        HIP_OK(hipStreamSynchronize(c->stream));
-        HIP_OK(hipFree(dw));
-        dw = dw8;
-    }
-    if (bias_host) {
-        HIP_OK(hipMalloc(&db, (size_t)Cout * sizeof(float)));
-        HIP_OK(hipMemcpy(db, bias_host, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice));
-    }
+    ScratchConv sc;
+    if (sc.setup(c, B, Hin, Win, C0, C1, Cout, ks, stride, up2, weight_host)) return -1;
+    DevBuf bias;
+    if (bias_host && bias.upload(bias_host, (size_t)Cout)) return -1;
+    ConvParams &p = sc.p;
+    p.bias = bias.p; p.chan_bias = chan_bias_dev; p.chan_bias_stride = Cout;
+    p.out = unpadded(out_dev, Cout, p.Hout, p.Wout);
+    if (resid_dev) p.resid = unpadded(const_cast<float *>(resid_dev), Cout, p.Hout, p.Wout);
     // the engine's own sequence: (GroupNorm apply | copy) + concat into a zero-bordered tensor, then conv
-    TDesc a; a.C = Cin; a.H = Hin; a.W = Win; a.pad = 1;
-    const size_t act_floats = a.floats(B);
-    HIP_OK(hipMalloc(&act, act_floats * sizeof(float)));
-    HIP_OK(hipMemsetAsync(act, 0, act_floats * sizeof(float), c->stream));
-    a.p = act;
+    HIP_OK(hipMemsetAsync(p.in0.p, 0, p.in0.floats(B) * sizeof(float), c->stream));
     const TDesc i0 = unpadded(const_cast<float *>(in0_dev), C0, Hin, Win);
     const TDesc i1 = in1_dev ? unpadded(const_cast<float *>(in1_dev), C1, Hin, Win) : kNone;
     if (range_reset(c)) return -1;
-    launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, gn_scale_dev ? (swish ? 2 : 1) : 0, f8 ? 2 : c->prec, a,
+    launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, gn_scale_dev ? (swish ? 2 : 1) : 0, sc.f8 ? 2 : c->prec, p.in0,
                     c->stream, TDesc(), 0, c->d_ovf);
-    const int pad = ks / 2, Hv = Hin << up2, Wv = Win << up2;
-    ConvParams p;
-    p.in0 = a; p.B = B;
-    p.Hout = (Hv + 2 * pad - ks) / stride + 1; p.Wout = (Wv + 2 * pad - ks) / stride + 1;
-    p.ks = ks; p.stride = stride; p.up2 = up2;
-    p.prec = c->prec; p.w_unscale = w_unscale; p.f8 = f8 ? 1 : 0;
-    p.w = dw; p.bias = db; p.chan_bias = chan_bias_dev; p.chan_bias_stride = Cout;
-    (wfrag ? p.w_wino_f : p.w_wino) = dww;
-    p.wino_ws = dws;
-    p.out = unpadded(out_dev, Cout, p.Hout, p.Wout);
-    p.ovf = c->d_ovf;            // (range bits of twin stores and the 'wait gave up' bit of the in-place split-K)
-    if (resid_dev) p.resid = unpadded(const_cast<float *>(resid_dev), Cout, p.Hout, p.Wout);
-    // split-K exactly as the engine would choose it for this problem (in place or conv + reduce kernel)
-    float *part = nullptr;
-    {
-        const long Mo = (long)B * (up2 ? Hin * Win : p.Hout * p.Wout);
-        p.splits = conv_splits(Mo, Cout, Cin);
-        const int hs = (c->prec && ks == 3 && stride == 1 && !up2) ? conv_halo_splits(Mo, p.Hout, p.Wout, Cout, Cin) : 0;
-        if (p.splits > 1 || hs > 1) {
-            HIP_OK(hipMalloc(&part, (size_t)(up2 ? 4 : 1) * std::max(p.splits, hs) * Mo * Cout * sizeof(float)));
-            p.part = part;
-            p.tile_cnt = c->tile_cnt;
-        }
-    }
     // (this entry point owns its inputs: an in-place split-K wait that gave up — range_read == 2 — is answered by running
     // the conv again on the non-waiting path, as sr3_unet_forward / sr3_sample do)
-    int rc = 0;
     bool replayed = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
         p.no_halo_split = c->halo_split_off ? 1 : 0;
-        if (up2) launch_conv_up2(p, c->stream);
-        else launch_conv(p, c->stream);
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) { rc = fail("sr3_op_conv2d: launch failed"); break; }
-        if (const char *e = conv_take_error()) { rc = fail("sr3_op_conv2d: %s", e); break; }
+        launch_conv(p, c->stream);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("sr3_op_conv2d: launch failed");
+        if (const char *e = conv_take_error()) return fail("sr3_op_conv2d: %s", e);
         if (!c->prec) break;
         const int r = range_read(c);
         if (r == 2 && attempt == 0) { replayed = true; continue; }
-        rc = r == 0 ? 0 : (r < 0 ? -1 : (r == 2 ? fail("internal: inter-block wait flag raised with the in-place split-K disabled")
-                                                 : range_fail(c, "sr3_op_conv2d")));
+        if (r == 2) return fail("internal: inter-block wait flag raised with the in-place split-K disabled");
+        if (r) return r < 0 ? -1 : range_fail(c, "sr3_op_conv2d");
         break;
     }
-    HIP_OK(hipFree(dw));
-    HIP_OK(hipFree(act));
-    if (db) HIP_OK(hipFree(db));
-    if (part) HIP_OK(hipFree(part));
-    if (dww) HIP_OK(hipFree(dww));
-    if (dws) HIP_OK(hipFree(dws));
-    if (rc) return rc;
     return replayed ? warn_replay(c, "sr3_op_conv2d", "the conv") : 0;
 }
 
@@ -1892,66 +1947,34 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     if (!c || !avg_ms) return fail("null argument");
     if ((C0 % 32) || (C1 % 32) || C0 <= 0) return fail("sr3_bench_conv: channels must be multiples of 32");
     HIP_OK(hipSetDevice(c->device));
-    const int Cin = C0 + C1, pad = ks / 2, Hv = Hin << up2, Wv = Win << up2;
-    const int Ho = (Hv + 2 * pad - ks) / stride + 1, Wo = (Wv + 2 * pad - ks) / stride + 1;
-    TDesc i0, i1, act, out, res;
-    i0.C = C0; i1.C = C1; act.C = Cin; out.C = res.C = Cout;
-    i0.H = i1.H = act.H = Hin; i0.W = i1.W = act.W = Win; out.H = res.H = Ho; out.W = res.W = Wo;
-    i0.pad = i1.pad = act.pad = out.pad = res.pad = 1;
-    const size_t n_w = (size_t)(up2 ? 16 : ks * ks) * Cout * Cin;     // up2: 4 phases x 2x2 taps
-    float *w, *bias, *sc, *sh, *cb;
-    HIP_OK(hipMalloc(&i0.p, i0.floats(B) * 4));
-    if (C1) HIP_OK(hipMalloc(&i1.p, i1.floats(B) * 4));
-    HIP_OK(hipMalloc(&act.p, act.floats(B) * 4));
-    HIP_OK(hipMalloc(&out.p, out.floats(B) * 4));
-    HIP_OK(hipMalloc(&res.p, res.floats(B) * 4));
-    HIP_OK(hipMalloc(&w, n_w * 4));
-    HIP_OK(hipMalloc(&bias, (size_t)Cout * 4));
-    HIP_OK(hipMalloc(&sc, (size_t)B * Cin * 4));
-    HIP_OK(hipMalloc(&sh, (size_t)B * Cin * 4));
-    HIP_OK(hipMalloc(&cb, (size_t)B * Cout * 4));
-    auto rnd = [&](float *q, size_t n, int seed) { launch_philox_normal(seed, 0, 0, (int)std::min<size_t>(n, 1u << 30), q, c->stream); };
-    rnd(i0.p, i0.floats(B), 1); if (C1) rnd(i1.p, i1.floats(B), 2);
-    rnd(act.p, act.floats(B), 9); rnd(w, n_w, 3); rnd(bias, Cout, 4); rnd(res.p, res.floats(B), 5);
-    rnd(sc, (size_t)B * Cin, 6); rnd(sh, (size_t)B * Cin, 7); rnd(cb, (size_t)B * Cout, 8);
-    ConvParams p;
-    p.in0 = act; p.B = B; p.Hout = Ho; p.Wout = Wo;
-    p.ks = ks; p.stride = stride; p.up2 = up2; p.w = w; p.bias = bias;
-    p.prec = c->prec;
-    const bool f8 = c->prec == 1 && c->f8corr && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin);
-    p.f8 = f8 ? 1 : 0;       // (timing: the operand bytes are random either way)
-    p.chan_bias = with_chan_bias ? cb : nullptr; p.chan_bias_stride = Cout;
+    ScratchConv sc;
+    if (sc.setup(c, B, Hin, Win, C0, C1, Cout, ks, stride, up2, nullptr)) return -1;
+    ConvParams &p = sc.p;
+    const int Cin = C0 + C1;
+    TDesc i0, i1, out, res;
+    i0.C = C0; i1.C = C1; out.C = res.C = Cout;
+    i0.H = i1.H = Hin; i0.W = i1.W = Win; out.H = res.H = p.Hout; out.W = res.W = p.Wout;
+    i0.pad = i1.pad = out.pad = res.pad = 1;
+    DevBuf d_i0, d_i1, d_out, d_res, bias, scale, shift, cb;
+    if (d_i0.alloc(i0.floats(B)) || (C1 && d_i1.alloc(i1.floats(B))) || d_out.alloc(out.floats(B)) || d_res.alloc(res.floats(B)) ||
+        bias.alloc((size_t)Cout) || scale.alloc((size_t)B * Cin) || shift.alloc((size_t)B * Cin) || cb.alloc((size_t)B * Cout))
+        return -1;
+    i0.p = d_i0.p; i1.p = d_i1.p; out.p = d_out.p; res.p = d_res.p;
+    fill_random(c, i0.p, i0.floats(B), 1);
+    if (C1) fill_random(c, i1.p, i1.floats(B), 2);
+    fill_random(c, p.in0.p, p.in0.floats(B), 9); fill_random(c, bias.p, Cout, 4); fill_random(c, res.p, res.floats(B), 5);
+    fill_random(c, scale.p, (size_t)B * Cin, 6); fill_random(c, shift.p, (size_t)B * Cin, 7); fill_random(c, cb.p, (size_t)B * Cout, 8);
+    p.bias = bias.p;
+    p.chan_bias = with_chan_bias ? cb.p : nullptr; p.chan_bias_stride = Cout;
     if (with_resid) p.resid = res;
     p.out = out;
-    p.ovf = c->d_ovf;
-    float *wino_w = nullptr, *wino_ws = nullptr;      // Winograd form where the engine would take it (random weights)
-    if (!c->prec && ks == 3 && stride == 1 && !up2 && conv_wino_supported(B, Hin, Win, Cin, Cout)) {
-        HIP_OK(hipMalloc(&wino_w, (size_t)16 * Cout * Cin * 4));
-        if (const size_t wsf = conv_wino_ws_floats(B, Hin, Win, Cin, Cout)) HIP_OK(hipMalloc(&wino_ws, wsf * 4));
-        rnd(wino_w, (size_t)16 * Cout * Cin, 10);
-        (conv_wino_fused(B, Hin, Win, Cin, Cout) ? p.w_wino_f : p.w_wino) = wino_w;   // (either layout: random values)
-        p.wino_ws = wino_ws;
-    }
-    // split-K exactly as the engine would choose it for this problem (partials on a scratch buffer)
-    float *part = nullptr;
-    {
-        const long Mo = (long)B * (up2 ? (Ho / 2) * (Wo / 2) : Ho * Wo);
-        p.splits = conv_splits(Mo, Cout, Cin);
-        const int hs = (c->prec && ks == 3 && stride == 1 && !up2) ? conv_halo_splits(Mo, Ho, Wo, Cout, Cin) : 0;
-        if (p.splits > 1 || hs > 1) {
-            HIP_OK(hipMalloc(&part, (size_t)(up2 ? 4 : 1) * std::max(p.splits, hs) * Mo * Cout * sizeof(float)));
-            p.part = part;
-            p.tile_cnt = c->tile_cnt;
-        }
-    }
     hipEvent_t e0, e1, e2;
     HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1)); HIP_OK(hipEventCreate(&e2));
-    auto go = [&]() { if (up2) launch_conv_up2(p, c->stream); else launch_conv(p, c->stream); };
-    for (int i = 0; i < 2; ++i) go();
+    for (int i = 0; i < 2; ++i) launch_conv(p, c->stream);
     HIP_OK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < iters; ++i) go();
+    for (int i = 0; i < iters; ++i) launch_conv(p, c->stream);
     HIP_OK(hipEventRecord(e1, c->stream));
-    for (int i = 0; i < iters; ++i) launch_gn_apply(i0, C1 ? i1 : kNone, B, sc, sh, mode, f8 ? 2 : c->prec, act, c->stream);
+    for (int i = 0; i < iters; ++i) launch_gn_apply(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, sc.f8 ? 2 : c->prec, p.in0, c->stream);
     HIP_OK(hipEventRecord(e2, c->stream));
     HIP_OK(hipEventSynchronize(e2));
     float ms = 0.f;
@@ -1960,8 +1983,6 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     HIP_OK(hipEventElapsedTime(&ms, e1, e2));
     if (apply_ms) *apply_ms = ms / iters;
     HIP_OK(hipEventDestroy(e0)); HIP_OK(hipEventDestroy(e1)); HIP_OK(hipEventDestroy(e2));
-    for (float *q : {i0.p, i1.p, act.p, out.p, res.p, w, bias, sc, sh, cb, part, wino_w, wino_ws})
-        if (q) HIP_OK(hipFree(q));
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -14,7 +14,7 @@ namespace sr3 {
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
 //   SR3_HALO_SPLITS=0|2|4   in-place split-K of deep-K convs on 128x128 x-halo tiles: off / forced
 //   SR3_NO_INPLACE_SPLIT=1  split-K always as conv + reduce kernel
-//   SR3_NO_WINOGRAD=1       exact-f32 3x3 convs always on the direct implicit-GEMM kernel (conv_wino_supported)
+//   SR3_NO_WINOGRAD=1       exact-f32 3x3 convs always on the direct implicit-GEMM kernel (conv_plan)
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Activation tensor: NHWC fp32 with an optional 1-pixel zero border ("pad") stored around every
@@ -41,7 +41,7 @@ struct ConvParams {
     int B = 0;
     int Hout = 0, Wout = 0;
     int ks = 3, stride = 1, up2 = 0;   // ks 1 | 2 | 3; ks == 2 (stride 1) reads the window (oy+org_y+{0,1}, ox+org_x+{0,1})
-    // sub-pixel phases of the upsample conv (launch_conv_up2): window origin shift in padded
+    // sub-pixel phases of the upsample conv (launch_conv, up2): window origin shift in padded
     // coordinates, and the output pixel written for window (oy, ox) is (oy*out_step + out_oy, ...)
     int org_y = 0, org_x = 0;
     int out_step = 1, out_oy = 0, out_ox = 0;
@@ -65,7 +65,7 @@ struct ConvParams {
     int chan_bias_stride = 0;
     // optional fused GroupNorm statistics of the OUTPUT: per (image, M-tile-in-image, channel)
     // {sum, sum of squares} in fp64 at stats[((n * stats_slices + slice) * Cout + c) * 2]; requires
-    // Hout*Wout % BM == 0 for the tile the launcher picks (launch_conv_tile_m tells)
+    // Hout*Wout % BM == 0 for the tile the launcher picks; stats_slices as ConvPlan::stats_slices tells
     double *stats = nullptr;
     int stats_slices = 0;
     TDesc resid;            // p == nullptr if none; same geometry as out
@@ -91,24 +91,25 @@ struct ConvParams {
     float w_unscale = 1.0f;
     // split-K for small problems (few tiles, deep K): `splits` blocks share one output tile, each
     // reducing a contiguous range of 32-channel chunks into part[split][M][Cout]; a second kernel
-    // adds the partials and applies the epilogue. splits <= 1: single pass.
+    // adds the partials and applies the epilogue. splits <= 1: single pass. Set by launch_conv from its plan (a caller's
+    // value is ignored); part: ConvPlan::part_floats floats, nullptr: never split
     int splits = 1;
     float *part = nullptr;
-    // in-place split-K (conv_split_inplace() tells when launch_conv uses it): one zero-initialised counter per
+    // in-place split-K (ConvPlan::split tells when launch_conv uses it): CONV_TILE_COUNTERS counters, one zero-initialised counter per
     // output tile and sub-pixel phase; the last block to arrive at a tile adds the partials and runs the
     // epilogue itself (no reduce kernel; fused statistics in the unsplit layout: one slice per M-tile).
     // nullptr: always the two-kernel form.
     unsigned *tile_cnt = nullptr;
-    // 1: never the in-place split-K of the 128x128 x-halo tile (conv_halo_splits) — set for the rest of a context's
+    // 1: never the in-place split-K of the 128x128 x-halo tile (CS_INPLACE_HALO) — set for the rest of a context's
     // life once one of its bounded inter-block waits gave up (SR3_FLAG_WAIT_TIMEOUT): the conv then runs unsplit on the
     // generic 64x64 tile, whose blocks never wait for each other
     int no_halo_split = 0;
     // split-f16 range check: any value stored in the split format (out_split) with |v| > 65504 (or
     // non-finite) sets *ovf = 1; the API call that ran the launch then fails (never a silent clamp)
     int *ovf = nullptr;
-    // Winograd F(2x2, 3x3) form of this conv (prec 0 only; launch_conv takes it where conv_wino_supported says so and
-    // the conv uses nothing the Winograd path does not handle): transformed weights [16][Cout][CinPad]
-    // (make_wino_weights) and a workspace of conv_wino_ws_floats() floats; either null: direct kernel
+    // Winograd F(2x2, 3x3) form of this conv (prec 0 only; conv_plan takes it where the shape gains and the conv uses
+    // nothing the Winograd path does not handle): transformed weights [16][Cout][CinPad] (make_wino_weights) and a
+    // workspace of ConvPlan::wino_ws_floats floats; either null: direct kernel
     const float *w_wino = nullptr;
     float *wino_ws = nullptr;
     // the one-pass kernel's copy of w_wino in fragment-major order [16][CinPad/8][Cout][8] (make_wino_weights_frag);
@@ -154,21 +155,50 @@ constexpr int SR3_F8_XH = 0, SR3_F8_XL = 11;      // xh8 = e4m3(xh), xl8 = e4m3(
 constexpr int SR3_F8_WH = -3, SR3_F8_WL = 9;      // weights are pre-scaled into [1024, 2048): wh8 < 256, |wl| <= 0.5 -> wl8 <= 256
 constexpr float SPLIT_F8_MAX = 448.0f;
 // true when launch_conv runs this 3x3 / stride-1 split-f16 conv with the fp8 correction products if ConvParams::f8 is set
-// (the caller then writes the conv's input with split format 2 and passes the F8C weights)
+// (the caller then writes the conv's input with split format 2 and passes the F8C weights): conv_plan's answer
 bool conv_f8_supported(int B, int H, int W, int Cout, int Cin);
 // split weights [chunks][32 hi | 32 lo] -> F8C weights [chunks][32 hi | 32 wh8 | 32 wl8] (device to device)
 void launch_make_f8_weights(const float *split, float *dst, size_t chunks, hipStream_t s);
+// ---- the dispatch plan: which kernel, which split-K form, which buffers — decided in ONE place (conv_plan) ----------
+enum ConvKernel {
+    CK_WINO_ONE_PASS, CK_WINO_THREE_PASS,                        // exact-f32 Winograd F(2x2, 3x3) (kernels_wino.hip)
+    CK_HALO_F8C, CK_HALO_128x128_SEG32, CK_HALO_128x128_SEG8, CK_HALO_128x64,     // x-halo kernels (split-f16)
+    CK_GENERIC_128x32, CK_GENERIC_128x64, CK_GENERIC_64x64, CK_GENERIC_128x128,   // implicit GEMM over LDS-DMA rings
+    CK_COUNT
+};
+const char *conv_kernel_name(ConvKernel k);
+enum ConvSplit { CS_NONE, CS_REDUCE, CS_INPLACE, CS_INPLACE_HALO };   // conv + reduce kernel | in place, 64x64 tile | in place, x-halo tile
+constexpr int CONV_TILE_COUNTERS = 8192;    // capacity of ConvParams::tile_cnt (tiles x phases of one launch)
+struct ConvPlan {
+    ConvKernel kernel = CK_GENERIC_128x128;
+    int tile_m = 128, tile_n = 128;    // output tile of the main kernel (Winograd: of the direct kernel the shape would take)
+    ConvSplit split = CS_NONE;
+    int splits = 1;                    // K-splits (1 = none)
+    int phases = 1;                    // 4: the sub-pixel phases of an upsample conv in one launch
+    size_t part_floats = 0;            // ConvParams::part as this launch uses it (all phases), 0 = none
+    bool needs_counters = false;       // ConvParams::tile_cnt is used (in-place split-K)
+    // slices per image the fused statistics of the output come in for this shape (what the caller passes as
+    // ConvParams::stats_slices with ConvParams::stats), 0 = no fused statistics: the caller's statistics kernel runs
+    int stats_slices = 0;
+    size_t wino_ws_floats = 0;         // ConvParams::wino_ws: U [16][B*H*W/4][Cin] + M [16][B*H*W/4][Cout] (three-pass form)
+    bool needs_wino_frag = false;      // reads ConvParams::w_wino_f (one-pass form)
+    const char *error = nullptr;       // a request no kernel honours (ConvParams::f8 on a shape outside the F8C kernel)
+};
+// reads p as launch_conv does: a null part / tile_cnt / w_wino / w_wino_f / wino_ws / stats means "not offered", and the
+// plan degrades (no split-K, two-kernel split, direct kernel); p.up2: p describes the conv at the OUTPUT resolution
+ConvPlan conv_plan(const ConvParams &p);
+// the plan of a conv shape with every buffer offered (fused statistics, in the layout the plan names, only with
+// `stats`) — for callers that size buffers before they exist. H, W: input size; f8: the F8C request (prec 1)
+ConvPlan conv_plan_offered(int B, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int prec, bool f8, bool stats);
+// computes the plan and launches it. Upsample (nearest x2) + conv3x3 (unet.py:58-65, p.up2) runs as four sub-pixel
+// phases in one launch: output pixels of parity (py, px) see only a 2x2 window of the low-resolution input, with the
+// 3x3 taps that land on the same source pixel pre-added (make_up2_phase_weights) — 16 instead of 36 MACs per
+// low-resolution pixel, channel pair and 2x2 output block. p then describes the conv at the OUTPUT resolution (Hout,
+// Wout = 2H, 2W; in0 = low-resolution input), p.w = phase weights [4 phases][4 taps][Cout][CinPad].
 void launch_conv(const ConvParams &p, hipStream_t s);
 // launch_conv never aborts the process: a request it cannot honour (a caller / library bug) launches nothing and leaves
 // a message here; returns it once (nullptr if none) — the C-ABI entry points fail the call with it
 const char *conv_take_error();
-// Upsample (nearest x2) + conv3x3 (unet.py:58-65) as four sub-pixel phases: output pixels of
-// parity (py, px) see only a 2x2 window of the low-resolution input, with the 3x3 taps that land
-// on the same source pixel pre-added (make_up2_phase_weights) — 16 instead of 36 MACs per
-// low-resolution pixel, channel pair and 2x2 output block. p describes the conv at the OUTPUT
-// resolution (Hout, Wout = 2H, 2W; in0 = low-resolution input); p.w = phase weights
-// [4 phases][4 taps][Cout][CinPad]; stats_slices must be 4 * (H*W / conv_tile_m(B*H*W, Cout)).
-void launch_conv_up2(const ConvParams &p, hipStream_t s);
 // packed [9][Cout][CinPad] -> [py*2+px][dy2*2+dx2][Cout][CinPad]
 void make_up2_phase_weights(const float *packed9, int Cout, int CinPad, float *dst);
 // ---- Winograd F(2x2, 3x3) for the exact-f32 3x3 convs of the deep levels (kernels_wino.hip) ----------------------
@@ -182,36 +212,17 @@ constexpr int WINO_MIN_TILES = 1024;   // fewer 2x2 output tiles per launch (B *
 // many blocks of 32 tiles x 64 output channels (4 per CU) — fewer: the direct kernel
 constexpr int WINO_FUSED_CIN = 64;
 constexpr int WINO_FUSED_MIN_BLOCKS = 1024;
-// shape rule of the dispatch (3x3 / stride 1 / prec 0 convs): false also under SR3_NO_WINOGRAD=1
-bool conv_wino_supported(int B, int H, int W, int Cin, int Cout);
-// U [16][B*H*W/4][Cin] + M [16][B*H*W/4][Cout] for the three-pass form, 0 for the one-pass kernel
-size_t conv_wino_ws_floats(int B, int H, int W, int Cin, int Cout);
+// the one-pass kernel's block: a strip of WINO_FUSED_TILES 2x2 tiles along a tile row x WINO_FUSED_BN output channels
+constexpr int WINO_FUSED_TILES = 32, WINO_FUSED_BN = 64;
 // host helper: packed [9][Cout][CinPad] -> G g G^T as [16][Cout][CinPad] (fp64, rounded once to fp32)
 void make_wino_weights(const float *packed9, int Cout, int CinPad, float *dst);
-// conv_wino_supported and of the one-pass shapes (wino_fused_kernel, which reads ConvParams::w_wino_f)
-bool conv_wino_fused(int B, int H, int W, int Cin, int Cout);
 // host helper: [16][Cout][CinPad] (make_wino_weights) -> [16][CinPad/8][Cout][8]; launch_wino_frag: the same on the device
 void make_wino_weights_frag(const float *wino, int Cout, int CinPad, float *dst);
 void launch_wino_frag(const float *wino, int Cout, int CinPad, float *dst, hipStream_t s);
-// true when launch_conv runs this conv in Winograd form (p.w_wino / p.wino_ws set, as launch_conv would see it)
-bool conv_wino_taken(const ConvParams &p);
-void launch_conv_wino(const ConvParams &p, hipStream_t s);
+// the Winograd form conv_plan chose (CK_WINO_ONE_PASS | CK_WINO_THREE_PASS)
+void launch_conv_wino(const ConvParams &p, ConvKernel form, hipStream_t s);
 // the 16 position GEMMs of one Winograd conv on conv_igemm_dma_f32 (kernels_conv.hip); p as described at zbatch
 void launch_wino_gemm(const ConvParams &p, hipStream_t s);
-// BM of the tile launch_conv will use for this problem (so callers can size / enable fused stats)
-int conv_tile_m(long M, int Cout);
-// number of K-splits launch_conv wants for this problem (1 = none); Cin per tap, multiple of 32
-int conv_splits(long M, int Cout, int Cin);
-// true when a split conv of this shape adds its partials in place (ConvParams::tile_cnt given): its fused statistics
-// then have the unsplit layout, HWo / conv_tile_m() slices per image; HWo = pixels of one image (and phase)
-bool conv_split_inplace(long M, int HWo, int Cout, int Cin, int phases = 1);
-// K-splits of the 128x128 x-halo tile for deep-K 3x3 / stride-1 split-f16 convs over few tiles (kernels_conv.hip); <= 1: none
-int conv_halo_splits(long M, int H, int W, int Cout, int Cin);
-constexpr int CONV_TILE_COUNTERS = 8192;    // capacity of ConvParams::tile_cnt (tiles x phases of one launch)
-// a split conv's fused GroupNorm statistics come out of its reduce pass: slices per image (and per
-// sub-pixel phase) for an output of HWo pixels; the caller sizes / strides ConvParams::stats with it
-// (0: not available for this shape)
-int splitk_stats_slices(int HWo, int Cout);
 // host helper: OIHW -> [tap][Cout][CinPad] (zero pad input channels up to CinPad)
 void pack_conv_weight(const float *oihw, int Cout, int Cin, int ks, int CinPad, float *dst);
 // host helper: fp32 packed weights -> split-f16 layout (same byte size), returns the unscale factor

@@ -67,6 +67,24 @@ class DeviceBuffer:
             pass
 
 
+PRECISIONS = {"f32": 0, "f16x3": 1, "f16f8": 2}
+SPLIT_KINDS = ("none", "reduce", "inplace", "inplace_halo")
+
+
+def conv_plan(B: int, H: int, W: int, Cin: int, Cout: int, ks: int = 3, stride: int = 1, up2: int = 0,
+              precision: str = "f32", stats: bool = False) -> dict:
+    """The library's dispatch plan for one conv shape (H x W input pixels, Cin a multiple of 32) with every scratch buffer
+    offered; stats: the conv also produces fused GroupNorm statistics (the UNet's convs do, op_conv2d does not). Host
+    only: needs no GPU and no context."""
+    v = (C.c_int64 * 12)()
+    name = C.create_string_buffer(32)
+    _lib.check(_lib.load().sr3_conv_plan(B, H, W, Cin, Cout, ks, stride, up2, PRECISIONS[precision], int(bool(stats)),
+                                         v, name, len(name)))
+    return {"kernel": name.value.decode(), "kernel_id": v[0], "tile": [v[1], v[2]], "split": SPLIT_KINDS[v[3]], "splits": v[4],
+            "phases": v[5], "part_floats": v[6], "needs_counters": bool(v[7]), "stats_slices": v[8],
+            "wino_ws_floats": v[9], "needs_wino_frag": bool(v[10]), "f8": bool(v[11])}
+
+
 class Engine:
     def __init__(self, cfg: UNetConfig, device: int = 0):
         self.lib = _lib.load()
@@ -99,7 +117,12 @@ class Engine:
     def set_stream(self, stream_handle: Optional[int]):
         _lib.check(self.lib.sr3_set_stream(self.ctx, stream_handle or None))
 
-    PRECISIONS = {"f32": 0, "f16x3": 1, "f16f8": 2}
+    PRECISIONS = PRECISIONS
+
+    def conv_plan(self, B: int, H: int, W: int, Cin: int, Cout: int, ks: int = 3, stride: int = 1, up2: int = 0,
+                  precision: Optional[str] = None, stats: bool = False) -> dict:
+        """conv_plan() in this engine's precision (or the one named)."""
+        return conv_plan(B, H, W, Cin, Cout, ks, stride, up2, precision or getattr(self, "precision", "f32"), stats)
 
     def conv_f8_supported(self, B: int, H: int, W: int, Cout: int, Cin: int) -> bool:
         """Does the 'f16f8' mode run a 3x3 / stride-1 conv of this shape with fp8 correction products?"""

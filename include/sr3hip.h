@@ -93,6 +93,17 @@ int sr3_stream_wait_for_ctx(sr3_ctx *ctx, void *other_stream);
 int sr3_set_precision(sr3_ctx *ctx, int prec);
 /* 1 when mode 2 runs a 3x3 / stride-1 conv of this shape with fp8 correction products, else 0 (tests, tools) */
 int sr3_conv_f8_supported(int B, int H, int W, int Cout, int Cin);
+/* The dispatch plan of one conv shape (H x W input pixels, Cin a multiple of 32) as the engine runs it in `precision`
+ * (sr3_set_precision values), with every scratch buffer offered; with_stats: the conv also produces the fused GroupNorm
+ * statistics of its output (the UNet's convs do, sr3_op_conv2d does not). Host only: no GPU call. out12 =
+ * {kernel id, tile rows, tile columns, split kind (0 none | 1 conv + reduce kernel | 2 in place on the 64x64 tile |
+ * 3 in place on the x-halo tile), K-splits, phases (4: upsample conv), floats of split-K partials, 1 if tile counters are
+ * used, statistics slices per image (0: none for this shape), floats of Winograd workspace, 1 if the fragment-major
+ * Winograd weights are read, 1 if the conv takes the F8C operand format}; kernel_name (optional): the kernel's name,
+ * "wino_one_pass" | "wino_three_pass" | "halo_f8c" | "halo_128x128_seg32" | "halo_128x128_seg8" | "halo_128x64" |
+ * "generic_128x32" | "generic_128x64" | "generic_64x64" | "generic_128x128". (tests, tools) */
+int sr3_conv_plan(int B, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int precision, int with_stats,
+                  int64_t *out12, char *kernel_name, int name_cap);
 
 /* ---- weights: reference state_dict names and layouts ------------------------------------- */
 

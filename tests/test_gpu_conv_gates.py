@@ -1,13 +1,14 @@
 """Single 3x3 convs at the edges of the dispatch gates (sr3_op_conv2d runs a conv as the engine would run it for the
-shape): conv_wino_supported / wino_fused_shape in exact f32, conv_halo_splits / conv_f8_supported in the f16 modes.
-Every image of the batch against a float64 numpy conv.
+shape): the Winograd gates in exact f32, the x-halo split-K and F8C gates in the f16 modes. The library is asked which
+kernel it runs (Engine.conv_plan: the plan launch_conv itself switches on). Every image of the batch against a float64
+numpy conv.
 
 Data as in tests/test_gpu_ops.py: N(0,1) inputs, N(0,1) / sqrt(9 Cin) weights, N(0,1) bias; every other case adds the
 FeatureWiseAffine bias (chan_bias) and a residual. Bars: 2e-5 absolute in f32 and f16x3 (test_conv2d's bar; that test
 holds a K = 9216 Winograd conv to it), 2e-4 in f16f8 (tests/test_gpu_f16f8.py). Image B-1 is a copy of image 0: the two
 output rows must be bit-identical.
 
-Gate arithmetic (csrc/kernels_wino.hip, csrc/kernels_conv.hip):
+Gate arithmetic (csrc/kernels_conv.hip, conv_plan):
   three-pass Winograd: H, W even, H*W <= 1024, Cin >= 128, Cin % 32 == 0, Cout % 64 == 0, B*H/2*W/2 >= 1024 tiles
   one-pass Winograd:   H*W >= 4096, H even, W % 64 == 0, Cin >= 64, Cin % 32 == 0, Cout % 64 == 0,
                        B * H/2 * W/64 * Cout/64 >= 1024 blocks
@@ -66,7 +67,7 @@ def _run(eng, prec, x, w, b, cb, resid):
         eng.set_precision("f32")
 
 
-# (B, H, W, Cin, Cout), the form conv_wino_supported / wino_fused_shape give it in exact f32
+# (B, H, W, Cin, Cout), the form the Winograd gates give it in exact f32
 F32_CASES = [
     ((16, 16, 16, 128, 64), "three-pass"),      # exactly WINO_MIN_TILES tiles
     ((15, 16, 16, 128, 64), "direct"),          # 960 tiles: just below
@@ -90,8 +91,11 @@ F32_CASES = [
 ]
 
 
+WINO_KERNELS = {"one-pass": "wino_one_pass", "three-pass": "wino_three_pass"}
+
+
 def wino_form(B, H, W, Cin, Cout):
-    """The gates of csrc/kernels_wino.hip restated (conv_wino_supported, wino_fused_shape)."""
+    """The Winograd gates of csrc/kernels_conv.hip restated (wino_shape, wino_fused_shape)."""
     if H * W >= 4096 and H % 2 == 0 and W % 64 == 0 and Cin >= 64 and Cin % 32 == 0 and Cout % 64 == 0 \
             and B * (H // 2) * (W // 64) * (Cout // 64) >= 1024:
         return "one-pass"
@@ -105,6 +109,8 @@ def wino_form(B, H, W, Cin, Cout):
 def test_conv_f32_at_winograd_gates(eng, idx):
     case, form = F32_CASES[idx]
     assert wino_form(*case) == form
+    kernel = eng.conv_plan(*case, precision="f32")["kernel"]
+    assert kernel == WINO_KERNELS[form] if form != "direct" else kernel.startswith("generic_"), kernel
     x, w, b, cb, resid, want = _case_data(case, extras=idx % 2 == 1)
     got = _run(eng, "f32", x, w, b, cb, resid)
     B = case[0]
@@ -115,21 +121,26 @@ def test_conv_f32_at_winograd_gates(eng, idx):
     np.testing.assert_array_equal(got[0], got[B - 1])
 
 
-# (B, H, W, Cin, Cout), does conv_f8_supported take it; what the f16 modes run otherwise
+# (B, H, W, Cin, Cout), does conv_f8_supported take it, the kernel and split-K form f16x3 runs (f16f8: the F8C kernel
+# where conv_f8_supported, else the same)
 F16_CASES = [
-    ((64, 16, 32, 256, 512), True),       # non-square 16x32 level, 1024 tiles of 128x128
-    ((63, 32, 32, 256, 256), True),       # 504 M-tiles x 2: 1008 tiles, odd batch
-    ((128, 4, 32, 512, 512), True),       # H*W = 128 (one tile per image), exactly 512 tiles
-    ((64, 4, 32, 512, 512), False),       # 256 tiles of 128x128: the 128x64 x-halo tile
-    ((36, 8, 8, 544, 512), False),        # H*W = 64 < 128: in-place split-K of the x-halo tile, 17 K chunks, 72 tiles
+    ((64, 16, 32, 256, 512), True, "halo_128x128_seg32", "none"),   # non-square 16x32 level, 1024 tiles of 128x128
+    ((63, 32, 32, 256, 256), True, "halo_128x128_seg32", "none"),   # 504 M-tiles x 2: 1008 tiles, odd batch
+    ((128, 4, 32, 512, 512), True, "halo_128x128_seg32", "none"),   # H*W = 128 (one tile per image), exactly 512 tiles
+    ((64, 4, 32, 512, 512), False, "halo_128x64", "none"),          # 256 tiles of 128x128: the 128x64 x-halo tile
+    # H*W = 64 < 128: in-place split-K of the x-halo tile (rows of 8 pixels), 17 K chunks, 72 tiles
+    ((36, 8, 8, 544, 512), False, "halo_128x128_seg8", "inplace_halo"),
 ]
 
 
-@pytest.mark.parametrize("idx", range(len(F16_CASES)), ids=["x".join(map(str, c)) + ("-f8" if f else "-nof8") for c, f in F16_CASES])
+@pytest.mark.parametrize("idx", range(len(F16_CASES)), ids=["x".join(map(str, c)) + ("-f8" if f else "-nof8") for c, f, _, _ in F16_CASES])
 def test_conv_f16_at_halo_and_f8_gates(eng, idx):
-    case, f8 = F16_CASES[idx]
+    case, f8, kernel, split = F16_CASES[idx]
     B, H, W, Cin, Cout = case
     assert eng.conv_f8_supported(B, H, W, Cout, Cin) == f8
+    p3, p8 = eng.conv_plan(*case, precision="f16x3"), eng.conv_plan(*case, precision="f16f8")
+    assert (p3["kernel"], p3["split"], p3["f8"]) == (kernel, split, False), p3
+    assert (p8["kernel"], p8["split"], p8["f8"]) == (("halo_f8c", "none", True) if f8 else (kernel, split, False)), p8
     x, w, b, cb, resid, want = _case_data(case, extras=idx % 2 == 1)
     got3 = _run(eng, "f16x3", x, w, b, cb, resid)
     got8 = _run(eng, "f16f8", x, w, b, cb, resid)
