@@ -5,8 +5,8 @@ from .schedule import make_beta_schedule, schedule_buffers  # noqa: F401
 from ._lib import Sr3Error, LIB_PATH  # noqa: F401
 from .engine import Engine  # noqa: F401
 from .unet import UNet  # noqa: F401
-from .diffusion import GaussianDiffusion  # noqa: F401
+from .diffusion import GaussianDiffusion, DictTensor, draw_levels  # noqa: F401
 from .networks import define_G  # noqa: F401
 
 __all__ = ["UNetConfig", "param_specs", "count_params", "flops_per_image", "make_beta_schedule",
-           "schedule_buffers", "Sr3Error", "Engine", "UNet", "GaussianDiffusion", "define_G"]
+           "schedule_buffers", "Sr3Error", "Engine", "UNet", "GaussianDiffusion", "DictTensor", "draw_levels", "define_G"]

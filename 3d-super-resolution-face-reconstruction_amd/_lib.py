@@ -102,6 +102,8 @@ PROTOTYPES = {
     "sr3_postprocess_u8": (_I, [_P, _F, _I, _I, _I, _I, _I, _P, _P, _F, _F]),
     "sr3_postprocess_tensor_blob": (_I, [_P, _F, _I, _I, _I, _I, _F]),
     "sr3_metrics_psnr_ssim": (_I, [_P, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "sr3_denoise_loss": (_I, [_P, _F, _F, _I, _I, _F, _F, _F, _I, _U64, _U64, _I, _I, _I, _I, _P, _F, _F]),
+    "sr3_op_q_sample": (_I, [_P, _F, _I, _I, _F, _F, _F, _I, _U64, _U64, _I, _I, _I, _I, _F]),
     "sr3_dev_malloc": (_I, [_P, _U64, C.POINTER(_P)]),
     "sr3_dev_free": (_I, [_P, _P]),
     "sr3_memcpy_h2d": (_I, [_P, _P, _P, _U64]),

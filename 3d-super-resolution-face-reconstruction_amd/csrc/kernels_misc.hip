@@ -1459,39 +1459,7 @@ __global__ void nhwc_to_nchw_kernel(const TDesc src, int coff, int C, float *out
     out[i] = src.p[src.pix(n, y, x) * src.C + coff + c];
 }
 
-// Philox4x32-10 (Salmon et al. 2011). CPU twin: oracle/philox.py.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// Standard normal number `elem` of draw `draw` for image `image`: counter = (elem/4, draw,
-// image_lo, image_hi), key = seed; Box-Muller on the two 24-bit uniform pairs.
-__device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t image, uint32_t draw,
-                                               uint32_t elem) {
-    uint32_t r[4];
-    philox4x32_10(elem >> 2, draw, (uint32_t)image, (uint32_t)(image >> 32), (uint32_t)seed,
-                  (uint32_t)(seed >> 32), r);
-    const int pair = (elem >> 1) & 1;
-    const float u1 = ((float)(r[2 * pair] >> 8) + 0.5f) * 5.9604644775390625e-08f;      // 2^-24
-    const float u2 = ((float)(r[2 * pair + 1] >> 8) + 0.5f) * 5.9604644775390625e-08f;
-    const float rad = sqrtf(-2.0f * logf(u1));
-    const float th = 6.283185307179586f * u2;
-    return (elem & 1) ? rad * sinf(th) : rad * cosf(th);
-}
-
+// (philox4x32_10 / philox_normal: sr3_internal.h, shared with kernels_loss.hip)
 __global__ void philox_normal_kernel(uint64_t seed, uint64_t image, uint32_t draw, int n, float *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = philox_normal(seed, image, draw, (uint32_t)i);

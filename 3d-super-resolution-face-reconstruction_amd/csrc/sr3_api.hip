@@ -148,7 +148,7 @@ struct sr3_ctx {
     int fallback_calls = 0;             // calls finished by the f32 fallback since sr3_create
     float *ckpt = nullptr;              // sr3_sample: NCHW copy of the sampler state at the last clean checkpoint
     size_t ckpt_floats = 0;
-    double *metrics_ws = nullptr;       // sr3_metrics_psnr_ssim: per-block SSIM partial sums (grows on demand)
+    double *metrics_ws = nullptr;       // sr3_metrics_psnr_ssim / sr3_denoise_loss: per-block fp64 partial sums (grows on demand)
     size_t metrics_ws_n = 0;
     unsigned *tile_cnt = nullptr;       // ConvParams::tile_cnt: arrival counters of the in-place split-K convs (zero between launches)
     // Set (for the rest of the context's life) when a bounded inter-block wait of the in-place split-K on x-halo tiles
@@ -1611,6 +1611,111 @@ int sr3_unet_forward(sr3_ctx *c, const float *x_dev, const float *noise_level_de
     return warn_fallback(c, "sr3_unet_forward", "the forward pass");
 }
 
+// ---- the denoising loss (diffusion.py:284-313, evaluation only) ---------------------------------
+namespace {
+struct LossCall {
+    const float *hr, *cond, *level, *s;
+    NoiseRef nz;
+    int N, row_offset, B, H, W, loss_type;
+    double *per_image;
+    float *x_noisy_out, *eps_out;
+};
+}
+
+// fp64 partial sums of the reductions (metrics, loss): one buffer, grown on demand
+static int ensure_partials(sr3_ctx *c, size_t need) {
+    if (c->metrics_ws_n >= need) return 0;
+    if (c->metrics_ws) HIP_OK(hipFree(c->metrics_ws));   // (hipFree waits for the kernels still reading it)
+    c->metrics_ws = nullptr; c->metrics_ws_n = 0;
+    HIP_OK(hipMalloc(&c->metrics_ws, need * sizeof(double)));
+    c->metrics_ws_n = need;
+    return 0;
+}
+
+// one evaluation in the context's current arithmetic: state kernel, embedding, UNet body, loss kernels
+static int denoise_loss_once(sr3_ctx *c, const LossCall &k) {
+    if (range_reset(c)) return -1;
+    const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
+    c->pbegin(F_MISC);
+    launch_q_sample_state(k.hr, k.cond, k.N, k.row_offset, k.level, k.s, k.nz, k.B, C, nc, c->x0, c->x0p, c->d_ovf,
+                          k.x_noisy_out, c->stream);
+    c->pend();
+    run_embed(c, k.level, 1, k.B);
+    run_unet_body(c, k.B, k.H, k.W);
+    c->pbegin(F_MISC);
+    launch_denoise_loss(c->eps, k.nz, k.N, k.row_offset, k.B, C, k.loss_type, c->metrics_ws, k.per_image, k.eps_out, c->stream);
+    c->pend();
+    HIP_OK(hipGetLastError());
+    if (const char *e = conv_take_error()) return fail("sr3_denoise_loss: %s", e);
+    return 0;
+}
+
+int sr3_denoise_loss(sr3_ctx *c, const float *hr_dev, const float *cond_dev, int N, int row_offset, const float *level_dev,
+                     const float *s_dev, const float *noise_dev, int noise_per_source, uint64_t seed, uint64_t image_offset,
+                     int B, int H, int W, int loss_type, double *per_image_dev, float *x_noisy_out, float *eps_out) {
+    if (check_ready(c)) return -1;
+    if (!hr_dev || !level_dev || !s_dev || !per_image_dev) return fail("sr3_denoise_loss: null pointer");
+    if (loss_type != 0 && loss_type != 1) return fail("sr3_denoise_loss: loss_type %d is neither 0 (l1) nor 1 (l2)", loss_type);
+    if (N < 1 || row_offset < 0) return fail("sr3_denoise_loss: bad rows (N=%d row_offset=%d)", N, row_offset);
+    const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
+    if (cond_dev && nc <= 0) return fail("sr3_denoise_loss: conditioning given but in_channel == out_channel");
+    if (!cond_dev && nc != 0) return fail("sr3_denoise_loss: the unconditional loss needs in_channel == out_channel");
+    if (c->cfg.in_channel > 8)
+        return fail("sr3_denoise_loss: in_channel = %d, the state kernel builds at most 8 input channels", c->cfg.in_channel);
+    if (ensure_workspace(c, B, H, W)) return -1;
+    if (ensure_partials(c, (size_t)B * loss_blocks(H, W))) return -1;
+    c->sampling = false;
+    LossCall k;
+    k.hr = hr_dev; k.cond = cond_dev; k.level = level_dev; k.s = s_dev;
+    k.nz.noise = noise_dev; k.nz.seed = seed; k.nz.image_offset = image_offset; k.nz.per_source = noise_per_source != 0;
+    k.N = N; k.row_offset = row_offset; k.B = B; k.H = H; k.W = W; k.loss_type = loss_type;
+    k.per_image = per_image_dev; k.x_noisy_out = x_noisy_out; k.eps_out = eps_out;
+    // the policy of sr3_unet_forward: the caller owns every input, so a replay is the same evaluation again
+    if (denoise_loss_once(c, k)) return -1;
+    if (!c->prec) return 0;
+    int r = range_read(c);
+    bool replayed = false;
+    if (r == 2) {
+        replayed = true;
+        if (denoise_loss_once(c, k)) return -1;
+        r = range_read(c);
+        if (r == 2) return fail("internal: inter-block wait flag raised with the in-place split-K disabled");
+    }
+    if (r < 0) return -1;
+    if (r == 0) return replayed ? warn_replay(c, "sr3_denoise_loss", "the loss evaluation") : 0;
+    if (c->strict_range) return range_fail(c, "sr3_denoise_loss");
+    if (c->f8corr) {
+        c->f8corr = false;
+        const int rc8 = denoise_loss_once(c, k);
+        const int r8 = rc8 ? -1 : range_read(c);
+        c->f8corr = true;
+        if (r8 < 0) return -1;
+        if (r8 == 0) return warn_fallback(c, "sr3_denoise_loss", "the loss evaluation", true);
+    }
+    c->prec = 0;
+    const int rc = denoise_loss_once(c, k);
+    c->prec = 1;
+    if (rc) return -1;
+    return warn_fallback(c, "sr3_denoise_loss", "the loss evaluation");
+}
+
+int sr3_op_q_sample(sr3_ctx *c, const float *hr_dev, int N, int row_offset, const float *level_dev, const float *s_dev,
+                    const float *noise_dev, int noise_per_source, uint64_t seed, uint64_t image_offset, int B, int C, int H,
+                    int W, float *x_noisy_out) {
+    if (!c || !hr_dev || !level_dev || !s_dev || !x_noisy_out) return fail("sr3_op_q_sample: null argument");
+    if (N < 1 || row_offset < 0 || B < 1 || C < 1 || C > 4 || H < 1 || W < 1)
+        return fail("sr3_op_q_sample: bad size (N=%d row_offset=%d B=%d C=%d H=%d W=%d)", N, row_offset, B, C, H, W);
+    HIP_OK(hipSetDevice(c->device));
+    NoiseRef nz;
+    nz.noise = noise_dev; nz.seed = seed; nz.image_offset = image_offset; nz.per_source = noise_per_source != 0;
+    TDesc geom;                 // geometry only (p == nullptr): no state is written
+    geom.C = C; geom.H = H; geom.W = W;
+    launch_q_sample_state(hr_dev, nullptr, N, row_offset, level_dev, s_dev, nz, B, C, 0, geom, nullptr, nullptr, x_noisy_out,
+                          c->stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 static int set_step_tables(sr3_ctx *c, int T, const float *noise_level, const float *a, const float *b,
                            const float *c1, const float *c2, const float *c3, const std::vector<float> &sigma,
                            bool uses_hist) {
@@ -2188,13 +2293,7 @@ int sr3_metrics_psnr_ssim(sr3_ctx *c, const float *sr, const float *hr, int B, i
     const long long blocks = metrics_blocks(B, H, W);
     if (blocks > 0x7fffffffll) return fail("sr3_metrics_psnr_ssim: B=%d at %dx%d needs %lld blocks, more than one launch takes", B, H, W, blocks);
     HIP_OK(hipSetDevice(c->device));
-    const size_t need = (size_t)blocks;                        // one fp64 partial per block
-    if (c->metrics_ws_n < need) {
-        if (c->metrics_ws) HIP_OK(hipFree(c->metrics_ws));   // (hipFree waits for the kernels still reading it)
-        c->metrics_ws = nullptr; c->metrics_ws_n = 0;
-        HIP_OK(hipMalloc(&c->metrics_ws, need * sizeof(double)));
-        c->metrics_ws_n = need;
-    }
+    if (ensure_partials(c, (size_t)blocks)) return -1;         // one fp64 partial per block
     HIP_OK(hipMemsetAsync(ssd, 0, (size_t)B * sizeof(int64_t), c->stream));   // the blocks ADD their shares
     launch_metrics(sr, hr, B, N, row_offset, H, W, gauss11, c->metrics_ws, ssd, ssim, c->stream);
     HIP_OK(hipGetLastError());

@@ -327,6 +327,56 @@ void launch_init_state(const TDesc &state, int xoff, int C, const float *noise, 
 void launch_philox_normal(uint64_t seed, uint64_t image, uint32_t draw, int n, float *out,
                           hipStream_t s);
 
+// ---- Philox normal stream (device functions; the kernels that draw from it: kernels_misc.hip, kernels_loss.hip) ----
+// Philox4x32-10 (Salmon et al. 2011). CPU twin: oracle/philox.py.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// Standard normal number `elem` of draw `draw` for image `image`: counter = (elem/4, draw,
+// image_lo, image_hi), key = seed; Box-Muller on the two 24-bit uniform pairs.
+__device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t image, uint32_t draw,
+                                               uint32_t elem) {
+    uint32_t r[4];
+    philox4x32_10(elem >> 2, draw, (uint32_t)image, (uint32_t)(image >> 32), (uint32_t)seed,
+                  (uint32_t)(seed >> 32), r);
+    const int pair = (elem >> 1) & 1;
+    const float u1 = ((float)(r[2 * pair] >> 8) + 0.5f) * 5.9604644775390625e-08f;      // 2^-24
+    const float u2 = ((float)(r[2 * pair + 1] >> 8) + 0.5f) * 5.9604644775390625e-08f;
+    const float rad = sqrtf(-2.0f * logf(u1));
+    const float th = 6.283185307179586f * u2;
+    return (elem & 1) ? rad * sinf(th) : rad * cosf(th);
+}
+
+// The four standard normals of one counter: elements 4*quad .. 4*quad+3 of the same stream, each bit-equal to
+// philox_normal(seed, image, draw, 4*quad + j) (one Philox evaluation and two Box-Muller pairs instead of four of each).
+__device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t image, uint32_t draw, uint32_t quad, float out[4]) {
+    uint32_t r[4];
+    philox4x32_10(quad, draw, (uint32_t)image, (uint32_t)(image >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+    for (int pair = 0; pair < 2; ++pair) {
+        const float u1 = ((float)(r[2 * pair] >> 8) + 0.5f) * 5.9604644775390625e-08f;
+        const float u2 = ((float)(r[2 * pair + 1] >> 8) + 0.5f) * 5.9604644775390625e-08f;
+        const float rad = sqrtf(-2.0f * logf(u1));
+        const float th = 6.283185307179586f * u2;
+        out[2 * pair] = rad * cosf(th);
+        out[2 * pair + 1] = rad * sinf(th);
+    }
+}
+
 // ---- edge convolutions (kernels_edge.hip) ----------------------------------------------------------
 // final_conv = GroupNorm affine + Swish + Conv3x3(C -> Cout <= 4) in one fp32 VALU kernel: x is the raw
 // fp32 zero-bordered tensor, scale / shift [B][C] the folded GroupNorm (gn_finalize), wq the weights as
@@ -388,5 +438,31 @@ void launch_tensor_blob(const float *in_nchw, int B, int H, int W, int Hb, int W
 long long metrics_blocks(int B, int H, int W);           // blocks of the tile kernel (the caller bounds them by INT_MAX)
 void launch_metrics(const float *sr, const float *hr, int B, int N, int row_offset, int H, int W, const double *taps,
                     double *ws, int64_t *ssd, double *ssim, hipStream_t s);
+
+// ---- denoising loss: q_sample into the UNet's input state, summed L1 / L2 of noise against eps (kernels_loss.hip) ----
+// Batch row b noises source image n = (row_offset + b) % N of hr / cond (NCHW [N][C][H][W] / [N][nc][H][W], cond null:
+// unconditional) with coefficients a[b], s[b]. Its noise is row j of the NCHW slab `noise`, or (noise == nullptr) the
+// Philox stream (seed, image_offset + j, draw 0) in the sampler's element order c*H*W + y*W + x, where j = b, or j = n
+// with per_source (one noise image per SOURCE image, whatever the row's level).
+struct NoiseRef {
+    const float *noise = nullptr;
+    uint64_t seed = 0, image_offset = 0;
+    int per_source = 0;
+};
+// x_noisy = a*x + s*n (product, product, sum: each rounded to fp32) -> channels [nc, nc+C) of the interior of `state`
+// (cond in [0, nc)), nc + C <= 8; packed (optional): the split-f16 state of conv_in_kernel with pack_state_kernel's range
+// flag; x_noisy_out (optional): NCHW [B][C][H][W]. The border of `state` is not touched; its channels behind nc + C, up to
+// the next multiple of four, are stored as the zeros the workspace holds there. The packed twin always takes 8 channels,
+// those behind nc + C as register zeros: it equals pack_state_kernel's (which reads them from `state`) only because the
+// pad channels of `state` stay zero for the life of the workspace — whoever starts writing them must pack from memory.
+void launch_q_sample_state(const float *hr, const float *cond, int N, int row_offset, const float *a, const float *s,
+                           const NoiseRef &nz, int B, int C, int nc, const TDesc &state, float *packed, int *ovf,
+                           float *x_noisy_out, hipStream_t st);
+// per_image[b] = sum over the image of |n - eps| (loss_type 0) or (n - eps)^2 (1): difference and square in fp32,
+// accumulation in fp64, one partial per block added in block order (no floating-point atomics: bitwise reproducible).
+// eps: unpadded NHWC [B][H][W][C]; eps_out (optional): eps as NCHW. ws: loss_blocks(H, W) * B doubles.
+int loss_blocks(int H, int W);
+void launch_denoise_loss(const TDesc &eps, const NoiseRef &nz, int N, int row_offset, int B, int C, int loss_type, double *ws,
+                         double *per_image, float *eps_out, hipStream_t st);
 
 } // namespace sr3

@@ -1,7 +1,8 @@
 """`GaussianDiffusion`: the reference's sampler API (model/sr/sr3_modules/diffusion.py:66-225)
 over libsr3hip. The whole p_sample_loop — T UNet evaluations and the DDPM update — runs inside
 the HIP library; this class only holds the schedule buffers (for state_dict parity) and moves
-pointers. Training members (p_losses, forward, *_learn) are out of scope and raise.
+pointers. The denoising loss (q_sample, p_losses, forward: diffusion.py:275-318) is EVALUATED on the device
+(sr3_denoise_loss); backward passes and the *_learn members stay out of scope.
 """
 from __future__ import annotations
 
@@ -14,6 +15,49 @@ from torch import nn
 from . import samplers as _samplers
 from . import schedule as _schedule
 from ._lib import Sr3Error
+
+
+class DictTensor:
+    """The reference's wrapper of a batch dict (diffusion.py:323-344), which callers pass through DataParallel."""
+
+    def __init__(self, data):
+        self.data = data
+
+    def to(self, device):
+        self.data = {k: v.to(device) if isinstance(v, torch.Tensor) else v for k, v in self.data.items()}
+        return self
+
+    def __getitem__(self, key):
+        return self.data[key]
+
+    def __setitem__(self, key, value):
+        self.data[key] = value
+
+    def keys(self):
+        return self.data.keys()
+
+    def items(self):
+        return self.data.items()
+
+    def __repr__(self):
+        return str(self.data)
+
+
+def draw_levels(sqrt_alphas_cumprod_prev, T: int, b: int):
+    """The host draws of p_losses (diffusion.py:287-294), the reference's own two np.random calls in its order: one
+    timestep t in [1, T], then b continuous levels, uniform between sqrt_alphas_cumprod_prev[t-1] and [t]. Returns
+    (t, float32 [b]); the cast is torch.FloatTensor's. The same np.random.seed gives the reference's levels."""
+    t = np.random.randint(1, T + 1)
+    lv = np.random.uniform(sqrt_alphas_cumprod_prev[t - 1], sqrt_alphas_cumprod_prev[t], size=b)
+    return int(t), np.asarray(lv, dtype=np.float32)
+
+
+def noise_coefficient(levels) -> np.ndarray:
+    """s = sqrt(1 - a^2) of q_sample (diffusion.py:281) for fp32 levels a: the reference's expression
+    `(1 - a**2).sqrt()` with every operation a correctly rounded fp32 one (numpy: product, difference, square root), which
+    is what the reference gets on the GPU. torch's vectorised CPU sqrt is not used: it is 1 ulp off on some hosts."""
+    a = np.ascontiguousarray(np.asarray(levels, dtype=np.float32).reshape(-1))
+    return np.sqrt(np.float32(1) - a * a)
 
 
 class GaussianDiffusion(nn.Module):
@@ -32,9 +76,12 @@ class GaussianDiffusion(nn.Module):
 
     # ---- reference surface that is configuration only -----------------------------------------
     def set_loss(self, device=None):
-        # reference diffusion.py:85-91 builds an L1/L2 loss for training; nothing to do for sampling
+        """diffusion.py:85-91: selects the summed L1 ('l1') or L2 ('l2') loss that p_losses evaluates. Like the
+        reference's, a model on which set_loss was never called has no loss function (there p_losses fails on the missing
+        attribute; here it raises NotImplementedError, as it did before the loss existed)."""
         if self.loss_type not in ("l1", "l2"):
             raise NotImplementedError()
+        self.loss_func = self.loss_type
 
     def set_new_noise_schedule(self, schedule_opt, device=None):
         """diffusion.py:93-142. `device` may be 0, a list of ids (the reference's form), a
@@ -308,8 +355,143 @@ class GaussianDiffusion(nn.Module):
             x_recon.clamp_(-1.0, 1.0)
         return self.q_posterior(x_recon, x, t)
 
-    # ---- training members: out of scope ---------------------------------------------------------
-    def forward(self, x, *args, **kwargs):
-        raise NotImplementedError("training loss (p_losses) is outside the SR3 sampling hot path")
+    # ---- the denoising loss, evaluated on the device ---------------------------
+    def _loss_rows(self, hr, sr, levels, loss_type, noise=None, noise_per_source=False, seed=0, image_offset=0,
+                   row_offset=0, max_chunk=None, want=()):
+        """sr3_denoise_loss over `len(levels)` rows: row b noises hr[(row_offset + b) % N] at levels[b]. levels: fp32
+        CPU tensor. noise: [rows,C,H,W] (or [N,C,H,W] with noise_per_source) or None (Philox keyed by image_offset + row,
+        or + source image). Rows above the per-call limit run as equal chunks (chunk_plan; the last one padded, its
+        extra rows discarded). Returns {"per_image": fp64 [rows]} plus "x_noisy" / "eps" [rows,C,H,W] if named in want."""
+        eng = self._engine()
+        dev = hr.device
+        N, C, H, W = hr.shape
+        R = int(levels.numel())
+        levels = levels.to("cpu", torch.float32).reshape(-1).contiguous()
+        s = torch.from_numpy(noise_coefficient(levels.numpy()))
+        out = {"per_image": torch.empty(R, dtype=torch.float64, device=dev)}
+        for k in want:
+            out[k] = torch.empty((R, C, H, W), dtype=torch.float32, device=dev)
+        limit = eng.max_batch(H, W)
+        if max_chunk is not None:
+            limit = max(1, min(limit, int(max_chunk)))
+        n_chunks, chunk = self.chunk_plan(R, limit)
 
-    p_losses = q_sample = super_resolution_learn = p_sample_loop_learn = forward
+        def padded(t, a, b):
+            part = t[a:b]
+            if b - a < chunk:
+                part = torch.cat([part] + [part[-1:]] * (chunk - (b - a)), dim=0)
+            return part.contiguous()
+
+        for k in range(n_chunks):
+            a, b = k * chunk, min(R, (k + 1) * chunk)
+            whole = b - a == chunk
+            lv, sv = padded(levels, a, b).to(dev), padded(s, a, b).to(dev)
+            nz = None
+            if noise is not None:
+                nz = noise if noise_per_source else padded(noise, a, b)
+            bufs = {name: (t[a:b] if whole else torch.empty((chunk,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev))
+                    for name, t in out.items()}
+            self.denoise_fn.ready()
+            eng.denoise_loss(hr.data_ptr(), sr.data_ptr() if sr is not None else None, N, row_offset + a,
+                             lv.data_ptr(), sv.data_ptr(), chunk, H, W, bufs["per_image"].data_ptr(), loss_type,
+                             nz.data_ptr() if nz is not None else None, noise_per_source, seed,
+                             image_offset if noise_per_source else image_offset + a,
+                             bufs["x_noisy"].data_ptr() if "x_noisy" in bufs else None,
+                             bufs["eps"].data_ptr() if "eps" in bufs else None)
+            self.denoise_fn.finish()
+            if not whole:
+                for name, t in out.items():
+                    t[a:b] = bufs[name][: b - a]
+        return out
+
+    def _loss_inputs(self, x_in):
+        if getattr(self, "loss_func", None) is None:
+            raise NotImplementedError("no loss function: call set_loss(device) first (reference diffusion.py:85-91)")
+        if next(self.denoise_fn.parameters()).device.type != "cuda":
+            raise NotImplementedError("the denoising loss is evaluated by the HIP library only: p_losses has no CPU "
+                                      "implementation (move the model to the GPU)")
+        dev = next(self.denoise_fn.parameters()).device
+        if x_in["HR"].device != dev:        # the library reads raw device addresses: a host tensor must never reach it
+            raise RuntimeError(f"x_in['HR'] is on {x_in['HR'].device}: it must be on the model's device ({dev})")
+        hr = x_in["HR"].to(torch.float32).contiguous()
+        sr = x_in["SR"].to(device=hr.device, dtype=torch.float32).contiguous() if self.conditional else None
+        if hr.dim() != 4 or hr.shape[1] != self.channels or (sr is not None and sr.shape[0] != hr.shape[0]):
+            raise RuntimeError(f"expected HR [B, {self.channels}, H, W] and SR with the same B, got {tuple(hr.shape)}"
+                               + (f" and {tuple(sr.shape)}" if sr is not None else ""))
+        return hr, sr
+
+    @torch.no_grad()
+    def q_sample(self, x_start, continuous_sqrt_alpha_cumprod, noise=None):
+        """diffusion.py:275-282 on the device, bit-equal to the reference expression on the same fp32 inputs (with
+        sqrt(1 - a^2) formed as noise_coefficient does).
+        continuous_sqrt_alpha_cumprod: one level per image (any shape with B entries). noise=None draws one
+        torch.randn_like, as the reference does."""
+        dev = next(self.denoise_fn.parameters()).device
+        if dev.type != "cuda" or x_start.device != dev:     # (raw device addresses cross into the library)
+            raise RuntimeError(f"x_start is on {x_start.device} and the model on {dev}: both must be on the same GPU")
+        x = x_start.to(torch.float32).contiguous()
+        B, C, H, W = x.shape
+        lv = continuous_sqrt_alpha_cumprod.detach().to("cpu", torch.float32).reshape(-1)
+        if lv.numel() != B:
+            raise RuntimeError(f"need one level per image ({B}), got {lv.numel()}")
+        nz = (torch.randn_like(x) if noise is None else noise.to(device=x.device, dtype=torch.float32)).contiguous()
+        sv = torch.from_numpy(noise_coefficient(lv.numpy())).to(x.device)
+        lv = lv.contiguous().to(x.device)
+        out = torch.empty_like(x)
+        eng = self.denoise_fn.engine()
+        self.denoise_fn.ready()
+        eng.q_sample(x.data_ptr(), B, 0, lv.data_ptr(), sv.data_ptr(), B, C, H, W, out.data_ptr(), nz.data_ptr())
+        self.denoise_fn.finish()
+        return out
+
+    @torch.no_grad()
+    def p_losses(self, x_in, noise=None, sr_out=False, seed: Optional[int] = None, image_offset: int = 0,
+                 max_chunk: Optional[int] = None):
+        """The reference's denoising loss (diffusion.py:284-313), EVALUATED on the device: no gradient is formed and
+        the result carries no grad_fn (backward passes are out of scope).
+
+        x_in: {'HR': [B,C,H,W], 'SR': [B,C,H,W]}. The timestep and the B noise levels are drawn on the host with the
+        reference's own np.random calls (draw_levels), so np.random.seed reproduces the reference's levels. noise: the
+        [B,C,H,W] tensor the reference would draw; None draws it on the device from Philox (the sampler's generator,
+        not torch.randn) under `seed` (None: a fresh one from torch's generator, as sample_batch draws one), keyed by
+        image_offset + row. Dropout is the identity: in train() mode with dropout > 0 this differs from
+        the reference's stochastic forward, and one UserWarning per object says so.
+
+        Returns the SUM over the batch — L1Loss / MSELoss(reduction='sum'), callers divide by b*c*h*w themselves — as a
+        0-dim fp32 tensor on the input's device; the fp64 per-image sums stay on self.last_loss_per_image. Batches above
+        the library's per-call limit run as chunks (max_chunk lowers it). sr_out=True returns
+        super_resolution(x_in['SR']) — the reference's ret_img[-1] — without the forward the reference runs and
+        discards first."""
+        if sr_out:
+            return self.super_resolution(x_in["SR"])
+        hr, sr = self._loss_inputs(x_in)
+        if self.training and float(self.denoise_fn.cfg.dropout) > 0 and not getattr(self, "_warned_dropout", False):
+            import warnings
+            warnings.warn("p_losses in train() mode: the library evaluates the UNet with dropout as the identity "
+                          f"(dropout={self.denoise_fn.cfg.dropout} is not sampled); the loss is the eval() loss",
+                          UserWarning, stacklevel=2)
+            self._warned_dropout = True
+        B = hr.shape[0]
+        _, levels = draw_levels(self.sqrt_alphas_cumprod_prev, self.num_timesteps, B)
+        if noise is not None:
+            noise = noise.to(device=hr.device, dtype=torch.float32).contiguous()
+            if tuple(noise.shape) != tuple(hr.shape):
+                raise RuntimeError(f"noise must be {tuple(hr.shape)}, got {tuple(noise.shape)}")
+        elif seed is None:
+            seed = self._draw_seed()
+        res = self._loss_rows(hr, sr, torch.from_numpy(levels), self.loss_func, noise=noise, seed=seed or 0,
+                              image_offset=image_offset, max_chunk=max_chunk)
+        self.last_loss_per_image = res["per_image"]
+        return res["per_image"].sum().to(torch.float32)
+
+    def forward(self, x, sr_out=False, *args, **kwargs):
+        """diffusion.py:315-318: unwraps a DictTensor and evaluates p_losses."""
+        if isinstance(x, DictTensor):
+            x = x.data
+        return self.p_losses(x, sr_out=sr_out, *args, **kwargs)
+
+    # ---- training members: out of scope (DESIGN.md §7) --------------------------------------------
+    def super_resolution_learn(self, *args, **kwargs):
+        raise NotImplementedError("differentiable sampling (*_learn) needs a backward pass: out of scope")
+
+    p_sample_loop_learn = super_resolution_learn

@@ -189,6 +189,27 @@ class Engine:
     def unet_forward(self, x_ptr: int, nl_ptr: int, B: int, H: int, W: int, out_ptr: int) -> None:
         _lib.check(self.lib.sr3_unet_forward(self.ctx, x_ptr, nl_ptr, B, H, W, out_ptr))
 
+    # ---- denoising loss (GaussianDiffusion.p_losses, evaluation only) -----------
+    LOSS_TYPES = {"l1": 0, "l2": 1}
+
+    def denoise_loss(self, hr_ptr: int, cond_ptr: Optional[int], N: int, row_offset: int, level_ptr: int, s_ptr: int,
+                     B: int, H: int, W: int, per_image_ptr: int, loss_type: str = "l1", noise_ptr: Optional[int] = None,
+                     noise_per_source: bool = False, seed: int = 0, image_offset: int = 0,
+                     x_noisy_ptr: Optional[int] = None, eps_ptr: Optional[int] = None) -> None:
+        """Row b noises hr[(row_offset + b) % N] at level[b] (s[b] = float32 sqrt(1 - level^2)), runs the UNet on
+        cat(cond, x_noisy) and leaves the summed |noise - eps| ('l1') or (noise - eps)^2 ('l2') of the row as fp64 at
+        per_image_ptr [B] (sr3_denoise_loss; stream-ordered). noise_ptr None: device Philox (seed, image_offset + b)."""
+        _lib.check(self.lib.sr3_denoise_loss(self.ctx, hr_ptr, cond_ptr or None, N, row_offset, level_ptr, s_ptr,
+                                             noise_ptr or None, 1 if noise_per_source else 0, seed, image_offset, B, H, W,
+                                             self.LOSS_TYPES[loss_type], per_image_ptr, x_noisy_ptr or None, eps_ptr or None))
+
+    def q_sample(self, hr_ptr: int, N: int, row_offset: int, level_ptr: int, s_ptr: int, B: int, C: int, H: int, W: int,
+                 out_ptr: int, noise_ptr: Optional[int] = None, noise_per_source: bool = False, seed: int = 0,
+                 image_offset: int = 0) -> None:
+        """x_noisy = level * hr + s * noise of the same rows into out_ptr [B,C,H,W] (sr3_op_q_sample; stream-ordered)."""
+        _lib.check(self.lib.sr3_op_q_sample(self.ctx, hr_ptr, N, row_offset, level_ptr, s_ptr, noise_ptr or None,
+                                            1 if noise_per_source else 0, seed, image_offset, B, C, H, W, out_ptr))
+
     # ---- sampler --------------------------------------------------------------------------
     def set_schedule(self, bufs: Dict[str, np.ndarray]) -> None:
         nl = _host_f32(bufs["noise_level"])

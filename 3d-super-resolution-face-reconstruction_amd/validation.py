@@ -11,6 +11,9 @@ not against cv2 itself (parity unpinned for the cv2 call, formula-level faithful
 
 The host functions are the default and the yardstick. `validate_batch(metrics="device")` / `device_scores` compute the
 same scores on the device (sr3_metrics_psnr_ssim, csrc/kernels_metrics.hip) so that only two numbers per image leave it.
+
+`loss_by_level` is the checkpoint diagnostic: the denoising loss of a set of images over noise levels, one batch of
+images x levels through sr3_denoise_loss.
 """
 from __future__ import annotations
 
@@ -178,3 +181,42 @@ def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 
     return {"psnr": ps, "ssim": ss, "images": out if keep_images else None,
             "mean_psnr": float(ps[finite].mean()) if finite.any() else math.inf,
             "mean_ssim": float(ss.mean())}
+
+
+def loss_by_level(netG, hr: "torch.Tensor", sr: "torch.Tensor", levels, noise: "Optional[torch.Tensor]" = None,
+                  seed: Optional[int] = None, max_chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """The denoising loss (GaussianDiffusion.p_losses, evaluation only) of N images at K noise levels: the curve that
+    shows whether a checkpoint was ingested correctly and whether an arithmetic mode changes the network's prediction.
+
+    hr, sr: [N,3,H,W] on the GPU (sr is ignored by an unconditional model). levels: a sequence of K values of
+    sqrt(alpha_cumprod) in [0, 1], or an int K = that many entries of sqrt_alphas_cumprod_prev[1:], evenly spaced by index
+    (first and last included). netG.set_loss() selects l1 / l2. The K x N evaluations run as ONE batch (level k of image i
+    is row k*N + i; chunked above the per-call limit, max_chunk lowers it); hr and sr are indexed with % N, never
+    replicated. Every image meets the SAME noise at every level, so the curve of an image moves with the level alone:
+    noise [N,3,H,W] is indexed by the source image, and with noise=None the Philox stream is keyed by the source image
+    (seed, i) — not by the row — under `seed` (None: a fresh one).
+
+    Returns {"levels": fp32 [K], "loss": [K] mean loss per element (the sum over the N images / (N*3*H*W)),
+    "per_image": fp64 [K,N] summed loss of every image}."""
+    import torch
+
+    hr, sr = netG._loss_inputs({"HR": hr, "SR": sr})
+    N, C, H, W = hr.shape
+    if isinstance(levels, (int, np.integer)):
+        prev = np.asarray(netG.sqrt_alphas_cumprod_prev, dtype=np.float64)[1:]
+        if not 1 <= int(levels) <= prev.size:
+            raise ValueError(f"levels={levels}: need 1 <= K <= T = {prev.size}")
+        levels = prev[np.round(np.linspace(0, prev.size - 1, int(levels))).astype(np.int64)]
+    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.float32).reshape(-1))
+    if lv.size < 1 or not (np.isfinite(lv).all() and (lv >= 0).all() and (lv <= 1).all()):
+        raise ValueError("levels must be values of sqrt(alpha_cumprod) in [0, 1]")
+    if noise is not None:
+        noise = noise.to(device=hr.device, dtype=torch.float32).contiguous()
+        if tuple(noise.shape) != tuple(hr.shape):
+            raise RuntimeError(f"noise must be {tuple(hr.shape)} (one image per source image), got {tuple(noise.shape)}")
+    elif seed is None:
+        seed = netG._draw_seed()
+    res = netG._loss_rows(hr, sr, torch.from_numpy(np.repeat(lv, N)), netG.loss_func, noise=noise, noise_per_source=True,
+                          seed=seed or 0, max_chunk=max_chunk)
+    per = res["per_image"].cpu().numpy().reshape(lv.size, N)
+    return {"levels": lv, "loss": per.sum(axis=1) / float(N * C * H * W), "per_image": per}

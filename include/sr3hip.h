@@ -327,6 +327,38 @@ int sr3_metrics_psnr_ssim(sr3_ctx *ctx, const float *sr_nchw_dev, const float *h
                           int row_offset, int H, int W, const double *gauss11_host, int64_t *ssd_dev,
                           double *ssim_dev);
 
+/* ---- the denoising loss: GaussianDiffusion.p_losses without a backward pass ---------------- */
+
+/* replaces what the reference wraps around one UNet forward when it evaluates its objective
+ * (model/sr/sr3_modules/diffusion.py:284-313; evaluation only: no gradient is formed), per batch row b on source
+ * image n = (row_offset + b) % N:
+ *   x_noisy = level[b] * HR[n] + s[b] * noise          q_sample, diffusion.py:275-282 (product, product, sum, each
+ *             rounded to fp32 like torch; s[b] = float32(sqrt(1 - level[b]^2)) comes from the host, which forms it with
+ *             the reference's own fp32 expression, so x_noisy is bit-equal to q_sample)
+ *   eps     = denoise_fn(cat([SR[n], x_noisy], 1), level)   diffusion.py:302-306, unet.py:235-265 (cond_dev NULL:
+ *             denoise_fn(x_noisy, level), the unconditional branch; needs in_channel == out_channel)
+ *   per_image[b] = sum |noise - eps| (loss_type 0, L1Loss(reduction='sum')) or sum (noise - eps)^2 (1, MSELoss)
+ *             diffusion.py:85-91,312 — difference and square in fp32, accumulated in fp64 in a fixed order (no
+ *             floating-point atomics: two calls return bitwise equal sums). The reference's scalar is their sum.
+ * hr_dev [N, out_channel, H, W], cond_dev [N, in_channel - out_channel, H, W] (never replicated: level k of image i is
+ * row k*N + i of an images-x-levels batch), level_dev / s_dev [B] fp32, per_image_dev [B] fp64: device pointers.
+ * noise_dev: an NCHW slab, or NULL for device Philox with the sampler's keying (seed, image_offset + j, draw 0, element
+ * c*H*W + y*W + x: the stream of the sampler's initial image). noise_per_source == 0: j = b, slab [B, out_channel, H, W];
+ * != 0: j = n, slab [N, out_channel, H, W] — one noise image per SOURCE image whatever the row's level. No copy of drawn
+ * noise is stored: the loss pass regenerates it.
+ * x_noisy_out / eps_out (optional, NCHW [B, out_channel, H, W]): the noised images and the UNet's prediction.
+ * Range policy as sr3_unet_forward (the caller owns every input, so the call is simply evaluated again): SR3_OK_REPLAYED,
+ * f16f8 -> f16x3 -> f32 with SR3_OK_F32_FALLBACK, an error under the strict policy. B <= sr3_max_batch. */
+int sr3_denoise_loss(sr3_ctx *ctx, const float *hr_dev, const float *cond_dev, int N, int row_offset,
+                     const float *level_dev, const float *s_dev, const float *noise_dev, int noise_per_source,
+                     uint64_t seed, uint64_t image_offset, int B, int H, int W, int loss_type, double *per_image_dev,
+                     float *x_noisy_out, float *eps_out);
+/* q_sample alone (diffusion.py:275-282) into a caller buffer: x_noisy_out [B, C, H, W] from hr_dev [N, C, H, W]
+ * (1 <= C <= 4), any H, W; rows, coefficients and noise as above. Needs no weights. Asynchronous. */
+int sr3_op_q_sample(sr3_ctx *ctx, const float *hr_dev, int N, int row_offset, const float *level_dev,
+                    const float *s_dev, const float *noise_dev, int noise_per_source, uint64_t seed,
+                    uint64_t image_offset, int B, int C, int H, int W, float *x_noisy_out);
+
 /* ---- device memory helpers (so hosts without torch can drive the library) ---------------- */
 int sr3_dev_malloc(sr3_ctx *ctx, uint64_t bytes, void **out_dev);
 int sr3_dev_free(sr3_ctx *ctx, void *dev);
