@@ -1122,6 +1122,11 @@ __global__ __launch_bounds__(NWAVES * 64) void attention_split_kernel(const floa
 
 bool attention_split_supported(int N, int C) { return N <= 512 && C <= 512 && (C % 32) == 0; }
 size_t attention_vt_floats(int B, int N, int C) { return (size_t)B * C * ((N + 31) & ~31); }
+AttnCore attention_core(bool split_f16, long N, int C) {
+    if (split_f16 && N <= ATTN_TILE_MAX_TOKENS && attention_split_supported((int)N, C)) return ATTN_SPLIT;
+    if (N <= ATTN_TILE_MAX_TOKENS) return ATTN_TILE;
+    return attention_stream_supported(C) ? ATTN_STREAM : ATTN_UNSUPPORTED;
+}
 
 // qkv_split: [B][N][3C] in the split operand format; vt: scratch of attention_vt_floats(B, N, C) floats;
 // out (fp32) and / or out_split ([B][N][C] split) may be null

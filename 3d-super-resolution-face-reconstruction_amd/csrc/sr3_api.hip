@@ -103,6 +103,10 @@ struct Module {
     int ih = 0, iw = 0;             // input resolution
 };
 
+// exact f32 MFMA | split-f16, three f16 products (f16x3) | split-f16 with two fp8 correction products (f16f8): the values
+// of sr3_set_precision, and the order of the range policy's ladder (step_down)
+enum Arith { A_F32 = 0, A_F16X3 = 1, A_F16F8 = 2 };
+
 enum Family { F_CONV = 0, F_GN = 1, F_ATTN = 2, F_EMBED = 3, F_MISC = 4 };
 
 struct ProfRec { int fam; hipEvent_t a, b; double flops; std::string tag; };
@@ -131,10 +135,16 @@ struct sr3_ctx {
     int in_pad = 0;     // in_channel padded to 32
     int c_max = 0;      // widest GroupNorm input
     uint64_t weight_bytes = 0;
-    int prec = 0;       // 0 exact f32 MFMA, 1 split-f16 (f16x3) for the 3x3 / activated-input convs
-    // "f16f8" (sr3_set_precision(ctx, 2)): prec 1 with the two correction products of eligible convs on the fp8 matrix
-    // path (ConvParams::f8, conv_f8_supported). The f32 fallback of the range check leaves this flag alone.
-    bool f8corr = false;
+    // The arithmetic of the 3x3 / activated-input convs (sr3_set_precision). Assigned by sr3_set_precision, step_down
+    // and ModeScope only; everything else asks the four questions below.
+    Arith mode = A_F32;
+    bool split() const { return mode != A_F32; }        // split-f16 operands (f16x3 or f16f8)
+    // "f16f8": the two correction products of eligible convs run on the fp8 matrix path (ConvParams::f8, conv_f8_supported)
+    bool f8() const { return mode == A_F16F8; }
+    int graph_slot() const { return (int)mode; }        // which of the three captured step graphs
+    // split format of an activated conv input (launch_gn_apply's `split`): 0 fp32, 1 split-f16, 2 F8C when the consumer
+    // conv takes the fp8 operands (f8_conv() said so)
+    int act_format(bool f8_operand) const { return split() ? (f8_operand ? 2 : 1) : 0; }
     bool f8_dirty = true;      // dev_f8 copies are stale (weights loaded / re-split since they were made)
     bool fused_dirty = true;   // fused bias / common weight scales need (re)building
     bool all_fused = false;        // every GroupNorm of the current workspace gets its statistics from a conv epilogue
@@ -495,8 +505,8 @@ int max_batch(const sr3_ctx *c, int H, int W) {
         else if (m.kind == M_UP) { h *= 2; w *= 2; }
         uint64_t ch = m.kind == M_RES ? (uint64_t)m.rb.cout : (uint64_t)m.conv.cout;
         if (m.kind == M_RES) ch = std::max<uint64_t>(ch, std::max<uint64_t>(m.rb.attn ? 3ull * m.rb.cout : 0ull, (uint64_t)m.rb.cin));
-        // attention over more than 1024 tokens runs on the streaming core, which has a channel bound (ensure_workspace)
-        if (m.kind == M_RES && m.rb.attn && (long)h * w > 1024 && !attention_stream_supported(m.rb.cout)) return -1;
+        // (no core for this token count and width: ensure_workspace says which; both arithmetics share the bound)
+        if (m.kind == M_RES && m.rb.attn && attention_core(false, (long)h * w, m.rb.cout) == ATTN_UNSUPPORTED) return -1;
         per = std::max(per, (uint64_t)(h + 2) * (w + 2) * ch);
     }
     const uint64_t by_bytes = ((1ull << 32) - 1) / (per * sizeof(float));
@@ -565,10 +575,12 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
                 const uint64_t nu = (uint64_t)B * h * w * oc;
                 if (3 * nu > max_qkv) max_qkv = 3 * nu;
                 if (nu > max_ao) max_ao = nu;
-                if (attention_split_supported(h * w, oc)) max_vt = std::max<uint64_t>(max_vt, attention_vt_floats(B, h * w, oc));
-                // over 1024 tokens the streaming core runs (no N x N tile): only its channel bound remains
-                if ((long)h * w > 1024 && !attention_stream_supported(oc))
-                    return fail("attention over %d tokens at %d channels: the streaming core takes at most 512 channels", h * w, oc);
+                for (const bool split : {false, true}) {       // (either arithmetic runs on this workspace)
+                    const AttnCore core = attention_core(split, (long)h * w, oc);
+                    if (core == ATTN_UNSUPPORTED)
+                        return fail("attention over %d tokens at %d channels: the streaming core takes at most 512 channels", h * w, oc);
+                    if (core == ATTN_SPLIT) max_vt = std::max<uint64_t>(max_vt, attention_vt_floats(B, h * w, oc));
+                }
             }
         }
         m.oc = oc; m.oh = h; m.ow = w; m.ih = ih; m.iw = iw;
@@ -678,7 +690,7 @@ const TDesc kNone{};
 // f8: the consumer conv takes the F8C operand format (f8_conv() said so)
 void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int B, int mode, const TDesc &act,
                 const StatsRef &sa, const StatsRef &sb, const TDesc &raw = TDesc(), int in_split = 0, bool f8 = false) {
-    const int fmt = c->prec ? (f8 ? 2 : 1) : 0;
+    const int fmt = c->act_format(f8);
     c->pbegin(F_GN);
     const float *gamma = c->params[g.gamma].dev, *beta = c->params[g.beta].dev;
     // bytes the pass moves (read + write, 4 B per element each way): above ~200 MB the one-item-per-thread
@@ -736,7 +748,7 @@ void run_conv(sr3_ctx *c, const ConvCall &k) {
     ConvParams p;
     p.in0 = a; p.B = B; p.Hout = out.H; p.Wout = out.W;
     p.ks = cv.ks; p.stride = k.stride; p.up2 = k.up2;
-    p.prec = k.activated ? c->prec : 0;
+    p.prec = (k.activated && c->split()) ? 1 : 0;
     p.w = p.prec ? c->params[cv.w].dev_split : c->params[cv.w].dev;
     if (!p.prec && cv.cin_pad == a.C) {
         p.w_wino = c->params[cv.w].dev_wino; p.w_wino_f = c->params[cv.w].dev_wino_f; p.wino_ws = c->wino_ws;
@@ -746,7 +758,7 @@ void run_conv(sr3_ctx *c, const ConvCall &k) {
     p.bias = k.bias_override ? k.bias_override : (cv.b >= 0 ? c->params[cv.b].dev : nullptr);
     p.chan_bias = k.chan_bias; p.chan_bias_stride = c->cb_stride;
     p.resid = k.resid; p.out = out;
-    if (c->prec) p.out_split = k.out_split;
+    if (c->split()) p.out_split = k.out_split;
     p.out_f32 = (k.out_f32 || !p.out_split.p) ? 1 : 0;
     p.resid_split = k.resid_split ? 1 : 0;
     if (k.stats.p) { p.stats = const_cast<double *>(k.stats.p); p.stats_slices = k.stats.slices; }
@@ -774,7 +786,7 @@ void run_conv(sr3_ctx *c, const ConvCall &k) {
 
 // "f16f8" mode: does this ResnetBlock conv (3x3, stride 1, activated input of cin channels) take the F8C operand format?
 bool f8_conv(const sr3_ctx *c, const ConvRef &cv, int B, int H, int W) {
-    return c->prec == 1 && c->f8corr && cv.ks == 3 && c->params[cv.w].dev_f8 != nullptr && conv_f8_supported(B, H, W, cv.cout, cv.cin);
+    return c->f8() && cv.ks == 3 && c->params[cv.w].dev_f8 != nullptr && conv_f8_supported(B, H, W, cv.cout, cv.cin);
 }
 
 TDesc unpadded(float *p, int C, int H, int W) {
@@ -815,7 +827,7 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     if (rb.has_res) {
         k2.in2 = direct ? xr : m.raw1; k2.in2b = direct && skip.p ? skr : kNone;
         k2.fused1x1 = &rb.res; k2.bias_override = rb.fused_bias;
-    } else if (c->prec && rb.ident_w && xr.p) {
+    } else if (c->split() && rb.ident_w && xr.p) {
         k2.in2 = xr; k2.ident_w = rb.ident_w;
     } else {
         k2.resid = x_so ? xr : x; k2.resid_split = x_so;
@@ -823,7 +835,8 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     run_conv(c, k2);
     if (rb.attn) {
         run_gn_act(c, m.rb_out, kNone, rb.agn, B, 1, m.act2, m.st_rb, StatsRef());
-        const bool split_attn = c->prec && attention_split_supported(h * w, rb.cout);
+        const AttnCore core = attention_core(c->split(), (long)h * w, rb.cout);
+        const bool split_attn = core == ATTN_SPLIT;
         ConvCall kq, ko;
         kq.in = m.act2; kq.conv = &rb.qkv; kq.B = B; kq.activated = true;
         kq.out = unpadded(c->qkvb, 3 * rb.cout, h, w);
@@ -841,9 +854,8 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
         } else {
             run_conv(c, kq);
             c->pbegin(F_ATTN);
-            // over 1024 tokens the 32 x N score tile no longer fits in LDS: the online-softmax core (every mode)
-            const double fl = h * w > 1024 ? launch_attention_stream(c->qkvb, B, h * w, rb.cout, c->aob, c->stream)
-                                           : launch_attention(c->qkvb, B, h * w, rb.cout, c->aob, c->stream);
+            const double fl = core == ATTN_STREAM ? launch_attention_stream(c->qkvb, B, h * w, rb.cout, c->aob, c->stream)
+                                                  : launch_attention(c->qkvb, B, h * w, rb.cout, c->aob, c->stream);
             c->pend(fl);
         }
         run_conv(c, ko);
@@ -859,7 +871,7 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
     // split-only mode: a module output that has a twin is written ONLY as the twin (4 instead of 8
     // bytes per element); GroupNorm apply and residual adds read hi + lo. Needs every GroupNorm to get
     // its statistics from a conv epilogue (the fallback statistics kernel reads fp32 tensors).
-    const bool so_mode = c->prec && c->all_fused;
+    const bool so_mode = c->split() && c->all_fused;
     const int n_pre = c->n_downs + c->n_mid;
     for (int i = 0; i < (int)c->mods.size(); ++i) {
         Module &m = c->mods[i];
@@ -870,7 +882,7 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
         case M_CONV_IN:
             m.st_out.slices = m.slices_default;
             k.stats = m.st_out;
-            if (c->prec && c->x0p) {
+            if (c->split() && c->x0p) {
                 // downs.0 on the packed split-f16 state (kernels_edge.hip): 3 K-steps of 24 live k-values instead
                 // of 9 K-steps of 32 mostly-zero channels, no split copy of the state tensor
                 if (m.st_out.p) m.st_out.slices = H * W / 256;       // one statistics slice per 256-pixel block
@@ -883,7 +895,7 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
                     snprintf(tag, sizeof tag, "conv_in k3 %dx%d cin%d cout%d packed-state mfma16", H, W, m.conv.cin, m.conv.cout);
                     c->pend(2.0 * (double)B * H * W * m.conv.cout * 9.0 * m.conv.cin, tag);
                 }
-            } else if (c->prec) {   // the 6 (of 32 padded) input channels in split-f16 form: the first conv then runs
+            } else if (c->split()) {   // the 6 (of 32 padded) input channels in split-f16 form: the first conv then runs
                                 // on the fast path too instead of 9 mostly-zero K-steps of f32 MFMA
                 c->pbegin(F_GN);
                 launch_gn_apply_rows(cur, kNone, B, nullptr, nullptr, 0, 1, c->x0s, c->stream, TDesc(), 0, c->d_ovf);
@@ -898,9 +910,9 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
         case M_DOWN:
         case M_UP: {
             k.stride = m.kind == M_DOWN ? 2 : 1; k.up2 = m.kind == M_UP ? 1 : 0;
-            if (c->prec && cur_s.p) {           // the producer left a split-f16 twin: read it directly
+            if (c->split() && cur_s.p) {        // the producer left a split-f16 twin: read it directly
                 k.in = cur_s; k.activated = true; k.out_f32 = !(so_mode && m.out_s.p);
-            } else if (c->prec) {               // no twin: re-store the raw input in split-f16 form first
+            } else if (c->split()) {            // no twin: re-store the raw input in split-f16 form first
                 c->pbegin(F_GN);
                 launch_gn_apply(cur, kNone, B, nullptr, nullptr, 0, 1, m.up_in, c->stream, TDesc(), 0, c->d_ovf);
                 c->pend();
@@ -915,11 +927,11 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
             if (is_up_path) {
                 Module &sk = c->mods[feats.back()];
                 feats.pop_back();
-                if (c->prec) run_res(c, m, cur, scur, sk.out, sk.st_out, B, cur_s, sk.out_s, cur_so, sk.so_now,
+                if (c->split()) run_res(c, m, cur, scur, sk.out, sk.st_out, B, cur_s, sk.out_s, cur_so, sk.so_now,
                                      so_mode && m.out_s.p && !m.rb.attn);
                 else run_res(c, m, cur, scur, sk.out, sk.st_out, B, cur, sk.out);
             } else {
-                if (c->prec) run_res(c, m, cur, scur, kNone, StatsRef(), B, cur_s, kNone, cur_so, false,
+                if (c->split()) run_res(c, m, cur, scur, kNone, StatsRef(), B, cur_s, kNone, cur_so, false,
                                      so_mode && m.out_s.p && !m.rb.attn);
                 else run_res(c, m, cur, scur, kNone, StatsRef(), B, cur, kNone);
             }
@@ -945,7 +957,7 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
                                     c->gpart, c->gscale, c->gshift, c->stream);
         c->pend();
         c->pbegin(F_CONV);
-        const bool mfma = c->prec && c->final_wm;
+        const bool mfma = c->split() && c->final_wm;
         if (mfma)
             launch_final_conv_mfma(cur, B, c->gscale, c->gshift, c->final_wm, c->final_unscale, c->params[c->final_conv.b].dev,
                                    c->eps, c->stream, c->d_ovf);
@@ -965,13 +977,19 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
     run_conv(c, k);
 }
 
-void run_embed(sr3_ctx *c, const float *nl, int stride, int B) {
+// the noise-level MLP and the concatenated FeatureWiseAffine linears of this context, writing temb / chan_bias
+EmbedParams embed_params(const sr3_ctx *c, const float *nl, int stride, float *temb, float *chan_bias) {
     EmbedParams e;
     e.noise_level = nl; e.nl_stride = stride; e.dim = c->cfg.inner_channel;
     e.w1 = c->params[c->mlp_w1].dev; e.b1 = c->params[c->mlp_b1].dev;
     e.w2 = c->params[c->mlp_w2].dev; e.b2 = c->params[c->mlp_b2].dev;
     e.nfw = c->nfw; e.nfb = c->nfb; e.total = c->nf_total;
-    e.temb = c->temb; e.chan_bias = c->cbias;
+    e.temb = temb; e.chan_bias = chan_bias;
+    return e;
+}
+
+void run_embed(sr3_ctx *c, const float *nl, int stride, int B) {
+    const EmbedParams e = embed_params(c, nl, stride, c->temb, c->cbias);
     // sampler steps: the noise level is the same for every image (diffusion.py:166-167 repeats one scalar), so the
     // embedding and the FeatureWiseAffine biases are computed ONCE and every conv reads row 0 (stride 0)
     const bool uniform = stride == 0;
@@ -1034,7 +1052,7 @@ int prepare_fused(sr3_ctx *c) {
 
 // "f16f8" mode: F8C copies of the 3x3 conv weights (made on the device from the split-f16 copies; same byte size)
 int prepare_f8(sr3_ctx *c) {
-    if (!c->f8corr || !c->f8_dirty) return 0;
+    if (!c->f8() || !c->f8_dirty) return 0;
     for (auto &p : c->params) {
         if (p.kind != P_CONV || p.ks != 3 || p.up_phase || (p.cin_pad % 32) != 0 || !p.dev_split) continue;
         if (!p.dev_f8) {
@@ -1111,7 +1129,7 @@ int warn_fallback(sr3_ctx *c, const char *what, const char *redo, bool to_f16x3 
 }
 
 int range_fail(sr3_ctx *c, const char *what) {
-    if (c->f8corr)
+    if (c->f8())
         return fail("%s: an activation exceeded the operand range of the f16f8 arithmetic — the fp8 range (|v| > %g) in a "
                     "conv on the fp8 correction path, or the fp16 range (|v| > 65504) of the split-f16 format elsewhere; "
                     "the result is invalid — run this model in f16x3 (sr3_set_precision(ctx, 1): no fp8 operands) or, if "
@@ -1129,6 +1147,55 @@ int range_check(sr3_ctx *c, const char *what) {
                     "up: this result is invalid; the context now uses the conv path without inter-block waits — repeat the "
                     "call (sr3_sample / sr3_unet_forward replay by themselves)", what);
     return range_fail(c, what);
+}
+
+// ---- the range policy of the split-f16 modes -----------------------------------------------------------------------
+// One rung down the ladder f16f8 -> f16x3 (the fp8 operands have the narrower range) -> exact f32 (to_f32: straight to
+// the bottom); returns the rung landed on.
+Arith step_down(sr3_ctx *c, bool to_f32 = false) {
+    c->mode = (to_f32 || c->mode == A_F16X3) ? A_F32 : A_F16X3;
+    return c->mode;
+}
+
+// puts the context's arithmetic back on every exit path of a call that may step down
+struct ModeScope {
+    sr3_ctx *c;
+    const Arith was;
+    explicit ModeScope(sr3_ctx *ctx) : c(ctx), was(ctx->mode) {}
+    ModeScope(const ModeScope &) = delete;
+    ~ModeScope() { c->mode = was; }
+};
+
+// The range policy for an entry point that OWNS ITS INPUTS, so that repeating the work is the same evaluation again.
+// `once` enqueues one evaluation in the context's current arithmetic (0, or -1 with the error set); `what` names the
+// entry point and `redo` what was recomputed in the warnings. Clean flag: done. A split-K wait that gave up
+// (range_read == 2): again on the non-waiting path, same arithmetic. Out of range: the call fails under the strict
+// policy (and where may_step_down is false: a single op keeps the arithmetic it was asked for), else it is evaluated one
+// arithmetic down (step_down) until a rung is clean or f32, which has no range limit, is reached.
+template <class Once>
+int guarded_eval(sr3_ctx *c, const char *what, const char *redo, bool may_step_down, Once &&once) {
+    if (range_reset(c) || once()) return -1;
+    if (!c->split()) return 0;
+    int r = range_read(c);
+    bool replayed = false;
+    if (r == 2) {
+        replayed = true;
+        if (range_reset(c) || once()) return -1;
+        r = range_read(c);
+        if (r == 2) return fail("internal: inter-block wait flag raised with the in-place split-K disabled");
+    }
+    if (r < 0) return -1;
+    if (r == 0) return replayed ? warn_replay(c, what, redo) : 0;
+    if (c->strict_range || !may_step_down) return range_fail(c, what);
+    ModeScope scope(c);
+    while (step_down(c) != A_F32) {
+        if (range_reset(c) || once()) return -1;
+        const int r16 = range_read(c);
+        if (r16 < 0) return -1;
+        if (r16 == 0) return warn_fallback(c, what, redo, true);
+    }
+    if (range_reset(c) || once()) return -1;
+    return warn_fallback(c, what, redo);
 }
 
 int check_ready(sr3_ctx *c) {
@@ -1161,7 +1228,7 @@ void enqueue_step(sr3_ctx *c) {
     u.xoff = c->cfg.in_channel - c->cfg.out_channel;
     u.eps = c->eps;
     u.args = c->d_step;
-    u.ovf = c->prec ? c->d_ovf : nullptr;       // (the packed copy is only read in split-f16 mode)
+    u.ovf = c->split() ? c->d_ovf : nullptr;    // (the packed copy is only read in split-f16 mode)
     u.hist = c->xhist;                          // constant per workspace: the captured graph stays valid
     c->pbegin(F_MISC);
     launch_ddpm_update(u, B, c->stream);
@@ -1172,7 +1239,7 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     if (!c->sampling) return fail("sr3_sample_step before sr3_sample_begin");
     if (t < 0 || t >= c->T) return fail("step t=%d outside schedule of %d steps", t, c->T);
     // (the arithmetic mode may have been switched between steps: the F8C weight copies are made on demand)
-    if (c->f8corr && c->f8_dirty && prepare_f8(c)) return -1;
+    if (prepare_f8(c)) return -1;
     if (!c->h_ring) {
         HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&c->h_ring), sizeof(StepArgs) * sr3_ctx::kRing, hipHostMallocDefault));
         HIP_OK(hipMalloc(&c->d_step, sizeof(StepArgs)));
@@ -1192,7 +1259,7 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     sa.seed = c->seed; sa.image_offset = c->image_offset;
     HIP_OK(hipMemcpyAsync(c->d_step, &sa, sizeof(StepArgs), hipMemcpyHostToDevice, c->stream));
 
-    const int g = c->prec ? (c->f8corr ? 2 : 1) : 0;
+    const int g = c->graph_slot();
     if (c->prof || c->no_graph) {
         enqueue_step(c);
         return 0;
@@ -1253,8 +1320,8 @@ struct ScratchConv {
     // channels) is allocated and left for the caller to fill.
     int setup(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout, int ks, int stride, int up2, const float *weight_host) {
         const int Cin = C0 + C1;
-        f8 = c->prec == 1 && c->f8corr && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin);
-        plan = conv_plan_offered(B, Hin, Win, Cin, Cout, ks, stride, up2, c->prec, f8, false);
+        f8 = c->f8() && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin);
+        plan = conv_plan_offered(B, Hin, Win, Cin, Cout, ks, stride, up2, c->split() ? 1 : 0, f8, false);
         const bool wino = plan.kernel == CK_WINO_ONE_PASS || plan.kernel == CK_WINO_THREE_PASS;
         const size_t n_w = (size_t)(up2 ? 16 : ks * ks) * Cout * Cin;     // up2: 4 phases x 2x2 taps
         const size_t n_wino = (size_t)16 * Cout * Cin;
@@ -1276,7 +1343,7 @@ struct ScratchConv {
                 }
                 if (wino_w.upload(wv.data(), n_wino)) return -1;
             }
-            if (c->prec) {
+            if (c->split()) {
                 tmp.resize(n_w);
                 p.w_unscale = split_conv_weight(packed.data(), n_w / Cin, Cin, tmp.data());
                 packed.swap(tmp);
@@ -1306,7 +1373,7 @@ struct ScratchConv {
         p.in0 = a; p.B = B;
         p.Hout = (Hv + 2 * pad - ks) / stride + 1; p.Wout = (Wv + 2 * pad - ks) / stride + 1;
         p.ks = ks; p.stride = stride; p.up2 = up2;
-        p.prec = c->prec; p.f8 = f8 ? 1 : 0;
+        p.prec = c->split() ? 1 : 0; p.f8 = f8 ? 1 : 0;
         p.w = w.p;
         (plan.needs_wino_frag ? p.w_wino_f : p.w_wino) = wino_w.p;
         p.wino_ws = wino_ws.p;
@@ -1430,8 +1497,7 @@ int sr3_set_precision(sr3_ctx *c, int prec) {
     if (!c) return fail("null context");
     if (prec < 0 || prec > 2)
         return fail("precision %d unknown (0 = f32 exact, 1 = split-f16, 2 = split-f16 with fp8 correction products)", prec);
-    c->prec = prec ? 1 : 0;
-    c->f8corr = prec == 2;
+    c->mode = (Arith)prec;
     return 0;
 }
 
@@ -1558,9 +1624,9 @@ int sr3_weights_missing(sr3_ctx *c) {
 
 int sr3_chan_bias_total(sr3_ctx *c) { return c ? c->nf_total : fail("null context"); }
 
+// one evaluation in the context's current arithmetic (the callable of guarded_eval)
 static int unet_forward_once(sr3_ctx *c, const float *x_dev, const float *noise_level_dev, int B, int H, int W,
                              float *out_dev) {
-    if (range_reset(c)) return -1;
     c->pbegin(F_MISC);
     launch_nchw_to_nhwc(x_dev, B, c->cfg.in_channel, c->x0, 0, c->stream);
     if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
@@ -1581,34 +1647,8 @@ int sr3_unet_forward(sr3_ctx *c, const float *x_dev, const float *noise_level_de
     if (!x_dev || !noise_level_dev || !out_dev) return fail("sr3_unet_forward: null pointer");
     if (ensure_workspace(c, B, H, W)) return -1;
     c->sampling = false;
-    if (unet_forward_once(c, x_dev, noise_level_dev, B, H, W, out_dev)) return -1;
-    if (!c->prec) return 0;
-    int r = range_read(c);
-    bool replayed = false;
-    if (r == 2) {       // an in-place split-K wait gave up: evaluate again on the non-waiting path (same arithmetic)
-        replayed = true;
-        if (unet_forward_once(c, x_dev, noise_level_dev, B, H, W, out_dev)) return -1;
-        r = range_read(c);
-        if (r == 2) return fail("internal: inter-block wait flag raised with the in-place split-K disabled");
-    }
-    if (r < 0) return -1;
-    if (r == 0) return replayed ? warn_replay(c, "sr3_unet_forward", "the forward pass") : 0;
-    if (c->strict_range) return range_fail(c, "sr3_unet_forward");
-    // out of range: the caller still owns x and noise_level, so the forward is simply evaluated again — f16f8 first
-    // without the fp8 products (their operand range is the narrower one), then in f32
-    if (c->f8corr) {
-        c->f8corr = false;
-        const int rc8 = unet_forward_once(c, x_dev, noise_level_dev, B, H, W, out_dev);
-        const int r8 = rc8 ? -1 : range_read(c);
-        c->f8corr = true;
-        if (r8 < 0) return -1;
-        if (r8 == 0) return warn_fallback(c, "sr3_unet_forward", "the forward pass", true);
-    }
-    c->prec = 0;
-    const int rc = unet_forward_once(c, x_dev, noise_level_dev, B, H, W, out_dev);
-    c->prec = 1;
-    if (rc) return -1;
-    return warn_fallback(c, "sr3_unet_forward", "the forward pass");
+    return guarded_eval(c, "sr3_unet_forward", "the forward pass", true,
+                        [&] { return unet_forward_once(c, x_dev, noise_level_dev, B, H, W, out_dev); });
 }
 
 // ---- the denoising loss (diffusion.py:284-313, evaluation only) ---------------------------------
@@ -1634,7 +1674,6 @@ static int ensure_partials(sr3_ctx *c, size_t need) {
 
 // one evaluation in the context's current arithmetic: state kernel, embedding, UNet body, loss kernels
 static int denoise_loss_once(sr3_ctx *c, const LossCall &k) {
-    if (range_reset(c)) return -1;
     const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
     c->pbegin(F_MISC);
     launch_q_sample_state(k.hr, k.cond, k.N, k.row_offset, k.level, k.s, k.nz, k.B, C, nc, c->x0, c->x0p, c->d_ovf,
@@ -1670,33 +1709,7 @@ int sr3_denoise_loss(sr3_ctx *c, const float *hr_dev, const float *cond_dev, int
     k.nz.noise = noise_dev; k.nz.seed = seed; k.nz.image_offset = image_offset; k.nz.per_source = noise_per_source != 0;
     k.N = N; k.row_offset = row_offset; k.B = B; k.H = H; k.W = W; k.loss_type = loss_type;
     k.per_image = per_image_dev; k.x_noisy_out = x_noisy_out; k.eps_out = eps_out;
-    // the policy of sr3_unet_forward: the caller owns every input, so a replay is the same evaluation again
-    if (denoise_loss_once(c, k)) return -1;
-    if (!c->prec) return 0;
-    int r = range_read(c);
-    bool replayed = false;
-    if (r == 2) {
-        replayed = true;
-        if (denoise_loss_once(c, k)) return -1;
-        r = range_read(c);
-        if (r == 2) return fail("internal: inter-block wait flag raised with the in-place split-K disabled");
-    }
-    if (r < 0) return -1;
-    if (r == 0) return replayed ? warn_replay(c, "sr3_denoise_loss", "the loss evaluation") : 0;
-    if (c->strict_range) return range_fail(c, "sr3_denoise_loss");
-    if (c->f8corr) {
-        c->f8corr = false;
-        const int rc8 = denoise_loss_once(c, k);
-        const int r8 = rc8 ? -1 : range_read(c);
-        c->f8corr = true;
-        if (r8 < 0) return -1;
-        if (r8 == 0) return warn_fallback(c, "sr3_denoise_loss", "the loss evaluation", true);
-    }
-    c->prec = 0;
-    const int rc = denoise_loss_once(c, k);
-    c->prec = 1;
-    if (rc) return -1;
-    return warn_fallback(c, "sr3_denoise_loss", "the loss evaluation");
+    return guarded_eval(c, "sr3_denoise_loss", "the loss evaluation", true, [&] { return denoise_loss_once(c, k); });
 }
 
 int sr3_op_q_sample(sr3_ctx *c, const float *hr_dev, int N, int row_offset, const float *level_dev, const float *s_dev,
@@ -1805,16 +1818,22 @@ int sr3_sample_step(sr3_ctx *c, int t, const float *noise_slab_dev) {
     return 0;
 }
 
-int sr3_sample_end(sr3_ctx *c, float *out_dev) {
-    if (!c || !out_dev) return fail("sr3_sample_end: null argument");
-    if (!c->sampling) return fail("sr3_sample_end before sr3_sample_begin");
+// the sampler state (channels after the conditioning) as NCHW
+static int sample_copy_out(sr3_ctx *c, float *out_dev) {
     const int C = c->cfg.out_channel;
     c->pbegin(F_MISC);
     launch_nhwc_to_nchw(c->x0, c->cfg.in_channel - C, c->wB, C, out_dev, c->stream);
     c->pend();
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int sr3_sample_end(sr3_ctx *c, float *out_dev) {
+    if (!c || !out_dev) return fail("sr3_sample_end: null argument");
+    if (!c->sampling) return fail("sr3_sample_end before sr3_sample_begin");
+    if (sample_copy_out(c, out_dev)) return -1;
     // split-f16 mode: synchronises and fails if an activation left the fp16 range during the steps
-    return c->prec ? range_check(c, "sr3_sample_end") : 0;
+    return c->split() ? range_check(c, "sr3_sample_end") : 0;
 }
 
 int sr3_range_check(sr3_ctx *c) {
@@ -1823,123 +1842,98 @@ int sr3_range_check(sr3_ctx *c) {
     return range_check(c, "sr3_range_check");
 }
 
+namespace {
+// sr3_sample's checkpoint (c->ckpt): the sampler state as NCHW, the x0 history of a multistep sampler (its update also
+// reads the previous step's x0) and hist_valid, as they were BEFORE step t, when `frames` frames had been written.
+// save / restore: 0, or -1 with the error set
+struct Checkpoint {
+    sr3_ctx *c;
+    size_t slab;            // floats of the state (and of the history)
+    int t = 0, frames = 0;
+    bool hist_valid = false;
+
+    Checkpoint(sr3_ctx *ctx, size_t slab_floats) : c(ctx), slab(slab_floats) {}
+    int reserve() {
+        const size_t need = c->uses_hist ? 2 * slab : slab;
+        if (c->ckpt_floats >= need) return 0;
+        if (c->ckpt) HIP_OK(hipFree(c->ckpt));
+        c->ckpt = nullptr; c->ckpt_floats = 0;
+        HIP_OK(hipMalloc(&c->ckpt, need * sizeof(float)));
+        c->ckpt_floats = need;
+        return 0;
+    }
+    int save(int before_step, int frames_written) {
+        const int C = c->cfg.out_channel;
+        launch_nhwc_to_nchw(c->x0, c->cfg.in_channel - C, c->wB, C, c->ckpt, c->stream);
+        if (c->uses_hist) {
+            const hipError_t e = hipMemcpyAsync(c->ckpt + slab, c->xhist, slab * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+            if (e != hipSuccess) return fail("sr3_sample: checkpoint of the x0 history: %s", hipGetErrorString(e));
+        }
+        t = before_step; frames = frames_written; hist_valid = c->hist_valid;
+        return 0;
+    }
+    int restore() {
+        const int C = c->cfg.out_channel;
+        launch_init_state(c->x0, c->cfg.in_channel - C, C, c->ckpt, c->seed, c->image_offset, c->wB, c->stream);
+        if (c->x0p) launch_pack_state(c->x0, c->wB, c->x0p, c->stream, c->d_ovf);
+        if (c->uses_hist) {
+            const hipError_t e = hipMemcpyAsync(c->xhist, c->ckpt + slab, slab * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+            if (e != hipSuccess) return fail("sr3_sample: restore of the x0 history: %s", hipGetErrorString(e));
+        }
+        c->hist_valid = hist_valid;
+        return 0;
+    }
+};
+}
+
 int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *noise_dev, uint64_t seed,
                uint64_t image_offset, float *out_dev, float *frames_dev) {
     if (!out_dev) return fail("sr3_sample: out_dev is null");
     if (sr3_sample_begin(c, cond_dev, B, H, W, noise_dev, seed, image_offset)) return -1;
     const int T = c->T, si = 1 | (T / 10);
-    const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
-    const size_t slab = (size_t)B * C * H * W;
-    // Guard of the split-f16 modes: the loop is cut into segments of `seg` steps. At every segment boundary the device
-    // flag is read (one stream synchronisation per segment: ~10 per call); while it is clean the sampler state is saved
-    // (NCHW copy, 12 B per pixel). Two things can raise it:
-    //  * RANGE (an activation beyond the operand format). Default policy: the state of the last clean boundary is
-    //    restored and the REST of the loop runs one arithmetic down (f16f8 -> f16x3 -> exact f32) — every draw of the
-    //    noise (injected slab or Philox draw index) and every frame slot is a function of t, so the replay is exact.
-    //    Strict policy: the call fails at that boundary.
-    //  * an in-place split-K WAIT that gave up because a co-tenant kernel held the CU slots (range_read == 2): the
-    //    context has switched to the non-waiting conv path; the segment is replayed from the boundary in the SAME
-    //    arithmetic, whatever the policy.
-    const bool guard = c->prec == 1;
+    const size_t slab = (size_t)B * c->cfg.out_channel * H * W;
+    // Guard of the split-f16 modes (the policy of guarded_eval, with a segment of `seg` steps as the unit of replay): at
+    // the end of every segment the device flag is read (one stream synchronisation: ~10 per call); while it is clean the
+    // sampler state is saved (NCHW copy, 12 B per pixel). A WAIT that gave up replays the segment from that checkpoint in
+    // the same arithmetic, whatever the policy. Out of RANGE fails the call under the strict policy; else the checkpoint
+    // is restored and the REST of the loop runs one arithmetic down (step_down) — every draw of the noise (injected slab
+    // or Philox draw index) and every frame slot is a function of t, so the replay is exact.
     const int seg = std::max(1, T / 10);
-    // a multistep sampler's update also reads the previous step's x0: the checkpoint holds that history too
-    const size_t ck_floats = c->uses_hist ? 2 * slab : slab;
-    if (guard && c->ckpt_floats < ck_floats) {
-        if (c->ckpt) HIP_OK(hipFree(c->ckpt));
-        c->ckpt = nullptr; c->ckpt_floats = 0;
-        HIP_OK(hipMalloc(&c->ckpt, ck_floats * sizeof(float)));
-        c->ckpt_floats = ck_floats;
-    }
-    // save / restore: 0, or -1 with the error set
-    bool ck_hist_valid = false;
-    auto save = [&]() -> int {
-        launch_nhwc_to_nchw(c->x0, nc, B, C, c->ckpt, c->stream);
-        ck_hist_valid = c->hist_valid;
-        if (c->uses_hist) {
-            const hipError_t e = hipMemcpyAsync(c->ckpt + slab, c->xhist, slab * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) return fail("sr3_sample: checkpoint of the x0 history: %s", hipGetErrorString(e));
-        }
-        return 0;
-    };
-    auto restore = [&]() -> int {
-        launch_init_state(c->x0, nc, C, c->ckpt, seed, image_offset, B, c->stream);
-        if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
-        c->hist_valid = ck_hist_valid;
-        if (c->uses_hist) {
-            const hipError_t e = hipMemcpyAsync(c->xhist, c->ckpt + slab, slab * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) return fail("sr3_sample: restore of the x0 history: %s", hipGetErrorString(e));
-        }
-        return 0;
-    };
-    // back to the last clean boundary, one arithmetic down from here on: f16f8 -> f16x3 (the fp8 operands have the
-    // narrower range; the guard stays on) -> exact f32 (the mode is restored before the call returns)
-    const bool f8_was = c->f8corr;
-    auto fall_back = [&]() -> int {
-        if (restore()) return -1;
-        if (c->f8corr) c->f8corr = false;
-        else c->prec = 0;
-        return 0;
-    };
-    int t_ck = T - 1, f_ck = 0;          // the checkpoint holds the state BEFORE step t_ck; f_ck frames were written by then
-    bool fell_back = false;              // exact f32 from here on: no more checks
-    bool any_fallback = false, replayed = false;
-    int rc = 0;
+    ModeScope scope(c);                  // (the mode is restored on every return)
+    Checkpoint ck(c, slab);
+    bool guard = c->split();             // false in exact f32, from the start or after stepping down: no more checks
+    bool stepped_down = false, replayed = false;
     if (guard) {
+        if (ck.reserve()) return -1;
         const int r = range_read(c);     // (the initial state / its packed copy)
         if (r < 0) return -1;
         if (r == 1 && c->strict_range) return range_fail(c, "sr3_sample");
-        if (r == 1) { c->prec = 0; fell_back = any_fallback = true; }
-        else if (save()) return -1;
+        if (r == 1) { step_down(c, true); guard = false; stepped_down = true; }
+        else if (ck.save(T - 1, 0)) return -1;
     }
-    int f = 0;
-    // boundary check: 0 = clean (checkpoint taken by the caller), 1 = rewound to the checkpoint, -1 = error (rc set)
-    auto boundary = [&]() -> int {
-        const int r = range_read(c);
-        if (r < 0) { rc = -1; return -1; }
-        if (r == 0) return 0;
-        if (r == 2) {
-            if (restore()) { rc = -1; return -1; }
-            replayed = true;
-            return 1;
-        }
-        if (c->strict_range) { rc = range_fail(c, "sr3_sample"); return -1; }
-        if (fall_back()) { rc = -1; return -1; }
-        fell_back = c->prec == 0; any_fallback = true;
-        return 1;
-    };
-    for (int t = T - 1; t >= 0; --t) {
-        if (guard && !fell_back && t != T - 1 && ((T - 1 - t) % seg) == 0) {
-            const int b = boundary();
-            if (b < 0) break;
-            if (b == 1) { t = t_ck; f = f_ck; }
-            else if (save()) { rc = -1; break; }
-            else { t_ck = t; f_ck = f; }
-        }
+    for (int t = T - 1, f = 0; t >= 0; --t) {
         const float *nz = (noise_dev && t > 0) ? noise_dev + (size_t)(T - t) * slab : nullptr;
         float *fr = (frames_dev && (t % si == 0)) ? frames_dev + (size_t)(f++) * slab : nullptr;
-        if (step_checked(c, t, nz, fr)) { rc = -1; break; }
+        if (step_checked(c, t, nz, fr)) return -1;
         if (c->prof && (t % 8) == 0) c->pflush();  // bound the number of live events
-        if (guard && !fell_back && t == 0) {        // the last segment
-            const int b = boundary();
-            if (b < 0) break;
-            if (b == 1) { t = t_ck + 1; f = f_ck; }             // (the loop's --t resumes at t_ck)
+        if (!guard || (t != 0 && ((T - t) % seg) != 0)) continue;
+        // a segment ends here: the state is the one before step t - 1 (after the last step: the result)
+        const int r = range_read(c);
+        if (r < 0) return -1;
+        if (r == 0) {
+            if (t > 0 && ck.save(t - 1, f)) return -1;
+            continue;
         }
+        if (r == 1 && c->strict_range) return range_fail(c, "sr3_sample");
+        if (ck.restore()) return -1;
+        if (r == 2) replayed = true;
+        else { guard = step_down(c) != A_F32; stepped_down = true; }
+        t = ck.t + 1; f = ck.frames;     // (the loop's --t resumes at the checkpoint; the frame index rewinds with t)
     }
-    if (rc == 0) {
-        if (guard) {
-            c->pbegin(F_MISC);
-            launch_nhwc_to_nchw(c->x0, nc, c->wB, C, out_dev, c->stream);
-            c->pend();
-            if (hipGetLastError() != hipSuccess) rc = fail("sr3_sample: launch failed");
-            if (any_fallback && rc == 0 && hipMemsetAsync(c->d_ovf, 0, sizeof(int), c->stream) != hipSuccess) rc = fail("hipMemsetAsync failed");
-        } else {
-            rc = sr3_sample_end(c, out_dev);
-        }
-    }
-    const bool to_f16x3 = any_fallback && !fell_back;
-    if (guard) { c->prec = 1; c->f8corr = f8_was; }
-    if (rc) return rc;
-    if (any_fallback) return warn_fallback(c, "sr3_sample", "the rest of the loop from the last in-range checkpoint", to_f16x3);
+    if (sample_copy_out(c, out_dev)) return -1;
+    // (nothing reads the flag once the loop runs in f32, and the packed-state stores still raise it: leave it clean)
+    if (stepped_down && range_reset(c)) return -1;
+    if (stepped_down) return warn_fallback(c, "sr3_sample", "the rest of the loop from the last in-range checkpoint", c->split());
     return replayed ? warn_replay(c, "sr3_sample", "the segment of T/10 steps it happened in") : 0;
 }
 
@@ -2023,25 +2017,17 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     HIP_OK(hipMemsetAsync(p.in0.p, 0, p.in0.floats(B) * sizeof(float), c->stream));
     const TDesc i0 = unpadded(const_cast<float *>(in0_dev), C0, Hin, Win);
     const TDesc i1 = in1_dev ? unpadded(const_cast<float *>(in1_dev), C1, Hin, Win) : kNone;
-    if (range_reset(c)) return -1;
-    launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, gn_scale_dev ? (swish ? 2 : 1) : 0, sc.f8 ? 2 : c->prec, p.in0,
-                    c->stream, TDesc(), 0, c->d_ovf);
-    // (this entry point owns its inputs: an in-place split-K wait that gave up — range_read == 2 — is answered by running
-    // the conv again on the non-waiting path, as sr3_unet_forward / sr3_sample do)
-    bool replayed = false;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    // (this entry point owns its inputs: an in-place split-K wait that gave up is answered by running the pass and the
+    // conv again on the non-waiting path, as sr3_unet_forward / sr3_sample do; it never leaves the arithmetic it was asked for)
+    return guarded_eval(c, "sr3_op_conv2d", "the conv", false, [&]() -> int {
+        launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, gn_scale_dev ? (swish ? 2 : 1) : 0, c->act_format(sc.f8), p.in0,
+                        c->stream, TDesc(), 0, c->d_ovf);
         p.no_halo_split = c->halo_split_off ? 1 : 0;
         launch_conv(p, c->stream);
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("sr3_op_conv2d: launch failed");
         if (const char *e = conv_take_error()) return fail("sr3_op_conv2d: %s", e);
-        if (!c->prec) break;
-        const int r = range_read(c);
-        if (r == 2 && attempt == 0) { replayed = true; continue; }
-        if (r == 2) return fail("internal: inter-block wait flag raised with the in-place split-K disabled");
-        if (r) return r < 0 ? -1 : range_fail(c, "sr3_op_conv2d");
-        break;
-    }
-    return replayed ? warn_replay(c, "sr3_op_conv2d", "the conv") : 0;
+        return 0;
+    });
 }
 
 // Times `iters` launches of one conv shape on scratch buffers (random contents; f32 MFMA time does
@@ -2079,7 +2065,7 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     HIP_OK(hipEventRecord(e0, c->stream));
     for (int i = 0; i < iters; ++i) launch_conv(p, c->stream);
     HIP_OK(hipEventRecord(e1, c->stream));
-    for (int i = 0; i < iters; ++i) launch_gn_apply(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, sc.f8 ? 2 : c->prec, p.in0, c->stream);
+    for (int i = 0; i < iters; ++i) launch_gn_apply(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, c->act_format(sc.f8), p.in0, c->stream);
     HIP_OK(hipEventRecord(e2, c->stream));
     HIP_OK(hipEventSynchronize(e2));
     float ms = 0.f;
@@ -2118,10 +2104,11 @@ int sr3_op_groupnorm_affine(sr3_ctx *c, const float *in0_dev, int C0, const floa
 int sr3_op_attention(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev) {
     if (!c || !qkv_dev || !out_dev) return fail("sr3_op_attention: null argument");
     if (C % 32 || N < 1) return fail("sr3_op_attention: need C %% 32 == 0 and N >= 1");
-    if (N > 1024 && !attention_stream_supported(C))
+    const AttnCore core = attention_core(c->split(), N, C);
+    if (core == ATTN_UNSUPPORTED)
         return fail("sr3_op_attention: over 1024 tokens the streaming core takes at most 512 channels (C = %d)", C);
     HIP_OK(hipSetDevice(c->device));
-    if (c->prec && attention_split_supported(N, C)) {
+    if (core == ATTN_SPLIT) {
         // split-f16 mode: the engine's own sequence — q, k, v in the split operand format, fp32 result
         float *tmp = nullptr;
         HIP_OK(hipMalloc(&tmp, ((size_t)B * N * 3 * C + attention_vt_floats(B, N, C)) * sizeof(float)));
@@ -2134,7 +2121,7 @@ int sr3_op_attention(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, floa
         HIP_OK(hipGetLastError());
         return range_check(c, "sr3_op_attention");
     }
-    if (N > 1024) launch_attention_stream(qkv_dev, B, N, C, out_dev, c->stream);
+    if (core == ATTN_STREAM) launch_attention_stream(qkv_dev, B, N, C, out_dev, c->stream);
     else launch_attention(qkv_dev, B, N, C, out_dev, c->stream);
     HIP_OK(hipGetLastError());
     return 0;
@@ -2154,13 +2141,7 @@ int sr3_op_attention_stream(sr3_ctx *c, const float *qkv_dev, int B, int N, int 
 int sr3_op_noise_embed(sr3_ctx *c, const float *noise_level_dev, int B, float *temb_dev, float *chan_bias_dev) {
     if (check_ready(c)) return -1;
     if (!noise_level_dev || !chan_bias_dev) return fail("sr3_op_noise_embed: null argument");
-    EmbedParams e;
-    e.noise_level = noise_level_dev; e.nl_stride = 1; e.dim = c->cfg.inner_channel;
-    e.w1 = c->params[c->mlp_w1].dev; e.b1 = c->params[c->mlp_b1].dev;
-    e.w2 = c->params[c->mlp_w2].dev; e.b2 = c->params[c->mlp_b2].dev;
-    e.nfw = c->nfw; e.nfb = c->nfb; e.total = c->nf_total;
-    e.temb = temb_dev; e.chan_bias = chan_bias_dev;
-    launch_noise_embed(e, B, c->stream);
+    launch_noise_embed(embed_params(c, noise_level_dev, 1, temb_dev, chan_bias_dev), B, c->stream);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -276,6 +276,12 @@ double launch_attention_stream(const float *qkv, int B, int N, int C, float *out
 // out (fp32 [B][N][C]) and / or out_split (the same tensor in the split format) may be null
 bool attention_split_supported(int N, int C);
 size_t attention_vt_floats(int B, int N, int C);     // scratch for v^T
+// Which core runs self-attention over N tokens of C channels: the split-f16 core where the arithmetic is split-f16 and the
+// shape fits it; else the 32 x N score-tile core while that tile fits in LDS; else the streaming core within its channel
+// bound. The one decision behind workspace sizing, the batch bound, the UNet's launch and sr3_op_attention.
+constexpr int ATTN_TILE_MAX_TOKENS = 1024;
+enum AttnCore { ATTN_SPLIT, ATTN_TILE, ATTN_STREAM, ATTN_UNSUPPORTED };
+AttnCore attention_core(bool split_f16, long N, int C);
 double launch_attention_split(const float *qkv_split, float *vt, int B, int N, int C, float *out, float *out_split,
                               int *ovf, hipStream_t s);
 

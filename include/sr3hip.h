@@ -194,6 +194,8 @@ int sr3_sample_end(sr3_ctx *ctx, float *out_dev);
  *   In mode 2 ("f16f8") the flag is also raised by an activation beyond the fp8 operand range (|v| > 448) in a conv on
  *     the fp8 correction path; the message then names mode 1 (f16x3) as the first remedy, mode 0 as the second, and the
  *     default policy of sr3_unet_forward / sr3_sample retries in exactly that order.
+ *     (The ladder is written once for the owned-input calls, sr3_denoise_loss included — guarded_eval in
+ *     csrc/sr3_api.hip — and once for sr3_sample's checkpointed segments.)
  *   The same flag word carries the "in-place split-K wait gave up" bit (SR3_OK_REPLAYED above): sr3_unet_forward and
  *     sr3_sample replay by themselves; sr3_sample_end / sr3_range_check fail with a message that says to repeat the call. */
 int sr3_range_check(sr3_ctx *ctx);

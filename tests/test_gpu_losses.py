@@ -350,6 +350,60 @@ def test_range_policy_finishes_in_f32_and_strict_mode_raises(nets):
         netG.denoise_fn.precision = "f32"
 
 
+def test_fp8_range_steps_down_to_f16x3_first(nets):
+    """The f16f8 -> f16x3 rung of the loss entry. The network of tests/test_gpu_f16f8.py::test_fp8_range_falls_back_to_f16x3_first
+    (yml-224 UNet, one block2 GroupNorm gamma of the 32x32 level x 400: |activation| ~ 1e3, beyond the fp8 operand range of
+    448 and far inside the fp16 range) on 128x128 images, at the smallest batch at which the f16f8 mode puts the 256 -> 256
+    convs of that level on the fp8 path."""
+    import torch
+    cfg = synth.yml_unet_config(224)
+    sd = synth.synth_state_dict(cfg, 3)
+    name = next(k for k, v in sd.items() if k.startswith("downs.") and k.endswith("res_block.block2.block.0.weight") and v.shape == (256,))
+    sd[name] = sd[name] * np.float32(400.0)
+    netG = nets("fp8_overflow", lambda: _net(cfg, S20, 3, sd=sd))
+    eng = netG._engine()
+    B = next((b for b in range(1, 64) if eng.conv_f8_supported(b, 32, 32, 256, 256)), 64)
+    assert eng.conv_f8_supported(B, 32, 32, 256, 256)                        # the fp8 path runs, or the test shows nothing
+    hr, sr = _images(2, 128, 23)
+    noise = torch.from_numpy(synth.synth_noise(1, B, 3, 128, 128, 23)[0]).cuda()
+    levels = np.linspace(0.9, 0.1, B).astype(np.float32)
+    unet = netG.denoise_fn
+    unet.strict_range = False
+    try:
+        unet.precision = "f16x3"
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            want = _raw(netG, hr, sr, levels, noise=noise)
+        unet.precision = "f16f8"
+        before = eng.fallback_calls()
+        with warnings.catch_warnings(record=True) as rec:
+            warnings.simplefilter("always")
+            got = _raw(netG, hr, sr, levels, noise=noise)
+        hits = [w for w in rec if issubclass(w.category, Sr3RangeWarning)]
+        print(f"f16f8 loss at B = {B}: {len(hits)} range warning(s): {[str(w.message)[:90] for w in hits]}; "
+              f"fallback_calls {before} -> {eng.fallback_calls()}")
+        assert len(hits) == 1 and "f16x3" in str(hits[0].message)
+        assert eng.fallback_calls() == before + 1
+        assert np.isfinite(got[0]).all()
+        for a, b in zip(got, want):                                          # per-image losses, x_noisy, eps
+            assert a.tobytes() == b.tobytes()
+        # the mode was put back: an in-range call (two rows: no conv on the fp8 path) passes without a warning, and the
+        # same out-of-range call is caught and counted again
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            small = _raw(netG, hr, sr, levels[:2], noise=noise[:2].contiguous())
+        assert np.isfinite(small[0]).all() and eng.fallback_calls() == before + 1
+        with pytest.warns(Sr3RangeWarning, match="f16x3"):
+            again = _raw(netG, hr, sr, levels, noise=noise)
+        assert again[0].tobytes() == want[0].tobytes() and eng.fallback_calls() == before + 2
+        unet.strict_range = True
+        with pytest.raises(Sr3Error, match="fp8 range"):
+            _raw(netG, hr, sr, levels, noise=noise)
+    finally:
+        unet.strict_range = False
+        unet.precision = "f32"
+
+
 def test_bad_arguments_raise(tiny):
     import torch
     hr, sr = _images(2, 16, 1)
