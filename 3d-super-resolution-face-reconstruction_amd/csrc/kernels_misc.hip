@@ -315,13 +315,81 @@ struct GnFold {
 
 constexpr int GA_T = 512;      // threads per block of the apply pass
 
+// The prologue of the apply passes (gn_apply_kernel, gn_wino_input_kernel; blocks of GA_T threads, all of image n):
+// leaves scale = rstd * gamma, shift = beta - mean * scale of the C channels in smem ([C] scale | [C] shift | scratch
+// of the fold, ga_lds_bytes) and synchronises. scale / shift != null: copied from memory; else folded from the fp64
+// statistics partials: per channel it adds the slices, assembles groups from channels (any group size, groups may
+// straddle the x / skip boundary of a concatenation). Deterministic (fixed summation order, no atomics).
+__device__ __forceinline__ void gn_scale_shift_to_lds(const float *__restrict__ scale, const float *__restrict__ shift,
+                                                      const GnFold &st, const int n, const int C, float *ga_smem) {
+    const int t = threadIdx.x;
+    float *sc = ga_smem, *sh = ga_smem + C;             // [C] each
+    if (scale != nullptr) {
+        for (int c = t; c < C; c += GA_T) { sc[c] = scale[(size_t)n * C + c]; sh[c] = shift[(size_t)n * C + c]; }
+    } else {
+        double2 *chs = reinterpret_cast<double2 *>(ga_smem + 2 * C);    // [C] per-channel totals
+        double2 *red = chs + C;                                         // [GA_T]
+        float *gm = reinterpret_cast<float *>(red + GA_T), *gr = gm + st.groups;
+        const int CP = min(C, GA_T), L = GA_T / CP;                     // slice lanes per channel
+        for (int cbase = 0; cbase < C; cbase += CP) {
+            const int c = cbase + t % CP, l = t / CP;
+            double a = 0, b = 0;
+            if (l < L && c < C) {
+                const bool first = c < st.C0;
+                const double *pp = first ? st.p0 : st.p1;
+                const int Cs = first ? st.C0 : st.C1, cl = first ? c : c - st.C0, sl = first ? st.slices0 : st.slices1;
+                const double *base = pp + ((size_t)n * sl * Cs + cl) * 2;
+                const size_t stride = (size_t)Cs * 2;                   // doubles between slices
+                int s = l;
+                // eight loads in flight per thread (a plain loop waits for every load before the next);
+                // summed in slice order: deterministic
+                for (; s + 7 * L < sl; s += 8 * L) {
+                    double2 v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const double2 *>(base + (size_t)(s + u * L) * stride);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { a += v[u].x; b += v[u].y; }
+                }
+                for (; s < sl; s += L) {
+                    const double2 v = *reinterpret_cast<const double2 *>(base + (size_t)s * stride);
+                    a += v.x; b += v.y;
+                }
+            }
+            red[t] = make_double2(a, b);
+            __syncthreads();
+            if (t < CP && cbase + t < C) {
+                double sa = 0, sb = 0;
+                for (int l2 = 0; l2 < L; ++l2) { const double2 v = red[l2 * CP + t]; sa += v.x; sb += v.y; }
+                chs[cbase + t] = make_double2(sa, sb);
+            }
+            __syncthreads();
+        }
+        const int Cg = C / st.groups;
+        for (int g = t; g < st.groups; g += GA_T) {
+            double sa = 0, sb = 0;
+            for (int cc = 0; cc < Cg; ++cc) { const double2 v = chs[g * Cg + cc]; sa += v.x; sb += v.y; }
+            const double cnt = (double)Cg * st.HW;
+            const double mean = sa / cnt;
+            const double var = fmax(sb / cnt - mean * mean, 0.0);
+            gm[g] = (float)mean;
+            gr[g] = 1.0f / sqrtf((float)var + st.eps);
+        }
+        __syncthreads();
+        for (int c = t; c < C; c += GA_T) {
+            const int g = c / Cg;
+            const float v = gr[g] * st.gamma[c];
+            sc[c] = v;
+            sh[c] = st.beta[c] - gm[g] * v;
+        }
+    }
+    __syncthreads();
+}
+
 // One block = `ppb` consecutive pixels of one image, all channels; a thread owns 8 consecutive
 // channels of a pixel per iteration (two 16-B loads, 16-B stores). The prologue folds the
-// GroupNorm FINALIZE into the pass (it used to be a launch of its own in front of every apply):
-// per channel it adds the slices, assembles groups from channels (any group size, groups may
-// straddle the x / skip boundary of a concatenation), and leaves scale = rstd * gamma,
-// shift = beta - mean * scale in LDS. Deterministic (fixed summation order, no atomics).
-// MODE 0 copy, 1 affine, 2 affine + Swish; scale/shift != null: take them from memory instead.
+// GroupNorm FINALIZE into the pass (it used to be a launch of its own in front of every apply;
+// gn_scale_shift_to_lds). MODE 0 copy, 1 affine, 2 affine + Swish; scale/shift != null: take them
+// from memory instead.
 template <int MODE, int SPLIT>
 __global__ __launch_bounds__(GA_T) void gn_apply_kernel(const TDesc in0, const TDesc in1,
                                                          const float *__restrict__ scale,
@@ -332,67 +400,7 @@ __global__ __launch_bounds__(GA_T) void gn_apply_kernel(const TDesc in0, const T
     const int C0 = in0.C, C = out.C, C8 = C >> 3;
     const int n = blockIdx.y, t = threadIdx.x;
     float *sc = ga_smem, *sh = ga_smem + C;             // [C] each
-    if (MODE != 0) {
-        if (scale != nullptr) {
-            for (int c = t; c < C; c += GA_T) { sc[c] = scale[(size_t)n * C + c]; sh[c] = shift[(size_t)n * C + c]; }
-        } else {
-            double2 *chs = reinterpret_cast<double2 *>(ga_smem + 2 * C);    // [C] per-channel totals
-            double2 *red = chs + C;                                         // [GA_T]
-            float *gm = reinterpret_cast<float *>(red + GA_T), *gr = gm + st.groups;
-            const int CP = min(C, GA_T), L = GA_T / CP;                     // slice lanes per channel
-            for (int cbase = 0; cbase < C; cbase += CP) {
-                const int c = cbase + t % CP, l = t / CP;
-                double a = 0, b = 0;
-                if (l < L && c < C) {
-                    const bool first = c < st.C0;
-                    const double *pp = first ? st.p0 : st.p1;
-                    const int Cs = first ? st.C0 : st.C1, cl = first ? c : c - st.C0, sl = first ? st.slices0 : st.slices1;
-                    const double *base = pp + ((size_t)n * sl * Cs + cl) * 2;
-                    const size_t stride = (size_t)Cs * 2;                   // doubles between slices
-                    int s = l;
-                    // eight loads in flight per thread (a plain loop waits for every load before the next);
-                    // summed in slice order: deterministic
-                    for (; s + 7 * L < sl; s += 8 * L) {
-                        double2 v[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const double2 *>(base + (size_t)(s + u * L) * stride);
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) { a += v[u].x; b += v[u].y; }
-                    }
-                    for (; s < sl; s += L) {
-                        const double2 v = *reinterpret_cast<const double2 *>(base + (size_t)s * stride);
-                        a += v.x; b += v.y;
-                    }
-                }
-                red[t] = make_double2(a, b);
-                __syncthreads();
-                if (t < CP && cbase + t < C) {
-                    double sa = 0, sb = 0;
-                    for (int l2 = 0; l2 < L; ++l2) { const double2 v = red[l2 * CP + t]; sa += v.x; sb += v.y; }
-                    chs[cbase + t] = make_double2(sa, sb);
-                }
-                __syncthreads();
-            }
-            const int Cg = C / st.groups;
-            for (int g = t; g < st.groups; g += GA_T) {
-                double sa = 0, sb = 0;
-                for (int cc = 0; cc < Cg; ++cc) { const double2 v = chs[g * Cg + cc]; sa += v.x; sb += v.y; }
-                const double cnt = (double)Cg * st.HW;
-                const double mean = sa / cnt;
-                const double var = fmax(sb / cnt - mean * mean, 0.0);
-                gm[g] = (float)mean;
-                gr[g] = 1.0f / sqrtf((float)var + st.eps);
-            }
-            __syncthreads();
-            for (int c = t; c < C; c += GA_T) {
-                const int g = c / Cg;
-                const float v = gr[g] * st.gamma[c];
-                sc[c] = v;
-                sh[c] = st.beta[c] - gm[g] * v;
-            }
-        }
-        __syncthreads();
-    }
+    if (MODE != 0) gn_scale_shift_to_lds(scale, shift, st, n, C, ga_smem);
     // thread = (pixel lane, channel octet): the octet and its scale / shift stay in registers, the pixel
     // advances by `rows` per iteration (no division in the loop)
     const int W = out.W, HW = out.H * W;
@@ -549,6 +557,94 @@ __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const TDesc in0, con
 }
 } // namespace
 
+namespace {
+// GroupNorm apply (+ Swish) (+ concat) + Winograd F(2x2, 3x3) input transform in ONE pass (exact f32, unsplit inputs):
+// U[pos][tile][Cin] = (B^T d B)[pos] of the activated, zero-bordered window d, as wino_input_kernel writes it from
+// the tensor gn_apply_kernel would have stored in between — the same fmaf / swish_fast per value and the same order of
+// the +-1 adds (rows, then columns), so U is bit for bit the two passes' U. Window pixels outside the image are 0.0f
+// (their address is clamped into the image, the value loaded there is dropped).
+// Block = GA_T threads of one image (the prologue of gn_apply_kernel); an item = one channel quad of one tile, as in
+// wino_input_kernel: every pixel is fetched and activated by the four windows that hold it, out of the caches.
+// Consecutive threads take consecutive channel quads: a wave stores 1 KiB of contiguous memory into each of the 16 planes.
+template <int MODE>
+__global__ __launch_bounds__(GA_T) void gn_wino_input_kernel(const TDesc in0, const TDesc in1,
+                                                              const float *__restrict__ scale,
+                                                              const float *__restrict__ shift, const GnFold st,
+                                                              float *__restrict__ U, const int B) {
+#pragma clang fp contract(off)      // (an activation must not fuse into the adds of the transform)
+    extern __shared__ __attribute__((aligned(16))) float ga_smem[];
+    const int C0 = in0.C, C = C0 + (in1.p ? in1.C : 0), cq = C >> 2;
+    const int n = blockIdx.y;
+    const float *sc = ga_smem, *sh = ga_smem + C;
+    if (MODE != 0) gn_scale_shift_to_lds(scale, shift, st, n, C, ga_smem);
+    const int H = in0.H, W = in0.W, th = H >> 1, tw = W >> 1;
+    const unsigned items = (unsigned)th * tw * cq;
+    const size_t plane = (size_t)B * th * tw * C;
+    for (unsigned i = blockIdx.x * GA_T + threadIdx.x; i < items; i += gridDim.x * GA_T) {
+        const unsigned r = i / (unsigned)cq;
+        const int c4 = (int)(i - r * (unsigned)cq) * 4;
+        const int tx = (int)(r % (unsigned)tw), ty = (int)(r / (unsigned)tw);
+        const bool first = c4 < C0;
+        const TDesc &src = first ? in0 : in1;
+        const float *sp = src.p + (first ? c4 : c4 - C0);
+        const size_t Cs = src.C;
+        f32x4v scv = {0.f, 0.f, 0.f, 0.f}, shv = {0.f, 0.f, 0.f, 0.f};
+        if (MODE != 0) { scv = *reinterpret_cast<const f32x4v *>(sc + c4); shv = *reinterpret_cast<const f32x4v *>(sh + c4); }
+        // columns of the window: image x = 2 tx - 1 + j
+        int xc[4];
+        bool xin[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = 2 * tx - 1 + j;
+            xin[j] = (unsigned)x < (unsigned)W;
+            xc[j] = min(max(x, 0), W - 1);
+        }
+        // one activated window row (image row y) into d[0..3]
+        auto row = [&](int y, f32x4v (&d)[4]) {
+            const bool yin = (unsigned)y < (unsigned)H;
+            const int yc = min(max(y, 0), H - 1);
+            f32x4v v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const f32x4v *>(sp + src.pix(n, yc, xc[j]) * Cs);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                f32x4v f = v[j];
+                if (MODE != 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) f[k] = fmaf(f[k], scv[k], shv[k]);
+                }
+                if (MODE == 2) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) f[k] = swish_fast(f[k]);
+                }
+                const bool in = yin && xin[j];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) d[j][k] = in ? f[k] : 0.0f;
+            }
+        };
+        f32x4v d[4][4];
+#pragma unroll
+        for (int y = 0; y < 4; ++y) row(2 * ty - 1 + y, d[y]);
+        f32x4v e[4][4];            // B^T d
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            e[0][x] = d[0][x] - d[2][x];
+            e[1][x] = d[1][x] + d[2][x];
+            e[2][x] = d[2][x] - d[1][x];
+            e[3][x] = d[1][x] - d[3][x];
+        }
+        float *o = U + ((size_t)(n * th + ty) * tw + tx) * C + c4;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {   // (B^T d) B
+            *reinterpret_cast<f32x4v *>(o + (size_t)(a * 4 + 0) * plane) = e[a][0] - e[a][2];
+            *reinterpret_cast<f32x4v *>(o + (size_t)(a * 4 + 1) * plane) = e[a][1] + e[a][2];
+            *reinterpret_cast<f32x4v *>(o + (size_t)(a * 4 + 2) * plane) = e[a][2] - e[a][1];
+            *reinterpret_cast<f32x4v *>(o + (size_t)(a * 4 + 3) * plane) = e[a][1] - e[a][3];
+        }
+    }
+}
+} // namespace
+
 void launch_gn_apply_rows(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
                           int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw, int in_split, int *ovf) {
     const int items = out.W * (out.C >> 3);
@@ -580,15 +676,20 @@ static int ga_pixels_per_block(int B, int HW, int C8) {
     return (HW + P - 1) / P;
 }
 
+// LDS of gn_scale_shift_to_lds: scale / shift [C] floats; fold scratch: per-channel totals [C] + lanes [GA_T] double2,
+// group mean / rstd
+static size_t ga_lds_bytes(int mode, int C, bool from_memory, int groups) {
+    return mode == 0 ? 16 : ((size_t)2 * C * sizeof(float) +
+                             (from_memory ? 0 : ((size_t)C + GA_T) * sizeof(double2) + (size_t)2 * groups * sizeof(float)));
+}
+
 static void launch_gn_apply_impl(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
                                  const GnFold &st, int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw,
                                  int in_split, int *ovf) {
     const int HW = out.H * out.W, C = out.C;
     const int ppb = ga_pixels_per_block(B, HW, C >> 3);
     const dim3 grid((HW + ppb - 1) / ppb, B);
-    // LDS: scale / shift [C] floats; fold scratch: per-channel totals [C] + lanes [GA_T] double2, group mean / rstd
-    const size_t lds = mode == 0 ? 16 : ((size_t)2 * C * sizeof(float) +
-                       (scale ? 0 : ((size_t)C + GA_T) * sizeof(double2) + (size_t)2 * st.groups * sizeof(float)));
+    const size_t lds = ga_lds_bytes(mode, C, scale != nullptr, st.groups);
 #define SR3_GA(M, S)                                                                                               \
     {                                                                                                              \
         static size_t attr = 48 * 1024;                                                                            \
@@ -615,16 +716,55 @@ void launch_gn_apply(const TDesc &in0, const TDesc &in1, int B, const float *sca
     launch_gn_apply_impl(in0, in1, B, scale, shift, GnFold(), mode, split, out, s, raw, in_split, ovf);
 }
 
-// GroupNorm (statistics already accumulated as partials) + affine (+ Swish) (+ concat) in ONE launch
-void launch_gn_fold_apply(const TDesc &in0, const TDesc &in1, int B, const StatsRef &s0, const StatsRef &s1, int groups,
-                          const float *gamma, const float *beta, float eps, int mode, int split, const TDesc &out,
-                          hipStream_t s, const TDesc &raw, int in_split, int *ovf) {
+static GnFold gn_fold_of(const TDesc &in0, const TDesc &in1, const StatsRef &s0, const StatsRef &s1, int groups,
+                         const float *gamma, const float *beta, float eps) {
     GnFold st;
     st.p0 = s0.p; st.C0 = in0.C; st.slices0 = s0.slices;
     st.p1 = s1.p; st.C1 = in1.p ? in1.C : 0; st.slices1 = s1.slices;
     if (in1.p && !s1.p) { st.C0 = in0.C + in1.C; st.C1 = 0; }      // s0 describes the whole concatenation
     st.gamma = gamma; st.beta = beta; st.eps = eps; st.groups = groups; st.HW = in0.H * in0.W;
-    launch_gn_apply_impl(in0, in1, B, nullptr, nullptr, st, mode, split, out, s, raw, in_split, ovf);
+    return st;
+}
+
+// GroupNorm (statistics already accumulated as partials) + affine (+ Swish) (+ concat) in ONE launch
+void launch_gn_fold_apply(const TDesc &in0, const TDesc &in1, int B, const StatsRef &s0, const StatsRef &s1, int groups,
+                          const float *gamma, const float *beta, float eps, int mode, int split, const TDesc &out,
+                          hipStream_t s, const TDesc &raw, int in_split, int *ovf) {
+    launch_gn_apply_impl(in0, in1, B, nullptr, nullptr, gn_fold_of(in0, in1, s0, s1, groups, gamma, beta, eps), mode, split,
+                         out, s, raw, in_split, ovf);
+}
+
+static void launch_gn_wino_impl(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
+                                const GnFold &st, int mode, float *U, hipStream_t s) {
+    const int C = in0.C + (in1.p ? in1.C : 0), th = in0.H / 2, tw = in0.W / 2;
+    const size_t items = (size_t)th * tw * (C / 4);
+    // blocks per image: one item per thread where the prologue only copies scale / shift; where it folds the
+    // statistics, as few blocks as keep every CU busy (gn_apply_kernel's ~1024 blocks of the whole grid)
+    unsigned gx = (unsigned)((items + GA_T - 1) / GA_T);
+    if (mode != 0 && !scale) gx = std::min(gx, (unsigned)std::max(1, (1024 + B - 1) / B));
+    const size_t lds = ga_lds_bytes(mode, C, scale != nullptr, st.groups);
+#define SR3_GW(M)                                                                                                  \
+    {                                                                                                              \
+        static size_t attr = 48 * 1024;                                                                            \
+        if (lds > attr) {                                                                                          \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gn_wino_input_kernel<M>),                     \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
+            attr = lds;                                                                                            \
+        }                                                                                                          \
+        hipLaunchKernelGGL((gn_wino_input_kernel<M>), dim3(gx, B), dim3(GA_T), lds, s, in0, in1, scale, shift, st, U, B);      \
+    }
+    if (mode == 0) SR3_GW(0) else if (mode == 1) SR3_GW(1) else SR3_GW(2)
+#undef SR3_GW
+}
+
+void launch_gn_wino_input(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift, int mode,
+                          float *U, hipStream_t s) {
+    launch_gn_wino_impl(in0, in1, B, scale, shift, GnFold(), mode, U, s);
+}
+
+void launch_gn_fold_wino_input(const TDesc &in0, const TDesc &in1, int B, const StatsRef &s0, const StatsRef &s1, int groups,
+                               const float *gamma, const float *beta, float eps, int mode, float *U, hipStream_t s) {
+    launch_gn_wino_impl(in0, in1, B, nullptr, nullptr, gn_fold_of(in0, in1, s0, s1, groups, gamma, beta, eps), mode, U, s);
 }
 
 // statistics by the streaming kernel (tensors whose producer could not fuse them): partials of the

@@ -8,8 +8,12 @@
 //         | 0  1  0 -1 |         | 0    0    1  |
 //
 // At <= 32x32 pixels, three passes per conv, all on one stream (64x64 and up: wino_fused_kernel, one pass):
-//   1. wino_input_kernel: U[pos][tile][Cin] = (B^T d B)[pos] over the zero-bordered input (window origins (2ty, 2tx)
-//      in padded coordinates, so the borders are already zero and nothing is masked); in0 || in1 concatenated here.
+//   1. the GroupNorm apply pass itself (gn_wino_input_kernel, kernels_misc.hip; ConvParams::u_ready), or
+//      wino_input_kernel where no such pass precedes the conv (and under SR3_NO_GN_WINO=1):
+//      U[pos][tile][Cin] = (B^T d B)[pos] over the zero-bordered input; in0 || in1 concatenated here.
+//      wino_input_kernel reads the activated tensor (window origins (2ty, 2tx) in padded coordinates, so the borders
+//      are already zero and nothing is masked); the apply pass activates the raw tensor on the way and never stores
+//      the activated one: the same values through the same +-1 adds, so U is bit-identical either way.
 //   2. launch_wino_gemm: M[pos] = U[pos] x V[pos] for the 16 positions, on the f32 implicit-GEMM kernel
 //      (conv_igemm_dma_f32 as a 1x1 conv, blockIdx.z = position): fixed K order, no atomics.
 //   3. wino_output_kernel: A^T M A per tile + bias + FeatureWiseAffine bias + residual into the zero-bordered output,
@@ -460,7 +464,8 @@ void launch_conv_wino(const ConvParams &p, ConvKernel form, hipStream_t s) {
     const size_t tiles = (size_t)p.B * (H / 2) * (W / 2);
     float *U = p.wino_ws, *Mw = p.wino_ws + 16 * tiles * Cin;
     const size_t items = tiles * (Cin / 4);
-    hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p.in0, p.in1, p.B, U);
+    if (!p.u_ready)
+        hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p.in0, p.in1, p.B, U);
 
     ConvParams g;
     g.in0.p = U; g.in0.C = Cin; g.in0.H = H / 2; g.in0.W = W / 2; g.in0.pad = 0;

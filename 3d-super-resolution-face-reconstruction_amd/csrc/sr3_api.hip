@@ -156,6 +156,7 @@ struct sr3_ctx {
     // the reference computes in fp32 and has no such limit (unet.py:235-265) — and returns SR3_OK_F32_FALLBACK.
     bool strict_range = false;
     int fallback_calls = 0;             // calls finished by the f32 fallback since sr3_create
+    int gn_wino_passes = 0;             // GroupNorm apply passes launched as launch_gn_wino_input / _fold_ since sr3_create
     float *ckpt = nullptr;              // sr3_sample: NCHW copy of the sampler state at the last clean checkpoint
     size_t ckpt_floats = 0;
     double *metrics_ws = nullptr;       // sr3_metrics_psnr_ssim / sr3_denoise_loss: per-block fp64 partial sums (grows on demand)
@@ -688,9 +689,14 @@ const TDesc kNone{};
 
 // GroupNorm statistics + apply (+Swish) (+concat) -> activated, zero-bordered conv input
 // f8: the consumer conv takes the F8C operand format (f8_conv() said so)
+// U != null (gn_writes_u() said so): the consumer is a three-pass Winograd conv and the pass writes its transformed
+// input there instead of `act` (the conv then runs with ConvParams::u_ready); the choice between the folded form and
+// finalize + streaming form is the same either way, so no pass gains or loses a finalize launch
 void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int B, int mode, const TDesc &act,
-                const StatsRef &sa, const StatsRef &sb, const TDesc &raw = TDesc(), int in_split = 0, bool f8 = false) {
+                const StatsRef &sa, const StatsRef &sb, const TDesc &raw = TDesc(), int in_split = 0, bool f8 = false,
+                float *U = nullptr) {
     const int fmt = c->act_format(f8);
+    if (U) ++c->gn_wino_passes;
     c->pbegin(F_GN);
     const float *gamma = c->params[g.gamma].dev, *beta = c->params[g.beta].dev;
     // bytes the pass moves (read + write, 4 B per element each way): above ~200 MB the one-item-per-thread
@@ -705,17 +711,20 @@ void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int 
     if (sa.p && (!b.p || sb.p) && (pass_bytes > fold_max || many_slices)) {
         launch_groupnorm_finalize(sa, a.C, sb, b.p ? b.C : 0, B, a.H * a.W, c->cfg.norm_groups, gamma, beta, 1e-5f,
                                   c->gscale, c->gshift, c->stream);
-        launch_gn_apply_rows(a, b, B, c->gscale, c->gshift, mode, fmt, act, c->stream, raw, in_split, c->d_ovf);
+        if (U) launch_gn_wino_input(a, b, B, c->gscale, c->gshift, mode, U, c->stream);
+        else launch_gn_apply_rows(a, b, B, c->gscale, c->gshift, mode, fmt, act, c->stream, raw, in_split, c->d_ovf);
     } else if (sa.p && (!b.p || sb.p)) {
         // statistics came out of the producing convs' epilogues: finalize + apply are ONE launch
-        launch_gn_fold_apply(a, b, B, sa, sb, c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream, raw,
-                             in_split, c->d_ovf);
+        if (U) launch_gn_fold_wino_input(a, b, B, sa, sb, c->cfg.norm_groups, gamma, beta, 1e-5f, mode, U, c->stream);
+        else launch_gn_fold_apply(a, b, B, sa, sb, c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream, raw,
+                                  in_split, c->d_ovf);
     } else {
         // fallback: streaming statistics kernel over the (fp32) tensors; its partials describe the
         // virtual concatenation as one source of a.C + b.C channels
         const StatsRef sp = launch_groupnorm_partials(a, b, B, c->gpart, c->stream);
-        launch_gn_fold_apply(a, b, B, sp, StatsRef(), c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream,
-                             raw, in_split, c->d_ovf);
+        if (U) launch_gn_fold_wino_input(a, b, B, sp, StatsRef(), c->cfg.norm_groups, gamma, beta, 1e-5f, mode, U, c->stream);
+        else launch_gn_fold_apply(a, b, B, sp, StatsRef(), c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream,
+                                  raw, in_split, c->d_ovf);
     }
     c->pend();
 }
@@ -739,9 +748,11 @@ struct ConvCall {
     TDesc in2, in2b;
     const ConvRef *fused1x1 = nullptr;
     const float *ident_w = nullptr;
+    bool u_ready = false;               // the GroupNorm pass wrote the Winograd input transform (gn_writes_u), `in` holds nothing
 };
 
-void run_conv(sr3_ctx *c, const ConvCall &k) {
+// the ConvParams of a ConvCall: what run_conv launches and what conv_plan is asked about before the conv's input exists
+ConvParams conv_params(const sr3_ctx *c, const ConvCall &k) {
     const ConvRef &cv = *k.conv;
     const TDesc &a = k.in, &out = k.out;
     const int B = k.B;
@@ -773,6 +784,28 @@ void run_conv(sr3_ctx *c, const ConvCall &k) {
         p.in2 = k.in2;
         p.w2 = k.ident_w;
     }
+    p.u_ready = k.u_ready ? 1 : 0;
+    return p;
+}
+
+// SR3_NO_GN_WINO=1 (product switch, read once): the parent's two passes in front of every three-pass Winograd conv
+bool gn_wino_off() {
+    static const bool off = env_int("SR3_NO_GN_WINO", 0) != 0;
+    return off;
+}
+
+// Does the GroupNorm apply pass in front of conv k write the conv's Winograd input transform (into c->wino_ws) instead
+// of k.in? Where the conv's plan is the three-pass form, in f32 with unsplit inputs and no raw side output wanted.
+bool gn_writes_u(const sr3_ctx *c, const ConvCall &k, bool raw_wanted, int in_split) {
+    if (gn_wino_off() || c->split() || raw_wanted || in_split) return false;
+    return conv_plan(conv_params(c, k)).kernel == CK_WINO_THREE_PASS;
+}
+
+void run_conv(sr3_ctx *c, const ConvCall &k) {
+    const ConvRef &cv = *k.conv;
+    const TDesc &a = k.in, &out = k.out;
+    const int B = k.B;
+    const ConvParams p = conv_params(c, k);
     c->pbegin(F_CONV);
     launch_conv(p, c->stream);
     if (c->prof) {
@@ -809,15 +842,18 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     // (conv2's fused 1x1 K-steps read x / skip — or the raw concatenation — in 32-channel chunks of the plain split format)
     const bool fused_ok = !rb.has_res || (direct ? ((xr.C % 32) == 0 && (!skip.p || (skr.C % 32) == 0)) : (rb.cin % 32) == 0);
     const bool f8a = f8_conv(c, rb.c1, B, h, w), f8b = fused_ok && f8_conv(c, rb.c2, B, h, w);
-    run_gn_act(c, x_so ? xr : x, (skip.p && sk_so) ? skr : skip, rb.gn1, B, 2, m.act1, sx, ss,
-               rb.has_res && !direct ? m.raw1 : kNone, (x_so ? 1 : 0) | (skip.p && sk_so ? 2 : 0), f8a);
-    // block1's conv + FeatureWiseAffine bias writes the fp32 h1, then block2's GroupNorm + Swish as the apply pass over it
+    // (each conv's plan is asked before its GroupNorm pass runs: the pass writes U for a three-pass Winograd conv)
     ConvCall k1;
     k1.in = m.act1; k1.conv = &rb.c1; k1.B = B; k1.activated = true; k1.f8 = f8a;
     k1.chan_bias = c->cbias + rb.nf_off;
     k1.out = m.h1; k1.stats = m.st_h1;
+    const bool raw1 = rb.has_res && !direct;
+    const int in_split1 = (x_so ? 1 : 0) | (skip.p && sk_so ? 2 : 0);
+    k1.u_ready = gn_writes_u(c, k1, raw1, in_split1);
+    run_gn_act(c, x_so ? xr : x, (skip.p && sk_so) ? skr : skip, rb.gn1, B, 2, m.act1, sx, ss, raw1 ? m.raw1 : kNone, in_split1,
+               f8a, k1.u_ready ? c->wino_ws : nullptr);
+    // block1's conv + FeatureWiseAffine bias writes the fp32 h1, then block2's GroupNorm + Swish as the apply pass over it
     run_conv(c, k1);
-    run_gn_act(c, m.h1, kNone, rb.gn2, B, 2, m.act2, m.st_h1, StatsRef(), TDesc(), 0, f8b);
     // block2 + skip path in one launch: conv3x3(act2) [+ res_conv 1x1 (raw x ‖ skip) as extra
     // K-steps | + x as residual when the block keeps its width]
     ConvCall k2;
@@ -832,6 +868,8 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     } else {
         k2.resid = x_so ? xr : x; k2.resid_split = x_so;
     }
+    k2.u_ready = gn_writes_u(c, k2, false, 0);
+    run_gn_act(c, m.h1, kNone, rb.gn2, B, 2, m.act2, m.st_h1, StatsRef(), TDesc(), 0, f8b, k2.u_ready ? c->wino_ws : nullptr);
     run_conv(c, k2);
     if (rb.attn) {
         run_gn_act(c, m.rb_out, kNone, rb.agn, B, 1, m.act2, m.st_rb, StatsRef());
@@ -1382,6 +1420,8 @@ struct ScratchConv {
         p.ovf = c->d_ovf;            // (range bits of twin stores and the 'wait gave up' bit of the in-place split-K)
         return 0;
     }
+    // the engine's rule (gn_writes_u of the UNet's convs): the apply pass in front of this conv writes U into wino_ws
+    bool gn_writes_u(const sr3_ctx *c) const { return !gn_wino_off() && !c->split() && plan.kernel == CK_WINO_THREE_PASS; }
 };
 
 } // namespace
@@ -1943,6 +1983,7 @@ int sr3_set_range_policy(sr3_ctx *c, int strict) {
     return 0;
 }
 int sr3_fallback_calls(sr3_ctx *c) { return c ? c->fallback_calls : fail("null context"); }
+int sr3_gn_wino_passes(sr3_ctx *c) { return c ? c->gn_wino_passes : fail("null context"); }
 int sr3_replay_calls(sr3_ctx *c) { return c ? c->replay_calls : fail("null context"); }
 void *sr3_test_flag_address(sr3_ctx *c) { return c ? c->d_ovf : nullptr; }
 const char *sr3_last_warning(void) { return g_warn.c_str(); }
@@ -2013,15 +2054,23 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     p.bias = bias.p; p.chan_bias = chan_bias_dev; p.chan_bias_stride = Cout;
     p.out = unpadded(out_dev, Cout, p.Hout, p.Wout);
     if (resid_dev) p.resid = unpadded(const_cast<float *>(resid_dev), Cout, p.Hout, p.Wout);
-    // the engine's own sequence: (GroupNorm apply | copy) + concat into a zero-bordered tensor, then conv
-    HIP_OK(hipMemsetAsync(p.in0.p, 0, p.in0.floats(B) * sizeof(float), c->stream));
+    // the engine's own sequence: (GroupNorm apply | copy) + concat into a zero-bordered tensor, then conv; in front of a
+    // three-pass Winograd conv the pass writes the transformed input instead (nothing reads p.in0 then)
+    const bool to_u = sc.gn_writes_u(c);
+    if (!to_u) HIP_OK(hipMemsetAsync(p.in0.p, 0, p.in0.floats(B) * sizeof(float), c->stream));
     const TDesc i0 = unpadded(const_cast<float *>(in0_dev), C0, Hin, Win);
     const TDesc i1 = in1_dev ? unpadded(const_cast<float *>(in1_dev), C1, Hin, Win) : kNone;
     // (this entry point owns its inputs: an in-place split-K wait that gave up is answered by running the pass and the
     // conv again on the non-waiting path, as sr3_unet_forward / sr3_sample do; it never leaves the arithmetic it was asked for)
     return guarded_eval(c, "sr3_op_conv2d", "the conv", false, [&]() -> int {
-        launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, gn_scale_dev ? (swish ? 2 : 1) : 0, c->act_format(sc.f8), p.in0,
-                        c->stream, TDesc(), 0, c->d_ovf);
+        const int mode = gn_scale_dev ? (swish ? 2 : 1) : 0;
+        if (to_u) {
+            launch_gn_wino_input(i0, i1, B, gn_scale_dev, gn_shift_dev, mode, p.wino_ws, c->stream);
+            ++c->gn_wino_passes;
+        } else {
+            launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, mode, c->act_format(sc.f8), p.in0, c->stream, TDesc(), 0, c->d_ovf);
+        }
+        p.u_ready = to_u ? 1 : 0;
         p.no_halo_split = c->halo_split_off ? 1 : 0;
         launch_conv(p, c->stream);
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("sr3_op_conv2d: launch failed");
@@ -2061,11 +2110,17 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     p.out = out;
     hipEvent_t e0, e1, e2;
     HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1)); HIP_OK(hipEventCreate(&e2));
+    // as the engine runs the shape: behind the fused pass the conv starts from U (random contents like every input here)
+    const bool to_u = sc.gn_writes_u(c);
+    if (to_u) { fill_random(c, p.wino_ws, (size_t)16 * B * (Hin / 2) * (Win / 2) * Cin, 11); p.u_ready = 1; }
     for (int i = 0; i < 2; ++i) launch_conv(p, c->stream);
     HIP_OK(hipEventRecord(e0, c->stream));
     for (int i = 0; i < iters; ++i) launch_conv(p, c->stream);
     HIP_OK(hipEventRecord(e1, c->stream));
-    for (int i = 0; i < iters; ++i) launch_gn_apply(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, c->act_format(sc.f8), p.in0, c->stream);
+    for (int i = 0; i < iters; ++i) {
+        if (to_u) launch_gn_wino_input(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, p.wino_ws, c->stream);
+        else launch_gn_apply(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, c->act_format(sc.f8), p.in0, c->stream);
+    }
     HIP_OK(hipEventRecord(e2, c->stream));
     HIP_OK(hipEventSynchronize(e2));
     float ms = 0.f;

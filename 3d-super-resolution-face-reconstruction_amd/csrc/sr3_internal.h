@@ -8,13 +8,15 @@
 namespace sr3 {
 
 // ---- environment switches ---------------------------------------------------------------------------
-// Everything the library reads from the environment (INTEGRATION.md lists the same five; each is read once per process
+// Everything the library reads from the environment (INTEGRATION.md lists the same six; each is read once per process
 // and then baked into captured graphs):
 //   SR3_NO_GRAPH=1          every kernel launched individually, no hipGraph replay (hosts that cannot capture)
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
 //   SR3_HALO_SPLITS=0|2|4   in-place split-K of deep-K convs on 128x128 x-halo tiles: off / forced
 //   SR3_NO_INPLACE_SPLIT=1  split-K always as conv + reduce kernel
 //   SR3_NO_WINOGRAD=1       exact-f32 3x3 convs always on the direct implicit-GEMM kernel (conv_plan)
+//   SR3_NO_GN_WINO=1        three-pass Winograd convs always behind gn_apply + wino_input_kernel: the GroupNorm apply
+//                           pass never writes the transformed input itself (no conv-plan switch: every plan stays)
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Activation tensor: NHWC fp32 with an optional 1-pixel zero border ("pad") stored around every
@@ -115,6 +117,9 @@ struct ConvParams {
     // the one-pass kernel's copy of w_wino in fragment-major order [16][CinPad/8][Cout][8] (make_wino_weights_frag);
     // null: a conv of the one-pass shapes runs on the direct kernel
     const float *w_wino_f = nullptr;
+    // 1 (CK_WINO_THREE_PASS only): U of in0 || in1 is already at the head of wino_ws (launch_gn_wino_input wrote it);
+    // launch_conv_wino then skips wino_input_kernel and does nothing else differently. No input of conv_plan.
+    int u_ready = 0;
     // GEMM batch (launch_wino_gemm only): blockIdx.z = z multiplies in0.p + z * batch_in_stride by
     // w + z * phase_w_stride into out.p + z * batch_out_stride
     int zbatch = 1;
@@ -261,6 +266,14 @@ void launch_gn_apply_rows(const TDesc &in0, const TDesc &in1, int B, const float
 void launch_gn_fold_apply(const TDesc &in0, const TDesc &in1, int B, const StatsRef &s0, const StatsRef &s1, int groups,
                           const float *gamma, const float *beta, float eps, int mode, int split, const TDesc &out,
                           hipStream_t s, const TDesc &raw = TDesc(), int in_split = 0, int *ovf = nullptr);
+// The apply pass in front of a three-pass Winograd conv (exact f32, unsplit inputs): activates in0 || in1 as
+// launch_gn_apply / launch_gn_fold_apply do and writes, instead of the zero-bordered tensor, its Winograd input
+// transform U [16][B*H/2*W/2][C] — bit for bit what wino_input_kernel makes of that tensor (ConvParams::u_ready).
+// in0 / in1 padded or not; H, W even; C multiples of 4 on both sides of the concatenation.
+void launch_gn_wino_input(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift, int mode,
+                          float *U, hipStream_t s);
+void launch_gn_fold_wino_input(const TDesc &in0, const TDesc &in1, int B, const StatsRef &s0, const StatsRef &s1, int groups,
+                               const float *gamma, const float *beta, float eps, int mode, float *U, hipStream_t s);
 StatsRef launch_groupnorm_partials(const TDesc &in0, const TDesc &in1, int B, float *part, hipStream_t s);
 // common power-of-two scale for several weight tensors: returns k with max|w| * 2^k in [1024, 2048)
 int split_scale_exponent(const float *packed, size_t n);

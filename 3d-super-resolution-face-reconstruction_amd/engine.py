@@ -142,6 +142,11 @@ class Engine:
     def fallback_calls(self) -> int:
         return int(self.lib.sr3_fallback_calls(self.ctx))
 
+    def gn_wino_passes(self) -> int:
+        """GroupNorm apply passes launched (or captured into a graph) in the form that writes the Winograd input transform of
+        the conv behind them, since the engine was created; 0 under SR3_NO_GN_WINO=1 and outside the f32 mode."""
+        return int(self.lib.sr3_gn_wino_passes(self.ctx))
+
     def replay_calls(self) -> int:
         """Calls finished after replaying work whose in-place split-K wait had given up (SR3_OK_REPLAYED)."""
         return int(self.lib.sr3_replay_calls(self.ctx))

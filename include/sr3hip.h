@@ -202,6 +202,9 @@ int sr3_range_check(sr3_ctx *ctx);
 int sr3_set_range_policy(sr3_ctx *ctx, int strict);
 int sr3_fallback_calls(sr3_ctx *ctx);
 int sr3_replay_calls(sr3_ctx *ctx);
+/* GroupNorm apply passes launched (or captured into a graph) since sr3_create in the form that writes the Winograd input
+ * transform of the three-pass conv behind them (exact f32 only; 0 under SR3_NO_GN_WINO=1): tells a test which route ran. */
+int sr3_gn_wino_passes(sr3_ctx *ctx);
 /* TEST HOOK (tests/test_gpu_round4.py): device address of the context's flag word (bit 0: range overflow, bit 1: an
  * in-place split-K wait gave up), so that a test kernel on another stream can raise a bit in the middle of a running
  * sr3_sample call and the replay logic is exercised deterministically. Not for production use. */
@@ -227,7 +230,8 @@ int sr3_profile_dump_csv(sr3_ctx *ctx, const char *path);
 
 /* Kernel micro-benchmark: average ms of `iters` launches of one conv shape on scratch buffers
  * and, in *apply_ms, of the
- * GroupNorm apply pass that precedes it (mode 0 copy, 1 affine, 2 affine + Swish). */
+ * GroupNorm apply pass that precedes it (mode 0 copy, 1 affine, 2 affine + Swish), as the engine runs the shape: in front
+ * of a three-pass Winograd conv the pass writes the transformed input and the conv starts from it. */
 int sr3_bench_conv(sr3_ctx *ctx, int B, int Hin, int Win, int C0, int C1, int Cout, int ks, int stride,
                    int up2, int mode, int with_resid, int with_chan_bias, int iters, float *avg_ms,
                    float *apply_ms);
