@@ -85,6 +85,11 @@ PROTOTYPES = {
     "sr3_test_flag_address": (_P, [_P]),
     "sr3_last_warning": (C.c_char_p, []),
     "sr3_philox_normal": (_I, [_P, _U64, _U64, C.c_uint32, _I, _F]),
+    "sr3_set_dropout": (_I, [_P, _I, _U64, _U64]),
+    "sr3_set_dropout_masks": (_I, [_P, _P, _U64]),
+    "sr3_dropout_layers": (_I, [_P, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "sr3_dropout_mask_bytes": (C.c_int64, [_P, _I, _I, _I]),
+    "sr3_op_dropout_mask": (_I, [_P, _U64, _U64, C.c_uint32, _I, _I, _I, _I, _P]),
     "sr3_profile_enable": (_I, [_P, _I]),
     "sr3_profile_reset": (_I, [_P]),
     "sr3_profile_get": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -112,8 +117,9 @@ PROTOTYPES = {
     "sr3_device_bytes": (_U64, [_P]),
 }
 
-# counters added to the C-ABI after its first A/B-able build (load)
-NEWER_COUNTERS = ("sr3_gn_wino_passes",)
+# counters and opt-in entry points added to the C-ABI after its first A/B-able build (load)
+NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_set_dropout", "sr3_set_dropout_masks", "sr3_dropout_layers",
+                  "sr3_dropout_mask_bytes", "sr3_op_dropout_mask")
 
 _lib = None
 
@@ -134,7 +140,8 @@ def load() -> C.CDLL:
         try:
             fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
         except AttributeError:
-            # an A/B against an older build of the C-ABI (SR3_LIB): its later counters are missing, nothing it computes is
+            # an A/B against an older build of the C-ABI (SR3_LIB): its later counters and the opt-in dropout entry points
+            # are missing, nothing it computes by default is
             if name in NEWER_COUNTERS and os.environ.get("SR3_LIB"):
                 continue
             raise

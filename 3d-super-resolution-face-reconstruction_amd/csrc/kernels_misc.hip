@@ -390,13 +390,16 @@ __device__ __forceinline__ void gn_scale_shift_to_lds(const float *__restrict__ 
 // GroupNorm FINALIZE into the pass (it used to be a launch of its own in front of every apply;
 // gn_scale_shift_to_lds). MODE 0 copy, 1 affine, 2 affine + Swish; scale/shift != null: take them
 // from memory instead.
-template <int MODE, int SPLIT>
-__global__ __launch_bounds__(GA_T) void gn_apply_kernel(const TDesc in0, const TDesc in1,
-                                                         const float *__restrict__ scale,
-                                                         const float *__restrict__ shift, const GnFold st,
-                                                         const TDesc out, const TDesc raw, const int in_split,
-                                                         int *ovf, const int ppb) {
+// DROP 1 (MODE 2; gn_apply_drop_kernel): the Dropout mask of ResnetBlock.block2 (unet.py:81-91) multiplies the 8 activated
+// values in registers between swish_fast and store8 (dropout_apply8; `raw` is never masked); DROP 0 is gn_apply_kernel.
+template <int MODE, int SPLIT, int DROP>
+__device__ __forceinline__ void gn_apply_body(const TDesc &in0, const TDesc &in1, const float *__restrict__ scale,
+                                              const float *__restrict__ shift, const GnFold &st, const TDesc &out,
+                                              const TDesc &raw, const int in_split, int *ovf, const int ppb,
+                                              const DropLayer &dl) {
     extern __shared__ __attribute__((aligned(16))) float ga_smem[];
+    DropArgs da;
+    if (DROP) da = *dl.a;
     const int C0 = in0.C, C = out.C, C8 = C >> 3;
     const int n = blockIdx.y, t = threadIdx.x;
     float *sc = ga_smem, *sh = ga_smem + C;             // [C] each
@@ -459,6 +462,7 @@ __global__ __launch_bounds__(GA_T) void gn_apply_kernel(const TDesc in0, const T
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = swish_fast(f[j]);
             }
+            if (DROP) dropout_apply8(da, dl, n, y, x, c, C, out.H, W, f);
             store8<SPLIT>(out.p + out.pix(n, y, x) * C, c, f, absmax);
         };
         int pix = pix0 + pl;
@@ -481,6 +485,24 @@ __global__ __launch_bounds__(GA_T) void gn_apply_kernel(const TDesc in0, const T
     if (SPLIT && ovf != nullptr && (absmax > (SPLIT == 2 ? SPLIT_F8_MAX : SPLIT_F16_MAX) || absmax_raw > SPLIT_F16_MAX)) *ovf = 1;
 }
 
+template <int MODE, int SPLIT>
+__global__ __launch_bounds__(GA_T) void gn_apply_kernel(const TDesc in0, const TDesc in1,
+                                                         const float *__restrict__ scale,
+                                                         const float *__restrict__ shift, const GnFold st,
+                                                         const TDesc out, const TDesc raw, const int in_split,
+                                                         int *ovf, const int ppb) {
+    gn_apply_body<MODE, SPLIT, 0>(in0, in1, scale, shift, st, out, raw, in_split, ovf, ppb, DropLayer());
+}
+
+template <int SPLIT>
+__global__ __launch_bounds__(GA_T) void gn_apply_drop_kernel(const TDesc in0, const TDesc in1,
+                                                              const float *__restrict__ scale,
+                                                              const float *__restrict__ shift, const GnFold st,
+                                                              const TDesc out, const TDesc raw, const int in_split,
+                                                              int *ovf, const int ppb, const DropLayer dl) {
+    gn_apply_body<2, SPLIT, 1>(in0, in1, scale, shift, st, out, raw, in_split, ovf, ppb, dl);
+}
+
 } // namespace
 
 namespace {
@@ -490,11 +512,20 @@ namespace {
 // for the separate finalize launch; the folded form wins wherever a launch is latency bound.
 // NR = 2: two rows per thread (y and y + H/2), both loads in flight before either is used: +1.4 % on the pass
 // (A/B on one box; nontemporal loads of the input measured 8 % slower)
-template <int MODE, int SPLIT, int NR>
+// DROP 1 (MODE 2): as in gn_apply_body; the mask's launch argument exists only in those instantiations (DropArg)
+struct NoDrop {};
+template <int DROP> struct DropArg { typedef NoDrop type; };
+template <> struct DropArg<1> { typedef DropLayer type; };
+__device__ __forceinline__ void dropout_rows8(const NoDrop &, int, int, int, int, int, int, int, float (&)[8]) {}
+__device__ __forceinline__ void dropout_rows8(const DropLayer &dl, int n, int y, int x, int c, int C, int H, int W, float (&f)[8]) {
+    dropout_apply8(*dl.a, dl, n, y, x, c, C, H, W, f);
+}
+template <int MODE, int SPLIT, int NR, int DROP = 0>
 __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const TDesc in0, const TDesc in1,
                                                             const float *__restrict__ scale,
                                                             const float *__restrict__ shift, const TDesc out,
-                                                            const TDesc raw, const int in_split, int *ovf) {
+                                                            const TDesc raw, const int in_split, int *ovf,
+                                                            const typename DropArg<DROP>::type dl) {
     // grid: x = chunks of (pixel-in-row, channel octet), y = n * (H / NR) + row
     const int C0 = in0.C, C = out.C, C8 = C >> 3;
     const int Hh = out.H / NR;
@@ -551,6 +582,7 @@ __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const TDesc in0, con
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = swish_fast(f[j]);
         }
+        if (DROP) dropout_rows8(dl, n, y, x, c, C, out.H, out.W, f);
         store8<SPLIT>(out.p + out.pix(n, y, x) * C, c, f, absmax);
     }
     if (SPLIT && ovf != nullptr && (absmax > (SPLIT == 2 ? SPLIT_F8_MAX : SPLIT_F16_MAX) || absmax_raw > SPLIT_F16_MAX)) *ovf = 1;
@@ -646,14 +678,25 @@ __global__ __launch_bounds__(GA_T) void gn_wino_input_kernel(const TDesc in0, co
 } // namespace
 
 void launch_gn_apply_rows(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
-                          int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw, int in_split, int *ovf) {
+                          int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw, int in_split, int *ovf,
+                          const DropLayer &drop) {
     const int items = out.W * (out.C >> 3);
     const int nr = (out.H % 2) == 0 ? 2 : 1;
     const dim3 grid((items + 255) / 256, B * out.H / nr);
+    if (drop.a != nullptr) {            // (the callers mask block2's input only: affine + Swish)
+#define SR3_GRD(S)                                                                                                 \
+    {                                                                                                              \
+        if (nr == 2) hipLaunchKernelGGL((gn_apply_rows_kernel<2, S, 2, 1>), grid, dim3(256), 0, s, in0, in1, scale, shift, out, raw, in_split, ovf, drop); \
+        else hipLaunchKernelGGL((gn_apply_rows_kernel<2, S, 1, 1>), grid, dim3(256), 0, s, in0, in1, scale, shift, out, raw, in_split, ovf, drop);         \
+    }
+        if (split == 2) SR3_GRD(2) else if (split) SR3_GRD(1) else SR3_GRD(0)
+#undef SR3_GRD
+        return;
+    }
 #define SR3_GR(M, S)                                                                                               \
     {                                                                                                              \
-        if (nr == 2) hipLaunchKernelGGL((gn_apply_rows_kernel<M, S, 2>), grid, dim3(256), 0, s, in0, in1, scale, shift, out, raw, in_split, ovf); \
-        else hipLaunchKernelGGL((gn_apply_rows_kernel<M, S, 1>), grid, dim3(256), 0, s, in0, in1, scale, shift, out, raw, in_split, ovf);         \
+        if (nr == 2) hipLaunchKernelGGL((gn_apply_rows_kernel<M, S, 2>), grid, dim3(256), 0, s, in0, in1, scale, shift, out, raw, in_split, ovf, NoDrop()); \
+        else hipLaunchKernelGGL((gn_apply_rows_kernel<M, S, 1>), grid, dim3(256), 0, s, in0, in1, scale, shift, out, raw, in_split, ovf, NoDrop());         \
     }
     if (split == 2) {
         if (mode == 0) SR3_GR(0, 2) else if (mode == 1) SR3_GR(1, 2) else SR3_GR(2, 2)
@@ -685,11 +728,27 @@ static size_t ga_lds_bytes(int mode, int C, bool from_memory, int groups) {
 
 static void launch_gn_apply_impl(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
                                  const GnFold &st, int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw,
-                                 int in_split, int *ovf) {
+                                 int in_split, int *ovf, const DropLayer &drop) {
     const int HW = out.H * out.W, C = out.C;
     const int ppb = ga_pixels_per_block(B, HW, C >> 3);
     const dim3 grid((HW + ppb - 1) / ppb, B);
     const size_t lds = ga_lds_bytes(mode, C, scale != nullptr, st.groups);
+    if (drop.a != nullptr) {            // (the callers mask block2's input only: affine + Swish)
+#define SR3_GAD(S)                                                                                                 \
+    {                                                                                                              \
+        static size_t attr = 48 * 1024;                                                                            \
+        if (lds > attr) {                                                                                          \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gn_apply_drop_kernel<S>),                     \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
+            attr = lds;                                                                                            \
+        }                                                                                                          \
+        hipLaunchKernelGGL((gn_apply_drop_kernel<S>), grid, dim3(GA_T), lds, s, in0, in1, scale, shift, st, out, raw, \
+                           in_split, ovf, ppb, drop);                                                              \
+    }
+        if (split == 2) SR3_GAD(2) else if (split) SR3_GAD(1) else SR3_GAD(0)
+#undef SR3_GAD
+        return;
+    }
 #define SR3_GA(M, S)                                                                                               \
     {                                                                                                              \
         static size_t attr = 48 * 1024;                                                                            \
@@ -712,8 +771,9 @@ static void launch_gn_apply_impl(const TDesc &in0, const TDesc &in1, int B, cons
 }
 
 void launch_gn_apply(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
-                     int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw, int in_split, int *ovf) {
-    launch_gn_apply_impl(in0, in1, B, scale, shift, GnFold(), mode, split, out, s, raw, in_split, ovf);
+                     int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw, int in_split, int *ovf,
+                     const DropLayer &drop) {
+    launch_gn_apply_impl(in0, in1, B, scale, shift, GnFold(), mode, split, out, s, raw, in_split, ovf, drop);
 }
 
 static GnFold gn_fold_of(const TDesc &in0, const TDesc &in1, const StatsRef &s0, const StatsRef &s1, int groups,
@@ -729,9 +789,9 @@ static GnFold gn_fold_of(const TDesc &in0, const TDesc &in1, const StatsRef &s0,
 // GroupNorm (statistics already accumulated as partials) + affine (+ Swish) (+ concat) in ONE launch
 void launch_gn_fold_apply(const TDesc &in0, const TDesc &in1, int B, const StatsRef &s0, const StatsRef &s1, int groups,
                           const float *gamma, const float *beta, float eps, int mode, int split, const TDesc &out,
-                          hipStream_t s, const TDesc &raw, int in_split, int *ovf) {
+                          hipStream_t s, const TDesc &raw, int in_split, int *ovf, const DropLayer &drop) {
     launch_gn_apply_impl(in0, in1, B, nullptr, nullptr, gn_fold_of(in0, in1, s0, s1, groups, gamma, beta, eps), mode, split,
-                         out, s, raw, in_split, ovf);
+                         out, s, raw, in_split, ovf, drop);
 }
 
 static void launch_gn_wino_impl(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
@@ -1610,6 +1670,17 @@ __global__ void philox_normal_kernel(uint64_t seed, uint64_t image, uint32_t dra
     if (i < n) out[i] = philox_normal(seed, image, draw, (uint32_t)i);
 }
 
+// one thread = one octet of the layer: the mask stream exactly as dropout_apply8 evaluates it, as bytes [C][H][W]
+__global__ void dropout_mask_kernel(uint64_t seed, uint64_t image, uint32_t c1, uint32_t thr, int C, int H, int W, uint8_t *out) {
+    const uint32_t octet = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t C8 = (uint32_t)C >> 3;
+    if (octet >= (uint32_t)H * W * C8) return;
+    const uint32_t pix = octet / C8, c = (octet - pix * C8) << 3;
+    uint32_t field[8];
+    dropout_fields8(seed, image, c1, octet, field);
+    for (int j = 0; j < 8; ++j) out[(size_t)(c + j) * H * W + pix] = field[j] >= thr ? 1 : 0;
+}
+
 __global__ void init_state_kernel(const TDesc state, int xoff, int C, const float *noise, uint64_t seed,
                                   uint64_t image_offset, size_t total) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // over B*C*HW, NCHW order
@@ -1695,6 +1766,12 @@ void launch_philox_normal(uint64_t seed, uint64_t image, uint32_t draw, int n, f
                           hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(philox_normal_kernel, dim3(nblk(n)), dim3(256), 0, s, seed, image, draw, n, out);
+}
+void launch_dropout_mask(uint64_t seed, uint64_t image, uint32_t draw, int layer, uint32_t thr, int C, int H, int W,
+                         uint8_t *out, hipStream_t s) {
+    const size_t octets = (size_t)H * W * (C >> 3);
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(nblk(octets)), dim3(256), 0, s, seed, image, ((uint32_t)(layer + 1) << 24) | draw,
+                       thr, C, H, W, out);
 }
 
 } // namespace sr3

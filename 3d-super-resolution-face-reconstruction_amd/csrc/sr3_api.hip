@@ -168,6 +168,19 @@ struct sr3_ctx {
     bool halo_split_off = false;
     int replay_calls = 0;               // calls (or segments) replayed for that reason since sr3_create
 
+    // Train-mode Dropout of every ResnetBlock.block2 (unet.py:81-91; sr3_set_dropout). Off by default; p is
+    // latched from cfg.dropout by the setter. drop_live(): the block2 apply passes launch their masked instantiations.
+    bool drop_on = false;
+    uint64_t drop_seed = 0, drop_offset = 0;    // drop_offset: image offset of sr3_unet_forward (the other entry points take one)
+    uint32_t drop_thr = 0;                      // round-half-even(p * 65536)
+    float drop_s = 1.0f;                        // float32(1.0 / (1.0 - p))
+    const uint8_t *drop_masks = nullptr;        // injected masks (sr3_set_dropout_masks) or null -> Philox
+    uint64_t drop_mask_bytes = 0;
+    int n_res = 0;                              // ResnetBlocks = Dropout layers (build_graph)
+    int drop_layer = 0;                         // run_unet_body's cursor: ordinal of the next ResnetBlock ...
+    uint64_t drop_base = 0;                     // ... and its offset in the injected buffer
+    bool drop_live() const { return drop_on && drop_thr > 0; }
+
     // workspace for one (B, H, W)
     int wB = 0, wH = 0, wW = 0;
     char *arena = nullptr;
@@ -290,6 +303,7 @@ bool ident_eligible(const ResBlock &rb) { return !rb.has_res && rb.cout <= 128 &
 Module make_res(sr3_ctx *c, const std::string &prefix, int cin, int cout, bool attn) {
     Module m;
     m.kind = M_RES;
+    ++c->n_res;
     ResBlock &rb = m.rb;
     rb.cin = cin; rb.cout = cout; rb.attn = attn;
     const int inner = c->cfg.inner_channel;
@@ -694,7 +708,7 @@ const TDesc kNone{};
 // finalize + streaming form is the same either way, so no pass gains or loses a finalize launch
 void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int B, int mode, const TDesc &act,
                 const StatsRef &sa, const StatsRef &sb, const TDesc &raw = TDesc(), int in_split = 0, bool f8 = false,
-                float *U = nullptr) {
+                float *U = nullptr, const DropLayer &drop = DropLayer()) {
     const int fmt = c->act_format(f8);
     if (U) ++c->gn_wino_passes;
     c->pbegin(F_GN);
@@ -712,19 +726,19 @@ void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int 
         launch_groupnorm_finalize(sa, a.C, sb, b.p ? b.C : 0, B, a.H * a.W, c->cfg.norm_groups, gamma, beta, 1e-5f,
                                   c->gscale, c->gshift, c->stream);
         if (U) launch_gn_wino_input(a, b, B, c->gscale, c->gshift, mode, U, c->stream);
-        else launch_gn_apply_rows(a, b, B, c->gscale, c->gshift, mode, fmt, act, c->stream, raw, in_split, c->d_ovf);
+        else launch_gn_apply_rows(a, b, B, c->gscale, c->gshift, mode, fmt, act, c->stream, raw, in_split, c->d_ovf, drop);
     } else if (sa.p && (!b.p || sb.p)) {
         // statistics came out of the producing convs' epilogues: finalize + apply are ONE launch
         if (U) launch_gn_fold_wino_input(a, b, B, sa, sb, c->cfg.norm_groups, gamma, beta, 1e-5f, mode, U, c->stream);
         else launch_gn_fold_apply(a, b, B, sa, sb, c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream, raw,
-                                  in_split, c->d_ovf);
+                                  in_split, c->d_ovf, drop);
     } else {
         // fallback: streaming statistics kernel over the (fp32) tensors; its partials describe the
         // virtual concatenation as one source of a.C + b.C channels
         const StatsRef sp = launch_groupnorm_partials(a, b, B, c->gpart, c->stream);
         if (U) launch_gn_fold_wino_input(a, b, B, sp, StatsRef(), c->cfg.norm_groups, gamma, beta, 1e-5f, mode, U, c->stream);
         else launch_gn_fold_apply(a, b, B, sp, StatsRef(), c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream,
-                                  raw, in_split, c->d_ovf);
+                                  raw, in_split, c->d_ovf, drop);
     }
     c->pend();
 }
@@ -795,7 +809,8 @@ bool gn_wino_off() {
 }
 
 // Does the GroupNorm apply pass in front of conv k write the conv's Winograd input transform (into c->wino_ws) instead
-// of k.in? Where the conv's plan is the three-pass form, in f32 with unsplit inputs and no raw side output wanted.
+// of k.in? Where the conv's plan is the three-pass form, in f32 with unsplit inputs and no raw side output wanted
+// (raw_wanted also stands for "the pass applies a Dropout mask": only launch_gn_apply* know one).
 bool gn_writes_u(const sr3_ctx *c, const ConvCall &k, bool raw_wanted, int in_split) {
     if (gn_wino_off() || c->split() || raw_wanted || in_split) return false;
     return conv_plan(conv_params(c, k)).kernel == CK_WINO_THREE_PASS;
@@ -868,8 +883,21 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     } else {
         k2.resid = x_so ? xr : x; k2.resid_split = x_so;
     }
-    k2.u_ready = gn_writes_u(c, k2, false, 0);
-    run_gn_act(c, m.h1, kNone, rb.gn2, B, 2, m.act2, m.st_h1, StatsRef(), TDesc(), 0, f8b, k2.u_ready ? c->wino_ws : nullptr);
+    // train-mode Dropout (unet.py:81-91: after block2's Swish, i.e. this pass's output): the masked instantiation of the
+    // apply pass. A three-pass Winograd conv then runs behind the masked two-pass apply (gn_wino_input_kernel sees every
+    // window pixel in up to four tiles and knows no mask): gn_writes_u answers no. block1, the attention norm and the
+    // res_conv operand are never masked.
+    DropLayer drop;
+    if (c->drop_live()) {
+        drop.a = &c->d_step->drop;
+        drop.c1_hi = (uint32_t)(c->drop_layer + 1) << 24;
+        drop.base = c->drop_base;
+    }
+    ++c->drop_layer;
+    c->drop_base += (uint64_t)B * rb.cout * h * w;
+    k2.u_ready = gn_writes_u(c, k2, drop.a != nullptr, 0);
+    run_gn_act(c, m.h1, kNone, rb.gn2, B, 2, m.act2, m.st_h1, StatsRef(), TDesc(), 0, f8b, k2.u_ready ? c->wino_ws : nullptr,
+               drop);
     run_conv(c, k2);
     if (rb.attn) {
         run_gn_act(c, m.rb_out, kNone, rb.agn, B, 1, m.act2, m.st_rb, StatsRef());
@@ -903,6 +931,7 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
 // UNet.forward body (unet.py:240-265): consumes c->x0 and c->cbias, leaves eps NHWC in c->eps
 void run_unet_body(sr3_ctx *c, int B, int H, int W) {
     std::vector<int> feats;
+    c->drop_layer = 0; c->drop_base = 0;      // (run_res numbers the Dropout layers in execution order)
     TDesc cur = c->x0, cur_s;         // cur_s: split twin of cur (prec 1), null if none
     bool cur_so = false;              // cur exists only as cur_s
     StatsRef scur;
@@ -1253,6 +1282,70 @@ void drop_graphs(sr3_ctx *c) {
     }
 }
 
+// The per-call arguments kernels read from device memory (StepArgs): a pinned host ring slot, filled by the caller and
+// copied to c->d_step by push_step_args. next_step_slot: null with the error set.
+StepArgs *next_step_slot(sr3_ctx *c) {
+    if (!c->h_ring) {
+        if (hipHostMalloc(reinterpret_cast<void **>(&c->h_ring), sizeof(StepArgs) * sr3_ctx::kRing, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(&c->d_step, sizeof(StepArgs)) != hipSuccess) {
+            fail("allocating the step arguments failed");
+            return nullptr;
+        }
+    }
+    // the host may run far ahead of the GPU: never reuse a ring slot that may still be pending
+    if (c->step_count && (c->step_count % (sr3_ctx::kRing / 2)) == 0 && hipStreamSynchronize(c->stream) != hipSuccess) {
+        fail("hipStreamSynchronize failed");
+        return nullptr;
+    }
+    StepArgs *sa = &c->h_ring[c->step_count % sr3_ctx::kRing];
+    ++c->step_count;
+    *sa = StepArgs();
+    return sa;
+}
+int push_step_args(sr3_ctx *c, const StepArgs *sa) {
+    HIP_OK(hipMemcpyAsync(c->d_step, sa, sizeof(StepArgs), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
+// Dropout layers of the UNet at H x W, in execution order (= the order of the reference's nn.Dropout modules): chw[3*l..]
+// = {C, H, W} of layer l's block2 input (chw may be null); returns the bytes of one image's masks over all layers
+uint64_t dropout_layers(const sr3_ctx *c, int H, int W, int *chw) {
+    uint64_t per_image = 0;
+    int h = H, w = W, l = 0;
+    for (const Module &m : c->mods) {
+        if (m.kind == M_DOWN) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+        else if (m.kind == M_UP) { h *= 2; w *= 2; }
+        if (m.kind != M_RES) continue;
+        if (chw) { chw[3 * l] = m.rb.cout; chw[3 * l + 1] = h; chw[3 * l + 2] = w; }
+        ++l;
+        per_image += (uint64_t)m.rb.cout * h * w;
+    }
+    return per_image;
+}
+
+// the mask stream's arguments of one call (draw: StepArgs::draw in the sampler, 0 elsewhere); the injected buffer must
+// hold exactly the layers of the current workspace
+int fill_drop_args(sr3_ctx *c, const char *what, DropArgs &d, uint32_t draw, uint64_t image_offset) {
+    if (draw >= DROP_MAX_DRAW) return fail("%s: dropout draw index %u does not fit the mask stream's 24 bits", what, draw);
+    if (c->drop_masks) {
+        const uint64_t need = (uint64_t)c->wB * dropout_layers(c, c->wH, c->wW, nullptr);
+        if (c->drop_mask_bytes != need)
+            return fail("%s: the injected dropout masks hold %llu bytes, B=%d H=%d W=%d needs %llu (sr3_dropout_mask_bytes)", what,
+                        (unsigned long long)c->drop_mask_bytes, c->wB, c->wH, c->wW, (unsigned long long)need);
+    }
+    d.seed = c->drop_seed; d.image_offset = image_offset; d.mask = c->drop_masks;
+    d.draw = draw; d.thr = c->drop_thr; d.s = c->drop_s; d.pad_ = 0;
+    return 0;
+}
+// sr3_unet_forward / sr3_denoise_loss with dropout live: the arguments go to the device once, in front of guarded_eval
+// (every repeat of the evaluation reads the same ones)
+int push_drop_args(sr3_ctx *c, const char *what, uint64_t image_offset) {
+    if (!c->drop_live()) return 0;
+    StepArgs *sa = next_step_slot(c);
+    if (!sa || fill_drop_args(c, what, sa->drop, 0, image_offset)) return -1;
+    return push_step_args(c, sa);
+}
+
 // the launches of one p_sample step (embedding, UNet body, DDPM update); every per-step value is
 // read from c->d_step, so the sequence is identical for every t
 void enqueue_step(sr3_ctx *c) {
@@ -1278,14 +1371,9 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     if (t < 0 || t >= c->T) return fail("step t=%d outside schedule of %d steps", t, c->T);
     // (the arithmetic mode may have been switched between steps: the F8C weight copies are made on demand)
     if (prepare_f8(c)) return -1;
-    if (!c->h_ring) {
-        HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&c->h_ring), sizeof(StepArgs) * sr3_ctx::kRing, hipHostMallocDefault));
-        HIP_OK(hipMalloc(&c->d_step, sizeof(StepArgs)));
-    }
-    // the host may run far ahead of the GPU: never reuse a ring slot that may still be pending
-    if (c->step_count && (c->step_count % (sr3_ctx::kRing / 2)) == 0) HIP_OK(hipStreamSynchronize(c->stream));
-    StepArgs &sa = c->h_ring[c->step_count % sr3_ctx::kRing];
-    ++c->step_count;
+    StepArgs *slot = next_step_slot(c);
+    if (!slot) return -1;
+    StepArgs &sa = *slot;
     sa.nl = c->s_nl[t + 1];
     sa.a = c->s_a[t]; sa.b = c->s_b[t]; sa.c1 = c->s_c1[t]; sa.c2 = c->s_c2[t]; sa.c3 = c->s_c3[t];
     sa.sigma = c->s_sig[t];
@@ -1295,7 +1383,9 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     if (c->uses_hist) c->hist_valid = true;
     sa.noise = noise_slab; sa.frame = frame;
     sa.seed = c->seed; sa.image_offset = c->image_offset;
-    HIP_OK(hipMemcpyAsync(c->d_step, &sa, sizeof(StepArgs), hipMemcpyHostToDevice, c->stream));
+    // (the masks of step t are a function of t: a replayed segment draws the same ones)
+    if (c->drop_live() && fill_drop_args(c, "p_sample step", sa.drop, sa.draw, c->image_offset)) return -1;
+    if (push_step_args(c, &sa)) return -1;
 
     const int g = c->graph_slot();
     if (c->prof || c->no_graph) {
@@ -1443,6 +1533,7 @@ int sr3_create(const sr3_unet_cfg *cfg, int device, sr3_ctx **out) {
     if (cfg->n_attn_res < 0 || cfg->n_attn_res > SR3_MAX_ATTN_RES) return fail("n_attn_res out of range");
     if (cfg->in_channel < cfg->out_channel || cfg->out_channel < 1) return fail("in_channel/out_channel invalid");
     if (cfg->res_blocks < 1) return fail("res_blocks must be >= 1");
+    if (!(cfg->dropout >= 0.f) || cfg->dropout >= 1.f) return fail("dropout=%g: must be in [0, 1)", (double)cfg->dropout);
     for (int i = 0; i < cfg->n_mults; ++i)
         if (cfg->channel_mults[i] < 1) return fail("channel_mults[%d] invalid", i);
     int ndev = 0;
@@ -1687,6 +1778,7 @@ int sr3_unet_forward(sr3_ctx *c, const float *x_dev, const float *noise_level_de
     if (!x_dev || !noise_level_dev || !out_dev) return fail("sr3_unet_forward: null pointer");
     if (ensure_workspace(c, B, H, W)) return -1;
     c->sampling = false;
+    if (push_drop_args(c, "sr3_unet_forward", c->drop_offset)) return -1;
     return guarded_eval(c, "sr3_unet_forward", "the forward pass", true,
                         [&] { return unet_forward_once(c, x_dev, noise_level_dev, B, H, W, out_dev); });
 }
@@ -1749,6 +1841,9 @@ int sr3_denoise_loss(sr3_ctx *c, const float *hr_dev, const float *cond_dev, int
     k.nz.noise = noise_dev; k.nz.seed = seed; k.nz.image_offset = image_offset; k.nz.per_source = noise_per_source != 0;
     k.N = N; k.row_offset = row_offset; k.B = B; k.H = H; k.W = W; k.loss_type = loss_type;
     k.per_image = per_image_dev; k.x_noisy_out = x_noisy_out; k.eps_out = eps_out;
+    // (dropout masks follow the batch ROW: with one noise image per source, image_offset does not advance with the rows
+    // of a chunked call, row_offset does)
+    if (push_drop_args(c, "sr3_denoise_loss", image_offset + (noise_per_source ? (uint64_t)row_offset : 0))) return -1;
     return guarded_eval(c, "sr3_denoise_loss", "the loss evaluation", true, [&] { return denoise_loss_once(c, k); });
 }
 
@@ -1929,6 +2024,10 @@ struct Checkpoint {
 int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *noise_dev, uint64_t seed,
                uint64_t image_offset, float *out_dev, float *frames_dev) {
     if (!out_dev) return fail("sr3_sample: out_dev is null");
+    if (c && c->drop_live() && c->drop_masks)
+        return fail("sr3_sample: injected dropout masks are set, and one buffer cannot hold the masks of every step — drive the "
+                    "loop with sr3_sample_step (each step consumes the buffer set at that moment) or return to the Philox "
+                    "masks with sr3_set_dropout_masks(ctx, NULL, 0)");
     if (sr3_sample_begin(c, cond_dev, B, H, W, noise_dev, seed, image_offset)) return -1;
     const int T = c->T, si = 1 | (T / 10);
     const size_t slab = (size_t)B * c->cfg.out_channel * H * W;
@@ -1992,6 +2091,64 @@ int sr3_philox_normal(sr3_ctx *c, uint64_t seed, uint64_t image, uint32_t draw, 
     if (!c || !out_dev) return fail("sr3_philox_normal: null argument");
     HIP_OK(hipSetDevice(c->device));
     launch_philox_normal(seed, image, draw, n, out_dev, c->stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- train-mode Dropout (unet.py:81-91) ---------------------------------------------------------
+int sr3_set_dropout(sr3_ctx *c, int enable, uint64_t seed, uint64_t image_offset) {
+    if (!c) return fail("null context");
+    const bool was_live = c->drop_live();
+    if (!enable) {
+        c->drop_on = false;
+    } else {
+        const double p = (double)c->cfg.dropout;
+        if (!(p >= 0.0) || p >= 1.0) return fail("sr3_set_dropout: dropout p = %g outside [0, 1)", p);
+        if (c->n_res > DROP_MAX_LAYERS)
+            return fail("sr3_set_dropout: %d ResnetBlocks, the mask stream numbers at most %d layers", c->n_res, DROP_MAX_LAYERS);
+        c->drop_on = true;
+        c->drop_seed = seed; c->drop_offset = image_offset;
+        c->drop_thr = (uint32_t)nearbyint(p * 65536.0);     // round half to even (the default rounding mode)
+        c->drop_s = (float)(1.0 / (1.0 - p));
+    }
+    if (was_live != c->drop_live()) drop_graphs(c);         // the block2 apply passes launch other kernels
+    return 0;
+}
+
+int sr3_set_dropout_masks(sr3_ctx *c, const uint8_t *dev, uint64_t bytes) {
+    if (!c) return fail("null context");
+    if (dev && !bytes) return fail("sr3_set_dropout_masks: empty buffer");
+    c->drop_masks = dev;                    // (read from device memory by the kernels: captured steps stay valid)
+    c->drop_mask_bytes = dev ? bytes : 0;
+    return 0;
+}
+
+int sr3_dropout_layers(sr3_ctx *c, int H, int W, int *n, int *chw) {
+    if (!c || !n) return fail("sr3_dropout_layers: null argument");
+    const int b = max_batch(c, H, W);
+    if (b <= 0) return fail("sr3_dropout_layers: unsupported shape H=%d W=%d", H, W);
+    *n = c->n_res;
+    (void)dropout_layers(c, H, W, chw);
+    return 0;
+}
+
+int64_t sr3_dropout_mask_bytes(sr3_ctx *c, int B, int H, int W) {
+    if (!c) return fail("null context");
+    if (B < 1 || max_batch(c, H, W) <= 0) return fail("sr3_dropout_mask_bytes: unsupported shape B=%d H=%d W=%d", B, H, W);
+    return (int64_t)((uint64_t)B * dropout_layers(c, H, W, nullptr));
+}
+
+int sr3_op_dropout_mask(sr3_ctx *c, uint64_t seed, uint64_t image, uint32_t draw, int layer, int C, int H, int W,
+                        uint8_t *out_dev) {
+    if (!c || !out_dev) return fail("sr3_op_dropout_mask: null argument");
+    if (layer < 0 || layer >= DROP_MAX_LAYERS) return fail("sr3_op_dropout_mask: layer %d outside [0, %d)", layer, DROP_MAX_LAYERS);
+    if (draw >= DROP_MAX_DRAW) return fail("sr3_op_dropout_mask: draw %u does not fit 24 bits", draw);
+    if (C < 8 || (C % 8) || H < 1 || W < 1 || (uint64_t)C / 8 * H * W > 0xffffffffull)
+        return fail("sr3_op_dropout_mask: bad size C=%d H=%d W=%d (C a multiple of 8)", C, H, W);
+    const double p = (double)c->cfg.dropout;
+    if (!(p >= 0.0) || p >= 1.0) return fail("sr3_op_dropout_mask: dropout p = %g outside [0, 1)", p);
+    HIP_OK(hipSetDevice(c->device));
+    launch_dropout_mask(seed, image, draw, layer, (uint32_t)nearbyint(p * 65536.0), C, H, W, out_dev, c->stream);
     HIP_OK(hipGetLastError());
     return 0;
 }

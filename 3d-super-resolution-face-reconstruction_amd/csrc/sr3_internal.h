@@ -233,6 +233,27 @@ void pack_conv_weight(const float *oihw, int Cout, int Cin, int ks, int CinPad, 
 // host helper: fp32 packed weights -> split-f16 layout (same byte size), returns the unscale factor
 float split_conv_weight(const float *packed, size_t rows, int CinPad, float *dst);
 
+// ---- train-mode Dropout of ResnetBlock.block2 (unet.py:81-91) -----------------------------------------
+// What the masked apply passes read from device memory, refreshed like the rest of StepArgs: a captured step keeps its
+// launch arguments. The input of block2's conv is keep ? swish(gn(h1)) * s : 0.
+struct DropArgs {
+    uint64_t seed = 0, image_offset = 0;    // key of the mask stream; global image index = image_offset + n
+    const uint8_t *mask = nullptr;          // injected masks (layers concatenated, each NCHW [B][C][H][W], nonzero = keep) or null -> Philox
+    uint32_t draw = 0;                      // StepArgs::draw in the sampler, 0 in the forward and the loss
+    uint32_t thr = 0;                       // round-half-even(p * 65536): an element is kept iff its 16-bit field >= thr
+    float s = 1.0f;                         // float32(1.0 / (1.0 - p)), the division in double
+    uint32_t pad_ = 0;
+};
+// One masked apply pass (a launch argument, constant per workspace): a == null: no dropout
+struct DropLayer {
+    const DropArgs *a = nullptr;
+    uint32_t c1_hi = 0;                     // (layer + 1) << 24, layer = 0-based ordinal of the ResnetBlock (downs, mid, ups)
+    uint32_t pad_ = 0;
+    uint64_t base = 0;                      // offset of this layer in the injected buffer
+};
+constexpr int DROP_MAX_LAYERS = 254;        // the top byte of counter word c1 is layer + 1 in [1, 255)
+constexpr uint32_t DROP_MAX_DRAW = 1u << 24;
+
 // ---- GroupNorm (kernels_misc.hip) -------------------------------------------------------------
 // statistics over the virtual concatenation in0 ‖ in1 -> folded affine scale/shift [B][C]
 size_t gn_workspace_floats(int B, int c_max);   // c_max = widest normalised tensor
@@ -252,20 +273,23 @@ void launch_groupnorm_finalize(const StatsRef &s0, int C0, const StatsRef &s1, i
 // format (the input of a fused res_conv).
 // in_split: bit 0 / bit 1 = in0 / in1 is itself stored in the split-f16 format (split-only tensors)
 // ovf: range-check flag of the split format (see ConvParams::ovf), may be null
+// drop (drop.a != null; mode 2 only): the Dropout mask of ResnetBlock.block2 multiplies the activated values in registers
+// in front of the store, whatever the format (the range check sees the scaled value); `raw` is never masked
 void launch_gn_apply(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
                      int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw = TDesc(),
-                     int in_split = 0, int *ovf = nullptr);
+                     int in_split = 0, int *ovf = nullptr, const DropLayer &drop = DropLayer());
 // streaming form of the apply pass for large tensors (one item per thread; scale / shift from memory)
 void launch_gn_apply_rows(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift,
                           int mode, int split, const TDesc &out, hipStream_t s, const TDesc &raw = TDesc(),
-                          int in_split = 0, int *ovf = nullptr);
+                          int in_split = 0, int *ovf = nullptr, const DropLayer &drop = DropLayer());
 // GroupNorm finalize folded into the apply pass (one launch per normalised tensor): s0 / s1 are the fp64
 // partial statistics of in0 / in1 (ConvParams::stats layout; from conv epilogues or
 // launch_groupnorm_partials, which returns the virtual concatenation as one source: pass it as s0
 // with s1 empty)
 void launch_gn_fold_apply(const TDesc &in0, const TDesc &in1, int B, const StatsRef &s0, const StatsRef &s1, int groups,
                           const float *gamma, const float *beta, float eps, int mode, int split, const TDesc &out,
-                          hipStream_t s, const TDesc &raw = TDesc(), int in_split = 0, int *ovf = nullptr);
+                          hipStream_t s, const TDesc &raw = TDesc(), int in_split = 0, int *ovf = nullptr,
+                          const DropLayer &drop = DropLayer());
 // The apply pass in front of a three-pass Winograd conv (exact f32, unsplit inputs): activates in0 || in1 as
 // launch_gn_apply / launch_gn_fold_apply do and writes, instead of the zero-bordered tensor, its Winograd input
 // transform U [16][B*H/2*W/2][C] — bit for bit what wino_input_kernel makes of that tensor (ConvParams::u_ready).
@@ -329,6 +353,7 @@ struct StepArgs {
     const float *noise;         // NCHW [B][C][HW] or null -> Philox
     float *frame;               // NCHW [B][C][HW] or null: copy of the updated image
     uint64_t seed, image_offset;
+    DropArgs drop;              // read by the block2 apply passes while dropout is live (DropLayer::a points here)
 };
 struct UpdateParams {
     float *packed = nullptr;   // optional packed split-f16 copy of the state (conv_in_kernel): 16 halfs per padded pixel
@@ -345,6 +370,9 @@ void launch_init_state(const TDesc &state, int xoff, int C, const float *noise, 
                        uint64_t image_offset, int B, hipStream_t s);
 void launch_philox_normal(uint64_t seed, uint64_t image, uint32_t draw, int n, float *out,
                           hipStream_t s);
+// one image's Philox Dropout mask as uint8 [C][H][W] (1 = keep): the stream the masked apply passes evaluate (C % 8 == 0)
+void launch_dropout_mask(uint64_t seed, uint64_t image, uint32_t draw, int layer, uint32_t thr, int C, int H, int W,
+                         uint8_t *out, hipStream_t s);
 
 // ---- Philox normal stream (device functions; the kernels that draw from it: kernels_misc.hip, kernels_loss.hip) ----
 // Philox4x32-10 (Salmon et al. 2011). CPU twin: oracle/philox.py.
@@ -393,6 +421,32 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t image, ui
         const float th = 6.283185307179586f * u2;
         out[2 * pair] = rad * cosf(th);
         out[2 * pair + 1] = rad * sinf(th);
+    }
+}
+
+// ---- Dropout mask stream (same Philox, disjoint counters: c1's top byte is layer + 1 >= 1, the noise stream's draw < 2^24) ----
+// One evaluation serves the 8 consecutive channels c .. c+7 (c a multiple of 8) of pixel (y, x) of a [C][H][W] layer:
+// counter = (octet = (y*W + x)*(C/8) + c/8, (layer+1) << 24 | draw, image_lo, image_hi), key = seed; channel c + j takes
+// the 16-bit field (r[j>>1] >> 16*(j&1)) & 0xffff and is kept iff field >= thr. CPU twin: tests/dropout_ref.py.
+__device__ __forceinline__ void dropout_fields8(uint64_t seed, uint64_t image, uint32_t c1, uint32_t octet, uint32_t field[8]) {
+    uint32_t r[4];
+    philox4x32_10(octet, c1, (uint32_t)image, (uint32_t)(image >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) field[j] = (r[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+}
+// f[j] <- keep ? f[j] * s : 0 for channels c .. c+7 of pixel (y, x) of batch row n (one fp32 multiply, as torch's Dropout)
+__device__ __forceinline__ void dropout_apply8(const DropArgs &a, const DropLayer &L, int n, int y, int x, int c, int C, int H,
+                                               int W, float (&f)[8]) {
+    if (a.mask != nullptr) {
+        const uint8_t *m = a.mask + L.base + (((size_t)n * C + c) * H + y) * W + x;
+        const size_t plane = (size_t)H * W;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = m[j * plane] != 0 ? f[j] * a.s : 0.0f;
+    } else {
+        uint32_t field[8];
+        dropout_fields8(a.seed, a.image_offset + (uint64_t)n, L.c1_hi | a.draw, (uint32_t)(y * W + x) * (uint32_t)(C >> 3) + (uint32_t)(c >> 3), field);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = field[j] >= a.thr ? f[j] * a.s : 0.0f;
     }
 }
 

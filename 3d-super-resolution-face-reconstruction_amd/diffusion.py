@@ -118,6 +118,20 @@ class GaussianDiffusion(nn.Module):
         self._sampler = (kind, None if steps is None or kind == "ddpm" else int(steps), float(eta))
         self._sched_pushed = None
 
+    def set_dropout_sampling(self, on: bool, seed: Optional[int] = None) -> None:
+        """Opt in to sampling the UNet's Dropout as the reference does under .train() (unet.py:81-91; model 3 samples
+        with the SR model in train mode, model/sr3d/model.py:234-249). While on, in train() mode and with cfg.dropout >
+        0, these run with dropout: denoise_fn(x, level), p_losses / forward, p_sample, super_resolution, sample,
+        sample_batch (and what is built on them). A fresh dropout seed comes from torch's generator per call unless
+        `seed` pins it; chunks of one call share the seed and pass their image offset, so masks follow the GLOBAL image
+        index. In eval() dropout is always the identity. DESIGN.md §3.7."""
+        self.denoise_fn.set_dropout_sampling(on, seed)
+
+    def set_dropout_masks(self, masks) -> None:
+        """Injected keep masks (UNet.set_dropout_masks) for p_losses, denoise_fn and p_sample; the whole-loop entry points
+        refuse them (one buffer cannot hold every step's masks)."""
+        self.denoise_fn.set_dropout_masks(masks)
+
     @property
     def num_sampling_steps(self) -> int:
         """S: UNet evaluations of one sampling call (num_timesteps = T for the default "ddpm" sampler)."""
@@ -213,6 +227,7 @@ class GaussianDiffusion(nn.Module):
         if max_chunk is not None:
             limit = max(1, min(limit, int(max_chunk)))
         n_chunks, chunk = self.chunk_plan(B, limit)
+        self.denoise_fn.arm_dropout(eng)            # (one dropout seed per call; the chunks pass their image offset)
         if n_chunks == 1:
             self.denoise_fn.ready()
             eng.sample(x.data_ptr() if x is not None else None, B, H, W, out.data_ptr(),
@@ -300,6 +315,7 @@ class GaussianDiffusion(nn.Module):
             noise = torch.randn_like(x)
         nz = noise.to(torch.float32).contiguous() if (noise is not None and t > 0) else None
         out = torch.empty_like(x)
+        self.denoise_fn.arm_dropout(eng)
 
         def one_step():
             self.denoise_fn.ready()
@@ -375,6 +391,7 @@ class GaussianDiffusion(nn.Module):
         if max_chunk is not None:
             limit = max(1, min(limit, int(max_chunk)))
         n_chunks, chunk = self.chunk_plan(R, limit)
+        self.denoise_fn.arm_dropout(eng)            # (one dropout seed per call; the chunks pass their image offset)
 
         def padded(t, a, b):
             part = t[a:b]
@@ -454,8 +471,9 @@ class GaussianDiffusion(nn.Module):
         reference's own np.random calls (draw_levels), so np.random.seed reproduces the reference's levels. noise: the
         [B,C,H,W] tensor the reference would draw; None draws it on the device from Philox (the sampler's generator,
         not torch.randn) under `seed` (None: a fresh one from torch's generator, as sample_batch draws one), keyed by
-        image_offset + row. Dropout is the identity: in train() mode with dropout > 0 this differs from
-        the reference's stochastic forward, and one UserWarning per object says so.
+        image_offset + row. Dropout is the identity unless set_dropout_sampling(True) opted in: without it,
+        in train() mode with dropout > 0 this differs from the reference's stochastic forward, and one UserWarning per
+        object says so; with it the block2 masks are sampled on the device.
 
         Returns the SUM over the batch — L1Loss / MSELoss(reduction='sum'), callers divide by b*c*h*w themselves — as a
         0-dim fp32 tensor on the input's device; the fp64 per-image sums stay on self.last_loss_per_image. Batches above
@@ -465,7 +483,8 @@ class GaussianDiffusion(nn.Module):
         if sr_out:
             return self.super_resolution(x_in["SR"])
         hr, sr = self._loss_inputs(x_in)
-        if self.training and float(self.denoise_fn.cfg.dropout) > 0 and not getattr(self, "_warned_dropout", False):
+        if (self.training and float(self.denoise_fn.cfg.dropout) > 0 and not self.denoise_fn.dropout_live()
+                and not getattr(self, "_warned_dropout", False)):
             import warnings
             warnings.warn("p_losses in train() mode: the library evaluates the UNet with dropout as the identity "
                           f"(dropout={self.denoise_fn.cfg.dropout} is not sampled); the loss is the eval() loss",

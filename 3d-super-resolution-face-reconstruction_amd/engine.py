@@ -286,6 +286,52 @@ class Engine:
         """Device Philox stream of (seed, image, draw) written to a device buffer (stream-ordered)."""
         _lib.check(self.lib.sr3_philox_normal(self.ctx, seed, image, draw, n, out_ptr))
 
+    # ---- train-mode Dropout (DESIGN.md §3.7) ---------------------------------------------------
+    def set_dropout(self, enable: bool, seed: int = 0, image_offset: int = 0) -> None:
+        """Train-mode Dropout (p = cfg.dropout) in front of every ResnetBlock.block2 conv, as the reference's UNet under
+        .train(); off (the default) is the identity and launches exactly the kernels it always did. `seed` keys the Philox
+        mask stream; `image_offset` is the global index of row 0 for unet_forward (sample / denoise_loss take their own)."""
+        _lib.check(self.lib.sr3_set_dropout(self.ctx, 1 if enable else 0, int(seed) & (2 ** 64 - 1), int(image_offset)))
+
+    def set_dropout_masks(self, masks_ptr: Optional[int], nbytes: int = 0) -> None:
+        """Injected keep masks instead of Philox: one uint8 device buffer, the layers of dropout_layers() concatenated, each
+        [B,C,H,W], nonzero = keep; nbytes must be dropout_mask_bytes(B, H, W). None returns to Philox. The buffer must
+        outlive the calls that read it."""
+        _lib.check(self.lib.sr3_set_dropout_masks(self.ctx, masks_ptr or None, int(nbytes) if masks_ptr else 0))
+
+    def dropout_layers(self, H: int, W: int) -> List[Tuple[int, int, int]]:
+        """(C, H, W) of every Dropout layer (one per ResnetBlock, execution order) for an H x W input."""
+        n = C.c_int()
+        _lib.check(self.lib.sr3_dropout_layers(self.ctx, int(H), int(W), C.byref(n), None))
+        chw = (C.c_int * (3 * n.value))()
+        _lib.check(self.lib.sr3_dropout_layers(self.ctx, int(H), int(W), C.byref(n), chw))
+        return [(chw[3 * i], chw[3 * i + 1], chw[3 * i + 2]) for i in range(n.value)]
+
+    def dropout_mask_bytes(self, B: int, H: int, W: int) -> int:
+        n = int(self.lib.sr3_dropout_mask_bytes(self.ctx, int(B), int(H), int(W)))
+        if n < 0:
+            _lib.check(-1)
+        return n
+
+    def dropout_mask(self, seed: int, image: int, draw: int, layer: int, C_: int, H: int, W: int) -> np.ndarray:
+        """The device's Philox keep mask of one image and layer as uint8 [C,H,W] (CPU twin: tests/dropout_ref.py)."""
+        n = C_ * H * W
+        buf = self.buffer((n + 3) // 4)
+        _lib.check(self.lib.sr3_op_dropout_mask(self.ctx, int(seed) & (2 ** 64 - 1), int(image), int(draw), int(layer), C_, H, W,
+                                                buf.ptr))
+        out = np.empty(n, dtype=np.uint8)
+        _lib.check(self.lib.sr3_synchronize(self.ctx))
+        _lib.check(self.lib.sr3_memcpy_d2h(self.ctx, out.ctypes.data, buf.ptr, n))
+        buf.free()
+        return out.reshape(C_, H, W)
+
+    def upload_bytes(self, a: np.ndarray) -> DeviceBuffer:
+        """A uint8 host array in a library-owned device buffer (injected dropout masks for hosts without torch)."""
+        h = np.ascontiguousarray(a, dtype=np.uint8).ravel()
+        buf = self.buffer((h.size + 3) // 4)
+        _lib.check(self.lib.sr3_memcpy_h2d(self.ctx, buf.ptr, h.ctypes.data, h.size))
+        return buf
+
     # ---- pre-processing ---------------------------------------------------------------------
     def preprocess_bicubic(self, in_ptr: int, B: int, Hin: int, Win: int, Hout: int, Wout: int,
                            out_ptr: int, out_u8_ptr: Optional[int] = None) -> None:

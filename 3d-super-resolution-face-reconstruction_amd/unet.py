@@ -92,6 +92,10 @@ class UNet(nn.Module):
         # split-f16 range policy: False (default) = a call whose activations leave the fp16 range is finished in
         # exact f32 with an `Sr3RangeWarning`; True = it raises `Sr3Error` (sr3_set_range_policy)
         self.strict_range = bool(int(os.environ.get("SR3_STRICT_RANGE", "0")))
+        # train-mode Dropout (unet.py:81-91 of the reference), opt-in: set_dropout_sampling()
+        self.dropout_sampling = False
+        self.dropout_seed: Optional[int] = None
+        self._dropout_masks: Optional[torch.Tensor] = None
 
     # ---- engine management -------------------------------------------------------------------
     def _device_index(self) -> int:
@@ -145,10 +149,51 @@ class UNet(nn.Module):
                 self._engine.load_weight(name, p.detach().to("cpu", torch.float32).contiguous().numpy())
                 self._synced[name] = sig
 
+    # ---- train-mode Dropout ---------------------------------------------------
+    def set_dropout_sampling(self, on: bool, seed: Optional[int] = None) -> None:
+        """Opt in to the reference's train-mode Dropout(cfg.dropout) in every ResnetBlock.block2. It runs only while
+        this switch is on AND the module is in train() mode AND cfg.dropout > 0; in eval() dropout is always the
+        identity, as in the reference. seed pins the key of the mask stream; None draws a fresh one from torch's
+        generator for every call (torch.manual_seed makes runs reproducible)."""
+        self.dropout_sampling = bool(on)
+        self.dropout_seed = None if seed is None else int(seed)
+
+    def set_dropout_masks(self, masks: Optional[torch.Tensor]) -> None:
+        """Injected keep masks for the next calls (parity with recorded masks of the reference): a uint8 tensor on the
+        model's device holding the layers of engine().dropout_layers(H, W) concatenated, each [B,C,H,W], nonzero =
+        keep. None returns to the Philox stream. Used only while dropout is live (set_dropout_sampling)."""
+        if masks is not None:
+            masks = masks.to(device=next(self.parameters()).device, dtype=torch.uint8).contiguous().reshape(-1)
+        self._dropout_masks = masks
+
+    def dropout_live(self) -> bool:
+        return bool(self.dropout_sampling and self.training and float(self.cfg.dropout) > 0)
+
+    def arm_dropout(self, eng: Engine, seed: Optional[int] = None, image_offset: int = 0) -> Optional[int]:
+        """Puts the engine in the state the next library call needs: dropout off (the default state), or on with the
+        key of the mask stream — `seed`, else the pinned one, else a fresh draw from torch's generator — and the
+        injected masks if any. Returns the seed in use (None: off). Callers that split one logical call into several
+        library calls (chunks) draw the seed once and pass it again."""
+        if not self.dropout_live():
+            if getattr(eng, "_dropout_on", False):
+                eng.set_dropout(False)
+                eng._dropout_on = False
+            return None
+        if seed is None:
+            seed = self.dropout_seed
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        eng.set_dropout(True, seed, image_offset)
+        eng._dropout_on = True
+        m = self._dropout_masks
+        eng.set_dropout_masks(m.data_ptr() if m is not None else None, m.numel() if m is not None else 0)
+        return seed
+
     # ---- reference API -----------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, x: torch.Tensor, time: torch.Tensor) -> torch.Tensor:
         eng = self.engine()
+        self.arm_dropout(eng)
         if x.dim() != 4 or x.shape[1] != self.cfg.in_channel:
             raise RuntimeError(f"expected input [B, {self.cfg.in_channel}, H, W], got {tuple(x.shape)}")
         B, _, H, W = x.shape

@@ -220,3 +220,32 @@ def loss_by_level(netG, hr: "torch.Tensor", sr: "torch.Tensor", levels, noise: "
                           seed=seed or 0, max_chunk=max_chunk)
     per = res["per_image"].cpu().numpy().reshape(lv.size, N)
     return {"levels": lv, "loss": per.sum(axis=1) / float(N * C * H * W), "per_image": per}
+
+
+def mc_dropout(netG, x_sr: "torch.Tensor", passes: int, noise_seed: int, dropout_seed: int, image_offset: int = 0):
+    """Monte-Carlo dropout over the sampler: `passes` (K) calls of netG.sample_batch on the same
+    conditioning with the SAME diffusion noise (noise_seed) and K dropout seeds dropout_seed, dropout_seed + 1, ... —
+    what varies between the passes is only the masks of the UNet's Dropout, so the spread is the model's own
+    uncertainty about each pixel. netG must have opted in (set_dropout_sampling(True)) and be in train() mode;
+    otherwise dropout is the identity, every pass is the same image and the std is exactly 0.
+
+    Returns (mean, std): per-pixel mean and population standard deviation (divisor K) over the passes, fp32 [B,C,H,W]
+    device tensors; the sum and the sum of squared deviations are formed in fp64 in pass order. The pinned dropout seed of
+    netG is restored afterwards."""
+    import torch
+
+    if passes < 1:
+        raise ValueError("mc_dropout: passes must be >= 1")
+    unet = netG.denoise_fn
+    keep = unet.dropout_seed
+    outs = []
+    try:
+        for k in range(int(passes)):
+            unet.dropout_seed = int(dropout_seed) + k
+            outs.append(netG.sample_batch(x_sr, False, None, int(noise_seed), image_offset))
+    finally:
+        unet.dropout_seed = keep
+    stack = torch.stack(outs).to(torch.float64)
+    mean = stack.sum(dim=0) / len(outs)
+    var = ((stack - mean) ** 2).sum(dim=0) / len(outs)
+    return mean.to(torch.float32), var.sqrt().to(torch.float32)

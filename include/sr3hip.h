@@ -45,7 +45,8 @@ typedef struct sr3_unet_cfg {
     int32_t attn_res[SR3_MAX_ATTN_RES];
     int32_t res_blocks;
     int32_t image_size;      /* only decides attention placement (unet.py:192-207) */
-    float dropout;           /* accepted for API parity; eval semantics (identity) only */
+    float dropout;           /* p of the Dropout in every ResnetBlock.block2 (unet.py:81-91), in [0, 1). Identity (eval
+                              * semantics) unless sr3_set_dropout enables train-mode sampling of it */
 } sr3_unet_cfg;
 
 /* ---- lifecycle -------------------------------------------------------------------------- */
@@ -214,6 +215,41 @@ void *sr3_test_flag_address(sr3_ctx *ctx);
  * comparison: n floats of draw `draw` for image `image`. */
 int sr3_philox_normal(sr3_ctx *ctx, uint64_t seed, uint64_t image, uint32_t draw, int n,
                       float *out_dev);
+
+/* ---- train-mode Dropout: the UNet as the reference evaluates it under .train() ------------------ */
+
+/* replaces: the nn.Dropout(p) between Swish and Conv3x3 of every ResnetBlock.block2 (unet.py:81-91, built with
+ * p = cfg.dropout at unet.py:100-101) in train mode: the conv's input is keep ? swish(gn(h1)) * s : 0 with
+ * s = float32(1.0 / (1.0 - p)) (what torch.nn.Dropout multiplies by). block1, final_conv, the attention norm and the
+ * res_conv operand are never masked. Off by default (eval semantics: identity); enable = 0 restores exactly that — the
+ * same kernels, the same bits. enable != 0 latches p from the config (p >= 1 fails; p = 0 has no effect) and sets the
+ * key of the mask stream: keep bits are a pure function of (seed, global image index, draw, layer, channel, y, x) —
+ * Philox4x32-10, one evaluation per 8 channels of a pixel, a 16-bit field per element, kept iff field >=
+ * round-half-even(p * 65536): the keep probability is 1 - thr/65536 (0.80000305 for p = 0.2), p quantised to 2^-16.
+ * layer = 0-based ordinal of the ResnetBlock in execution order (downs, mid, ups) = the order of the reference's
+ * nn.Dropout modules in named_modules(). draw = T - t in step t of the sampler, 0 in sr3_unet_forward and
+ * sr3_denoise_loss. global image index = image_offset + batch row, with the image_offset sr3_sample / sr3_sample_begin /
+ * sr3_denoise_loss take (with noise_per_source, where image_offset indexes source images, the row's index is
+ * image_offset + row_offset + b); sr3_unet_forward has none and uses the one given here. So a mask does not depend on the batch
+ * an image sits in, on chunking, on the arithmetic mode or on the range policy's repeats (CPU twin:
+ * tests/dropout_ref.py). Drops the captured step graphs when it changes what the apply passes launch. */
+int sr3_set_dropout(sr3_ctx *ctx, int enable, uint64_t seed, uint64_t image_offset);
+/* Injected masks instead of the Philox stream (parity with recorded masks of the reference's nn.Dropout modules,
+ * unet.py:81-91): one uint8 device buffer, the layers concatenated in layer order, each [B][C][H][W] (NCHW, like the
+ * reference's tensor), nonzero = keep; bytes must equal sr3_dropout_mask_bytes for the call's B, H, W or the call that
+ * uses them fails. Honoured by sr3_unet_forward, sr3_denoise_loss and the step API, where each sr3_sample_step consumes
+ * the buffer set at that moment (per-step masks); sr3_sample fails while masks are injected. The buffer stays the
+ * caller's and must outlive the calls. NULL returns to Philox. Only read while sr3_set_dropout is enabled. */
+int sr3_set_dropout_masks(sr3_ctx *ctx, const uint8_t *dev, uint64_t bytes);
+/* The Dropout layers (unet.py:81-91: one per ResnetBlock) at H x W: *n = their number, chw (NULL, or 3 * n ints) =
+ * {C, H, W} of each layer's masked tensor in layer order. Host only. */
+int sr3_dropout_layers(sr3_ctx *ctx, int H, int W, int *n, int *chw /* 3 per layer */);
+/* bytes of the injected mask buffer for a batch of B images at H x W (the sum of B*C*H*W over the layers); < 0: error */
+int64_t sr3_dropout_mask_bytes(sr3_ctx *ctx, int B, int H, int W);
+/* The counterpart of sr3_philox_normal for the mask stream (unet.py:81-91 has torch's generator here): one image's Philox
+ * mask of one layer as uint8 [C][H][W], 1 = keep, with p from the config; C a multiple of 8, draw < 2^24, layer < 254. */
+int sr3_op_dropout_mask(sr3_ctx *ctx, uint64_t seed, uint64_t image, uint32_t draw, int layer, int C, int H, int W,
+                        uint8_t *out_dev);
 
 /* ---- measurement ------------------------------------------------------------------------- */
 
