@@ -97,7 +97,11 @@ PROTOTYPES = {
     "sr3_bench_conv": (_I, [_P] + [_I] * 13 + [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sr3_wino_weights_host": (_I, [_F, _I, _I, _I, _F]),
     "sr3_op_conv2d": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F]),
+    "sr3_op_conv2d_stats": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F, _F, _U64,
+                                C.POINTER(_I)]),
     "sr3_op_groupnorm_affine": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _F]),
+    "sr3_op_groupnorm_apply": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F,
+                                   C.POINTER(_I), C.POINTER(_I)]),
     "sr3_op_attention": (_I, [_P, _F, _I, _I, _I, _F]),
     "sr3_op_attention_stream": (_I, [_P, _F, _I, _I, _I, _F]),
     "sr3_op_noise_embed": (_I, [_P, _F, _I, _F, _F]),

@@ -270,11 +270,18 @@ __device__ __forceinline__ void store8(float *dst, int c, const float (&f)[8], f
     if (SPLIT) {
         // chunk of 32 channels = 128 B: halfs [0,32) hi, [32,64) lo; x = hi + lo to ~2^-22 |x|.
         // Values beyond the fp16 range are not clamped but detected (absmax -> the ovf flag).
+        // The halves are those of the fp32 VALUE g, the number format 0 stores: hi = fp16(g) and lo = fp16(g - hi) round
+        // from g as rounded to fp32. Without the (empty, free) register constraint below the compiler contracts across the
+        // call: fp16(fmaf(x, a, b)) becomes one v_fma_mixlo_f16 that rounds the exact sum once (the other half at a tie of
+        // the fp32 value), and g - hi with g = x * r becomes fma(x, r, -hi) on the unrounded product — the same tensor then
+        // differs by a half's last bit between the formats (tests/test_gpu_gn_consumers.py::test_output_formats_bitwise).
         h16x8 hi, lo;
-        float lof[8];
+        float lof[8], gv[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float g = f[j];
+            float g = f[j];
+            asm("" : "+v"(g));
+            gv[j] = g;
             absmax = fmaxf(absmax, fabsf(g));
             hi[j] = (_Float16)g;
             lof[j] = g - (float)hi[j];
@@ -289,8 +296,8 @@ __device__ __forceinline__ void store8(float *dst, int c, const float (&f)[8], f
             l8.x = pack4_e4m3(lof[0] * SL, lof[1] * SL, lof[2] * SL, lof[3] * SL);
             l8.y = pack4_e4m3(lof[4] * SL, lof[5] * SL, lof[6] * SL, lof[7] * SL);
             // (the fp32 value itself instead of its fp16 rounding: the same e4m3 number except at rounding ties)
-            h8.x = pack4_e4m3(f[0] * SH, f[1] * SH, f[2] * SH, f[3] * SH);
-            h8.y = pack4_e4m3(f[4] * SH, f[5] * SH, f[6] * SH, f[7] * SH);
+            h8.x = pack4_e4m3(gv[0] * SH, gv[1] * SH, gv[2] * SH, gv[3] * SH);
+            h8.y = pack4_e4m3(gv[4] * SH, gv[5] * SH, gv[6] * SH, gv[7] * SH);
             *reinterpret_cast<uint2 *>(b8) = l8;
             *reinterpret_cast<uint2 *>(b8 + 32) = h8;
         } else {

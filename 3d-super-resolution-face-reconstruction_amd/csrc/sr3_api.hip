@@ -701,6 +701,50 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
 // ---------------------------------------------------------------------------------------------
 const TDesc kNone{};
 
+// The form an apply pass takes: decided HERE for the engine (run_gn_act) and for sr3_op_groupnorm_apply's route 0
+enum GnRoute { GN_FOLDED = 1, GN_FINALIZE_ROWS = 2 };   // finalize folded into the apply launch | finalize launch + streaming rows
+// do the producers' epilogues cover the pass? (else the streaming statistics kernel runs first: launch_groupnorm_partials)
+bool gn_stats_fused(const TDesc &b, const StatsRef &sa, const StatsRef &sb) { return sa.p && (!b.p || sb.p); }
+GnRoute gn_route(const TDesc &a, const TDesc &b, int B, const StatsRef &sa, const StatsRef &sb) {
+    if (!gn_stats_fused(b, sa, sb)) return GN_FOLDED;
+    // bytes the pass moves (read + write, 4 B per element each way): above ~200 MB the one-item-per-thread
+    // streaming kernel behind a separate finalize launch is faster than the folded form (A/B on one box,
+    // profiles/README.md); below it the launch saved and the shorter critical path win
+    const double pass_bytes = 8.0 * B * a.H * a.W * (a.C + (b.p ? b.C : 0));
+    constexpr double fold_max = 200.0 * 1e6;
+    // few images with many statistics slices (a single 128x128 image on 64x64 tiles leaves 256): the folded form's
+    // prologue walks them in 12-16 dependent round trips in EVERY block (12-23 us per apply at B = 1); the
+    // per-(image, group) finalize launch takes one round trip
+    const bool many_slices = (long)B * 4 < 128 && std::max(sa.slices, b.p ? sb.slices : 0) >= 64;
+    return (pass_bytes > fold_max || many_slices) ? GN_FINALIZE_ROWS : GN_FOLDED;
+}
+
+// scratch of an apply pass: scale / shift [B][C] of the finalize launch, partials of the statistics kernel (gn_workspace_floats)
+struct GnScratch { float *scale = nullptr, *shift = nullptr, *part = nullptr; };
+
+// the launches of one apply pass on `route`; statistics the producers did not fuse come from the streaming statistics
+// kernel over the (fp32) tensors, whose partials describe the virtual concatenation as one source of a.C + b.C channels
+void launch_gn_act(GnRoute route, const TDesc &a, const TDesc &b, int B, int groups, const float *gamma, const float *beta, int mode,
+                   int fmt, const TDesc &act, const StatsRef &sa, const StatsRef &sb, const GnScratch &ws, const TDesc &raw, int in_split,
+                   float *U, int *ovf, const DropLayer &drop, hipStream_t s) {
+    StatsRef s0 = sa, s1 = sb;
+    int C0 = a.C, C1 = b.p ? b.C : 0;
+    if (!gn_stats_fused(b, sa, sb)) {
+        s0 = launch_groupnorm_partials(a, b, B, ws.part, s);
+        s1 = StatsRef();
+        C0 += C1; C1 = 0;
+    }
+    if (route == GN_FINALIZE_ROWS) {
+        launch_groupnorm_finalize(s0, C0, s1, C1, B, a.H * a.W, groups, gamma, beta, 1e-5f, ws.scale, ws.shift, s);
+        if (U) launch_gn_wino_input(a, b, B, ws.scale, ws.shift, mode, U, s);
+        else launch_gn_apply_rows(a, b, B, ws.scale, ws.shift, mode, fmt, act, s, raw, in_split, ovf, drop);
+    } else {
+        // statistics as partials: finalize + apply are ONE launch
+        if (U) launch_gn_fold_wino_input(a, b, B, s0, s1, groups, gamma, beta, 1e-5f, mode, U, s);
+        else launch_gn_fold_apply(a, b, B, s0, s1, groups, gamma, beta, 1e-5f, mode, fmt, act, s, raw, in_split, ovf, drop);
+    }
+}
+
 // GroupNorm statistics + apply (+Swish) (+concat) -> activated, zero-bordered conv input
 // f8: the consumer conv takes the F8C operand format (f8_conv() said so)
 // U != null (gn_writes_u() said so): the consumer is a three-pass Winograd conv and the pass writes its transformed
@@ -712,34 +756,10 @@ void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int 
     const int fmt = c->act_format(f8);
     if (U) ++c->gn_wino_passes;
     c->pbegin(F_GN);
-    const float *gamma = c->params[g.gamma].dev, *beta = c->params[g.beta].dev;
-    // bytes the pass moves (read + write, 4 B per element each way): above ~200 MB the one-item-per-thread
-    // streaming kernel behind a separate finalize launch is faster than the folded form (A/B on one box,
-    // profiles/README.md); below it the launch saved and the shorter critical path win
-    const double pass_bytes = 8.0 * B * a.H * a.W * (a.C + (b.p ? b.C : 0));
-    constexpr double fold_max = 200.0 * 1e6;
-    // few images with many statistics slices (a single 128x128 image on 64x64 tiles leaves 256): the folded form's
-    // prologue walks them in 12-16 dependent round trips in EVERY block (12-23 us per apply at B = 1); the
-    // per-(image, group) finalize launch takes one round trip
-    const bool many_slices = (long)B * 4 < 128 && std::max(sa.slices, b.p ? sb.slices : 0) >= 64;
-    if (sa.p && (!b.p || sb.p) && (pass_bytes > fold_max || many_slices)) {
-        launch_groupnorm_finalize(sa, a.C, sb, b.p ? b.C : 0, B, a.H * a.W, c->cfg.norm_groups, gamma, beta, 1e-5f,
-                                  c->gscale, c->gshift, c->stream);
-        if (U) launch_gn_wino_input(a, b, B, c->gscale, c->gshift, mode, U, c->stream);
-        else launch_gn_apply_rows(a, b, B, c->gscale, c->gshift, mode, fmt, act, c->stream, raw, in_split, c->d_ovf, drop);
-    } else if (sa.p && (!b.p || sb.p)) {
-        // statistics came out of the producing convs' epilogues: finalize + apply are ONE launch
-        if (U) launch_gn_fold_wino_input(a, b, B, sa, sb, c->cfg.norm_groups, gamma, beta, 1e-5f, mode, U, c->stream);
-        else launch_gn_fold_apply(a, b, B, sa, sb, c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream, raw,
-                                  in_split, c->d_ovf, drop);
-    } else {
-        // fallback: streaming statistics kernel over the (fp32) tensors; its partials describe the
-        // virtual concatenation as one source of a.C + b.C channels
-        const StatsRef sp = launch_groupnorm_partials(a, b, B, c->gpart, c->stream);
-        if (U) launch_gn_fold_wino_input(a, b, B, sp, StatsRef(), c->cfg.norm_groups, gamma, beta, 1e-5f, mode, U, c->stream);
-        else launch_gn_fold_apply(a, b, B, sp, StatsRef(), c->cfg.norm_groups, gamma, beta, 1e-5f, mode, fmt, act, c->stream,
-                                  raw, in_split, c->d_ovf, drop);
-    }
+    GnScratch ws;
+    ws.scale = c->gscale; ws.shift = c->gshift; ws.part = c->gpart;
+    launch_gn_act(gn_route(a, b, B, sa, sb), a, b, B, c->cfg.norm_groups, c->params[g.gamma].dev, c->params[g.beta].dev, mode, fmt,
+                  act, sa, sb, ws, raw, in_split, U, c->d_ovf, drop, c->stream);
     c->pend();
 }
 
@@ -1435,7 +1455,8 @@ void fill_random(sr3_ctx *c, float *q, size_t n, int seed) {
     launch_philox_normal(seed, 0, 0, (int)std::min<size_t>(n, 1u << 30), q, c->stream);
 }
 
-// A single conv as the engine runs this shape: the plan of the shape with every buffer offered (no fused statistics)
+// A single conv as the engine runs this shape: the plan of the shape with every buffer offered (fused statistics only
+// with `stats`: the caller then passes ConvParams::stats with the plan's stats_slices)
 // names the weight layouts and scratch buffers; p comes back with input, weights, partials and Winograd workspace
 // filled in — output, bias, residual and FeatureWiseAffine bias are the caller's.
 struct ScratchConv {
@@ -1446,10 +1467,11 @@ struct ScratchConv {
 
     // weight_host: OIHW weights, nullptr: random values (timing). The activated input `act` (zero-bordered, Cin
     // channels) is allocated and left for the caller to fill.
-    int setup(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout, int ks, int stride, int up2, const float *weight_host) {
+    int setup(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout, int ks, int stride, int up2, const float *weight_host,
+              bool stats = false) {
         const int Cin = C0 + C1;
         f8 = c->f8() && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin);
-        plan = conv_plan_offered(B, Hin, Win, Cin, Cout, ks, stride, up2, c->split() ? 1 : 0, f8, false);
+        plan = conv_plan_offered(B, Hin, Win, Cin, Cout, ks, stride, up2, c->split() ? 1 : 0, f8, stats);
         const bool wino = plan.kernel == CK_WINO_ONE_PASS || plan.kernel == CK_WINO_THREE_PASS;
         const size_t n_w = (size_t)(up2 ? 16 : ks * ks) * Cout * Cin;     // up2: 4 phases x 2x2 taps
         const size_t n_wino = (size_t)16 * Cout * Cin;
@@ -2192,25 +2214,36 @@ int sr3_profile_get(sr3_ctx *c, int family, double *total_ms, int64_t *launches,
 }
 
 // ---- single ops --------------------------------------------------------------------------------
-int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int Hin,
-                  int Win, const float *weight_host, const float *bias_host, int Cout, int ks, int stride,
-                  int up2, const float *gn_scale_dev, const float *gn_shift_dev, int swish,
-                  const float *chan_bias_dev, const float *resid_dev, float *out_dev) {
-    if (!c || !in0_dev || !weight_host || !out_dev) return fail("sr3_op_conv2d: null argument");
-    if ((C0 % 32) || (C1 % 32) || C0 <= 0 || C1 < 0) return fail("sr3_op_conv2d: C0=%d C1=%d must be multiples of 32", C0, C1);
-    if (!(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (up2 & ~1)) return fail("sr3_op_conv2d: bad ks/stride/up2");
-    if ((gn_scale_dev == nullptr) != (gn_shift_dev == nullptr)) return fail("sr3_op_conv2d: scale and shift go together");
-    if (up2 && (ks != 3 || stride != 1)) return fail("sr3_op_conv2d: up2 needs ks 3, stride 1");
+// sr3_op_conv2d (stats_dev == null) and sr3_op_conv2d_stats: one body. With statistics the plan is the one the engine's
+// convs get (fused statistics offered); a shape whose plan has none runs without them and reports 0 slices.
+static int op_conv2d_impl(const char *what, sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int Hin,
+                          int Win, const float *weight_host, const float *bias_host, int Cout, int ks, int stride,
+                          int up2, const float *gn_scale_dev, const float *gn_shift_dev, int swish,
+                          const float *chan_bias_dev, const float *resid_dev, float *out_dev, double *stats_dev,
+                          uint64_t stats_capacity_doubles, int *slices_out) {
+    if (!c || !in0_dev || !weight_host || !out_dev) return fail("%s: null argument", what);
+    if ((C0 % 32) || (C1 % 32) || C0 <= 0 || C1 < 0) return fail("%s: C0=%d C1=%d must be multiples of 32", what, C0, C1);
+    if (!(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (up2 & ~1)) return fail("%s: bad ks/stride/up2", what);
+    if ((gn_scale_dev == nullptr) != (gn_shift_dev == nullptr)) return fail("%s: scale and shift go together", what);
+    if (up2 && (ks != 3 || stride != 1)) return fail("%s: up2 needs ks 3, stride 1", what);
     HIP_OK(hipSetDevice(c->device));
     if (!in1_dev) C1 = 0;
     ScratchConv sc;
-    if (sc.setup(c, B, Hin, Win, C0, C1, Cout, ks, stride, up2, weight_host)) return -1;
+    if (sc.setup(c, B, Hin, Win, C0, C1, Cout, ks, stride, up2, weight_host, stats_dev != nullptr)) return -1;
     DevBuf bias;
     if (bias_host && bias.upload(bias_host, (size_t)Cout)) return -1;
     ConvParams &p = sc.p;
     p.bias = bias.p; p.chan_bias = chan_bias_dev; p.chan_bias_stride = Cout;
     p.out = unpadded(out_dev, Cout, p.Hout, p.Wout);
     if (resid_dev) p.resid = unpadded(const_cast<float *>(resid_dev), Cout, p.Hout, p.Wout);
+    if (stats_dev && sc.plan.stats_slices > 0) {
+        const uint64_t need = (uint64_t)B * sc.plan.stats_slices * Cout * 2;
+        if (stats_capacity_doubles < need)
+            return fail("%s: the statistics take %llu doubles ([B][%d slices][Cout][2]), the buffer holds %llu", what,
+                        (unsigned long long)need, sc.plan.stats_slices, (unsigned long long)stats_capacity_doubles);
+        p.stats = stats_dev; p.stats_slices = sc.plan.stats_slices;
+    }
+    if (slices_out) *slices_out = p.stats_slices;
     // the engine's own sequence: (GroupNorm apply | copy) + concat into a zero-bordered tensor, then conv; in front of a
     // three-pass Winograd conv the pass writes the transformed input instead (nothing reads p.in0 then)
     const bool to_u = sc.gn_writes_u(c);
@@ -2219,8 +2252,10 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
     const TDesc i1 = in1_dev ? unpadded(const_cast<float *>(in1_dev), C1, Hin, Win) : kNone;
     // (this entry point owns its inputs: an in-place split-K wait that gave up is answered by running the pass and the
     // conv again on the non-waiting path, as sr3_unet_forward / sr3_sample do; it never leaves the arithmetic it was asked for)
-    return guarded_eval(c, "sr3_op_conv2d", "the conv", false, [&]() -> int {
+    return guarded_eval(c, what, "the conv", false, [&]() -> int {
         const int mode = gn_scale_dev ? (swish ? 2 : 1) : 0;
+        // (0xFF bytes read back as NaN: a slice no kernel wrote stays visible)
+        if (stats_dev) HIP_OK(hipMemsetAsync(stats_dev, 0xFF, stats_capacity_doubles * sizeof(double), c->stream));
         if (to_u) {
             launch_gn_wino_input(i0, i1, B, gn_scale_dev, gn_shift_dev, mode, p.wino_ws, c->stream);
             ++c->gn_wino_passes;
@@ -2230,10 +2265,29 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
         p.u_ready = to_u ? 1 : 0;
         p.no_halo_split = c->halo_split_off ? 1 : 0;
         launch_conv(p, c->stream);
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("sr3_op_conv2d: launch failed");
-        if (const char *e = conv_take_error()) return fail("sr3_op_conv2d: %s", e);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("%s: launch failed", what);
+        if (const char *e = conv_take_error()) return fail("%s: %s", what, e);
         return 0;
     });
+}
+
+int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int Hin,
+                  int Win, const float *weight_host, const float *bias_host, int Cout, int ks, int stride,
+                  int up2, const float *gn_scale_dev, const float *gn_shift_dev, int swish,
+                  const float *chan_bias_dev, const float *resid_dev, float *out_dev) {
+    return op_conv2d_impl("sr3_op_conv2d", c, in0_dev, C0, in1_dev, C1, B, Hin, Win, weight_host, bias_host, Cout, ks, stride, up2,
+                          gn_scale_dev, gn_shift_dev, swish, chan_bias_dev, resid_dev, out_dev, nullptr, 0, nullptr);
+}
+
+int sr3_op_conv2d_stats(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int Hin,
+                        int Win, const float *weight_host, const float *bias_host, int Cout, int ks, int stride,
+                        int up2, const float *gn_scale_dev, const float *gn_shift_dev, int swish,
+                        const float *chan_bias_dev, const float *resid_dev, float *out_dev, double *stats_dev,
+                        uint64_t stats_capacity_doubles, int *slices_out) {
+    if (!stats_dev || !slices_out) return fail("sr3_op_conv2d_stats: null argument");
+    return op_conv2d_impl("sr3_op_conv2d_stats", c, in0_dev, C0, in1_dev, C1, B, Hin, Win, weight_host, bias_host, Cout, ks, stride,
+                          up2, gn_scale_dev, gn_shift_dev, swish, chan_bias_dev, resid_dev, out_dev, stats_dev,
+                          stats_capacity_doubles, slices_out);
 }
 
 // Times `iters` launches of one conv shape on scratch buffers (random contents; f32 MFMA time does
@@ -2310,6 +2364,53 @@ int sr3_op_groupnorm_affine(sr3_ctx *c, const float *in0_dev, int C0, const floa
     HIP_OK(hipStreamSynchronize(c->stream));
     HIP_OK(hipFree(dg)); HIP_OK(hipFree(db)); HIP_OK(hipFree(part));
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int sr3_op_groupnorm_apply(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int H, int W,
+                           int groups, const float *gamma_host, const float *beta_host, const double *stats0_dev, int slices0,
+                           const double *stats1_dev, int slices1, int mode, int format, int in_split, int route,
+                           float *out_dev, float *raw_out_dev, int *route_out, int *range_out) {
+    if (!c || !in0_dev || !gamma_host || !beta_host || !out_dev) return fail("sr3_op_groupnorm_apply: null argument");
+    if (!in1_dev) C1 = 0;
+    const int C = C0 + C1;
+    if (B < 1 || H < 1 || W < 1 || C0 <= 0 || (C0 % 8) || (C1 % 8) || C > 2048)
+        return fail("sr3_op_groupnorm_apply: bad size B=%d H=%d W=%d C0=%d C1=%d (channels in multiples of 8, at most 2048)", B, H, W, C0, C1);
+    if (groups <= 0 || C % groups) return fail("sr3_op_groupnorm_apply: groups=%d does not divide C=%d", groups, C);
+    if (mode < 0 || mode > 2 || format < 0 || format > 2 || (in_split & ~3) || route < 0 || route > 2)
+        return fail("sr3_op_groupnorm_apply: mode %d / format %d / in_split %d / route %d out of range", mode, format, in_split, route);
+    if ((in_split & 2) && !in1_dev) return fail("sr3_op_groupnorm_apply: in_split names a second input, there is none");
+    // the split formats are laid out in 32-channel chunks: of the output, and of each input stored that way
+    if ((format && ((C0 % 32) || (C1 % 32))) || ((in_split & 1) && (C0 % 32)) || ((in_split & 2) && (C1 % 32)))
+        return fail("sr3_op_groupnorm_apply: the split formats need channels in multiples of 32 (C0=%d C1=%d)", C0, C1);
+    if (stats0_dev ? (slices0 < 1 || (in1_dev && (!stats1_dev || slices1 < 1))) : stats1_dev != nullptr)
+        return fail("sr3_op_groupnorm_apply: partials of both inputs (at least one slice each) or of neither");
+    // (without partials the statistics kernel reads the inputs as fp32)
+    if (!stats0_dev && in_split) return fail("sr3_op_groupnorm_apply: split-f16 inputs need their partials");
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf dg, db, scale, shift, part;
+    if (dg.upload(gamma_host, (size_t)C) || db.upload(beta_host, (size_t)C) || scale.alloc((size_t)B * C) || shift.alloc((size_t)B * C) ||
+        part.alloc(gn_workspace_floats(B, C)))
+        return -1;
+    const TDesc a = unpadded(const_cast<float *>(in0_dev), C0, H, W);
+    const TDesc b = in1_dev ? unpadded(const_cast<float *>(in1_dev), C1, H, W) : kNone;
+    const TDesc act = unpadded(out_dev, C, H, W);
+    const TDesc raw = raw_out_dev ? unpadded(raw_out_dev, C, H, W) : TDesc();
+    StatsRef sa, sb;
+    sa.p = stats0_dev; sa.slices = stats0_dev ? slices0 : 0;
+    if (in1_dev) { sb.p = stats1_dev; sb.slices = stats1_dev ? slices1 : 0; }
+    const GnRoute r = route == 0 ? gn_route(a, b, B, sa, sb) : (GnRoute)route;
+    if (r == GN_FINALIZE_ROWS && (long)B * H / ((H % 2) ? 1 : 2) > 65535)
+        return fail("sr3_op_groupnorm_apply: B=%d x H=%d rows exceed the streaming form's grid", B, H);
+    GnScratch ws;
+    ws.scale = scale.p; ws.shift = shift.p; ws.part = part.p;
+    if (range_reset(c)) return -1;
+    launch_gn_act(r, a, b, B, groups, dg.p, db.p, mode, format, act, sa, sb, ws, raw, in_split, nullptr, c->d_ovf, DropLayer(), c->stream);
+    const int flag = range_read(c);         // (synchronises; clears the flag)
+    if (flag < 0) return -1;
+    HIP_OK(hipGetLastError());
+    if (route_out) *route_out = (int)r;
+    if (range_out) *range_out = flag ? 1 : 0;
     return 0;
 }
 

@@ -428,7 +428,10 @@ class Engine:
 
     # ---- single ops (numpy in / numpy out; NHWC) --------------------------------------------
     def op_conv2d(self, x0, weight, bias=None, x1=None, stride=1, up2=False, gn_scale=None,
-                  gn_shift=None, swish=False, chan_bias=None, resid=None) -> np.ndarray:
+                  gn_shift=None, swish=False, chan_bias=None, resid=None, return_stats=False):
+        """return_stats=True runs the conv as the engine runs it, with the fused GroupNorm statistics of its output offered
+        (conv_plan(..., stats=True) names the kernel), and returns (out, stats): stats float64 [B, slices, Cout, 2] =
+        {sum, sum of squares} per (image, slice, channel), NaN where no kernel wrote; None where the plan has none."""
         x0 = _host_f32(x0)
         B, H, W, C0 = x0.shape
         C1 = 0 if x1 is None else x1.shape[-1]
@@ -446,12 +449,66 @@ class Engine:
         drs = self.to_device(resid) if resid is not None else None
         out = self.buffer(B * Ho * Wo * Cout)
         bh = _host_f32(bias) if bias is not None else None
-        _lib.check(self.lib.sr3_op_conv2d(
-            self.ctx, d0.ptr, C0, d1.ptr if d1 else None, C1, B, H, W, weight.ctypes.data,
-            bh.ctypes.data if bh is not None else None, Cout, ks, stride, 1 if up2 else 0,
-            dsc.ptr if dsc else None, dsh.ptr if dsh else None, 1 if swish else 0,
-            dcb.ptr if dcb else None, drs.ptr if drs else None, out.ptr))
-        return out.download((B, Ho, Wo, Cout))
+        args = (self.ctx, d0.ptr, C0, d1.ptr if d1 else None, C1, B, H, W, weight.ctypes.data,
+                bh.ctypes.data if bh is not None else None, Cout, ks, stride, 1 if up2 else 0,
+                dsc.ptr if dsc else None, dsh.ptr if dsh else None, 1 if swish else 0,
+                dcb.ptr if dcb else None, drs.ptr if drs else None, out.ptr)
+        if not return_stats:
+            _lib.check(self.lib.sr3_op_conv2d(*args))
+            return out.download((B, Ho, Wo, Cout))
+        # (sized by the plan the call will take; the call fails if it takes another)
+        slices = self.conv_plan(B, H, W, Cin, Cout, ks, stride, 1 if up2 else 0, stats=True)["stats_slices"]
+        cap = max(1, B * slices * Cout * 2)
+        st = self.buffer(cap * 2)
+        got = C.c_int(-1)
+        _lib.check(self.lib.sr3_op_conv2d_stats(*args, st.ptr, cap, C.byref(got)))
+        o = out.download((B, Ho, Wo, Cout))
+        if got.value == 0:
+            return o, None
+        assert got.value == slices, (got.value, slices)
+        return o, st.download().view(np.float64).reshape(B, slices, Cout, 2)
+
+    def op_groupnorm_apply(self, x0, gamma, beta, groups=32, x1=None, stats0=None, stats1=None, mode=2, fmt=0,
+                           in_split=0, route=0, want_raw=False):
+        """The engine's GroupNorm apply pass over x0 ‖ x1 (NHWC; float32, or the uint32 words of the split-f16 format for an
+        input named in in_split). stats0 / stats1: float64 partials [B, slices, C, 2] of x0 / x1 (None: the statistics
+        kernel runs). mode 0 copy | 1 affine | 2 affine + Swish; fmt 0 fp32 | 1 split-f16 | 2 F8C; route 0 the engine's
+        choice | 1 folded | 2 finalize + streaming rows. Returns a dict: out (float32 for fmt 0, else uint32 words), raw
+        (want_raw), route (taken), range_flag."""
+        def words(a):
+            a = np.ascontiguousarray(a)
+            return a.view(np.float32) if a.dtype == np.uint32 else _host_f32(a)
+
+        def doubles(a):
+            return self.to_device(np.ascontiguousarray(a, dtype=np.float64).view(np.float32))
+
+        x0 = words(x0)
+        B, H, W, C0 = x0.shape
+        C1 = 0 if x1 is None else x1.shape[-1]
+        Cc = C0 + C1
+        d0 = self.to_device(x0)
+        d1 = self.to_device(words(x1)) if x1 is not None else None
+        s0 = doubles(stats0) if stats0 is not None else None
+        s1 = doubles(stats1) if stats1 is not None else None
+        for st, Cs in ((stats0, C0), (stats1, C1)):
+            assert st is None or (st.ndim == 4 and st.shape[0] == B and st.shape[2:] == (Cs, 2)), st.shape
+        g, b = _host_f32(gamma), _host_f32(beta)
+        assert g.size == Cc and b.size == Cc
+        out = self.buffer(B * H * W * Cc)
+        raw = self.buffer(B * H * W * Cc) if want_raw else None
+        took, flag = C.c_int(0), C.c_int(0)
+        _lib.check(self.lib.sr3_op_groupnorm_apply(
+            self.ctx, d0.ptr, C0, d1.ptr if d1 else None, C1, B, H, W, groups, g.ctypes.data, b.ctypes.data,
+            s0.ptr if s0 else None, stats0.shape[1] if stats0 is not None else 0,
+            s1.ptr if s1 else None, stats1.shape[1] if stats1 is not None else 0,
+            mode, fmt, in_split, route, out.ptr, raw.ptr if raw else None, C.byref(took), C.byref(flag)))
+        res = {"out": out.download((B, H, W, Cc)), "route": took.value, "range_flag": bool(flag.value)}
+        if fmt:
+            res["out"] = res["out"].view(np.uint32)
+        if want_raw:
+            r = raw.download((B, H, W, Cc))
+            res["raw"] = r.view(np.uint32) if fmt else r
+        return res
 
     def op_groupnorm_affine(self, x0, gamma, beta, groups=32, x1=None):
         x0 = _host_f32(x0)

@@ -291,11 +291,41 @@ int sr3_op_conv2d(sr3_ctx *ctx, const float *in0_dev, int C0, const float *in1_d
                   int ks, int stride, int up2, const float *gn_scale_dev,
                   const float *gn_shift_dev, int swish, const float *chan_bias_dev,
                   const float *resid_dev, float *out_dev);
+/* sr3_op_conv2d as the ENGINE runs the conv: with the fused GroupNorm statistics of its output offered, so the dispatch
+ * plan is the one sr3_conv_plan reports with with_stats = 1 (which may name another kernel than without). stats_dev
+ * (stats_capacity_doubles doubles) is first filled with 0xFF bytes (they read back as NaN), then receives fp64 {sum, sum
+ * of squares} of the stored fp32 output per (image, slice, channel) as [B][*slices_out][Cout][2]; *slices_out = the
+ * plan's slices per image. A shape whose plan has no fused statistics runs without them: *slices_out = 0 and the output
+ * is sr3_op_conv2d's. Fails if the buffer is too small. (tests) */
+int sr3_op_conv2d_stats(sr3_ctx *ctx, const float *in0_dev, int C0, const float *in1_dev, int C1, int B,
+                        int Hin, int Win, const float *weight_host, const float *bias_host, int Cout,
+                        int ks, int stride, int up2, const float *gn_scale_dev,
+                        const float *gn_shift_dev, int swish, const float *chan_bias_dev,
+                        const float *resid_dev, float *out_dev, double *stats_dev,
+                        uint64_t stats_capacity_doubles, int *slices_out);
 /* GroupNorm statistics folded with the affine: scale[b,c] = rstd*gamma[c],
  * shift[b,c] = beta[c] - mean*rstd*gamma[c]  (torch GroupNorm, eps 1e-5; unet.py:84,119). */
 int sr3_op_groupnorm_affine(sr3_ctx *ctx, const float *in0_dev, int C0, const float *in1_dev,
                             int C1, int B, int H, int W, int groups, const float *gamma_host,
                             const float *beta_host, float *scale_dev, float *shift_dev);
+/* The GroupNorm apply pass of the engine (unet.py:84-86 Block: GroupNorm -> Swish, over torch.cat((x, skip), 1)) on
+ * unpadded NHWC inputs in0 ‖ in1 (in1_dev NULL: none): out = act(group_norm(in0 ‖ in1)), mode 0 copy | 1 affine |
+ * 2 affine + Swish; gamma_host / beta_host [C0+C1]. Channels in multiples of 8 (32 for any split format), C0+C1 <= 2048.
+ * stats0_dev / stats1_dev: fp64 partial statistics of in0 / in1 as conv epilogues leave them, [B][slices][C][2] with
+ * slices0 / slices1 slices (any split of an image's pixels); both NULL: the streaming statistics kernel runs first (fp32
+ * inputs only); stats1_dev NULL with in1 present is an error unless both are NULL.
+ * format: 0 fp32 | 1 split-f16 (per 32-channel chunk 32 hi halfs | 32 lo halfs) | 2 the F8C variant (32 hi halfs |
+ * 32 x e4m3(lo * 2^11) | 32 x e4m3(value)); out_dev [B,H,W,C0+C1] receives the 32-bit words as stored. in_split bit 0 /
+ * bit 1: in0 / in1 is itself stored in format 1. raw_out_dev (optional): the un-normalised concatenation, in format 1
+ * if `format` is non-zero, else fp32.
+ * route: 1 = statistics finalize folded into the apply launch, 2 = finalize launch + streaming apply, 0 = what the
+ * engine chooses for this pass; *route_out (optional) = the route taken (1 | 2); *range_out (optional) = 1 if a stored
+ * value exceeded the range of its split format (the range flag; never in format 0), which is NOT an error here. (tests) */
+int sr3_op_groupnorm_apply(sr3_ctx *ctx, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int H,
+                           int W, int groups, const float *gamma_host, const float *beta_host,
+                           const double *stats0_dev, int slices0, const double *stats1_dev, int slices1, int mode,
+                           int format, int in_split, int route, float *out_dev, float *raw_out_dev,
+                           int *route_out, int *range_out);
 /* SelfAttention core (unet.py:132-139): qkv_dev [B, N, 3C] (q|k|v along the last axis) -> out
  * [B, N, C]; softmax(q.k / sqrt(C)) v, one head. Any N >= 1, C a multiple of 32: up to 1024 tokens the
  * engine's cores for the precision mode run (32 x N score tile in LDS); above, the exact-f32 streaming
