@@ -68,6 +68,9 @@ PROTOTYPES = {
     "sr3_param_info": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(C.c_int64), C.POINTER(_I)]),
     "sr3_load_weight": (_I, [_P, C.c_char_p, _F, C.POINTER(C.c_int64), _I]),
     "sr3_weights_missing": (_I, [_P]),
+    "sr3_load_weights_dev": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_F), C.POINTER(C.c_int64), C.POINTER(_I)]),
+    "sr3_read_weight_layout": (C.c_int64, [_P, C.c_char_p, _I, _P, C.c_int64]),
+    "sr3_weight_unscale": (C.c_float, [_P, C.c_char_p]),
     "sr3_unet_forward": (_I, [_P, _F, _F, _I, _I, _I, _F]),
     "sr3_set_schedule": (_I, [_P, _I, _F, _F, _F, _F, _F, _F]),
     "sr3_set_sampler_schedule": (_I, [_P, _I, _F, _F, _F, _F, _F, _F, _F, _I]),
@@ -123,7 +126,8 @@ PROTOTYPES = {
 
 # counters and opt-in entry points added to the C-ABI after its first A/B-able build (load)
 NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_set_dropout", "sr3_set_dropout_masks", "sr3_dropout_layers",
-                  "sr3_dropout_mask_bytes", "sr3_op_dropout_mask")
+                  "sr3_dropout_mask_bytes", "sr3_op_dropout_mask", "sr3_load_weights_dev", "sr3_read_weight_layout",
+                  "sr3_weight_unscale")
 
 _lib = None
 

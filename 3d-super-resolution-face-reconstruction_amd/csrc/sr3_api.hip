@@ -58,7 +58,8 @@ struct Param {
     float w_unscale = 1.0f;
     bool keep_host = false;                      // part of a fused (conv2 + res_conv) launch
     bool up_phase = false;                       // Upsample conv: stored as 4 sub-pixel phases x 2x2 taps
-    std::vector<float> host;                     // packed fp32 weights / bias kept for re-scaling
+    std::vector<float> host;                     // packed fp32 weights / bias kept for re-scaling; empty after a device
+                                                 // refresh (sr3_load_weights_dev): fused_host fetches dev again on demand
     size_t dev_floats = 0;
     bool owns = true;                            // false: a view into a concatenated buffer
     bool loaded = false;
@@ -161,6 +162,10 @@ struct sr3_ctx {
     size_t ckpt_floats = 0;
     double *metrics_ws = nullptr;       // sr3_metrics_psnr_ssim / sr3_denoise_loss: per-block fp64 partial sums (grows on demand)
     size_t metrics_ws_n = 0;
+    // sr3_load_weights_dev: max|w| per parameter (bit patterns, reduced on the device) and the pinned staging area of its
+    // one device-to-host copy: the maxima, the OIHW sources of the edge convs, and their packed forms on the way back
+    unsigned *d_wmax = nullptr;
+    float *h_stage = nullptr;
     unsigned *tile_cnt = nullptr;       // ConvParams::tile_cnt: arrival counters of the in-place split-K convs (zero between launches)
     // Set (for the rest of the context's life) when a bounded inter-block wait of the in-place split-K on x-halo tiles
     // gave up — a co-tenant kernel held the CU slots its sibling blocks needed (range_read): every conv then runs on a
@@ -1088,9 +1093,25 @@ void run_embed(sr3_ctx *c, const float *nl, int stride, int B) {
 
 // ResnetBlocks with a res_conv run conv2 and the 1x1 res_conv as ONE launch (extra K-steps): the
 // two biases are pre-added and, for the split-f16 weights, both tensors get the same 2^k scale.
+// the host copy prepare_fused re-splits from: what sr3_load_weight kept, or, after a device refresh dropped it, the
+// parameter's current device copy (the same values: the packed weights / the bias)
+int fused_host(Param &p) {
+    if (!p.host.empty()) return 0;
+    p.host.resize(p.dev_floats);
+    HIP_OK(hipMemcpy(p.host.data(), p.dev, p.dev_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int prepare_fused(sr3_ctx *c) {
     if (!c->fused_dirty) return 0;
     HIP_OK(hipStreamSynchronize(c->stream));
+    for (auto &m : c->mods) {
+        if (m.kind != M_RES) continue;
+        if (m.rb.has_res) {
+            for (int idx : {m.rb.c2.w, m.rb.c2.b, m.rb.res.w, m.rb.res.b})
+                if (fused_host(c->params[idx])) return -1;
+        } else if (ident_eligible(m.rb) && fused_host(c->params[m.rb.c2.w])) return -1;
+    }
     for (auto &m : c->mods) {
         if (m.kind != M_RES || !ident_eligible(m.rb)) continue;
         ResBlock &rb = m.rb;
@@ -1609,6 +1630,8 @@ void sr3_destroy(sr3_ctx *c) {
     if (c->ckpt) (void)hipFree(c->ckpt);
     if (c->metrics_ws) (void)hipFree(c->metrics_ws);
     if (c->tile_cnt) (void)hipFree(c->tile_cnt);
+    if (c->d_wmax) (void)hipFree(c->d_wmax);
+    if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_ovf) (void)hipHostFree(c->h_ovf);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     if (c->d_step) (void)hipFree(c->d_step);
@@ -1766,6 +1789,233 @@ int sr3_load_weight(sr3_ctx *c, const char *name, const float *host, const int64
         return 0;
     }
     return fail("unknown parameter '%s'", name);
+}
+
+namespace {
+
+// split_scale_exponent, from the maximum the device reduced
+int scale_exponent_of_max(float mx) {
+    if (!(mx > 0.f)) return 0;
+    int e;
+    frexpf(mx, &e);
+    return 11 - e;
+}
+
+int find_param(sr3_ctx *c, const char *name, const int64_t *shape, int ndim) {
+    for (size_t i = 0; i < c->params.size(); ++i) {
+        const Param &p = c->params[i];
+        if (p.name != name) continue;
+        if ((int)p.shape.size() != ndim) return fail("%s: expected %zu dims, got %d", name, p.shape.size(), ndim);
+        for (int d = 0; d < ndim; ++d)
+            if (p.shape[d] != shape[d])
+                return fail("%s: dim %d is %lld, expected %lld", name, d, (long long)shape[d], (long long)p.shape[d]);
+        return (int)i;
+    }
+    return fail("unknown parameter '%s'", name);
+}
+
+// layout of h_stage in floats: [maxima : nparams][conv_in OIHW][final_conv OIHW][ci_w][final_wm][final_wq]
+struct StageLayout { size_t ci_src, fc_src, ci_w, final_wm, final_wq, total; };
+StageLayout stage_layout(const sr3_ctx *c) {
+    StageLayout L;
+    const Param &ci = c->params[c->mods[0].conv.w], &fc = c->params[c->final_conv.w];
+    size_t o = c->params.size();
+    L.ci_src = o;   o += (size_t)ci.cout * ci.cin * 9;
+    L.fc_src = o;   o += (size_t)fc.cout * fc.cin * 9;
+    L.ci_w = o;     o += c->ci_w ? conv_in_weight_floats(ci.cout) : 0;
+    L.final_wm = o; o += c->final_wm ? final_conv_mfma_weight_floats(fc.cin) : 0;
+    L.final_wq = o; o += c->final_wq ? (size_t)9 * fc.cin * 4 : 0;
+    L.total = o;
+    return L;
+}
+
+} // namespace
+
+// The device route of sr3_load_weight. Phase one (enqueued): every layout that does not depend on the split exponent is
+// written straight from the caller's tensors, and max|w| of every conv tensor is reduced into d_wmax. One small copy brings
+// the maxima (and the two edge convs' few thousand source floats) to the host and the stream is synchronised ONCE. The host
+// derives every exponent, with prepare_fused's rules for the fused (conv2 + res_conv) pairs and the identity-skip blocks,
+// and phase two enqueues the split passes and the products of prepare_fused for the blocks it touched. The host copies
+// (Param::host) of the refreshed tensors are dropped; a later prepare_fused fetches them from the device again.
+int sr3_load_weights_dev(sr3_ctx *c, int n, const char *const *names, const float *const *dev_ptrs, const int64_t *shapes,
+                         const int *ndims) {
+    if (!c || n < 0 || (n > 0 && (!names || !dev_ptrs || !shapes || !ndims))) return fail("sr3_load_weights_dev: null argument");
+    if (n == 0) return 0;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t np = c->params.size();
+    std::vector<int> idx(n);
+    std::vector<char> touched(np, 0);
+    for (int e = 0; e < n; ++e) {
+        if (!names[e] || !dev_ptrs[e]) return fail("sr3_load_weights_dev: null argument");
+        if (ndims[e] < 0 || ndims[e] > 4) return fail("%s: expected at most 4 dims, got %d", names[e], ndims[e]);
+        idx[e] = find_param(c, names[e], shapes + (size_t)4 * e, ndims[e]);
+        if (idx[e] < 0) return -1;
+        if (touched[idx[e]]) return fail("%s: listed twice in one sr3_load_weights_dev call", names[e]);
+        touched[idx[e]] = 1;
+    }
+    const StageLayout L = stage_layout(c);
+    if (!c->d_wmax) {
+        HIP_OK(hipMalloc(&c->d_wmax, np * sizeof(unsigned)));
+        c->weight_bytes += np * sizeof(unsigned);
+    }
+    if (!c->h_stage) HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&c->h_stage), L.total * sizeof(float), hipHostMallocDefault));
+    hipStream_t s = c->stream;
+    const int ci_idx = c->mods[0].conv.w, fc_idx = c->final_conv.w;
+
+    // ---- phase one ----
+    HIP_OK(hipMemsetAsync(c->d_wmax, 0, np * sizeof(unsigned), s));
+    for (int e = 0; e < n; ++e) {
+        Param &p = c->params[idx[e]];
+        const float *src = dev_ptrs[e];
+        if (p.kind != P_CONV) {
+            HIP_OK(hipMemcpyAsync(p.dev, src, p.dev_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+        } else {
+            const size_t src_bytes = (size_t)p.cout * p.cin * p.ks * p.ks * sizeof(float);
+            if (idx[e] == ci_idx && c->ci_w) HIP_OK(hipMemcpyAsync(c->h_stage + L.ci_src, src, src_bytes, hipMemcpyDeviceToHost, s));
+            if (idx[e] == fc_idx && (c->final_wm || c->final_wq))
+                HIP_OK(hipMemcpyAsync(c->h_stage + L.fc_src, src, src_bytes, hipMemcpyDeviceToHost, s));
+            launch_weight_pack(src, p.cout, p.cin, p.ks, p.cin_pad, p.up_phase, p.dev, p.dev_wino, c->d_wmax + idx[e], s);
+            if (p.dev_wino && p.dev_wino_f) launch_wino_frag(p.dev_wino, p.cout, p.cin_pad, p.dev_wino_f, s);
+        }
+        p.host.clear();
+    }
+    // blocks with fused products: the partner of a refreshed tensor is split again with the common exponent, from its own
+    // packed copy, and needs its maximum too
+    bool every_block = true;        // this call refreshed every tensor prepare_fused reads
+    for (auto &m : c->mods) {
+        if (m.kind != M_RES) continue;
+        ResBlock &rb = m.rb;
+        if (rb.has_res) {
+            every_block = every_block && touched[rb.c2.w] && touched[rb.res.w] && touched[rb.c2.b] && touched[rb.res.b];
+            if (touched[rb.c2.w] != touched[rb.res.w]) {
+                const int other = touched[rb.c2.w] ? rb.res.w : rb.c2.w;
+                launch_weight_absmax(c->params[other].dev, c->params[other].dev_floats, c->d_wmax + other, s);
+            }
+            if (touched[rb.c2.b] || touched[rb.res.b]) {
+                if (!rb.fused_bias) HIP_OK(hipMalloc(&rb.fused_bias, (size_t)rb.cout * sizeof(float)));
+                launch_weight_bias_sum(c->params[rb.c2.b].dev, c->params[rb.res.b].dev, rb.cout, rb.fused_bias, s);
+            }
+        } else if (ident_eligible(rb)) {
+            every_block = every_block && touched[rb.c2.w];
+        }
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(c->h_stage, c->d_wmax, np * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));        // the one host synchronisation of a refresh
+
+    // ---- the exponents ----
+    std::vector<int> kexp(np, 0);
+    std::vector<char> resplit(np, 0);
+    for (size_t i = 0; i < np; ++i) {
+        if (c->params[i].kind != P_CONV) continue;
+        kexp[i] = scale_exponent_of_max(c->h_stage[i]);
+        resplit[i] = touched[i];
+    }
+    for (auto &m : c->mods) {
+        if (m.kind != M_RES) continue;
+        ResBlock &rb = m.rb;
+        if (rb.has_res && (touched[rb.c2.w] || touched[rb.res.w])) {
+            const int k = std::min(kexp[rb.c2.w], kexp[rb.res.w]);
+            kexp[rb.c2.w] = kexp[rb.res.w] = k;
+            resplit[rb.c2.w] = resplit[rb.res.w] = 1;
+        } else if (!rb.has_res && ident_eligible(rb) && touched[rb.c2.w]) {
+            kexp[rb.c2.w] = std::min(kexp[rb.c2.w], 15);      // the identity matrix holds 2^k as a half (prepare_fused)
+        }
+    }
+
+    // ---- phase two ----
+    for (size_t i = 0; i < np; ++i) {
+        if (!resplit[i]) continue;
+        Param &p = c->params[i];
+        launch_weight_split(p.dev, p.dev_floats, kexp[i], p.dev_split, s);
+        p.w_unscale = ldexpf(1.0f, -kexp[i]);
+    }
+    for (auto &m : c->mods) {
+        if (m.kind != M_RES || m.rb.has_res || !ident_eligible(m.rb) || !touched[m.rb.c2.w]) continue;
+        ResBlock &rb = m.rb;
+        if (!rb.ident_w) HIP_OK(hipMalloc(&rb.ident_w, (size_t)rb.cout * rb.cout * sizeof(float)));
+        launch_weight_ident(rb.cout, 1.0f / c->params[rb.c2.w].w_unscale, rb.ident_w, s);
+    }
+    if (touched[ci_idx] && c->ci_w) {
+        const Param &p = c->params[ci_idx];
+        c->ci_unscale = pack_conv_in_weight(c->h_stage + L.ci_src, p.cout, p.cin, c->h_stage + L.ci_w);
+        HIP_OK(hipMemcpyAsync(c->ci_w, c->h_stage + L.ci_w, conv_in_weight_floats(p.cout) * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    if (touched[fc_idx] && c->final_wm) {
+        const Param &p = c->params[fc_idx];
+        c->final_unscale = pack_final_conv_mfma_weight(c->h_stage + L.fc_src, p.cin, c->h_stage + L.final_wm);
+        HIP_OK(hipMemcpyAsync(c->final_wm, c->h_stage + L.final_wm, final_conv_mfma_weight_floats(p.cin) * sizeof(float),
+                              hipMemcpyHostToDevice, s));
+    }
+    if (touched[fc_idx] && c->final_wq) {
+        const Param &p = c->params[fc_idx];
+        pack_final_conv_weight(c->h_stage + L.fc_src, p.cout, p.cin, c->h_stage + L.final_wq);
+        HIP_OK(hipMemcpyAsync(c->final_wq, c->h_stage + L.final_wq, (size_t)9 * p.cin * 4 * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    HIP_OK(hipGetLastError());
+
+    for (int e = 0; e < n; ++e) c->params[idx[e]].loaded = true;
+    // sr3_load_weight leaves the fused products to prepare_fused (fused_dirty); here the blocks this call touched are up to
+    // date already, so the flag only stays set for what was pending before — and not even that when this call covered
+    // every such tensor
+    if (every_block) c->fused_dirty = false;
+    c->f8_dirty = true;
+    drop_graphs(c);         // captured steps hold the old w_unscale scalars in their kernel arguments
+    return n;
+}
+
+int64_t sr3_read_weight_layout(sr3_ctx *c, const char *name, int layout, void *host, int64_t cap_bytes) {
+    if (!c || !name || cap_bytes < 0 || (cap_bytes > 0 && !host)) return fail("sr3_read_weight_layout: bad argument");
+    if (layout < 0 || layout >= SR3_N_WEIGHT_LAYOUTS) return fail("sr3_read_weight_layout: layout %d unknown", layout);
+    HIP_OK(hipSetDevice(c->device));
+    int pi = -1;
+    for (size_t i = 0; i < c->params.size(); ++i)
+        if (c->params[i].name == name) { pi = (int)i; break; }
+    if (pi < 0) return fail("unknown parameter '%s'", name);
+    const Param &p = c->params[pi];
+    const float *src = nullptr;
+    size_t floats = 0;
+    const bool conv = p.kind == P_CONV;
+    const size_t wino_floats = (size_t)16 * p.cout * p.cin_pad;
+    switch (layout) {
+    case SR3_WL_PLAIN: src = p.dev; floats = p.dev_floats; break;
+    case SR3_WL_SPLIT: src = p.dev_split; floats = p.dev_floats; break;
+    case SR3_WL_F8: src = p.dev_f8; floats = p.dev_floats; break;
+    case SR3_WL_WINO: src = p.dev_wino; floats = wino_floats; break;
+    case SR3_WL_WINO_FRAG: src = p.dev_wino_f; floats = wino_floats; break;
+    case SR3_WL_CONV_IN:
+        if (conv && pi == c->mods[0].conv.w) { src = c->ci_w; floats = conv_in_weight_floats(p.cout); }
+        break;
+    case SR3_WL_FINAL_MFMA:
+        if (conv && pi == c->final_conv.w) { src = c->final_wm; floats = final_conv_mfma_weight_floats(p.cin); }
+        break;
+    case SR3_WL_FINAL_VALU:
+        if (conv && pi == c->final_conv.w) { src = c->final_wq; floats = (size_t)9 * p.cin * 4; }
+        break;
+    case SR3_WL_FUSED_BIAS:
+        for (auto &m : c->mods)
+            if (m.kind == M_RES && m.rb.has_res && m.rb.c2.b == pi) { src = m.rb.fused_bias; floats = (size_t)m.rb.cout; }
+        break;
+    case SR3_WL_IDENT:
+        for (auto &m : c->mods)
+            if (m.kind == M_RES && !m.rb.has_res && m.rb.c2.w == pi) { src = m.rb.ident_w; floats = (size_t)m.rb.cout * m.rb.cout; }
+        break;
+    }
+    if (!src) return 0;
+    const int64_t bytes = (int64_t)(floats * sizeof(float));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (cap_bytes > 0) HIP_OK(hipMemcpy(host, src, (size_t)std::min(bytes, cap_bytes), hipMemcpyDeviceToHost));
+    return bytes;
+}
+
+float sr3_weight_unscale(sr3_ctx *c, const char *name) {
+    if (!c || !name) { fail("sr3_weight_unscale: null argument"); return 0.f; }
+    for (auto &p : c->params)
+        if (p.name == name) {
+            return p.w_unscale;
+        }
+    fail("unknown parameter '%s'", name);
+    return 0.f;
 }
 
 int sr3_weights_missing(sr3_ctx *c) {

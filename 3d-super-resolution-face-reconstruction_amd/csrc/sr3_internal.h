@@ -303,6 +303,20 @@ StatsRef launch_groupnorm_partials(const TDesc &in0, const TDesc &in1, int B, fl
 int split_scale_exponent(const float *packed, size_t n);
 float split_conv_weight_k(const float *packed, size_t rows, int CinPad, int k, float *dst);
 
+// ---- weight layouts made on the device (kernels_weights.hip; sr3_load_weights_dev) -----------------------------------
+// The device twins of the host helpers above, bit for bit. launch_weight_pack: fp32 OIHW in device memory -> packed
+// [tap][Cout][CinPad] (up_phase: the 16 phase planes), G g G^T planes into `wino` when given (ks 3, not up_phase), and
+// max|w| of what it wrote to `packed` (NaN ignored) as a bit pattern into *wmax by atomic max (zero it first).
+void launch_weight_pack(const float *oihw, int Cout, int Cin, int ks, int CinPad, bool up_phase, float *packed, float *wino,
+                        unsigned *wmax, hipStream_t s);
+// the same maximum of a tensor that is packed already (n a multiple of 4)
+void launch_weight_absmax(const float *packed, size_t n, unsigned *wmax, hipStream_t s);
+// split_conv_weight_k over `floats` packed values (a multiple of 32)
+void launch_weight_split(const float *packed, size_t floats, int k, float *dst, hipStream_t s);
+void launch_weight_bias_sum(const float *a, const float *b, int n, float *dst, hipStream_t s);
+// ResBlock::ident_w of a C-wide block: (fp16)v on the diagonal of the split-f16 [C][C] matrix, zero elsewhere
+void launch_weight_ident(int C, float v, float *dst, hipStream_t s);
+
 // ---- attention core ----------------------------------------------------------------------------
 double launch_attention(const float *qkv, int B, int N, int C, float *out, hipStream_t s);
 // streaming form (online softmax, any N >= 1, no N x N score tile): same operands and result as launch_attention;

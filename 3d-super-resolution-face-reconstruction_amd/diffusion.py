@@ -132,6 +132,14 @@ class GaussianDiffusion(nn.Module):
         refuse them (one buffer cannot hold every step's masks)."""
         self.denoise_fn.set_dropout_masks(masks)
 
+    def tie_weights(self, ref_netG: nn.Module) -> None:
+        """UNet.tie_weights through the `denoise_fn.` prefix: this model's UNet shares the nn.Parameter objects of
+        `ref_netG.denoise_fn.*` (the reference GaussianDiffusion a trainer optimises) and refreshes its kernel layouts on
+        the device whenever they change."""
+        prefix = "denoise_fn."
+        theirs = {k[len(prefix):]: v for k, v in ref_netG.named_parameters() if k.startswith(prefix)}
+        self.denoise_fn.tie_weights(theirs)
+
     @property
     def num_sampling_steps(self) -> int:
         """S: UNet evaluations of one sampling call (num_timesteps = T for the default "ddpm" sampler)."""

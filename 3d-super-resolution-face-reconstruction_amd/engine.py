@@ -187,6 +187,58 @@ class Engine:
         for name, _ in self.param_list():
             self.load_weight(name, sd[prefix + name])
 
+    WEIGHT_LAYOUTS = {"plain": 0, "split": 1, "f8": 2, "wino": 3, "wino_frag": 4, "conv_in": 5, "final_mfma": 6,
+                      "final_valu": 7, "fused_bias": 8, "ident": 9}
+
+    def load_weights_device(self, items: Sequence[Tuple[str, object]]) -> int:
+        """Refreshes the listed parameters from tensors that live on this engine's device: `items` is a list of
+        (name, tensor), the tensors fp32, contiguous, in the reference layout (anything with `data_ptr()`, `shape`,
+        `dtype`, `device`, `is_contiguous()`: torch tensors). Every kernel layout is rebuilt on the device with one host
+        synchronisation for the whole list, and is the same bytes as `load_weight` makes. Returns the number refreshed."""
+        items = list(items)
+        n = len(items)
+        if n == 0:
+            return 0
+        names = (C.c_char_p * n)()
+        ptrs = (C.c_void_p * n)()
+        shapes = (C.c_int64 * (4 * n))()
+        ndims = (C.c_int * n)()
+        for i, (name, t) in enumerate(items):
+            dev = t.device
+            if (str(t.dtype) != "torch.float32" or not t.is_contiguous() or dev.type != "cuda"
+                    or (dev.index is not None and dev.index != self.device)):
+                raise _lib.Sr3Error(f"{name}: load_weights_device needs a contiguous fp32 tensor on device {self.device} "
+                                    f"(got {t.dtype}, {dev}); use load_weight for anything else")
+            if len(t.shape) > 4:
+                raise _lib.Sr3Error(f"{name}: more than 4 dims")
+            names[i] = name.encode()
+            ptrs[i] = t.data_ptr()
+            ndims[i] = len(t.shape)
+            for k, d in enumerate(t.shape):
+                shapes[4 * i + k] = int(d)
+        rc = self.lib.sr3_load_weights_dev(self.ctx, n, names, ptrs, shapes, ndims)
+        _lib.check(min(rc, 0))
+        return int(rc)
+
+    def read_weight_layout(self, name: str, layout) -> Optional[np.ndarray]:
+        """The bytes (uint8 array) of one kernel layout the engine keeps of a parameter (`WEIGHT_LAYOUTS`: a name or an
+        id); None when the parameter has no such layout. For tests and tools."""
+        lid = self.WEIGHT_LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+        size = int(self.lib.sr3_read_weight_layout(self.ctx, name.encode(), lid, None, 0))
+        _lib.check(min(size, 0))
+        if size == 0:
+            return None
+        out = np.empty(size, dtype=np.uint8)
+        _lib.check(min(int(self.lib.sr3_read_weight_layout(self.ctx, name.encode(), lid, out.ctypes.data, size)), 0))
+        return out
+
+    def weight_unscale(self, name: str) -> float:
+        """2^-k of the parameter's split-f16 copy (1.0 for parameters without one)."""
+        v = float(self.lib.sr3_weight_unscale(self.ctx, name.encode()))
+        if v == 0.0:
+            _lib.check(-1)
+        return v
+
     def weights_missing(self) -> int:
         return int(self.lib.sr3_weights_missing(self.ctx))
 

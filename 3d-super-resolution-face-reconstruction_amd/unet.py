@@ -83,6 +83,9 @@ class UNet(nn.Module):
             _register(self, name, nn.Parameter(t))
         self._engine: Optional[Engine] = None
         self._synced = {}
+        self.weight_sync = "host"               # set_weight_sync / tie_weights
+        self.last_refreshed: list = []
+        self.last_refreshed_on_device: list = []
         # conv arithmetic: "f16x3" = split-f16 operands with fp32 accumulation (fp32-equivalent accuracy, ~2.6x
         # faster than "f32" = exact fp32 MFMA); "f16f8" (default) = f16x3 with the two correction products of the
         # MFMA-bound convs (32x32- and 16x16-pixel levels at full batch) on the fp8 matrix path, another 2-3 %
@@ -142,12 +145,60 @@ class UNet(nn.Module):
         if self._engine is not None and getattr(self, "_own_stream", True):
             self._engine.stream_wait_for_engine(0)
 
-    def _sync_weights(self) -> None:
+    def set_weight_sync(self, route: str) -> None:
+        """How changed parameters reach the library. "host" (default): each one through a CPU copy and the host packers
+        (`Engine.load_weight`). "device": all of them in one `Engine.load_weights_device` call that rebuilds the kernel
+        layouts on the GPU from the parameters' own storage, with one host synchronisation — for models whose weights
+        change between sampling calls (an optimiser stepping them). Both routes produce the same bytes."""
+        if route not in ("host", "device"):
+            raise ValueError(f"weight sync route {route!r}: 'host' or 'device'")
+        self.weight_sync = route
+
+    def tie_weights(self, module) -> None:
+        """Registers `module`'s parameters (an nn.Module, or a dict of name -> nn.Parameter) — the SAME nn.Parameter objects, matched by name — as this model's own, and
+        turns the device route on: whoever trains `module` (the reference UNet under torch autograd) keeps optimising its
+        own parameters, and the next call of this model samples with the new values without a copy."""
+        theirs = dict(module) if isinstance(module, dict) else dict(module.named_parameters())
+        mine = list(self.named_parameters())
+        for name, p in mine:
+            q = theirs.get(name)
+            if q is None:
+                raise KeyError(f"tie_weights: the module has no parameter {name!r}")
+            if tuple(q.shape) != tuple(p.shape):
+                raise ValueError(f"tie_weights: {name} is {tuple(q.shape)} in the module, {tuple(p.shape)} here")
+        for name, _ in mine:
+            _register(self, name, theirs[name])
+        self._synced = {}
+        self.set_weight_sync("device")
+
+    def _sync_weights(self) -> int:
+        """Hands every parameter whose storage or version changed to the engine; returns how many. `last_refreshed`
+        keeps their names."""
+        changed = []
         for name, p in self.named_parameters():
             sig = (p.data_ptr(), p._version)
             if self._synced.get(name) != sig:
+                changed.append((name, p, sig))
+        on_device = []
+        for name, p, sig in changed:
+            if (self.weight_sync == "device" and p.dtype == torch.float32 and p.is_contiguous() and p.device.type == "cuda"
+                    and (p.device.index is None or p.device.index == self._engine.device)):
+                on_device.append((name, p.detach()))
+            else:
                 self._engine.load_weight(name, p.detach().to("cpu", torch.float32).contiguous().numpy())
-                self._synced[name] = sig
+            self._synced[name] = sig
+        if on_device:
+            # the library reads the parameters on its own stream: after what torch has enqueued (the optimiser step), and
+            # before anything torch enqueues next
+            cur = torch.cuda.current_stream(self._engine.device)
+            self._own_stream = cur.cuda_stream == 0
+            self._engine.set_stream(cur.cuda_stream)
+            self.ready()
+            self._engine.load_weights_device(on_device)
+            self.finish()
+        self.last_refreshed = [name for name, _, _ in changed]
+        self.last_refreshed_on_device = [name for name, _ in on_device]
+        return len(changed)
 
     # ---- train-mode Dropout (DESIGN.md §3.7) ---------------------------------------------------
     def set_dropout_sampling(self, on: bool, seed: Optional[int] = None) -> None:

@@ -119,6 +119,35 @@ int sr3_load_weight(sr3_ctx *ctx, const char *name, const float *host, const int
 /* number of parameters that have never been loaded (0 = ready) */
 int sr3_weights_missing(sr3_ctx *ctx);
 
+/* The same for n tensors that are in DEVICE memory already (live torch parameters after an optimiser step): fp32,
+ * contiguous, reference layout, on the context's device. names[i], dev_ptrs[i], shapes[4 * i .. 4 * i + ndims[i] - 1].
+ * Every kernel layout is built on the device, enqueued on the context's stream, with ONE host synchronisation per call
+ * (the per-tensor maxima that decide the split-f16 scales have to reach the host); the tensors must stay unchanged until
+ * the call returns. Same checks and errors as the host route, and the layouts are the same bytes. The fused
+ * (conv2 + res_conv) products of the blocks it touches are rebuilt by the call itself. Returns n, or < 0. */
+int sr3_load_weights_dev(sr3_ctx *ctx, int n, const char *const *names, const float *const *dev_ptrs,
+                         const int64_t *shapes, const int *ndims);
+
+/* Read-only introspection (tests, tools): the kernel layouts the context keeps of one parameter. */
+enum {
+    SR3_WL_PLAIN = 0,      /* the fp32 copy: conv weights packed [tap][Cout][CinPad] (Upsample convs: 16 phase planes) */
+    SR3_WL_SPLIT = 1,      /* split-f16 hi | lo per 32-channel chunk */
+    SR3_WL_F8 = 2,         /* F8C copy of the split weights (made on demand in the f16f8 arithmetic) */
+    SR3_WL_WINO = 3,       /* G g G^T [16][Cout][CinPad] */
+    SR3_WL_WINO_FRAG = 4,  /* the same in the one-pass kernel's fragment order (made on demand) */
+    SR3_WL_CONV_IN = 5,    /* first conv: MFMA fragments */
+    SR3_WL_FINAL_MFMA = 6, /* final conv: MFMA fragments */
+    SR3_WL_FINAL_VALU = 7, /* final conv: [9][C][4] */
+    SR3_WL_FUSED_BIAS = 8, /* asked of a block's conv2 bias: conv2 bias + res_conv bias */
+    SR3_WL_IDENT = 9,      /* asked of a block's conv2 weight: the identity-skip matrix */
+    SR3_N_WEIGHT_LAYOUTS = 10
+};
+/* Copies at most cap_bytes of the layout to `host` and returns the layout's size in bytes; 0: the parameter has no such
+ * layout (now); < 0: error. Synchronises the context's stream. */
+int64_t sr3_read_weight_layout(sr3_ctx *ctx, const char *name, int layout, void *host, int64_t cap_bytes);
+/* 2^-k of a conv parameter's split-f16 copy (1 for the others; 0 and an error message: unknown name) */
+float sr3_weight_unscale(sr3_ctx *ctx, const char *name);
+
 /* ---- the denoiser: UNet.forward(x, noise_level)  (unet.py:235-265) ------------------------ */
 
 /* x_dev: [B, in_channel, H, W] NCHW; noise_level_dev: [B]; out_dev: [B, out_channel, H, W]. */
