@@ -1806,6 +1806,27 @@ static ConvKernel wino_form(const ConvParams &p) {
     return (p.stats == nullptr || (p.stats_slices > 0 && (tiles % p.stats_slices) == 0)) ? CK_WINO_THREE_PASS : CK_COUNT;
 }
 
+// second form of the three-pass plan (kernels_wino.hip, wino_gemm_out_kernel): output channels per block, 0 = the
+// position GEMMs + wino_output_kernel. Preconditions: whole channel blocks (wino_shape: Cout % 64 == 0), statistics
+// slices of 16 | 32 tiles (what a block's waves hold whole). Tuning (profiles/README.md finding 86): enough blocks of
+// 64 tiles to fill the chip, as each runs all 16 positions, and Cin small enough for M's traffic to matter
+static int wino_gemm_out_bn(const ConvParams &p, int Cin) {
+    static const bool off = env_int("SR3_NO_WINO_GEMM_OUT", 0) != 0;         // product switches (read once)
+    static const bool force = env_int("SR3_WINO_GEMM_OUT_FORCE", 0) != 0;
+    if (off) return 0;
+    const int tpi = (p.Hout >> 1) * (p.Wout >> 1), Cout = p.out.C;
+    if (p.stats) {
+        const int tps = tpi / p.stats_slices;
+        if (tps != 16 && tps != 32) return 0;
+    }
+    // the epilogue addresses the zero-bordered output (and the residual, same geometry) with 32-bit byte offsets
+    if ((uint64_t)p.out.floats(p.B) * 4 >= (1ull << 32)) return 0;
+    const int bn = (Cout % 128) == 0 ? 128 : 64;
+    if (force) return bn;
+    const long blocks = (((long)p.B * tpi + WINO_GEMM_OUT_TILES - 1) / WINO_GEMM_OUT_TILES) * (Cout / bn);
+    return (blocks >= WINO_GEMM_OUT_MIN_BLOCKS && Cin <= WINO_GEMM_OUT_MAX_CIN) ? bn : 0;
+}
+
 // p as the kernels see it: an upsample conv becomes its four sub-pixel phases over the low-resolution pixels (one
 // launch: blockIdx.z picks (py, px)); splits / phase_slices / phase_part_stride are the plan's to fill
 static ConvParams phase_form(const ConvParams &p_in) {
@@ -1848,7 +1869,10 @@ ConvPlan conv_plan(const ConvParams &p_in) {
     if (wino != CK_COUNT) {
         plan.kernel = wino;
         plan.needs_wino_frag = wino == CK_WINO_ONE_PASS;       // (U and M never leave the CU)
-        if (wino == CK_WINO_THREE_PASS) plan.wino_ws_floats = (size_t)16 * p.B * (p.Hout / 2) * (p.Wout / 2) * (Cin + Cout);
+        if (wino == CK_WINO_THREE_PASS) {
+            plan.wino_ws_floats = (size_t)16 * p.B * (p.Hout / 2) * (p.Wout / 2) * (Cin + Cout);
+            plan.wino_gemm_out = wino_gemm_out_bn(p, Cin);
+        }
         return plan;
     }
     auto split = [&](ConvSplit kind, int splits) {
@@ -1944,7 +1968,7 @@ void launch_wino_gemm(const ConvParams &p_in, hipStream_t s) {
 void launch_conv(const ConvParams &p_in, hipStream_t s) {
     const ConvPlan plan = conv_plan(p_in);
     if (plan.error) { g_conv_error = plan.error; return; }
-    if (plan.kernel == CK_WINO_ONE_PASS || plan.kernel == CK_WINO_THREE_PASS) { launch_conv_wino(p_in, plan.kernel, s); return; }
+    if (plan.kernel == CK_WINO_ONE_PASS || plan.kernel == CK_WINO_THREE_PASS) { launch_conv_wino(p_in, plan, s); return; }
     ConvParams p = phase_form(p_in);     // up2: the weights must be in phase form (make_up2_phase_weights)
     const int HWo = p.Hout * p.Wout;
     const long M = (long)p.B * HWo;

@@ -376,6 +376,282 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     }
 }
 
+// ---- second form of the three-pass plan: the 16 position GEMMs and the output transform in ONE kernel ----------------
+// U -> wino_gemm_out_kernel -> output: M never goes through memory (it is four times the conv's output), and one block
+// runs ONE K loop of 16 * Cin / 32 steps instead of 16 blocks with Cin / 32 steps, a pipeline fill and an M-tile store each.
+// Block = WG_BT consecutive tiles (global tile index of U, so A rows are contiguous in every position plane) x BN output
+// channels; 2 x BN/32 consumer waves with ONE 32x32 accumulator tile each, 4 producer waves (conv_igemm_dma_f32's
+// pipeline, swizzle and v_mfma_f32_32x32x2_f32 fragment mapping; the K loop runs over (position, 32-channel step)).
+// Bit-identical to launch_wino_gemm + wino_output_kernel:
+//   * every position's chain starts from zero and adds its K-steps in ascending order (kk = 0..3, elements x, y, z, w):
+//     the bits of M[pos] as conv_igemm_dma_f32 leaves them, whatever its tile;
+//   * the positions are walked column-major (pos = 4a + b, b outer) and folded with per-lane adds in the accumulator
+//     layout, in wino_output_kernel's left-to-right order: u0 = (M0b + M1b) + M2b, u1 = (M1b - M2b) - M3b,
+//     y.0 = (u.[0] + u.[1]) + u.[2], y.1 = (u.[1] - u.[2]) - u.[3]: 7 accumulator sets (t, u0, u1, four y) x 16 registers;
+//   * the epilogue order is the direct kernel's (bias, residual, FeatureWiseAffine bias);
+//   * the statistics of a slice of tps = 16 | 32 tiles are added as wino_output_kernel does (tile lane k mod 16: its
+//     tiles in order, four pixels each; then the lanes in order): a lane holds whole tiles, tiles k and k + 16 of a
+//     32-tile slice are accumulator registers r and r + 8 of the same lane, and the running sum over the 16 tile lanes
+//     alternates between the two lane halves (rows 0-3 | 4-7 | 8-11 | 12-15) through three exchanges. No LDS, no atomics.
+// Whole channel blocks (Cout % BN == 0); rows past the last tile are clamped (min(t, tiles - 1)) and never stored.
+constexpr int WG_BT = 64;                   // 2x2 output tiles per block
+constexpr int WG_NS = 3;                    // LDS pipeline stages (4 stages, or two K-steps per stage and barrier: measured the same)
+
+template <int N>
+__device__ __forceinline__ void wg_producer_sync() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+    __builtin_amdgcn_s_barrier();
+}
+
+// keeps a value (and the adds that made it) where the program has it
+__device__ __forceinline__ void wg_pin(f32x16 &x) { asm volatile("" : "+v"(x)); }
+
+template <int BN>
+__global__ __launch_bounds__((2 * (BN / 32) + 4) * 64) void wino_gemm_out_kernel(const ConvParams p, const float *__restrict__ U,
+                                                                                  int Cin, int tps) {
+#pragma clang fp contract(off)
+    constexpr int BT = WG_BT, NS = WG_NS;
+    constexpr int WGN = BN / 32, NC = 2 * WGN;          // consumer waves: 2 (tiles) x WGN (channels)
+    constexpr int AR = BT / 32, BR = BN / 32;           // DMA instructions per producer wave and K-step
+    constexpr int STAGE = (BT + BN) * 32;               // floats per pipeline stage
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    int *rowpix = reinterpret_cast<int *>(smem + NS * STAGE);   // [BT] padded output pixel of the tile's (0, 0)
+    int *rowimg = rowpix + BT;                                  // [BT] image
+
+    const int Cout = p.out.C, th = p.Hout >> 1, tw = p.Wout >> 1, tpi = th * tw;
+    const int tiles = p.B * tpi;
+    const int tilesN = Cout / BN;
+    int bid = blockIdx.x;                   // XCD-aware remap (conv_igemm_dma_f32): the channel blocks of a tile range share an L2
+    {
+        const int nwg = gridDim.x;
+        const int xcd = bid & 7, loc = bid >> 3;
+        const int qq = nwg >> 3, rr = nwg & 7;
+        bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + loc;
+    }
+    const int t0 = (bid / tilesN) * BT;
+    const int n0 = (bid % tilesN) * BN;
+    const int nc = Cin >> 5;                // K-steps per position
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+
+    if (wid >= NC) {
+        // ------------------------------- producer waves -------------------------------------
+        const int w = wid - NC;
+        const int tid = threadIdx.x - NC * 64;
+        if (tid < BT) {
+            const int t = min(t0 + tid, tiles - 1);
+            const int n = t / tpi, rem = t - n * tpi;
+            const int ty = rem / tw, tx = rem - ty * tw;
+            rowpix[tid] = (int)p.out.pix(n, 2 * ty, 2 * tx);
+            rowimg[tid] = n;
+        }
+        // DMA instruction i of this wave fills rows (4i + w) * 8 + (lane >> 3); uniform 64-bit base per position and
+        // K-step, per-lane 32-bit byte offsets constant over the whole K loop (conv_igemm_dma_f32)
+        const int rsub = lane >> 3;
+        const unsigned schunk16 = (unsigned)(((lane & 7) ^ ((((w & 1) << 2) | (lane >> 4)) & 7)) * 16);
+        unsigned vA[AR], vB[BR];
+        wf_static_for<AR>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            const int t = min(t0 + (4 * i + w) * 8 + rsub, tiles - 1);
+            vA[i] = (unsigned)t * (unsigned)Cin * 4u + schunk16;
+        });
+        wf_static_for<BR>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            const int n = n0 + (4 * i + w) * 8 + rsub;
+            vB[i] = (unsigned)n * (unsigned)Cin * 4u + schunk16;
+        });
+        const size_t uplane = (size_t)tiles * Cin, wplane = (size_t)Cout * Cin;
+        int k = 0, stage = 0;
+        for (int b = 0; b < 4; ++b)
+            for (int a = 0; a < 4; ++a) {
+                const int ps = 4 * a + b;
+                const float *ub = U + (size_t)ps * uplane, *wb = p.w_wino + (size_t)ps * wplane;
+                for (int c0 = 0; c0 < Cin; c0 += 32) {
+                    float *Ad = smem + stage * STAGE + w * 256;
+                    float *Bd = Ad + BT * 32;
+                    const char *ab = reinterpret_cast<const char *>(ub + c0);
+                    const char *bb = reinterpret_cast<const char *>(wb + c0);
+                    wf_static_for<AR>([&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        wf_dma16(ab, vA[i], Ad + i * 1024);
+                    });
+                    wf_static_for<BR>([&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        wf_dma16(bb, vB[i], Bd + i * 1024);
+                    });
+                    if (k >= NS - 2) wg_producer_sync<(NS - 2) * (AR + BR)>();
+                    ++k;
+                    stage = stage + 1 == NS ? 0 : stage + 1;
+                }
+            }
+        wf_static_for<NS - 2>([&](auto rc) {          // drain: the last NS-2 tiles are still in flight
+            constexpr int r = NS - 3 - decltype(rc)::value;
+            wg_producer_sync<r * (AR + BR)>();
+        });
+        __syncthreads();
+        return;
+    }
+
+    // ----------------------------------- consumer waves -----------------------------------------
+    const int li = lane & 31, lh = lane >> 5;
+    const int wm = wid / WGN, wn = wid % WGN;
+    const int swz = (li >> 1) & 7;
+    const float *Abase = smem + (wm * 32 + li) * 32;
+    const float *Bbase = smem + BT * 32 + (wn * 32 + li) * 32;
+    int koff[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) koff[kk] = (((2 * kk + lh) ^ swz) & 7) * 4;
+    f32x4 fa[4], fb[4];
+#define WG_FRAG_READ(SET, CUR, KK)                                                              \
+    {                                                                                           \
+        fa[SET] = *reinterpret_cast<const f32x4 *>(Abase + (CUR) * STAGE + koff[KK]);           \
+        fb[SET] = *reinterpret_cast<const f32x4 *>(Bbase + (CUR) * STAGE + koff[KK]);           \
+    }
+#define WG_FRAG_MMA(SET)                                                                        \
+    {                                                                                           \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[SET].x, fb[SET].x, acc, 0, 0, 0);         \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[SET].y, fb[SET].y, acc, 0, 0, 0);         \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[SET].z, fb[SET].z, acc, 0, 0, 0);         \
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[SET].w, fb[SET].w, acc, 0, 0, 0);         \
+    }
+    int cur = 0;
+    // M[pos] of this wave's 32 tiles x 32 channels: nc K-steps from zero
+    auto chain = [&](f32x16 &acc) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int c = 0; c < nc; ++c) {
+            const int nxt = cur + 1 == NS ? 0 : cur + 1;
+            // Group kk has its own register set; every read is issued one MFMA group (256 cycles) before the wait that
+            // covers it. Scheduling barriers: left alone, the scheduler reuses one set and waits right behind each read.
+            WG_FRAG_MMA(0)
+            __builtin_amdgcn_sched_barrier(0);
+            WG_FRAG_READ(2, cur, 2)
+            __builtin_amdgcn_sched_barrier(0);
+            WG_FRAG_MMA(1)
+            __builtin_amdgcn_sched_barrier(0);
+            WG_FRAG_READ(3, cur, 3)
+            __builtin_amdgcn_sched_barrier(0);
+            WG_FRAG_MMA(2)
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();                   // every read of this stage has been issued and waited
+            WG_FRAG_READ(0, nxt, 0)            // next K-step, whichever position it belongs to (stale data after the
+            WG_FRAG_READ(1, nxt, 1)            // last one: unused)
+            __builtin_amdgcn_sched_barrier(0);
+            WG_FRAG_MMA(3)
+            __builtin_amdgcn_sched_barrier(0);
+            cur = nxt;
+        }
+    };
+    f32x16 t, u0, u1, y[2][2];
+    __syncthreads();
+    WG_FRAG_READ(0, 0, 0)
+    WG_FRAG_READ(1, 0, 1)
+    wf_static_for<4>([&](auto bc) {
+        constexpr int b = decltype(bc)::value;
+        // (the folds are pinned where they stand: left to the optimiser they sink to the epilogue and all 16 M tiles
+        // stay live, 256 registers)
+        chain(u0);                              // a = 0
+        chain(u1);                              // a = 1
+        u0 += u1;
+        wg_pin(u0);
+        chain(t);                               // a = 2
+        u0 += t;
+        u1 -= t;
+        wg_pin(u0); wg_pin(u1);
+        chain(t);                               // a = 3
+        u1 -= t;
+        wg_pin(u1);
+        if constexpr (b == 0) { y[0][0] = u0; y[1][0] = u1; }
+        if constexpr (b == 1) { y[0][0] += u0; y[1][0] += u1; y[0][1] = u0; y[1][1] = u1; }
+        if constexpr (b == 2) { y[0][0] += u0; y[1][0] += u1; y[0][1] -= u0; y[1][1] -= u1; }
+        if constexpr (b == 3) { y[0][1] -= u0; y[1][1] -= u1; }
+        wg_pin(y[0][0]); wg_pin(y[0][1]); wg_pin(y[1][0]); wg_pin(y[1][1]);
+    });
+#undef WG_FRAG_READ
+#undef WG_FRAG_MMA
+
+    // epilogue: lane (li, lh) holds channel col of tiles wm * 32 + (r & 3) + 8 (r >> 2) + 4 lh, r = 0..15
+    const unsigned col = (unsigned)(n0 + wn * 32 + li);
+    const float bs = p.bias ? p.bias[col] : 0.f;
+    const unsigned Wp = (unsigned)p.out.Wp(), uC = (unsigned)Cout;
+    const bool want_stats = p.stats != nullptr;
+    const bool pair = tps == 32;               // a slice is the wave's 32 tiles (else its rows 0-15 and 16-31 are two slices)
+    double run[2][2] = {{0, 0}, {0, 0}};       // [slice of the wave: rows 0-15 | 16-31][sum, sum of squares]
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {              // tile lanes 8g .. 8g+7: registers 4g .. 4g+3 of both lane halves
+        double s1[2][4], s2[2][4];             // partials of tile lane (r & 3) + 8g + 4 lh in the two slices
+#pragma unroll
+        for (int h = 0; h < 2; ++h)            // h = 1: registers r + 8 (tiles + 16)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int r = 8 * h + 4 * g + j;
+                const int row = wm * 32 + 16 * h + 8 * g + 4 * lh + j;
+                const unsigned pix = (unsigned)rowpix[row];
+                const bool ok = t0 + row < tiles;
+                const float cb = p.chan_bias ? p.chan_bias[(size_t)rowimg[row] * p.chan_bias_stride + col] : 0.f;
+                double a1 = (h == 1 && pair) ? s1[0][j] : 0.0, a2 = (h == 1 && pair) ? s2[0][j] : 0.0;
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+                    for (int cc = 0; cc < 2; ++cc) {
+                        const unsigned off = (pix + rr * Wp + cc) * uC + col;
+                        float add = bs;        // (the direct kernel's epilogue order: bias, residual, FeatureWiseAffine bias)
+                        if (p.resid.p) add += p.resid.p[off];
+                        if (p.chan_bias) add += cb;
+                        const float o = y[rr][cc][r] + add;
+                        if (ok) p.out.p[off] = o;
+                        if (want_stats) { a1 += (double)o; a2 = fma((double)o, (double)o, a2); }
+                    }
+                s1[h][j] = a1; s2[h][j] = a2;
+                __builtin_amdgcn_sched_barrier(0);      // one tile's four pixels in flight at a time: bounds the registers
+            }
+        if (want_stats) {
+            // the lanes of half 0 add their four tile lanes, hand the sum to half 1, which adds its four
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+#pragma unroll
+                for (int sl = 0; sl < 2; ++sl) {
+                    // slice 0 of a 32-tile slice carries the chained partials in s.[1]; two 16-tile slices carry s.[sl]
+                    double a = run[sl][0], q = run[sl][1];
+                    if (g + hh > 0) { a = __shfl_xor(a, 32); q = __shfl_xor(q, 32); }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        a += (pair ? s1[1][j] : s1[sl][j]);
+                        q += (pair ? s2[1][j] : s2[sl][j]);
+                    }
+                    run[sl][0] = a; run[sl][1] = q;
+                }
+            }
+        }
+    }
+    if (want_stats && lh == 1) {
+#pragma unroll
+        for (int sl = 0; sl < 2; ++sl) {
+            if (pair && sl == 1) break;
+            const int first = t0 + wm * 32 + 16 * sl;           // first tile of the slice
+            if (first < tiles) {
+                double *o = p.stats + ((size_t)(first / tps) * Cout + col) * 2;
+                o[0] = run[sl][0]; o[1] = run[sl][1];
+            }
+        }
+    }
+}
+
+template <int BN>
+void launch_wino_gemm_out(const ConvParams &o, const float *U, int Cin, hipStream_t s) {
+    static bool attr_set = false;           // (more than 64 KiB of dynamic LDS at BN = 128)
+    constexpr size_t lds = ((size_t)WG_NS * (WG_BT + BN) * 32 + 2 * WG_BT) * sizeof(float);
+    auto kern = wino_gemm_out_kernel<BN>;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
+    }
+    const int tpi = (o.Hout / 2) * (o.Wout / 2), tiles = o.B * tpi;
+    const int tps = o.stats ? tpi / o.stats_slices : 0;
+    const unsigned blocks = (unsigned)((tiles + WG_BT - 1) / WG_BT) * (unsigned)(o.out.C / BN);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3((2 * (BN / 32) + 4) * 64), lds, s, o, U, Cin, tps);
+}
+
 int out_slices(const ConvParams &p) {
     const int tiles = (p.Hout >> 1) * (p.Wout >> 1);
     if (p.stats) return p.stats_slices;
@@ -430,7 +706,8 @@ void launch_wino_frag(const float *wino, int Cout, int CinPad, float *dst, hipSt
     hipLaunchKernelGGL(wino_frag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wino, Cout, CinPad, dst);
 }
 
-void launch_conv_wino(const ConvParams &p, ConvKernel form, hipStream_t s) {
+void launch_conv_wino(const ConvParams &p, const ConvPlan &plan, hipStream_t s) {
+    const ConvKernel form = plan.kernel;
     const int H = p.Hout, W = p.Wout, Cout = p.out.C;
     const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
     ConvParams o = p;
@@ -466,6 +743,13 @@ void launch_conv_wino(const ConvParams &p, ConvKernel form, hipStream_t s) {
     const size_t items = tiles * (Cin / 4);
     if (!p.u_ready)
         hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p.in0, p.in1, p.B, U);
+
+    if (plan.wino_gemm_out) {
+        // second form: position GEMMs + output transform in one kernel (the M half of the workspace stays unused)
+        if (plan.wino_gemm_out == 128) launch_wino_gemm_out<128>(o, U, Cin, s);
+        else launch_wino_gemm_out<64>(o, U, Cin, s);
+        return;
+    }
 
     ConvParams g;
     g.in0.p = U; g.in0.C = Cin; g.in0.H = H / 2; g.in0.W = W / 2; g.in0.pad = 0;

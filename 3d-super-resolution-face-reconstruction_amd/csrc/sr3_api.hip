@@ -158,6 +158,7 @@ struct sr3_ctx {
     bool strict_range = false;
     int fallback_calls = 0;             // calls finished by the f32 fallback since sr3_create
     int gn_wino_passes = 0;             // GroupNorm apply passes launched as launch_gn_wino_input / _fold_ since sr3_create
+    int wino_gemm_out_launches = 0;     // three-pass Winograd convs launched in the one-kernel form (ConvPlan::wino_gemm_out) since sr3_create
     float *ckpt = nullptr;              // sr3_sample: NCHW copy of the sampler state at the last clean checkpoint
     size_t ckpt_floats = 0;
     double *metrics_ws = nullptr;       // sr3_metrics_psnr_ssim / sr3_denoise_loss: per-block fp64 partial sums (grows on demand)
@@ -841,13 +842,19 @@ bool gn_writes_u(const sr3_ctx *c, const ConvCall &k, bool raw_wanted, int in_sp
     return conv_plan(conv_params(c, k)).kernel == CK_WINO_THREE_PASS;
 }
 
+// launch_conv on the context's stream; counts the convs whose plan takes the one-kernel form of the three-pass Winograd plan
+static void ctx_launch_conv(sr3_ctx *c, const ConvParams &p) {
+    if (conv_plan(p).wino_gemm_out) ++c->wino_gemm_out_launches;
+    launch_conv(p, c->stream);
+}
+
 void run_conv(sr3_ctx *c, const ConvCall &k) {
     const ConvRef &cv = *k.conv;
     const TDesc &a = k.in, &out = k.out;
     const int B = k.B;
     const ConvParams p = conv_params(c, k);
     c->pbegin(F_CONV);
-    launch_conv(p, c->stream);
+    ctx_launch_conv(c, p);
     if (c->prof) {
         char tag[160];
         const int cin2 = k.fused1x1 ? k.fused1x1->cin : 0;
@@ -2355,6 +2362,7 @@ int sr3_set_range_policy(sr3_ctx *c, int strict) {
 }
 int sr3_fallback_calls(sr3_ctx *c) { return c ? c->fallback_calls : fail("null context"); }
 int sr3_gn_wino_passes(sr3_ctx *c) { return c ? c->gn_wino_passes : fail("null context"); }
+int sr3_wino_gemm_out_launches(sr3_ctx *c) { return c ? c->wino_gemm_out_launches : fail("null context"); }
 int sr3_replay_calls(sr3_ctx *c) { return c ? c->replay_calls : fail("null context"); }
 void *sr3_test_flag_address(sr3_ctx *c) { return c ? c->d_ovf : nullptr; }
 const char *sr3_last_warning(void) { return g_warn.c_str(); }
@@ -2514,7 +2522,7 @@ static int op_conv2d_impl(const char *what, sr3_ctx *c, const float *in0_dev, in
         }
         p.u_ready = to_u ? 1 : 0;
         p.no_halo_split = c->halo_split_off ? 1 : 0;
-        launch_conv(p, c->stream);
+        ctx_launch_conv(c, p);
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("%s: launch failed", what);
         if (const char *e = conv_take_error()) return fail("%s: %s", what, e);
         return 0;

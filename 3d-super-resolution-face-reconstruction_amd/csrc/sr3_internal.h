@@ -8,7 +8,7 @@
 namespace sr3 {
 
 // ---- environment switches ---------------------------------------------------------------------------
-// Everything the library reads from the environment (INTEGRATION.md lists the same six; each is read once per process
+// Everything the library reads from the environment (INTEGRATION.md lists the same eight; each is read once per process
 // and then baked into captured graphs):
 //   SR3_NO_GRAPH=1          every kernel launched individually, no hipGraph replay (hosts that cannot capture)
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
@@ -17,6 +17,10 @@ namespace sr3 {
 //   SR3_NO_WINOGRAD=1       exact-f32 3x3 convs always on the direct implicit-GEMM kernel (conv_plan)
 //   SR3_NO_GN_WINO=1        three-pass Winograd convs always behind gn_apply + wino_input_kernel: the GroupNorm apply
 //                           pass never writes the transformed input itself (no conv-plan switch: every plan stays)
+//   SR3_NO_WINO_GEMM_OUT=1  three-pass Winograd convs always as position GEMMs + wino_output_kernel (M through memory);
+//                           same bits
+//   SR3_WINO_GEMM_OUT_FORCE=1  that one-kernel form wherever its preconditions hold, whatever the block count and Cin
+//                           (tests, per-shape timing)
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Activation tensor: NHWC fp32 with an optional 1-pixel zero border ("pad") stored around every
@@ -187,6 +191,9 @@ struct ConvPlan {
     int stats_slices = 0;
     size_t wino_ws_floats = 0;         // ConvParams::wino_ws: U [16][B*H*W/4][Cin] + M [16][B*H*W/4][Cout] (three-pass form)
     bool needs_wino_frag = false;      // reads ConvParams::w_wino_f (one-pass form)
+    // CK_WINO_THREE_PASS only: 0 = position GEMMs + wino_output_kernel; 64 | 128 = wino_gemm_out_kernel with that many
+    // output channels per block (the M half of wino_ws then stays unused). Not part of the exported plan.
+    int wino_gemm_out = 0;
     const char *error = nullptr;       // a request no kernel honours (ConvParams::f8 on a shape outside the F8C kernel)
 };
 // reads p as launch_conv does: a null part / tile_cnt / w_wino / w_wino_f / wino_ws / stats means "not offered", and the
@@ -225,7 +232,17 @@ void make_wino_weights(const float *packed9, int Cout, int CinPad, float *dst);
 void make_wino_weights_frag(const float *wino, int Cout, int CinPad, float *dst);
 void launch_wino_frag(const float *wino, int Cout, int CinPad, float *dst, hipStream_t s);
 // the Winograd form conv_plan chose (CK_WINO_ONE_PASS | CK_WINO_THREE_PASS)
-void launch_conv_wino(const ConvParams &p, ConvKernel form, hipStream_t s);
+void launch_conv_wino(const ConvParams &p, const ConvPlan &plan, hipStream_t s);
+// Second form of the three-pass plan (ConvPlan::wino_gemm_out): U -> wino_gemm_out_kernel -> output. One block owns
+// WINO_GEMM_OUT_TILES consecutive tiles x 64 | 128 output channels, walks the 16 positions in ONE K loop and folds
+// A^T M A in the accumulators, so M is never stored; bit-identical to launch_wino_gemm + wino_output_kernel. Each block
+// runs 16 times longer than a position-GEMM block, so the form is taken only from WINO_GEMM_OUT_MIN_BLOCKS blocks on
+// (fewer: the position-parallel form, whose 16 x more blocks spread further), and up to WINO_GEMM_OUT_MAX_CIN input
+// channels (what it saves is M's traffic, fixed per conv; its K loop is no faster than the position GEMMs').
+constexpr int WINO_GEMM_OUT_TILES = 64;
+constexpr int WINO_GEMM_OUT_MIN_BLOCKS = 256;
+constexpr int WINO_GEMM_OUT_MAX_CIN = 256;
+// (tests/test_gpu_wino_gemm_out.py restates the gate with both constants: retune them there too)
 // the 16 position GEMMs of one Winograd conv on conv_igemm_dma_f32 (kernels_conv.hip); p as described at zbatch
 void launch_wino_gemm(const ConvParams &p, hipStream_t s);
 // host helper: OIHW -> [tap][Cout][CinPad] (zero pad input channels up to CinPad)

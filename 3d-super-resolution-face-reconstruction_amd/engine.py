@@ -147,6 +147,11 @@ class Engine:
         the conv behind them, since the engine was created; 0 under SR3_NO_GN_WINO=1 and outside the f32 mode."""
         return int(self.lib.sr3_gn_wino_passes(self.ctx))
 
+    def wino_gemm_out_launches(self) -> int:
+        """Three-pass Winograd convs this engine launched (or captured into a graph) in the form that runs the position GEMMs
+        and the output transform in one kernel; 0 under SR3_NO_WINO_GEMM_OUT=1 and outside the f32 mode."""
+        return int(self.lib.sr3_wino_gemm_out_launches(self.ctx))
+
     def replay_calls(self) -> int:
         """Calls finished after replaying work whose in-place split-K wait had given up (SR3_OK_REPLAYED)."""
         return int(self.lib.sr3_replay_calls(self.ctx))

@@ -235,6 +235,9 @@ int sr3_replay_calls(sr3_ctx *ctx);
 /* GroupNorm apply passes launched (or captured into a graph) since sr3_create in the form that writes the Winograd input
  * transform of the three-pass conv behind them (exact f32 only; 0 under SR3_NO_GN_WINO=1): tells a test which route ran. */
 int sr3_gn_wino_passes(sr3_ctx *ctx);
+/* Three-pass Winograd convs this context launched (or captured into a graph) since sr3_create in the form that runs the position GEMMs
+ * and the output transform in one kernel (0 under SR3_NO_WINO_GEMM_OUT=1): tells a test which form ran. */
+int sr3_wino_gemm_out_launches(sr3_ctx *ctx);
 /* TEST HOOK (tests/test_gpu_round4.py): device address of the context's flag word (bit 0: range overflow, bit 1: an
  * in-place split-K wait gave up), so that a test kernel on another stream can raise a bit in the middle of a running
  * sr3_sample call and the replay logic is exercised deterministically. Not for production use. */

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark for the implicit-GEMM conv (development tool; run on the GPU box):
-    python tools/conv_bench.py [--iters N] [--set main|all]
-Prints ms and TFLOP/s per shape of the B=64, 128x128 SR3 step."""
+    python tools/conv_bench.py [--iters N] [--set main|wino3] [--only i,j,...]
+Prints ms and TFLOP/s per shape of the B=64, 128x128 SR3 step (--set wino3: every distinct shape of its three-pass
+Winograd convs, timed from U on: the position GEMMs + output transform, in whichever form the plan takes)."""
 import argparse
 import importlib
 import os
@@ -35,9 +36,15 @@ MAIN = [
     (64, 64, 64, 256, 128, 128, 3, 1, 0, 2, 0, 1),
 ]
 
+# the three-pass Winograd shapes of the step: 32x32 (-> 256), 16x16 (-> 512), 8x8 (-> 512); Cin of x || skip inputs in C0
+WINO3 = [(64, 32, 32, cin, 0, 256, 3, 1, 0, 2, 1, 1) for cin in (128, 256, 384, 512, 768)] + \
+        [(64, 16, 16, cin, 0, 512, 3, 1, 0, 2, 1, 1) for cin in (256, 512, 768, 1024)] + \
+        [(64, 8, 8, cin, 0, 512, 3, 1, 0, 2, 1, 1) for cin in (512, 1024)]
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--set", type=str, default="main", choices=["main", "wino3"])
     ap.add_argument("--only", type=str, default="", help="comma list of shape indices")
     ap.add_argument("--precision", type=str, default="f32", choices=["f32", "f16x3", "f16f8"])
     args = ap.parse_args()
@@ -47,7 +54,8 @@ if __name__ == "__main__":
     Engine = importlib.import_module(PKG + ".engine").Engine
     e = Engine(synth.tiny_unet_config(), 0)
     e.set_precision(args.precision)
-    shapes = MAIN if not args.only else [MAIN[int(i)] for i in args.only.split(",")]
+    table = WINO3 if args.set == "wino3" else MAIN
+    shapes = table if not args.only else [table[int(i)] for i in args.only.split(",")]
     for (B, H, W, C0, C1, Cout, ks, st, up, mode, rs, cb) in shapes:
         ms, ams = e.bench_conv(B, H, W, C0, C1, Cout, ks, st, up, mode, rs, cb, args.iters)
         Ho, Wo = (H * (2 if up else 1)) // st, (W * (2 if up else 1)) // st
