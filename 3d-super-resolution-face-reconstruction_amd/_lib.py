@@ -118,6 +118,10 @@ PROTOTYPES = {
     "sr3_metrics_psnr_ssim": (_I, [_P, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sr3_denoise_loss": (_I, [_P, _F, _F, _I, _I, _F, _F, _F, _I, _U64, _U64, _I, _I, _I, _I, _P, _F, _F]),
     "sr3_op_q_sample": (_I, [_P, _F, _I, _I, _F, _F, _F, _I, _U64, _U64, _I, _I, _I, _I, _F]),
+    "sr3_lr_operators_host": (_I, [_I, _I, _P, _P]),
+    "sr3_set_lr_consistency": (_I, [_P, _F, _I, _I, _I, _U64, C.c_float]),
+    "sr3_op_lr_project": (_I, [_P, _F, _I, _I, _I, _I, _F, _I, _I, _I, _U64, C.c_float, _I]),
+    "sr3_lr_residual": (_I, [_P, _F, _I, _I, _I, _I, _F, _I, _I, _I, _U64, _P, _P]),
     "sr3_dev_malloc": (_I, [_P, _U64, C.POINTER(_P)]),
     "sr3_dev_free": (_I, [_P, _P]),
     "sr3_memcpy_h2d": (_I, [_P, _P, _P, _U64]),
@@ -128,7 +132,7 @@ PROTOTYPES = {
 # counters and opt-in entry points added to the C-ABI after its first A/B-able build (load)
 NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_set_dropout", "sr3_set_dropout_masks", "sr3_dropout_layers",
                   "sr3_dropout_mask_bytes", "sr3_op_dropout_mask", "sr3_load_weights_dev", "sr3_read_weight_layout",
-                  "sr3_weight_unscale")
+                  "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual")
 
 _lib = None
 

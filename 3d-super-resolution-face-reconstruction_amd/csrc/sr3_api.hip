@@ -6,6 +6,7 @@
 #include "../../include/sr3hip.h"
 #include "sr3_internal.h"
 
+#include <limits.h>
 #include <math.h>
 #include <cmath>
 #include <stdarg.h>
@@ -142,7 +143,8 @@ struct sr3_ctx {
     bool split() const { return mode != A_F32; }        // split-f16 operands (f16x3 or f16f8)
     // "f16f8": the two correction products of eligible convs run on the fp8 matrix path (ConvParams::f8, conv_f8_supported)
     bool f8() const { return mode == A_F16F8; }
-    int graph_slot() const { return (int)mode; }        // which of the three captured step graphs
+    // which captured step graph: one per arithmetic, and per arithmetic one with the consistency projection in the step
+    int graph_slot() const { return (int)mode + (lr_on() ? 3 : 0); }
     // split format of an activated conv input (launch_gn_apply's `split`): 0 fp32, 1 split-f16, 2 F8C when the consumer
     // conv takes the fp8 operands (f8_conv() said so)
     int act_format(bool f8_operand) const { return split() ? (f8_operand ? 2 : 1) : 0; }
@@ -187,6 +189,24 @@ struct sr3_ctx {
     uint64_t drop_base = 0;                     // ... and its offset in the injected buffer
     bool drop_live() const { return drop_on && drop_thr > 0; }
 
+    // Low-resolution consistency (sr3_set_lr_consistency). Off by default: a step then launches exactly
+    // the kernels it always did. lr: the host copy of what d_lr holds; lr_cur / lr_cur_lds: the operators and the form of
+    // the current sampling call (sr3_sample_begin), launch arguments of the captured steps 3..5.
+    struct LrDev { float *buf = nullptr; int *bounds = nullptr; LrOps ops; };
+    std::map<std::tuple<int, int, int, int>, LrDev> lr_ops;     // per (lh, lw, H, W), built on first use
+    LrArgs lr;
+    int lr_lh = 0, lr_lw = 0;
+    LrArgs *d_lr = nullptr, *h_lr = nullptr;    // device copy <- pinned host ring (as StepArgs: the copy is asynchronous)
+    static constexpr int kLrRing = 64;
+    uint64_t lr_count = 0;
+    float *x0hat = nullptr;             // NCHW [B][out_channel][H][W]: the predicted x0 between the two halves of the update
+    size_t x0hat_floats = 0;
+    float *lr_scratch = nullptr;        // T | U | R of the multi-launch projection and of the residual score
+    size_t lr_scratch_n = 0;
+    LrOps lr_cur;
+    bool lr_cur_lds = false;
+    bool lr_on() const { return lr.lr != nullptr && lr.strength != 0.f; }
+
     // workspace for one (B, H, W)
     int wB = 0, wH = 0, wW = 0;
     char *arena = nullptr;
@@ -220,8 +240,9 @@ struct sr3_ctx {
     StepArgs *h_ring = nullptr, *d_step = nullptr;
     uint64_t step_count = 0;
     // one p_sample step captured as a hipGraph (per precision); rebuilt when the workspace changes
-    hipGraphExec_t step_graph[3] = {nullptr, nullptr, nullptr};   // per arithmetic: f32, f16x3, f16f8
-    int graph_warm[3] = {0, 0, 0};
+    static constexpr int kGraphs = 6;   // per arithmetic (f32, f16x3, f16f8), without | with the consistency projection
+    hipGraphExec_t step_graph[kGraphs] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int graph_warm[kGraphs] = {0, 0, 0, 0, 0, 0};
     bool no_graph = false;
 
     // profiling
@@ -1323,7 +1344,7 @@ int check_ready(sr3_ctx *c) {
 }
 
 void drop_graphs(sr3_ctx *c) {
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < sr3_ctx::kGraphs; ++i) {
         if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
         c->step_graph[i] = nullptr;
         c->graph_warm[i] = 0;
@@ -1394,6 +1415,89 @@ int push_drop_args(sr3_ctx *c, const char *what, uint64_t image_offset) {
     return push_step_args(c, sa);
 }
 
+// ---- low-resolution consistency: operators and buffers ---------------------------------------------------------------
+void drop_lr_graphs(sr3_ctx *c) {
+    for (int i = 3; i < sr3_ctx::kGraphs; ++i) {
+        if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
+        c->step_graph[i] = nullptr;
+        c->graph_warm[i] = 0;
+    }
+}
+
+int check_lr_shape(const char *what, int C, int H, int W, int N, int lh, int lw) {
+    if (C <= 0 || N <= 0 || lh <= 0 || lw <= 0 || H <= lh || W <= lw)
+        return fail("%s: needs C, N > 0 and an LR size below the image size on both axes (got C=%d N=%d, %dx%d -> %dx%d)", what, C,
+                    N, lh, lw, H, W);
+    return 0;
+}
+
+// the device operators of (lh, lw) -> (H, W), built on first use and kept for the life of the context (captured steps
+// hold their addresses)
+int get_lr_ops(sr3_ctx *c, int lh, int lw, int H, int W, LrOps *out) {
+    const auto key = std::make_tuple(lh, lw, H, W);
+    auto it = c->lr_ops.find(key);
+    if (it != c->lr_ops.end()) { *out = it->second.ops; return 0; }
+    std::vector<double> Av((size_t)lh * H), Pv((size_t)H * lh), Ah((size_t)lw * W), Ph((size_t)W * lw);
+    std::vector<int> bnd((size_t)2 * (lh + lw));
+    if (!lr_operators(lh, H, Av.data(), Pv.data(), bnd.data()) || !lr_operators(lw, W, Ah.data(), Ph.data(), bnd.data() + 2 * lh))
+        return fail("low-resolution operators %dx%d -> %dx%d: the Gram matrix is not positive definite", lh, lw, H, W);
+    // A_v | A_h | P_v | P_h^T
+    const size_t nAv = Av.size(), nAh = Ah.size(), nPv = Pv.size(), nPh = Ph.size();
+    std::vector<float> h(nAv + nAh + nPv + nPh);
+    for (size_t i = 0; i < nAv; ++i) h[i] = (float)Av[i];
+    for (size_t i = 0; i < nAh; ++i) h[nAv + i] = (float)Ah[i];
+    for (size_t i = 0; i < nPv; ++i) h[nAv + nAh + i] = (float)Pv[i];
+    for (int x = 0; x < W; ++x)
+        for (int j = 0; j < lw; ++j) h[nAv + nAh + nPv + (size_t)j * W + x] = (float)Ph[(size_t)x * lw + j];
+    sr3_ctx::LrDev d;
+    HIP_OK(hipMalloc(&d.buf, h.size() * sizeof(float)));
+    if (hipMalloc(&d.bounds, bnd.size() * sizeof(int)) != hipSuccess) { (void)hipFree(d.buf); return fail("allocating the LR operators failed"); }
+    if (hipMemcpy(d.buf, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d.bounds, bnd.data(), bnd.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d.buf); (void)hipFree(d.bounds);
+        return fail("uploading the LR operators failed");
+    }
+    d.ops.Av = d.buf; d.ops.Ah = d.buf + nAv; d.ops.Pv = d.buf + nAv + nAh; d.ops.PhT = d.buf + nAv + nAh + nPv;
+    d.ops.bv = d.bounds; d.ops.bh = d.bounds + 2 * lh;
+    d.ops.lh = lh; d.ops.lw = lw; d.ops.H = H; d.ops.W = W;
+    c->lr_ops[key] = d;
+    *out = d.ops;
+    return 0;
+}
+
+// scratch of the multi-launch form / the residual score; a new allocation invalidates the captured steps that hold it
+int ensure_lr_scratch(sr3_ctx *c, size_t floats) {
+    if (c->lr_scratch_n >= floats) return 0;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (c->lr_scratch) HIP_OK(hipFree(c->lr_scratch));
+    c->lr_scratch = nullptr; c->lr_scratch_n = 0;
+    drop_lr_graphs(c);
+    HIP_OK(hipMalloc(&c->lr_scratch, floats * sizeof(float)));
+    c->lr_scratch_n = floats;
+    return 0;
+}
+
+// sr3_sample_begin with the feature on: operators, form, x0 buffer and scratch of this call's shape
+int prepare_lr_step(sr3_ctx *c, int B, int H, int W) {
+    const int C = c->cfg.out_channel;
+    if (check_lr_shape("sr3_sample_begin (low-resolution consistency)", C, H, W, c->lr.N, c->lr_lh, c->lr_lw)) return -1;
+    LrOps o;
+    if (get_lr_ops(c, c->lr_lh, c->lr_lw, H, W, &o)) return -1;
+    const bool lds = lr_lds_fits(o);
+    if (o.Av != c->lr_cur.Av || lds != c->lr_cur_lds) drop_lr_graphs(c);
+    c->lr_cur = o; c->lr_cur_lds = lds;
+    const size_t need = (size_t)B * C * H * W;
+    if (c->x0hat_floats < need) {
+        HIP_OK(hipStreamSynchronize(c->stream));
+        if (c->x0hat) HIP_OK(hipFree(c->x0hat));
+        c->x0hat = nullptr; c->x0hat_floats = 0;
+        drop_lr_graphs(c);
+        HIP_OK(hipMalloc(&c->x0hat, need * sizeof(float)));
+        c->x0hat_floats = need;
+    }
+    return lds ? 0 : ensure_lr_scratch(c, lr_scratch_floats(B * C, o));
+}
+
 // the launches of one p_sample step (embedding, UNet body, DDPM update); every per-step value is
 // read from c->d_step, so the sequence is identical for every t
 void enqueue_step(sr3_ctx *c) {
@@ -1410,7 +1514,14 @@ void enqueue_step(sr3_ctx *c) {
     u.ovf = c->split() ? c->d_ovf : nullptr;    // (the packed copy is only read in split-f16 mode)
     u.hist = c->xhist;                          // constant per workspace: the captured graph stays valid
     c->pbegin(F_MISC);
-    launch_ddpm_update(u, B, c->stream);
+    if (c->lr_on()) {
+        // x0 prediction | projection onto {x : A x = y} | the rest of the update
+        launch_x0_predict(u, c->x0hat, B, c->stream);
+        launch_lr_project(c->x0hat, B * u.C, u.C, c->lr_cur, c->lr, c->d_lr, c->lr_cur_lds, c->lr_scratch, c->stream);
+        launch_update_from_x0(u, c->x0hat, B, c->stream);
+    } else {
+        launch_ddpm_update(u, B, c->stream);
+    }
     c->pend();
 }
 
@@ -1419,6 +1530,9 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     if (t < 0 || t >= c->T) return fail("step t=%d outside schedule of %d steps", t, c->T);
     // (the arithmetic mode may have been switched between steps: the F8C weight copies are made on demand)
     if (prepare_f8(c)) return -1;
+    if (c->lr_on() && (c->lr_cur.lh != c->lr_lh || c->lr_cur.lw != c->lr_lw || c->lr_cur.H != c->wH || c->lr_cur.W != c->wW ||
+                       c->x0hat_floats < (size_t)c->wB * c->cfg.out_channel * c->wH * c->wW))
+        return fail("p_sample step: low-resolution consistency was turned on or resized after sr3_sample_begin; set it before");
     StepArgs *slot = next_step_slot(c);
     if (!slot) return -1;
     StepArgs &sa = *slot;
@@ -1642,6 +1756,11 @@ void sr3_destroy(sr3_ctx *c) {
     if (c->h_ovf) (void)hipHostFree(c->h_ovf);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     if (c->d_step) (void)hipFree(c->d_step);
+    for (auto &kv : c->lr_ops) { (void)hipFree(kv.second.buf); (void)hipFree(kv.second.bounds); }
+    if (c->d_lr) (void)hipFree(c->d_lr);
+    if (c->h_lr) (void)hipHostFree(c->h_lr);
+    if (c->x0hat) (void)hipFree(c->x0hat);
+    if (c->lr_scratch) (void)hipFree(c->lr_scratch);
     for (auto &r : c->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
@@ -1709,6 +1828,12 @@ int sr3_wino_weights_host(const float *packed_host, int Cout, int CinPad, int fr
     std::vector<float> wv((size_t)16 * Cout * CinPad);
     make_wino_weights(packed_host, Cout, CinPad, wv.data());
     make_wino_weights_frag(wv.data(), Cout, CinPad, dst_host);
+    return 0;
+}
+
+int sr3_lr_operators_host(int l, int r, double *A, double *P) {
+    if (!A || !P || l <= 0 || r <= l) return fail("sr3_lr_operators_host: needs 0 < l < r and both outputs");
+    if (!lr_operators(l, r, A, P, nullptr)) return fail("sr3_lr_operators_host: the Gram matrix of %d -> %d is not positive definite", r, l);
     return 0;
 }
 
@@ -2213,6 +2338,7 @@ int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, con
     c->seed = seed;
     c->image_offset = image_offset;
     c->hist_valid = false;
+    if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
     if (range_reset(c)) return -1;
     c->pbegin(F_MISC);
     if (cond_dev) launch_nchw_to_nhwc(cond_dev, B, nc, c->x0, 0, c->stream);
@@ -2848,6 +2974,70 @@ int sr3_metrics_psnr_ssim(sr3_ctx *c, const float *sr, const float *hr, int B, i
     if (ensure_partials(c, (size_t)blocks)) return -1;         // one fp64 partial per block
     HIP_OK(hipMemsetAsync(ssd, 0, (size_t)B * sizeof(int64_t), c->stream));   // the blocks ADD their shares
     launch_metrics(sr, hr, B, N, row_offset, H, W, gauss11, c->metrics_ws, ssd, ssim, c->stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- low-resolution consistency --------------------------------------------------
+int sr3_set_lr_consistency(sr3_ctx *c, const float *lr_dev, int N, int lh, int lw, uint64_t row_offset, float strength) {
+    if (!c) return fail("null context");
+    if (!lr_dev || strength == 0.f) {       // off: the steps launch what they always did (graphs 0..2)
+        c->lr = LrArgs();
+        return 0;
+    }
+    if (!(strength > 0.f) || strength > 1.f) return fail("sr3_set_lr_consistency: strength must lie in [0, 1], got %g", (double)strength);
+    if (N <= 0 || lh <= 0 || lw <= 0) return fail("sr3_set_lr_consistency: needs N, lh, lw > 0 (got %d, %d, %d)", N, lh, lw);
+    HIP_OK(hipSetDevice(c->device));
+    if (!c->d_lr) HIP_OK(hipMalloc(&c->d_lr, sizeof(LrArgs)));
+    if (!c->h_lr) HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&c->h_lr), sizeof(LrArgs) * sr3_ctx::kLrRing, hipHostMallocDefault));
+    // (never reuse a ring slot whose copy may still be pending)
+    if (c->lr_count && (c->lr_count % (sr3_ctx::kLrRing / 2)) == 0) HIP_OK(hipStreamSynchronize(c->stream));
+    LrArgs &a = c->h_lr[c->lr_count++ % sr3_ctx::kLrRing];
+    a = LrArgs();
+    a.lr = lr_dev; a.row_offset = row_offset; a.N = N; a.strength = strength;
+    // the copy runs on the stream behind the steps enqueued so far, which still read the old values
+    HIP_OK(hipMemcpyAsync(c->d_lr, &a, sizeof(LrArgs), hipMemcpyHostToDevice, c->stream));
+    if (lh != c->lr_lh || lw != c->lr_lw) drop_lr_graphs(c);        // the LR size is a launch argument of the captured steps
+    c->lr = a; c->lr_lh = lh; c->lr_lw = lw;
+    return 0;
+}
+
+int sr3_op_lr_project(sr3_ctx *c, float *x_dev, int B, int C, int H, int W, const float *lr_dev, int N, int lh, int lw,
+                      uint64_t row_offset, float strength, int form) {
+    if (!c || !x_dev || !lr_dev) return fail("sr3_op_lr_project: null argument");
+    if (B <= 0 || form < 0 || form > 2) return fail("sr3_op_lr_project: needs B > 0 and form 0 (auto) | 1 (LDS) | 2 (scratch)");
+    if (check_lr_shape("sr3_op_lr_project", C, H, W, N, lh, lw)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    LrOps o;
+    if (get_lr_ops(c, lh, lw, H, W, &o)) return -1;
+    if (form == 1 && !lr_lds_fits(o))
+        return fail("sr3_op_lr_project: the LDS form needs %zu bytes per plane, above its %zu", lr_lds_bytes(o), LR_LDS_MAX_BYTES);
+    const bool lds = form == 1 || (form == 0 && lr_lds_fits(o));
+    if (!lds && ensure_lr_scratch(c, lr_scratch_floats(B * C, o))) return -1;
+    LrArgs a;
+    a.lr = lr_dev; a.row_offset = row_offset; a.N = N; a.strength = strength;
+    c->pbegin(F_MISC);
+    launch_lr_project(x_dev, B * C, C, o, a, nullptr, lds, c->lr_scratch, c->stream);
+    c->pend();
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int sr3_lr_residual(sr3_ctx *c, const float *img_dev, int B, int C, int H, int W, const float *lr_dev, int N, int lh, int lw,
+                    uint64_t row_offset, double *sumsq_dev, float *maxabs_dev) {
+    if (!c || !img_dev || !lr_dev || !sumsq_dev || !maxabs_dev) return fail("sr3_lr_residual: null argument");
+    if (B <= 0) return fail("sr3_lr_residual: needs B > 0");
+    if (check_lr_shape("sr3_lr_residual", C, H, W, N, lh, lw)) return -1;
+    if ((size_t)C * lh * lw > (size_t)INT_MAX) return fail("sr3_lr_residual: the LR image is too large");
+    HIP_OK(hipSetDevice(c->device));
+    LrOps o;
+    if (get_lr_ops(c, lh, lw, H, W, &o)) return -1;
+    if (ensure_lr_scratch(c, lr_scratch_floats(B * C, o))) return -1;
+    LrArgs a;
+    a.lr = lr_dev; a.row_offset = row_offset; a.N = N; a.strength = 0.f;
+    c->pbegin(F_MISC);
+    launch_lr_residual(img_dev, B, C, o, a, c->lr_scratch, sumsq_dev, maxabs_dev, c->stream);
+    c->pend();
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -405,6 +405,43 @@ void launch_philox_normal(uint64_t seed, uint64_t image, uint32_t draw, int n, f
 void launch_dropout_mask(uint64_t seed, uint64_t image, uint32_t draw, int layer, uint32_t thr, int C, int H, int W,
                          uint8_t *out, hipStream_t s);
 
+// ---- low-resolution consistency (kernels_consist.hip) --------------------------------------------------
+// The operators of one size pair (lh, lw) -> (H, W), fp32 on the device: A_v [lh][H] and A_h [lw][W] dense with the band of
+// every row in bv / bh ({first, count} pairs), P_v [H][lh], and P_h transposed, PhT [lw][W].
+struct LrOps {
+    const float *Av = nullptr, *Ah = nullptr, *Pv = nullptr, *PhT = nullptr;
+    const int *bv = nullptr, *bh = nullptr;
+    int lh = 0, lw = 0, H = 0, W = 0;
+};
+// What varies between calls. The sampler's kernels read it from device memory (`dyn`), like StepArgs: a captured step
+// keeps its launch arguments. Batch row b is held to lr[(row_offset + b) % N] (NCHW [N][C][lh][lw]).
+struct LrArgs {
+    const float *lr = nullptr;
+    uint64_t row_offset = 0;
+    int N = 1;
+    float strength = 0.f;
+};
+// host, float64: A [l][r] (Pillow's real bicubic weights of the r -> l resample, rows normalised), P [r][l] = A^T (A A^T)^-1,
+// bounds [l][2] (optional); false if the Gram matrix is not positive definite
+bool lr_operators(int l, int r, double *A, double *P, int *bounds);
+// X <- X + strength * P_v (Y - A_v X A_h^T) P_h^T in place on `planes` = B*C planes of x (NCHW). lds_form: one block per
+// plane with the intermediates in LDS (lr_lds_fits); else four launches over scratch (lr_scratch_floats). Both forms run
+// the same arithmetic in the same order. dyn (device) overrides val when not null.
+constexpr size_t LR_LDS_MAX_BYTES = 64 * 1024;
+size_t lr_lds_bytes(const LrOps &o);
+bool lr_lds_fits(const LrOps &o);
+size_t lr_scratch_floats(int planes, const LrOps &o);
+void launch_lr_project(float *x, int planes, int C, const LrOps &o, const LrArgs &val, const LrArgs *dyn, bool lds_form,
+                       float *scratch, hipStream_t s);
+// per image b: sumsq[b] = sum over its C planes of (A img - y)^2 (fp32 residuals, fp64 sum), maxabs[b] = max |A img - y|;
+// scratch as for the projection
+void launch_lr_residual(const float *img, int B, int C, const LrOps &o, const LrArgs &val, float *scratch, double *sumsq,
+                        float *maxabs, hipStream_t s);
+// launch_ddpm_update in two halves: the clamped x0 prediction into x0hat (NCHW [B][C][H][W]), and the rest of the update
+// reading x0 from there (between them: launch_lr_project on x0hat)
+void launch_x0_predict(const UpdateParams &p, float *x0hat, int B, hipStream_t s);
+void launch_update_from_x0(const UpdateParams &p, const float *x0hat, int B, hipStream_t s);
+
 // ---- Philox normal stream (device functions; the kernels that draw from it: kernels_misc.hip, kernels_loss.hip) ----
 // Philox4x32-10 (Salmon et al. 2011). CPU twin: oracle/philox.py.
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

@@ -60,6 +60,21 @@ def noise_coefficient(levels) -> np.ndarray:
     return np.sqrt(np.float32(1) - a * a)
 
 
+def lr_to_tensor(lr) -> torch.Tensor:
+    """The LR images the consistency projection holds a sample to, as fp32 [N,3,l,l] in [-1,1]: an fp32 NCHW tensor is
+    taken as it is (the dataset's `LR` entry), uint8 [N,l,l,3] (HWC crops) is mapped as the dataset maps them, ToTensor and
+    min_max (-1, 1): (u8 / 255) * 2 - 1 in fp32 (datasets/util.py:76-83)."""
+    lr = torch.as_tensor(lr)
+    if lr.dtype == torch.uint8:
+        if lr.dim() != 4 or lr.shape[-1] != 3:
+            raise RuntimeError(f"uint8 LR images must be [N,l,l,3], got {tuple(lr.shape)}")
+        x = lr.to(torch.float32) / 255.0
+        return (x * 2.0 + (-1.0)).permute(0, 3, 1, 2).contiguous()
+    if lr.dtype != torch.float32 or lr.dim() != 4:
+        raise RuntimeError(f"LR images must be fp32 [N,C,l,l] in [-1,1] or uint8 [N,l,l,3], got {lr.dtype} {tuple(lr.shape)}")
+    return lr.contiguous()
+
+
 class GaussianDiffusion(nn.Module):
     def __init__(self, denoise_fn, image_size, channels=3, loss_type="l1", conditional=True,
                  schedule_opt=None):
@@ -73,6 +88,7 @@ class GaussianDiffusion(nn.Module):
         self._sched_np = None
         self._sched_pushed = None   # engine id the schedule was pushed to
         self._sampler = ("ddpm", None, 0.0)   # set_sampler(); not part of state_dict()
+        self._lr = None                       # set_lr_consistency(): (fp32 [N,C,lh,lw], strength); not part of state_dict()
 
     # ---- reference surface that is configuration only -----------------------------------------
     def set_loss(self, device=None):
@@ -117,6 +133,44 @@ class GaussianDiffusion(nn.Module):
         _samplers.check_sampler(kind, steps, eta, self.num_timesteps if self._sched_np is not None else None)
         self._sampler = (kind, None if steps is None or kind == "ddpm" else int(steps), float(eta))
         self._sched_pushed = None
+
+    def set_lr_consistency(self, lr, strength: float = 1.0) -> None:
+        """Keeps every sample consistent with its low-resolution input: each step of every sampling
+        entry point projects its x0 prediction onto the images whose antialiased bicubic downsample — the reference's
+        degradation, datasets/tool/prepare_data.py:37-47 — is the LR image, so the result provably downsamples to it
+        (strength 1; 0 < strength < 1 moves that fraction of the way) and only what the LR image cannot see is left to
+        the network. lr: fp32 [N,3,l,l] in [-1,1] (the dataset's `LR` entry) or uint8 [N,l,l,3] (lr_to_tensor); batch
+        row b is held to lr[(image_offset + b) % N], so samples x images batches, chunks and shards pass the images once.
+        None (or strength 0) turns it off: the sampler is then bit for bit what it was. The setting survives set_sampler
+        and set_new_noise_schedule and adds nothing to state_dict(). p_sample stays the reference's single step."""
+        if lr is None or float(strength) == 0.0:
+            self._lr = None
+            return
+        if not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f"strength must lie in [0, 1], got {strength}")
+        t = lr_to_tensor(lr)
+        if t.shape[1] != self.channels:
+            raise RuntimeError(f"LR images need {self.channels} channels, got {tuple(t.shape)}")
+        self._lr = (t, float(strength))
+
+    def _arm_lr(self, eng, dev, H: int, W: int, row_offset: int):
+        """Puts the engine's consistency setting in the state the next sampling call needs; returns the LR tensor on the
+        device (the caller keeps it alive until the call is enqueued and ordered)."""
+        if self._lr is None:
+            if getattr(eng, "_lr_on", False):
+                eng.set_lr_consistency(None)
+                eng._lr_on = False
+            return None
+        t, strength = self._lr
+        if t.device != dev:
+            t = t.to(dev)
+            self._lr = (t, strength)
+        N, _, lh, lw = t.shape
+        if lh >= H or lw >= W:
+            raise RuntimeError(f"LR images of {lh}x{lw} cannot constrain samples of {H}x{W}")
+        eng.set_lr_consistency(t.data_ptr(), N, lh, lw, int(row_offset), strength)
+        eng._lr_on = True
+        return t
 
     def set_dropout_sampling(self, on: bool, seed: Optional[int] = None) -> None:
         """Opt in to sampling the UNet's Dropout as the reference does under .train() (unet.py:81-91; model 3 samples
@@ -238,6 +292,7 @@ class GaussianDiffusion(nn.Module):
         self.denoise_fn.arm_dropout(eng)            # (one dropout seed per call; the chunks pass their image offset)
         if n_chunks == 1:
             self.denoise_fn.ready()
+            self._arm_lr(eng, dev, H, W, image_offset)
             eng.sample(x.data_ptr() if x is not None else None, B, H, W, out.data_ptr(),
                        noise.data_ptr() if noise is not None else None, seed, image_offset,
                        frames.data_ptr() if frames is not None else None)
@@ -260,6 +315,7 @@ class GaussianDiffusion(nn.Module):
             oc = out[a:b] if whole else torch.empty((chunk, C, H, W), dtype=torch.float32, device=dev)
             fc = torch.empty((frames.shape[0], chunk, C, H, W), dtype=torch.float32, device=dev) if continous else None
             self.denoise_fn.ready()
+            self._arm_lr(eng, dev, H, W, image_offset + a)
             eng.sample(xc.data_ptr() if xc is not None else None, chunk, H, W, oc.data_ptr(),
                        nc.data_ptr() if nc is not None else None, seed, image_offset + a,
                        fc.data_ptr() if fc is not None else None)
@@ -327,6 +383,9 @@ class GaussianDiffusion(nn.Module):
 
         def one_step():
             self.denoise_fn.ready()
+            if getattr(eng, "_lr_on", False):       # (the reference's single step: never projected)
+                eng.set_lr_consistency(None)
+                eng._lr_on = False
             eng.sample_begin(cond.data_ptr() if cond is not None else None, B, H, W, x.data_ptr(), 0, 0)
             eng.sample_step(int(t), nz.data_ptr() if nz is not None else None)
             eng.sample_end(out.data_ptr())

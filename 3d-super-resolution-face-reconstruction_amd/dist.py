@@ -4,7 +4,9 @@ backend is "nccl"; "gloo" in the CPU tests). The reference itself is single-proc
 (SURVEY.md §0, §8e); every image's chain is independent, so this is the whole exchange.
 
 RNG: rank r samples images [start, stop) with `image_offset=start`, so the device Philox stream of
-image i is the same whatever the world size.
+image i is the same whatever the world size. The same offset is the first global row of the shard for the low-resolution
+consistency projection (GaussianDiffusion.set_lr_consistency: row b is held to lr[(image_offset + b) % N]), so every
+rank is given the whole LR batch and picks its rows itself.
 """
 from __future__ import annotations
 

@@ -85,6 +85,15 @@ def conv_plan(B: int, H: int, W: int, Cin: int, Cout: int, ks: int = 3, stride: 
             "wino_ws_floats": v[9], "needs_wino_frag": bool(v[10]), "f8": bool(v[11])}
 
 
+def lr_operators(l: int, r: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(A [l,r], P [r,l]) in float64 for one axis of the r -> l bicubic resample: A the real weights of Pillow's
+    precompute_coeffs with rows normalised, P = A^T (A A^T)^-1 (sr3_lr_operators_host). Host only: needs
+    no GPU and no context."""
+    A, P = np.empty((int(l), int(r)), dtype=np.float64), np.empty((int(r), int(l)), dtype=np.float64)
+    _lib.check(_lib.load().sr3_lr_operators_host(int(l), int(r), A.ctypes.data, P.ctypes.data))
+    return A, P
+
+
 class Engine:
     def __init__(self, cfg: UNetConfig, device: int = 0):
         self.lib = _lib.load()
@@ -342,6 +351,55 @@ class Engine:
     def philox_normal_into(self, seed: int, image: int, draw: int, n: int, out_ptr: int) -> None:
         """Device Philox stream of (seed, image, draw) written to a device buffer (stream-ordered)."""
         _lib.check(self.lib.sr3_philox_normal(self.ctx, seed, image, draw, n, out_ptr))
+
+    # ---- low-resolution consistency (DESIGN.md §3.5c) --------------------------------------------
+    def set_lr_consistency(self, lr_ptr: Optional[int], N: int = 0, lh: int = 0, lw: int = 0, row_offset: int = 0,
+                           strength: float = 1.0) -> None:
+        """While set, every sampling step projects its x0 prediction onto the images whose bicubic downsample is the LR
+        input: batch row b is held to lr[(row_offset + b) % N], lr fp32 [N,C,lh,lw] in [-1,1] on the device (it must
+        outlive the calls). None or strength 0 turns it off (sr3_set_lr_consistency). Set before sample / sample_begin."""
+        _lib.check(self.lib.sr3_set_lr_consistency(self.ctx, lr_ptr or None, int(N), int(lh), int(lw), int(row_offset),
+                                                   float(strength) if lr_ptr else 0.0))
+
+    LR_FORMS = {"auto": 0, "lds": 1, "scratch": 2}
+
+    def lr_project(self, x_ptr: int, B: int, C_: int, H: int, W: int, lr_ptr: int, N: int, lh: int, lw: int,
+                   row_offset: int = 0, strength: float = 1.0, form: str = "auto") -> None:
+        """X <- X + strength * P_v (Y - A_v X A_h^T) P_h^T in place on x fp32 [B,C,H,W] (sr3_op_lr_project;
+        stream-ordered). form: 'auto' | 'lds' (one block per plane) | 'scratch' (one launch per stage)."""
+        _lib.check(self.lib.sr3_op_lr_project(self.ctx, x_ptr, B, C_, H, W, lr_ptr, N, lh, lw, int(row_offset), float(strength),
+                                              self.LR_FORMS[form]))
+
+    def lr_residual(self, img_ptr: int, B: int, C_: int, H: int, W: int, lr_ptr: int, N: int, lh: int, lw: int,
+                    row_offset: int, sumsq_ptr: int, maxabs_ptr: int) -> None:
+        """Per row b: sum (A img - y)^2 -> fp64 [B] at sumsq_ptr, max |A img - y| -> fp32 [B] at maxabs_ptr, against
+        lr[(row_offset + b) % N] (sr3_lr_residual; stream-ordered)."""
+        _lib.check(self.lib.sr3_lr_residual(self.ctx, img_ptr, B, C_, H, W, lr_ptr, N, lh, lw, int(row_offset), sumsq_ptr,
+                                            maxabs_ptr))
+
+    def lr_project_np(self, x, lr, row_offset: int = 0, strength: float = 1.0, form: str = "auto") -> np.ndarray:
+        """numpy convenience: x [B,C,H,W], lr [N,C,lh,lw] -> the projected x."""
+        x, lr = _host_f32(x), _host_f32(lr)
+        B, C_, H, W = x.shape
+        N, _, lh, lw = lr.shape
+        dx, dl = self.to_device(x), self.to_device(lr)
+        self.lr_project(dx.ptr, B, C_, H, W, dl.ptr, N, lh, lw, row_offset, strength, form)
+        out = dx.download(x.shape)
+        dx.free(); dl.free()
+        return out
+
+    def lr_residual_np(self, img, lr, row_offset: int = 0) -> Dict[str, np.ndarray]:
+        """numpy convenience: {"sumsq": float64 [B], "max_abs": float32 [B]} of img [B,C,H,W] against lr [N,C,lh,lw]."""
+        img, lr = _host_f32(img), _host_f32(lr)
+        B, C_, H, W = img.shape
+        N, _, lh, lw = lr.shape
+        di, dl = self.to_device(img), self.to_device(lr)
+        ds, dm = self.buffer(2 * B), self.buffer(B)
+        self.lr_residual(di.ptr, B, C_, H, W, dl.ptr, N, lh, lw, row_offset, ds.ptr, dm.ptr)
+        out = {"sumsq": ds.download().view(np.float64).copy(), "max_abs": dm.download()}
+        for b in (di, dl, ds, dm):
+            b.free()
+        return out
 
     # ---- train-mode Dropout (DESIGN.md §3.7) ---------------------------------------------------
     def set_dropout(self, enable: bool, seed: int = 0, image_offset: int = 0) -> None:

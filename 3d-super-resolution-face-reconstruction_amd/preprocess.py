@@ -7,9 +7,10 @@ import torch
 
 
 @torch.no_grad()
-def bicubic_sr(netG_or_unet, lr_u8: torch.Tensor, r: int, return_u8: bool = False):
+def bicubic_sr(netG_or_unet, lr_u8: torch.Tensor, r: int, return_u8: bool = False, return_lr: bool = False):
     """lr_u8: [B,l,l,3] uint8 CUDA tensor (HWC, RGB) -> fp32 [B,3,r,r] in [-1,1] on the same device
-    (and the resized uint8 [B,r,r,3] if return_u8)."""
+    (and the resized uint8 [B,r,r,3] if return_u8; and, last, the crops themselves as fp32 [B,3,l,l] in [-1,1] if
+    return_lr: the `y` of GaussianDiffusion.set_lr_consistency)."""
     unet = getattr(netG_or_unet, "denoise_fn", netG_or_unet)
     eng = unet.engine()
     if lr_u8.dtype != torch.uint8 or lr_u8.dim() != 4 or lr_u8.shape[-1] != 3:
@@ -21,4 +22,8 @@ def bicubic_sr(netG_or_unet, lr_u8: torch.Tensor, r: int, return_u8: bool = Fals
     unet.ready()
     eng.preprocess_bicubic(x.data_ptr(), B, H, W, r, r, out.data_ptr(), u8.data_ptr() if return_u8 else None)
     unet.finish()
-    return (out, u8) if return_u8 else out
+    res = (out, u8) if return_u8 else (out,)
+    if return_lr:
+        from .diffusion import lr_to_tensor
+        res = res + (lr_to_tensor(x),)
+    return res if len(res) > 1 else res[0]

@@ -103,6 +103,31 @@ def device_scores(netG, images: "torch.Tensor", hr: "torch.Tensor", row_offset: 
     return {"psnr": scores_from_sums(ssd.cpu().numpy(), 3 * H * W), "ssim": ss.cpu().numpy()}
 
 
+def lr_consistency(netG, images: "torch.Tensor", lr, row_offset: int = 0) -> Dict[str, np.ndarray]:
+    """How far `images` [B,3,H,W] (CUDA) are from downsampling to their low-resolution inputs, on the device
+    (sr3_lr_residual): row b is scored against lr[(row_offset + b) % N] (fp32 [N,3,l,l] in [-1,1] or uint8 [N,l,l,3]) under
+    the reference's degradation in real arithmetic, A = the antialiased bicubic resample. Needs no HR
+    image: the SR3 paper's "consistency". Returns {"mse": float64 [B] mean squared residual, "max_abs": float32 [B]}."""
+    import torch
+    from .diffusion import lr_to_tensor
+    from .postprocess import _check, _unet
+
+    img = _check(images)
+    y = lr_to_tensor(lr).to(img.device)
+    B, C, H, W = img.shape
+    N, Cl, lh, lw = y.shape
+    if Cl != C or lh >= H or lw >= W:
+        raise RuntimeError(f"images {tuple(img.shape)} and lr {tuple(y.shape)} do not match")
+    ss = torch.empty(B, dtype=torch.float64, device=img.device)
+    mx = torch.empty(B, dtype=torch.float32, device=img.device)
+    unet = _unet(netG)
+    eng = unet.engine()
+    unet.ready()
+    eng.lr_residual(img.data_ptr(), B, C, H, W, y.data_ptr(), N, lh, lw, int(row_offset), ss.data_ptr(), mx.data_ptr())
+    unet.finish()
+    return {"mse": ss.cpu().numpy() / float(C * lh * lw), "max_abs": mx.cpu().numpy()}
+
+
 def _gather_rows(local: "torch.Tensor", n_total: int, gpu: "torch.device") -> "torch.Tensor":
     """dist.all_gather_images for a tensor on any device: the collective runs where the backend has one — host memory
     for gloo, the rank's GPU `gpu` for nccl (RCCL) — and the result comes back on `local`'s device."""
@@ -116,7 +141,7 @@ def _gather_rows(local: "torch.Tensor", n_total: int, gpu: "torch.device") -> "t
 
 def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 1,
                    seed: Optional[int] = None, sharded: bool = False, metrics: str = "host",
-                   keep_images: bool = True) -> Dict[str, np.ndarray]:
+                   keep_images: bool = True, lr=None) -> Dict[str, np.ndarray]:
     """Runs `samples` independent SR3 chains per conditioning image as one batch of N*samples
     images (sample k of image i is batch row k*N + i) and scores them against `hr`.
 
@@ -133,9 +158,23 @@ def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 
     own shard (dist.shard_bounds; a rank left without rows samples nothing) and the ranks exchange the two score
     arrays — on the GPU with nccl / RCCL, through host memory with gloo; the images are gathered only if keep_images.
     keep_images=False: "images" is None in the result.
+
+    lr (fp32 [N,3,l,l] in [-1,1] or uint8 [N,l,l,3]): adds "consistency" ([samples, N] mean squared residual of every
+    sample against its LR image, lr_consistency) and "mean_consistency". That score needs no HR image: with lr given, hr
+    may be None, and "psnr" / "ssim" and their means are then None. Whether the chains are PROJECTED onto their LR images
+    is netG's setting (GaussianDiffusion.set_lr_consistency), not this argument's.
     """
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics must be 'host' or 'device', got {metrics!r}")
+    if hr is None and lr is None:
+        raise ValueError("validate_batch needs hr (PSNR / SSIM), lr (consistency) or both")
+    if lr is not None:
+        from .diffusion import lr_to_tensor
+        lr = lr_to_tensor(lr)
+        if lr.shape[0] != sr.shape[0]:
+            raise ValueError(f"lr holds {lr.shape[0]} images, sr {sr.shape[0]}")
+    if hr is None:
+        return _validate_lr_only(netG, sr, lr, samples, seed, sharded, keep_images)
     import torch
     from . import dist as _dist
 
@@ -178,9 +217,38 @@ def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 
                 ps[k, i] = psnr(a, b)
                 ss[k, i] = calculate_ssim(a, b)
     finite = np.isfinite(ps)
-    return {"psnr": ps, "ssim": ss, "images": out if keep_images else None,
-            "mean_psnr": float(ps[finite].mean()) if finite.any() else math.inf,
-            "mean_ssim": float(ss.mean())}
+    res = {"psnr": ps, "ssim": ss, "images": out if keep_images else None,
+           "mean_psnr": float(ps[finite].mean()) if finite.any() else math.inf,
+           "mean_ssim": float(ss.mean())}
+    if lr is not None:
+        if out is None or out.shape[0] != samples * N:      # device metrics, sharded, images not gathered
+            raise ValueError("validate_batch(lr=...) scores the gathered images: with sharded device metrics keep_images must be True")
+        dev = next(netG.parameters()).device
+        cons = lr_consistency(netG, out.to(dev), lr)["mse"].reshape(samples, N)
+        res["consistency"], res["mean_consistency"] = cons, float(cons.mean())
+    return res
+
+
+def _validate_lr_only(netG, sr, lr, samples, seed, sharded, keep_images):
+    """validate_batch without HR: the chains and their consistency score only."""
+    import torch
+    from . import dist as _dist
+
+    N = sr.shape[0]
+    x = sr.repeat(samples, 1, 1, 1)
+    if seed is None:
+        seed = netG._draw_seed()
+        if sharded and torch.distributed.is_available() and torch.distributed.is_initialized():
+            box = [seed]
+            torch.distributed.broadcast_object_list(box, src=0)
+            seed = int(box[0])
+    if sharded:
+        out = _dist.sharded_super_resolution(lambda xs, off: netG.super_resolution_batch(xs, seed=seed, image_offset=off), x)
+    else:
+        out = netG.super_resolution_batch(x, seed=seed)
+    cons = lr_consistency(netG, out.to(next(netG.parameters()).device), lr)["mse"].reshape(samples, N)
+    return {"psnr": None, "ssim": None, "mean_psnr": None, "mean_ssim": None, "images": out if keep_images else None,
+            "consistency": cons, "mean_consistency": float(cons.mean())}
 
 
 def loss_by_level(netG, hr: "torch.Tensor", sr: "torch.Tensor", levels, noise: "Optional[torch.Tensor]" = None,

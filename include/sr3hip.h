@@ -463,6 +463,46 @@ int sr3_op_q_sample(sr3_ctx *ctx, const float *hr_dev, int N, int row_offset, co
                     const float *s_dev, const float *noise_dev, int noise_per_source, uint64_t seed,
                     uint64_t image_offset, int B, int C, int H, int W, float *x_noisy_out);
 
+/* ---- low-resolution consistency of the sampler ---------------------------- */
+/* The reference makes its LR images with Pillow's antialiased bicubic resample (datasets/tool/prepare_data.py:37-47).
+ * In real arithmetic that is, per axis and for sizes r -> l (r > l, any ratio),
+ *   A in R^{l x r}:  A[i][x] = w((x - (i + 0.5) r/l + 0.5) l/r) / sum over the row, for x in the clipped support
+ *                    [int(c - 2r/l + 0.5), int(c + 2r/l + 0.5)) of c = (i + 0.5) r/l, w the bicubic kernel (a = -0.5)
+ * (Resample.c precompute_coeffs before its fixed-point rounding); every row sums to 1. A A^T is symmetric positive
+ * definite with a condition number near 2, so
+ *   P = A^T (A A^T)^-1 in R^{r x l}     (Cholesky, float64),   A P = I,   P A the orthogonal projector on range(A^T).
+ * Host only, no context: A receives l*r doubles (row-major [l][r]), P receives r*l ([r][l]). */
+int sr3_lr_operators_host(int l, int r, double *A_host, double *P_host);
+/* While set, every step of sr3_sample and of sr3_sample_begin / _step / _end projects its clamped x0 prediction onto the
+ * images that downsample to the LR input, between the prediction and the posterior update:
+ *   x0  = clamp(a x - b eps, -1, 1)                                        (as without the feature)
+ *   x0 <- x0 + strength * P_v (Y - A_v x0 A_h^T) P_h^T                     per (image, channel) plane, fp32
+ *   x'  = c1 x0 + c2 x [+ c3 x0_prev] [+ sigma z]                          (x0_prev: the PROJECTED x0 of the step before)
+ * with A_v, P_v for lh -> H and A_h, P_h for lw -> W, and Y the plane of lr[(row_offset + b) % N] for batch row b (the
+ * row convention of sr3_metrics_psnr_ssim: samples x images batches never replicate the LR images; a chunk or shard
+ * passes its first global row). Nothing is clamped after the projection: the last step of every sampler returns
+ * 1 * x0 + 0 * x, so at strength 1 the result satisfies A x = y to fp32 rounding. lr_dev: fp32 NCHW [N, out_channel,
+ * lh, lw] in [-1, 1], read by every later step: it must outlive them. NULL or strength 0 turns the feature off, and a
+ * step then launches exactly the kernels it always did; 0 < strength <= 1 otherwise. Set it before sr3_sample_begin.
+ * The pointer, N, row_offset and strength are read from device memory, so captured step graphs survive their change;
+ * a change of (lh, lw) rebuilds them. Works in all three arithmetic modes (the projection is always fp32), with the
+ * range policy's replays, the x0 history and Dropout. */
+int sr3_set_lr_consistency(sr3_ctx *ctx, const float *lr_dev, int N, int lh, int lw, uint64_t row_offset,
+                           float strength);
+/* The projection alone, in place on x_dev (fp32 NCHW [B, C, H, W]; lr_dev [N, C, lh, lw]; H > lh, W > lw):
+ *   X <- X + strength * P_v (Y - A_v X A_h^T) P_h^T
+ * in four stages, T = X A_h^T (banded), R = Y - A_v T (banded), U = P_v R, X += strength * U P_h^T. form 1: one block
+ * per plane with T, R, U in LDS (fails if (H + lh) * lw floats exceed 64 KB); form 2: one launch per stage over global
+ * scratch; form 0: form 1 where it fits, as the sampler chooses. Both forms return the same bits. Asynchronous. */
+int sr3_op_lr_project(sr3_ctx *ctx, float *x_dev, int B, int C, int H, int W, const float *lr_dev, int N, int lh,
+                      int lw, uint64_t row_offset, float strength, int form);
+/* The consistency score, which needs no HR image: per batch row b over its C planes,
+ *   sumsq_dev[b]  = sum (A_v X A_h^T - Y)^2   (fp32 residuals, fp64 sum; mse = sumsq / (C lh lw))
+ *   maxabs_dev[b] = max |A_v X A_h^T - Y|
+ * with Y as above. Bitwise reproducible (no atomics). Asynchronous. */
+int sr3_lr_residual(sr3_ctx *ctx, const float *img_dev, int B, int C, int H, int W, const float *lr_dev, int N,
+                    int lh, int lw, uint64_t row_offset, double *sumsq_dev, float *maxabs_dev);
+
 /* ---- device memory helpers (so hosts without torch can drive the library) ---------------- */
 int sr3_dev_malloc(sr3_ctx *ctx, uint64_t bytes, void **out_dev);
 int sr3_dev_free(sr3_ctx *ctx, void *dev);
