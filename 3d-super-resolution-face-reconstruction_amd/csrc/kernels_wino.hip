@@ -150,7 +150,9 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const ConvParams p, co
 //   * epilogue: each wave folds its row over the columns of A (t_c = M[a] A[:, c]) in registers, the four rows meet in
 //     LDS, y = A^T t, then the direct kernel's epilogue order (bias, residual, FeatureWiseAffine bias), the store and the
 //     fused GroupNorm statistics (per tile in LDS, then per slice in tile order; spb slices per strip).
-// Registers: 4 positions x 2 N-fragments x 16 accumulators = 128, plus two sets of B fragments (64): 2 waves per SIMD.
+// Registers: 4 positions x 2 N-fragments x 16 accumulators = 128, one ring of four B pairs (32, each refilled right
+// behind its MFMAs: see the K loop), two generations of window sums and one half-window landing area (48): 246 in
+// all, 2 waves per SIMD.
 // A 64-tile or 128-channel block doubles the accumulators (256: 1 wave per SIMD, nothing left for operands).
 // One input tensor only (conv_plan): the engine writes x || skip as one tensor in the GroupNorm apply pass.
 constexpr int WF_T = 32;                    // 2x2 output tiles per block (one strip of a tile row)
@@ -159,7 +161,6 @@ constexpr int WF_WX = 2 * WF_T + 2;         // padded input columns of a strip's
 constexpr int WF_ROWS = 4 * WF_WX;          // pixel rows of 32 floats per LDS stage
 constexpr int WF_STAGE = WF_ROWS * 32;      // floats per stage
 constexpr int WF_DMA = WF_ROWS / 8;         // LDS-DMA instructions per stage (64 lanes x 16 B each)
-constexpr int WF_DMA_PER_WAVE = (WF_DMA + 3) / 4;
 static_assert(WF_ROWS % 8 == 0, "whole DMA instructions per stage");
 constexpr size_t WF_LDS = (size_t)2 * WF_STAGE * sizeof(float);
 static_assert(WF_LDS >= (size_t)4 * 2 * WF_T * WF_BN * sizeof(float), "epilogue exchange fits in the stages");
@@ -202,21 +203,32 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     const char *src0 = reinterpret_cast<const char *>(p.in0.p + pix0 * Cin);
 
     // LDS-DMA: wave a issues instructions i = a + 4m; lane -> pixel row 8i + (lane >> 3) (window row r, column x),
-    // stored chunk lane & 7 (offsets recomputed per K-step: a few VALU operations, no registers held across the loop)
-    auto issue = [&](int c0, int stage) {
-        const char *sb = src0 + (size_t)c0 * 4;
+    // stored chunk lane & 7 (offsets recomputed per K-step: a few VALU operations, no registers held across the loop).
+    // Nothing in the K loop issues a vector memory instruction under a branch that the compiler cannot count: the
+    // s_waitcnt vmcnt(N) it inserts assume the fewest loads in flight, so a skipped DMA makes every later wait one
+    // instruction stricter. A step with no next stage (on == false) sends its eight instructions past the end of the
+    // descriptor (no memory request; the free stage may receive zeros, which nobody reads); only instruction 32
+    // (m = 8, wave 0 alone) sits behind a wave-uniform branch, and it goes first.
+    // Bit 31 of the lane offset is that switch and the descriptor ends at 2^31 - 1 bytes, so a live offset must stay
+    // below it: (3 Wp + 65) * Cin * 4 + 128 < 2^31, i.e. Wp * Cin < 1.7e8 (the widest row of the UNet: 130 * 384 = 5e4).
+    auto issue = [&](int c0, int stage, bool on) {
+        const __amdgpu_buffer_rsrc_t rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(src0 + (size_t)c0 * 4), 0, 0x7fffffff, 0x00020000);
         const unsigned cs4 = (unsigned)Cin * 4u;
+        const unsigned off = on ? 0u : 0x80000000u;
         float *dst = smem + stage * WF_STAGE;
-        wf_static_for<WF_DMA_PER_WAVE>([&](auto mc) {
-            constexpr int m = decltype(mc)::value;
-            if (a + 4 * m < WF_DMA) {
-                int q = 8 * (a + 4 * m) + (lane >> 3);
-                asm volatile("" : "+v"(q));      // (kept in the loop: hoisted, the per-instruction offsets would be held in registers)
-                const int r = q / WF_WX, x = q - r * WF_WX;
-                const unsigned voff = (unsigned)(r * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16);
-                wf_dma16(sb, voff, dst + (a + 4 * m) * 256);
-            }
-        });
+        auto one = [&](int i) {
+            int q = 8 * i + (lane >> 3);
+            asm volatile("" : "+v"(q));      // (kept in the loop: hoisted, the per-instruction offsets would be held in registers)
+            const int r = q / WF_WX, x = q - r * WF_WX;
+            const unsigned voff =
+                ((unsigned)(r * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16)) | off;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst + i * 256), 16,
+                                                     (int)voff, 0, 0, 0);
+        };
+        static_assert(WF_DMA == 33, "eight instructions per wave and one more for wave 0");
+        if (a == 0 && on) one(32);
+        wf_static_for<8>([&](auto mc) { one(a + 4 * decltype(mc)::value); });
     };
 
     // B fragments: lane (li, h) loads channels c0 + 8kk + 4h .. +3 of output channel n0 + 32ni + li, position 4a + b,
@@ -227,14 +239,12 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     const size_t plane = (size_t)Cout * Cin;
     const __amdgpu_buffer_rsrc_t wrsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w_wino_f + (size_t)(4 * a) * plane), 0, -1, 0x00020000);
-    auto loadB = [&](f32x4 (&bf)[4][2], int c0, int kk) {
+    auto loadB = [&](f32x4 (&bfb)[2], int b, int c8) {      // position 4a + b, 8-channel group c8 = channel / 8
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-                const int soff = (int)(((size_t)b * plane + ((size_t)(c0 / 8 + kk) * Cout + (size_t)ni * 32) * 8) * 4);
-                bf[b][ni] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (int)wlane, soff, 0));
-            }
+        for (int ni = 0; ni < 2; ++ni) {
+            const int soff = (int)(((size_t)b * plane + ((size_t)c8 * Cout + (size_t)ni * 32) * 8) * 4);
+            bfb[ni] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (int)wlane, soff, 0));
+        }
     };
 
     // rows of the 4x4 window that (B^T d)[a] combines: e = d[ra] + sg * d[rb]
@@ -258,39 +268,65 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[b][ni][r] = 0.f;
 
+    // K loop. One ring of four B pairs, bf[b] = the two N-fragments of position 4a + b: the eight MFMAs of position b
+    // are followed at once by the loads of the same position's next 8-channel group (the next step's first group after
+    // kk = 3; past the last step the same addresses again, never used), so every B load is issued about 24 MFMAs of
+    // this wave (19-33 in the binary) before the wait that covers it. The window reads of group kk + 1 are issued in
+    // two halves under the MFMAs of group kk and folded into e as they land; only a step's first group reads after the
+    // barrier. The next stage's DMA goes between groups 2 and 3: every B load that a later MFMA of this step waits for
+    // is older than it (vmcnt retires in order), and it has a group's time to land before the barrier that publishes
+    // it. sched_barrier(0) after each position keeps the loads where they are written; the compiler places the waits.
     const int nk = Cin / 32;
-    f32x4 bf[2][4][2];
-    issue(0, 0);
-    loadB(bf[0], 0, 0);
+    f32x4 bf[4][2];
+    auto window = [&](const float *st, int kk, int x, f32x4 &d0, f32x4 &d1) {
+        const int ch = 2 * kk + h;
+        d0 = *reinterpret_cast<const f32x4 *>(st + aoff[0][x] + ((ch ^ asw[x]) << 2));
+        d1 = *reinterpret_cast<const f32x4 *>(st + aoff[1][x] + ((ch ^ asw[x]) << 2));
+    };
+    issue(0, 0, true);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) loadB(bf[b], b, 0);
     __syncthreads();                          // (waits for this wave's DMA; the barrier publishes everybody's)
     for (int kt = 0; kt < nk; ++kt) {
         const int c0 = kt * 32;
-        if (kt + 1 < nk) issue(c0 + 32, (kt + 1) & 1);   // stage free since the barrier that ended step kt - 1
+        const bool more = kt + 1 < nk;
+        const int c8n = more ? c0 / 8 + 4 : c0 / 8;
         const float *st = smem + (kt & 1) * WF_STAGE;
+        f32x4 e[4];
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            f32x4 d0, d1;
+            window(st, 0, x, d0, d1);
+            e[x] = d0 + sg * d1;
+        }
         wf_static_for<4>([&](auto kc) {
             constexpr int kk = decltype(kc)::value;
-            if constexpr (kk < 3) loadB(bf[(kk + 1) & 1], c0, kk + 1);
-            else if (kt + 1 < nk) loadB(bf[0], c0 + 32, 0);
-            const int ch = 2 * kk + h;
-            f32x4 e[4];
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const f32x4 d0 = *reinterpret_cast<const f32x4 *>(st + aoff[0][x] + ((ch ^ asw[x]) << 2));
-                const f32x4 d1 = *reinterpret_cast<const f32x4 *>(st + aoff[1][x] + ((ch ^ asw[x]) << 2));
-                e[x] = d0 + sg * d1;
-            }
-            f32x4 u[4];
-            u[0] = e[0] - e[2];
-            u[1] = e[1] + e[2];
-            u[2] = e[2] - e[1];
-            u[3] = e[1] - e[3];
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
+            f32x4 en[4], d0[2], d1[2];
+            wf_static_for<4>([&](auto bc) {
+                constexpr int b = decltype(bc)::value;
+                const f32x4 u = b == 0 ? e[0] - e[2] : b == 1 ? e[1] + e[2] : b == 2 ? e[2] - e[1] : e[1] - e[3];
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
                     for (int ni = 0; ni < 2; ++ni)
-                        acc[b][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[b][j], bf[kk & 1][b][ni][j], acc[b][ni], 0, 0, 0);
+                        acc[b][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[j], bf[b][ni][j], acc[b][ni], 0, 0, 0);
+                loadB(bf[b], b, kk < 3 ? c0 / 8 + kk + 1 : c8n);
+                if constexpr (kk < 3) {
+                    if constexpr (b == 0) { window(st, kk + 1, 0, d0[0], d1[0]); window(st, kk + 1, 1, d0[1], d1[1]); }
+                    if constexpr (b == 1) {
+                        en[0] = d0[0] + sg * d1[0]; en[1] = d0[1] + sg * d1[1];
+                        window(st, kk + 1, 2, d0[0], d1[0]); window(st, kk + 1, 3, d0[1], d1[1]);
+                    }
+                    if constexpr (b == 3) { en[2] = d0[0] + sg * d1[0]; en[3] = d0[1] + sg * d1[1]; }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            if constexpr (kk < 3) {
+#pragma unroll
+                for (int x = 0; x < 4; ++x) e[x] = en[x];
+            }
+            // (stage (kt + 1) & 1 is free since the barrier that ended step kt - 1)
+            if constexpr (kk == 2) { issue(c0 + 32, (kt + 1) & 1, more); __builtin_amdgcn_sched_barrier(0); }
         });
         __syncthreads();                      // DMA of step kt + 1 landed; every read of stage kt & 1 done
     }
