@@ -1846,7 +1846,40 @@ const char *conv_kernel_name(ConvKernel k) {
     return (unsigned)k < (unsigned)CK_COUNT ? names[k] : "?";
 }
 
+// Upsample convs (prec 0): tile rows per block of wino_up2_kernel (kernels_wino.hip), 0 = the four phase convs of `direct`.
+// Preconditions: one f32 input with its zero border, f32 output only, nothing fused but the biases; whole 32-channel
+// blocks on both sides; a low-resolution width of 16, 32 or a multiple of 64 and whole blocks of 32 tiles; an unsplit
+// direct plan; statistics absent or in the direct plan's slices of 128 pixels (one phase of a block: widths 16, 32, 64; two
+// strips of a tile row, run by one block: multiples of 128) or of 64 (half of that; few-tile shapes); 32-bit offsets of the input DMA (as wino_fused_kernel: bit
+// 31 of a lane's offset switches an instruction off) and of the weight loads (the nine planes of a phase).
+// Tuning: UP2_WINO_MIN_BLOCKS.
+static int up2_wino_rows(const ConvParams &p, const ConvPlan &direct) {
+    static const bool off = env_int("SR3_NO_UP2_WINO", 0) != 0;             // product switches (read once)
+    static const bool force = env_int("SR3_UP2_WINO_FORCE", 0) != 0;
+    if (off || !p.up2 || p.prec != 0 || p.f8 || p.ks != 3 || p.stride != 1 || !p.w_up_wino) return 0;
+    if (p.in1.p || p.in2.p || p.resid.p || p.out_split.p || !p.out_f32 || p.in0.pad != 1) return 0;
+    const int Hl = p.in0.H, Wl = p.in0.W, Cin = p.in0.C, Cout = p.out.C;
+    if (p.B <= 0 || 2 * Hl != p.Hout || 2 * Wl != p.Wout || (Cin % 32) || (Cout % UP2_WINO_BN)) return 0;
+    const int R = Wl == 16 ? 4 : Wl == 32 ? 2 : (Wl % 64) == 0 ? 1 : 0;
+    if (R == 0 || (Hl % (2 * R))) return 0;
+    if (direct.split != CS_NONE || direct.error) return 0;
+    if (p.stats) {
+        if ((direct.tile_m != 128 && direct.tile_m != 64) || p.stats_slices != 4 * (Hl * Wl / direct.tile_m)) return 0;
+        if (direct.tile_m == 128 && Wl > 64 && (Wl % 128)) return 0;
+    }
+    if (((uint64_t)10 * (Wl + 2) + 70) * (uint64_t)Cin * 4 >= (1ull << 31) || (uint64_t)9 * Cout * Cin * 4 >= (1ull << 31)) return 0;
+    const uint64_t blocks = (uint64_t)p.B * ((uint64_t)Hl * Wl / (4 * UP2_WINO_TILES)) * (Cout / UP2_WINO_BN);
+    return (force || blocks >= (uint64_t)UP2_WINO_MIN_BLOCKS) ? R : 0;
+}
+
+static ConvPlan conv_plan_direct(const ConvParams &p_in);
 ConvPlan conv_plan(const ConvParams &p_in) {
+    ConvPlan plan = conv_plan_direct(p_in);
+    plan.up2_wino = up2_wino_rows(p_in, plan);
+    return plan;
+}
+
+static ConvPlan conv_plan_direct(const ConvParams &p_in) {
     const ConvParams p = phase_form(p_in);
     const int Cout = p.out.C, Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
     const int HWo = p.Hout * p.Wout;                 // pixels of one image (and phase)
@@ -1920,7 +1953,7 @@ ConvPlan conv_plan_offered(int B, int H, int W, int Cin, int Cout, int ks, int s
     p.B = B; p.ks = ks; p.stride = stride; p.up2 = up2; p.prec = prec; p.f8 = f8 ? 1 : 0;
     p.Hout = (Hv + 2 * pad - ks) / stride + 1; p.Wout = (Wv + 2 * pad - ks) / stride + 1;
     p.out.p = &buf; p.out.C = Cout; p.out.H = p.Hout; p.out.W = p.Wout;
-    p.w = p.w_wino = p.w_wino_f = &buf;
+    p.w = p.w_wino = p.w_wino_f = p.w_up_wino = &buf;
     p.part = p.wino_ws = &buf;
     p.tile_cnt = &cnt;
     if (stats) {
@@ -1969,6 +2002,7 @@ void launch_conv(const ConvParams &p_in, hipStream_t s) {
     const ConvPlan plan = conv_plan(p_in);
     if (plan.error) { g_conv_error = plan.error; return; }
     if (plan.kernel == CK_WINO_ONE_PASS || plan.kernel == CK_WINO_THREE_PASS) { launch_conv_wino(p_in, plan, s); return; }
+    if (plan.up2_wino) { launch_conv_up2_wino(p_in, plan, s); return; }
     ConvParams p = phase_form(p_in);     // up2: the weights must be in phase form (make_up2_phase_weights)
     const int HWo = p.Hout * p.Wout;
     const long M = (long)p.B * HWo;
@@ -2023,6 +2057,27 @@ void make_up2_phase_weights(const float *w9, int Cout, int CinPad, float *dst) {
                         }
                         d[i] = (float)acc;
                     }
+                }
+}
+
+void make_up2_wino_weights(const float *w9, int Cout, int CinPad, float *dst) {
+    // 1-D: G (g0, g1) = (g0, g0 + g1, g1) with the phase taps (g0, g1) = (w0, w1 + w2) | (w0 + w1, w2): position i of
+    // phase py adds the taps d with lo <= d <= hi below; the 2-D value adds w[dy][dx] over both ranges
+    static const int lo[2][3] = {{0, 0, 1}, {0, 0, 2}}, hi[2][3] = {{0, 2, 2}, {1, 2, 2}};
+    const size_t plane = (size_t)Cout * CinPad;
+    for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < 2; ++px)
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    float *d = dst + ((size_t)(py * 2 + px) * 9 + i * 3 + j) * plane;
+                    for (int o = 0; o < Cout; ++o)
+                        for (int c = 0; c < CinPad; ++c) {
+                            double acc = 0.0;
+                            for (int dy = lo[py][i]; dy <= hi[py][i]; ++dy)
+                                for (int dx = lo[px][j]; dx <= hi[px][j]; ++dx)
+                                    acc += (double)w9[(size_t)(dy * 3 + dx) * plane + (size_t)o * CinPad + c];
+                            d[((size_t)(c / 8) * Cout + o) * 8 + (c & 7)] = (float)acc;
+                        }
                 }
 }
 

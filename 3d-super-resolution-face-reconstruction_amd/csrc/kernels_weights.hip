@@ -1,5 +1,5 @@
 // Weight layouts built on the device from fp32 tensors in the reference layout (Conv2d OIHW, Linear [out,in]) — the
-// device twin of the host helpers pack_conv_weight, make_up2_phase_weights, make_wino_weights and split_conv_weight_k,
+// device twin of the host helpers pack_conv_weight, make_up2_phase_weights, make_up2_wino_weights, make_wino_weights and split_conv_weight_k,
 // byte for byte: the same operations in the same order in the same precision (the Winograd and phase sums in fp64,
 // rounded once). Everything here is a permutation or an elementwise pass, so the only concerns are that every tensor is
 // read once, that every layout is written once, and that the 64 lanes of a wave touch consecutive addresses:
@@ -36,7 +36,7 @@ __device__ __forceinline__ void block_absmax(float m, unsigned *slot) {
 template <int KS, bool UP>
 __global__ __launch_bounds__(256) void weight_pack_kernel(const float *__restrict__ oihw, int Cout, int Cin, int CinPad,
                                                           float *__restrict__ packed, float *__restrict__ wino,
-                                                          unsigned *__restrict__ wmax) {
+                                                          unsigned *__restrict__ wmax, float *__restrict__ up_wino) {
 #pragma clang fp contract(off)
     constexpr int TAPS = KS * KS;
     const size_t plane = (size_t)Cout * CinPad;
@@ -76,6 +76,30 @@ __global__ __launch_bounds__(256) void weight_pack_kernel(const float *__restric
                             packed[(size_t)((py * 2 + px) * 4 + r2 * 2 + c2) * plane + t] = v;
                             m = fmaxf(m, fabsf(v));
                         }
+            if (up_wino) {
+                // make_up2_wino_weights: position (i, j) of phase (py, px) adds the taps lo <= d <= hi of both axes, in
+                // (dy, dx) order, in fp64 from 0.0; fragment-major [phase][position][CinPad/8][Cout][8]
+                const int lo[2][3] = {{0, 0, 1}, {0, 0, 2}}, hi[2][3] = {{0, 2, 2}, {1, 2, 2}};
+                const size_t at = ((size_t)(i >> 3) * Cout + o) * 8 + (i & 7);
+#pragma unroll
+                for (int py = 0; py < 2; ++py)
+#pragma unroll
+                    for (int px = 0; px < 2; ++px)
+#pragma unroll
+                        for (int a = 0; a < 3; ++a)
+#pragma unroll
+                            for (int b = 0; b < 3; ++b) {
+                                double acc = 0.0;
+#pragma unroll
+                                for (int dy = 0; dy < 3; ++dy) {
+                                    if (dy < lo[py][a] || dy > hi[py][a]) continue;
+#pragma unroll
+                                    for (int dx = 0; dx < 3; ++dx)
+                                        if (dx >= lo[px][b] && dx <= hi[px][b]) acc += (double)w[dy * 3 + dx];
+                                }
+                                up_wino[(size_t)((py * 2 + px) * 9 + a * 3 + b) * plane + at] = (float)acc;
+                            }
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < TAPS; ++k) {
@@ -156,12 +180,12 @@ __global__ __launch_bounds__(256) void weight_ident_kernel(int C, unsigned half_
 } // namespace
 
 void launch_weight_pack(const float *oihw, int Cout, int Cin, int ks, int CinPad, bool up_phase, float *packed, float *wino,
-                        unsigned *wmax, hipStream_t s) {
+                        unsigned *wmax, hipStream_t s, float *up_wino) {
     const size_t plane = (size_t)Cout * CinPad;
     const dim3 grid((unsigned)((plane + 255) / 256)), block(256);
-    if (ks == 1) hipLaunchKernelGGL((weight_pack_kernel<1, false>), grid, block, 0, s, oihw, Cout, Cin, CinPad, packed, wino, wmax);
-    else if (up_phase) hipLaunchKernelGGL((weight_pack_kernel<3, true>), grid, block, 0, s, oihw, Cout, Cin, CinPad, packed, wino, wmax);
-    else hipLaunchKernelGGL((weight_pack_kernel<3, false>), grid, block, 0, s, oihw, Cout, Cin, CinPad, packed, wino, wmax);
+    if (ks == 1) hipLaunchKernelGGL((weight_pack_kernel<1, false>), grid, block, 0, s, oihw, Cout, Cin, CinPad, packed, wino, wmax, up_wino);
+    else if (up_phase) hipLaunchKernelGGL((weight_pack_kernel<3, true>), grid, block, 0, s, oihw, Cout, Cin, CinPad, packed, wino, wmax, up_wino);
+    else hipLaunchKernelGGL((weight_pack_kernel<3, false>), grid, block, 0, s, oihw, Cout, Cin, CinPad, packed, wino, wmax, up_wino);
 }
 
 void launch_weight_absmax(const float *packed, size_t n, unsigned *wmax, hipStream_t s) {

@@ -412,6 +412,246 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     }
 }
 
+// ---- Upsample (nearest x2) + conv3x3 as sub-pixel Winograd F(2x2, 2x2) ---------------------------------------------------
+// (transforms and indexing: sr3_internal.h at make_up2_wino_weights.) One pass, modelled on wino_fused_kernel:
+//   * block = 32 tiles of the phase images (R tile rows x TPR = 32 / R tiles) x WU_BN = 32 output channels x the four
+//     phases; wave a owns phase (py, px) = (a >> 1, a & 1). The 3x3 windows of all four phases lie inside the 4x4
+//     low-resolution window (padded rows 2ti .. 2ti + 3) of the tile, so a stage is wino_fused_kernel's: per tile row 4
+//     rows of WX = 2 TPR + 2 padded pixels x 32 channels, by LDS-DMA with the same swizzle (264 | 272 | 288 pixel rows
+//     for R = 1 | 2 | 4: 33 | 34 | 36 instructions). Every wave issues nine instructions per stage, whatever R: the ones
+//     past the stage's last (and all nine of a step that has no next stage) go past the end of the descriptor, so no
+//     vector memory instruction of the K loop sits behind a branch; a stage has room for all 36.
+//   * per 8-channel group a lane reads the nine window pixels of its tile (4 channels each), forms B^T d B with
+//     differences only, and runs 9 positions x 4 MFMAs against B fragments loaded straight from the fragment-major
+//     weights [phase][position][CinPad/8][Cout][8]; each position's fragment is reloaded for the next group right
+//     behind its MFMAs, as in wino_fused_kernel.
+//   * epilogue: the wave holds all nine M of its phase, so A^T M A is per-lane arithmetic on the accumulators: lane
+//     (li, h) holds channel li of 16 tiles and stores 128 contiguous bytes per pixel with its 31 neighbours. Bias and
+//     FeatureWiseAffine bias in the direct kernel's order. Statistics: per lane in fp64 over its tiles in register
+//     order, then the two lane halves; one slice = one phase of 128 consecutive low-resolution pixels, which is what a
+//     wave holds at R = 1 | 2 | 4, or of 64 (where the direct plan's tile is 64 pixels high): the two halves of them, kept
+//     apart from the start. At widths of a multiple of 128 with 128-pixel slices the block runs the two strips of a slice
+//     pair one after the other and the second adds to what the first stored. No LDS, no atomics, no inter-block waits.
+// Registers: 9 positions x 16 accumulators = 144, a ring of six B fragments (24), nine transformed values (36).
+constexpr int WU_BN = 32;
+constexpr int WU_DMA = 36;                  // LDS-DMA slots per stage (nine per wave)
+constexpr int WU_STAGE = WU_DMA * 256;      // floats per stage
+constexpr size_t WU_LDS = (size_t)2 * WU_STAGE * sizeof(float);
+static_assert(WU_BN == UP2_WINO_BN && UP2_WINO_TILES == 32, "conv_plan gates wino_up2_kernel on its block shape");
+
+template <int R>
+__global__ __launch_bounds__(256, 2) void wino_up2_kernel(const ConvParams p, int smode) {
+    const int nst = smode == 1 ? 2 : 1;
+    constexpr int TPR = 32 / R, WX = 2 * TPR + 2, ROWS = R * 4 * WX, NDMA = ROWS / 8;
+    static_assert(ROWS % 8 == 0 && NDMA <= WU_DMA, "whole DMA instructions, inside a stage");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int Cin = p.in0.C, Cout = p.out.C;
+    const int Hl = p.in0.H, Wl = p.in0.W, th = Hl >> 1, tw = Wl >> 1;     // tiles of a phase image
+    const int bpr = (tw / TPR) / nst;                    // blocks per group of R tile rows
+    const int bpi = (th / R) * bpr;                      // blocks per image
+    const int nbl = Cout / WU_BN;
+    int bid = blockIdx.x;
+    {   // XCD-aware remap (as wino_fused_kernel): the channel blocks of one strip share an L2
+        const int nwg = gridDim.x;
+        const int xcd = bid & 7, loc = bid >> 3;
+        const int qq = nwg >> 3, rr = nwg & 7;
+        bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + loc;
+    }
+    const int nb = bid % nbl, blk = bid / nbl;
+    const int n = blk / bpi, bi = blk - n * bpi;
+    const int tg = bi / bpr, sj = bi - tg * bpr;
+    const int ti0 = tg * R;
+    const int n0 = nb * WU_BN;
+    const int a = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int py = a >> 1, px = a & 1;
+    const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
+    const int Wp = p.in0.Wp();
+    const int phase_slices = p.stats_slices >> 2;
+
+    // B fragments of position pos, 8-channel group c8: lane (li, h) loads channels 8 c8 + 4h .. + 3 of output channel
+    // n0 + li from w_up_wino[phase a][pos][c8][n0 + li][4h ..] (a wave-uniform descriptor over the phase's nine planes)
+    const unsigned wlane = ((unsigned)(n0 + li) * 8u + 4u * h) * 4u;
+    const size_t plane = (size_t)Cout * Cin;
+    const __amdgpu_buffer_rsrc_t wrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w_up_wino + (size_t)(9 * a) * plane), 0, -1, 0x00020000);
+    auto loadB = [&](f32x4 &bfb, int pos, int c8) {
+        const int soff = (int)((unsigned)pos * (unsigned)plane + (unsigned)c8 * (unsigned)Cout * 8u) * 4;
+        bfb = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (int)wlane, soff, 0));
+    };
+
+    // the lane's tile and its window: pixel (py + i, px + j) of the tile's 4x4 window, i, j = 0..2
+    // (float offset wbase + (i WX + j) * 32 in a stage, 16-B chunk c of column j at c ^ wsw[j])
+    const int ltr = li / TPR, ltc = li - ltr * TPR;
+    const int wbase = ((ltr * 4 + py) * WX + 2 * ltc + px) * 32;
+    int wsw[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) wsw[j] = (ltc + ((px + j) >> 1)) & 7;
+
+    const int co = n0 + li;
+    float add = p.bias ? p.bias[co] : 0.f;               // (the direct kernel's epilogue order: bias, FeatureWiseAffine bias)
+    if (p.chan_bias) add += p.chan_bias[(size_t)n * p.chan_bias_stride + co];
+
+    const int nk = Cin / 32;
+    for (int ss = 0; ss < nst; ++ss) {
+        const int tj0 = (sj * nst + ss) * TPR;
+        const size_t pix0 = ((size_t)n * p.in0.Hp() + 2 * ti0) * Wp + 2 * tj0;      // window origin of the block's first tile
+        const char *src0 = reinterpret_cast<const char *>(p.in0.p + pix0 * Cin);
+
+        // LDS-DMA: wave a issues instructions i = a + 4m, m = 0..8; lane -> pixel row 8i + (lane >> 3) of the stage
+        // (tile row, window row r, column x), stored chunk lane & 7. Bit 31 of the lane offset switches an instruction
+        // off (on == false, or i >= NDMA) and the descriptor ends at 2^31 - 1 bytes, so a live offset stays below it
+        // (conv_plan: (10 Wp + 70) * Cin * 4 < 2^31).
+        auto issue = [&](int c0, int stage, bool on) {
+            const __amdgpu_buffer_rsrc_t rsrc =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(src0 + (size_t)c0 * 4), 0, 0x7fffffff, 0x00020000);
+            const unsigned cs4 = (unsigned)Cin * 4u;
+            float *dst = smem + stage * WU_STAGE;
+            wf_static_for<9>([&](auto mc) {
+                const int i = a + 4 * decltype(mc)::value;
+                int q = 8 * i + (lane >> 3);
+                asm volatile("" : "+v"(q));      // (kept in the loop, as in wino_fused_kernel)
+                const int wr = q / WX, x = q - wr * WX;
+                const int row = 2 * (wr >> 2) + (wr & 3);
+                const unsigned off = (on && i < NDMA) ? 0u : 0x80000000u;
+                const unsigned voff = ((unsigned)(row * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16)) | off;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst + i * 256), 16,
+                                                         (int)voff, 0, 0, 0);
+            });
+        };
+
+        // window pixel (py + i, px + j) of the lane's tile, channels 8 kk + 4h .. + 3
+        auto rd = [&](const float *st, int kk, int i, int j) {
+            return *reinterpret_cast<const f32x4 *>(st + wbase + (i * WX + j) * 32 + (((2 * kk + h) ^ wsw[j]) << 2));
+        };
+
+        f32x16 acc[9];
+#pragma unroll
+        for (int ps = 0; ps < 9; ++ps)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ps][r] = 0.f;
+
+        // K loop. The 36 (group, position) products of a step take their B fragments from a ring of six: slot t % 6 for
+        // product t = 9 kk + position, refilled right behind its MFMAs with the fragment of product t + 6 (20 MFMAs of this
+        // wave ahead of its use; past kk = 3 the next step's first group, past the last step the same addresses again,
+        // never used).
+        f32x4 bf[6];
+        issue(0, 0, true);
+#pragma unroll
+        for (int t = 0; t < 6; ++t) loadB(bf[t], t, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's DMA landed; the barrier publishes everybody's
+        __syncthreads();
+        for (int kt = 0; kt < nk; ++kt) {
+            const int c0 = kt * 32;
+            const bool more = kt + 1 < nk;
+            const int c8n = more ? c0 / 8 + 4 : c0 / 8;
+            const float *st = smem + (kt & 1) * WU_STAGE;
+            f32x4 dn0[3], dn1[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { dn0[j] = rd(st, 0, 0, j); dn1[j] = rd(st, 0, 1, j); }
+            wf_static_for<4>([&](auto kc) {
+                constexpr int kk = decltype(kc)::value;
+                // B^T d B: rows (d0 - d1, d1, d1 - d2), then the same over the columns. Rows 0 and 1 of the window were
+                // read under the previous group's last positions (a step's first group: after the barrier); row 2 is
+                // read behind position 2 and folded in behind position 5; the next group's rows 0 and 1 follow position 6.
+                f32x4 u[9];
+                {
+                    f32x4 e0[3];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) e0[j] = dn0[j] - dn1[j];
+                    u[0] = e0[0] - e0[1]; u[1] = e0[1]; u[2] = e0[1] - e0[2];
+                    u[3] = dn1[0] - dn1[1]; u[4] = dn1[1]; u[5] = dn1[1] - dn1[2];
+                }
+                f32x4 d1[3], d2[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) d1[j] = dn1[j];
+                __builtin_amdgcn_sched_barrier(0);
+                wf_static_for<9>([&](auto pc) {
+                    constexpr int ps = decltype(pc)::value;
+                    constexpr int t = 9 * kk + ps, slot = t % 6;
+                    constexpr int tn = t + 6, psn = tn % 9, kkn = tn / 9;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc[ps] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[ps][j], bf[slot][j], acc[ps], 0, 0, 0);
+                    loadB(bf[slot], psn, kkn < 4 ? c0 / 8 + kkn : c8n);
+                    if constexpr (ps == 2) {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) d2[j] = rd(st, kk, 2, j);
+                    }
+                    if constexpr (ps == 5) {
+                        f32x4 e2[3];
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) e2[j] = d1[j] - d2[j];
+                        u[6] = e2[0] - e2[1]; u[7] = e2[1]; u[8] = e2[1] - e2[2];
+                    }
+                    if constexpr (ps == 6 && kk < 3) {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) { dn0[j] = rd(st, kk + 1, 0, j); dn1[j] = rd(st, kk + 1, 1, j); }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                // (stage (kt + 1) & 1 is free since the barrier that ended step kt - 1)
+                if constexpr (kk == 2) { issue(c0 + 32, (kt + 1) & 1, more); __builtin_amdgcn_sched_barrier(0); }
+            });
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();                      // DMA of step kt + 1 landed; every read of stage kt & 1 done
+        }
+
+        // A^T M A per tile in the accumulator layout (register r of lane half h = tile (r & 3) + 8 (r >> 2) + 4h)
+        // (4h is less than the distance to the next multiple of 8, so the tile row is the same in both halves and the
+        // half only shifts the lane by 4 tiles = 16 output pixels along the row: every other term of the address is
+        // wave-uniform)
+        // statistics of the two 64-pixel halves of the wave's 128 low-resolution pixels (row-major): the tiles' pixel rows
+        // 0 | 1 at R = 1, the tile rows 0 | 1 at R = 2, 0-1 | 2-3 at R = 4
+        double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
+        const int Wpo = p.out.Wp();
+        float *const ob = p.out.p + p.out.pix(n, 4 * ti0 + py, 4 * tj0 + px) * Cout;
+        const unsigned lo = (unsigned)(16 * h * Cout + co);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int tl = (r & 3) + 8 * (r >> 2), tr = tl / TPR, tc = tl - tr * TPR;
+            const float t00 = acc[0][r] + acc[3][r], t01 = acc[1][r] + acc[4][r], t02 = acc[2][r] + acc[5][r];
+            const float t10 = acc[3][r] - acc[6][r], t11 = acc[4][r] - acc[7][r], t12 = acc[5][r] - acc[8][r];
+            const float y[2][2] = {{t00 + t01, t01 - t02}, {t10 + t11, t11 - t12}};
+#pragma unroll
+            for (int ya = 0; ya < 2; ++ya)
+#pragma unroll
+                for (int xb = 0; xb < 2; ++xb) {
+                    const float o = y[ya][xb] + add;
+                    (ob + (size_t)((4 * tr + 2 * ya) * Wpo + 4 * tc + 2 * xb) * Cout)[lo] = o;
+                    const int g = R == 1 ? ya : R == 2 ? tr : tr >> 1;
+                    s1[g] += (double)o;
+                    s2[g] = fma((double)o, (double)o, s2[g]);
+                }
+        }
+        if (p.stats != nullptr) {
+            // the two lane halves hold different tiles of the same channel; half 0 writes. The second strip of a slice
+            // pair adds to what the same lane stored after the first (its own store: no other thread touches the word)
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                s1[g] += __shfl_xor(s1[g], 32);
+                s2[g] += __shfl_xor(s2[g], 32);
+            }
+            if (h == 0) {
+                if (smode == 0) {           // one 128-pixel slice per wave
+                    double *o = p.stats + (((size_t)n * p.stats_slices + a * phase_slices + bi) * Cout + co) * 2;
+                    o[0] = s1[0] + s1[1]; o[1] = s2[0] + s2[1];
+                } else {
+#pragma unroll
+                    for (int g = 0; g < 2; ++g) {
+                        // smode 1 (R = 1): pixel row g of the tile row, 128 columns = this block's two strips;
+                        // smode 2: the 64-pixel slices (R = 1: one strip's part of pixel row g)
+                        const int slice = a * phase_slices + (smode == 1 ? (2 * ti0 + g) * (Wl / 128) + sj
+                                                              : R == 1 ? (2 * ti0 + g) * (Wl / 64) + sj : 2 * bi + g);
+                        double *o = p.stats + (((size_t)n * p.stats_slices + slice) * Cout + co) * 2;
+                        if (ss == 0) { o[0] = s1[g]; o[1] = s2[g]; }
+                        else { o[0] += s1[g]; o[1] += s2[g]; }
+                    }
+                }
+            }
+        }
+    }
+}
+
 // ---- second form of the three-pass plan: the 16 position GEMMs and the output transform in ONE kernel ----------------
 // U -> wino_gemm_out_kernel -> output: M never goes through memory (it is four times the conv's output), and one block
 // runs ONE K loop of 16 * Cin / 32 steps instead of 16 blocks with Cin / 32 steps, a pipeline fill and an M-tile store each.
@@ -801,6 +1041,25 @@ void launch_conv_wino(const ConvParams &p, const ConvPlan &plan, hipStream_t s) 
 
     const int sl = out_slices(o);
     hipLaunchKernelGGL(wino_output_kernel, dim3(Cout / 64, sl, p.B), dim3(256), 0, s, o, Mw, sl);
+}
+
+void launch_conv_up2_wino(const ConvParams &p, const ConvPlan &plan, hipStream_t s) {
+    const int R = plan.up2_wino, Hl = p.in0.H, Wl = p.in0.W;
+    // statistics: 0 = one 128-pixel slice per wave, 1 = 128-pixel slices over the two strips a block then runs (conv_plan:
+    // Wl % 128 == 0), 2 = 64-pixel slices (the direct plan's tile of 64 pixels)
+    const int smode = !p.stats ? 0 : p.stats_slices == 4 * (Hl * Wl / 64) ? 2 : Wl > 64 ? 1 : 0;
+    const int nst = smode == 1 ? 2 : 1;
+    const unsigned blocks = (unsigned)((size_t)p.B * ((size_t)Hl * Wl / (4 * UP2_WINO_TILES) / nst) * (p.out.C / WU_BN));
+    static bool attr_set = false;          // (more than 64 KiB of dynamic LDS)
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wino_up2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WU_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wino_up2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WU_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wino_up2_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WU_LDS);
+        attr_set = true;
+    }
+    if (R == 1) hipLaunchKernelGGL(wino_up2_kernel<1>, dim3(blocks), dim3(256), WU_LDS, s, p, smode);
+    else if (R == 2) hipLaunchKernelGGL(wino_up2_kernel<2>, dim3(blocks), dim3(256), WU_LDS, s, p, smode);
+    else hipLaunchKernelGGL(wino_up2_kernel<4>, dim3(blocks), dim3(256), WU_LDS, s, p, smode);
 }
 
 } // namespace sr3

@@ -56,6 +56,8 @@ struct Param {
     float *dev_wino = nullptr;                   // P_CONV 3x3 (wino_weights): G g G^T [16][cout][cin_pad] for prec 0
     float *dev_wino_f = nullptr;                 // the same in fragment-major order [16][cin_pad/8][cout][8] for the
                                                  // one-pass kernel: made when a workspace plan runs the conv there
+    float *dev_up_wino = nullptr;                // Upsample convs (up2_wino_weights): sub-pixel Winograd F(2x2, 2x2) weights
+                                                 // [4][9][cin_pad/8][cout][8] for prec 0 (make_up2_wino_weights)
     float w_unscale = 1.0f;
     bool keep_host = false;                      // part of a fused (conv2 + res_conv) launch
     bool up_phase = false;                       // Upsample conv: stored as 4 sub-pixel phases x 2x2 taps
@@ -160,6 +162,7 @@ struct sr3_ctx {
     bool strict_range = false;
     int fallback_calls = 0;             // calls finished by the f32 fallback since sr3_create
     int gn_wino_passes = 0;             // GroupNorm apply passes launched as launch_gn_wino_input / _fold_ since sr3_create
+    int up2_wino_launches = 0;          // Upsample convs launched on wino_up2_kernel (ConvPlan::up2_wino) since sr3_create
     int wino_gemm_out_launches = 0;     // three-pass Winograd convs launched in the one-kernel form (ConvPlan::wino_gemm_out) since sr3_create
     float *ckpt = nullptr;              // sr3_sample: NCHW copy of the sampler state at the last clean checkpoint
     size_t ckpt_floats = 0;
@@ -443,6 +446,13 @@ bool wino_weights(const Param &p) {
            (p.cout % 64) == 0;
 }
 
+// Upsample conv weights that may run as sub-pixel Winograd F(2x2, 2x2) (conv_plan decides per launch). The layout is made
+// with the phase planes at every load, by either route: it adds original 3x3 taps, which the engine does not keep, so
+// unlike dev_wino_f it cannot be made later from what is on the device.
+bool up2_wino_weights(const Param &p) {
+    return p.kind == P_CONV && p.ks == 3 && p.up_phase && (p.cin_pad % 32) == 0 && (p.cout % UP2_WINO_BN) == 0;
+}
+
 // the one-pass Winograd kernel's fragment-major copy of a parameter's transformed weights, made from dev_wino on the
 // device the first time a workspace plan runs the conv at a one-pass shape (a parameter does not know its level; only
 // the 64x64 and 128x128 levels' convs get one). sr3_load_weight refreshes it with dev_wino.
@@ -501,6 +511,10 @@ int alloc_weights(sr3_ctx *c) {
         if (wino_weights(p)) {
             HIP_OK(hipMalloc(&p.dev_wino, (size_t)16 * p.cout * p.cin_pad * sizeof(float)));
             c->weight_bytes += (size_t)16 * p.cout * p.cin_pad * sizeof(float);
+        }
+        if (up2_wino_weights(p)) {
+            HIP_OK(hipMalloc(&p.dev_up_wino, up2_wino_floats(p.cout, p.cin_pad) * sizeof(float)));
+            c->weight_bytes += up2_wino_floats(p.cout, p.cin_pad) * sizeof(float);
         }
     }
     return 0;
@@ -824,6 +838,7 @@ ConvParams conv_params(const sr3_ctx *c, const ConvCall &k) {
     p.w = p.prec ? c->params[cv.w].dev_split : c->params[cv.w].dev;
     if (!p.prec && cv.cin_pad == a.C) {
         p.w_wino = c->params[cv.w].dev_wino; p.w_wino_f = c->params[cv.w].dev_wino_f; p.wino_ws = c->wino_ws;
+        p.w_up_wino = c->params[cv.w].dev_up_wino;
     }
     if (k.f8 && p.prec) { p.f8 = 1; p.w = c->params[cv.w].dev_f8; }
     p.w_unscale = c->params[cv.w].w_unscale;
@@ -863,9 +878,12 @@ bool gn_writes_u(const sr3_ctx *c, const ConvCall &k, bool raw_wanted, int in_sp
     return conv_plan(conv_params(c, k)).kernel == CK_WINO_THREE_PASS;
 }
 
-// launch_conv on the context's stream; counts the convs whose plan takes the one-kernel form of the three-pass Winograd plan
+// launch_conv on the context's stream; counts the convs whose plan takes the one-kernel form of the three-pass Winograd
+// plan, and the Upsample convs whose plan takes the sub-pixel Winograd form
 static void ctx_launch_conv(sr3_ctx *c, const ConvParams &p) {
-    if (conv_plan(p).wino_gemm_out) ++c->wino_gemm_out_launches;
+    const ConvPlan pl = conv_plan(p);
+    if (pl.wino_gemm_out) ++c->wino_gemm_out_launches;
+    if (pl.up2_wino) ++c->up2_wino_launches;
     launch_conv(p, c->stream);
 }
 
@@ -1604,7 +1622,7 @@ void fill_random(sr3_ctx *c, float *q, size_t n, int seed) {
 struct ScratchConv {
     ConvPlan plan;
     bool f8 = false;                // "f16f8" mode and the shape takes the F8C operand format
-    DevBuf act, w, wino_w, wino_ws, part;
+    DevBuf act, w, wino_w, up_wino_w, wino_ws, part;
     ConvParams p;
 
     // weight_host: OIHW weights, nullptr: random values (timing). The activated input `act` (zero-bordered, Cin
@@ -1620,6 +1638,11 @@ struct ScratchConv {
         if (weight_host) {
             std::vector<float> packed((size_t)ks * ks * Cout * Cin), tmp;
             pack_conv_weight(weight_host, Cout, Cin, ks, Cin, packed.data());
+            if (plan.up2_wino) {
+                tmp.resize(up2_wino_floats(Cout, Cin));
+                make_up2_wino_weights(packed.data(), Cout, Cin, tmp.data());
+                if (up_wino_w.upload(tmp.data(), tmp.size())) return -1;
+            }
             if (up2) {
                 tmp.resize(n_w);
                 make_up2_phase_weights(packed.data(), Cout, Cin, tmp.data());
@@ -1655,6 +1678,10 @@ struct ScratchConv {
                 if (wino_w.alloc(n_wino)) return -1;
                 fill_random(c, wino_w.p, n_wino, 10);       // (either layout: random values)
             }
+            if (plan.up2_wino) {
+                if (up_wino_w.alloc(up2_wino_floats(Cout, Cin))) return -1;
+                fill_random(c, up_wino_w.p, up2_wino_floats(Cout, Cin), 11);
+            }
         }
         if (plan.wino_ws_floats && wino_ws.alloc(plan.wino_ws_floats)) return -1;
         if (plan.part_floats && part.alloc(plan.part_floats)) return -1;
@@ -1668,6 +1695,7 @@ struct ScratchConv {
         p.prec = c->split() ? 1 : 0; p.f8 = f8 ? 1 : 0;
         p.w = w.p;
         (plan.needs_wino_frag ? p.w_wino_f : p.w_wino) = wino_w.p;
+        p.w_up_wino = up_wino_w.p;
         p.wino_ws = wino_ws.p;
         p.part = part.p;
         if (part.p) p.tile_cnt = c->tile_cnt;
@@ -1738,6 +1766,7 @@ void sr3_destroy(sr3_ctx *c) {
         if (p.dev_f8) (void)hipFree(p.dev_f8);
         if (p.dev_wino) (void)hipFree(p.dev_wino);
         if (p.dev_wino_f) (void)hipFree(p.dev_wino_f);
+        if (p.dev_up_wino) (void)hipFree(p.dev_up_wino);
     }
     if (c->final_wq) (void)hipFree(c->final_wq);
     if (c->ci_w) (void)hipFree(c->ci_w);
@@ -1824,6 +1853,7 @@ int sr3_conv_plan(int B, int H, int W, int Cin, int Cout, int ks, int stride, in
 int sr3_wino_weights_host(const float *packed_host, int Cout, int CinPad, int frag, float *dst_host) {
     if (!packed_host || !dst_host || Cout <= 0 || CinPad <= 0 || (CinPad % 8))
         return fail("sr3_wino_weights_host: Cout > 0 and CinPad a positive multiple of 8");
+    if (frag == 2) { make_up2_wino_weights(packed_host, Cout, CinPad, dst_host); return 0; }
     if (!frag) { make_wino_weights(packed_host, Cout, CinPad, dst_host); return 0; }
     std::vector<float> wv((size_t)16 * Cout * CinPad);
     make_wino_weights(packed_host, Cout, CinPad, wv.data());
@@ -1889,6 +1919,11 @@ int sr3_load_weight(sr3_ctx *c, const char *name, const float *host, const int64
             std::vector<float> packed((size_t)p.ks * p.ks * p.cout * p.cin_pad);
             pack_conv_weight(host, p.cout, p.cin, p.ks, p.cin_pad, packed.data());
             size_t rows = (size_t)p.ks * p.ks * p.cout;
+            if (p.dev_up_wino) {    // (from the nine taps, before the phase planes replace them)
+                std::vector<float> uw(up2_wino_floats(p.cout, p.cin_pad));
+                make_up2_wino_weights(packed.data(), p.cout, p.cin_pad, uw.data());
+                HIP_OK(hipMemcpy(p.dev_up_wino, uw.data(), uw.size() * sizeof(float), hipMemcpyHostToDevice));
+            }
             if (p.up_phase) {       // nearest x2 + 3x3 == four 2x2 phase convs on the low-res input
                 std::vector<float> ph(p.dev_floats);
                 make_up2_phase_weights(packed.data(), p.cout, p.cin_pad, ph.data());
@@ -2006,7 +2041,7 @@ int sr3_load_weights_dev(sr3_ctx *c, int n, const char *const *names, const floa
             if (idx[e] == ci_idx && c->ci_w) HIP_OK(hipMemcpyAsync(c->h_stage + L.ci_src, src, src_bytes, hipMemcpyDeviceToHost, s));
             if (idx[e] == fc_idx && (c->final_wm || c->final_wq))
                 HIP_OK(hipMemcpyAsync(c->h_stage + L.fc_src, src, src_bytes, hipMemcpyDeviceToHost, s));
-            launch_weight_pack(src, p.cout, p.cin, p.ks, p.cin_pad, p.up_phase, p.dev, p.dev_wino, c->d_wmax + idx[e], s);
+            launch_weight_pack(src, p.cout, p.cin, p.ks, p.cin_pad, p.up_phase, p.dev, p.dev_wino, c->d_wmax + idx[e], s, p.dev_up_wino);
             if (p.dev_wino && p.dev_wino_f) launch_wino_frag(p.dev_wino, p.cout, p.cin_pad, p.dev_wino_f, s);
         }
         p.host.clear();
@@ -2115,6 +2150,7 @@ int64_t sr3_read_weight_layout(sr3_ctx *c, const char *name, int layout, void *h
     case SR3_WL_F8: src = p.dev_f8; floats = p.dev_floats; break;
     case SR3_WL_WINO: src = p.dev_wino; floats = wino_floats; break;
     case SR3_WL_WINO_FRAG: src = p.dev_wino_f; floats = wino_floats; break;
+    case SR3_WL_UP_WINO_FRAG: src = p.dev_up_wino; floats = up2_wino_floats(p.cout, p.cin_pad); break;
     case SR3_WL_CONV_IN:
         if (conv && pi == c->mods[0].conv.w) { src = c->ci_w; floats = conv_in_weight_floats(p.cout); }
         break;
@@ -2489,6 +2525,7 @@ int sr3_set_range_policy(sr3_ctx *c, int strict) {
 int sr3_fallback_calls(sr3_ctx *c) { return c ? c->fallback_calls : fail("null context"); }
 int sr3_gn_wino_passes(sr3_ctx *c) { return c ? c->gn_wino_passes : fail("null context"); }
 int sr3_wino_gemm_out_launches(sr3_ctx *c) { return c ? c->wino_gemm_out_launches : fail("null context"); }
+int sr3_up2_wino_launches(sr3_ctx *c) { return c ? c->up2_wino_launches : fail("null context"); }
 int sr3_replay_calls(sr3_ctx *c) { return c ? c->replay_calls : fail("null context"); }
 void *sr3_test_flag_address(sr3_ctx *c) { return c ? c->d_ovf : nullptr; }
 const char *sr3_last_warning(void) { return g_warn.c_str(); }
@@ -2708,9 +2745,9 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     // as the engine runs the shape: behind the fused pass the conv starts from U (random contents like every input here)
     const bool to_u = sc.gn_writes_u(c);
     if (to_u) { fill_random(c, p.wino_ws, (size_t)16 * B * (Hin / 2) * (Win / 2) * Cin, 11); p.u_ready = 1; }
-    for (int i = 0; i < 2; ++i) launch_conv(p, c->stream);
+    for (int i = 0; i < 2; ++i) ctx_launch_conv(c, p);       // (the counters tell a tool which form it timed)
     HIP_OK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < iters; ++i) launch_conv(p, c->stream);
+    for (int i = 0; i < iters; ++i) ctx_launch_conv(c, p);
     HIP_OK(hipEventRecord(e1, c->stream));
     for (int i = 0; i < iters; ++i) {
         if (to_u) launch_gn_wino_input(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, p.wino_ws, c->stream);

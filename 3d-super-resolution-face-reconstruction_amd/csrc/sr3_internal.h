@@ -8,7 +8,7 @@
 namespace sr3 {
 
 // ---- environment switches ---------------------------------------------------------------------------
-// Everything the library reads from the environment (INTEGRATION.md lists the same eight; each is read once per process
+// Everything the library reads from the environment (INTEGRATION.md lists the same ten; each is read once per process
 // and then baked into captured graphs):
 //   SR3_NO_GRAPH=1          every kernel launched individually, no hipGraph replay (hosts that cannot capture)
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
@@ -20,6 +20,10 @@ namespace sr3 {
 //   SR3_NO_WINO_GEMM_OUT=1  three-pass Winograd convs always as position GEMMs + wino_output_kernel (M through memory);
 //                           same bits
 //   SR3_WINO_GEMM_OUT_FORCE=1  that one-kernel form wherever its preconditions hold, whatever the block count and Cin
+//                           (tests, per-shape timing)
+//   SR3_NO_UP2_WINO=1       exact-f32 Upsample convs always as four sub-pixel 2x2 phase convs on the direct kernel (the
+//                           bits of the library before wino_up2_kernel)
+//   SR3_UP2_WINO_FORCE=1    the sub-pixel Winograd form wherever its preconditions hold, whatever the block count
 //                           (tests, per-shape timing)
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
@@ -121,6 +125,9 @@ struct ConvParams {
     // the one-pass kernel's copy of w_wino in fragment-major order [16][CinPad/8][Cout][8] (make_wino_weights_frag);
     // null: a conv of the one-pass shapes runs on the direct kernel
     const float *w_wino_f = nullptr;
+    // Upsample convs (up2, prec 0): the sub-pixel Winograd F(2x2, 2x2) weights [4 phases][9][CinPad/8][Cout][8]
+    // (make_up2_wino_weights); null: the four phase convs on the direct kernel
+    const float *w_up_wino = nullptr;
     // 1 (CK_WINO_THREE_PASS only): U of in0 || in1 is already at the head of wino_ws (launch_gn_wino_input wrote it);
     // launch_conv_wino then skips wino_input_kernel and does nothing else differently. No input of conv_plan.
     int u_ready = 0;
@@ -194,6 +201,10 @@ struct ConvPlan {
     // CK_WINO_THREE_PASS only: 0 = position GEMMs + wino_output_kernel; 64 | 128 = wino_gemm_out_kernel with that many
     // output channels per block (the M half of wino_ws then stays unused). Not part of the exported plan.
     int wino_gemm_out = 0;
+    // Upsample convs only: 0 = the four phase convs on `kernel`; 1 | 2 | 4 = wino_up2_kernel (kernels_wino.hip) with that
+    // many tile rows per block, reading ConvParams::w_up_wino instead of w. Not part of the exported plan: kernel, phases,
+    // split and stats_slices stay the direct plan's, and the statistics come in the same slices.
+    int up2_wino = 0;
     const char *error = nullptr;       // a request no kernel honours (ConvParams::f8 on a shape outside the F8C kernel)
 };
 // reads p as launch_conv does: a null part / tile_cnt / w_wino / w_wino_f / wino_ws / stats means "not offered", and the
@@ -213,6 +224,22 @@ void launch_conv(const ConvParams &p, hipStream_t s);
 const char *conv_take_error();
 // packed [9][Cout][CinPad] -> [py*2+px][dy2*2+dx2][Cout][CinPad]
 void make_up2_phase_weights(const float *packed9, int Cout, int CinPad, float *dst);
+// ---- Upsample conv as sub-pixel Winograd F(2x2, 2x2) (kernels_wino.hip, wino_up2_kernel) --------------------------------
+// Each phase (py, px) is a stride-1 2x2 conv over the zero-bordered low-resolution image, so 2x2 outputs of a phase come
+// from a 3x3 window with 9 products instead of 16:
+//   Y = A^T [ (G g G^T) . (B^T d B) ] A,  G = [[1,0],[1,1],[0,1]],  B^T = [[1,-1,0],[0,1,0],[0,1,-1]],  A^T = [[1,1,0],[0,1,-1]]
+//   d = padded low-resolution rows 2ti + py .. 2ti + py + 2, columns 2tj + px .. + 2; outputs at (2(2ti + a) + py, 2(2tj + b) + px).
+// The transforms hold 0 and +-1 only; G g G^T is a sum of original 3x3 taps (1-D: py = 0 -> {w0}, {w0, w1, w2}, {w1, w2};
+// py = 1 -> {w0, w1}, {w0, w1, w2}, {w2}), added in fp64 from 0.0 in (dy, dx) order and rounded once.
+// One block = 32 tiles (R tile rows of 32 / R tiles: R = 1 | 2 | 4 for low-resolution widths 64k | 32 | 16) x 32 output
+// channels x the four phases, one phase per wave. Taken from UP2_WINO_MIN_BLOCKS blocks on (two resident per CU).
+constexpr int UP2_WINO_TILES = 32, UP2_WINO_BN = 32;
+constexpr int UP2_WINO_MIN_BLOCKS = 512;
+// host helper: packed [9][Cout][CinPad] -> [py*2+px][3i+j][CinPad/8][Cout][8]; up2_wino_floats: its size
+inline size_t up2_wino_floats(int Cout, int CinPad) { return (size_t)36 * Cout * CinPad; }
+void make_up2_wino_weights(const float *packed9, int Cout, int CinPad, float *dst);
+// the form ConvPlan::up2_wino names; p as launch_conv takes it (up2 = 1, at the output resolution)
+void launch_conv_up2_wino(const ConvParams &p, const ConvPlan &plan, hipStream_t s);
 // ---- Winograd F(2x2, 3x3) for the exact-f32 3x3 convs of the deep levels (kernels_wino.hip) ----------------------
 // Y = A^T [ (G g G^T) . (B^T d B) ] A per 2x2 output tile: the 16 positions of the transformed 4x4 window are 16
 // independent GEMMs [B*H/2*W/2][Cin] x [Cin][Cout] on the f32 implicit-GEMM kernel (4 instead of 9 MACs per output
@@ -324,8 +351,9 @@ float split_conv_weight_k(const float *packed, size_t rows, int CinPad, int k, f
 // The device twins of the host helpers above, bit for bit. launch_weight_pack: fp32 OIHW in device memory -> packed
 // [tap][Cout][CinPad] (up_phase: the 16 phase planes), G g G^T planes into `wino` when given (ks 3, not up_phase), and
 // max|w| of what it wrote to `packed` (NaN ignored) as a bit pattern into *wmax by atomic max (zero it first).
+// up_wino (up_phase only, may be null): the make_up2_wino_weights layout.
 void launch_weight_pack(const float *oihw, int Cout, int Cin, int ks, int CinPad, bool up_phase, float *packed, float *wino,
-                        unsigned *wmax, hipStream_t s);
+                        unsigned *wmax, hipStream_t s, float *up_wino = nullptr);
 // the same maximum of a tensor that is packed already (n a multiple of 4)
 void launch_weight_absmax(const float *packed, size_t n, unsigned *wmax, hipStream_t s);
 // split_conv_weight_k over `floats` packed values (a multiple of 32)

@@ -161,6 +161,11 @@ class Engine:
         and the output transform in one kernel; 0 under SR3_NO_WINO_GEMM_OUT=1 and outside the f32 mode."""
         return int(self.lib.sr3_wino_gemm_out_launches(self.ctx))
 
+    def up2_wino_launches(self) -> int:
+        """Upsample convs this engine launched (or captured into a graph) as sub-pixel Winograd F(2x2, 2x2); 0 under
+        SR3_NO_UP2_WINO=1 and outside the f32 mode."""
+        return int(self.lib.sr3_up2_wino_launches(self.ctx))
+
     def replay_calls(self) -> int:
         """Calls finished after replaying work whose in-place split-K wait had given up (SR3_OK_REPLAYED)."""
         return int(self.lib.sr3_replay_calls(self.ctx))
@@ -202,7 +207,7 @@ class Engine:
             self.load_weight(name, sd[prefix + name])
 
     WEIGHT_LAYOUTS = {"plain": 0, "split": 1, "f8": 2, "wino": 3, "wino_frag": 4, "conv_in": 5, "final_mfma": 6,
-                      "final_valu": 7, "fused_bias": 8, "ident": 9}
+                      "final_valu": 7, "fused_bias": 8, "ident": 9, "up_wino_frag": 10}
 
     def load_weights_device(self, items: Sequence[Tuple[str, object]]) -> int:
         """Refreshes the listed parameters from tensors that live on this engine's device: `items` is a list of

@@ -140,7 +140,8 @@ enum {
     SR3_WL_FINAL_VALU = 7, /* final conv: [9][C][4] */
     SR3_WL_FUSED_BIAS = 8, /* asked of a block's conv2 bias: conv2 bias + res_conv bias */
     SR3_WL_IDENT = 9,      /* asked of a block's conv2 weight: the identity-skip matrix */
-    SR3_N_WEIGHT_LAYOUTS = 10
+    SR3_WL_UP_WINO_FRAG = 10, /* Upsample convs: sub-pixel Winograd F(2x2, 2x2) weights [4 phases][9][CinPad/8][Cout][8] */
+    SR3_N_WEIGHT_LAYOUTS = 11
 };
 /* Copies at most cap_bytes of the layout to `host` and returns the layout's size in bytes; 0: the parameter has no such
  * layout (now); < 0: error. Synchronises the context's stream. */
@@ -238,6 +239,9 @@ int sr3_gn_wino_passes(sr3_ctx *ctx);
 /* Three-pass Winograd convs this context launched (or captured into a graph) since sr3_create in the form that runs the position GEMMs
  * and the output transform in one kernel (0 under SR3_NO_WINO_GEMM_OUT=1): tells a test which form ran. */
 int sr3_wino_gemm_out_launches(sr3_ctx *ctx);
+/* Upsample convs this context launched (or captured into a graph) since sr3_create as sub-pixel Winograd F(2x2, 2x2)
+ * (wino_up2_kernel; exact f32 only; 0 under SR3_NO_UP2_WINO=1): tells a test which form ran. */
+int sr3_up2_wino_launches(sr3_ctx *ctx);
 /* TEST HOOK (tests/test_gpu_round4.py): device address of the context's flag word (bit 0: range overflow, bit 1: an
  * in-place split-K wait gave up), so that a test kernel on another stream can raise a bit in the middle of a running
  * sr3_sample call and the replay logic is exercised deterministically. Not for production use. */
@@ -307,7 +311,9 @@ int sr3_bench_conv(sr3_ctx *ctx, int B, int Hin, int Win, int C0, int C1, int Co
 /* Host-side weight layouts of the exact-f32 Winograd convs (no GPU involved): packed_host is the
  * kernel layout [9][Cout][CinPad] of a 3x3 conv; dst receives 16 * Cout * CinPad floats of
  * G g G^T as [16][Cout][CinPad] (frag = 0, the three-pass path) or [16][CinPad/8][Cout][8]
- * (frag = 1, the one-pass kernel). CinPad a multiple of 8. */
+ * (frag = 1, the one-pass kernel). CinPad a multiple of 8.
+ * frag = 2: the Upsample conv's sub-pixel Winograd F(2x2, 2x2) weights instead, 36 * Cout * CinPad floats as
+ * [py * 2 + px][3i + j][CinPad/8][Cout][8]: sums of the original taps, added in fp64 in (dy, dx) order, rounded once. */
 int sr3_wino_weights_host(const float *packed_host, int Cout, int CinPad, int frag, float *dst_host);
 
 /* ---- single ops through the same kernels (parity tests call these) ------------------------ */
