@@ -80,6 +80,9 @@ PROTOTYPES = {
     "sr3_sample_begin": (_I, [_P, _F, _I, _I, _I, _F, _U64, _U64]),
     "sr3_sample_step": (_I, [_P, _I, _F]),
     "sr3_sample_end": (_I, [_P, _F]),
+    "sr3_sample_begin_from": (_I, [_P, _F, _I, _I, _I, _F, _I, _I, _F, _U64, _U64]),
+    "sr3_sample_from": (_I, [_P, _F, _I, _I, _I, _F, _I, _I, _F, _U64, _U64, _F, _F]),
+    "sr3_num_frames_from": (_I, [_P, _I]),
     "sr3_range_check": (_I, [_P]),
     "sr3_set_range_policy": (_I, [_P, _I]),
     "sr3_fallback_calls": (_I, [_P]),
@@ -133,7 +136,8 @@ PROTOTYPES = {
 # counters and opt-in entry points added to the C-ABI after its first A/B-able build (load)
 NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_wino_launches", "sr3_set_dropout", "sr3_set_dropout_masks", "sr3_dropout_layers",
                   "sr3_dropout_mask_bytes", "sr3_op_dropout_mask", "sr3_load_weights_dev", "sr3_read_weight_layout",
-                  "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual")
+                  "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual",
+                  "sr3_sample_begin_from", "sr3_sample_from", "sr3_num_frames_from")
 
 _lib = None
 

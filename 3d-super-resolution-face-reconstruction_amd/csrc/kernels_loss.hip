@@ -179,6 +179,14 @@ __global__ void loss_final_kernel(const double *__restrict__ part, int B, int bp
     per_image[b] = s;
 }
 
+// a[b] = av, s[b] = sv: the per-row coefficients of a q_sample whose rows share one level (the sampler's warm start)
+__global__ void fill_pair_kernel(float *__restrict__ a, float *__restrict__ s, float av, float sv, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    a[b] = av;
+    s[b] = sv;
+}
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int blocks_of(int HW, int G) { return ((HW + G - 1) / G + THREADS - 1) / THREADS; }
 } // namespace
@@ -196,6 +204,11 @@ void launch_q_sample_state(const float *hr, const float *cond, int N, int row_of
     const dim3 grid((unsigned)((size_t)B * p.bpi)), block(THREADS);
     if (vec) hipLaunchKernelGGL(q_sample_state_kernel<4>, grid, block, 0, st, p);
     else hipLaunchKernelGGL(q_sample_state_kernel<1>, grid, block, 0, st, p);
+}
+
+void launch_fill_pair(float *a, float *s, float av, float sv, int B, hipStream_t st) {
+    if (B <= 0) return;
+    hipLaunchKernelGGL(fill_pair_kernel, dim3((B + 63) / 64), dim3(64), 0, st, a, s, av, sv, B);
 }
 
 int loss_blocks(int H, int W) { return blocks_of(H * W, 1); }     // the scalar form: the most blocks

@@ -234,6 +234,12 @@ struct sr3_ctx {
     bool uses_hist = false; // the update keeps the clamped x0 of the previous step (xhist)
     bool hist_valid = false;// xhist holds the x0 of an earlier step of the current call (reset by sr3_sample_begin)
     float *d_nl = nullptr;  // [T+1]
+    // Warm start (sr3_sample_begin_from). d_start: a[B] | s[B], the per-row q_sample coefficients of the
+    // start state (grown on demand). fold_first: the call was begun there with a multistep sampler, so its first step
+    // (no x0 history yet) takes c1 + c3 as its c1; sr3_sample_begin clears it.
+    float *d_start = nullptr;
+    int start_rows = 0;
+    bool fold_first = false;
 
     // sampler state
     uint64_t seed = 0, image_offset = 0;
@@ -1557,6 +1563,9 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     sa.nl = c->s_nl[t + 1];
     sa.a = c->s_a[t]; sa.b = c->s_b[t]; sa.c1 = c->s_c1[t]; sa.c2 = c->s_c2[t]; sa.c3 = c->s_c3[t];
     sa.sigma = c->s_sig[t];
+    // a call begun below the top of the schedule (sr3_sample_begin_from): its first step has no previous x0, and c1[t]
+    // alone is the second-order weight; with c3[t] folded in, the step is the first-order one exactly
+    if (c->fold_first && c->uses_hist && !c->hist_valid) sa.c1 = c->s_c1[t] + c->s_c3[t];
     sa.draw = (uint32_t)(c->T - t); sa.pad_ = 0;
     // the first step after sr3_sample_begin has no previous x0: it only stores its own
     sa.hist = c->uses_hist ? (c->hist_valid ? 2u : 1u) : 0u;
@@ -1775,6 +1784,7 @@ void sr3_destroy(sr3_ctx *c) {
     if (c->nfb) (void)hipFree(c->nfb);
     if (c->arena) (void)hipFree(c->arena);
     if (c->d_nl) (void)hipFree(c->d_nl);
+    if (c->d_start) (void)hipFree(c->d_start);
     drop_graphs(c);
     if (c->d_ovf) (void)hipFree(c->d_ovf);
     if (c->ckpt) (void)hipFree(c->ckpt);
@@ -2354,13 +2364,21 @@ int sr3_max_batch(sr3_ctx *c, int H, int W) {
     return b;
 }
 
+int sr3_num_frames_from(sr3_ctx *c, int start_step) {
+    if (!c) return fail("null context");
+    if (c->T < 1) return fail("no schedule set");
+    if (start_step < 1 || start_step > c->T)
+        return fail("sr3_num_frames_from: start_step %d outside [1, %d]", start_step, c->T);
+    const int si = 1 | (c->T / 10);
+    int n = 0;
+    for (int i = 0; i < start_step; ++i) n += (i % si == 0) ? 1 : 0;
+    return n;
+}
+
 int sr3_num_frames(sr3_ctx *c) {
     if (!c) return fail("null context");
     if (c->T < 1) return fail("no schedule set");
-    const int si = 1 | (c->T / 10);
-    int n = 0;
-    for (int i = 0; i < c->T; ++i) n += (i % si == 0) ? 1 : 0;
-    return n;
+    return sr3_num_frames_from(c, c->T);
 }
 
 int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_noise_dev,
@@ -2374,12 +2392,73 @@ int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, con
     c->seed = seed;
     c->image_offset = image_offset;
     c->hist_valid = false;
+    c->fold_first = false;
     if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
     if (range_reset(c)) return -1;
     c->pbegin(F_MISC);
     if (cond_dev) launch_nchw_to_nhwc(cond_dev, B, nc, c->x0, 0, c->stream);
     launch_init_state(c->x0, nc, C, init_noise_dev, seed, image_offset, B, c->stream);
     if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
+    c->pend();
+    c->sampling = true;
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+namespace {
+// float32 sqrt(1 - a^2) of q_sample (diffusion.py:281), every operation rounded by itself as noise_coefficient
+// (diffusion.py of this package) forms it: the product must not meet the difference in one fused multiply-add
+float q_sample_noise_coefficient(float a) {
+#pragma clang fp contract(off)
+    const float aa = a * a;
+    const float d = 1.0f - aa;
+    return sqrtf(d);
+}
+}
+
+int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_dev, int start_step,
+                          int noised, const float *noise0_dev, uint64_t seed, uint64_t image_offset) {
+    if (check_ready(c)) return -1;
+    if (c->T < 1) return fail("sr3_sample_begin_from: no schedule set (sr3_set_schedule)");
+    if (!init_dev) return fail("sr3_sample_begin_from: init_dev is null");
+    if (start_step < 1 || start_step > c->T)
+        return fail("sr3_sample_begin_from: start_step %d outside [1, %d]", start_step, c->T);
+    if (B < 1) return fail("sr3_sample_begin_from: bad batch B=%d", B);
+    const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
+    if (cond_dev && nc <= 0) return fail("conditioning given but in_channel == out_channel");
+    if (!cond_dev && nc != 0) return fail("unconditional sampling needs in_channel == out_channel");
+    if (init_dev == cond_dev && nc != C)
+        return fail("sr3_sample_begin_from: the conditioning image has %d channels and cannot start a state of %d", nc, C);
+    if (noised && c->cfg.in_channel > 8)
+        return fail("sr3_sample_begin_from: in_channel = %d, the state kernel builds at most 8 input channels", c->cfg.in_channel);
+    if (ensure_workspace(c, B, H, W)) return -1;
+    if (noised && c->start_rows < B) {
+        if (c->d_start) HIP_OK(hipFree(c->d_start));   // (hipFree waits for the kernels still reading it)
+        c->d_start = nullptr; c->start_rows = 0;
+        HIP_OK(hipMalloc(&c->d_start, (size_t)2 * B * sizeof(float)));
+        c->start_rows = B;
+    }
+    c->seed = seed;
+    c->image_offset = image_offset;
+    c->hist_valid = false;
+    c->fold_first = true;
+    if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
+    if (range_reset(c)) return -1;
+    c->pbegin(F_MISC);
+    if (noised) {
+        // the reference's q_sample (diffusion.py:275-282) at the level of the state before step start_step - 1
+        const float level = c->s_nl[start_step];
+        float *a = c->d_start, *s = c->d_start + c->start_rows;
+        launch_fill_pair(a, s, level, q_sample_noise_coefficient(level), B, c->stream);
+        NoiseRef nz;
+        nz.noise = noise0_dev; nz.seed = seed; nz.image_offset = image_offset; nz.per_source = 0;
+        launch_q_sample_state(init_dev, cond_dev, B, 0, a, s, nz, B, C, nc, c->x0, c->x0p, c->d_ovf, nullptr, c->stream);
+    } else {
+        // the image itself, bit for bit (as Checkpoint::restore reloads a state)
+        if (cond_dev) launch_nchw_to_nhwc(cond_dev, B, nc, c->x0, 0, c->stream);
+        launch_init_state(c->x0, nc, C, init_dev, seed, image_offset, B, c->stream);
+        if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
+    }
     c->pend();
     c->sampling = true;
     HIP_OK(hipGetLastError());
@@ -2462,15 +2541,21 @@ struct Checkpoint {
 };
 }
 
-int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *noise_dev, uint64_t seed,
-               uint64_t image_offset, float *out_dev, float *frames_dev) {
-    if (!out_dev) return fail("sr3_sample: out_dev is null");
+namespace {
+// sr3_sample (init_dev == nullptr: from pure noise, start_step = T) and sr3_sample_from: steps t = start_step-1 .. 0
+int sample_impl(sr3_ctx *c, const char *what, const float *cond_dev, int B, int H, int W, const float *init_dev,
+                int start_step, int noised, const float *noise_dev, uint64_t seed, uint64_t image_offset, float *out_dev,
+                float *frames_dev) {
+    if (!out_dev) return fail("%s: out_dev is null", what);
     if (c && c->drop_live() && c->drop_masks)
-        return fail("sr3_sample: injected dropout masks are set, and one buffer cannot hold the masks of every step — drive the "
+        return fail("%s: injected dropout masks are set, and one buffer cannot hold the masks of every step — drive the "
                     "loop with sr3_sample_step (each step consumes the buffer set at that moment) or return to the Philox "
-                    "masks with sr3_set_dropout_masks(ctx, NULL, 0)");
-    if (sr3_sample_begin(c, cond_dev, B, H, W, noise_dev, seed, image_offset)) return -1;
+                    "masks with sr3_set_dropout_masks(ctx, NULL, 0)", what);
+    if (init_dev ? sr3_sample_begin_from(c, cond_dev, B, H, W, init_dev, start_step, noised, noise_dev, seed, image_offset)
+                 : sr3_sample_begin(c, cond_dev, B, H, W, noise_dev, seed, image_offset))
+        return -1;
     const int T = c->T, si = 1 | (T / 10);
+    const int s0 = init_dev ? start_step : T;      // steps of this call; the injected noise is [s0, B, C, H, W]
     const size_t slab = (size_t)B * c->cfg.out_channel * H * W;
     // Guard of the split-f16 modes (the policy of guarded_eval, with a segment of `seg` steps as the unit of replay): at
     // the end of every segment the device flag is read (one stream synchronisation: ~10 per call); while it is clean the
@@ -2487,16 +2572,16 @@ int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const flo
         if (ck.reserve()) return -1;
         const int r = range_read(c);     // (the initial state / its packed copy)
         if (r < 0) return -1;
-        if (r == 1 && c->strict_range) return range_fail(c, "sr3_sample");
+        if (r == 1 && c->strict_range) return range_fail(c, what);
         if (r == 1) { step_down(c, true); guard = false; stepped_down = true; }
-        else if (ck.save(T - 1, 0)) return -1;
+        else if (ck.save(s0 - 1, 0)) return -1;
     }
-    for (int t = T - 1, f = 0; t >= 0; --t) {
-        const float *nz = (noise_dev && t > 0) ? noise_dev + (size_t)(T - t) * slab : nullptr;
+    for (int t = s0 - 1, f = 0; t >= 0; --t) {
+        const float *nz = (noise_dev && t > 0) ? noise_dev + (size_t)(s0 - t) * slab : nullptr;
         float *fr = (frames_dev && (t % si == 0)) ? frames_dev + (size_t)(f++) * slab : nullptr;
         if (step_checked(c, t, nz, fr)) return -1;
         if (c->prof && (t % 8) == 0) c->pflush();  // bound the number of live events
-        if (!guard || (t != 0 && ((T - t) % seg) != 0)) continue;
+        if (!guard || (t != 0 && ((s0 - t) % seg) != 0)) continue;
         // a segment ends here: the state is the one before step t - 1 (after the last step: the result)
         const int r = range_read(c);
         if (r < 0) return -1;
@@ -2504,7 +2589,7 @@ int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const flo
             if (t > 0 && ck.save(t - 1, f)) return -1;
             continue;
         }
-        if (r == 1 && c->strict_range) return range_fail(c, "sr3_sample");
+        if (r == 1 && c->strict_range) return range_fail(c, what);
         if (ck.restore()) return -1;
         if (r == 2) replayed = true;
         else { guard = step_down(c) != A_F32; stepped_down = true; }
@@ -2513,8 +2598,21 @@ int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const flo
     if (sample_copy_out(c, out_dev)) return -1;
     // (nothing reads the flag once the loop runs in f32, and the packed-state stores still raise it: leave it clean)
     if (stepped_down && range_reset(c)) return -1;
-    if (stepped_down) return warn_fallback(c, "sr3_sample", "the rest of the loop from the last in-range checkpoint", c->split());
-    return replayed ? warn_replay(c, "sr3_sample", "the segment of T/10 steps it happened in") : 0;
+    if (stepped_down) return warn_fallback(c, what, "the rest of the loop from the last in-range checkpoint", c->split());
+    return replayed ? warn_replay(c, what, "the segment of T/10 steps it happened in") : 0;
+}
+}
+
+int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *noise_dev, uint64_t seed,
+               uint64_t image_offset, float *out_dev, float *frames_dev) {
+    return sample_impl(c, "sr3_sample", cond_dev, B, H, W, nullptr, 0, 0, noise_dev, seed, image_offset, out_dev, frames_dev);
+}
+
+int sr3_sample_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_dev, int start_step, int noised,
+                    const float *noise_dev, uint64_t seed, uint64_t image_offset, float *out_dev, float *frames_dev) {
+    if (!init_dev) return fail("sr3_sample_from: init_dev is null");
+    return sample_impl(c, "sr3_sample_from", cond_dev, B, H, W, init_dev, start_step, noised, noise_dev, seed, image_offset,
+                       out_dev, frames_dev);
 }
 
 int sr3_set_range_policy(sr3_ctx *c, int strict) {

@@ -627,6 +627,9 @@ struct NoiseRef {
 void launch_q_sample_state(const float *hr, const float *cond, int N, int row_offset, const float *a, const float *s,
                            const NoiseRef &nz, int B, int C, int nc, const TDesc &state, float *packed, int *ovf,
                            float *x_noisy_out, hipStream_t st);
+// a[b] = av, s[b] = sv for b < B: the coefficient arrays of launch_q_sample_state when every row shares one level
+// (sr3_sample_begin_from), written on the stream from kernel arguments: no host copy, no synchronisation
+void launch_fill_pair(float *a, float *s, float av, float sv, int B, hipStream_t st);
 // per_image[b] = sum over the image of |n - eps| (loss_type 0) or (n - eps)^2 (1): difference and square in fp32,
 // accumulation in fp64, one partial per block added in block order (no floating-point atomics: bitwise reproducible).
 // eps: unpadded NHWC [B][H][W][C]; eps_out (optional): eps as NCHW. ws: loss_blocks(H, W) * B doubles.

@@ -89,6 +89,7 @@ class GaussianDiffusion(nn.Module):
         self._sched_pushed = None   # engine id the schedule was pushed to
         self._sampler = ("ddpm", None, 0.0)   # set_sampler(); not part of state_dict()
         self._lr = None                       # set_lr_consistency(): (fp32 [N,C,lh,lw], strength); not part of state_dict()
+        self._start = None                    # set_start(): (strength | None, step | None, init, noised); not part of state_dict()
 
     # ---- reference surface that is configuration only -----------------------------------------
     def set_loss(self, device=None):
@@ -133,6 +134,58 @@ class GaussianDiffusion(nn.Module):
         _samplers.check_sampler(kind, steps, eta, self.num_timesteps if self._sched_np is not None else None)
         self._sampler = (kind, None if steps is None or kind == "ddpm" else int(steps), float(eta))
         self._sched_pushed = None
+
+    def set_start(self, strength=None, *, step=None, init="cond", noised=True) -> None:
+        """Warm start of every sampling entry point: instead of pure noise at the top of the schedule,
+        a call starts from its own conditioning image, forward-diffused (q_sample, diffusion.py:275-282) to an
+        intermediate level, and runs only the last s0 of its S steps — the reference's own p_sample steps (:183-215), s0
+        UNet evaluations instead of S.
+
+          strength  in (0, 1]: s0 = max(1, round(strength * S)), re-derived whenever S changes (set_sampler,
+                    set_new_noise_schedule); 1.0 runs every step, from q_sample at the top level rather than pure noise
+          step      s0 itself, in [1, S] (checked against the S of the moment at every call)
+          init      "cond": every call starts from its own x_in — super_resolution, sample_batch, p_sample_loop,
+                    validation.validate_batch (samples x images), mc-dropout runs and the dist.sharded_* helpers pick it
+                    up with no further plumbing. Raises for the unconditional model, which has no such image. An
+                    explicit start image is a per-call argument (sample_batch(init=...)).
+          noised    False: the image is taken as the state itself (it already sits at that level)
+
+        Both None turns it off: every call is then bit for bit what it was. Like set_sampler, the setting survives
+        set_new_noise_schedule and set_sampler, adds nothing to state_dict(), and leaves p_sample alone. Sample quality at
+        a given strength is a property of the checkpoint and is not established here."""
+        if strength is None and step is None:
+            self._start = None
+            return
+        if strength is not None and step is not None:
+            raise ValueError("give strength or step, not both")
+        if init != "cond":
+            raise ValueError(f"init must be 'cond' (an explicit image is passed per call: sample_batch(init=...)), got {init!r}")
+        if not self.conditional:
+            raise ValueError("init='cond' needs a conditional model: the unconditional one has no conditioning image")
+        if strength is not None:
+            strength = float(strength)
+            if not 0.0 < strength <= 1.0:       # (also refuses NaN)
+                raise ValueError(f"strength must lie in (0, 1], got {strength}")
+        else:
+            if isinstance(step, bool) or int(step) != step:
+                raise ValueError(f"step must be an integer, got {step!r}")
+            step = int(step)
+            S = self.num_sampling_steps if self._sched_np is not None or self._sampler[1] is not None else None
+            if step < 1 or (S is not None and step > S):
+                raise ValueError(f"step must lie in [1, S] (S = {S} sampling steps), got {step}")
+        self._start = (strength, step, "cond", bool(noised))
+
+    @staticmethod
+    def start_steps(S: int, strength=None, step=None) -> int:
+        """s0 of a warm start over S steps: max(1, round(strength * S)), or `step` checked against [1, S]."""
+        if strength is not None:
+            strength = float(strength)
+            if not 0.0 < strength <= 1.0:
+                raise ValueError(f"strength must lie in (0, 1], got {strength}")
+            return max(1, min(int(S), int(round(strength * int(S)))))
+        if isinstance(step, bool) or int(step) != step or not 1 <= int(step) <= int(S):
+            raise ValueError(f"step must be an integer in [1, S] (S = {int(S)} sampling steps), got {step!r}")
+        return int(step)
 
     def set_lr_consistency(self, lr, strength: float = 1.0) -> None:
         """Keeps every sample consistent with its low-resolution input: each step of every sampling
@@ -200,6 +253,13 @@ class GaussianDiffusion(nn.Module):
         kind, steps, _ = self._sampler
         return self.num_timesteps if steps is None else int(steps)
 
+    @property
+    def num_steps_run(self) -> int:
+        """UNet evaluations one sampling call actually runs: s0 under set_start, else S."""
+        if self._start is None:
+            return self.num_sampling_steps
+        return self.start_steps(self.num_sampling_steps, self._start[0], self._start[1])
+
     def _engine(self):
         eng = self.denoise_fn.engine()
         if self._sched_np is None:
@@ -216,9 +276,13 @@ class GaussianDiffusion(nn.Module):
             kind, steps, eta = self._sampler
             if kind == "ddpm":
                 eng.set_schedule(bufs)
+                levels = bufs["noise_level"]
             else:
                 bufs["sqrt_alphas_cumprod_prev"] = self._sched_np["sqrt_alphas_cumprod_prev"]
-                eng.set_sampler_schedule(_samplers.sampler_tables(bufs, kind, steps, eta))
+                tables = _samplers.sampler_tables(bufs, kind, steps, eta)
+                eng.set_sampler_schedule(tables)
+                levels = tables["noise_level"]
+            self._levels_pushed = np.asarray(levels, dtype=np.float32)    # [S+1]: the state before step t-1 sits at [t]
             self._sched_pushed = sig
         return eng
 
@@ -252,7 +316,8 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def sample_batch(self, x_in, continous=False, noise: Optional[torch.Tensor] = None,
-                     seed: Optional[int] = None, image_offset: int = 0, max_chunk: Optional[int] = None):
+                     seed: Optional[int] = None, image_offset: int = 0, max_chunk: Optional[int] = None,
+                     init: Optional[torch.Tensor] = None, start=None, noised: Optional[bool] = None):
         """p_sample_loop for a whole batch (diffusion.py:189-215).
 
         x_in: conditioning [B,3,H,W] (conditional) or a shape tuple (unconditional, :193-201).
@@ -264,6 +329,12 @@ class GaussianDiffusion(nn.Module):
         reference's validation loop is 15 samples x N images (lib/trainer_temp.py:441-446), BASELINE configs[3] is 512
         images — run as equal chunks, one sr3_sample call each; Philox streams stay keyed by the GLOBAL image index
         (image_offset + row), so the result does not depend on the chunking. max_chunk lowers the limit (tests).
+
+        Warm start: init [B,C,H,W] is an explicit start image and overrides set_start; it is chunked,
+        and its last chunk padded, like x_in. start: a strength in (0, 1] (float) or s0 itself (int); None takes
+        set_start's, or S without one. noised (None: set_start's, or True): False takes the image as the state itself.
+        The call runs steps t = s0-1 .. 0; noise is then [s0,B,C,H,W] (slab 0 = the z of q_sample, slab k = the draw of
+        step t = s0-k) and there are len(schedule.frame_steps(S, s0)) frames.
         """
         eng = self._engine()
         if self.conditional:
@@ -275,14 +346,36 @@ class GaussianDiffusion(nn.Module):
             dev, x = next(self.denoise_fn.parameters()).device, None
         C = self.channels
         T = self.num_sampling_steps
+        # the start of this call: (image, s0, noised) or None (pure noise at the top: the library's sr3_sample)
+        s0, x_init = None, None
+        if init is not None:
+            x_init = init.to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(x_init.shape) != (B, C, H, W):
+                raise RuntimeError(f"init must be {(B, C, H, W)}, got {tuple(x_init.shape)}")
+            if start is None:
+                s0 = self.num_steps_run
+            elif isinstance(start, float):
+                s0 = self.start_steps(T, strength=start)
+            else:
+                s0 = self.start_steps(T, step=start)
+            if noised is None:
+                noised = self._start[3] if self._start is not None else True
+        elif start is not None or noised is not None:
+            raise ValueError("start / noised describe an explicit start image: pass init (or use set_start)")
+        elif self._start is not None:
+            if x is None or x.shape[1] != C:
+                raise RuntimeError("set_start(init='cond') needs a conditioning image with the channels of the result")
+            x_init, s0, noised = x, self.num_steps_run, self._start[3]
+        n_run = T if s0 is None else s0
+        n_frames = eng.num_frames(s0) if continous else 0
         out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
         frames = None
         if continous:
-            frames = torch.empty((eng.num_frames(), B, C, H, W), dtype=torch.float32, device=dev)
+            frames = torch.empty((n_frames, B, C, H, W), dtype=torch.float32, device=dev)
         if noise is not None:
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(noise.shape) != (T, B, C, H, W):
-                raise RuntimeError(f"noise must be {(T, B, C, H, W)}, got {tuple(noise.shape)}")
+            if tuple(noise.shape) != (n_run, B, C, H, W):
+                raise RuntimeError(f"noise must be {(n_run, B, C, H, W)}, got {tuple(noise.shape)}")
         if seed is None:
             seed = self._draw_seed()
         limit = eng.max_batch(H, W)
@@ -290,12 +383,19 @@ class GaussianDiffusion(nn.Module):
             limit = max(1, min(limit, int(max_chunk)))
         n_chunks, chunk = self.chunk_plan(B, limit)
         self.denoise_fn.arm_dropout(eng)            # (one dropout seed per call; the chunks pass their image offset)
+
+        def run(xc, b, oc, nc, off, fc, ic):
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            if ic is None:
+                eng.sample(ptr(xc), b, H, W, oc.data_ptr(), ptr(nc), seed, off, ptr(fc))
+            else:
+                eng.sample(ptr(xc), b, H, W, oc.data_ptr(), ptr(nc), seed, off, ptr(fc), init_ptr=ic.data_ptr(),
+                           start_step=s0, noised=bool(noised))
+
         if n_chunks == 1:
             self.denoise_fn.ready()
             self._arm_lr(eng, dev, H, W, image_offset)
-            eng.sample(x.data_ptr() if x is not None else None, B, H, W, out.data_ptr(),
-                       noise.data_ptr() if noise is not None else None, seed, image_offset,
-                       frames.data_ptr() if frames is not None else None)
+            run(x, B, out, noise, image_offset, frames, x_init)
             self.denoise_fn.finish()
             return (out, frames) if continous else out
 
@@ -311,14 +411,15 @@ class GaussianDiffusion(nn.Module):
             a, b = k * chunk, min(B, (k + 1) * chunk)
             xc = rows(x, a, b, 0) if x is not None else None
             nc = rows(noise, a, b, 1) if noise is not None else None
+            ic = None
+            if x_init is not None:
+                ic = xc if x_init is x else rows(x_init, a, b, 0)
             whole = b - a == chunk
             oc = out[a:b] if whole else torch.empty((chunk, C, H, W), dtype=torch.float32, device=dev)
             fc = torch.empty((frames.shape[0], chunk, C, H, W), dtype=torch.float32, device=dev) if continous else None
             self.denoise_fn.ready()
             self._arm_lr(eng, dev, H, W, image_offset + a)
-            eng.sample(xc.data_ptr() if xc is not None else None, chunk, H, W, oc.data_ptr(),
-                       nc.data_ptr() if nc is not None else None, seed, image_offset + a,
-                       fc.data_ptr() if fc is not None else None)
+            run(xc, chunk, oc, nc, image_offset + a, fc, ic)
             self.denoise_fn.finish()
             if not whole:
                 out[a:b] = oc[: b - a]
@@ -362,9 +463,48 @@ class GaussianDiffusion(nn.Module):
         return self.p_sample_loop(x_in, continous)
 
     @torch.no_grad()
-    def super_resolution_batch(self, x_in, noise=None, seed=None, image_offset=0, max_chunk=None):
-        """Throughput entry point: every image of the batch, [B,3,H,W] (any B: see sample_batch)."""
-        return self.sample_batch(x_in, False, noise, seed, image_offset, max_chunk)
+    def super_resolution_batch(self, x_in, noise=None, seed=None, image_offset=0, max_chunk=None, init=None, start=None,
+                               noised=None):
+        """Throughput entry point: every image of the batch, [B,3,H,W] (any B: see sample_batch, also for the warm
+        start's init / start / noised)."""
+        return self.sample_batch(x_in, False, noise, seed, image_offset, max_chunk, init=init, start=start, noised=noised)
+
+    @torch.no_grad()
+    def refine(self, x_in, img, strength, noise=None, seed=None, image_offset=0, max_chunk=None, noised=True):
+        """Refines an existing image — the result of a cheaper run or of a previous cascade stage — under the
+        conditioning x_in: img [B,C,H,W] is forward-diffused to the level of `strength` (a float in (0, 1], or s0 as an
+        int) and the last s0 steps run from there. super_resolution_batch(x_in, init=img, start=strength)."""
+        return self.super_resolution_batch(x_in, noise, seed, image_offset, max_chunk, init=img, start=strength, noised=noised)
+
+    @torch.no_grad()
+    def interpolate(self, x1, x2, t=None, lam=0.5, x_in=None, noise=None, noise2=None, seed=None):
+        """The `interpolate` member of the reference's ddpm variant (model/sr/ddpm_modules/diffusion.py:243-257): both
+        images are noised with independent noise (q_sample on the device), mixed as (1 - lam) * xt1 + lam * xt2, and the
+        last t steps of the loop, i = t-1 .. 0, run from the mix (an un-noised start with s0 = t). No new device code.
+
+        The level convention is this class's: the mix is the state before step t-1, so both images are noised to
+        sqrt_alphas_cumprod_prev[t] (entry t of the S-step level table under a few-step sampler) — the level step t-1
+        feeds the UNet. That is ONE index below the ddpm variant's, whose q_sample(t) noises with sqrt_alphas_cumprod[t] =
+        sqrt_alphas_cumprod_prev[t+1] before the same steps t-1 .. 0. t=None is S-1, the variant's default.
+
+        x_in: the conditioning ([B,Cc,H,W]) of the conditional model. noise: optional [t,B,C,H,W]; slab 0 noises x1 (and is
+        the unread slab 0 of the loop), slab k is the draw of step t-k. noise2: optional [B,C,H,W] noising x2. Without
+        them the two q_sample draws are torch.randn_like (as the reference's) and the loop draws from Philox under `seed`."""
+        self._engine()
+        S = self.num_sampling_steps
+        s0 = self.start_steps(S, step=S - 1 if t is None else t)
+        if self.conditional and x_in is None:
+            raise RuntimeError("the conditional model interpolates under a conditioning image: pass x_in")
+        x1 = x1.to(torch.float32).contiguous()
+        x2 = x2.to(device=x1.device, dtype=torch.float32).contiguous()
+        if x1.shape != x2.shape:
+            raise RuntimeError(f"x1 {tuple(x1.shape)} and x2 {tuple(x2.shape)} differ in shape")
+        level = torch.full((x1.shape[0],), float(self._levels_pushed[s0]), dtype=torch.float32)
+        xt1 = self.q_sample(x1, level, None if noise is None else noise[0])
+        xt2 = self.q_sample(x2, level, noise2)
+        mix = (1.0 - float(lam)) * xt1 + float(lam) * xt2
+        cond = x_in if self.conditional else tuple(x1.shape)
+        return self.sample_batch(cond, False, noise, seed, init=mix, start=s0, noised=False)
 
     @torch.no_grad()
     def p_sample(self, x, t, clip_denoised=True, condition_x=None, noise=None):

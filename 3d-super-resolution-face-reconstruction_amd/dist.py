@@ -78,11 +78,15 @@ def _local_shard(x_full: torch.Tensor):
     return shard_bounds(x_full.shape[0], world, rank)
 
 
-def sharded_super_resolution(sample_fn: Callable[[torch.Tensor, int], torch.Tensor],
-                             x_full: torch.Tensor, gather: bool = True) -> torch.Tensor:
+def sharded_super_resolution(sample_fn: Callable[..., torch.Tensor],
+                             x_full: torch.Tensor, gather: bool = True, init: torch.Tensor = None) -> torch.Tensor:
     """Runs `sample_fn(x_local, image_offset)` on this rank's slice of `x_full` [N,3,H,W] and
     all-gathers the results. `sample_fn` is `lambda x, off: netG.super_resolution_batch(x,
     seed=seed, image_offset=off)` in production.
+
+    init [N,C,H,W]: explicit start images of a warm start (GaussianDiffusion.sample_batch(init=...)), sharded with
+    x_full; sample_fn is then called as `sample_fn(x_local, image_offset, init_local)`. A start set with
+    GaussianDiffusion.set_start needs nothing here: every rank's call starts from its own slice of x_full.
 
     Stream ordering: the result must be ordered on torch's CURRENT stream of its device when `sample_fn` returns — the
     torch facade guarantees it (UNet.finish(): torch's stream waits on the device for the library's stream, an event,
@@ -90,7 +94,12 @@ def sharded_super_resolution(sample_fn: Callable[[torch.Tensor, int], torch.Tens
     a raw `Engine` calls `eng.stream_wait_for_engine(torch.cuda.current_stream().cuda_stream)` itself. No host
     synchronisation happens here."""
     a, b = _local_shard(x_full)
-    local = sample_fn(x_full[a:b], a)
+    if init is None:
+        local = sample_fn(x_full[a:b], a)
+    else:
+        if init.shape[0] != x_full.shape[0]:
+            raise ValueError(f"init holds {init.shape[0]} images, x_full {x_full.shape[0]}")
+        local = sample_fn(x_full[a:b], a, init[a:b])
     return all_gather_images(local, x_full.shape[0]) if gather else local
 
 
@@ -102,7 +111,8 @@ def sharded_p_sample_loop(netG, x_full: torch.Tensor, continous: bool = False, s
       continous=True  -> `ret_img` = cat([x_in, frame_0, ..., frame_9]) on dim 0, [(1 + n_frames) * N, 3, H, W], the
                          conditioning batch first (:203-204), then the whole batch after every recorded step (:209-211)
 
-    The sampler is netG's setting (GaussianDiffusion.set_sampler); with S steps there are len(frame_steps(S)) frames.
+    The sampler is netG's setting (GaussianDiffusion.set_sampler); with S steps there are len(frame_steps(S)) frames
+    (len(frame_steps(S, s0)) under a warm start, GaussianDiffusion.set_start, which every rank applies to its own slice).
     Two collectives at most: the final images (N/world x 3 x r x r per rank) and, if continous, the frames (n_frames
     times as much: 126 MB per rank for 256 images at 128x128 — still one call). `seed` must be the same on every rank
     (Philox streams are keyed by the global image index)."""

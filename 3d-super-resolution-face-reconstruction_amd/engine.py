@@ -315,8 +315,13 @@ class Engine:
                                                      1 if tables["uses_history"] else 0))
         self.T = S
 
-    def num_frames(self) -> int:
-        n = self.lib.sr3_num_frames(self.ctx)
+    def num_frames(self, start_step: Optional[int] = None) -> int:
+        """Frames one sampling call writes: after every step i with i % (1 | S // 10) == 0, over all S steps or, with
+        start_step, over the start_step steps of a warm start (sr3_num_frames_from)."""
+        if start_step is None:
+            n = self.lib.sr3_num_frames(self.ctx)
+        else:
+            n = self.lib.sr3_num_frames_from(self.ctx, int(start_step))
         if n < 0:
             _lib.check(n)
         return n
@@ -330,13 +335,30 @@ class Engine:
 
     def sample(self, cond_ptr: Optional[int], B: int, H: int, W: int, out_ptr: int,
                noise_ptr: Optional[int] = None, seed: int = 0, image_offset: int = 0,
-               frames_ptr: Optional[int] = None) -> None:
-        _lib.check(self.lib.sr3_sample(self.ctx, cond_ptr or None, B, H, W, noise_ptr or None,
-                                       seed, image_offset, out_ptr, frames_ptr or None))
+               frames_ptr: Optional[int] = None, init_ptr: Optional[int] = None, start_step: Optional[int] = None,
+               noised: bool = True) -> None:
+        """sr3_sample; with init_ptr ([B,C,H,W]) the warm start sr3_sample_from: the last start_step steps (None: all S)
+        from that image, noised to noise_level[start_step] first unless noised is False. noise_ptr is then
+        [start_step,B,C,H,W]."""
+        if init_ptr is None:
+            if start_step is not None:
+                raise ValueError("start_step needs init_ptr: the image the loop starts from")
+            _lib.check(self.lib.sr3_sample(self.ctx, cond_ptr or None, B, H, W, noise_ptr or None,
+                                           seed, image_offset, out_ptr, frames_ptr or None))
+            return
+        s0 = self.T if start_step is None else int(start_step)
+        _lib.check(self.lib.sr3_sample_from(self.ctx, cond_ptr or None, B, H, W, init_ptr, s0, 1 if noised else 0,
+                                            noise_ptr or None, seed, image_offset, out_ptr, frames_ptr or None))
 
     def sample_begin(self, cond_ptr, B, H, W, init_noise_ptr=None, seed=0, image_offset=0):
         _lib.check(self.lib.sr3_sample_begin(self.ctx, cond_ptr or None, B, H, W,
                                              init_noise_ptr or None, seed, image_offset))
+
+    def sample_begin_from(self, cond_ptr, B, H, W, init_ptr, start_step, noised=True, noise0_ptr=None, seed=0,
+                          image_offset=0):
+        """Step API of the warm start (sr3_sample_begin_from): the state before step start_step - 1, from init_ptr."""
+        _lib.check(self.lib.sr3_sample_begin_from(self.ctx, cond_ptr or None, B, H, W, init_ptr, int(start_step),
+                                                  1 if noised else 0, noise0_ptr or None, seed, image_offset))
 
     def sample_step(self, t: int, noise_ptr: Optional[int] = None):
         _lib.check(self.lib.sr3_sample_step(self.ctx, int(t), noise_ptr or None))
@@ -672,8 +694,10 @@ class Engine:
         self.unet_forward(dx.ptr, dn.ptr, B, H, W, out.ptr)
         return out.download((B, self.cfg.out_channel, H, W))
 
-    def sample_np(self, cond, noise=None, seed=0, image_offset=0, frames=False, shape=None):
-        """cond [B,Cc,H,W] (or None with shape=(B,C,H,W)); noise [T,B,C,H,W] or None (Philox)."""
+    def sample_np(self, cond, noise=None, seed=0, image_offset=0, frames=False, shape=None, init=None, start_step=None,
+                  noised=True):
+        """cond [B,Cc,H,W] (or None with shape=(B,C,H,W)); noise [T,B,C,H,W] or None (Philox). init [B,C,H,W] with
+        start_step: the warm start (Engine.sample); noise is then [start_step,B,C,H,W]."""
         C_ = self.cfg.out_channel
         if cond is not None:
             cond = _host_f32(cond)
@@ -683,11 +707,13 @@ class Engine:
             B, _, H, W = shape
             dc = None
         dn = self.to_device(noise) if noise is not None else None
+        di = self.to_device(init) if init is not None else None
         out = self.buffer(B * C_ * H * W)
-        nf = self.num_frames()
+        nf = self.num_frames(start_step if init is not None else None)
         fr = self.buffer(nf * B * C_ * H * W) if frames else None
         self.sample(dc.ptr if dc else None, B, H, W, out.ptr, dn.ptr if dn else None, seed,
-                    image_offset, fr.ptr if fr else None)
+                    image_offset, fr.ptr if fr else None, init_ptr=di.ptr if di else None, start_step=start_step,
+                    noised=noised)
         o = out.download((B, C_, H, W))
         if frames:
             return o, fr.download((nf, B, C_, H, W))

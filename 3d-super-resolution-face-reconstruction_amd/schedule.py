@@ -82,7 +82,11 @@ def sample_inter(T: int) -> int:
     return 1 | (int(T) // 10)
 
 
-def frame_steps(T: int):
-    """Steps i (descending) after which the reference appends a frame (diffusion.py:192,209-211)."""
+def frame_steps(T: int, start=None):
+    """Steps i (descending) after which the reference appends a frame (diffusion.py:192,209-211). start (s0): the steps
+    of a warm start, i < s0 of the same T-step loop (GaussianDiffusion.set_start)."""
     si = sample_inter(T)
-    return [i for i in reversed(range(int(T))) if i % si == 0]
+    n = int(T) if start is None else int(start)
+    if not 1 <= n <= int(T):
+        raise ValueError(f"start must lie in [1, {int(T)}], got {start}")
+    return [i for i in reversed(range(n)) if i % si == 0]

@@ -149,6 +149,8 @@ def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 
     N * samples may exceed what one library call takes (~250 images at 128x128): `sample_batch` runs equal chunks
     with the Philox streams keyed by the global row, so the scores do not depend on the chunking.
     The chains use netG's sampler setting (GaussianDiffusion.set_sampler: the reference's DDPM loop by default).
+    Under a warm start (GaussianDiffusion.set_start) every chain starts from its own row of `sr`, noised with its own
+    Philox stream, and runs netG.num_steps_run steps.
     Returns per (sample, image) PSNR / SSIM arrays and their means. The reference's running
     `avg / idx * sample` (lib/trainer_temp.py:445-446) multiplies by `sample` instead of dividing —
     the plain means are reported here.

@@ -206,6 +206,34 @@ int sr3_sample_begin(sr3_ctx *ctx, const float *cond_dev, int B, int H, int W,
                      const float *init_noise_dev, uint64_t seed, uint64_t image_offset);
 int sr3_sample_step(sr3_ctx *ctx, int t, const float *noise_slab_dev);
 int sr3_sample_end(sr3_ctx *ctx, float *out_dev);
+/* Warm start: the loop begins at an intermediate noise level from a given image and runs only the last
+ * start_step steps, t = start_step-1 .. 0 of the tables currently set (sr3_set_schedule's T or sr3_set_sampler_schedule's
+ * S; start_step in [1, S]). The state before step start_step-1 is at noise_level[start_step].
+ *   replaces: q_sample (model/sr/sr3_modules/diffusion.py:275-282) of init at that level, followed by the last
+ *   start_step iterations of p_sample_loop (:183-215).
+ *   init_dev   [B,C,H,W]; may be cond_dev itself when in_channel - out_channel == out_channel.
+ *   noised != 0: state = level * init + sqrt(1 - level^2) * z, level = noise_level[start_step], product, product and
+ *              sum each rounded to fp32 and the coefficient formed as float32 sqrt(1 - level*level): bit-equal to the
+ *              reference's q_sample expression on the same fp32 inputs. z is Philox draw 0 of (seed, image_offset + row)
+ *              or slab 0 of the injected noise. One pass writes cond, state, packed twin and range flag; needs
+ *              in_channel <= 8, like sr3_denoise_loss.
+ *   noised == 0: state = init, bit for bit (refining an image that already sits at that level: a frame of an earlier
+ *              call, an interpolation of two noised images).
+ *   noise      [start_step, B, C, H, W]: slab 0 is z (present but unread when noised == 0), slab k the draw of step
+ *              t = start_step - k. Philox draws keep draw = S - t, so a tail begun from a frame of a full run repeats it.
+ *   frames     after every step i < start_step with i % sample_inter == 0, sample_inter = 1 | (S/10);
+ *              sr3_num_frames_from(ctx, start_step) counts them.
+ * sr3_sample_from is sr3_sample's loop (the same range guard, its segments counted from the first step that runs);
+ * sr3_sample_begin_from is the step API's counterpart of sr3_sample_begin. With a sampler that keeps an x0 history
+ * (DPM-Solver++(2M)) the first step of a call begun through these two takes c1[t] + c3[t] (fp32 sum on the host) as its
+ * c1, which makes it the first-order step exactly; a call begun with sr3_sample_begin keeps applying c1[t] alone in its
+ * first step, as it always did (right only at t = S-1, where c3 is 0). */
+int sr3_sample_begin_from(sr3_ctx *ctx, const float *cond_dev, int B, int H, int W, const float *init_dev,
+                          int start_step, int noised, const float *noise0_dev, uint64_t seed, uint64_t image_offset);
+int sr3_sample_from(sr3_ctx *ctx, const float *cond_dev, int B, int H, int W, const float *init_dev, int start_step,
+                    int noised, const float *noise_dev, uint64_t seed, uint64_t image_offset, float *out_dev,
+                    float *frames_dev);
+int sr3_num_frames_from(sr3_ctx *ctx, int start_step);
 /* Range check of the split-f16 arithmetic (sr3_set_precision(ctx, 1)): the reference computes in
  * fp32 (diffusion.py:164-180, unet.py:235-265) and has no such limit, so a value that does not fit
  * the hi + lo fp16 operand format (|v| > 65504, or a NaN) must never pass silently. Every kernel that stores
