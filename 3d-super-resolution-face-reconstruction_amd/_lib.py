@@ -90,6 +90,7 @@ PROTOTYPES = {
     "sr3_gn_wino_passes": (_I, [_P]),
     "sr3_wino_gemm_out_launches": (_I, [_P]),
     "sr3_up2_wino_launches": (_I, [_P]),
+    "sr3_wino_fused_rows_launches": (_I, [_P]),
     "sr3_test_flag_address": (_P, [_P]),
     "sr3_last_warning": (C.c_char_p, []),
     "sr3_philox_normal": (_I, [_P, _U64, _U64, C.c_uint32, _I, _F]),
@@ -134,7 +135,7 @@ PROTOTYPES = {
 }
 
 # counters and opt-in entry points added to the C-ABI after its first A/B-able build (load)
-NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_wino_launches", "sr3_set_dropout", "sr3_set_dropout_masks", "sr3_dropout_layers",
+NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_wino_launches", "sr3_wino_fused_rows_launches", "sr3_set_dropout", "sr3_set_dropout_masks", "sr3_dropout_layers",
                   "sr3_dropout_mask_bytes", "sr3_op_dropout_mask", "sr3_load_weights_dev", "sr3_read_weight_layout",
                   "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual",
                   "sr3_sample_begin_from", "sr3_sample_from", "sr3_num_frames_from")

@@ -1827,6 +1827,32 @@ static int wino_gemm_out_bn(const ConvParams &p, int Cin) {
     return (blocks >= WINO_GEMM_OUT_MIN_BLOCKS && Cin <= WINO_GEMM_OUT_MAX_CIN) ? bn : 0;
 }
 
+// third form of the three-pass plan: the one-pass kernel with R = 2 | 4 tile rows per block (kernels_wino.hip,
+// wino_fused_kernel<R>), 0 = not taken. Preconditions: one input tensor (the engine's GroupNorm pass concatenates) and
+// the fragment-major weights; a width of 32 | 16 (R = 2 | 4: a block's 32 tiles are R whole tile rows) and whole blocks
+// (H % 2R == 0); whole 32-channel K-steps and 64-channel blocks; statistics slices that are a whole block or 2 | 4
+// equal parts of one; 32-bit offsets of the input DMA (bit 31 of a lane's offset switches an instruction off) and of
+// the weight loads (the four planes of a wave). Tuning: WINO_FUSED_ROWS_MIN_BLOCKS (per level).
+static int wino_fused_rows(const ConvParams &p, int Cin) {
+    static const bool off = env_int("SR3_NO_WINO_FUSED_ROWS", 0) != 0;       // product switches (read once)
+    static const bool force = env_int("SR3_WINO_FUSED_ROWS_FORCE", 0) != 0;
+    if (off || p.in1.p || !p.w_wino_f) return 0;
+    const int H = p.Hout, W = p.Wout, Cout = p.out.C;
+    const int R = W == 32 ? 2 : W == 16 ? 4 : 0;
+    if (R == 0 || (H % (2 * R)) || (Cin % 32) || (Cout % WINO_FUSED_BN)) return 0;
+    const int bpi = (H / 2) * (W / 2) / WINO_FUSED_TILES;                    // blocks per image
+    if (p.stats) {
+        if (p.stats_slices <= 0 || (p.stats_slices % bpi)) return 0;
+        const int spb = p.stats_slices / bpi;
+        if (spb != 1 && spb != 2 && spb != 4) return 0;
+    }
+    if (((uint64_t)(2 * R + 1) * (W + 2) + W + 1) * (uint64_t)Cin * 4 + 128 >= (1ull << 31) || (uint64_t)4 * Cout * Cin * 4 >= (1ull << 31)) return 0;
+    if (force) return R;
+    const int min_blocks = R == 2 ? WINO_FUSED_ROWS_MIN_BLOCKS : WINO_FUSED_ROWS_MIN_BLOCKS_16;
+    const uint64_t blocks = (uint64_t)p.B * bpi * (Cout / WINO_FUSED_BN);
+    return (min_blocks > 0 && blocks >= (uint64_t)min_blocks) ? R : 0;
+}
+
 // p as the kernels see it: an upsample conv becomes its four sub-pixel phases over the low-resolution pixels (one
 // launch: blockIdx.z picks (py, px)); splits / phase_slices / phase_part_stride are the plan's to fill
 static ConvParams phase_form(const ConvParams &p_in) {
@@ -1904,7 +1930,8 @@ static ConvPlan conv_plan_direct(const ConvParams &p_in) {
         plan.needs_wino_frag = wino == CK_WINO_ONE_PASS;       // (U and M never leave the CU)
         if (wino == CK_WINO_THREE_PASS) {
             plan.wino_ws_floats = (size_t)16 * p.B * (p.Hout / 2) * (p.Wout / 2) * (Cin + Cout);
-            plan.wino_gemm_out = wino_gemm_out_bn(p, Cin);
+            plan.wino_fused_rows = wino_fused_rows(p, Cin);
+            plan.wino_gemm_out = plan.wino_fused_rows ? 0 : wino_gemm_out_bn(p, Cin);
         }
         return plan;
     }

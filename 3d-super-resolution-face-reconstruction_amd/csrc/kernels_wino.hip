@@ -155,15 +155,28 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const ConvParams p, co
 // all, 2 waves per SIMD.
 // A 64-tile or 128-channel block doubles the accumulators (256: 1 wave per SIMD, nothing left for operands).
 // One input tensor only (conv_plan): the engine writes x || skip as one tensor in the GroupNorm apply pass.
-constexpr int WF_T = 32;                    // 2x2 output tiles per block (one strip of a tile row)
+// Tile rows (R, as wino_up2_kernel): the block's 32 tiles are R tile rows of TPR = 32 / R tiles, R = 1 | 2 | 4 for widths
+// 64k | 32 | 16 (R > 1: ConvPlan::wino_fused_rows, a form of the three-pass plan at the 32x32 and 16x16 levels). Lane li
+// holds tile (li / TPR, li % TPR), which is tile li of the block in the image's row-major tile order, so the K loop, the
+// fragment ring, the exchange and the statistics slices are R = 1's. A stage holds, per tile row, the 4 window rows of
+// 2 TPR + 2 padded columns (padded rows 2 (ty + tr) + 0..3: the two rows that neighbouring tile rows share are staged
+// twice): 264 | 272 | 288 pixel rows of 32 floats, 33 | 34 | 36 LDS-DMA instructions; two stages are at most 73728 B, so
+// two blocks still fit in a CU's LDS.
+constexpr int WF_T = 32;                    // 2x2 output tiles per block (R = 1: one strip of a tile row)
 constexpr int WF_BN = 64;                   // output channels per block
-constexpr int WF_WX = 2 * WF_T + 2;         // padded input columns of a strip's windows
-constexpr int WF_ROWS = 4 * WF_WX;          // pixel rows of 32 floats per LDS stage
-constexpr int WF_STAGE = WF_ROWS * 32;      // floats per stage
-constexpr int WF_DMA = WF_ROWS / 8;         // LDS-DMA instructions per stage (64 lanes x 16 B each)
-static_assert(WF_ROWS % 8 == 0, "whole DMA instructions per stage");
-constexpr size_t WF_LDS = (size_t)2 * WF_STAGE * sizeof(float);
-static_assert(WF_LDS >= (size_t)4 * 2 * WF_T * WF_BN * sizeof(float), "epilogue exchange fits in the stages");
+template <int R>
+struct WfGeom {
+    static_assert(R == 1 || R == 2 || R == 4, "tile rows per block");
+    static constexpr int TPR = WF_T / R;            // tiles per tile row of the block
+    static constexpr int WX = 2 * TPR + 2;          // padded input columns of a tile row's windows
+    static constexpr int ROWS = R * 4 * WX;         // pixel rows of 32 floats per LDS stage
+    static constexpr int STAGE = ROWS * 32;         // floats per stage
+    static constexpr int DMA = ROWS / 8;            // LDS-DMA instructions per stage (64 lanes x 16 B each)
+    static constexpr size_t LDS = (size_t)2 * STAGE * sizeof(float);
+    static_assert(ROWS % 8 == 0, "whole DMA instructions per stage");
+    static_assert(DMA > 32 && DMA <= 36, "eight instructions per wave and one more for the first DMA - 32 waves");
+    static_assert(LDS >= (size_t)4 * 2 * WF_T * WF_BN * sizeof(float), "epilogue exchange fits in the stages");
+};
 
 template <int N, class F>
 __device__ __forceinline__ void wf_static_for(F &&f) {
@@ -179,11 +192,14 @@ __device__ __forceinline__ void wf_dma16(const char *sbase, unsigned voff, float
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)lds, 16, (int)voff, 0, 0, 0);
 }
 
+template <int R>
 __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, int spb) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    using G = WfGeom<R>;
+    constexpr int TPR = G::TPR, WF_WX = G::WX, WF_STAGE = G::STAGE, WF_DMA = G::DMA;
     const int Cin = p.in0.C;                             // (one input tensor: conv_wino_taken)
     const int Cout = p.out.C, th = p.Hout >> 1, tw = p.Wout >> 1;
-    const int spr = tw / WF_T, spi = th * spr;           // strips per tile row / per image
+    const int spr = tw / TPR, spi = (th / R) * spr;      // blocks ("strips") per group of R tile rows / per image
     const int nbl = Cout / WF_BN;
     int bid = blockIdx.x;
     {   // XCD-aware remap (as conv_igemm_dma_f32): the channel blocks of one strip share an L2
@@ -194,7 +210,8 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     }
     const int nb = bid % nbl, strip = bid / nbl;
     const int n = strip / spi, si = strip - n * spi;
-    const int ty = si / spr, tx0 = (si - ty * spr) * WF_T;
+    const int tg = si / spr;
+    const int ty = tg * R, tx0 = (si - tg * spr) * TPR;  // the block's first tile row and column
     const int n0 = nb * WF_BN;
     const int a = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, li = lane & 31, h = lane >> 5;
@@ -202,15 +219,18 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     const size_t pix0 = ((size_t)n * p.in0.Hp() + 2 * ty) * Wp + 2 * tx0;     // window origin of the strip
     const char *src0 = reinterpret_cast<const char *>(p.in0.p + pix0 * Cin);
 
-    // LDS-DMA: wave a issues instructions i = a + 4m; lane -> pixel row 8i + (lane >> 3) (window row r, column x),
+    // LDS-DMA: wave a issues instructions i = a + 4m; lane -> pixel row 8i + (lane >> 3) of the stage (tile row, window
+    // row, column x: padded input row 2 * tile row + window row),
     // stored chunk lane & 7 (offsets recomputed per K-step: a few VALU operations, no registers held across the loop).
     // Nothing in the K loop issues a vector memory instruction under a branch that the compiler cannot count: the
     // s_waitcnt vmcnt(N) it inserts assume the fewest loads in flight, so a skipped DMA makes every later wait one
     // instruction stricter. A step with no next stage (on == false) sends its eight instructions past the end of the
-    // descriptor (no memory request; the free stage may receive zeros, which nobody reads); only instruction 32
-    // (m = 8, wave 0 alone) sits behind a wave-uniform branch, and it goes first.
+    // descriptor (no memory request; the free stage may receive zeros, which nobody reads); only the instructions
+    // from 32 on (m = 8; wave 0 alone at R = 1, waves 0 and 1 at R = 2, every wave at R = 4) sit behind a wave-uniform
+    // branch, one per wave, and they go first.
     // Bit 31 of the lane offset is that switch and the descriptor ends at 2^31 - 1 bytes, so a live offset must stay
-    // below it: (3 Wp + 65) * Cin * 4 + 128 < 2^31, i.e. Wp * Cin < 1.7e8 (the widest row of the UNet: 130 * 384 = 5e4).
+    // below it: (3 Wp + 65) * Cin * 4 + 128 < 2^31, i.e. Wp * Cin < 1.7e8 (the widest row of the UNet: 130 * 384 = 5e4);
+    // R > 1: ((2R + 1) Wp + 2 TPR + 1) * Cin * 4 + 128, with Wp = 2 TPR + 2 <= 34 (conv_plan checks it).
     auto issue = [&](int c0, int stage, bool on) {
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(src0 + (size_t)c0 * 4), 0, 0x7fffffff, 0x00020000);
@@ -220,14 +240,18 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
         auto one = [&](int i) {
             int q = 8 * i + (lane >> 3);
             asm volatile("" : "+v"(q));      // (kept in the loop: hoisted, the per-instruction offsets would be held in registers)
-            const int r = q / WF_WX, x = q - r * WF_WX;
+            const int wr = q / WF_WX, x = q - wr * WF_WX;
+            const int r = R == 1 ? wr : 2 * (wr >> 2) + (wr & 3);
             const unsigned voff =
                 ((unsigned)(r * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16)) | off;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst + i * 256), 16,
                                                      (int)voff, 0, 0, 0);
         };
-        static_assert(WF_DMA == 33, "eight instructions per wave and one more for wave 0");
-        if (a == 0 && on) one(32);
+        if constexpr (R == 1) {
+            if (a == 0 && on) one(32);
+        } else {
+            if (a < WF_DMA - 32 && on) one(32 + a);
+        }
         wf_static_for<8>([&](auto mc) { one(a + 4 * decltype(mc)::value); });
     };
 
@@ -251,13 +275,20 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     const int ra = a == 0 ? 0 : (a == 2 ? 2 : 1);
     const int rb = a == 0 ? 2 : (a == 1 ? 2 : (a == 2 ? 1 : 3));
     const float sg = a == 1 ? 1.f : -1.f;
+    const int ltr = li / TPR, ltc = li - ltr * TPR;       // the lane's tile in the block (R = 1: (0, li))
     int aoff[2][4];          // float offsets of the lane's window pixels (rows ra, rb; columns 0..3) in a stage
     int asw[4];              // swizzle of those columns
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
-        aoff[0][x] = (ra * WF_WX + 2 * li + x) * 32;
-        aoff[1][x] = (rb * WF_WX + 2 * li + x) * 32;
-        asw[x] = (li + (x >> 1)) & 7;
+        if constexpr (R == 1) {
+            aoff[0][x] = (ra * WF_WX + 2 * li + x) * 32;
+            aoff[1][x] = (rb * WF_WX + 2 * li + x) * 32;
+            asw[x] = (li + (x >> 1)) & 7;
+        } else {
+            aoff[0][x] = ((4 * ltr + ra) * WF_WX + 2 * ltc + x) * 32;
+            aoff[1][x] = ((4 * ltr + rb) * WF_WX + 2 * ltc + x) * 32;
+            asw[x] = (ltc + (x >> 1)) & 7;
+        }
     }
 
     f32x16 acc[4][2];
@@ -346,8 +377,8 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
-                const int tl = (threadIdx.x >> 4) + 16 * u;
-                rv[u][r][cc] = p.resid.p ? *reinterpret_cast<const f32x4 *>(p.resid.p + p.resid.pix(n, 2 * ty + r, 2 * (tx0 + tl) + cc) * Cout + c)
+                const int tl = (threadIdx.x >> 4) + 16 * u, tr = R == 1 ? 0 : tl / TPR, tc = tl - tr * TPR;
+                rv[u][r][cc] = p.resid.p ? *reinterpret_cast<const f32x4 *>(p.resid.p + p.resid.pix(n, 2 * (ty + tr) + r, 2 * (tx0 + tc) + cc) * Cout + c)
                                          : f32x4{0.f, 0.f, 0.f, 0.f};
             }
 
@@ -367,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     double s1[2][4], s2[2][4];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int tl = (threadIdx.x >> 4) + 16 * u;
+        const int tl = (threadIdx.x >> 4) + 16 * u, tr = R == 1 ? 0 : tl / TPR, tc = tl - tr * TPR;
         f32x4 t[4][2];
 #pragma unroll
         for (int aa = 0; aa < 4; ++aa)
@@ -385,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
-                const int oy = 2 * ty + r, ox = 2 * (tx0 + tl) + cc;
+                const int oy = 2 * (ty + tr) + r, ox = 2 * (tx0 + tc) + cc;
                 f32x4 add = bias;   // (the direct kernel's epilogue order: bias, residual, FeatureWiseAffine bias)
                 if (p.resid.p) add += rv[u][r][cc];
                 if (p.chan_bias) add += cb;
@@ -1000,17 +1031,24 @@ void launch_conv_wino(const ConvParams &p, const ConvPlan &plan, hipStream_t s) 
         launch_conv(r, s);
         o.resid = p.out;
     }
-    if (form == CK_WINO_ONE_PASS) {
-        const int spi = (H / 2) * (W / (2 * WF_T));
+    if (form == CK_WINO_ONE_PASS || plan.wino_fused_rows) {
+        // (the second case: a form of the three-pass plan; U and M, the whole workspace, stay unused)
+        const int spi = (H / 2) * (W / 2) / WF_T;          // blocks of 32 tiles per image
         const int spb = o.stats ? o.stats_slices / spi : 1;
         const unsigned blocks = (unsigned)((size_t)p.B * spi * (Cout / WF_BN));
         static bool attr_set = false;          // (more than 64 KiB of dynamic LDS)
         if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wino_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)WF_LDS);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wino_fused_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)WfGeom<1>::LDS);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wino_fused_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)WfGeom<2>::LDS);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wino_fused_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)WfGeom<4>::LDS);
             attr_set = true;
         }
-        hipLaunchKernelGGL(wino_fused_kernel, dim3(blocks), dim3(256), WF_LDS, s, o, spb);
+        if (form == CK_WINO_ONE_PASS) hipLaunchKernelGGL(wino_fused_kernel<1>, dim3(blocks), dim3(256), WfGeom<1>::LDS, s, o, spb);
+        else if (plan.wino_fused_rows == 2) hipLaunchKernelGGL(wino_fused_kernel<2>, dim3(blocks), dim3(256), WfGeom<2>::LDS, s, o, spb);
+        else hipLaunchKernelGGL(wino_fused_kernel<4>, dim3(blocks), dim3(256), WfGeom<4>::LDS, s, o, spb);
         return;
     }
 

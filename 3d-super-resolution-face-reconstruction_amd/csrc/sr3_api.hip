@@ -163,6 +163,7 @@ struct sr3_ctx {
     int fallback_calls = 0;             // calls finished by the f32 fallback since sr3_create
     int gn_wino_passes = 0;             // GroupNorm apply passes launched as launch_gn_wino_input / _fold_ since sr3_create
     int up2_wino_launches = 0;          // Upsample convs launched on wino_up2_kernel (ConvPlan::up2_wino) since sr3_create
+    int wino_fused_rows_launches = 0;   // three-pass Winograd convs launched on the one-pass kernel's tile-row form (ConvPlan::wino_fused_rows) since sr3_create
     int wino_gemm_out_launches = 0;     // three-pass Winograd convs launched in the one-kernel form (ConvPlan::wino_gemm_out) since sr3_create
     float *ckpt = nullptr;              // sr3_sample: NCHW copy of the sampler state at the last clean checkpoint
     size_t ckpt_floats = 0;
@@ -460,8 +461,9 @@ bool up2_wino_weights(const Param &p) {
 }
 
 // the one-pass Winograd kernel's fragment-major copy of a parameter's transformed weights, made from dev_wino on the
-// device the first time a workspace plan runs the conv at a one-pass shape (a parameter does not know its level; only
-// the 64x64 and 128x128 levels' convs get one). sr3_load_weight refreshes it with dev_wino.
+// device the first time a workspace plan runs the conv at a one-pass shape or in the tile-row form of the three-pass plan
+// (ConvPlan::wino_fused_rows) (a parameter does not know its level; only the convs of the 64x64 and 128x128 levels, and
+// of the 32x32 level from WINO_FUSED_ROWS_MIN_BLOCKS blocks on, get one). sr3_load_weight refreshes it with dev_wino.
 int ensure_wino_frag(sr3_ctx *c, Param &p) {
     if (p.dev_wino_f) return 0;
     const size_t n = (size_t)16 * p.cout * p.cin_pad;
@@ -616,7 +618,7 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
             slices = pl.stats_slices;
             if (!wino_weights(c->params[cr.w])) continue;
             max_wino = std::max<uint64_t>(max_wino, pl.wino_ws_floats);
-            if (pl.needs_wino_frag && ensure_wino_frag(c, c->params[cr.w])) frag_ok = false;
+            if ((pl.needs_wino_frag || pl.wino_fused_rows) && ensure_wino_frag(c, c->params[cr.w])) frag_ok = false;
         }
         return slices;
     };
@@ -877,18 +879,21 @@ bool gn_wino_off() {
 }
 
 // Does the GroupNorm apply pass in front of conv k write the conv's Winograd input transform (into c->wino_ws) instead
-// of k.in? Where the conv's plan is the three-pass form, in f32 with unsplit inputs and no raw side output wanted
+// of k.in? Where the conv's plan is the three-pass form (not its wino_fused_rows form, which reads the zero-bordered
+// activated tensor like the one-pass plan), in f32 with unsplit inputs and no raw side output wanted
 // (raw_wanted also stands for "the pass applies a Dropout mask": only launch_gn_apply* know one).
 bool gn_writes_u(const sr3_ctx *c, const ConvCall &k, bool raw_wanted, int in_split) {
     if (gn_wino_off() || c->split() || raw_wanted || in_split) return false;
-    return conv_plan(conv_params(c, k)).kernel == CK_WINO_THREE_PASS;
+    const ConvPlan pl = conv_plan(conv_params(c, k));
+    return pl.kernel == CK_WINO_THREE_PASS && !pl.wino_fused_rows;
 }
 
 // launch_conv on the context's stream; counts the convs whose plan takes the one-kernel form of the three-pass Winograd
-// plan, and the Upsample convs whose plan takes the sub-pixel Winograd form
+// plan or its tile-row form on the one-pass kernel, and the Upsample convs whose plan takes the sub-pixel Winograd form
 static void ctx_launch_conv(sr3_ctx *c, const ConvParams &p) {
     const ConvPlan pl = conv_plan(p);
     if (pl.wino_gemm_out) ++c->wino_gemm_out_launches;
+    if (pl.wino_fused_rows) ++c->wino_fused_rows_launches;
     if (pl.up2_wino) ++c->up2_wino_launches;
     launch_conv(p, c->stream);
 }
@@ -1631,7 +1636,7 @@ void fill_random(sr3_ctx *c, float *q, size_t n, int seed) {
 struct ScratchConv {
     ConvPlan plan;
     bool f8 = false;                // "f16f8" mode and the shape takes the F8C operand format
-    DevBuf act, w, wino_w, up_wino_w, wino_ws, part;
+    DevBuf act, w, wino_w, wino_wf, up_wino_w, wino_ws, part;
     ConvParams p;
 
     // weight_host: OIHW weights, nullptr: random values (timing). The activated input `act` (zero-bordered, Cin
@@ -1660,6 +1665,11 @@ struct ScratchConv {
             if (wino) {
                 std::vector<float> wv(n_wino);
                 make_wino_weights(packed.data(), Cout, Cin, wv.data());
+                if (plan.wino_fused_rows) {     // both layouts: the three-pass plan asks for w_wino, this form reads w_wino_f
+                    tmp.resize(n_wino);
+                    make_wino_weights_frag(wv.data(), Cout, Cin, tmp.data());
+                    if (wino_wf.upload(tmp.data(), n_wino)) return -1;
+                }
                 if (plan.needs_wino_frag) {
                     tmp.resize(n_wino);
                     make_wino_weights_frag(wv.data(), Cout, Cin, tmp.data());
@@ -1686,6 +1696,10 @@ struct ScratchConv {
             if (wino) {
                 if (wino_w.alloc(n_wino)) return -1;
                 fill_random(c, wino_w.p, n_wino, 10);       // (either layout: random values)
+                if (plan.wino_fused_rows) {
+                    if (wino_wf.alloc(n_wino)) return -1;
+                    fill_random(c, wino_wf.p, n_wino, 12);
+                }
             }
             if (plan.up2_wino) {
                 if (up_wino_w.alloc(up2_wino_floats(Cout, Cin))) return -1;
@@ -1704,6 +1718,7 @@ struct ScratchConv {
         p.prec = c->split() ? 1 : 0; p.f8 = f8 ? 1 : 0;
         p.w = w.p;
         (plan.needs_wino_frag ? p.w_wino_f : p.w_wino) = wino_w.p;
+        if (plan.wino_fused_rows) p.w_wino_f = wino_wf.p;
         p.w_up_wino = up_wino_w.p;
         p.wino_ws = wino_ws.p;
         p.part = part.p;
@@ -1712,7 +1727,9 @@ struct ScratchConv {
         return 0;
     }
     // the engine's rule (gn_writes_u of the UNet's convs): the apply pass in front of this conv writes U into wino_ws
-    bool gn_writes_u(const sr3_ctx *c) const { return !gn_wino_off() && !c->split() && plan.kernel == CK_WINO_THREE_PASS; }
+    bool gn_writes_u(const sr3_ctx *c) const {
+        return !gn_wino_off() && !c->split() && plan.kernel == CK_WINO_THREE_PASS && !plan.wino_fused_rows;
+    }
 };
 
 } // namespace
@@ -2624,6 +2641,7 @@ int sr3_fallback_calls(sr3_ctx *c) { return c ? c->fallback_calls : fail("null c
 int sr3_gn_wino_passes(sr3_ctx *c) { return c ? c->gn_wino_passes : fail("null context"); }
 int sr3_wino_gemm_out_launches(sr3_ctx *c) { return c ? c->wino_gemm_out_launches : fail("null context"); }
 int sr3_up2_wino_launches(sr3_ctx *c) { return c ? c->up2_wino_launches : fail("null context"); }
+int sr3_wino_fused_rows_launches(sr3_ctx *c) { return c ? c->wino_fused_rows_launches : fail("null context"); }
 int sr3_replay_calls(sr3_ctx *c) { return c ? c->replay_calls : fail("null context"); }
 void *sr3_test_flag_address(sr3_ctx *c) { return c ? c->d_ovf : nullptr; }
 const char *sr3_last_warning(void) { return g_warn.c_str(); }

@@ -8,7 +8,7 @@
 namespace sr3 {
 
 // ---- environment switches ---------------------------------------------------------------------------
-// Everything the library reads from the environment (INTEGRATION.md lists the same ten; each is read once per process
+// Everything the library reads from the environment (INTEGRATION.md lists the same twelve; each is read once per process
 // and then baked into captured graphs):
 //   SR3_NO_GRAPH=1          every kernel launched individually, no hipGraph replay (hosts that cannot capture)
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
@@ -25,6 +25,10 @@ namespace sr3 {
 //                           bits of the library before wino_up2_kernel)
 //   SR3_UP2_WINO_FORCE=1    the sub-pixel Winograd form wherever its preconditions hold, whatever the block count
 //                           (tests, per-shape timing)
+//   SR3_NO_WINO_FUSED_ROWS=1  three-pass Winograd convs never on the one-pass kernel's tile-row instantiations
+//                           (ConvPlan::wino_fused_rows): the launches of the library before them, same bits
+//   SR3_WINO_FUSED_ROWS_FORCE=1  that form wherever its preconditions hold, whatever the block count and Cin (tests,
+//                           per-shape timing)
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Activation tensor: NHWC fp32 with an optional 1-pixel zero border ("pad") stored around every
@@ -201,6 +205,12 @@ struct ConvPlan {
     // CK_WINO_THREE_PASS only: 0 = position GEMMs + wino_output_kernel; 64 | 128 = wino_gemm_out_kernel with that many
     // output channels per block (the M half of wino_ws then stays unused). Not part of the exported plan.
     int wino_gemm_out = 0;
+    // CK_WINO_THREE_PASS only: 0 = one of the forms above; 2 | 4 = the one-pass kernel with that many tile rows per block
+    // (wino_fused_kernel<R>, kernels_wino.hip), reading ConvParams::w_wino_f: neither U nor M exists, the whole of
+    // wino_ws stays unused and the conv reads its zero-bordered activated input, as the one-pass plan does. Wins over
+    // wino_gemm_out. Not part of the exported plan: kernel, stats_slices, wino_ws_floats and needs_wino_frag stay the
+    // three-pass plan's, and the statistics come in the same slices.
+    int wino_fused_rows = 0;
     // Upsample convs only: 0 = the four phase convs on `kernel`; 1 | 2 | 4 = wino_up2_kernel (kernels_wino.hip) with that
     // many tile rows per block, reading ConvParams::w_up_wino instead of w. Not part of the exported plan: kernel, phases,
     // split and stats_slices stay the direct plan's, and the statistics come in the same slices.
@@ -253,6 +263,14 @@ constexpr int WINO_FUSED_CIN = 64;
 constexpr int WINO_FUSED_MIN_BLOCKS = 1024;
 // the one-pass kernel's block: a strip of WINO_FUSED_TILES 2x2 tiles along a tile row x WINO_FUSED_BN output channels
 constexpr int WINO_FUSED_TILES = 32, WINO_FUSED_BN = 64;
+// The same kernel at the 32x32 and 16x16 levels (ConvPlan::wino_fused_rows, a form of the three-pass plan): a block's 32
+// tiles are R = 2 | 4 tile rows of 16 | 8 tiles, i.e. 32 consecutive tiles of the image. What it saves over the three
+// passes is U's trip through memory (four times the activated input, written by the GroupNorm pass and read by the
+// GEMMs) and, beyond WINO_GEMM_OUT_MAX_CIN, M's. Taken from WINO_FUSED_ROWS_MIN_BLOCKS blocks on at a width of 32 (the
+// smallest count timed: the B = 64 step's 32x32 convs; profiles/README.md finding 91); the 16x16 level did not pass
+// the 0.9 rule there and is reached only under SR3_WINO_FUSED_ROWS_FORCE=1 (0: never by default).
+constexpr int WINO_FUSED_ROWS_MIN_BLOCKS = 2048;
+constexpr int WINO_FUSED_ROWS_MIN_BLOCKS_16 = 0;
 // host helper: packed [9][Cout][CinPad] -> G g G^T as [16][Cout][CinPad] (fp64, rounded once to fp32)
 void make_wino_weights(const float *packed9, int Cout, int CinPad, float *dst);
 // host helper: [16][Cout][CinPad] (make_wino_weights) -> [16][CinPad/8][Cout][8]; launch_wino_frag: the same on the device

@@ -166,6 +166,11 @@ class Engine:
         SR3_NO_UP2_WINO=1 and outside the f32 mode."""
         return int(self.lib.sr3_up2_wino_launches(self.ctx))
 
+    def wino_fused_rows_launches(self) -> int:
+        """Three-pass Winograd convs this engine launched (or captured into a graph) on the one-pass kernel with 2 | 4 tile rows
+        per block (the 32x32 and 16x16 levels); 0 under SR3_NO_WINO_FUSED_ROWS=1 and outside the f32 mode."""
+        return int(self.lib.sr3_wino_fused_rows_launches(self.ctx))
+
     def replay_calls(self) -> int:
         """Calls finished after replaying work whose in-place split-K wait had given up (SR3_OK_REPLAYED)."""
         return int(self.lib.sr3_replay_calls(self.ctx))

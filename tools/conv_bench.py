@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark for the implicit-GEMM conv (development tool; run on the GPU box):
-    python tools/conv_bench.py [--iters N] [--set main|wino3|up2] [--only i,j,...] [--repeat R]
+    python tools/conv_bench.py [--iters N] [--set main|wino3|up2|rows] [--only i,j,...] [--repeat R]
 Prints ms and TFLOP/s per shape of the B=64, 128x128 SR3 step (--set wino3: every distinct shape of its three-pass
 Winograd convs, timed from U on: the position GEMMs + output transform, in whichever form the plan takes).
 --set up2: the four Upsample convs of the step, and the 64 -> 128 one at B = 4 and 16, in the form the plan takes, as
 four phase convs (SR3_NO_UP2_WINO=1) and as sub-pixel Winograd wherever its preconditions hold (SR3_UP2_WINO_FORCE=1):
-one child process per form (the switches are read once per process), the forms alternating, --repeat rounds."""
+one child process per form (the switches are read once per process), the forms alternating, --repeat rounds.
+--set rows: every distinct 3x3 shape of the step's 32x32 and 16x16 levels from the RAW input on (GroupNorm apply pass + conv),
+in the parent's three-pass forms (SR3_NO_WINO_FUSED_ROWS=1) and on the one-pass kernel with 2 | 4 tile rows per block
+(SR3_WINO_FUSED_ROWS_FORCE=1), alternating in the same way: the table that sets WINO_FUSED_ROWS_MIN_BLOCKS."""
 import argparse
 import importlib
 import os
@@ -50,14 +53,21 @@ UP2 = [(64, 8, 8, 512, 0, 512, 3, 1, 1, 0, 0, 0), (64, 16, 16, 512, 0, 512, 3, 1
        (64, 64, 64, 128, 0, 128, 3, 1, 1, 0, 0, 0), (4, 64, 64, 128, 0, 128, 3, 1, 1, 0, 0, 0), (16, 64, 64, 128, 0, 128, 3, 1, 1, 0, 0, 0)]
 UP2_FORMS = [("plan", {}), ("phase", {"SR3_NO_UP2_WINO": "1"}), ("wino", {"SR3_UP2_WINO_FORCE": "1"})]
 
+# the three-pass shapes of the 32x32 and 16x16 levels, in both forms of the plan
+ROWS = WINO3[:9]
+ROWS_FORMS = [("three-pass", {"SR3_NO_WINO_FUSED_ROWS": "1"}), ("rows", {"SR3_WINO_FUSED_ROWS_FORCE": "1"})]
+FORMS = {"up2": UP2_FORMS, "rows": ROWS_FORMS}
 
-def up2_parent(args):
+
+def forms_parent(args):
     """one child per form and round; nothing here touches the GPU"""
+    forms = FORMS[args.set]
+    switches = {k for _, env_add in forms for k in env_add}
     for rnd in range(args.repeat):
-        for form, env_add in UP2_FORMS:
-            env = {k: v for k, v in os.environ.items() if k not in ("SR3_NO_UP2_WINO", "SR3_UP2_WINO_FORCE")}
+        for form, env_add in forms:
+            env = {k: v for k, v in os.environ.items() if k not in switches}
             env.update(env_add)
-            cmd = [sys.executable, os.path.abspath(__file__), "--set", "up2", "--child", form, "--iters", str(args.iters),
+            cmd = [sys.executable, os.path.abspath(__file__), "--set", args.set, "--child", form, "--iters", str(args.iters),
                    "--precision", args.precision] + (["--only", args.only] if args.only else [])
             print(f"# round {rnd + 1}, form '{form}' {env_add}", flush=True)
             r = subprocess.run(cmd, env=env, timeout=600)
@@ -68,14 +78,14 @@ def up2_parent(args):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--set", type=str, default="main", choices=["main", "wino3", "up2"])
-    ap.add_argument("--repeat", type=int, default=2, help="--set up2: rounds over the three forms")
+    ap.add_argument("--set", type=str, default="main", choices=["main", "wino3", "up2", "rows"])
+    ap.add_argument("--repeat", type=int, default=2, help="--set up2 | rows: rounds over the forms")
     ap.add_argument("--child", type=str, default="", help=argparse.SUPPRESS)
     ap.add_argument("--only", type=str, default="", help="comma list of shape indices")
     ap.add_argument("--precision", type=str, default="f32", choices=["f32", "f16x3", "f16f8"])
     args = ap.parse_args()
-    if args.set == "up2" and not args.child:
-        up2_parent(args)
+    if args.set in FORMS and not args.child:
+        forms_parent(args)
         sys.exit(0)
     if os.environ.get("SR3_LIB"):       # timing experiments with an alternative build of the library
         importlib.import_module(PKG + "._lib").LIB_PATH = os.path.abspath(os.environ["SR3_LIB"])
@@ -83,10 +93,10 @@ if __name__ == "__main__":
     Engine = importlib.import_module(PKG + ".engine").Engine
     e = Engine(synth.tiny_unet_config(), 0)
     e.set_precision(args.precision)
-    table = WINO3 if args.set == "wino3" else UP2 if args.set == "up2" else MAIN
+    table = {"wino3": WINO3, "up2": UP2, "rows": ROWS}.get(args.set, MAIN)
     shapes = table if not args.only else [table[int(i)] for i in args.only.split(",")]
     for (B, H, W, C0, C1, Cout, ks, st, up, mode, rs, cb) in shapes:
-        n0 = e.up2_wino_launches() if args.set == "up2" else 0
+        n0 = e.up2_wino_launches() if args.set == "up2" else e.wino_fused_rows_launches() if args.set == "rows" else 0
         ms, ams = e.bench_conv(B, H, W, C0, C1, Cout, ks, st, up, mode, rs, cb, args.iters)
         Ho, Wo = (H * (2 if up else 1)) // st, (W * (2 if up else 1)) // st
         fl = 2.0 * B * Ho * Wo * Cout * ks * ks * (C0 + C1)
@@ -94,6 +104,9 @@ if __name__ == "__main__":
         if args.set == "up2":           # which kernel ran, and its rate on the MACs it executes (16 | 9 of the 36)
             wino = e.up2_wino_launches() > n0
             tail = f"[{args.child}: {'wino_up2_kernel' if wino else 'phase convs'}, {fl * (9 if wino else 16) / 36 / ms / 1e9:6.2f} TFLOP/s executed]"
+        if args.set == "rows":          # from the raw input: the apply pass (writes U | the activated tensor) + the conv
+            rows = e.wino_fused_rows_launches() > n0
+            tail = f"[{args.child}: {'wino_fused_kernel<R>' if rows else 'three-pass'}; apply pass {ams:.4f} ms, pass + conv {ms + ams:8.4f} ms]"
         print(f"B{B} {H}x{W} cin{C0}+{C1} cout{Cout} k{ks} s{st} u{up} mode{mode} res{rs} cb{cb}: "
               f"{ms:8.4f} ms  {fl / ms / 1e9:7.2f} TFLOP/s   {tail}", flush=True)
     e.close()
