@@ -108,6 +108,9 @@ PROTOTYPES = {
     "sr3_op_conv2d": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F]),
     "sr3_op_conv2d_stats": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F, _F, _U64,
                                 C.POINTER(_I)]),
+    "sr3_op_conv_in": (_I, [_P, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F, _U64, C.POINTER(_I), _P]),
+    "sr3_op_final_conv": (_I, [_P, _F, _I, _I, _I, _I, _F, _F, _F, _F, _I, _F, C.POINTER(_I)]),
+    "sr3_read_packed_state": (C.c_int64, [_P, _F, _P, C.POINTER(_I)]),
     "sr3_op_groupnorm_affine": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _F]),
     "sr3_op_groupnorm_apply": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F,
                                    C.POINTER(_I), C.POINTER(_I)]),
@@ -138,7 +141,8 @@ PROTOTYPES = {
 NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_wino_launches", "sr3_wino_fused_rows_launches", "sr3_set_dropout", "sr3_set_dropout_masks", "sr3_dropout_layers",
                   "sr3_dropout_mask_bytes", "sr3_op_dropout_mask", "sr3_load_weights_dev", "sr3_read_weight_layout",
                   "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual",
-                  "sr3_sample_begin_from", "sr3_sample_from", "sr3_num_frames_from")
+                  "sr3_sample_begin_from", "sr3_sample_from", "sr3_num_frames_from", "sr3_op_conv_in", "sr3_op_final_conv",
+                  "sr3_read_packed_state")
 
 _lib = None
 

@@ -235,9 +235,12 @@ __global__ __launch_bounds__(256) void final_conv_mfma_kernel(const TDesc x, con
             for (int e = 0; e < 8; ++e) {
                 float a = swish_fast(fmaf(f[e], sc[ks][e], sh[ks][e]));
                 a = ok ? a : 0.f;
-                ah[e] = (_Float16)a;
-                al[e] = (_Float16)(a - (float)ah[e]);
-                const unsigned eb = (unsigned)__builtin_bit_cast(unsigned short, ah[e]) & 0x7C00u;
+                // (the range bits are taken from a scalar: __builtin_bit_cast of the vector element ah[e] compiled to a
+                // read of element 0 for every e, so 7 of 8 channels went unchecked)
+                const _Float16 h = (_Float16)a;
+                ah[e] = h;
+                al[e] = (_Float16)(a - (float)h);
+                const unsigned eb = (unsigned)__builtin_bit_cast(unsigned short, h) & 0x7C00u;
                 range_bits = eb > range_bits ? eb : range_bits;
             }
 #pragma unroll
@@ -469,9 +472,10 @@ __global__ __launch_bounds__(256, 2) void conv_in_kernel(const _Float16 *__restr
                     h16x8 hi, lo;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        hi[e] = (_Float16)f[e];
-                        lo[e] = (_Float16)(f[e] - (float)hi[e]);
-                        const unsigned eb = (unsigned)__builtin_bit_cast(unsigned short, hi[e]) & 0x7C00u;
+                        const _Float16 h = (_Float16)f[e];      // (a scalar for the range bits: see final_conv_mfma_kernel)
+                        hi[e] = h;
+                        lo[e] = (_Float16)(f[e] - (float)h);
+                        const unsigned eb = (unsigned)__builtin_bit_cast(unsigned short, h) & 0x7C00u;
                         range_bits = eb > range_bits ? eb : range_bits;
                     }
                     const size_t pixel = out.pix(n, ty[mt], tx[mt] + px);

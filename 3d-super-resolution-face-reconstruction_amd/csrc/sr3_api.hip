@@ -2827,6 +2827,108 @@ int sr3_op_conv2d_stats(sr3_ctx *c, const float *in0_dev, int C0, const float *i
                           stats_capacity_doubles, slices_out);
 }
 
+// ---- the edge convs (kernels_edge.hip) on scratch buffers: the forward's launchers, weight packers and gates ----
+int sr3_op_conv_in(sr3_ctx *c, const float *state_nchw_dev, int B, int H, int W, int Cin, const float *weight_host,
+                   const float *bias_host, int Cout, float *out_dev, float *twin_dev, double *stats_dev,
+                   uint64_t stats_capacity_doubles, int *slices_out, void *packed_host) {
+    const char *what = "sr3_op_conv_in";
+    if (!c || !state_nchw_dev || !weight_host) return fail("%s: null argument", what);
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return fail("%s: bad shape", what);
+    // run_unet_body's gate (M_CONV_IN): c->split() && c->x0p, the latter decided by conv_in_supported
+    if (!c->split())
+        return fail("%s: the packed-state conv runs in the split-f16 arithmetics only (sr3_set_precision 1 | 2)", what);
+    if (!conv_in_supported(Cin, Cout, H, W))
+        return fail("%s: Cin=%d Cout=%d H=%d W=%d is no shape of the packed-state conv (Cin <= 8, Cout 32 | 64, W %% 16 == 0, "
+                    "H*W %% 256 == 0)", what, Cin, Cout, H, W);
+    const int slices = H * W / 256;
+    if (stats_dev) {
+        const uint64_t need = (uint64_t)B * slices * Cout * 2;
+        if (stats_capacity_doubles < need)
+            return fail("%s: the statistics take %llu doubles ([B][%d slices][Cout][2]), the buffer holds %llu", what,
+                        (unsigned long long)need, slices, (unsigned long long)stats_capacity_doubles);
+    }
+    if (slices_out) *slices_out = slices;
+    HIP_OK(hipSetDevice(c->device));
+    // the workspace's x0 / x0p (ensure_workspace): zero-bordered fp32 state of in_pad channels, packed twin + 16 floats of slack
+    TDesc x0; x0.C = round_up(Cin, 32); x0.H = H; x0.W = W; x0.pad = 1;
+    const size_t npix = (size_t)B * (H + 2) * (W + 2), xp_floats = npix * 8 + 16;
+    DevBuf state, xp, wci, bias;
+    if (state.alloc(x0.floats(B)) || xp.alloc(xp_floats)) return -1;
+    x0.p = state.p;
+    std::vector<float> wf(conv_in_weight_floats(Cout));
+    const float unscale = pack_conv_in_weight(weight_host, Cout, Cin, wf.data());
+    if (wci.upload(wf.data(), wf.size())) return -1;
+    if (bias_host && bias.upload(bias_host, (size_t)Cout)) return -1;
+    const TDesc out = unpadded(out_dev, Cout, H, W);
+    const TDesc twin = twin_dev ? unpadded(twin_dev, Cout, H, W) : TDesc();
+    const int rc = guarded_eval(c, what, "the conv", false, [&]() -> int {
+        HIP_OK(hipMemsetAsync(state.p, 0, x0.floats(B) * sizeof(float), c->stream));
+        HIP_OK(hipMemsetAsync(xp.p, 0, xp_floats * sizeof(float), c->stream));
+        if (stats_dev) HIP_OK(hipMemsetAsync(stats_dev, 0xFF, stats_capacity_doubles * sizeof(double), c->stream));
+        launch_nchw_to_nhwc(state_nchw_dev, B, Cin, x0, 0, c->stream);
+        launch_pack_state(x0, B, xp.p, c->stream, c->d_ovf);
+        launch_conv_in(xp.p, wci.p, bias.p, unscale, B, out, twin, out_dev ? 1 : 0, stats_dev, slices, c->d_ovf, c->stream);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("%s: launch failed", what);
+        return 0;
+    });
+    if (rc < 0) return rc;
+    if (packed_host) HIP_OK(hipMemcpy(packed_host, xp.p, npix * 16 * sizeof(_Float16), hipMemcpyDeviceToHost));
+    return rc;
+}
+
+int sr3_op_final_conv(sr3_ctx *c, const float *in_dev, int B, int H, int W, int C, const float *gn_scale_dev,
+                      const float *gn_shift_dev, const float *weight_host, const float *bias_host, int Cout,
+                      float *out_dev, int *form_out) {
+    const char *what = "sr3_op_final_conv";
+    if (!c || !in_dev || !gn_scale_dev || !gn_shift_dev || !weight_host || !bias_host || !out_dev) return fail("%s: null argument", what);
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0) return fail("%s: bad shape", what);
+    // run_unet_body's gates: the fused final conv is entered where the VALU weights exist (alloc_weights:
+    // final_conv_supported); in the split-f16 arithmetics it takes the MFMA form where those weights exist too
+    if (!final_conv_supported(C, Cout))
+        return fail("%s: C=%d Cout=%d is no shape of the fused final conv (C %% 64 == 0, Cout 1..4)", what, C, Cout);
+    const bool mfma = c->split() && final_conv_mfma_supported(C, Cout);
+    if (form_out) *form_out = mfma ? 2 : 1;
+    HIP_OK(hipSetDevice(c->device));
+    TDesc cur; cur.C = C; cur.H = H; cur.W = W; cur.pad = 1;      // a module output: zero-bordered (the kernels read the border, masked)
+    DevBuf act, w, bias;
+    if (act.alloc(cur.floats(B)) || bias.upload(bias_host, (size_t)Cout)) return -1;
+    cur.p = act.p;
+    float unscale = 1.f;
+    if (mfma) {
+        std::vector<float> wf(final_conv_mfma_weight_floats(C));
+        unscale = pack_final_conv_mfma_weight(weight_host, C, wf.data());
+        if (w.upload(wf.data(), wf.size())) return -1;
+    } else {
+        std::vector<float> wq((size_t)9 * C * 4);
+        pack_final_conv_weight(weight_host, Cout, C, wq.data());
+        if (w.upload(wq.data(), wq.size())) return -1;
+    }
+    const TDesc out = unpadded(out_dev, Cout, H, W);
+    return guarded_eval(c, what, "the conv", false, [&]() -> int {
+        HIP_OK(hipMemsetAsync(act.p, 0, cur.floats(B) * sizeof(float), c->stream));
+        launch_gn_apply(unpadded(const_cast<float *>(in_dev), C, H, W), kNone, B, nullptr, nullptr, 0, 0, cur, c->stream);
+        if (mfma) launch_final_conv_mfma(cur, B, gn_scale_dev, gn_shift_dev, w.p, unscale, bias.p, out, c->stream, c->d_ovf);
+        else launch_final_conv(cur, B, gn_scale_dev, gn_shift_dev, w.p, bias.p, out, c->stream);
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("%s: launch failed", what);
+        return 0;
+    });
+}
+
+int64_t sr3_read_packed_state(sr3_ctx *c, float *state_host, void *packed_host, int *dims3) {
+    if (!c) return fail("null context");
+    if (!c->arena || c->wB <= 0) return fail("sr3_read_packed_state: no call has set up a workspace yet");
+    if (dims3) { dims3[0] = c->wB; dims3[1] = c->wH; dims3[2] = c->wW; }
+    if (!c->x0p) return 0;
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const size_t npix = (size_t)c->wB * (c->wH + 2) * (c->wW + 2);
+    if (state_host)
+        HIP_OK(hipMemcpy2D(state_host, 8 * sizeof(float), c->x0.p, (size_t)c->x0.C * sizeof(float), 8 * sizeof(float), npix,
+                           hipMemcpyDeviceToHost));
+    if (packed_host) HIP_OK(hipMemcpy(packed_host, c->x0p, npix * 16 * sizeof(_Float16), hipMemcpyDeviceToHost));
+    return (int64_t)npix;
+}
+
 // Times `iters` launches of one conv shape on scratch buffers (random contents; f32 MFMA time does
 // not depend on the data). `mode` > 0 additionally times the GroupNorm apply pass that precedes the
 // conv in the engine (1 affine, 2 affine + Swish) and reports it in *apply_ms.

@@ -615,6 +615,73 @@ class Engine:
         assert got.value == slices, (got.value, slices)
         return o, st.download().view(np.float64).reshape(B, slices, Cout, 2)
 
+    def op_conv_in(self, state, weight, bias=None, want_out=True, want_twin=True, want_stats=True) -> dict:
+        """The UNet's first conv on the packed split-f16 state, as the split-f16 forward runs it (sr3_op_conv_in): state
+        [B, H, W, Cin <= 8] fp32, weight OIHW [Cout, Cin, 3, 3]. Returns a dict: out (float32 [B, H, W, Cout]), twin (the
+        uint16 halfs as stored, [B, H, W, Cout // 32, 2, 32]: per 32-channel chunk hi | lo), stats (float64
+        [B, H*W // 256, Cout, 2], NaN where no kernel wrote) — each None when switched off — and packed (uint16
+        [B, H+2, W+2, 2, 8]: per padded pixel 8 hi | 8 lo halfs)."""
+        state = _host_f32(state)
+        B, H, W, Cin = state.shape
+        weight = _host_f32(weight)
+        Cout = weight.shape[0]
+        assert weight.shape == (Cout, Cin, 3, 3), weight.shape
+        d = self.to_device(state.transpose(0, 3, 1, 2))
+        bh = _host_f32(bias) if bias is not None else None
+        n = B * H * W * Cout
+        out = self.buffer(n) if want_out else None
+        twin = self.buffer(n) if want_twin else None
+        slices = max(1, H * W // 256)
+        cap = B * slices * Cout * 2
+        st = self.buffer(cap * 2) if want_stats else None
+        packed = np.empty((B, H + 2, W + 2, 2, 8), dtype=np.uint16)
+        got = C.c_int(-1)
+        _lib.check(self.lib.sr3_op_conv_in(
+            self.ctx, d.ptr, B, H, W, Cin, weight.ctypes.data, bh.ctypes.data if bh is not None else None, Cout,
+            out.ptr if out else None, twin.ptr if twin else None, st.ptr if st else None, cap, C.byref(got),
+            packed.ctypes.data))
+        assert got.value == H * W // 256, got.value
+        return {"out": out.download((B, H, W, Cout)) if out else None,
+                "twin": twin.download().view(np.uint16).reshape(B, H, W, Cout // 32, 2, 32) if twin else None,
+                "stats": st.download().view(np.float64).reshape(B, got.value, Cout, 2) if st else None,
+                "packed": packed}
+
+    def op_final_conv(self, x, gn_scale, gn_shift, weight, bias, return_form=False):
+        """The UNet's last layer as the forward runs it (sr3_op_final_conv): swish(x * gn_scale + gn_shift), zero padding,
+        3x3 conv. x [B, H, W, C] fp32, gn_scale / gn_shift [B, C] (op_groupnorm_affine), weight OIHW [Cout, C, 3, 3]. The
+        fp32 VALU kernel runs in f32, the MFMA kernel in split-f16 where the forward takes it; return_form adds which
+        ("valu" | "mfma")."""
+        x = _host_f32(x)
+        B, H, W, Cc = x.shape
+        weight, bias = _host_f32(weight), _host_f32(bias)
+        Cout = weight.shape[0]
+        assert weight.shape == (Cout, Cc, 3, 3) and bias.shape == (Cout,), (weight.shape, bias.shape)
+        sc, sh = _host_f32(gn_scale), _host_f32(gn_shift)
+        assert sc.shape == (B, Cc) and sh.shape == (B, Cc), (sc.shape, sh.shape)
+        d, dsc, dsh = self.to_device(x), self.to_device(sc), self.to_device(sh)
+        out = self.buffer(B * H * W * Cout)
+        form = C.c_int(0)
+        _lib.check(self.lib.sr3_op_final_conv(self.ctx, d.ptr, B, H, W, Cc, dsc.ptr, dsh.ptr, weight.ctypes.data,
+                                              bias.ctypes.data, Cout, out.ptr, C.byref(form)))
+        o = out.download((B, H, W, Cout))
+        return (o, {1: "valu", 2: "mfma"}[form.value]) if return_form else o
+
+    def read_packed_state(self):
+        """(state, packed) of the current call's sampler state: state float32 [B, H+2, W+2, 8] (the 8 leading channels of
+        the zero-bordered fp32 state), packed uint16 [B, H+2, W+2, 2, 8] (8 hi | 8 lo halfs per pixel); None when the
+        call's shape keeps no packed state. For tests."""
+        dims = (C.c_int * 3)()
+        n = int(self.lib.sr3_read_packed_state(self.ctx, None, None, dims))
+        _lib.check(min(n, 0))
+        if n == 0:
+            return None
+        B, H, W = dims[0], dims[1], dims[2]
+        assert n == B * (H + 2) * (W + 2), (n, B, H, W)
+        state = np.empty((B, H + 2, W + 2, 8), dtype=np.float32)
+        packed = np.empty((B, H + 2, W + 2, 2, 8), dtype=np.uint16)
+        _lib.check(min(int(self.lib.sr3_read_packed_state(self.ctx, state.ctypes.data, packed.ctypes.data, dims)), 0))
+        return state, packed
+
     def op_groupnorm_apply(self, x0, gamma, beta, groups=32, x1=None, stats0=None, stats1=None, mode=2, fmt=0,
                            in_split=0, route=0, want_raw=False):
         """The engine's GroupNorm apply pass over x0 ‖ x1 (NHWC; float32, or the uint32 words of the split-f16 format for an

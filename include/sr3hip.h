@@ -373,6 +373,40 @@ int sr3_op_conv2d_stats(sr3_ctx *ctx, const float *in0_dev, int C0, const float 
                         const float *gn_shift_dev, int swish, const float *chan_bias_dev,
                         const float *resid_dev, float *out_dev, double *stats_dev,
                         uint64_t stats_capacity_doubles, int *slices_out);
+/* The UNet's first conv as the split-f16 forward runs it (unet.py:193-194 downs.0 on cat([cond, x_t]), diffusion.py:170):
+ * the zero-bordered fp32 state is built from state_nchw_dev [B, Cin, H, W] (Cin <= 8) as sr3_unet_forward builds it,
+ * packed by pack_state_kernel into [B][H+2][W+2] pixels of 16 halfs (channels 0..7 hi | channels 0..7 lo) and convolved by
+ * conv_in_kernel with weight_host (OIHW [Cout, Cin, 3, 3]) in the fragment layout the engine keeps (SR3_WL_CONV_IN),
+ * bias_host NULL or [Cout]. Every output is optional (NULL = the kernel runs with that option off):
+ *   out_dev     fp32 NHWC [B, H, W, Cout]
+ *   twin_dev    the split-f16 twin as stored, [B, H, W, Cout] 32-bit words (per 32-channel chunk 32 hi halfs | 32 lo halfs)
+ *   stats_dev   fp64 {sum, sum of squares} of the fp32 values per (image, 256-pixel block, channel),
+ *               [B][H*W/256][Cout][2]; the whole buffer (stats_capacity_doubles) is first filled with 0xFF bytes;
+ *               *slices_out = H*W/256
+ *   packed_host B*(H+2)*(W+2)*16 halfs (HOST memory): the packed state the conv read, borders included
+ * Fails where the forward would not take this path: an arithmetic that is not split-f16, a shape conv_in_supported
+ * refuses (Cin > 8, Cout not 32 | 64, W % 16, H*W % 256); nothing is launched then. A raised range flag (a state value or,
+ * with the twin, an output beyond the fp16 range, or not finite) is an error naming the range. (tests) */
+int sr3_op_conv_in(sr3_ctx *ctx, const float *state_nchw_dev, int B, int H, int W, int Cin, const float *weight_host,
+                   const float *bias_host, int Cout, float *out_dev, float *twin_dev, double *stats_dev,
+                   uint64_t stats_capacity_doubles, int *slices_out, void *packed_host);
+/* The UNet's last layer as the forward runs it (unet.py:229,263 final_conv = Block: GroupNorm -> Swish -> Conv3x3) behind
+ * the folded GroupNorm affine: in_dev fp32 NHWC [B, H, W, C], gn_scale_dev / gn_shift_dev [B, C]
+ * (sr3_op_groupnorm_affine), weight_host OIHW [Cout, C, 3, 3], bias_host [Cout], out_dev fp32 NHWC [B, H, W, Cout];
+ * zero padding applies to the activated tensor. The gates are the forward's: the fused final conv exists where
+ * final_conv_supported holds (C % 64 == 0, Cout 1..4), any other shape fails and launches nothing. Exact f32:
+ * final_conv_kernel (fp32 VALU), *form_out = 1. Split-f16: final_conv_mfma_kernel where final_conv_mfma_supported holds
+ * as well (Cout == 3, C 64 | 128), *form_out = 2, else the VALU kernel as in the forward. In the MFMA form a raised
+ * range flag (an activation beyond the fp16 range, or not finite) is an error naming the range. form_out is optional. (tests) */
+int sr3_op_final_conv(sr3_ctx *ctx, const float *in_dev, int B, int H, int W, int C, const float *gn_scale_dev,
+                      const float *gn_shift_dev, const float *weight_host, const float *bias_host, int Cout,
+                      float *out_dev, int *form_out);
+/* The sampler state of the current workspace (the last sr3_sample_begin / _step, sr3_unet_forward, sr3_denoise_loss ...
+ * call): state_host receives the 8 leading channels of the zero-bordered fp32 state, B*(H+2)*(W+2)*8 floats, packed_host
+ * its packed split-f16 copy, B*(H+2)*(W+2)*16 halfs (either may be NULL); dims3 (optional) = {B, H, W}. Returns the
+ * number of padded pixels B*(H+2)*(W+2); 0: this shape keeps no packed state (conv_in_supported), nothing is copied;
+ * < 0: error (no workspace yet). Synchronises the context's stream. (tests) */
+int64_t sr3_read_packed_state(sr3_ctx *ctx, float *state_host, void *packed_host, int *dims3);
 /* GroupNorm statistics folded with the affine: scale[b,c] = rstd*gamma[c],
  * shift[b,c] = beta[c] - mean*rstd*gamma[c]  (torch GroupNorm, eps 1e-5; unet.py:84,119). */
 int sr3_op_groupnorm_affine(sr3_ctx *ctx, const float *in0_dev, int C0, const float *in1_dev,
