@@ -130,6 +130,10 @@ PROTOTYPES = {
     "sr3_set_lr_consistency": (_I, [_P, _F, _I, _I, _I, _U64, C.c_float]),
     "sr3_op_lr_project": (_I, [_P, _F, _I, _I, _I, _I, _F, _I, _I, _I, _U64, C.c_float, _I]),
     "sr3_lr_residual": (_I, [_P, _F, _I, _I, _I, _I, _F, _I, _I, _I, _U64, _P, _P]),
+    "sr3_set_dynamic_threshold": (_I, [_P, C.c_float, C.c_float]),
+    "sr3_op_abs_quantile": (_I, [_P, _F, _I, C.c_int64, C.c_float, C.c_float, _F, _F, _F]),
+    "sr3_op_dynamic_threshold": (_I, [_P, _F, _I, C.c_int64, C.c_float, C.c_float, _F]),
+    "sr3_dynamic_threshold_launches": (_I, [_P]),
     "sr3_dev_malloc": (_I, [_P, _U64, C.POINTER(_P)]),
     "sr3_dev_free": (_I, [_P, _P]),
     "sr3_memcpy_h2d": (_I, [_P, _P, _P, _U64]),
@@ -142,7 +146,8 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_dropout_mask_bytes", "sr3_op_dropout_mask", "sr3_load_weights_dev", "sr3_read_weight_layout",
                   "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual",
                   "sr3_sample_begin_from", "sr3_sample_from", "sr3_num_frames_from", "sr3_op_conv_in", "sr3_op_final_conv",
-                  "sr3_read_packed_state")
+                  "sr3_read_packed_state", "sr3_set_dynamic_threshold", "sr3_op_abs_quantile", "sr3_op_dynamic_threshold",
+                  "sr3_dynamic_threshold_launches")
 
 _lib = None
 

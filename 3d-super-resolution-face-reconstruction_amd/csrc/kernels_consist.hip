@@ -263,7 +263,9 @@ void launch_lr_residual(const float *img, int B, int C, const LrOps &o, const Lr
 // ---- the DDPM update in two halves around the projection --------------------------------------------------------------
 namespace {
 
-// x0 = clamp(a*x - b*eps, -1, 1), the head of ddpm_update_kernel in its operation order, into x0hat NCHW [B][C][H][W]
+// x0 = clamp(a*x - b*eps, -1, 1), the head of ddpm_update_kernel in its operation order, into x0hat NCHW [B][C][H][W].
+// CLAMP false: the prediction as it is, for the dynamic threshold that takes the clamp's place (kernels_threshold.hip)
+template <bool CLAMP>
 __global__ void x0_predict_kernel(const UpdateParams u, float *__restrict__ x0hat, size_t total) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // over B*C*HW, NCHW order
     if (i >= total) return;
@@ -277,7 +279,7 @@ __global__ void x0_predict_kernel(const UpdateParams u, float *__restrict__ x0ha
     const float x = u.state.p[u.state.pix(n, y, xx) * u.state.C + u.xoff + c];
     const float e = u.eps.p[u.eps.pix(n, y, xx) * u.eps.C + c];
     const float x0 = __fsub_rn(__fmul_rn(sa.a, x), __fmul_rn(sa.b, e));
-    x0hat[i] = fminf(fmaxf(x0, -1.0f), 1.0f);
+    x0hat[i] = CLAMP ? fminf(fmaxf(x0, -1.0f), 1.0f) : x0;
 }
 
 // the tail of ddpm_update_kernel, statement for statement, with x0 read from x0hat (the projected prediction: nothing
@@ -319,9 +321,10 @@ __global__ void update_from_x0_kernel(const UpdateParams u, const float *__restr
 
 } // namespace
 
-void launch_x0_predict(const UpdateParams &p, float *x0hat, int B, hipStream_t s) {
+void launch_x0_predict(const UpdateParams &p, float *x0hat, int B, hipStream_t s, bool clamp) {
     const size_t total = (size_t)B * p.C * p.state.H * p.state.W;
-    hipLaunchKernelGGL(x0_predict_kernel, dim3(nblk(total)), dim3(256), 0, s, p, x0hat, total);
+    if (clamp) hipLaunchKernelGGL(x0_predict_kernel<true>, dim3(nblk(total)), dim3(256), 0, s, p, x0hat, total);
+    else hipLaunchKernelGGL(x0_predict_kernel<false>, dim3(nblk(total)), dim3(256), 0, s, p, x0hat, total);
 }
 void launch_update_from_x0(const UpdateParams &p, const float *x0hat, int B, hipStream_t s) {
     const size_t total = (size_t)B * p.C * p.state.H * p.state.W;

@@ -145,8 +145,9 @@ struct sr3_ctx {
     bool split() const { return mode != A_F32; }        // split-f16 operands (f16x3 or f16f8)
     // "f16f8": the two correction products of eligible convs run on the fp8 matrix path (ConvParams::f8, conv_f8_supported)
     bool f8() const { return mode == A_F16F8; }
-    // which captured step graph: one per arithmetic, and per arithmetic one with the consistency projection in the step
-    int graph_slot() const { return (int)mode + (lr_on() ? 3 : 0); }
+    // which captured step graph: one per arithmetic, and per arithmetic one per form of the update (plain | with the
+    // consistency projection | with the dynamic threshold | with both)
+    int graph_slot() const { return (int)mode + (lr_on() ? 3 : 0) + (dyn_on() ? 6 : 0); }
     // split format of an activated conv input (launch_gn_apply's `split`): 0 fp32, 1 split-f16, 2 F8C when the consumer
     // conv takes the fp8 operands (f8_conv() said so)
     int act_format(bool f8_operand) const { return split() ? (f8_operand ? 2 : 1) : 0; }
@@ -211,6 +212,20 @@ struct sr3_ctx {
     bool lr_cur_lds = false;
     bool lr_on() const { return lr.lr != nullptr && lr.strength != 0.f; }
 
+    // Dynamic thresholding of the x0 prediction (sr3_set_dynamic_threshold). Off by default (dyn_ratio 0):
+    // a step then launches exactly the kernels it always did. dyn_plan: rank, weight and blocks of the current sampling
+    // call's n = out_channel * H * W (sr3_sample_begin), launch arguments of the captured steps 6..11 like dyn_max.
+    float dyn_ratio = 0.f, dyn_max = INFINITY;
+    ThrPlan dyn_plan;
+    int64_t dyn_n = 0;
+    float *dyn_s = nullptr;             // [dyn_rows]: s of every image of the step
+    unsigned *dyn_bins = nullptr;       // [dyn_rows][THR_BINS_PER_IMAGE]: the select's counts
+    int dyn_rows = 0;
+    int dyn_steps = 0;                  // sampler steps issued in the thresholded form since sr3_create
+    bool dyn_on() const { return dyn_ratio > 0.f; }
+    unsigned *thr_op_bins = nullptr;    // sr3_op_abs_quantile / sr3_op_dynamic_threshold: counts, then thr_op_rows floats of s
+    int thr_op_rows = 0;
+
     // workspace for one (B, H, W)
     int wB = 0, wH = 0, wW = 0;
     char *arena = nullptr;
@@ -250,9 +265,9 @@ struct sr3_ctx {
     StepArgs *h_ring = nullptr, *d_step = nullptr;
     uint64_t step_count = 0;
     // one p_sample step captured as a hipGraph (per precision); rebuilt when the workspace changes
-    static constexpr int kGraphs = 6;   // per arithmetic (f32, f16x3, f16f8), without | with the consistency projection
-    hipGraphExec_t step_graph[kGraphs] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int graph_warm[kGraphs] = {0, 0, 0, 0, 0, 0};
+    static constexpr int kGraphs = 12;  // graph_slot(): per arithmetic (f32, f16x3, f16f8) and form of the update
+    hipGraphExec_t step_graph[kGraphs] = {};
+    int graph_warm[kGraphs] = {};
     bool no_graph = false;
 
     // profiling
@@ -1445,8 +1460,17 @@ int push_drop_args(sr3_ctx *c, const char *what, uint64_t image_offset) {
 }
 
 // ---- low-resolution consistency: operators and buffers ---------------------------------------------------------------
+// the captured steps that hold x0hat: every form but the plain one (slots 3..)
 void drop_lr_graphs(sr3_ctx *c) {
     for (int i = 3; i < sr3_ctx::kGraphs; ++i) {
+        if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
+        c->step_graph[i] = nullptr;
+        c->graph_warm[i] = 0;
+    }
+}
+// the captured steps with the dynamic threshold in them (slots 6..)
+void drop_dyn_graphs(sr3_ctx *c) {
+    for (int i = 6; i < sr3_ctx::kGraphs; ++i) {
         if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
         c->step_graph[i] = nullptr;
         c->graph_warm[i] = 0;
@@ -1506,6 +1530,19 @@ int ensure_lr_scratch(sr3_ctx *c, size_t floats) {
     return 0;
 }
 
+// the x0 prediction between the halves of the update (projection and dynamic threshold share it); a new allocation
+// invalidates the captured steps that hold it
+int ensure_x0hat(sr3_ctx *c, size_t need) {
+    if (c->x0hat_floats >= need) return 0;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (c->x0hat) HIP_OK(hipFree(c->x0hat));
+    c->x0hat = nullptr; c->x0hat_floats = 0;
+    drop_lr_graphs(c);
+    HIP_OK(hipMalloc(&c->x0hat, need * sizeof(float)));
+    c->x0hat_floats = need;
+    return 0;
+}
+
 // sr3_sample_begin with the feature on: operators, form, x0 buffer and scratch of this call's shape
 int prepare_lr_step(sr3_ctx *c, int B, int H, int W) {
     const int C = c->cfg.out_channel;
@@ -1515,16 +1552,30 @@ int prepare_lr_step(sr3_ctx *c, int B, int H, int W) {
     const bool lds = lr_lds_fits(o);
     if (o.Av != c->lr_cur.Av || lds != c->lr_cur_lds) drop_lr_graphs(c);
     c->lr_cur = o; c->lr_cur_lds = lds;
-    const size_t need = (size_t)B * C * H * W;
-    if (c->x0hat_floats < need) {
-        HIP_OK(hipStreamSynchronize(c->stream));
-        if (c->x0hat) HIP_OK(hipFree(c->x0hat));
-        c->x0hat = nullptr; c->x0hat_floats = 0;
-        drop_lr_graphs(c);
-        HIP_OK(hipMalloc(&c->x0hat, need * sizeof(float)));
-        c->x0hat_floats = need;
-    }
+    if (ensure_x0hat(c, (size_t)B * C * H * W)) return -1;
     return lds ? 0 : ensure_lr_scratch(c, lr_scratch_floats(B * C, o));
+}
+
+// sr3_sample_begin with the dynamic threshold on: x0 buffer, s and the select's counts for B images of n values; a new
+// rank, block count or buffer invalidates the captured steps that hold it
+int prepare_dyn_step(sr3_ctx *c, int B, int H, int W) {
+    const int64_t n = (int64_t)c->cfg.out_channel * H * W;
+    const ThrPlan p = threshold_plan(c->dyn_ratio, n);
+    if (n != c->dyn_n || p.k != c->dyn_plan.k || p.k2 != c->dyn_plan.k2 || p.frac != c->dyn_plan.frac || p.blocks != c->dyn_plan.blocks)
+        drop_dyn_graphs(c);
+    c->dyn_n = n; c->dyn_plan = p;
+    if (ensure_x0hat(c, (size_t)B * n)) return -1;
+    if (c->dyn_rows < B) {
+        HIP_OK(hipStreamSynchronize(c->stream));
+        if (c->dyn_s) HIP_OK(hipFree(c->dyn_s));
+        if (c->dyn_bins) HIP_OK(hipFree(c->dyn_bins));
+        c->dyn_s = nullptr; c->dyn_bins = nullptr; c->dyn_rows = 0;
+        drop_dyn_graphs(c);
+        HIP_OK(hipMalloc(&c->dyn_s, (size_t)B * sizeof(float)));
+        HIP_OK(hipMalloc(&c->dyn_bins, threshold_bins_bytes(B)));
+        c->dyn_rows = B;
+    }
+    return 0;
 }
 
 // the launches of one p_sample step (embedding, UNet body, DDPM update); every per-step value is
@@ -1543,7 +1594,15 @@ void enqueue_step(sr3_ctx *c) {
     u.ovf = c->split() ? c->d_ovf : nullptr;    // (the packed copy is only read in split-f16 mode)
     u.hist = c->xhist;                          // constant per workspace: the captured graph stays valid
     c->pbegin(F_MISC);
-    if (c->lr_on()) {
+    if (c->dyn_on()) {
+        // unclamped x0 prediction | per-image s and clamp(x0, -s, s) / s | [projection] | the rest
+        launch_x0_predict(u, c->x0hat, B, c->stream, false);
+        launch_abs_quantile(c->x0hat, B, c->dyn_n, c->dyn_plan, c->dyn_max, c->dyn_bins, nullptr, nullptr, c->dyn_s, c->stream);
+        launch_threshold_apply(c->x0hat, B, c->dyn_n, c->dyn_s, c->stream);
+        if (c->lr_on())
+            launch_lr_project(c->x0hat, B * u.C, u.C, c->lr_cur, c->lr, c->d_lr, c->lr_cur_lds, c->lr_scratch, c->stream);
+        launch_update_from_x0(u, c->x0hat, B, c->stream);
+    } else if (c->lr_on()) {
         // x0 prediction | projection onto {x : A x = y} | the rest of the update
         launch_x0_predict(u, c->x0hat, B, c->stream);
         launch_lr_project(c->x0hat, B * u.C, u.C, c->lr_cur, c->lr, c->d_lr, c->lr_cur_lds, c->lr_scratch, c->stream);
@@ -1562,6 +1621,12 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     if (c->lr_on() && (c->lr_cur.lh != c->lr_lh || c->lr_cur.lw != c->lr_lw || c->lr_cur.H != c->wH || c->lr_cur.W != c->wW ||
                        c->x0hat_floats < (size_t)c->wB * c->cfg.out_channel * c->wH * c->wW))
         return fail("p_sample step: low-resolution consistency was turned on or resized after sr3_sample_begin; set it before");
+    if (c->dyn_on()) {
+        const int64_t n = (int64_t)c->cfg.out_channel * c->wH * c->wW;
+        if (c->dyn_n != n || c->dyn_rows < c->wB || c->x0hat_floats < (size_t)c->wB * n || c->dyn_plan.k != threshold_plan(c->dyn_ratio, n).k)
+            return fail("p_sample step: the dynamic threshold was turned on or changed after sr3_sample_begin; set it before");
+        ++c->dyn_steps;
+    }
     StepArgs *slot = next_step_slot(c);
     if (!slot) return -1;
     StepArgs &sa = *slot;
@@ -1817,6 +1882,9 @@ void sr3_destroy(sr3_ctx *c) {
     if (c->h_lr) (void)hipHostFree(c->h_lr);
     if (c->x0hat) (void)hipFree(c->x0hat);
     if (c->lr_scratch) (void)hipFree(c->lr_scratch);
+    if (c->dyn_s) (void)hipFree(c->dyn_s);
+    if (c->dyn_bins) (void)hipFree(c->dyn_bins);
+    if (c->thr_op_bins) (void)hipFree(c->thr_op_bins);
     for (auto &r : c->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
@@ -2411,6 +2479,7 @@ int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, con
     c->hist_valid = false;
     c->fold_first = false;
     if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
+    if (c->dyn_on() && prepare_dyn_step(c, B, H, W)) return -1;
     if (range_reset(c)) return -1;
     c->pbegin(F_MISC);
     if (cond_dev) launch_nchw_to_nhwc(cond_dev, B, nc, c->x0, 0, c->stream);
@@ -2460,6 +2529,7 @@ int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W
     c->hist_valid = false;
     c->fold_first = true;
     if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
+    if (c->dyn_on() && prepare_dyn_step(c, B, H, W)) return -1;
     if (range_reset(c)) return -1;
     c->pbegin(F_MISC);
     if (noised) {
@@ -2641,6 +2711,7 @@ int sr3_fallback_calls(sr3_ctx *c) { return c ? c->fallback_calls : fail("null c
 int sr3_gn_wino_passes(sr3_ctx *c) { return c ? c->gn_wino_passes : fail("null context"); }
 int sr3_wino_gemm_out_launches(sr3_ctx *c) { return c ? c->wino_gemm_out_launches : fail("null context"); }
 int sr3_up2_wino_launches(sr3_ctx *c) { return c ? c->up2_wino_launches : fail("null context"); }
+int sr3_dynamic_threshold_launches(sr3_ctx *c) { return c ? c->dyn_steps : fail("null context"); }
 int sr3_wino_fused_rows_launches(sr3_ctx *c) { return c ? c->wino_fused_rows_launches : fail("null context"); }
 int sr3_replay_calls(sr3_ctx *c) { return c ? c->replay_calls : fail("null context"); }
 void *sr3_test_flag_address(sr3_ctx *c) { return c ? c->d_ovf : nullptr; }
@@ -3292,6 +3363,71 @@ int sr3_lr_residual(sr3_ctx *c, const float *img_dev, int B, int C, int H, int W
     a.lr = lr_dev; a.row_offset = row_offset; a.N = N; a.strength = 0.f;
     c->pbegin(F_MISC);
     launch_lr_residual(img_dev, B, C, o, a, c->lr_scratch, sumsq_dev, maxabs_dev, c->stream);
+    c->pend();
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- dynamic thresholding -----------------------------------------------------------------------------
+namespace {
+int check_threshold_args(const char *what, float ratio, float max_value) {
+    if (!(ratio <= 1.0f)) return fail("%s: ratio must lie in (0, 1] (or <= 0 for off), got %g", what, (double)ratio);
+    if (!(max_value >= 1.0f)) return fail("%s: max_value must be >= 1 (+inf: no bound), got %g", what, (double)max_value);
+    return 0;
+}
+
+// scratch of the two ops, apart from the sampler's (no captured step holds it): the select's counts, then B floats of s
+int ensure_thr_op_scratch(sr3_ctx *c, int B) {
+    if (c->thr_op_rows >= B) return 0;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (c->thr_op_bins) HIP_OK(hipFree(c->thr_op_bins));
+    c->thr_op_bins = nullptr; c->thr_op_rows = 0;
+    HIP_OK(hipMalloc(&c->thr_op_bins, threshold_bins_bytes(B) + (size_t)B * sizeof(float)));
+    c->thr_op_rows = B;
+    return 0;
+}
+
+int check_threshold_op(sr3_ctx *c, const char *what, const void *x, int B, int64_t n, float ratio, float max_value) {
+    if (!c || !x) return fail("%s: null argument", what);
+    if (B <= 0 || B > 65535 || n <= 0 || n > (int64_t)INT_MAX) return fail("%s: needs 0 < B <= 65535 and 0 < n < 2^31 (got %d, %lld)", what, B, (long long)n);
+    if (!(ratio > 0.0f)) return fail("%s: ratio must lie in (0, 1], got %g", what, (double)ratio);
+    return check_threshold_args(what, ratio, max_value);
+}
+}
+
+int sr3_set_dynamic_threshold(sr3_ctx *c, float ratio, float max_value) {
+    if (!c) return fail("null context");
+    if (!(ratio > 0.0f) && ratio == ratio) {        // off: the steps launch what they always did
+        c->dyn_ratio = 0.f;
+        return 0;
+    }
+    if (check_threshold_args("sr3_set_dynamic_threshold", ratio, max_value)) return -1;
+    // ratio (through the rank) and max_value are launch arguments of the captured steps
+    if (ratio != c->dyn_ratio || max_value != c->dyn_max) drop_dyn_graphs(c);
+    c->dyn_ratio = ratio; c->dyn_max = max_value;
+    return 0;
+}
+
+int sr3_op_abs_quantile(sr3_ctx *c, const float *x_dev, int B, int64_t n, float ratio, float max_value, float *lo_dev, float *hi_dev,
+                        float *s_dev) {
+    if (check_threshold_op(c, "sr3_op_abs_quantile", x_dev, B, n, ratio, max_value)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    if (ensure_thr_op_scratch(c, B)) return -1;
+    c->pbegin(F_MISC);
+    launch_abs_quantile(x_dev, B, n, threshold_plan(ratio, n), max_value, c->thr_op_bins, lo_dev, hi_dev, s_dev, c->stream);
+    c->pend();
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int sr3_op_dynamic_threshold(sr3_ctx *c, float *x0_dev, int B, int64_t n, float ratio, float max_value, float *s_dev) {
+    if (check_threshold_op(c, "sr3_op_dynamic_threshold", x0_dev, B, n, ratio, max_value)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    if (ensure_thr_op_scratch(c, B)) return -1;
+    float *s = s_dev ? s_dev : reinterpret_cast<float *>(c->thr_op_bins + (size_t)c->thr_op_rows * THR_BINS_PER_IMAGE);
+    c->pbegin(F_MISC);
+    launch_abs_quantile(x0_dev, B, n, threshold_plan(ratio, n), max_value, c->thr_op_bins, nullptr, nullptr, s, c->stream);
+    launch_threshold_apply(x0_dev, B, n, s, c->stream);
     c->pend();
     HIP_OK(hipGetLastError());
     return 0;

@@ -485,8 +485,30 @@ void launch_lr_residual(const float *img, int B, int C, const LrOps &o, const Lr
                         float *maxabs, hipStream_t s);
 // launch_ddpm_update in two halves: the clamped x0 prediction into x0hat (NCHW [B][C][H][W]), and the rest of the update
 // reading x0 from there (between them: launch_lr_project on x0hat)
-void launch_x0_predict(const UpdateParams &p, float *x0hat, int B, hipStream_t s);
+// clamp false: x0 = a x - b eps as it is (the dynamic threshold below takes the clamp's place)
+void launch_x0_predict(const UpdateParams &p, float *x0hat, int B, hipStream_t s, bool clamp = true);
 void launch_update_from_x0(const UpdateParams &p, const float *x0hat, int B, hipStream_t s);
+
+// ---- dynamic thresholding of the x0 prediction (kernels_threshold.hip) ----------------------------------
+// Exact per-image order statistics of |x| over x [B][n] by a radix select: THR_PASSES passes of THR_DIGIT_BITS key bits,
+// integer counts only. bins: [B][THR_PASSES][2][THR_BINS] unsigned of scratch (zeroed by the launch).
+constexpr int THR_DIGIT_BITS = 8, THR_BINS = 1 << THR_DIGIT_BITS, THR_PASSES = 4;
+constexpr size_t THR_BINS_PER_IMAGE = (size_t)THR_PASSES * 2 * THR_BINS;
+inline size_t threshold_bins_bytes(int B) { return (size_t)B * THR_BINS_PER_IMAGE * sizeof(unsigned); }
+// What (ratio, n) fix, on the host: pos = (double)ratio * (n - 1), k = min(floor(pos), n - 1), k2 = min(k + 1, n - 1),
+// frac = (float)(pos - k); and the blocks that share one image. Launch arguments: constant over a sampling call.
+struct ThrPlan {
+    unsigned k = 0, k2 = 0;
+    float frac = 0.f;
+    int blocks = 1;
+};
+ThrPlan threshold_plan(float ratio, int64_t n);
+// per image b: lo[b] / hi[b] = the k-th / k2-th smallest |x| (keys: bit patterns of |x| as unsigned integers),
+// s[b] = min(max(lo + frac * (hi - lo), 1), max_value); lo, hi, s may each be null
+void launch_abs_quantile(const float *x, int B, int64_t n, const ThrPlan &p, float max_value, unsigned *bins, float *lo, float *hi,
+                         float *s, hipStream_t st);
+// x[b][i] <- clamp(x[b][i], -s[b], s[b]) / s[b]
+void launch_threshold_apply(float *x, int B, int64_t n, const float *s, hipStream_t st);
 
 // ---- Philox normal stream (device functions; the kernels that draw from it: kernels_misc.hip, kernels_loss.hip) ----
 // Philox4x32-10 (Salmon et al. 2011). CPU twin: oracle/philox.py.

@@ -90,6 +90,7 @@ class GaussianDiffusion(nn.Module):
         self._sampler = ("ddpm", None, 0.0)   # set_sampler(); not part of state_dict()
         self._lr = None                       # set_lr_consistency(): (fp32 [N,C,lh,lw], strength); not part of state_dict()
         self._start = None                    # set_start(): (strength | None, step | None, init, noised); not part of state_dict()
+        self._dyn = None                      # set_dynamic_threshold(): (ratio, max_value | None); not part of state_dict()
 
     # ---- reference surface that is configuration only -----------------------------------------
     def set_loss(self, device=None):
@@ -224,6 +225,41 @@ class GaussianDiffusion(nn.Module):
         eng.set_lr_consistency(t.data_ptr(), N, lh, lw, int(row_offset), strength)
         eng._lr_on = True
         return t
+
+    def set_dynamic_threshold(self, ratio=None, max_value=None) -> None:
+        """Dynamic thresholding of the x0 prediction in every sampling entry point (Imagen, Saharia et
+        al. 2022, §2.3): each step replaces the reference's x_recon.clamp_(-1., 1.) (diffusion.py:175-176) by
+        clamp(x0, -s, s) / s, with s the `ratio`-quantile of |x0| over the C*H*W values of each image (exact, linear
+        interpolation between the two order statistics), never below 1 and never above max_value. With s = 1 that is the
+        static clamp bit for bit. The few-step samplers (set_sampler "ddim" / "dpmpp_2m", set_start) are where it
+        matters: their early x0 predictions lie far outside [-1, 1].
+
+          ratio      in (0, 1]; None turns the feature off: the sampler is then bit for bit what it was
+          max_value  >= 1, the cap on s; None means no bound
+
+        The statistic is per image, so chunks, shards and image offsets change nothing. The setting survives set_sampler
+        and set_new_noise_schedule, adds nothing to state_dict(), and leaves p_sample — the reference's single step —
+        alone. Sample quality with it on a trained checkpoint is not established here."""
+        if ratio is None:
+            if max_value is not None:
+                raise ValueError("max_value needs a ratio (ratio=None turns the feature off)")
+            self._dyn = None
+            return
+        ratio = float(ratio)
+        if not 0.0 < ratio <= 1.0:              # (also refuses NaN)
+            raise ValueError(f"ratio must lie in (0, 1], got {ratio}")
+        if max_value is not None:
+            max_value = float(max_value)
+            if not max_value >= 1.0:
+                raise ValueError(f"max_value must be >= 1 (None: no bound), got {max_value}")
+        self._dyn = (ratio, max_value)
+
+    def _arm_dyn(self, eng) -> None:
+        """Puts the engine's threshold setting in the state the next sampling call needs (next to _arm_lr)."""
+        want = self._dyn
+        if getattr(eng, "_dyn_set", None) != want:
+            eng.set_dynamic_threshold(*(want if want is not None else (None, None)))
+            eng._dyn_set = want
 
     def set_dropout_sampling(self, on: bool, seed: Optional[int] = None) -> None:
         """Opt in to sampling the UNet's Dropout as the reference does under .train() (unet.py:81-91; model 3 samples
@@ -395,6 +431,7 @@ class GaussianDiffusion(nn.Module):
         if n_chunks == 1:
             self.denoise_fn.ready()
             self._arm_lr(eng, dev, H, W, image_offset)
+            self._arm_dyn(eng)
             run(x, B, out, noise, image_offset, frames, x_init)
             self.denoise_fn.finish()
             return (out, frames) if continous else out
@@ -419,6 +456,7 @@ class GaussianDiffusion(nn.Module):
             fc = torch.empty((frames.shape[0], chunk, C, H, W), dtype=torch.float32, device=dev) if continous else None
             self.denoise_fn.ready()
             self._arm_lr(eng, dev, H, W, image_offset + a)
+            self._arm_dyn(eng)
             run(xc, chunk, oc, nc, image_offset + a, fc, ic)
             self.denoise_fn.finish()
             if not whole:
@@ -526,6 +564,9 @@ class GaussianDiffusion(nn.Module):
             if getattr(eng, "_lr_on", False):       # (the reference's single step: never projected)
                 eng.set_lr_consistency(None)
                 eng._lr_on = False
+            if getattr(eng, "_dyn_set", None) is not None:      # (nor thresholded)
+                eng.set_dynamic_threshold(None)
+                eng._dyn_set = None
             eng.sample_begin(cond.data_ptr() if cond is not None else None, B, H, W, x.data_ptr(), 0, 0)
             eng.sample_step(int(t), nz.data_ptr() if nz is not None else None)
             eng.sample_end(out.data_ptr())

@@ -434,6 +434,64 @@ class Engine:
         return out
 
     # ---- train-mode Dropout ---------------------------------------------------
+    # ---- dynamic thresholding of the x0 prediction ------------------------------
+    def set_dynamic_threshold(self, ratio: Optional[float] = None, max_value: Optional[float] = None) -> None:
+        """While set, every sampling step replaces the static clamp of its x0 prediction by clamp(x0, -s, s) / s with s the
+        per-image `ratio`-quantile of |x0|, at least 1 and at most max_value (None: no bound). ratio None (or <= 0) turns it
+        off (sr3_set_dynamic_threshold). Set before sample / sample_begin."""
+        if ratio is None:
+            _lib.check(self.lib.sr3_set_dynamic_threshold(self.ctx, 0.0, 1.0))
+            return
+        _lib.check(self.lib.sr3_set_dynamic_threshold(self.ctx, float(ratio), float("inf") if max_value is None else float(max_value)))
+
+    def dynamic_threshold_launches(self) -> int:
+        """Sampler steps issued in the thresholded form since the engine was created (sr3_dynamic_threshold_launches)."""
+        return int(self.lib.sr3_dynamic_threshold_launches(self.ctx))
+
+    def abs_quantile(self, x_ptr: int, B: int, n: int, ratio: float, max_value: Optional[float], lo_ptr: Optional[int],
+                     hi_ptr: Optional[int], s_ptr: Optional[int]) -> None:
+        """Per row of x fp32 [B,n]: the two order statistics of |x| around the ratio-quantile and s (sr3_op_abs_quantile;
+        stream-ordered)."""
+        _lib.check(self.lib.sr3_op_abs_quantile(self.ctx, x_ptr, int(B), int(n), float(ratio),
+                                                float("inf") if max_value is None else float(max_value), lo_ptr or None,
+                                                hi_ptr or None, s_ptr or None))
+
+    def dynamic_threshold(self, x_ptr: int, B: int, n: int, ratio: float, max_value: Optional[float] = None,
+                          s_ptr: Optional[int] = None) -> None:
+        """x <- clamp(x, -s, s) / s in place on x fp32 [B,n] (sr3_op_dynamic_threshold; stream-ordered)."""
+        _lib.check(self.lib.sr3_op_dynamic_threshold(self.ctx, x_ptr, int(B), int(n), float(ratio),
+                                                     float("inf") if max_value is None else float(max_value), s_ptr or None))
+
+    def op_abs_quantile(self, x, ratio: float, max_value: Optional[float] = None, misalign: bool = False) -> Dict[str, np.ndarray]:
+        """numpy convenience: x [B, ...] -> {"lo", "hi", "s"}, fp32 [B] each. misalign: the device copy starts 4 bytes past
+        a 16-byte boundary."""
+        x = _host_f32(x)
+        B = x.shape[0]
+        n = x.size // B
+        flat = x.reshape(-1)
+        if misalign:
+            flat = np.concatenate([np.zeros(1, np.float32), flat])
+        dx, out = self.to_device(flat), self.buffer(3 * B)
+        self.abs_quantile(dx.ptr + (4 if misalign else 0), B, n, ratio, max_value, out.ptr, out.ptr + 4 * B, out.ptr + 8 * B)
+        r = out.download((3, B))
+        dx.free(); out.free()
+        return {"lo": r[0].copy(), "hi": r[1].copy(), "s": r[2].copy()}
+
+    def op_dynamic_threshold(self, x, ratio: float, max_value: Optional[float] = None, misalign: bool = False):
+        """numpy convenience: x [B, ...] -> (the thresholded x, s [B])."""
+        x = _host_f32(x)
+        B = x.shape[0]
+        n = x.size // B
+        flat = x.reshape(-1)
+        if misalign:
+            flat = np.concatenate([np.zeros(1, np.float32), flat])
+        dx, ds = self.to_device(flat), self.buffer(B)
+        self.dynamic_threshold(dx.ptr + (4 if misalign else 0), B, n, ratio, max_value, ds.ptr)
+        got = dx.download()[1 if misalign else 0:].reshape(x.shape).copy()
+        s = ds.download()
+        dx.free(); ds.free()
+        return got, s
+
     def set_dropout(self, enable: bool, seed: int = 0, image_offset: int = 0) -> None:
         """Train-mode Dropout (p = cfg.dropout) in front of every ResnetBlock.block2 conv, as the reference's UNet under
         .train(); off (the default) is the identity and launches exactly the kernels it always did. `seed` keys the Philox

@@ -575,6 +575,36 @@ int sr3_op_lr_project(sr3_ctx *ctx, float *x_dev, int B, int C, int H, int W, co
 int sr3_lr_residual(sr3_ctx *ctx, const float *img_dev, int B, int C, int H, int W, const float *lr_dev, int N,
                     int lh, int lw, uint64_t row_offset, double *sumsq_dev, float *maxabs_dev);
 
+/* ---- dynamic thresholding of the x0 prediction ---------------------------- */
+/* Replaces, while on, the static x_recon.clamp_(-1., 1.) of every sampler step (model/sr/sr3_modules/diffusion.py:175-176)
+ * by the dynamic thresholding of Imagen (Saharia et al. 2022, section 2.3), which generalises it. Defined by DESIGN.md
+ * 3.5e; per image b of the batch, n = out_channel * H * W, before any low-resolution projection:
+ *   x0  = a x - b eps                                                   (the update's prediction, not clamped)
+ *   keys: the bit patterns of |x0| as unsigned integers (a total order: -0 = +0, denormals kept, NaN above inf)
+ *   pos = (double)ratio * (n - 1), k = min(floor(pos), n - 1), frac = (float)(pos - k)
+ *   lo  = the k-th smallest key (0-based, ties with their multiplicity), hi = the (k+1)-th, or lo when k = n - 1
+ *   s   = min(max(lo + frac * (hi - lo), 1), max_value)                 (every operation rounded by itself; NaN -> 1)
+ *   x0 <- clamp(x0, -s, s) / s                                          (s = 1: the bits of the static clamp)
+ * and everything downstream — the posterior mean, the x0 history of dpmpp_2m, the projection of
+ * sr3_set_lr_consistency — takes that x0. The order statistics are exact (a radix select with integer counts): two
+ * calls return the same bits. ratio in (0, 1] turns it on with max_value >= 1 (+inf: no upper bound); ratio <= 0
+ * turns it off, and a step then launches exactly the kernels it always did. Fails for ratio > 1 or NaN, and (when on)
+ * max_value < 1 or NaN. Set it before sr3_sample_begin; covers sr3_sample, sr3_sample_from and the step API in all three
+ * arithmetic modes (the threshold is always fp32), with the range policy's replays. A change rebuilds the captured
+ * steps that hold it. */
+int sr3_set_dynamic_threshold(sr3_ctx *ctx, float ratio, float max_value);
+/* The selection alone (defined by DESIGN.md 3.5e, items 2-3 above) on any fp32 x_dev [B][n], 0 < n < 2^31: lo_dev[b],
+ * hi_dev[b], s_dev[b] (each may be NULL). ratio in (0, 1], max_value >= 1. Needs no weights. x_dev needs only the
+ * alignment of a float. Asynchronous (stream-ordered). */
+int sr3_op_abs_quantile(sr3_ctx *ctx, const float *x_dev, int B, int64_t n, float ratio, float max_value, float *lo_dev,
+                        float *hi_dev, float *s_dev);
+/* Selection and x0 <- clamp(x0, -s, s) / s in place on a caller buffer [B][n] (with s = 1 the reference's
+ * x_recon.clamp_(-1., 1.), diffusion.py:175-176); s_dev [B] receives s when not NULL. Asynchronous. */
+int sr3_op_dynamic_threshold(sr3_ctx *ctx, float *x0_dev, int B, int64_t n, float ratio, float max_value, float *s_dev);
+/* Sampler steps this context issued since sr3_create in the thresholded form (x0 prediction | selection | threshold |
+ * [projection] | update), one per step whether launched or replayed from a captured graph: tells a test which form ran. */
+int sr3_dynamic_threshold_launches(sr3_ctx *ctx);
+
 /* ---- device memory helpers (so hosts without torch can drive the library) ---------------- */
 int sr3_dev_malloc(sr3_ctx *ctx, uint64_t bytes, void **out_dev);
 int sr3_dev_free(sr3_ctx *ctx, void *dev);
