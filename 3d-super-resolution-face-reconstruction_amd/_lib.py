@@ -134,6 +134,9 @@ PROTOTYPES = {
     "sr3_op_abs_quantile": (_I, [_P, _F, _I, C.c_int64, C.c_float, C.c_float, _F, _F, _F]),
     "sr3_op_dynamic_threshold": (_I, [_P, _F, _I, C.c_int64, C.c_float, C.c_float, _F]),
     "sr3_dynamic_threshold_launches": (_I, [_P]),
+    "sr3_set_feature_cache": (_I, [_P, _I, _I]),
+    "sr3_feature_cache_steps": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "sr3_unet_forward_cached": (_I, [_P, _F, _F, _I, _I, _I, _I, _F]),
     "sr3_dev_malloc": (_I, [_P, _U64, C.POINTER(_P)]),
     "sr3_dev_free": (_I, [_P, _P]),
     "sr3_memcpy_h2d": (_I, [_P, _P, _P, _U64]),
@@ -147,7 +150,7 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual",
                   "sr3_sample_begin_from", "sr3_sample_from", "sr3_num_frames_from", "sr3_op_conv_in", "sr3_op_final_conv",
                   "sr3_read_packed_state", "sr3_set_dynamic_threshold", "sr3_op_abs_quantile", "sr3_op_dynamic_threshold",
-                  "sr3_dynamic_threshold_launches")
+                  "sr3_dynamic_threshold_launches", "sr3_set_feature_cache", "sr3_feature_cache_steps", "sr3_unet_forward_cached")
 
 _lib = None
 

@@ -147,7 +147,11 @@ struct sr3_ctx {
     bool f8() const { return mode == A_F16F8; }
     // which captured step graph: one per arithmetic, and per arithmetic one per form of the update (plain | with the
     // consistency projection | with the dynamic threshold | with both)
-    int graph_slot() const { return (int)mode + (lr_on() ? 3 : 0) + (dyn_on() ? 6 : 0); }
+    // ... and all of those once more for the shallow step of the feature cache (kStepForms on)
+    static constexpr int kStepForms = 12;
+    int graph_slot(bool shallow = false) const {
+        return (int)mode + (lr_on() ? 3 : 0) + (dyn_on() ? 6 : 0) + (shallow ? kStepForms : 0);
+    }
     // split format of an activated conv input (launch_gn_apply's `split`): 0 fp32, 1 split-f16, 2 F8C when the consumer
     // conv takes the fp8 operands (f8_conv() said so)
     int act_format(bool f8_operand) const { return split() ? (f8_operand ? 2 : 1) : 0; }
@@ -226,6 +230,21 @@ struct sr3_ctx {
     unsigned *thr_op_bins = nullptr;    // sr3_op_abs_quantile / sr3_op_dynamic_threshold: counts, then thr_op_rows floats of s
     int thr_op_rows = 0;
 
+    // Feature cache (sr3_set_feature_cache; DeepCache, Ma, Fang, Wang 2023). Off by default (fc_interval
+    // <= 1): every step is then the whole forward it always was. On: step fc_k of a call is whole when fc_k % fc_interval
+    // == 0 or the cache is not valid, else it runs the fc_depth top levels on what the last whole step left in the
+    // workspace. The cache IS the workspace: fc_mode is the arithmetic of the last whole run_unet_body on it (-1: none
+    // since the workspace was built, a weight changed or sr3_set_precision was called), fc_call says that forward was a
+    // step of the live sampling call (any other run_unet_body clears it).
+    int fc_interval = 0, fc_depth = 1;
+    int fc_k = 0;                       // steps since sr3_sample_begin*
+    int fc_mode = -1;
+    bool fc_call = false;
+    int fc_whole = 0, fc_shallow = 0;   // steps of the last call, replayed ones included (sr3_feature_cache_steps)
+    bool fc_on() const { return fc_interval > 1; }
+    void fc_invalidate() { fc_mode = -1; fc_call = false; }
+    int fc_max_depth() const { return cfg.n_mults - 1; }
+
     // workspace for one (B, H, W)
     int wB = 0, wH = 0, wW = 0;
     char *arena = nullptr;
@@ -265,7 +284,7 @@ struct sr3_ctx {
     StepArgs *h_ring = nullptr, *d_step = nullptr;
     uint64_t step_count = 0;
     // one p_sample step captured as a hipGraph (per precision); rebuilt when the workspace changes
-    static constexpr int kGraphs = 12;  // graph_slot(): per arithmetic (f32, f16x3, f16f8) and form of the update
+    static constexpr int kGraphs = 2 * kStepForms;  // graph_slot(): per arithmetic (f32, f16x3, f16f8), form of the update, whole | shallow
     hipGraphExec_t step_graph[kGraphs] = {};
     int graph_warm[kGraphs] = {};
     bool no_graph = false;
@@ -605,6 +624,11 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
         c->arena = nullptr;
     }
     drop_graphs(c);
+    c->fc_invalidate();
+    // Feature cache: every module below gets an output (out_off), twin (tw_off) and statistics slices
+    // (so_off / sr_off / sh_off) of its own, which only the module's own convs write; acts, h1s and raws are
+    // block-internal. A shallow forward therefore leaves the outputs of the modules it skips as the last whole forward
+    // wrote them.
     // dry run over the graph for sizes
     Carver cv;
     ShapePool acts, h1s, raws;
@@ -1025,10 +1049,23 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     }
 }
 
-// UNet.forward body (unet.py:240-265): consumes c->x0 and c->cbias, leaves eps NHWC in c->eps
-void run_unet_body(sr3_ctx *c, int B, int H, int W) {
+// The modules a shallow forward of `depth` runs: conv_in and the next depth * res_blocks + (depth - 1)
+// down modules — everything in front of the Downsample that leaves level depth - 1 — are [0, down_end); the last
+// depth * (res_blocks + 1) + (depth - 1) up modules are [up_begin, mods.size()). mods[up_begin - 1] is the Upsample that
+// returns to level depth - 1: its output, as the last whole forward left it, is the cached feature.
+struct ShallowSplit { int down_end, up_begin; };
+ShallowSplit shallow_split(const sr3_ctx *c, int depth) {
+    const int rb = c->cfg.res_blocks;
+    return {1 + depth * rb + (depth - 1), (int)c->mods.size() - (depth * (rb + 1) + (depth - 1))};
+}
+
+// UNet.forward body (unet.py:240-265): consumes c->x0 and c->cbias, leaves eps NHWC in c->eps.
+// depth > 0: the shallow forward (shallow_split); the caller has checked that the workspace holds a whole forward in the
+// current arithmetic.
+void run_unet_body(sr3_ctx *c, int B, int H, int W, int depth = 0) {
     std::vector<int> feats;
     c->drop_layer = 0; c->drop_base = 0;      // (run_res numbers the Dropout layers in execution order)
+    const ShallowSplit sh = depth > 0 ? shallow_split(c, depth) : ShallowSplit{0, 0};
     TDesc cur = c->x0, cur_s;         // cur_s: split twin of cur (prec 1), null if none
     bool cur_so = false;              // cur exists only as cur_s
     StatsRef scur;
@@ -1038,6 +1075,20 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W) {
     const bool so_mode = c->split() && c->all_fused;
     const int n_pre = c->n_downs + c->n_mid;
     for (int i = 0; i < (int)c->mods.size(); ++i) {
+        if (depth > 0 && i == sh.down_end) {
+            // The jump of the shallow forward. The Dropout cursor advances over the skipped ResnetBlocks, so a fresh up
+            // block draws the masks it draws in a whole forward; the traversal continues from the cached Upsample's
+            // output, twin and statistics (so_now of an Upsample is a function of the arithmetic, which is the cache's).
+            for (int j = i; j < sh.up_begin; ++j) {
+                const Module &s = c->mods[j];
+                if (s.kind != M_RES) continue;
+                ++c->drop_layer;
+                c->drop_base += (uint64_t)B * s.rb.cout * s.oh * s.ow;
+            }
+            const Module &cm = c->mods[sh.up_begin - 1];
+            cur = cm.out; cur_s = cm.out_s; cur_so = so_mode && cm.out_s.p; scur = cm.st_out;
+            i = sh.up_begin;
+        }
         Module &m = c->mods[i];
         const bool is_up_path = i >= n_pre;
         ConvCall k;                       // the module's own conv (conv_in, Downsample, Upsample)
@@ -1460,17 +1511,19 @@ int push_drop_args(sr3_ctx *c, const char *what, uint64_t image_offset) {
 }
 
 // ---- low-resolution consistency: operators and buffers ---------------------------------------------------------------
-// the captured steps that hold x0hat: every form but the plain one (slots 3..)
+// the captured steps that hold x0hat: every form but the plain one (slots 3.. of the whole and of the shallow steps)
 void drop_lr_graphs(sr3_ctx *c) {
-    for (int i = 3; i < sr3_ctx::kGraphs; ++i) {
+    for (int i = 0; i < sr3_ctx::kGraphs; ++i) {
+        if (i % sr3_ctx::kStepForms < 3) continue;
         if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
         c->step_graph[i] = nullptr;
         c->graph_warm[i] = 0;
     }
 }
-// the captured steps with the dynamic threshold in them (slots 6..)
+// the captured steps with the dynamic threshold in them (slots 6.. of the whole and of the shallow steps)
 void drop_dyn_graphs(sr3_ctx *c) {
-    for (int i = 6; i < sr3_ctx::kGraphs; ++i) {
+    for (int i = 0; i < sr3_ctx::kGraphs; ++i) {
+        if (i % sr3_ctx::kStepForms < 6) continue;
         if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
         c->step_graph[i] = nullptr;
         c->graph_warm[i] = 0;
@@ -1580,11 +1633,12 @@ int prepare_dyn_step(sr3_ctx *c, int B, int H, int W) {
 
 // the launches of one p_sample step (embedding, UNet body, DDPM update); every per-step value is
 // read from c->d_step, so the sequence is identical for every t
-void enqueue_step(sr3_ctx *c) {
+// depth > 0: the shallow step of the feature cache (run_unet_body); the update half is the same
+void enqueue_step(sr3_ctx *c, int depth = 0) {
     const int B = c->wB, H = c->wH, W = c->wW;
     // noise_level = float32(sqrt_alphas_cumprod_prev[t+1]) repeated over the batch (diffusion.py:166-167)
     run_embed(c, &c->d_step->nl, 0, B);
-    run_unet_body(c, B, H, W);
+    run_unet_body(c, B, H, W, depth);
     UpdateParams u;
     u.state = c->x0; u.C = c->cfg.out_channel;
     u.packed = c->x0p;          // kept current in both arithmetic modes (the mode may change between steps)
@@ -1646,20 +1700,28 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     if (c->drop_live() && fill_drop_args(c, "p_sample step", sa.drop, sa.draw, c->image_offset)) return -1;
     if (push_step_args(c, &sa)) return -1;
 
-    const int g = c->graph_slot();
+    // Feature cache: step k of the call is shallow when k is no multiple of the interval and the workspace holds the
+    // whole forward of an earlier step of THIS call in the arithmetic this step runs in (a step-down of the guard, a
+    // forward from outside, a new workspace or new weights make the step whole, whatever k is).
+    const bool shallow = c->fc_on() && (c->fc_k % c->fc_interval) != 0 && c->fc_call && c->fc_mode == (int)c->mode;
+    const int depth = shallow ? c->fc_depth : 0;
+    ++c->fc_k;
+    ++(shallow ? c->fc_shallow : c->fc_whole);
+    if (!shallow) { c->fc_mode = (int)c->mode; c->fc_call = true; }
+    const int g = c->graph_slot(shallow);
     if (c->prof || c->no_graph) {
-        enqueue_step(c);
+        enqueue_step(c, depth);
         return 0;
     }
     if (!c->step_graph[g]) {
         if (c->graph_warm[g] < 1) {          // first step runs eagerly (one-time function attributes)
             ++c->graph_warm[g];
-            enqueue_step(c);
+            enqueue_step(c, depth);
             return 0;
         }
         hipGraph_t graph = nullptr;
         HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        enqueue_step(c);
+        enqueue_step(c, depth);
         HIP_OK(hipStreamEndCapture(c->stream, &graph));
         hipError_t e = hipGraphInstantiate(&c->step_graph[g], graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
@@ -1924,6 +1986,7 @@ int sr3_set_precision(sr3_ctx *c, int prec) {
     if (prec < 0 || prec > 2)
         return fail("precision %d unknown (0 = f32 exact, 1 = split-f16, 2 = split-f16 with fp8 correction products)", prec);
     c->mode = (Arith)prec;
+    c->fc_invalidate();
     return 0;
 }
 
@@ -1995,6 +2058,7 @@ int sr3_load_weight(sr3_ctx *c, const char *name, const float *host, const int64
             if (p.shape[i] != shape[i]) return fail("%s: dim %d is %lld, expected %lld", name, i, (long long)shape[i], (long long)p.shape[i]);
         // weights may change while earlier launches are still reading them
         HIP_OK(hipStreamSynchronize(c->stream));
+        c->fc_invalidate();     // (the cached features are those of the old weights)
         if (p.kind == P_CONV) {
             if (c->ci_w && &p == &c->params[c->mods[0].conv.w]) {
                 std::vector<float> wf(conv_in_weight_floats(p.cout));
@@ -2115,6 +2179,7 @@ int sr3_load_weights_dev(sr3_ctx *c, int n, const char *const *names, const floa
         if (touched[idx[e]]) return fail("%s: listed twice in one sr3_load_weights_dev call", names[e]);
         touched[idx[e]] = 1;
     }
+    c->fc_invalidate();     // (the cached features are those of the old weights)
     const StageLayout L = stage_layout(c);
     if (!c->d_wmax) {
         HIP_OK(hipMalloc(&c->d_wmax, np * sizeof(unsigned)));
@@ -2291,14 +2356,16 @@ int sr3_weights_missing(sr3_ctx *c) {
 int sr3_chan_bias_total(sr3_ctx *c) { return c ? c->nf_total : fail("null context"); }
 
 // one evaluation in the context's current arithmetic (the callable of guarded_eval)
-static int unet_forward_once(sr3_ctx *c, const float *x_dev, const float *noise_level_dev, int B, int H, int W,
+// depth > 0: the shallow forward; a whole one leaves the workspace as the cache of this arithmetic
+static int unet_forward_once(sr3_ctx *c, const float *x_dev, const float *noise_level_dev, int B, int H, int W, int depth,
                              float *out_dev) {
     c->pbegin(F_MISC);
     launch_nchw_to_nhwc(x_dev, B, c->cfg.in_channel, c->x0, 0, c->stream);
     if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
     c->pend();
     run_embed(c, noise_level_dev, 1, B);
-    run_unet_body(c, B, H, W);
+    run_unet_body(c, B, H, W, depth);
+    if (!depth) c->fc_mode = (int)c->mode;
     c->pbegin(F_MISC);
     launch_nhwc_to_nchw(c->eps, 0, B, c->cfg.out_channel, out_dev, c->stream);
     c->pend();
@@ -2314,8 +2381,62 @@ int sr3_unet_forward(sr3_ctx *c, const float *x_dev, const float *noise_level_de
     if (ensure_workspace(c, B, H, W)) return -1;
     c->sampling = false;
     if (push_drop_args(c, "sr3_unet_forward", c->drop_offset)) return -1;
-    return guarded_eval(c, "sr3_unet_forward", "the forward pass", true,
-                        [&] { return unet_forward_once(c, x_dev, noise_level_dev, B, H, W, out_dev); });
+    c->fc_invalidate();
+    // (each evaluation records its arithmetic: after a step down the workspace holds the features of the rung landed on)
+    const int r = guarded_eval(c, "sr3_unet_forward", "the forward pass", true,
+                               [&] { return unet_forward_once(c, x_dev, noise_level_dev, B, H, W, 0, out_dev); });
+    if (r < 0) c->fc_invalidate();
+    return r;
+}
+
+// the modules of a shallow forward of `depth`, checked against the graph this context built
+static int check_cache_depth(sr3_ctx *c, const char *what, int depth) {
+    if (depth < 1 || depth > c->fc_max_depth())
+        return fail("%s: depth %d outside [1, %d] (the resolution levels kept fresh; n_mults - 1 at the most)", what, depth,
+                    c->fc_max_depth());
+    const ShallowSplit sh = shallow_split(c, depth);
+    if (sh.down_end > c->n_downs || sh.up_begin <= c->n_downs + c->n_mid || c->mods[sh.up_begin - 1].kind != M_UP)
+        return fail("internal: the shallow forward of depth %d does not resume behind an Upsample", depth);
+    return 0;
+}
+
+int sr3_unet_forward_cached(sr3_ctx *c, const float *x_dev, const float *noise_level_dev, int B, int H, int W, int depth,
+                            float *out_dev) {
+    if (check_ready(c)) return -1;
+    if (!x_dev || !noise_level_dev || !out_dev) return fail("sr3_unet_forward_cached: null pointer");
+    if (check_cache_depth(c, "sr3_unet_forward_cached", depth)) return -1;
+    if (!c->arena || c->wB != B || c->wH != H || c->wW != W || c->fc_mode != (int)c->mode)
+        return fail("sr3_unet_forward_cached: the workspace holds no whole forward of B=%d H=%d W=%d in the current arithmetic "
+                    "(run sr3_unet_forward at that shape first; a new shape, sr3_set_precision, a weight load and a forward "
+                    "that the range policy finished in another arithmetic all discard it)", B, H, W);
+    c->sampling = false;
+    c->fc_call = false;
+    if (push_drop_args(c, "sr3_unet_forward_cached", c->drop_offset)) return -1;
+    // (no step down: the deep features are those of this arithmetic; out of range is an error that names it)
+    return guarded_eval(c, "sr3_unet_forward_cached", "the shallow forward pass", false,
+                        [&] { return unet_forward_once(c, x_dev, noise_level_dev, B, H, W, depth, out_dev); });
+}
+
+int sr3_set_feature_cache(sr3_ctx *c, int interval, int depth) {
+    if (!c) return fail("null context");
+    if (interval <= 1) { c->fc_interval = 0; return 0; }
+    if (check_cache_depth(c, "sr3_set_feature_cache", depth)) return -1;
+    if (depth != c->fc_depth) {     // the captured shallow steps run the old depth
+        HIP_OK(hipSetDevice(c->device));
+        for (int i = sr3_ctx::kStepForms; i < sr3_ctx::kGraphs; ++i) {
+            if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
+            c->step_graph[i] = nullptr;
+            c->graph_warm[i] = 0;
+        }
+    }
+    c->fc_interval = interval; c->fc_depth = depth;
+    return 0;
+}
+
+int sr3_feature_cache_steps(sr3_ctx *c, int *whole, int *shallow) {
+    if (!c || !whole || !shallow) return fail("sr3_feature_cache_steps: null argument");
+    *whole = c->fc_whole; *shallow = c->fc_shallow;
+    return 0;
 }
 
 // ---- the denoising loss (diffusion.py:284-313, evaluation only) ---------------------------------
@@ -2371,6 +2492,7 @@ int sr3_denoise_loss(sr3_ctx *c, const float *hr_dev, const float *cond_dev, int
     if (ensure_workspace(c, B, H, W)) return -1;
     if (ensure_partials(c, (size_t)B * loss_blocks(H, W))) return -1;
     c->sampling = false;
+    c->fc_invalidate();
     LossCall k;
     k.hr = hr_dev; k.cond = cond_dev; k.level = level_dev; k.s = s_dev;
     k.nz.noise = noise_dev; k.nz.seed = seed; k.nz.image_offset = image_offset; k.nz.per_source = noise_per_source != 0;
@@ -2478,6 +2600,7 @@ int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, con
     c->image_offset = image_offset;
     c->hist_valid = false;
     c->fold_first = false;
+    c->fc_k = 0; c->fc_call = false; c->fc_whole = c->fc_shallow = 0;
     if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
     if (c->dyn_on() && prepare_dyn_step(c, B, H, W)) return -1;
     if (range_reset(c)) return -1;
@@ -2528,6 +2651,7 @@ int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W
     c->image_offset = image_offset;
     c->hist_valid = false;
     c->fold_first = true;
+    c->fc_k = 0; c->fc_call = false; c->fc_whole = c->fc_shallow = 0;
     if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
     if (c->dyn_on() && prepare_dyn_step(c, B, H, W)) return -1;
     if (range_reset(c)) return -1;
@@ -2591,7 +2715,7 @@ namespace {
 struct Checkpoint {
     sr3_ctx *c;
     size_t slab;            // floats of the state (and of the history)
-    int t = 0, frames = 0;
+    int t = 0, frames = 0, k = 0;   // k: the feature cache's step counter (a multiple of its interval: the next step is whole)
     bool hist_valid = false;
 
     Checkpoint(sr3_ctx *ctx, size_t slab_floats) : c(ctx), slab(slab_floats) {}
@@ -2611,7 +2735,7 @@ struct Checkpoint {
             const hipError_t e = hipMemcpyAsync(c->ckpt + slab, c->xhist, slab * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
             if (e != hipSuccess) return fail("sr3_sample: checkpoint of the x0 history: %s", hipGetErrorString(e));
         }
-        t = before_step; frames = frames_written; hist_valid = c->hist_valid;
+        t = before_step; frames = frames_written; hist_valid = c->hist_valid; k = c->fc_k;
         return 0;
     }
     int restore() {
@@ -2623,6 +2747,7 @@ struct Checkpoint {
             if (e != hipSuccess) return fail("sr3_sample: restore of the x0 history: %s", hipGetErrorString(e));
         }
         c->hist_valid = hist_valid;
+        c->fc_k = k;
         return 0;
     }
 };
@@ -2650,7 +2775,11 @@ int sample_impl(sr3_ctx *c, const char *what, const float *cond_dev, int B, int 
     // the same arithmetic, whatever the policy. Out of RANGE fails the call under the strict policy; else the checkpoint
     // is restored and the REST of the loop runs one arithmetic down (step_down) — every draw of the noise (injected slab
     // or Philox draw index) and every frame slot is a function of t, so the replay is exact.
-    const int seg = std::max(1, T / 10);
+    // With the feature cache on, a segment is a whole number of its intervals: every checkpoint then stands in front of a
+    // whole step, so a restore needs no copy of the cache (the replayed segment rebuilds it first, in the arithmetic it now
+    // runs in), and which steps are whole stays a function of the step index alone.
+    int seg = std::max(1, T / 10);
+    if (c->fc_on()) seg = (seg + c->fc_interval - 1) / c->fc_interval * c->fc_interval;
     ModeScope scope(c);                  // (the mode is restored on every return)
     Checkpoint ck(c, slab);
     bool guard = c->split();             // false in exact f32, from the start or after stepping down: no more checks

@@ -91,6 +91,7 @@ class GaussianDiffusion(nn.Module):
         self._lr = None                       # set_lr_consistency(): (fp32 [N,C,lh,lw], strength); not part of state_dict()
         self._start = None                    # set_start(): (strength | None, step | None, init, noised); not part of state_dict()
         self._dyn = None                      # set_dynamic_threshold(): (ratio, max_value | None); not part of state_dict()
+        self._fc = None                       # set_feature_cache(): (interval, depth); not part of state_dict()
 
     # ---- reference surface that is configuration only -----------------------------------------
     def set_loss(self, device=None):
@@ -260,6 +261,37 @@ class GaussianDiffusion(nn.Module):
         if getattr(eng, "_dyn_set", None) != want:
             eng.set_dynamic_threshold(*(want if want is not None else (None, None)))
             eng._dyn_set = want
+
+    def set_feature_cache(self, interval=None, depth: int = 1) -> None:
+        """Reuses the deep UNet features across the steps of every sampling entry point (DeepCache, Ma,
+        Fang, Wang 2023; training-free): only every `interval`-th step of a call runs the whole UNet (unet.py:235-265), the
+        steps between run its `depth` top resolution levels on the feature the deep part produced at the last whole step.
+        The sampler, the schedule, the noise draws and the weights stay what they are.
+
+          interval  an integer >= 1; None (or 1) turns the feature off: the sampler is then bit for bit what it was
+          depth     resolution levels kept fresh, an integer in [1, len(channel_mults) - 1]
+
+        It covers sample_batch, super_resolution*, refine and interpolate in every sampler (set_sampler, set_start), with
+        set_lr_consistency and set_dynamic_threshold. The first step of every call is whole, so chunks and shards, each a
+        call of its own, behave alike. The setting survives set_sampler and set_new_noise_schedule, adds nothing to
+        state_dict(), and leaves p_sample — the reference's single step — alone. Sample quality with it on a trained
+        checkpoint is not established here."""
+        n_levels = len(self.denoise_fn.cfg.channel_mults)
+        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 1 <= int(depth) <= n_levels - 1:
+            raise ValueError(f"depth must be an integer in [1, {n_levels - 1}] (resolution levels kept fresh), got {depth!r}")
+        if interval is None:
+            self._fc = None
+            return
+        if isinstance(interval, bool) or not isinstance(interval, (int, np.integer)) or int(interval) < 1:
+            raise ValueError(f"interval must be an integer >= 1 (None: off), got {interval!r}")
+        self._fc = (int(interval), int(depth)) if int(interval) > 1 else None
+
+    def _arm_fc(self, eng) -> None:
+        """Puts the engine's feature-cache setting in the state the next sampling call needs (next to _arm_dyn)."""
+        want = self._fc
+        if getattr(eng, "_fc_set", None) != want:
+            eng.set_feature_cache(*(want if want is not None else (None, 1)))
+            eng._fc_set = want
 
     def set_dropout_sampling(self, on: bool, seed: Optional[int] = None) -> None:
         """Opt in to sampling the UNet's Dropout as the reference does under .train() (unet.py:81-91; model 3 samples
@@ -432,6 +464,7 @@ class GaussianDiffusion(nn.Module):
             self.denoise_fn.ready()
             self._arm_lr(eng, dev, H, W, image_offset)
             self._arm_dyn(eng)
+            self._arm_fc(eng)
             run(x, B, out, noise, image_offset, frames, x_init)
             self.denoise_fn.finish()
             return (out, frames) if continous else out
@@ -457,6 +490,7 @@ class GaussianDiffusion(nn.Module):
             self.denoise_fn.ready()
             self._arm_lr(eng, dev, H, W, image_offset + a)
             self._arm_dyn(eng)
+            self._arm_fc(eng)
             run(xc, chunk, oc, nc, image_offset + a, fc, ic)
             self.denoise_fn.finish()
             if not whole:

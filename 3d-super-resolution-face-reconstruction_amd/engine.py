@@ -433,6 +433,22 @@ class Engine:
             b.free()
         return out
 
+    # ---- feature cache: deep UNet features reused across sampler steps ---------------
+    def set_feature_cache(self, interval: Optional[int] = None, depth: int = 1) -> None:
+        """While set (interval > 1), only every interval-th step of a sampling call runs the whole UNet; the steps between
+        run its `depth` top resolution levels on the deep feature of the last whole step (DeepCache; sr3_set_feature_cache).
+        interval None (or <= 1) turns it off. depth is 1 .. len(channel_mults) - 1."""
+        _lib.check(self.lib.sr3_set_feature_cache(self.ctx, 0 if interval is None else int(interval), int(depth)))
+
+    def feature_cache_steps(self) -> Tuple[int, int]:
+        """(whole, shallow) steps of the last sampling call, replayed ones included (sr3_feature_cache_steps)."""
+        w, s = C.c_int(0), C.c_int(0)
+        _lib.check(self.lib.sr3_feature_cache_steps(self.ctx, C.byref(w), C.byref(s)))
+        return int(w.value), int(s.value)
+
+    def unet_forward_cached(self, x_ptr: int, nl_ptr: int, B: int, H: int, W: int, depth: int, out_ptr: int) -> None:
+        _lib.check(self.lib.sr3_unet_forward_cached(self.ctx, x_ptr, nl_ptr, B, H, W, int(depth), out_ptr))
+
     # ---- train-mode Dropout (DESIGN.md §3.7) ---------------------------------------------------
     # ---- dynamic thresholding of the x0 prediction (DESIGN.md §3.5e) ------------------------------
     def set_dynamic_threshold(self, ratio: Optional[float] = None, max_value: Optional[float] = None) -> None:
@@ -822,6 +838,15 @@ class Engine:
         dx, dn = self.to_device(x), self.to_device(np.asarray(noise_level).ravel())
         out = self.buffer(B * self.cfg.out_channel * H * W)
         self.unet_forward(dx.ptr, dn.ptr, B, H, W, out.ptr)
+        return out.download((B, self.cfg.out_channel, H, W))
+
+    def unet_forward_cached_np(self, x, noise_level, depth: int = 1) -> np.ndarray:
+        """The shallow forward of `depth` on what the last unet_forward_np of the same shape left in the workspace."""
+        x = _host_f32(x)
+        B, _, H, W = x.shape
+        dx, dn = self.to_device(x), self.to_device(np.asarray(noise_level).ravel())
+        out = self.buffer(B * self.cfg.out_channel * H * W)
+        self.unet_forward_cached(dx.ptr, dn.ptr, B, H, W, depth, out.ptr)
         return out.download((B, self.cfg.out_channel, H, W))
 
     def sample_np(self, cond, noise=None, seed=0, image_offset=0, frames=False, shape=None, init=None, start_step=None,

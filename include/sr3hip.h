@@ -605,6 +605,31 @@ int sr3_op_dynamic_threshold(sr3_ctx *ctx, float *x0_dev, int B, int64_t n, floa
  * [projection] | update), one per step whether launched or replayed from a captured graph: tells a test which form ran. */
 int sr3_dynamic_threshold_launches(sr3_ctx *ctx);
 
+/* ---- feature cache: deep UNet features reused across sampler steps --------- */
+/* DeepCache (Ma, Fang, Wang 2023, "DeepCache: Accelerating Diffusion Models for Free"), training-free, beside the
+ * reference's UNet.forward (model/sr/sr3_modules/unet.py:235-265) and its sampling loop (diffusion.py:189-215): with
+ * interval N > 1, step k of a sampling call (k counts from sr3_sample_begin / sr3_sample_begin_from) runs the whole UNet
+ * when k % N == 0, and otherwise only its `depth` top resolution levels — conv_in and the down modules in front of the
+ * Downsample that leaves level depth - 1, then the up modules behind the Upsample that returns to it, then final_conv —
+ * on the output that Upsample had in the last whole step. The noise embedding, the noise draws, the update (every
+ * sampler, x0 history, projection, dynamic threshold) and the Dropout masks of the blocks that run are those of a whole
+ * step. interval <= 1 turns it off: the sampler is then bit for bit what it was. Fails for depth outside
+ * [1, n_mults - 1]. A step is whole regardless of k when the workspace does not hold a whole step of this call in the
+ * arithmetic the step runs in: after a new workspace, sr3_set_precision, a weight load or refresh, a step down of the
+ * range policy, or any forward from outside the call. With the cache on, sr3_sample's range guard checks after whole
+ * numbers of intervals, so a replayed segment starts with a whole step and repeats the same pattern. Sample quality is
+ * a property of the trained weights and is not established by this library. */
+int sr3_set_feature_cache(sr3_ctx *ctx, int interval, int depth);
+/* whole and shallow steps of the last sampling call (since its sr3_sample_begin*), replayed ones included */
+int sr3_feature_cache_steps(sr3_ctx *ctx, int *whole, int *shallow);
+/* The shallow forward of `depth` alone, as sr3_unet_forward takes its arguments (Dropout setting included): the skipped
+ * modules are what the most recent whole forward of the same (B, H, W) in the current arithmetic left in the workspace.
+ * Fails when there is none (never run, other shape, sr3_set_precision or a weight load since, or the range policy
+ * finished that forward in another arithmetic). Never steps the arithmetic down: a result out of range is an error
+ * that names the mode. */
+int sr3_unet_forward_cached(sr3_ctx *ctx, const float *x_dev, const float *noise_level_dev, int B, int H, int W, int depth,
+                            float *out_dev);
+
 /* ---- device memory helpers (so hosts without torch can drive the library) ---------------- */
 int sr3_dev_malloc(sr3_ctx *ctx, uint64_t bytes, void **out_dev);
 int sr3_dev_free(sr3_ctx *ctx, void *dev);
