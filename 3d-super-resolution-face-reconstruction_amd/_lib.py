@@ -91,6 +91,7 @@ PROTOTYPES = {
     "sr3_wino_gemm_out_launches": (_I, [_P]),
     "sr3_up2_wino_launches": (_I, [_P]),
     "sr3_wino_fused_rows_launches": (_I, [_P]),
+    "sr3_step_graph_captures": (_I, [_P]),
     "sr3_test_flag_address": (_P, [_P]),
     "sr3_last_warning": (C.c_char_p, []),
     "sr3_philox_normal": (_I, [_P, _U64, _U64, C.c_uint32, _I, _F]),
@@ -150,7 +151,7 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual",
                   "sr3_sample_begin_from", "sr3_sample_from", "sr3_num_frames_from", "sr3_op_conv_in", "sr3_op_final_conv",
                   "sr3_read_packed_state", "sr3_set_dynamic_threshold", "sr3_op_abs_quantile", "sr3_op_dynamic_threshold",
-                  "sr3_dynamic_threshold_launches", "sr3_set_feature_cache", "sr3_feature_cache_steps", "sr3_unet_forward_cached")
+                  "sr3_dynamic_threshold_launches", "sr3_set_feature_cache", "sr3_feature_cache_steps", "sr3_unet_forward_cached", "sr3_step_graph_captures")
 
 _lib = None
 

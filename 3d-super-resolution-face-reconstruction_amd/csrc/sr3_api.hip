@@ -116,6 +116,38 @@ enum Family { F_CONV = 0, F_GN = 1, F_ATTN = 2, F_EMBED = 3, F_MISC = 4 };
 struct ProfRec { int fam; hipEvent_t a, b; double flops; std::string tag; };
 struct ProfAgg { double ms = 0, flops = 0; int64_t n = 0; };
 
+// What a captured p_sample step is valid for (step_key builds it from the live context, once per step). The rule: a launch
+// argument that a capture bakes in and that can change without a new workspace or new weights is a member. Equal keys then
+// mean a valid graph, whatever was freed, reallocated or set in between (an address that comes back after a free holds
+// what the step expects again). The members of a feature that is off stay zero: "off" is one value. Everything else a
+// step bakes in (arena addresses, weight pointers and unscale scalars, the choice of kernels) is constant until
+// drop_graphs.
+struct StepKey {
+    int mode = 0;                   // Arith
+    int depth = 0;                  // feature cache: levels a shallow step keeps fresh, 0 = the whole step
+    bool lr = false, dyn = false;   // form of the update: plain | projection | dynamic threshold | both
+    float *x0hat = nullptr;         // lr || dyn
+    LrOps lr_ops;                   // lr
+    bool lr_lds = false;
+    float *lr_scratch = nullptr;    // lr && !lr_lds (the LDS form takes no scratch)
+    int64_t dyn_n = 0;              // dyn
+    ThrPlan dyn_plan;
+    float dyn_max = 0.f;
+    float *dyn_s = nullptr;
+    unsigned *dyn_bins = nullptr;
+
+    // one graph is kept per (arithmetic, whole | shallow, form): 24 at the most
+    bool same_slot(const StepKey &o) const { return mode == o.mode && (depth > 0) == (o.depth > 0) && lr == o.lr && dyn == o.dyn; }
+    auto tie() const {
+        return std::tie(mode, depth, lr, dyn, x0hat, lr_ops.Av, lr_ops.Ah, lr_ops.Pv, lr_ops.PhT, lr_ops.bv, lr_ops.bh, lr_ops.lh,
+                        lr_ops.lw, lr_ops.H, lr_ops.W, lr_lds, lr_scratch, dyn_n, dyn_plan.k, dyn_plan.k2, dyn_plan.frac,
+                        dyn_plan.blocks, dyn_max, dyn_s, dyn_bins);
+    }
+    bool operator==(const StepKey &o) const { return tie() == o.tie(); }
+};
+// warm: steps run eagerly under this key (the first sets one-time function attributes; the second is captured)
+struct StepGraph { StepKey key; hipGraphExec_t exec = nullptr; int warm = 0; };
+
 } // namespace
 
 struct sr3_ctx {
@@ -140,18 +172,11 @@ struct sr3_ctx {
     int c_max = 0;      // widest GroupNorm input
     uint64_t weight_bytes = 0;
     // The arithmetic of the 3x3 / activated-input convs (sr3_set_precision). Assigned by sr3_set_precision, step_down
-    // and ModeScope only; everything else asks the four questions below.
+    // and ModeScope only; everything else asks the three questions below (step_key and the feature cache record it).
     Arith mode = A_F32;
     bool split() const { return mode != A_F32; }        // split-f16 operands (f16x3 or f16f8)
     // "f16f8": the two correction products of eligible convs run on the fp8 matrix path (ConvParams::f8, conv_f8_supported)
     bool f8() const { return mode == A_F16F8; }
-    // which captured step graph: one per arithmetic, and per arithmetic one per form of the update (plain | with the
-    // consistency projection | with the dynamic threshold | with both)
-    // ... and all of those once more for the shallow step of the feature cache (kStepForms on)
-    static constexpr int kStepForms = 12;
-    int graph_slot(bool shallow = false) const {
-        return (int)mode + (lr_on() ? 3 : 0) + (dyn_on() ? 6 : 0) + (shallow ? kStepForms : 0);
-    }
     // split format of an activated conv input (launch_gn_apply's `split`): 0 fp32, 1 split-f16, 2 F8C when the consumer
     // conv takes the fp8 operands (f8_conv() said so)
     int act_format(bool f8_operand) const { return split() ? (f8_operand ? 2 : 1) : 0; }
@@ -200,7 +225,7 @@ struct sr3_ctx {
 
     // Low-resolution consistency (sr3_set_lr_consistency). Off by default: a step then launches exactly
     // the kernels it always did. lr: the host copy of what d_lr holds; lr_cur / lr_cur_lds: the operators and the form of
-    // the current sampling call (sr3_sample_begin), launch arguments of the captured steps 3..5.
+    // the current sampling call (sr3_sample_begin), launch arguments of the captured steps (StepKey).
     struct LrDev { float *buf = nullptr; int *bounds = nullptr; LrOps ops; };
     std::map<std::tuple<int, int, int, int>, LrDev> lr_ops;     // per (lh, lw, H, W), built on first use
     LrArgs lr;
@@ -218,7 +243,7 @@ struct sr3_ctx {
 
     // Dynamic thresholding of the x0 prediction (sr3_set_dynamic_threshold). Off by default (dyn_ratio 0):
     // a step then launches exactly the kernels it always did. dyn_plan: rank, weight and blocks of the current sampling
-    // call's n = out_channel * H * W (sr3_sample_begin), launch arguments of the captured steps 6..11 like dyn_max.
+    // call's n = out_channel * H * W (sr3_sample_begin), launch arguments of the captured steps like dyn_max (StepKey).
     float dyn_ratio = 0.f, dyn_max = INFINITY;
     ThrPlan dyn_plan;
     int64_t dyn_n = 0;
@@ -283,10 +308,11 @@ struct sr3_ctx {
     static constexpr int kRing = 256;
     StepArgs *h_ring = nullptr, *d_step = nullptr;
     uint64_t step_count = 0;
-    // one p_sample step captured as a hipGraph (per precision); rebuilt when the workspace changes
-    static constexpr int kGraphs = 2 * kStepForms;  // graph_slot(): per arithmetic (f32, f16x3, f16f8), form of the update, whole | shallow
-    hipGraphExec_t step_graph[kGraphs] = {};
-    int graph_warm[kGraphs] = {};
+    // p_sample steps captured as hipGraphs, each with the key it is valid for: step_impl looks its step's key up, and
+    // replaces the graph of the same slot (StepKey::same_slot) when the key differs. drop_graphs empties it: the workspace,
+    // the weights or the choice of kernels changed.
+    std::vector<StepGraph> step_graphs;
+    int step_graph_captures = 0;        // graphs instantiated by step_impl since sr3_create
     bool no_graph = false;
 
     // profiling
@@ -1438,12 +1464,11 @@ int check_ready(sr3_ctx *c) {
     return prepare_f8(c);
 }
 
+// every captured step: what the UNet body bakes in changed (StepKey covers the update half by itself)
 void drop_graphs(sr3_ctx *c) {
-    for (int i = 0; i < sr3_ctx::kGraphs; ++i) {
-        if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
-        c->step_graph[i] = nullptr;
-        c->graph_warm[i] = 0;
-    }
+    for (StepGraph &g : c->step_graphs)
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    c->step_graphs.clear();
 }
 
 // The per-call arguments kernels read from device memory (StepArgs): a pinned host ring slot, filled by the caller and
@@ -1511,25 +1536,6 @@ int push_drop_args(sr3_ctx *c, const char *what, uint64_t image_offset) {
 }
 
 // ---- low-resolution consistency: operators and buffers ---------------------------------------------------------------
-// the captured steps that hold x0hat: every form but the plain one (slots 3.. of the whole and of the shallow steps)
-void drop_lr_graphs(sr3_ctx *c) {
-    for (int i = 0; i < sr3_ctx::kGraphs; ++i) {
-        if (i % sr3_ctx::kStepForms < 3) continue;
-        if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
-        c->step_graph[i] = nullptr;
-        c->graph_warm[i] = 0;
-    }
-}
-// the captured steps with the dynamic threshold in them (slots 6.. of the whole and of the shallow steps)
-void drop_dyn_graphs(sr3_ctx *c) {
-    for (int i = 0; i < sr3_ctx::kGraphs; ++i) {
-        if (i % sr3_ctx::kStepForms < 6) continue;
-        if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
-        c->step_graph[i] = nullptr;
-        c->graph_warm[i] = 0;
-    }
-}
-
 int check_lr_shape(const char *what, int C, int H, int W, int N, int lh, int lw) {
     if (C <= 0 || N <= 0 || lh <= 0 || lw <= 0 || H <= lh || W <= lw)
         return fail("%s: needs C, N > 0 and an LR size below the image size on both axes (got C=%d N=%d, %dx%d -> %dx%d)", what, C,
@@ -1571,26 +1577,23 @@ int get_lr_ops(sr3_ctx *c, int lh, int lw, int H, int W, LrOps *out) {
     return 0;
 }
 
-// scratch of the multi-launch form / the residual score; a new allocation invalidates the captured steps that hold it
+// scratch of the multi-launch form / the residual score (a member of the StepKey of the steps that take it)
 int ensure_lr_scratch(sr3_ctx *c, size_t floats) {
     if (c->lr_scratch_n >= floats) return 0;
     HIP_OK(hipStreamSynchronize(c->stream));
     if (c->lr_scratch) HIP_OK(hipFree(c->lr_scratch));
     c->lr_scratch = nullptr; c->lr_scratch_n = 0;
-    drop_lr_graphs(c);
     HIP_OK(hipMalloc(&c->lr_scratch, floats * sizeof(float)));
     c->lr_scratch_n = floats;
     return 0;
 }
 
-// the x0 prediction between the halves of the update (projection and dynamic threshold share it); a new allocation
-// invalidates the captured steps that hold it
+// the x0 prediction between the halves of the update (projection and dynamic threshold share it; a member of the StepKey)
 int ensure_x0hat(sr3_ctx *c, size_t need) {
     if (c->x0hat_floats >= need) return 0;
     HIP_OK(hipStreamSynchronize(c->stream));
     if (c->x0hat) HIP_OK(hipFree(c->x0hat));
     c->x0hat = nullptr; c->x0hat_floats = 0;
-    drop_lr_graphs(c);
     HIP_OK(hipMalloc(&c->x0hat, need * sizeof(float)));
     c->x0hat_floats = need;
     return 0;
@@ -1600,30 +1603,23 @@ int ensure_x0hat(sr3_ctx *c, size_t need) {
 int prepare_lr_step(sr3_ctx *c, int B, int H, int W) {
     const int C = c->cfg.out_channel;
     if (check_lr_shape("sr3_sample_begin (low-resolution consistency)", C, H, W, c->lr.N, c->lr_lh, c->lr_lw)) return -1;
-    LrOps o;
-    if (get_lr_ops(c, c->lr_lh, c->lr_lw, H, W, &o)) return -1;
-    const bool lds = lr_lds_fits(o);
-    if (o.Av != c->lr_cur.Av || lds != c->lr_cur_lds) drop_lr_graphs(c);
-    c->lr_cur = o; c->lr_cur_lds = lds;
+    if (get_lr_ops(c, c->lr_lh, c->lr_lw, H, W, &c->lr_cur)) return -1;
+    c->lr_cur_lds = lr_lds_fits(c->lr_cur);
     if (ensure_x0hat(c, (size_t)B * C * H * W)) return -1;
-    return lds ? 0 : ensure_lr_scratch(c, lr_scratch_floats(B * C, o));
+    return c->lr_cur_lds ? 0 : ensure_lr_scratch(c, lr_scratch_floats(B * C, c->lr_cur));
 }
 
-// sr3_sample_begin with the dynamic threshold on: x0 buffer, s and the select's counts for B images of n values; a new
-// rank, block count or buffer invalidates the captured steps that hold it
+// sr3_sample_begin with the dynamic threshold on: x0 buffer, s and the select's counts for B images of n values (all
+// of them members of the StepKey)
 int prepare_dyn_step(sr3_ctx *c, int B, int H, int W) {
-    const int64_t n = (int64_t)c->cfg.out_channel * H * W;
-    const ThrPlan p = threshold_plan(c->dyn_ratio, n);
-    if (n != c->dyn_n || p.k != c->dyn_plan.k || p.k2 != c->dyn_plan.k2 || p.frac != c->dyn_plan.frac || p.blocks != c->dyn_plan.blocks)
-        drop_dyn_graphs(c);
-    c->dyn_n = n; c->dyn_plan = p;
-    if (ensure_x0hat(c, (size_t)B * n)) return -1;
+    c->dyn_n = (int64_t)c->cfg.out_channel * H * W;
+    c->dyn_plan = threshold_plan(c->dyn_ratio, c->dyn_n);
+    if (ensure_x0hat(c, (size_t)B * c->dyn_n)) return -1;
     if (c->dyn_rows < B) {
         HIP_OK(hipStreamSynchronize(c->stream));
         if (c->dyn_s) HIP_OK(hipFree(c->dyn_s));
         if (c->dyn_bins) HIP_OK(hipFree(c->dyn_bins));
         c->dyn_s = nullptr; c->dyn_bins = nullptr; c->dyn_rows = 0;
-        drop_dyn_graphs(c);
         HIP_OK(hipMalloc(&c->dyn_s, (size_t)B * sizeof(float)));
         HIP_OK(hipMalloc(&c->dyn_bins, threshold_bins_bytes(B)));
         c->dyn_rows = B;
@@ -1631,40 +1627,58 @@ int prepare_dyn_step(sr3_ctx *c, int B, int H, int W) {
     return 0;
 }
 
-// the launches of one p_sample step (embedding, UNet body, DDPM update); every per-step value is
-// read from c->d_step, so the sequence is identical for every t
-// depth > 0: the shallow step of the feature cache (run_unet_body); the update half is the same
-void enqueue_step(sr3_ctx *c, int depth = 0) {
-    const int B = c->wB, H = c->wH, W = c->wW;
-    // noise_level = float32(sqrt_alphas_cumprod_prev[t+1]) repeated over the batch (diffusion.py:166-167)
-    run_embed(c, &c->d_step->nl, 0, B);
-    run_unet_body(c, B, H, W, depth);
+// the key of a step of `depth` as the context stands (StepKey: the members of a feature that is off stay zero)
+StepKey step_key(const sr3_ctx *c, int depth) {
+    StepKey k;
+    k.mode = (int)c->mode; k.depth = depth; k.lr = c->lr_on(); k.dyn = c->dyn_on();
+    if (k.lr || k.dyn) k.x0hat = c->x0hat;
+    if (k.lr) {
+        k.lr_ops = c->lr_cur; k.lr_lds = c->lr_cur_lds;
+        if (!k.lr_lds) k.lr_scratch = c->lr_scratch;
+    }
+    if (k.dyn) { k.dyn_n = c->dyn_n; k.dyn_plan = c->dyn_plan; k.dyn_max = c->dyn_max; k.dyn_s = c->dyn_s; k.dyn_bins = c->dyn_bins; }
+    return k;
+}
+
+// The update half of a step. Launch arguments come from the workspace (u: constant until drop_graphs), from c->d_step
+// and c->d_lr (device memory written before every step / by the setter, at addresses that never change) and from the
+// key, NOT from the live context: what a capture bakes in is then what its key says. (c->lr travels as launch_lr_project's
+// `val`, which no kernel reads when `dyn` is given.)
+void enqueue_update(sr3_ctx *c, const StepKey &k) {
+    const int B = c->wB;
     UpdateParams u;
     u.state = c->x0; u.C = c->cfg.out_channel;
     u.packed = c->x0p;          // kept current in both arithmetic modes (the mode may change between steps)
     u.xoff = c->cfg.in_channel - c->cfg.out_channel;
     u.eps = c->eps;
     u.args = c->d_step;
-    u.ovf = c->split() ? c->d_ovf : nullptr;    // (the packed copy is only read in split-f16 mode)
+    u.ovf = k.mode != A_F32 ? c->d_ovf : nullptr;   // (the packed copy is only read in split-f16 mode)
     u.hist = c->xhist;                          // constant per workspace: the captured graph stays valid
     c->pbegin(F_MISC);
-    if (c->dyn_on()) {
-        // unclamped x0 prediction | per-image s and clamp(x0, -s, s) / s | [projection] | the rest
-        launch_x0_predict(u, c->x0hat, B, c->stream, false);
-        launch_abs_quantile(c->x0hat, B, c->dyn_n, c->dyn_plan, c->dyn_max, c->dyn_bins, nullptr, nullptr, c->dyn_s, c->stream);
-        launch_threshold_apply(c->x0hat, B, c->dyn_n, c->dyn_s, c->stream);
-        if (c->lr_on())
-            launch_lr_project(c->x0hat, B * u.C, u.C, c->lr_cur, c->lr, c->d_lr, c->lr_cur_lds, c->lr_scratch, c->stream);
-        launch_update_from_x0(u, c->x0hat, B, c->stream);
-    } else if (c->lr_on()) {
-        // x0 prediction | projection onto {x : A x = y} | the rest of the update
-        launch_x0_predict(u, c->x0hat, B, c->stream);
-        launch_lr_project(c->x0hat, B * u.C, u.C, c->lr_cur, c->lr, c->d_lr, c->lr_cur_lds, c->lr_scratch, c->stream);
-        launch_update_from_x0(u, c->x0hat, B, c->stream);
-    } else {
+    if (!k.lr && !k.dyn) {
         launch_ddpm_update(u, B, c->stream);
+    } else {
+        // x0 prediction, unclamped under the dynamic threshold | per-image s and clamp(x0, -s, s) / s |
+        // projection onto {x : A x = y} | the rest of the update
+        launch_x0_predict(u, k.x0hat, B, c->stream, !k.dyn);
+        if (k.dyn) {
+            launch_abs_quantile(k.x0hat, B, k.dyn_n, k.dyn_plan, k.dyn_max, k.dyn_bins, nullptr, nullptr, k.dyn_s, c->stream);
+            launch_threshold_apply(k.x0hat, B, k.dyn_n, k.dyn_s, c->stream);
+        }
+        if (k.lr) launch_lr_project(k.x0hat, B * u.C, u.C, k.lr_ops, c->lr, c->d_lr, k.lr_lds, k.lr_scratch, c->stream);
+        launch_update_from_x0(u, k.x0hat, B, c->stream);
     }
     c->pend();
+}
+
+// the launches of one p_sample step (embedding, UNet body, DDPM update); every per-step value is
+// read from c->d_step, so the sequence is identical for every t
+// k.depth > 0: the shallow step of the feature cache (run_unet_body); the update half is the same
+void enqueue_step(sr3_ctx *c, const StepKey &k) {
+    // noise_level = float32(sqrt_alphas_cumprod_prev[t+1]) repeated over the batch (diffusion.py:166-167)
+    run_embed(c, &c->d_step->nl, 0, c->wB);
+    run_unet_body(c, c->wB, c->wH, c->wW, k.depth);
+    enqueue_update(c, k);
 }
 
 int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
@@ -1708,26 +1722,37 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     ++c->fc_k;
     ++(shallow ? c->fc_shallow : c->fc_whole);
     if (!shallow) { c->fc_mode = (int)c->mode; c->fc_call = true; }
-    const int g = c->graph_slot(shallow);
+    const StepKey key = step_key(c, depth);
     if (c->prof || c->no_graph) {
-        enqueue_step(c, depth);
+        enqueue_step(c, key);
         return 0;
     }
-    if (!c->step_graph[g]) {
-        if (c->graph_warm[g] < 1) {          // first step runs eagerly (one-time function attributes)
-            ++c->graph_warm[g];
-            enqueue_step(c, depth);
+    StepGraph *g = nullptr;
+    for (StepGraph &e : c->step_graphs)
+        if (e.key.same_slot(key)) { g = &e; break; }
+    if (!g) {
+        c->step_graphs.push_back(StepGraph{key});
+        g = &c->step_graphs.back();
+    } else if (!(g->key == key)) {      // a baked-in value changed: as for a new key, one eager step and one capture
+        if (g->exec) (void)hipGraphExecDestroy(g->exec);
+        *g = StepGraph{key};
+    }
+    if (!g->exec) {
+        if (g->warm < 1) {          // first step runs eagerly (one-time function attributes)
+            ++g->warm;
+            enqueue_step(c, key);
             return 0;
         }
         hipGraph_t graph = nullptr;
         HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        enqueue_step(c, depth);
+        enqueue_step(c, key);
         HIP_OK(hipStreamEndCapture(c->stream, &graph));
-        hipError_t e = hipGraphInstantiate(&c->step_graph[g], graph, nullptr, nullptr, 0);
+        hipError_t e = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) return fail("hipGraphInstantiate: %s", hipGetErrorString(e));
+        ++c->step_graph_captures;
     }
-    HIP_OK(hipGraphLaunch(c->step_graph[g], c->stream));
+    HIP_OK(hipGraphLaunch(g->exec, c->stream));
     return 0;
 }
 
@@ -2421,14 +2446,6 @@ int sr3_set_feature_cache(sr3_ctx *c, int interval, int depth) {
     if (!c) return fail("null context");
     if (interval <= 1) { c->fc_interval = 0; return 0; }
     if (check_cache_depth(c, "sr3_set_feature_cache", depth)) return -1;
-    if (depth != c->fc_depth) {     // the captured shallow steps run the old depth
-        HIP_OK(hipSetDevice(c->device));
-        for (int i = sr3_ctx::kStepForms; i < sr3_ctx::kGraphs; ++i) {
-            if (c->step_graph[i]) (void)hipGraphExecDestroy(c->step_graph[i]);
-            c->step_graph[i] = nullptr;
-            c->graph_warm[i] = 0;
-        }
-    }
     c->fc_interval = interval; c->fc_depth = depth;
     return 0;
 }
@@ -2588,32 +2605,6 @@ int sr3_num_frames(sr3_ctx *c) {
     return sr3_num_frames_from(c, c->T);
 }
 
-int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_noise_dev,
-                     uint64_t seed, uint64_t image_offset) {
-    if (check_ready(c)) return -1;
-    if (c->T < 1) return fail("sr3_sample_begin: no schedule set (sr3_set_schedule)");
-    const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
-    if (cond_dev && nc <= 0) return fail("conditioning given but in_channel == out_channel");
-    if (!cond_dev && nc != 0) return fail("unconditional sampling needs in_channel == out_channel");
-    if (ensure_workspace(c, B, H, W)) return -1;
-    c->seed = seed;
-    c->image_offset = image_offset;
-    c->hist_valid = false;
-    c->fold_first = false;
-    c->fc_k = 0; c->fc_call = false; c->fc_whole = c->fc_shallow = 0;
-    if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
-    if (c->dyn_on() && prepare_dyn_step(c, B, H, W)) return -1;
-    if (range_reset(c)) return -1;
-    c->pbegin(F_MISC);
-    if (cond_dev) launch_nchw_to_nhwc(cond_dev, B, nc, c->x0, 0, c->stream);
-    launch_init_state(c->x0, nc, C, init_noise_dev, seed, image_offset, B, c->stream);
-    if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
-    c->pend();
-    c->sampling = true;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
 namespace {
 // float32 sqrt(1 - a^2) of q_sample (diffusion.py:281), every operation rounded by itself as noise_coefficient
 // (diffusion.py of this package) forms it: the product must not meet the difference in one fused multiply-add
@@ -2623,23 +2614,19 @@ float q_sample_noise_coefficient(float a) {
     const float d = 1.0f - aa;
     return sqrtf(d);
 }
-}
 
-int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_dev, int start_step,
-                          int noised, const float *noise0_dev, uint64_t seed, uint64_t image_offset) {
-    if (check_ready(c)) return -1;
-    if (c->T < 1) return fail("sr3_sample_begin_from: no schedule set (sr3_set_schedule)");
-    if (!init_dev) return fail("sr3_sample_begin_from: init_dev is null");
-    if (start_step < 1 || start_step > c->T)
-        return fail("sr3_sample_begin_from: start_step %d outside [1, %d]", start_step, c->T);
-    if (B < 1) return fail("sr3_sample_begin_from: bad batch B=%d", B);
+// What sr3_sample_begin (init_dev null) and sr3_sample_begin_from share behind their own argument checks: the workspace,
+// the per-call resets, the features' buffers and the first state. That state: q_sample(init) at the level of the state
+// before step start_step - 1 (noised) | init itself | without an init, the noise (noise0_dev, or null: Philox draw 0).
+int begin_impl(sr3_ctx *c, const char *what, const float *cond_dev, int B, int H, int W, const float *init_dev, int start_step,
+               bool noised, const float *noise0_dev, uint64_t seed, uint64_t image_offset) {
     const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
     if (cond_dev && nc <= 0) return fail("conditioning given but in_channel == out_channel");
     if (!cond_dev && nc != 0) return fail("unconditional sampling needs in_channel == out_channel");
-    if (init_dev == cond_dev && nc != C)
-        return fail("sr3_sample_begin_from: the conditioning image has %d channels and cannot start a state of %d", nc, C);
+    if (init_dev && init_dev == cond_dev && nc != C)
+        return fail("%s: the conditioning image has %d channels and cannot start a state of %d", what, nc, C);
     if (noised && c->cfg.in_channel > 8)
-        return fail("sr3_sample_begin_from: in_channel = %d, the state kernel builds at most 8 input channels", c->cfg.in_channel);
+        return fail("%s: in_channel = %d, the state kernel builds at most 8 input channels", what, c->cfg.in_channel);
     if (ensure_workspace(c, B, H, W)) return -1;
     if (noised && c->start_rows < B) {
         if (c->d_start) HIP_OK(hipFree(c->d_start));   // (hipFree waits for the kernels still reading it)
@@ -2650,7 +2637,6 @@ int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W
     c->seed = seed;
     c->image_offset = image_offset;
     c->hist_valid = false;
-    c->fold_first = true;
     c->fc_k = 0; c->fc_call = false; c->fc_whole = c->fc_shallow = 0;
     if (c->lr_on() && prepare_lr_step(c, B, H, W)) return -1;
     if (c->dyn_on() && prepare_dyn_step(c, B, H, W)) return -1;
@@ -2665,14 +2651,38 @@ int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W
         nz.noise = noise0_dev; nz.seed = seed; nz.image_offset = image_offset; nz.per_source = 0;
         launch_q_sample_state(init_dev, cond_dev, B, 0, a, s, nz, B, C, nc, c->x0, c->x0p, c->d_ovf, nullptr, c->stream);
     } else {
-        // the image itself, bit for bit (as Checkpoint::restore reloads a state)
+        // the image itself, bit for bit (as Checkpoint::restore reloads a state), or the start noise
         if (cond_dev) launch_nchw_to_nhwc(cond_dev, B, nc, c->x0, 0, c->stream);
-        launch_init_state(c->x0, nc, C, init_dev, seed, image_offset, B, c->stream);
+        launch_init_state(c->x0, nc, C, init_dev ? init_dev : noise0_dev, seed, image_offset, B, c->stream);
         if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
     }
     c->pend();
     c->sampling = true;
     HIP_OK(hipGetLastError());
+    return 0;
+}
+}
+
+int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_noise_dev,
+                     uint64_t seed, uint64_t image_offset) {
+    if (check_ready(c)) return -1;
+    if (c->T < 1) return fail("sr3_sample_begin: no schedule set (sr3_set_schedule)");
+    if (begin_impl(c, "sr3_sample_begin", cond_dev, B, H, W, nullptr, c->T, false, init_noise_dev, seed, image_offset)) return -1;
+    c->fold_first = false;
+    return 0;
+}
+
+int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_dev, int start_step,
+                          int noised, const float *noise0_dev, uint64_t seed, uint64_t image_offset) {
+    if (check_ready(c)) return -1;
+    if (c->T < 1) return fail("sr3_sample_begin_from: no schedule set (sr3_set_schedule)");
+    if (!init_dev) return fail("sr3_sample_begin_from: init_dev is null");
+    if (start_step < 1 || start_step > c->T)
+        return fail("sr3_sample_begin_from: start_step %d outside [1, %d]", start_step, c->T);
+    if (B < 1) return fail("sr3_sample_begin_from: bad batch B=%d", B);
+    if (begin_impl(c, "sr3_sample_begin_from", cond_dev, B, H, W, init_dev, start_step, noised != 0, noise0_dev, seed, image_offset))
+        return -1;
+    c->fold_first = true;
     return 0;
 }
 
@@ -2839,6 +2849,7 @@ int sr3_set_range_policy(sr3_ctx *c, int strict) {
 int sr3_fallback_calls(sr3_ctx *c) { return c ? c->fallback_calls : fail("null context"); }
 int sr3_gn_wino_passes(sr3_ctx *c) { return c ? c->gn_wino_passes : fail("null context"); }
 int sr3_wino_gemm_out_launches(sr3_ctx *c) { return c ? c->wino_gemm_out_launches : fail("null context"); }
+int sr3_step_graph_captures(sr3_ctx *c) { return c ? c->step_graph_captures : fail("null context"); }
 int sr3_up2_wino_launches(sr3_ctx *c) { return c ? c->up2_wino_launches : fail("null context"); }
 int sr3_dynamic_threshold_launches(sr3_ctx *c) { return c ? c->dyn_steps : fail("null context"); }
 int sr3_wino_fused_rows_launches(sr3_ctx *c) { return c ? c->wino_fused_rows_launches : fail("null context"); }
@@ -3436,7 +3447,7 @@ int sr3_metrics_psnr_ssim(sr3_ctx *c, const float *sr, const float *hr, int B, i
 // ---- low-resolution consistency --------------------------------------------------
 int sr3_set_lr_consistency(sr3_ctx *c, const float *lr_dev, int N, int lh, int lw, uint64_t row_offset, float strength) {
     if (!c) return fail("null context");
-    if (!lr_dev || strength == 0.f) {       // off: the steps launch what they always did (graphs 0..2)
+    if (!lr_dev || strength == 0.f) {       // off: the steps launch what they always did
         c->lr = LrArgs();
         return 0;
     }
@@ -3452,7 +3463,6 @@ int sr3_set_lr_consistency(sr3_ctx *c, const float *lr_dev, int N, int lh, int l
     a.lr = lr_dev; a.row_offset = row_offset; a.N = N; a.strength = strength;
     // the copy runs on the stream behind the steps enqueued so far, which still read the old values
     HIP_OK(hipMemcpyAsync(c->d_lr, &a, sizeof(LrArgs), hipMemcpyHostToDevice, c->stream));
-    if (lh != c->lr_lh || lw != c->lr_lw) drop_lr_graphs(c);        // the LR size is a launch argument of the captured steps
     c->lr = a; c->lr_lh = lh; c->lr_lw = lw;
     return 0;
 }
@@ -3531,8 +3541,6 @@ int sr3_set_dynamic_threshold(sr3_ctx *c, float ratio, float max_value) {
         return 0;
     }
     if (check_threshold_args("sr3_set_dynamic_threshold", ratio, max_value)) return -1;
-    // ratio (through the rank) and max_value are launch arguments of the captured steps
-    if (ratio != c->dyn_ratio || max_value != c->dyn_max) drop_dyn_graphs(c);
     c->dyn_ratio = ratio; c->dyn_max = max_value;
     return 0;
 }

@@ -171,6 +171,11 @@ class Engine:
         per block (the 32x32 and 16x16 levels); 0 under SR3_NO_WINO_FUSED_ROWS=1 and outside the f32 mode."""
         return int(self.lib.sr3_wino_fused_rows_launches(self.ctx))
 
+    def step_graph_captures(self) -> int:
+        """Sampler steps this engine captured into a graph since it was created: a step whose form and baked-in values
+        were seen before replays its graph and adds nothing; 0 under SR3_NO_GRAPH=1."""
+        return int(self.lib.sr3_step_graph_captures(self.ctx))
+
     def replay_calls(self) -> int:
         """Calls finished after replaying work whose in-place split-K wait had given up (SR3_OK_REPLAYED)."""
         return int(self.lib.sr3_replay_calls(self.ctx))

@@ -274,6 +274,10 @@ int sr3_up2_wino_launches(sr3_ctx *ctx);
  * 2 | 4 tile rows per block (the 32x32 and 16x16 levels; exact f32 only; 0 under SR3_NO_WINO_FUSED_ROWS=1): tells a test
  * which form ran. */
 int sr3_wino_fused_rows_launches(sr3_ctx *ctx);
+/* Sampler steps this context captured into a graph since sr3_create (successful instantiations; 0 under SR3_NO_GRAPH=1
+ * and while profiling): tells a test that a step was replayed from its graph, or captured anew because a value the graph
+ * holds had changed. */
+int sr3_step_graph_captures(sr3_ctx *ctx);
 /* TEST HOOK (tests/test_gpu_round4.py): device address of the context's flag word (bit 0: range overflow, bit 1: an
  * in-place split-K wait gave up), so that a test kernel on another stream can raise a bit in the middle of a running
  * sr3_sample call and the replay logic is exercised deterministically. Not for production use. */
