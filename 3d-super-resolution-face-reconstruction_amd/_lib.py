@@ -83,6 +83,13 @@ PROTOTYPES = {
     "sr3_sample_begin_from": (_I, [_P, _F, _I, _I, _I, _F, _I, _I, _F, _U64, _U64]),
     "sr3_sample_from": (_I, [_P, _F, _I, _I, _I, _F, _I, _I, _F, _U64, _U64, _F, _F]),
     "sr3_num_frames_from": (_I, [_P, _I]),
+    "sr3_rows_begin": (_I, [_P, _I, _I, _I, _U64]),
+    "sr3_rows_admit": (_I, [_P, _I, _F, _F, _I, _I, _F, _U64]),
+    "sr3_rows_step": (_I, [_P, C.POINTER(_F)]),
+    "sr3_rows_position": (_I, [_P, _I]),
+    "sr3_rows_retire": (_I, [_P, _I, _F]),
+    "sr3_rows_drop": (_I, [_P, _I]),
+    "sr3_rows_end": (_I, [_P]),
     "sr3_range_check": (_I, [_P]),
     "sr3_set_range_policy": (_I, [_P, _I]),
     "sr3_fallback_calls": (_I, [_P]),
@@ -151,7 +158,9 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_weight_unscale", "sr3_lr_operators_host", "sr3_set_lr_consistency", "sr3_op_lr_project", "sr3_lr_residual",
                   "sr3_sample_begin_from", "sr3_sample_from", "sr3_num_frames_from", "sr3_op_conv_in", "sr3_op_final_conv",
                   "sr3_read_packed_state", "sr3_set_dynamic_threshold", "sr3_op_abs_quantile", "sr3_op_dynamic_threshold",
-                  "sr3_dynamic_threshold_launches", "sr3_set_feature_cache", "sr3_feature_cache_steps", "sr3_unet_forward_cached", "sr3_step_graph_captures")
+                  "sr3_dynamic_threshold_launches", "sr3_set_feature_cache", "sr3_feature_cache_steps", "sr3_unet_forward_cached", "sr3_step_graph_captures",
+                  "sr3_rows_begin", "sr3_rows_admit", "sr3_rows_step", "sr3_rows_position", "sr3_rows_retire", "sr3_rows_drop",
+                  "sr3_rows_end")
 
 _lib = None
 

@@ -135,11 +135,15 @@ struct StepKey {
     float dyn_max = 0.f;
     float *dyn_s = nullptr;
     unsigned *dyn_bins = nullptr;
+    RowArgs *rows = nullptr;        // rolling batch (sr3_rows_step): the per-row argument table; null: the uniform step
 
-    // one graph is kept per (arithmetic, whole | shallow, form): 24 at the most
-    bool same_slot(const StepKey &o) const { return mode == o.mode && (depth > 0) == (o.depth > 0) && lr == o.lr && dyn == o.dyn; }
+    // one graph is kept per (arithmetic, whole | shallow, form): 24 at the most, and per (arithmetic, plain | dynamic
+    // threshold) of the rows form (always whole, never projected): 6 more. A rows step and a uniform one never share a slot.
+    bool same_slot(const StepKey &o) const {
+        return mode == o.mode && (depth > 0) == (o.depth > 0) && lr == o.lr && dyn == o.dyn && (rows != nullptr) == (o.rows != nullptr);
+    }
     auto tie() const {
-        return std::tie(mode, depth, lr, dyn, x0hat, lr_ops.Av, lr_ops.Ah, lr_ops.Pv, lr_ops.PhT, lr_ops.bv, lr_ops.bh, lr_ops.lh,
+        return std::tie(mode, depth, lr, dyn, rows, x0hat, lr_ops.Av, lr_ops.Ah, lr_ops.Pv, lr_ops.PhT, lr_ops.bv, lr_ops.bh, lr_ops.lh,
                         lr_ops.lw, lr_ops.H, lr_ops.W, lr_lds, lr_scratch, dyn_n, dyn_plan.k, dyn_plan.k2, dyn_plan.frac,
                         dyn_plan.blocks, dyn_max, dyn_s, dyn_bins);
     }
@@ -304,6 +308,18 @@ struct sr3_ctx {
     // sampler state
     uint64_t seed = 0, image_offset = 0;
     bool sampling = false;
+    // Rolling batch (sr3_rows_begin): a session of wB slots, each idle or at its own position. The host
+    // is authoritative: rows[r].pos steps are left for slot r (its next step is t = pos - 1). d_rows: the table the
+    // kernels read, rows_cap entries (grown on demand: its address is a member of the StepKey); h_rows: the pinned ring
+    // it is refreshed from, kRowRing slots of rows_cap entries.
+    struct RowState { bool live = false, hist_valid = false, fold = false; int pos = 0; uint64_t image = 0; };
+    bool rows_on = false;
+    std::vector<RowState> rows;
+    RowArgs *d_rows = nullptr, *h_rows = nullptr;
+    int rows_cap = 0;
+    static constexpr int kRowRing = 256;        // as kRing: the host synchronises every 128 steps
+    uint64_t rows_count = 0;
+    float *d_row_start = nullptr;       // a[rows_cap] | s[rows_cap]: q_sample coefficients of the rows admitted noised
     // per-step arguments: pinned host ring -> device struct (async copy before every step)
     static constexpr int kRing = 256;
     StepArgs *h_ring = nullptr, *d_step = nullptr;
@@ -1644,7 +1660,31 @@ StepKey step_key(const sr3_ctx *c, int depth) {
 // and c->d_lr (device memory written before every step / by the setter, at addresses that never change) and from the
 // key, NOT from the live context: what a capture bakes in is then what its key says. (c->lr travels as launch_lr_project's
 // `val`, which no kernel reads when `dyn` is given.)
+void enqueue_rows_update(sr3_ctx *c, const StepKey &k) {
+    const int B = c->wB;
+    RowsUpdateParams u;
+    u.state = c->x0; u.C = c->cfg.out_channel;
+    u.packed = c->x0p;
+    u.xoff = c->cfg.in_channel - c->cfg.out_channel;
+    u.eps = c->eps;
+    u.rows = k.rows;
+    u.ovf = k.mode != A_F32 ? c->d_ovf : nullptr;
+    u.hist = c->xhist;
+    c->pbegin(F_MISC);
+    if (!k.dyn) {
+        launch_rows_update(u, B, c->stream);
+    } else {
+        // (the threshold kernels run over all B rows: an idle row's slab of x0hat is zeros, s = 1, and is never used)
+        launch_rows_x0_predict(u, k.x0hat, B, c->stream, false);
+        launch_abs_quantile(k.x0hat, B, k.dyn_n, k.dyn_plan, k.dyn_max, k.dyn_bins, nullptr, nullptr, k.dyn_s, c->stream);
+        launch_threshold_apply(k.x0hat, B, k.dyn_n, k.dyn_s, c->stream);
+        launch_rows_update_from_x0(u, k.x0hat, B, c->stream);
+    }
+    c->pend();
+}
+
 void enqueue_update(sr3_ctx *c, const StepKey &k) {
+    if (k.rows) { enqueue_rows_update(c, k); return; }
     const int B = c->wB;
     UpdateParams u;
     u.state = c->x0; u.C = c->cfg.out_channel;
@@ -1675,13 +1715,23 @@ void enqueue_update(sr3_ctx *c, const StepKey &k) {
 // read from c->d_step, so the sequence is identical for every t
 // k.depth > 0: the shallow step of the feature cache (run_unet_body); the update half is the same
 void enqueue_step(sr3_ctx *c, const StepKey &k) {
+    if (k.rows) {
+        // every row's own level: the embedding over B rows, each conv reading its row of the FeatureWiseAffine biases
+        run_embed(c, &k.rows->nl, (int)(sizeof(RowArgs) / sizeof(float)), c->wB);
+        run_unet_body(c, c->wB, c->wH, c->wW, 0);
+        enqueue_update(c, k);
+        return;
+    }
     // noise_level = float32(sqrt_alphas_cumprod_prev[t+1]) repeated over the batch (diffusion.py:166-167)
     run_embed(c, &c->d_step->nl, 0, c->wB);
     run_unet_body(c, c->wB, c->wH, c->wW, k.depth);
     enqueue_update(c, k);
 }
 
+int launch_step(sr3_ctx *c, const StepKey &key);
+
 int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
+    if (c->rows_on) return fail("sr3_sample_step inside a row session (sr3_rows_begin): its rows move with sr3_rows_step");
     if (!c->sampling) return fail("sr3_sample_step before sr3_sample_begin");
     if (t < 0 || t >= c->T) return fail("step t=%d outside schedule of %d steps", t, c->T);
     // (the arithmetic mode may have been switched between steps: the F8C weight copies are made on demand)
@@ -1722,7 +1772,12 @@ int step_impl(sr3_ctx *c, int t, const float *noise_slab, float *frame) {
     ++c->fc_k;
     ++(shallow ? c->fc_shallow : c->fc_whole);
     if (!shallow) { c->fc_mode = (int)c->mode; c->fc_call = true; }
-    const StepKey key = step_key(c, depth);
+    return launch_step(c, step_key(c, depth));
+}
+
+// one step of `key`: replayed from its graph, or run eagerly (profiling, SR3_NO_GRAPH=1, the first step of a key) and
+// then captured
+int launch_step(sr3_ctx *c, const StepKey &key) {
     if (c->prof || c->no_graph) {
         enqueue_step(c, key);
         return 0;
@@ -1964,6 +2019,9 @@ void sr3_destroy(sr3_ctx *c) {
     if (c->h_ovf) (void)hipHostFree(c->h_ovf);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     if (c->d_step) (void)hipFree(c->d_step);
+    if (c->h_rows) (void)hipHostFree(c->h_rows);
+    if (c->d_rows) (void)hipFree(c->d_rows);
+    if (c->d_row_start) (void)hipFree(c->d_row_start);
     for (auto &kv : c->lr_ops) { (void)hipFree(kv.second.buf); (void)hipFree(kv.second.bounds); }
     if (c->d_lr) (void)hipFree(c->d_lr);
     if (c->h_lr) (void)hipHostFree(c->h_lr);
@@ -2404,7 +2462,7 @@ int sr3_unet_forward(sr3_ctx *c, const float *x_dev, const float *noise_level_de
     if (check_ready(c)) return -1;
     if (!x_dev || !noise_level_dev || !out_dev) return fail("sr3_unet_forward: null pointer");
     if (ensure_workspace(c, B, H, W)) return -1;
-    c->sampling = false;
+    c->sampling = false; c->rows_on = false;
     if (push_drop_args(c, "sr3_unet_forward", c->drop_offset)) return -1;
     c->fc_invalidate();
     // (each evaluation records its arithmetic: after a step down the workspace holds the features of the rung landed on)
@@ -2434,7 +2492,7 @@ int sr3_unet_forward_cached(sr3_ctx *c, const float *x_dev, const float *noise_l
         return fail("sr3_unet_forward_cached: the workspace holds no whole forward of B=%d H=%d W=%d in the current arithmetic "
                     "(run sr3_unet_forward at that shape first; a new shape, sr3_set_precision, a weight load and a forward "
                     "that the range policy finished in another arithmetic all discard it)", B, H, W);
-    c->sampling = false;
+    c->sampling = false; c->rows_on = false;
     c->fc_call = false;
     if (push_drop_args(c, "sr3_unet_forward_cached", c->drop_offset)) return -1;
     // (no step down: the deep features are those of this arithmetic; out of range is an error that names it)
@@ -2508,7 +2566,7 @@ int sr3_denoise_loss(sr3_ctx *c, const float *hr_dev, const float *cond_dev, int
         return fail("sr3_denoise_loss: in_channel = %d, the state kernel builds at most 8 input channels", c->cfg.in_channel);
     if (ensure_workspace(c, B, H, W)) return -1;
     if (ensure_partials(c, (size_t)B * loss_blocks(H, W))) return -1;
-    c->sampling = false;
+    c->sampling = false; c->rows_on = false;
     c->fc_invalidate();
     LossCall k;
     k.hr = hr_dev; k.cond = cond_dev; k.level = level_dev; k.s = s_dev;
@@ -2628,6 +2686,7 @@ int begin_impl(sr3_ctx *c, const char *what, const float *cond_dev, int B, int H
     if (noised && c->cfg.in_channel > 8)
         return fail("%s: in_channel = %d, the state kernel builds at most 8 input channels", what, c->cfg.in_channel);
     if (ensure_workspace(c, B, H, W)) return -1;
+    c->rows_on = false;         // (a sampling call during a row session takes the workspace over, as it does during a step session)
     if (noised && c->start_rows < B) {
         if (c->d_start) HIP_OK(hipFree(c->d_start));   // (hipFree waits for the kernels still reading it)
         c->d_start = nullptr; c->start_rows = 0;
@@ -2657,7 +2716,7 @@ int begin_impl(sr3_ctx *c, const char *what, const float *cond_dev, int B, int H
         if (c->x0p) launch_pack_state(c->x0, B, c->x0p, c->stream, c->d_ovf);
     }
     c->pend();
-    c->sampling = true;
+    c->sampling = true; c->rows_on = false;
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -2716,6 +2775,219 @@ int sr3_range_check(sr3_ctx *c) {
     if (!c) return fail("null context");
     HIP_OK(hipSetDevice(c->device));
     return range_check(c, "sr3_range_check");
+}
+
+
+// ---- rolling batch: every row at its own position -------------------------------------------------
+namespace {
+// one row of the workspace as a batch of its own: the existing one-batch kernels then admit and retire single rows
+TDesc row_desc(const TDesc &d, int row) {
+    TDesc r = d;
+    r.p = d.p + (size_t)row * d.Hp() * d.Wp() * d.C;
+    return r;
+}
+float *row_packed(sr3_ctx *c, int row) {
+    return c->x0p ? c->x0p + (size_t)row * (c->wH + 2) * (c->wW + 2) * 8 : nullptr;
+}
+
+int rows_check(sr3_ctx *c, const char *what, int row) {
+    if (!c) return fail("null context");
+    if (!c->rows_on || (int)c->rows.size() != c->wB) return fail("%s outside a row session (sr3_rows_begin)", what);
+    if (row < 0 || row >= c->wB) return fail("%s: row %d outside the session's %d slots", what, row, c->wB);
+    return 0;
+}
+
+// table, pinned ring and q_sample coefficients for B slots (their addresses change only when B outgrows them)
+int rows_reserve(sr3_ctx *c, int B) {
+    if (c->rows_cap >= B) return 0;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (c->h_rows) HIP_OK(hipHostFree(c->h_rows));
+    if (c->d_rows) HIP_OK(hipFree(c->d_rows));
+    if (c->d_row_start) HIP_OK(hipFree(c->d_row_start));
+    c->h_rows = nullptr; c->d_rows = nullptr; c->d_row_start = nullptr; c->rows_cap = 0;
+    HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&c->h_rows), sizeof(RowArgs) * sr3_ctx::kRowRing * B, hipHostMallocDefault));
+    HIP_OK(hipMalloc(&c->d_rows, sizeof(RowArgs) * B));
+    HIP_OK(hipMalloc(&c->d_row_start, sizeof(float) * 2 * B));
+    c->rows_cap = B;
+    return 0;
+}
+}
+
+int sr3_rows_begin(sr3_ctx *c, int B, int H, int W, uint64_t seed) {
+    if (check_ready(c)) return -1;
+    if (c->T < 1) return fail("sr3_rows_begin: no schedule set (sr3_set_schedule)");
+    if (B < 1) return fail("sr3_rows_begin: bad slot count B=%d", B);
+    if (c->cfg.in_channel - c->cfg.out_channel <= 0)
+        return fail("sr3_rows_begin: the unconditional model (in_channel == out_channel) has no per-request input to admit");
+    if (c->lr_on())
+        return fail("sr3_rows_begin: low-resolution consistency (sr3_set_lr_consistency) is on: its LR rows follow one image "
+                    "offset per call, not a row session; turn it off first");
+    if (c->fc_on())
+        return fail("sr3_rows_begin: the feature cache (sr3_set_feature_cache) is on: its whole and shallow steps are counted "
+                    "per call, not per row; turn it off first");
+    if (c->drop_live())
+        return fail("sr3_rows_begin: Dropout sampling (sr3_set_dropout) is on: its masks are keyed by one image offset and one "
+                    "draw per step; turn it off first");
+    if (ensure_workspace(c, B, H, W)) return -1;
+    c->sampling = false; c->rows_on = false;
+    if (rows_reserve(c, B)) return -1;
+    if (c->dyn_on() && prepare_dyn_step(c, B, H, W)) return -1;
+    c->seed = seed;
+    c->image_offset = 0;
+    c->hist_valid = false;
+    c->fc_invalidate();
+    c->rows.assign((size_t)B, sr3_ctx::RowState());
+    if (range_reset(c)) return -1;
+    // every slot idle and zero: an idle row still runs through the UNet, and must never carry a NaN or Inf into it
+    // (the borders and pad channels of the state are zero already and stay so)
+    HIP_OK(hipMemsetAsync(c->x0.p, 0, c->x0.floats(B) * sizeof(float), c->stream));
+    if (c->x0p) HIP_OK(hipMemsetAsync(c->x0p, 0, (size_t)B * (H + 2) * (W + 2) * 8 * sizeof(float), c->stream));
+    HIP_OK(hipMemsetAsync(c->xhist, 0, (size_t)B * c->cfg.out_channel * H * W * sizeof(float), c->stream));
+    c->rows_on = true;
+    return 0;
+}
+
+int sr3_rows_admit(sr3_ctx *c, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
+                   const float *noise0_dev, uint64_t image_id) {
+    if (rows_check(c, "sr3_rows_admit", row)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    if (!cond_dev) return fail("sr3_rows_admit: cond_dev is null");
+    sr3_ctx::RowState &r = c->rows[row];
+    if (r.live) return fail("sr3_rows_admit: slot %d is live (%d steps left); retire or drop it first", row, r.pos);
+    const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
+    if (init_dev ? (start_step < 1 || start_step > c->T) : start_step != c->T)
+        return fail("sr3_rows_admit: start_step %d outside [1, %d] (%d without init_dev)", start_step, c->T, c->T);
+    if (init_dev && init_dev == cond_dev && nc != C)
+        return fail("sr3_rows_admit: the conditioning image has %d channels and cannot start a state of %d", nc, C);
+    const bool q = init_dev && noised;
+    if (q && c->cfg.in_channel > 8)
+        return fail("sr3_rows_admit: in_channel = %d, the state kernel builds at most 8 input channels", c->cfg.in_channel);
+    const TDesc x0r = row_desc(c->x0, row);
+    float *xpr = row_packed(c, row);
+    c->pbegin(F_MISC);
+    if (q) {
+        // sr3_sample_begin_from's kernel on this row alone: the same expression, the same stores
+        const float level = c->s_nl[start_step];
+        float *a = c->d_row_start + row, *s = c->d_row_start + c->rows_cap + row;
+        launch_fill_pair(a, s, level, q_sample_noise_coefficient(level), 1, c->stream);
+        NoiseRef nz;
+        nz.noise = noise0_dev; nz.seed = c->seed; nz.image_offset = image_id; nz.per_source = 0;
+        launch_q_sample_state(init_dev, cond_dev, 1, 0, a, s, nz, 1, C, nc, x0r, xpr, c->d_ovf, nullptr, c->stream);
+    } else {
+        launch_nchw_to_nhwc(cond_dev, 1, nc, x0r, 0, c->stream);
+        launch_init_state(x0r, nc, C, init_dev ? init_dev : noise0_dev, c->seed, image_id, 1, c->stream);
+        if (xpr) launch_pack_state(x0r, 1, xpr, c->stream, c->d_ovf);
+    }
+    c->pend();
+    HIP_OK(hipGetLastError());
+    r = sr3_ctx::RowState();
+    r.live = true; r.pos = start_step; r.image = image_id;
+    r.fold = init_dev != nullptr;       // (as sr3_sample_begin_from: the first step of a multistep sampler is first order)
+    return 0;
+}
+
+int sr3_rows_step(sr3_ctx *c, const float *const *noise_rows) {
+    if (rows_check(c, "sr3_rows_step", 0)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    const int B = c->wB;
+    int live = 0;
+    for (const auto &r : c->rows) {
+        // (positions index the step tables: a schedule set after a row was admitted may be shorter)
+        if (r.live && r.pos > c->T) return fail("sr3_rows_step: a row has %d steps left and the schedule %d: the schedule was changed after sr3_rows_admit", r.pos, c->T);
+        live += (r.live && r.pos > 0) ? 1 : 0;
+    }
+    if (!live) return 0;
+    if (prepare_f8(c)) return -1;
+    if (c->lr_on() || c->fc_on() || c->drop_live())
+        return fail("sr3_rows_step: low-resolution consistency, the feature cache or Dropout sampling was turned on after sr3_rows_begin");
+    if (c->dyn_on()) {
+        const int64_t n = (int64_t)c->cfg.out_channel * c->wH * c->wW;
+        if (c->dyn_n != n || c->dyn_rows < B || c->x0hat_floats < (size_t)B * n || c->dyn_plan.k != threshold_plan(c->dyn_ratio, n).k)
+            return fail("sr3_rows_step: the dynamic threshold was turned on or changed after sr3_rows_begin; set it before");
+    }
+    // the host may run ahead of the GPU: never reuse a ring slot that may still be pending
+    if (c->rows_count && (c->rows_count % (sr3_ctx::kRowRing / 2)) == 0) HIP_OK(hipStreamSynchronize(c->stream));
+    RowArgs *slot = c->h_rows + (size_t)(c->rows_count % sr3_ctx::kRowRing) * c->rows_cap;
+    ++c->rows_count;
+    // the positions as they stand after this step: committed only once the step is enqueued, so that a failed call
+    // leaves the host where the device is
+    std::vector<sr3_ctx::RowState> next = c->rows;
+    for (int n = 0; n < B; ++n) {
+        sr3_ctx::RowState &r = next[n];
+        RowArgs ra = RowArgs();
+        ra.nl = c->s_nl[0];             // an idle row runs through the UNet at the level of a finished image
+        if (r.live && r.pos > 0) {
+            const int t = r.pos - 1;
+            ra.live = 1;
+            ra.nl = c->s_nl[t + 1];
+            ra.a = c->s_a[t]; ra.b = c->s_b[t]; ra.c1 = c->s_c1[t]; ra.c2 = c->s_c2[t]; ra.c3 = c->s_c3[t];
+            ra.sigma = c->s_sig[t];
+            if (r.fold && c->uses_hist && !r.hist_valid) ra.c1 = c->s_c1[t] + c->s_c3[t];
+            ra.draw = (uint32_t)(c->T - t);
+            ra.hist = c->uses_hist ? (r.hist_valid ? 2u : 1u) : 0u;
+            if (c->uses_hist) r.hist_valid = true;
+            ra.image = r.image; ra.seed = c->seed;
+            ra.noise = (noise_rows && t > 0) ? noise_rows[n] : nullptr;
+            --r.pos;
+        }
+        slot[n] = ra;
+    }
+    HIP_OK(hipMemcpyAsync(c->d_rows, slot, sizeof(RowArgs) * B, hipMemcpyHostToDevice, c->stream));
+    c->fc_invalidate();
+    StepKey key = step_key(c, 0);
+    key.rows = c->d_rows;
+    if (launch_step(c, key)) return -1;
+    if (const char *e = conv_take_error()) return fail("sr3_rows_step: %s", e);
+    if (c->prof) c->pflush();           // bound the number of live events
+    HIP_OK(hipGetLastError());
+    c->rows.swap(next);
+    if (c->dyn_on()) ++c->dyn_steps;
+    return live;
+}
+
+int sr3_rows_position(sr3_ctx *c, int row) {
+    if (rows_check(c, "sr3_rows_position", row)) return -2;
+    return c->rows[row].live ? c->rows[row].pos : -1;
+}
+
+int sr3_rows_retire(sr3_ctx *c, int row, float *out_dev) {
+    if (rows_check(c, "sr3_rows_retire", row)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    if (!out_dev) return fail("sr3_rows_retire: out_dev is null");
+    sr3_ctx::RowState &r = c->rows[row];
+    if (!r.live) return fail("sr3_rows_retire: slot %d is idle", row);
+    if (r.pos != 0) return fail("sr3_rows_retire: slot %d has %d steps left (sr3_rows_drop abandons a row)", row, r.pos);
+    const int C = c->cfg.out_channel;
+    c->pbegin(F_MISC);
+    launch_nhwc_to_nchw(row_desc(c->x0, row), c->cfg.in_channel - C, 1, C, out_dev, c->stream);
+    c->pend();
+    HIP_OK(hipGetLastError());
+    r = sr3_ctx::RowState();
+    return 0;
+}
+
+int sr3_rows_drop(sr3_ctx *c, int row) {
+    if (rows_check(c, "sr3_rows_drop", row)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    if (c->rows[row].live) {
+        // a row abandoned mid-trajectory may hold anything (an unclamped prediction, an injected slab): as an idle row it
+        // would go on running through the UNet and could keep raising the range flag. Back to the zeros of sr3_rows_begin
+        // (one row of the state is contiguous, borders and pad channels included: they are zero already).
+        const TDesc x0r = row_desc(c->x0, row);
+        HIP_OK(hipMemsetAsync(x0r.p, 0, x0r.floats(1) * sizeof(float), c->stream));
+        if (float *xpr = row_packed(c, row))
+            HIP_OK(hipMemsetAsync(xpr, 0, (size_t)(c->wH + 2) * (c->wW + 2) * 8 * sizeof(float), c->stream));
+    }
+    c->rows[row] = sr3_ctx::RowState();
+    return 0;
+}
+
+int sr3_rows_end(sr3_ctx *c) {
+    if (!c) return fail("null context");
+    if (!c->rows_on) return fail("sr3_rows_end outside a row session (sr3_rows_begin)");
+    c->rows_on = false;
+    c->rows.clear();
+    return 0;
 }
 
 namespace {

@@ -442,6 +442,35 @@ struct UpdateParams {
     float *hist = nullptr;  // NCHW [B][C][H][W] clamped x0 of the previous step (StepArgs::hist)
 };
 void launch_ddpm_update(const UpdateParams &p, int B, hipStream_t s);
+// ---- rolling batch: every row at its own position of the schedule (kernels_rows.hip) ----------------
+// What StepArgs holds once per step, once per batch ROW: a table of B entries in device memory at an address that is
+// constant per session size, refreshed from a pinned ring before every step (so one captured step serves every mix of
+// positions). The host stays authoritative for the positions; the device sees only the values of the step at hand.
+struct RowArgs {
+    uint32_t live;              // 0: idle slot — the update kernels neither read nor write this row
+    float nl;                   // noise level fed to the embedding (EmbedParams::noise_level points here, stride sizeof / 4)
+    float a, b, c1, c2, c3, sigma;  // as StepArgs, of this row's step
+    uint32_t draw;
+    uint32_t hist;              // as StepArgs::hist, of this row
+    uint64_t image;             // global image id of the Philox key
+    uint64_t seed;
+    const float *noise;         // this row's [C][HW] slab of the step, or null -> Philox
+};
+static_assert(sizeof(RowArgs) % sizeof(float) == 0, "RowArgs::nl is read with a stride in floats");
+struct RowsUpdateParams {
+    float *packed = nullptr;    // as UpdateParams
+    TDesc state;
+    int xoff = 0, C = 0;
+    TDesc eps;
+    const RowArgs *rows = nullptr;  // [B]
+    int *ovf = nullptr;
+    float *hist = nullptr;
+};
+// launch_ddpm_update / launch_x0_predict / launch_update_from_x0 with the row's arguments; bit for bit the same update
+// for a live row, nothing touched for an idle one (launch_rows_x0_predict writes zeros into an idle row's slab of x0hat)
+void launch_rows_update(const RowsUpdateParams &p, int B, hipStream_t s);
+void launch_rows_x0_predict(const RowsUpdateParams &p, float *x0hat, int B, hipStream_t s, bool clamp = true);
+void launch_rows_update_from_x0(const RowsUpdateParams &p, const float *x0hat, int B, hipStream_t s);
 // x <- noise (NCHW buffer or Philox draw 0) into state channels
 void launch_init_state(const TDesc &state, int xoff, int C, const float *noise, uint64_t seed,
                        uint64_t image_offset, int B, hipStream_t s);

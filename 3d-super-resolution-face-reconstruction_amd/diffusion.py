@@ -499,6 +499,45 @@ class GaussianDiffusion(nn.Module):
                 frames[:, a:b] = fc[:, : b - a]
         return (out, frames) if continous else out
 
+    def rolling(self, slots: Optional[int] = None, seed: Optional[int] = None, shape=None):
+        """A `rolling.RollingSampler` on this model: single-image requests served through `slots` batch
+        rows, each at its own position of the schedule, so a request takes a free slot while the others are mid-trajectory.
+        It uses the model's sampler (set_sampler), arithmetic, range policy and dynamic threshold as they stand now. Every
+        step runs at batch `slots`, so a request is byte for byte its row of a uniform call of `slots` images —
+        super_resolution_batch(x, seed=seed, image_offset=image_id)[0] with x of `slots` rows, or refine(...) with a
+        strength — whatever shared the batch and wherever it sat. Against a call at ANOTHER batch size (the B = 1 call, say)
+        it differs as any two batch sizes differ: the conv dispatch depends on the batch (fp32 round-off in f32 / f16x3,
+        1e-5 in f16f8, whose fp8 path runs only from 32 or 64 images on). slots None: min(64, the per-call limit at `shape` = (H, W), default
+        image_size). LR consistency, the feature cache and Dropout sampling do not follow single rows: the session
+        refuses them, naming the setting. Use as a context manager, or close() it."""
+        from .rolling import RollingSampler
+        if not self.conditional:
+            raise Sr3Error("rolling() needs a conditional model: the unconditional one has no per-request input")
+        if self._lr is not None:
+            raise Sr3Error("rolling(): set_lr_consistency is on and holds rows to one image offset per call; turn it off")
+        if self._fc is not None:
+            raise Sr3Error("rolling(): set_feature_cache is on and counts whole and shallow steps per call; turn it off")
+        if self.denoise_fn.dropout_live():
+            raise Sr3Error("rolling(): Dropout sampling (set_dropout_sampling) is on and keys its masks per call; turn it off")
+        eng = self._engine()
+        self.denoise_fn.arm_dropout(eng)
+        dev = next(self.denoise_fn.parameters()).device
+        self._arm_lr(eng, dev, 0, 0, 0)
+        self._arm_dyn(eng)
+        self._arm_fc(eng)
+        if slots is None:
+            H, W = shape if shape is not None else (self.image_size, self.image_size)
+            slots = min(64, eng.max_batch(int(H), int(W)))
+        C = self.channels
+
+        def alloc(r):
+            return torch.empty((C,) + tuple(r.cond.shape[-2:]), dtype=torch.float32, device=r.cond.device)
+
+        return RollingSampler(eng, int(slots), self.num_sampling_steps, self._draw_seed() if seed is None else int(seed),
+                              precision=getattr(eng, "precision", "f32"), strict=self.denoise_fn.strict_range,
+                              start_steps=lambda S, strength: self.start_steps(S, strength=strength), alloc=alloc,
+                              ready=self.denoise_fn.ready, finish=self.denoise_fn.finish)
+
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, noise=None, seed=None):
         """Reference return convention (diffusion.py:212-215): `ret_img` = cat([x_in, frames...])

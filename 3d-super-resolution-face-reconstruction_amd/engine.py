@@ -380,6 +380,56 @@ class Engine:
         """Raises Sr3Error if a split-f16 store left the fp16 range since the last check."""
         _lib.check(self.lib.sr3_range_check(self.ctx))
 
+    # ---- rolling batch: every row at its own position (DESIGN.md §3.5g) ---------------------------
+    def rows_begin(self, B: int, H: int, W: int, seed: int = 0) -> None:
+        """Opens a row session of B slots at H x W, all idle (sr3_rows_begin). Uses the sampler, arithmetic and dynamic
+        threshold set on the engine; refuses LR consistency, the feature cache and Dropout sampling. Every step runs at
+        batch B whatever is live: a row's result is that of its row in a uniform call of B images."""
+        _lib.check(self.lib.sr3_rows_begin(self.ctx, int(B), int(H), int(W), int(seed) & (2 ** 64 - 1)))
+        self._rows_slots = int(B)
+
+    def rows_admit(self, row: int, cond_ptr: int, image_id: int, init_ptr: Optional[int] = None,
+                   start_step: Optional[int] = None, noised: bool = True, noise0_ptr: Optional[int] = None) -> None:
+        """One request into idle slot `row` (sr3_rows_admit): cond [Cc,H,W]; init_ptr None: from the start noise at the
+        top; init [C,H,W] with start_step (None: S): the warm start, noised to noise_level[start_step] unless noised is
+        False. noise0: the start noise / the z of q_sample, [C,H,W] (None: Philox draw 0 of image_id)."""
+        if init_ptr is None and start_step is not None and int(start_step) != self.T:
+            raise ValueError("start_step needs init_ptr: the image the row starts from")
+        s0 = self.T if start_step is None else int(start_step)
+        _lib.check(self.lib.sr3_rows_admit(self.ctx, int(row), cond_ptr, init_ptr or None, s0, 1 if noised else 0,
+                                           noise0_ptr or None, int(image_id) & (2 ** 64 - 1)))
+
+    def rows_step(self, noise_ptrs: Optional[Sequence[Optional[int]]] = None) -> int:
+        """One step of every live row at its own position (sr3_rows_step); noise_ptrs: one device address (or None)
+        per slot, the [C,H,W] draw of that row's step. Returns the number of rows stepped (0: nothing was launched)."""
+        arr = None
+        if noise_ptrs is not None:
+            # (the library reads one entry per slot of the session)
+            if len(noise_ptrs) != getattr(self, "_rows_slots", -1):
+                raise ValueError(f"noise_ptrs needs one entry per slot of the session ({getattr(self, '_rows_slots', 0)}), "
+                                 f"got {len(noise_ptrs)}")
+            arr = (C.c_void_p * len(noise_ptrs))(*[p or None for p in noise_ptrs])
+        n = int(self.lib.sr3_rows_step(self.ctx, arr))
+        _lib.check(min(n, 0))
+        return n
+
+    def rows_position(self, row: int) -> int:
+        """Steps left for the slot, -1 for an idle one (sr3_rows_position)."""
+        n = int(self.lib.sr3_rows_position(self.ctx, int(row)))
+        if n < -1:
+            _lib.check(-1)
+        return n
+
+    def rows_retire(self, row: int, out_ptr: int) -> None:
+        """Copies a finished row to out [C,H,W] and frees its slot (sr3_rows_retire)."""
+        _lib.check(self.lib.sr3_rows_retire(self.ctx, int(row), out_ptr))
+
+    def rows_drop(self, row: int) -> None:
+        _lib.check(self.lib.sr3_rows_drop(self.ctx, int(row)))
+
+    def rows_end(self) -> None:
+        _lib.check(self.lib.sr3_rows_end(self.ctx))
+
     def philox_normal(self, seed: int, image: int, draw: int, n: int) -> np.ndarray:
         buf = self.buffer(n)
         _lib.check(self.lib.sr3_philox_normal(self.ctx, seed, image, draw, n, buf.ptr))
@@ -878,3 +928,71 @@ class Engine:
         if frames:
             return o, fr.download((nf, B, C_, H, W))
         return o
+
+    def rows_np(self, requests, slots: int, seed: int = 0, on_step=None):
+        """numpy convenience (tests): a whole row session. requests: dicts with cond [Cc,H,W], image_id, and optionally
+        at (the earliest session step the request may be admitted at, default 0), init [C,H,W] with start_step and
+        noised, noise [s0,C,H,W] (slab 0 the start noise / the z of q_sample, slab k the draw of step t = s0 - k) and
+        slot (a slot of its own; default: the lowest free one). A request enters once `at` steps have run and a slot is
+        free; finished rows retire after every step. on_step(k) runs after step k, with the session open (read-backs).
+        Returns (images in request order, trace): trace[k] = the request index per slot (None: idle) during step k."""
+        C_ = self.cfg.out_channel
+        H, W = np.asarray(requests[0]["cond"]).shape[-2:]
+        self.rows_begin(slots, H, W, seed)
+        keep, held = [], [None] * slots         # device buffers of the live rows; request index per slot
+        pos0 = [0] * slots
+        out = [None] * len(requests)
+        obuf = self.buffer(C_ * H * W)
+        waiting = list(range(len(requests)))
+        trace, k = [], 0
+        try:
+            while waiting or any(h is not None for h in held):
+                for i in list(waiting):
+                    rq = requests[i]
+                    if int(rq.get("at", 0)) > k:
+                        continue
+                    free = [s for s in range(slots) if held[s] is None]
+                    s = rq.get("slot", free[0] if free else None)
+                    if s is None or held[s] is not None:
+                        continue
+                    dc = self.to_device(rq["cond"])
+                    di = self.to_device(rq["init"]) if rq.get("init") is not None else None
+                    nz = _host_f32(rq["noise"]) if rq.get("noise") is not None else None
+                    dn = [self.to_device(z) for z in nz] if nz is not None else None
+                    s0 = int(rq.get("start_step", self.T)) if di is not None else self.T
+                    self.rows_admit(s, dc.ptr, rq["image_id"], di.ptr if di else None, s0 if di else None,
+                                    bool(rq.get("noised", True)), dn[0].ptr if dn else None)
+                    keep.append((dc, di, dn))
+                    held[s], pos0[s] = (i, dn), s0
+                    waiting.remove(i)
+                if all(h is None for h in held):    # nothing admissible yet: an empty step of the session clock
+                    assert self.rows_step() == 0
+                    trace.append([None] * slots)
+                    k += 1
+                    continue
+                ptrs = None
+                if any(h is not None and h[1] is not None for h in held):
+                    ptrs = []
+                    for s in range(slots):
+                        dn = held[s][1] if held[s] is not None else None
+                        p = self.rows_position(s)
+                        # slab index of step t = p - 1 in a run of pos0 steps: pos0 - t (none for t == 0)
+                        ptrs.append(dn[pos0[s] - (p - 1)].ptr if dn is not None and p > 1 else None)
+                self.rows_step(ptrs)
+                trace.append([h[0] if h is not None else None for h in held])
+                if on_step is not None:
+                    on_step(k)
+                k += 1
+                for s in range(slots):
+                    if held[s] is not None and self.rows_position(s) == 0:
+                        self.rows_retire(s, obuf.ptr)
+                        out[held[s][0]] = obuf.download((C_, H, W)).copy()
+                        held[s] = None
+        finally:
+            self.rows_end()
+            for dc, di, dn in keep:
+                for b in [dc, di] + (dn or []):
+                    if b is not None:
+                        b.free()
+            obuf.free()
+        return out, trace

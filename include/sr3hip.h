@@ -234,6 +234,47 @@ int sr3_sample_from(sr3_ctx *ctx, const float *cond_dev, int B, int H, int W, co
                     int noised, const float *noise_dev, uint64_t seed, uint64_t image_offset, float *out_dev,
                     float *frames_dev);
 int sr3_num_frames_from(sr3_ctx *ctx, int start_step);
+/* Rolling batch: a session of B slots in which every batch row sits at its OWN position of the schedule,
+ * so a request takes a free slot while the others are mid-trajectory and the batch stays full. No kernel mixes rows and
+ * Philox is keyed by (seed, image id, draw, element): a row's result is the bytes of its row in a sr3_sample /
+ * sr3_sample_from call of the SAME batch size B with the same image id and seed, whatever its slot, its neighbours and
+ * the moment it was admitted. Every step runs at batch B, and which conv kernels run depends on B (the fp8 path of mode 2
+ * only from 32 or 64 images on, the split-K forms): against a call at another batch size a row differs as any two batch
+ * sizes do, by fp32 round-off in modes 0 / 1 and at the 1e-5 level in mode 2. The update half of
+ * a step reads a per-row argument table (RowArgs, csrc/kernels_rows.hip); one captured graph serves every step of every
+ * session of a size. Sampler, schedule, arithmetic and dynamic threshold are the context's; there are no frames.
+ *   sr3_rows_begin     opens a session of B slots at H x W, all idle, the state zeroed (an idle row still runs through the
+ *                      UNet and is never written by the update). Fails, naming the setting, while low-resolution
+ *                      consistency, the feature cache or Dropout sampling is on, and for the unconditional model.
+ *   sr3_rows_admit     puts one request into idle slot `row`: cond_dev [in_channel - out_channel, H, W]; init_dev NULL: the
+ *                      start noise at the top (start_step must be S; noise0_dev [C, H, W] or NULL: Philox draw 0 of
+ *                      image_id); init_dev [C, H, W]: the warm start of sr3_sample_begin_from at start_step in [1, S] —
+ *                      noised != 0: q_sample at noise_level[start_step] with z = noise0_dev or Philox draw 0, bit for bit
+ *                      what sr3_sample_begin_from writes for that row; noised == 0: init itself. With a sampler that
+ *                      keeps an x0 history such a row's first step takes c1 + c3 as its c1, as there, per row; a slot's
+ *                      new occupant never reads the history of the previous one. Fails if the slot is live.
+ *   sr3_rows_step      one step of every live row at its own position (t = position - 1, Philox draw S - t), then those
+ *                      positions go down by one. noise_rows: NULL (Philox), or B host-side entries of device pointers,
+ *                      entry r the [C, H, W] draw of row r's step (read for live rows with t > 0 only). Returns the number
+ *                      of rows stepped, < 0 on error; 0 (nothing launched) when no row has a step left.
+ *   sr3_rows_position  steps left for the slot, -1 for an idle one, < -1 on error.
+ *   sr3_rows_retire    copies a finished row (0 steps left, else an error) to out_dev [C, H, W] and frees its slot; the
+ *                      state stays where it is and is not touched again until the slot is admitted into.
+ *   sr3_rows_drop      frees a slot at any point, nothing copied; the state of a live row goes back to zeros (it may hold
+ *                      anything mid-trajectory, and an idle row still runs through the UNet).
+ *   sr3_rows_end       closes the session.
+ * Range contract: the step API's. Nothing is replayed inside the library; sr3_range_check reports an activation beyond
+ * the operand range since the last check (the caller re-admits what was in flight, its requests being pure functions of
+ * seed, image id and init), and sr3_set_precision is allowed between steps. sr3_sample* and sr3_unet_forward during a
+ * session take the workspace over and end it, as they end a sr3_sample_begin session; sr3_sample_step fails. */
+int sr3_rows_begin(sr3_ctx *ctx, int B, int H, int W, uint64_t seed);
+int sr3_rows_admit(sr3_ctx *ctx, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
+                   const float *noise0_dev, uint64_t image_id);
+int sr3_rows_step(sr3_ctx *ctx, const float *const *noise_rows);
+int sr3_rows_position(sr3_ctx *ctx, int row);
+int sr3_rows_retire(sr3_ctx *ctx, int row, float *out_dev);
+int sr3_rows_drop(sr3_ctx *ctx, int row);
+int sr3_rows_end(sr3_ctx *ctx);
 /* Range check of the split-f16 arithmetic (sr3_set_precision(ctx, 1)): the reference computes in
  * fp32 (diffusion.py:164-180, unet.py:235-265) and has no such limit, so a value that does not fit
  * the hi + lo fp16 operand format (|v| > 65504, or a NaN) must never pass silently. Every kernel that stores
