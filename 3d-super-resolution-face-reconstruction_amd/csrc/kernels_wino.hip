@@ -151,8 +151,8 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const ConvParams p, co
 //     LDS, y = A^T t, then the direct kernel's epilogue order (bias, residual, FeatureWiseAffine bias), the store and the
 //     fused GroupNorm statistics (per tile in LDS, then per slice in tile order; spb slices per strip).
 // Registers: 4 positions x 2 N-fragments x 16 accumulators = 128, one ring of four B pairs (32, each refilled right
-// behind its MFMAs: see the K loop), two generations of window sums and one half-window landing area (48): 246 in
-// all, 2 waves per SIMD.
+// behind its MFMAs: see the K loop), two generations of window sums and one half-window landing area (48), the A operands
+// of two positions (8), the nine held DMA offsets: 238 in all, 2 waves per SIMD.
 // A 64-tile or 128-channel block doubles the accumulators (256: 1 wave per SIMD, nothing left for operands).
 // One input tensor only (conv_plan): the engine writes x || skip as one tensor in the GroupNorm apply pass.
 // Tile rows (R, as wino_up2_kernel): the block's 32 tiles are R tile rows of TPR = 32 / R tiles, R = 1 | 2 | 4 for widths
@@ -220,39 +220,51 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     const char *src0 = reinterpret_cast<const char *>(p.in0.p + pix0 * Cin);
 
     // LDS-DMA: wave a issues instructions i = a + 4m; lane -> pixel row 8i + (lane >> 3) of the stage (tile row, window
-    // row, column x: padded input row 2 * tile row + window row),
-    // stored chunk lane & 7 (offsets recomputed per K-step: a few VALU operations, no registers held across the loop).
+    // row, column x: padded input row 2 * tile row + window row), stored chunk lane & 7.
+    // The lane's byte offset of an instruction depends on lane, i, Wp and Cin only (the channel step c0 goes into the
+    // descriptor's base), so the nine offsets of the wave are computed once here and held across the K loop: dvoff[m] for
+    // i = a + 4m, dvoff[8] for the one from 32 on. Recomputed per K-step they cost 13 vector instructions each (a
+    // division by WF_WX, three 64-bit multiply-adds, the swizzle) beside the MFMAs, and the registers were held anyway
+    // (for the row index the arithmetic started from). one() pins the offset itself, so the compiler neither
+    // rematerialises it in the loop nor moves the arithmetic back in: a K-step issues its DMAs with no vector
+    // arithmetic in front of them.
     // Nothing in the K loop issues a vector memory instruction under a branch that the compiler cannot count: the
     // s_waitcnt vmcnt(N) it inserts assume the fewest loads in flight, so a skipped DMA makes every later wait one
-    // instruction stricter. A step with no next stage (on == false) sends its eight instructions past the end of the
-    // descriptor (no memory request; the free stage may receive zeros, which nobody reads); only the instructions
-    // from 32 on (m = 8; wave 0 alone at R = 1, waves 0 and 1 at R = 2, every wave at R = 4) sit behind a wave-uniform
-    // branch, one per wave, and they go first.
-    // Bit 31 of the lane offset is that switch and the descriptor ends at 2^31 - 1 bytes, so a live offset must stay
-    // below it: (3 Wp + 65) * Cin * 4 + 128 < 2^31, i.e. Wp * Cin < 1.7e8 (the widest row of the UNet: 130 * 384 = 5e4);
+    // instruction stricter. A step with no next stage (on == false) is wave-uniform and switches its instructions off
+    // in the descriptor: num_records = 0 puts every offset past its end (no memory request; the free stage may receive
+    // zeros, which nobody reads); only the instructions from 32 on (m = 8; wave 0 alone at R = 1, waves 0 and 1 at
+    // R = 2, every wave at R = 4) sit behind a wave-uniform branch, one per wave, and they go first.
+    // A live descriptor ends at 2^31 - 1 bytes, so a live offset must stay below it:
+    // (3 Wp + 65) * Cin * 4 + 128 < 2^31, i.e. Wp * Cin < 1.7e8 (the widest row of the UNet: 130 * 384 = 5e4);
     // R > 1: ((2R + 1) Wp + 2 TPR + 1) * Cin * 4 + 128, with Wp = 2 TPR + 2 <= 34 (conv_plan checks it).
-    auto issue = [&](int c0, int stage, bool on) {
-        const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(src0 + (size_t)c0 * 4), 0, 0x7fffffff, 0x00020000);
+    unsigned dvoff[9];
+    {
         const unsigned cs4 = (unsigned)Cin * 4u;
-        const unsigned off = on ? 0u : 0x80000000u;
-        float *dst = smem + stage * WF_STAGE;
-        auto one = [&](int i) {
-            int q = 8 * i + (lane >> 3);
-            asm volatile("" : "+v"(q));      // (kept in the loop: hoisted, the per-instruction offsets would be held in registers)
+        auto lane_off = [&](int i) {
+            const int q = 8 * i + (lane >> 3);
             const int wr = q / WF_WX, x = q - wr * WF_WX;
             const int r = R == 1 ? wr : 2 * (wr >> 2) + (wr & 3);
-            const unsigned voff =
-                ((unsigned)(r * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16)) | off;
+            return (unsigned)(r * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16);
+        };
+#pragma unroll
+        for (int m = 0; m < 8; ++m) dvoff[m] = lane_off(a + 4 * m);
+        dvoff[8] = lane_off(R == 1 ? 32 : 32 + a);       // (R > 1, a >= WF_DMA - 32: never issued)
+    }
+    auto issue = [&](int c0, int stage, bool on) {
+        const __amdgpu_buffer_rsrc_t rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(src0 + (size_t)c0 * 4), 0, on ? 0x7fffffff : 0, 0x00020000);
+        float *dst = smem + stage * WF_STAGE;
+        auto one = [&](int i, unsigned &voff) {
+            asm volatile("" : "+v"(voff));   // (held, not recomputed: see above)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst + i * 256), 16,
                                                      (int)voff, 0, 0, 0);
         };
         if constexpr (R == 1) {
-            if (a == 0 && on) one(32);
+            if (a == 0 && on) one(32, dvoff[8]);
         } else {
-            if (a < WF_DMA - 32 && on) one(32 + a);
+            if (a < WF_DMA - 32 && on) one(32 + a, dvoff[8]);
         }
-        wf_static_for<8>([&](auto mc) { one(a + 4 * decltype(mc)::value); });
+        wf_static_for<8>([&](auto mc) { constexpr int m = decltype(mc)::value; one(a + 4 * m, dvoff[m]); });
     };
 
     // B fragments: lane (li, h) loads channels c0 + 8kk + 4h .. +3 of output channel n0 + 32ni + li, position 4a + b,
@@ -307,6 +319,10 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     // barrier. The next stage's DMA goes between groups 2 and 3: every B load that a later MFMA of this step waits for
     // is older than it (vmcnt retires in order), and it has a group's time to land before the barrier that publishes
     // it. sched_barrier(0) after each position keeps the loads where they are written; the compiler places the waits.
+    // The A operands u of position b + 1 (the next group's position 0 after b = 3) are formed in front of the MFMAs of
+    // position b and pinned there, so no MFMA reads a register that the instruction before it wrote: formed right before
+    // their use, each u[j] cost the MFMA pair behind it a padded wait (32 s_nop per K-step, 5 now: those of a step's first
+    // position). Same sums, same operands, same order: the bits do not change.
     const int nk = Cin / 32;
     f32x4 bf[4][2];
     auto window = [&](const float *st, int kk, int x, f32x4 &d0, f32x4 &d1) {
@@ -330,12 +346,21 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
             window(st, 0, x, d0, d1);
             e[x] = d0 + sg * d1;
         }
+        f32x4 u = e[0] - e[2];
         wf_static_for<4>([&](auto kc) {
             constexpr int kk = decltype(kc)::value;
             f32x4 en[4], d0[2], d1[2];
             wf_static_for<4>([&](auto bc) {
                 constexpr int b = decltype(bc)::value;
-                const f32x4 u = b == 0 ? e[0] - e[2] : b == 1 ? e[1] + e[2] : b == 2 ? e[2] - e[1] : e[1] - e[3];
+                f32x4 un;
+                if constexpr (b == 0) un = e[1] + e[2];
+                if constexpr (b == 1) un = e[2] - e[1];
+                if constexpr (b == 2) un = e[1] - e[3];
+                if constexpr (b == 3 && kk < 3) {
+                    en[2] = d0[0] + sg * d1[0]; en[3] = d0[1] + sg * d1[1];
+                    un = en[0] - en[2];
+                }
+                if constexpr (b < 3 || kk < 3) asm volatile("" : "+v"(un));
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -348,8 +373,8 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
                         en[0] = d0[0] + sg * d1[0]; en[1] = d0[1] + sg * d1[1];
                         window(st, kk + 1, 2, d0[0], d1[0]); window(st, kk + 1, 3, d0[1], d1[1]);
                     }
-                    if constexpr (b == 3) { en[2] = d0[0] + sg * d1[0]; en[3] = d0[1] + sg * d1[1]; }
                 }
+                if constexpr (b < 3 || kk < 3) u = un;
                 __builtin_amdgcn_sched_barrier(0);
             });
             if constexpr (kk < 3) {
@@ -522,31 +547,43 @@ __global__ __launch_bounds__(256, 2) void wino_up2_kernel(const ConvParams p, in
     float add = p.bias ? p.bias[co] : 0.f;               // (the direct kernel's epilogue order: bias, FeatureWiseAffine bias)
     if (p.chan_bias) add += p.chan_bias[(size_t)n * p.chan_bias_stride + co];
 
+    // LDS-DMA: wave a issues instructions i = a + 4m, m = 0..8; lane -> pixel row 8i + (lane >> 3) of the stage
+    // (tile row, window row r, column x), stored chunk lane & 7. The lane's byte offsets depend on lane, i, Wp and Cin
+    // only (strip and channel step go into the descriptor's base), so they are computed once for all strips and K-steps
+    // and held (dvoff, pinned in issue() as in wino_fused_kernel). A live descriptor ends at 2^31 - 1 bytes and a live
+    // offset stays below it (conv_plan: (10 Wp + 70) * Cin * 4 < 2^31); an instruction past the stage's last
+    // (i >= NDMA, fixed per wave and m) holds an offset with bit 31 set, and a step with no next stage (on == false,
+    // wave-uniform) takes a descriptor with num_records = 0: either way the load is out of range and makes no memory
+    // request.
+    unsigned dvoff[9];
+    {
+        const unsigned cs4 = (unsigned)Cin * 4u;
+#pragma unroll
+        for (int m = 0; m < 9; ++m) {
+            const int i = a + 4 * m;
+            const int q = 8 * i + (lane >> 3);
+            const int wr = q / WX, x = q - wr * WX;
+            const int row = 2 * (wr >> 2) + (wr & 3);
+            const unsigned voff = (unsigned)(row * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16);
+            dvoff[m] = i < NDMA ? voff : 0x80000000u;
+        }
+    }
+
     const int nk = Cin / 32;
     for (int ss = 0; ss < nst; ++ss) {
         const int tj0 = (sj * nst + ss) * TPR;
         const size_t pix0 = ((size_t)n * p.in0.Hp() + 2 * ti0) * Wp + 2 * tj0;      // window origin of the block's first tile
         const char *src0 = reinterpret_cast<const char *>(p.in0.p + pix0 * Cin);
 
-        // LDS-DMA: wave a issues instructions i = a + 4m, m = 0..8; lane -> pixel row 8i + (lane >> 3) of the stage
-        // (tile row, window row r, column x), stored chunk lane & 7. Bit 31 of the lane offset switches an instruction
-        // off (on == false, or i >= NDMA) and the descriptor ends at 2^31 - 1 bytes, so a live offset stays below it
-        // (conv_plan: (10 Wp + 70) * Cin * 4 < 2^31).
         auto issue = [&](int c0, int stage, bool on) {
             const __amdgpu_buffer_rsrc_t rsrc =
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(src0 + (size_t)c0 * 4), 0, 0x7fffffff, 0x00020000);
-            const unsigned cs4 = (unsigned)Cin * 4u;
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(src0 + (size_t)c0 * 4), 0, on ? 0x7fffffff : 0, 0x00020000);
             float *dst = smem + stage * WU_STAGE;
             wf_static_for<9>([&](auto mc) {
-                const int i = a + 4 * decltype(mc)::value;
-                int q = 8 * i + (lane >> 3);
-                asm volatile("" : "+v"(q));      // (kept in the loop, as in wino_fused_kernel)
-                const int wr = q / WX, x = q - wr * WX;
-                const int row = 2 * (wr >> 2) + (wr & 3);
-                const unsigned off = (on && i < NDMA) ? 0u : 0x80000000u;
-                const unsigned voff = ((unsigned)(row * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16)) | off;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst + i * 256), 16,
-                                                         (int)voff, 0, 0, 0);
+                constexpr int m = decltype(mc)::value;
+                asm volatile("" : "+v"(dvoff[m]));   // (held, not recomputed: as in wino_fused_kernel)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst + (a + 4 * m) * 256),
+                                                         16, (int)dvoff[m], 0, 0, 0);
             });
         };
 

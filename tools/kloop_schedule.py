@@ -8,6 +8,10 @@ Reads the first loop marked "Inner Loop Header" of the named kernel, walks it th
 would (every LDS-DMA block entered, no skip or exit branch taken) and replays the in-order vmcnt counter: a load is
 covered by the first s_waitcnt vmcnt(N) that leaves at most N younger loads outstanding. Prints, for the middle
 walk, each load with the number of MFMAs between its issue and that wait, and where the s_barrier falls.
+Then a histogram of the middle walk's instructions by class: MFMA, fragment load, LDS-DMA, ds_read, s_nop, integer and
+float vector ALU (a v_ instruction whose name carries _f16 / _f32 / _f64 is float; moves, lane reads and everything else
+are integer), with the integer multiplies, lane reads and wait states of the s_nop (N + 1 each) spelled out, and the
+other scalar instructions in one figure.
 Needs no GPU; the listing is evidence for a reader, not a test.
 """
 import re
@@ -19,6 +23,8 @@ def main():
     lines = open(path).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*%s\w*:" % kernel, l))
     head = next(i for i in range(start, len(lines)) if "Inner Loop Header" in lines[i])
+    if not lines[head].startswith("."):          # a loop inside another: the label is on the line before
+        head -= 1
     label = lines[head].split(":")[0]
     end = next(i for i in range(head, len(lines)) if ".end_amdhsa_kernel" in lines[i] or "s_endpgm" in lines[i])
     back = max(i for i in range(head, end) if re.search(r"s_c?branch\w*\s+%s\b" % re.escape(label), lines[i]))
@@ -90,6 +96,48 @@ def main():
             continue
         kind, at, w, t = rows[key]
         print("%-4s %9d %10s %8s" % (kind, at - per_walk, "-" if w is None else w - per_walk, "-" if w is None else w - at))
+    histogram(kernel, [t for w, t in events if w == 1])
+
+
+def classify(t):
+    op = t.split()[0]
+    if op.startswith("v_mfma"):
+        return "MFMA"
+    if op.startswith(("buffer_load", "global_load", "flat_load")):
+        return "LDS-DMA" if t.endswith(" lds") else "fragment load"
+    if op.startswith("ds_read") or op.startswith("ds_load"):
+        return "ds_read"
+    if op == "s_nop":
+        return "s_nop"
+    if op.startswith("v_"):
+        return "float VALU" if re.search(r"_f(16|32|64)\b|_f(16|32|64)_", op) else "integer VALU"
+    if op.startswith("s_"):
+        return "other scalar"
+    return "other"
+
+
+def histogram(kernel, walk):
+    classes = ["MFMA", "fragment load", "LDS-DMA", "ds_read", "s_nop", "integer VALU", "float VALU", "other scalar", "other"]
+    n = dict.fromkeys(classes, 0)
+    ops = {}
+    nop_states = 0
+    for t in walk:
+        c = classify(t)
+        n[c] += 1
+        op = t.split()[0]
+        if c in ("integer VALU", "float VALU"):
+            ops[op] = ops.get(op, 0) + 1
+        if c == "s_nop":
+            nop_states += int(t.split()[1], 0) + 1
+    print("# %s: instructions of one K-step (wave 0, a middle step), by class" % kernel)
+    for c in classes:
+        if n[c] or c != "other":
+            print("%-14s %5d" % (c, n[c]))
+    print("%-14s %5d" % ("vector ALU", n["integer VALU"] + n["float VALU"]))
+    print("%-14s %5d" % ("s_nop states", nop_states))
+    print("# vector ALU by instruction")
+    for op in sorted(ops, key=lambda o: (-ops[o], o)):
+        print("  %-22s %4d" % (op, ops[op]))
 
 
 if __name__ == "__main__":
