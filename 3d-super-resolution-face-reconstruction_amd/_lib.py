@@ -116,6 +116,8 @@ PROTOTYPES = {
     "sr3_op_conv2d": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F]),
     "sr3_op_conv2d_stats": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F, _F, _U64,
                                 C.POINTER(_I)]),
+    "sr3_op_conv2d_fused": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _I, _F, _F, _F, _I, _F, _I, _F, _F, _I, _F, _F,
+                                _F, _U64, C.POINTER(_I)]),
     "sr3_op_conv_in": (_I, [_P, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F, _U64, C.POINTER(_I), _P]),
     "sr3_op_final_conv": (_I, [_P, _F, _I, _I, _I, _I, _F, _F, _F, _F, _I, _F, C.POINTER(_I)]),
     "sr3_read_packed_state": (C.c_int64, [_P, _F, _P, C.POINTER(_I)]),
@@ -123,6 +125,7 @@ PROTOTYPES = {
     "sr3_op_groupnorm_apply": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F,
                                    C.POINTER(_I), C.POINTER(_I)]),
     "sr3_op_attention": (_I, [_P, _F, _I, _I, _I, _F]),
+    "sr3_op_attention_twin": (_I, [_P, _F, _I, _I, _I, _F, _F, _I]),
     "sr3_op_attention_stream": (_I, [_P, _F, _I, _I, _I, _F]),
     "sr3_op_noise_embed": (_I, [_P, _F, _I, _F, _F]),
     "sr3_chan_bias_total": (_I, [_P]),
@@ -160,7 +163,7 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_read_packed_state", "sr3_set_dynamic_threshold", "sr3_op_abs_quantile", "sr3_op_dynamic_threshold",
                   "sr3_dynamic_threshold_launches", "sr3_set_feature_cache", "sr3_feature_cache_steps", "sr3_unet_forward_cached", "sr3_step_graph_captures",
                   "sr3_rows_begin", "sr3_rows_admit", "sr3_rows_step", "sr3_rows_position", "sr3_rows_retire", "sr3_rows_drop",
-                  "sr3_rows_end")
+                  "sr3_rows_end", "sr3_op_conv2d_fused", "sr3_op_attention_twin")
 
 _lib = None
 

@@ -1267,6 +1267,27 @@ int fused_host(Param &p) {
     return 0;
 }
 
+// The identity skip of a narrow block as extra K-steps of conv2 (ResBlock::ident_w): the split-f16 [cout][cout] matrix
+// with 2^k of conv2's split weights on the diagonal, for conv2's packed weights w ([9][cout][cin_pad], n floats, currently
+// split with w_unscale = 2^-k). The matrix holds 2^k as an fp16 number, so k <= 15 (2^16 is +inf in fp16 and the extra
+// K-steps would compute x * inf: NaN). conv2 tensors with max|w| < 2^-5 (k >= 16; e.g. PyTorch's default init of a
+// 128 -> 128 conv, bound 1/sqrt(1152)) are re-split with k = 15 into `resplit` (left empty otherwise): hi + lo then
+// still carries the weight to 2^-24 absolute in scaled units (fp16 subnormal spacing), far below the 2^-22 relative
+// accuracy of the format. Returns conv2's w_unscale to use from now on.
+float ident_skip_weights(const float *w, size_t n, int cout, int cin_pad, float w_unscale, std::vector<float> &resplit,
+                         std::vector<float> &ident) {
+    resplit.clear();
+    if (split_scale_exponent(w, n) > 15) {
+        resplit.resize(n);
+        w_unscale = split_conv_weight_k(w, (size_t)9 * cout, cin_pad, 15, resplit.data());
+    }
+    ident.assign((size_t)cout * cout, 0.f);
+    _Float16 *h = reinterpret_cast<_Float16 *>(ident.data());
+    const float v = 1.0f / w_unscale;                               // 2^k of conv2's split weights (k <= 15)
+    for (int o = 0; o < cout; ++o) h[((size_t)o * cout + (o & ~31)) * 2 + (o & 31)] = (_Float16)v;
+    return w_unscale;
+}
+
 int prepare_fused(sr3_ctx *c) {
     if (!c->fused_dirty) return 0;
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -1281,23 +1302,10 @@ int prepare_fused(sr3_ctx *c) {
         if (m.kind != M_RES || !ident_eligible(m.rb)) continue;
         ResBlock &rb = m.rb;
         const size_t n = (size_t)rb.cout * rb.cout;
-        std::vector<float> buf(n, 0.f);
-        _Float16 *h = reinterpret_cast<_Float16 *>(buf.data());
-        // The identity matrix holds 2^k as an fp16 number, so k <= 15 (2^16 is +inf in fp16 and the extra
-        // K-steps would compute x * inf: NaN). conv2 tensors with max|w| < 2^-5 (k >= 16; e.g. PyTorch's
-        // default init of a 128 -> 128 conv, bound 1/sqrt(1152)) are re-split with k = 15: hi + lo then
-        // still carries the weight to 2^-24 absolute in scaled units (fp16 subnormal spacing), far below
-        // the 2^-22 relative accuracy of the format.
         Param &w2 = c->params[rb.c2.w];
-        int k = split_scale_exponent(w2.host.data(), w2.host.size());
-        if (k > 15) {
-            k = 15;
-            std::vector<float> sp(w2.host.size());
-            w2.w_unscale = split_conv_weight_k(w2.host.data(), (size_t)9 * w2.cout, w2.cin_pad, k, sp.data());
-            HIP_OK(hipMemcpy(w2.dev_split, sp.data(), w2.dev_floats * sizeof(float), hipMemcpyHostToDevice));
-        }
-        const float v = 1.0f / w2.w_unscale;                        // 2^k of conv2's split weights (k <= 15)
-        for (int o = 0; o < rb.cout; ++o) h[((size_t)o * rb.cout + (o & ~31)) * 2 + (o & 31)] = (_Float16)v;
+        std::vector<float> buf, sp;
+        w2.w_unscale = ident_skip_weights(w2.host.data(), w2.host.size(), w2.cout, w2.cin_pad, w2.w_unscale, sp, buf);
+        if (!sp.empty()) HIP_OK(hipMemcpy(w2.dev_split, sp.data(), w2.dev_floats * sizeof(float), hipMemcpyHostToDevice));
         if (!rb.ident_w) HIP_OK(hipMalloc(&rb.ident_w, n * sizeof(float)));
         HIP_OK(hipMemcpy(rb.ident_w, buf.data(), n * sizeof(float), hipMemcpyHostToDevice));
     }
@@ -1836,6 +1844,14 @@ void fill_random(sr3_ctx *c, float *q, size_t n, int seed) {
     launch_philox_normal(seed, 0, 0, (int)std::min<size_t>(n, 1u << 30), q, c->stream);
 }
 
+// the weights of conv2's fused 1x1 term as run_res hands them over: a res_conv (w2_host: [Cout][C2], OIHW of a 1x1
+// conv), or — split-f16 arithmetics — the identity skip as extra K-steps (ident: ResBlock::ident_w)
+struct FusedTerm {
+    const float *w2_host = nullptr;
+    int C2 = 0;
+    bool ident = false;
+};
+
 // A single conv as the engine runs this shape: the plan of the shape with every buffer offered (fused statistics only
 // with `stats`: the caller then passes ConvParams::stats with the plan's stats_slices)
 // names the weight layouts and scratch buffers; p comes back with input, weights, partials and Winograd workspace
@@ -1843,13 +1859,15 @@ void fill_random(sr3_ctx *c, float *q, size_t n, int seed) {
 struct ScratchConv {
     ConvPlan plan;
     bool f8 = false;                // "f16f8" mode and the shape takes the F8C operand format
-    DevBuf act, w, wino_w, wino_wf, up_wino_w, wino_ws, part;
+    DevBuf act, w, w2, wino_w, wino_wf, up_wino_w, wino_ws, part;
     ConvParams p;
 
     // weight_host: OIHW weights, nullptr: random values (timing). The activated input `act` (zero-bordered, Cin
     // channels) is allocated and left for the caller to fill.
+    // fused (with weight_host): p.w2 in the layout and, in the split-f16 arithmetics, with the common weight scale
+    // prepare_fused gives the pair; p.in2 / p.in2b are the caller's.
     int setup(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout, int ks, int stride, int up2, const float *weight_host,
-              bool stats = false) {
+              bool stats = false, const FusedTerm *fused = nullptr) {
         const int Cin = C0 + C1;
         f8 = c->f8() && ks == 3 && stride == 1 && !up2 && conv_f8_supported(B, Hin, Win, Cout, Cin);
         plan = conv_plan_offered(B, Hin, Win, Cin, Cout, ks, stride, up2, c->split() ? 1 : 0, f8, stats);
@@ -1884,12 +1902,32 @@ struct ScratchConv {
                 }
                 if (wino_w.upload(wv.data(), n_wino)) return -1;
             }
+            std::vector<float> w2v;
+            if (fused && fused->w2_host) {
+                w2v.resize((size_t)Cout * fused->C2);
+                pack_conv_weight(fused->w2_host, Cout, fused->C2, 1, fused->C2, w2v.data());
+            }
             if (c->split()) {
                 tmp.resize(n_w);
-                p.w_unscale = split_conv_weight(packed.data(), n_w / Cin, Cin, tmp.data());
+                if (!w2v.empty()) {         // prepare_fused: conv2 and the res_conv share one 2^k
+                    const int k = std::min(split_scale_exponent(packed.data(), n_w), split_scale_exponent(w2v.data(), w2v.size()));
+                    p.w_unscale = split_conv_weight_k(packed.data(), n_w / Cin, Cin, k, tmp.data());
+                    std::vector<float> sp(w2v.size());
+                    split_conv_weight_k(w2v.data(), (size_t)Cout, fused->C2, k, sp.data());
+                    w2v.swap(sp);
+                } else {
+                    p.w_unscale = split_conv_weight(packed.data(), n_w / Cin, Cin, tmp.data());
+                    if (fused && fused->ident) {
+                        std::vector<float> sp;
+                        p.w_unscale = ident_skip_weights(packed.data(), n_w, Cout, Cin, p.w_unscale, sp, w2v);
+                        if (!sp.empty()) tmp.swap(sp);
+                    }
+                }
                 packed.swap(tmp);
             }
             if (w.upload(packed.data(), n_w)) return -1;
+            if (!w2v.empty() && w2.upload(w2v.data(), w2v.size())) return -1;
+            p.w2 = w2.p;
             if (f8) {
                 DevBuf w8;
                 if (w8.alloc(n_w)) return -1;
@@ -3234,13 +3272,24 @@ int sr3_profile_get(sr3_ctx *c, int family, double *total_ms, int64_t *launches,
 }
 
 // ---- single ops --------------------------------------------------------------------------------
-// sr3_op_conv2d (stats_dev == null) and sr3_op_conv2d_stats: one body. With statistics the plan is the one the engine's
-// convs get (fused statistics offered); a shape whose plan has none runs without them and reports 0 slices.
+// what sr3_op_conv2d_fused adds to sr3_op_conv2d_stats: the rest of the launch run_res builds for conv2
+struct FusedArgs {
+    const float *in2_dev = nullptr, *in2b_dev = nullptr;    // fp32 NHWC at the output pixels
+    int C2a = 0, C2b = 0;
+    const float *w2_host = nullptr, *b2_host = nullptr;     // [Cout][C2a + C2b], [Cout]
+    int flags = 0;                                          // SR3_FUSED_*
+    float *out_split_dev = nullptr;
+    bool any() const { return in2_dev || flags || out_split_dev; }
+};
+
+// sr3_op_conv2d (stats_dev == null), sr3_op_conv2d_stats and sr3_op_conv2d_fused (fa): one body. With statistics the plan
+// is the one the engine's convs get (fused statistics offered); a shape whose plan has none runs without them and reports
+// 0 slices.
 static int op_conv2d_impl(const char *what, sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int Hin,
                           int Win, const float *weight_host, const float *bias_host, int Cout, int ks, int stride,
                           int up2, const float *gn_scale_dev, const float *gn_shift_dev, int swish,
                           const float *chan_bias_dev, const float *resid_dev, float *out_dev, double *stats_dev,
-                          uint64_t stats_capacity_doubles, int *slices_out) {
+                          uint64_t stats_capacity_doubles, int *slices_out, const FusedArgs &fa = FusedArgs()) {
     if (!c || !in0_dev || !weight_host || !out_dev) return fail("%s: null argument", what);
     if ((C0 % 32) || (C1 % 32) || C0 <= 0 || C1 < 0) return fail("%s: C0=%d C1=%d must be multiples of 32", what, C0, C1);
     if (!(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (up2 & ~1)) return fail("%s: bad ks/stride/up2", what);
@@ -3248,14 +3297,57 @@ static int op_conv2d_impl(const char *what, sr3_ctx *c, const float *in0_dev, in
     if (up2 && (ks != 3 || stride != 1)) return fail("%s: up2 needs ks 3, stride 1", what);
     HIP_OK(hipSetDevice(c->device));
     if (!in1_dev) C1 = 0;
+    const bool ident = (fa.flags & SR3_FUSED_IDENT) != 0;
+    const int C2a = fa.in2_dev ? fa.C2a : 0, C2b = fa.in2b_dev ? fa.C2b : 0;
+    if (fa.any()) {
+        if (fa.flags & ~(SR3_FUSED_IDENT | SR3_FUSED_NO_F32 | SR3_FUSED_RESID_SPLIT)) return fail("%s: unknown flag in %d", what, fa.flags);
+        if ((fa.flags || fa.out_split_dev) && !c->split())
+            return fail("%s: the identity K-steps, the split twin, the twin-only output and a split residual exist in the "
+                        "split-f16 arithmetics only (sr3_set_precision 1 | 2)", what);
+        if ((fa.out_split_dev || (fa.flags & SR3_FUSED_RESID_SPLIT)) && (Cout % 32)) return fail("%s: the split format needs Cout %% 32 == 0 (Cout=%d)", what, Cout);
+        if ((fa.flags & SR3_FUSED_NO_F32) && !fa.out_split_dev) return fail("%s: no fp32 output and no twin: nothing to write", what);
+        if ((fa.flags & SR3_FUSED_RESID_SPLIT) && !resid_dev) return fail("%s: a split residual was announced, there is none", what);
+        if (fa.in2b_dev && !fa.in2_dev) return fail("%s: in2b without in2", what);
+        // the engine's fused_ok (run_res): the 1x1 K-steps read their operands in 32-channel chunks
+        if (fa.in2_dev && ((C2a % 32) || (C2b % 32) || C2a <= 0 || C2b < 0))
+            return fail("%s: C2a=%d C2b=%d must be multiples of 32", what, C2a, C2b);
+        if (ident) {
+            // ident_eligible + run_res: a narrow block that keeps its width, its input as the split operand
+            if (fa.w2_host || fa.in2b_dev || !fa.in2_dev) return fail("%s: the identity K-steps take in2 alone, and no 1x1 weights", what);
+            if (Cout > 128 || (Cout % 32) || C2a != Cout) return fail("%s: the identity K-steps need Cout <= 128, Cout %% 32 == 0 and C2a == Cout (Cout=%d C2a=%d)", what, Cout, C2a);
+        } else if ((fa.in2_dev != nullptr) != (fa.w2_host != nullptr)) {
+            return fail("%s: in2 and w2 go together", what);
+        }
+    }
+    FusedTerm ft;
+    ft.w2_host = fa.w2_host; ft.C2 = C2a + C2b; ft.ident = ident;
     ScratchConv sc;
-    if (sc.setup(c, B, Hin, Win, C0, C1, Cout, ks, stride, up2, weight_host, stats_dev != nullptr)) return -1;
-    DevBuf bias;
+    if (sc.setup(c, B, Hin, Win, C0, C1, Cout, ks, stride, up2, weight_host, stats_dev != nullptr, fa.in2_dev ? &ft : nullptr)) return -1;
+    DevBuf bias, in2s, in2bs;
+    std::vector<float> bsum;
+    if (fa.b2_host && fa.in2_dev && !ident) {       // prepare_fused: the two biases are pre-added
+        bsum.assign(fa.b2_host, fa.b2_host + Cout);
+        if (bias_host) for (int i = 0; i < Cout; ++i) bsum[i] = bias_host[i] + fa.b2_host[i];
+        bias_host = bsum.data();
+    }
     if (bias_host && bias.upload(bias_host, (size_t)Cout)) return -1;
     ConvParams &p = sc.p;
     p.bias = bias.p; p.chan_bias = chan_bias_dev; p.chan_bias_stride = Cout;
     p.out = unpadded(out_dev, Cout, p.Hout, p.Wout);
     if (resid_dev) p.resid = unpadded(const_cast<float *>(resid_dev), Cout, p.Hout, p.Wout);
+    p.resid_split = (fa.flags & SR3_FUSED_RESID_SPLIT) ? 1 : 0;
+    if (fa.out_split_dev) p.out_split = unpadded(fa.out_split_dev, Cout, p.Hout, p.Wout);
+    p.out_f32 = (fa.flags & SR3_FUSED_NO_F32) ? 0 : 1;
+    // the 1x1 operands at the output pixels: the fp32 tensors themselves in f32, copies in the plain split format (what a
+    // twin or run_res's raw1 holds, also under F8C) in the split-f16 arithmetics
+    const TDesc i2 = fa.in2_dev ? unpadded(const_cast<float *>(fa.in2_dev), C2a, p.Hout, p.Wout) : TDesc();
+    const TDesc i2b = C2b ? unpadded(const_cast<float *>(fa.in2b_dev), C2b, p.Hout, p.Wout) : TDesc();
+    p.in2 = i2; p.in2b = i2b;
+    if (c->split()) {
+        if (i2.p && in2s.alloc(i2.floats(B))) return -1;
+        if (i2b.p && in2bs.alloc(i2b.floats(B))) return -1;
+        p.in2.p = in2s.p; p.in2b.p = in2bs.p;
+    }
     if (stats_dev && sc.plan.stats_slices > 0) {
         const uint64_t need = (uint64_t)B * sc.plan.stats_slices * Cout * 2;
         if (stats_capacity_doubles < need)
@@ -3282,8 +3374,18 @@ static int op_conv2d_impl(const char *what, sr3_ctx *c, const float *in0_dev, in
         } else {
             launch_gn_apply(i0, i1, B, gn_scale_dev, gn_shift_dev, mode, c->act_format(sc.f8), p.in0, c->stream, TDesc(), 0, c->d_ovf);
         }
+        if (c->split() && i2.p) launch_gn_apply(i2, kNone, B, nullptr, nullptr, 0, 1, p.in2, c->stream, TDesc(), 0, c->d_ovf);
+        if (c->split() && i2b.p) launch_gn_apply(i2b, kNone, B, nullptr, nullptr, 0, 1, p.in2b, c->stream, TDesc(), 0, c->d_ovf);
         p.u_ready = to_u ? 1 : 0;
         p.no_halo_split = c->halo_split_off ? 1 : 0;
+        if (fa.any() && !p.no_halo_split) {
+            // the fused term, the twin and the residual's format change no plan: the launch is the 3x3 shape's
+            const ConvPlan run = conv_plan(p);
+            if (run.kernel != sc.plan.kernel || run.split != sc.plan.split || run.splits != sc.plan.splits ||
+                run.wino_gemm_out != sc.plan.wino_gemm_out || run.wino_fused_rows != sc.plan.wino_fused_rows)
+                return fail("%s: internal: the fused launch takes %s, the plan of the 3x3 shape names %s", what,
+                            conv_kernel_name(run.kernel), conv_kernel_name(sc.plan.kernel));
+        }
         ctx_launch_conv(c, p);
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("%s: launch failed", what);
         if (const char *e = conv_take_error()) return fail("%s: %s", what, e);
@@ -3308,6 +3410,21 @@ int sr3_op_conv2d_stats(sr3_ctx *c, const float *in0_dev, int C0, const float *i
     return op_conv2d_impl("sr3_op_conv2d_stats", c, in0_dev, C0, in1_dev, C1, B, Hin, Win, weight_host, bias_host, Cout, ks, stride,
                           up2, gn_scale_dev, gn_shift_dev, swish, chan_bias_dev, resid_dev, out_dev, stats_dev,
                           stats_capacity_doubles, slices_out);
+}
+
+int sr3_op_conv2d_fused(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int Hin, int Win,
+                        const float *weight_host, const float *bias_host, int Cout, const float *gn_scale_dev,
+                        const float *gn_shift_dev, int swish, const float *chan_bias_dev, const float *resid_dev,
+                        const float *in2_dev, int C2a, const float *in2b_dev, int C2b, const float *w2_host,
+                        const float *b2_host, int flags, float *out_dev, float *out_split_dev, double *stats_dev,
+                        uint64_t stats_capacity_doubles, int *slices_out) {
+    if (!stats_dev || !slices_out) return fail("sr3_op_conv2d_fused: null argument");
+    FusedArgs fa;
+    fa.in2_dev = in2_dev; fa.C2a = C2a; fa.in2b_dev = in2b_dev; fa.C2b = C2b;
+    fa.w2_host = w2_host; fa.b2_host = b2_host; fa.flags = flags; fa.out_split_dev = out_split_dev;
+    return op_conv2d_impl("sr3_op_conv2d_fused", c, in0_dev, C0, in1_dev, C1, B, Hin, Win, weight_host, bias_host, Cout, 3, 1, 0,
+                          gn_scale_dev, gn_shift_dev, swish, chan_bias_dev, resid_dev, out_dev, stats_dev, stats_capacity_doubles,
+                          slices_out, fa);
 }
 
 // ---- the edge convs (kernels_edge.hip) on scratch buffers: the forward's launchers, weight packers and gates ----
@@ -3536,30 +3653,44 @@ int sr3_op_groupnorm_apply(sr3_ctx *c, const float *in0_dev, int C0, const float
     return 0;
 }
 
-int sr3_op_attention(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev) {
-    if (!c || !qkv_dev || !out_dev) return fail("sr3_op_attention: null argument");
-    if (C % 32 || N < 1) return fail("sr3_op_attention: need C %% 32 == 0 and N >= 1");
+// sr3_op_attention (out_split_dev == null, fp32 on) and sr3_op_attention_twin: one body
+static int op_attention_impl(const char *what, sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev,
+                             float *out_split_dev, bool twin_call) {
+    if (C % 32 || N < 1) return fail("%s: need C %% 32 == 0 and N >= 1", what);
     const AttnCore core = attention_core(c->split(), N, C);
     if (core == ATTN_UNSUPPORTED)
-        return fail("sr3_op_attention: over 1024 tokens the streaming core takes at most 512 channels (C = %d)", C);
+        return fail("%s: over 1024 tokens the streaming core takes at most 512 channels (C = %d)", what, C);
+    if (twin_call && core != ATTN_SPLIT)
+        return fail("%s: the twin is written by the split-f16 core only (sr3_set_precision 1 | 2, N <= 512, C <= 512)", what);
     HIP_OK(hipSetDevice(c->device));
     if (core == ATTN_SPLIT) {
-        // split-f16 mode: the engine's own sequence — q, k, v in the split operand format, fp32 result
+        // split-f16 mode: the engine's own sequence — q, k, v in the split operand format, fp32 result and / or its twin
         float *tmp = nullptr;
         HIP_OK(hipMalloc(&tmp, ((size_t)B * N * 3 * C + attention_vt_floats(B, N, C)) * sizeof(float)));
         if (range_reset(c)) return -1;
         const TDesc src = unpadded(const_cast<float *>(qkv_dev), 3 * C, N, 1), dst = unpadded(tmp, 3 * C, N, 1);
         launch_gn_apply_rows(src, kNone, B, nullptr, nullptr, 0, 1, dst, c->stream, TDesc(), 0, c->d_ovf);
-        launch_attention_split(tmp, tmp + (size_t)B * N * 3 * C, B, N, C, out_dev, nullptr, c->d_ovf, c->stream);
+        launch_attention_split(tmp, tmp + (size_t)B * N * 3 * C, B, N, C, out_dev, out_split_dev, c->d_ovf, c->stream);
         HIP_OK(hipStreamSynchronize(c->stream));
         HIP_OK(hipFree(tmp));
         HIP_OK(hipGetLastError());
-        return range_check(c, "sr3_op_attention");
+        return range_check(c, what);
     }
     if (core == ATTN_STREAM) launch_attention_stream(qkv_dev, B, N, C, out_dev, c->stream);
     else launch_attention(qkv_dev, B, N, C, out_dev, c->stream);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+int sr3_op_attention(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev) {
+    if (!c || !qkv_dev || !out_dev) return fail("sr3_op_attention: null argument");
+    return op_attention_impl("sr3_op_attention", c, qkv_dev, B, N, C, out_dev, nullptr, false);
+}
+
+int sr3_op_attention_twin(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev, float *out_split_dev,
+                          int fp32_off) {
+    if (!c || !qkv_dev || !out_split_dev || (!out_dev && !fp32_off)) return fail("sr3_op_attention_twin: null argument");
+    return op_attention_impl("sr3_op_attention_twin", c, qkv_dev, B, N, C, fp32_off ? nullptr : out_dev, out_split_dev, true);
 }
 
 int sr3_op_attention_stream(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev) {

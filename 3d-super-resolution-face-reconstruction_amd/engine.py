@@ -744,6 +744,61 @@ class Engine:
         assert got.value == slices, (got.value, slices)
         return o, st.download().view(np.float64).reshape(B, slices, Cout, 2)
 
+    FUSED_SENTINEL = 0x7FC0FEED     # (a quiet NaN: what op_conv2d_fused fills `out` with before a twin-only call)
+
+    def op_conv2d_fused(self, x0, weight, bias=None, x1=None, gn_scale=None, gn_shift=None, swish=False, chan_bias=None,
+                        resid=None, in2=None, in2b=None, w2=None, b2=None, ident=False, twin=False, f32_out=True,
+                        resid_split=False) -> dict:
+        """The second launch of a ResnetBlock as the engine builds it (sr3_op_conv2d_fused): the 3x3 / stride 1 conv of
+        op_conv2d(..., return_stats=True) plus
+          in2 [B,H,W,C2a], in2b [B,H,W,C2b] (optional), w2 [Cout, C2a+C2b], b2 [Cout]: the res_conv as extra 1x1 K-steps;
+          ident=True (split-f16): in2 is the block input, added through the identity K-steps (no w2);
+          twin=True (split-f16): also the split-f16 twin of the output; f32_out=False: the twin alone;
+          resid_split=True: resid holds the uint32 words of the split format.
+        Returns a dict: out (float32 [B,H,W,Cout]; with f32_out=False the buffer as the call left it, filled with
+        FUSED_SENTINEL words before), twin (uint32 words [B,H,W,Cout] or None), stats (float64 [B, slices, Cout, 2], NaN
+        where no kernel wrote; None where the plan has none)."""
+        def words(a):
+            a = np.ascontiguousarray(a)
+            return a.view(np.float32) if a.dtype == np.uint32 else _host_f32(a)
+
+        x0 = _host_f32(x0)
+        B, H, W, C0 = x0.shape
+        C1 = 0 if x1 is None else x1.shape[-1]
+        weight = _host_f32(weight)
+        Cout, Cin, ks, _ = weight.shape
+        assert Cin == C0 + C1 and ks == 3
+        dev = lambda a: self.to_device(_host_f32(a)) if a is not None else None
+        ptr = lambda d: d.ptr if d is not None else None
+        host = lambda a: _host_f32(a) if a is not None else None
+        hptr = lambda a: a.ctypes.data if a is not None else None
+        d0, d1, dsc, dsh, dcb, d2, d2b = dev(x0), dev(x1), dev(gn_scale), dev(gn_shift), dev(chan_bias), dev(in2), dev(in2b)
+        drs = self.to_device(words(resid)) if resid is not None else None
+        C2a = 0 if in2 is None else in2.shape[-1]
+        C2b = 0 if in2b is None else in2b.shape[-1]
+        bh, w2h, b2h = host(bias), host(w2), host(b2)
+        if w2h is not None:
+            assert w2h.reshape(Cout, -1).shape == (Cout, C2a + C2b), w2h.shape
+        n = B * H * W * Cout
+        if f32_out:
+            out = self.buffer(n)
+        else:
+            out = self.to_device(np.full(n, self.FUSED_SENTINEL, dtype=np.uint32).view(np.float32))
+        tw = self.buffer(n) if twin else None
+        slices = self.conv_plan(B, H, W, Cin, Cout, 3, 1, 0, stats=True)["stats_slices"]
+        cap = max(1, B * slices * Cout * 2)
+        st = self.buffer(cap * 2)
+        got = C.c_int(-1)
+        flags = (1 if ident else 0) | (0 if f32_out else 2) | (4 if resid_split else 0)
+        _lib.check(self.lib.sr3_op_conv2d_fused(
+            self.ctx, d0.ptr, C0, ptr(d1), C1, B, H, W, weight.ctypes.data, hptr(bh), Cout, ptr(dsc), ptr(dsh),
+            1 if swish else 0, ptr(dcb), ptr(drs), ptr(d2), C2a, ptr(d2b), C2b, hptr(w2h), hptr(b2h), flags, out.ptr,
+            ptr(tw), st.ptr, cap, C.byref(got)))
+        assert got.value in (0, slices), (got.value, slices)
+        return {"out": out.download((B, H, W, Cout)),
+                "twin": tw.download((B, H, W, Cout)).view(np.uint32) if tw else None,
+                "stats": st.download().view(np.float64).reshape(B, slices, Cout, 2) if got.value else None}
+
     def op_conv_in(self, state, weight, bias=None, want_out=True, want_twin=True, want_stats=True) -> dict:
         """The UNet's first conv on the packed split-f16 state, as the split-f16 forward runs it (sr3_op_conv_in): state
         [B, H, W, Cin <= 8] fp32, weight OIHW [Cout, Cin, 3, 3]. Returns a dict: out (float32 [B, H, W, Cout]), twin (the
@@ -867,12 +922,21 @@ class Engine:
             b.ctypes.data, sc.ptr, sh.ptr))
         return sc.download((B, C)), sh.download((B, C))
 
-    def op_attention(self, qkv, streaming: bool = False) -> np.ndarray:
-        """streaming=True runs the online-softmax core at any N (otherwise it runs only above 1024 tokens)."""
+    def op_attention(self, qkv, streaming: bool = False, twin: bool = False, f32_out: bool = True):
+        """streaming=True runs the online-softmax core at any N (otherwise it runs only above 1024 tokens). twin=True
+        (split-f16 core only, sr3_op_attention_twin) returns (out, twin): twin the uint32 words of the split-f16 copy of the
+        result; f32_out=False writes the twin alone and returns (None, twin)."""
         qkv = _host_f32(qkv)
         B, N, C3 = qkv.shape
         d = self.to_device(qkv)
-        out = self.buffer(B * N * (C3 // 3))
+        n = B * N * (C3 // 3)
+        out = self.buffer(n) if f32_out else None
+        if twin:
+            assert not streaming
+            tw = self.buffer(n)
+            _lib.check(self.lib.sr3_op_attention_twin(self.ctx, d.ptr, B, N, C3 // 3, out.ptr if out else None, tw.ptr,
+                                                      0 if f32_out else 1))
+            return (out.download((B, N, C3 // 3)) if out else None), tw.download((B, N, C3 // 3)).view(np.uint32)
         fn = self.lib.sr3_op_attention_stream if streaming else self.lib.sr3_op_attention
         _lib.check(fn(self.ctx, d.ptr, B, N, C3 // 3, out.ptr))
         return out.download((B, N, C3 // 3))

@@ -418,6 +418,32 @@ int sr3_op_conv2d_stats(sr3_ctx *ctx, const float *in0_dev, int C0, const float 
                         const float *gn_shift_dev, int swish, const float *chan_bias_dev,
                         const float *resid_dev, float *out_dev, double *stats_dev,
                         uint64_t stats_capacity_doubles, int *slices_out);
+/* The SECOND launch of a ResnetBlock as the engine builds it (run_res): sr3_op_conv2d_stats for a 3x3 / stride 1 conv,
+ * plus the skip forms and output forms of that launch. The dispatch plan is the one sr3_conv_plan reports for the 3x3 shape
+ * with with_stats = 1: none of the following changes it.
+ *   in2_dev / in2b_dev, w2_host, b2_host   the res_conv (unet.py:102-103,110) as extra 1x1 K-steps: in2 [B,H,W,C2a] and
+ *               the optional in2b [B,H,W,C2b] (x and skip of torch.cat, unet.py:261) fp32 NHWC on the device, w2_host
+ *               [Cout, C2a+C2b] (OIHW of the 1x1 conv), b2_host NULL or [Cout]. The kernel gets what the engine prepares:
+ *               bias + b2; in f32 w2 as packed 1x1 weights; in the split-f16 arithmetics w and w2 split with one common
+ *               2^k and in2 / in2b copied into the plain split format. C2a and C2b must be multiples of 32.
+ *   flags & SR3_FUSED_IDENT       (split-f16 only; Cout <= 128; no w2, no in2b) in2 [B,H,W,Cout] is the block input and
+ *               the identity skip runs as extra K-steps against the engine's identity matrix (2^k on the diagonal, k the
+ *               exponent of w capped at 15, w re-split where the cap bites).
+ *   out_split_dev                 (split-f16 only, optional) the split-f16 twin of the output, [B,H,W,Cout] 32-bit words (per
+ *               32-channel chunk 32 hi halfs | 32 lo halfs); a value beyond the fp16 range is the "range" error.
+ *   flags & SR3_FUSED_NO_F32      only the twin is written; out_dev (still required) is left untouched.
+ *   flags & SR3_FUSED_RESID_SPLIT resid_dev holds split-format words (a residual that exists only as its twin).
+ * Any other combination is an error and launches nothing. (tests) */
+#define SR3_FUSED_IDENT 1
+#define SR3_FUSED_NO_F32 2
+#define SR3_FUSED_RESID_SPLIT 4
+int sr3_op_conv2d_fused(sr3_ctx *ctx, const float *in0_dev, int C0, const float *in1_dev, int C1, int B, int Hin,
+                        int Win, const float *weight_host, const float *bias_host, int Cout,
+                        const float *gn_scale_dev, const float *gn_shift_dev, int swish,
+                        const float *chan_bias_dev, const float *resid_dev, const float *in2_dev, int C2a,
+                        const float *in2b_dev, int C2b, const float *w2_host, const float *b2_host, int flags,
+                        float *out_dev, float *out_split_dev, double *stats_dev, uint64_t stats_capacity_doubles,
+                        int *slices_out);
 /* The UNet's first conv as the split-f16 forward runs it (unet.py:193-194 downs.0 on cat([cond, x_t]), diffusion.py:170):
  * the zero-bordered fp32 state is built from state_nchw_dev [B, Cin, H, W] (Cin <= 8) as sr3_unet_forward builds it,
  * packed by pack_state_kernel into [B][H+2][W+2] pixels of 16 halfs (channels 0..7 hi | channels 0..7 lo) and convolved by
@@ -480,6 +506,12 @@ int sr3_op_groupnorm_apply(sr3_ctx *ctx, const float *in0_dev, int C0, const flo
  * engine's cores for the precision mode run (32 x N score tile in LDS); above, the exact-f32 streaming
  * core (online softmax, C <= 512) runs in every mode. */
 int sr3_op_attention(sr3_ctx *ctx, const float *qkv_dev, int B, int N, int C, float *out_dev);
+/* sr3_op_attention in the split-f16 core with the output forms the forward uses: out_split_dev [B, N, C] 32-bit words
+ * receives the split-f16 twin of the result (a value beyond the fp16 range is the "range" error); fp32_off != 0: only
+ * the twin is written and out_dev (may be NULL then) is left untouched. Outside the split core (another arithmetic, or a
+ * shape it does not take) this is an error. (tests) */
+int sr3_op_attention_twin(sr3_ctx *ctx, const float *qkv_dev, int B, int N, int C, float *out_dev, float *out_split_dev,
+                          int fp32_off);
 /* The streaming core alone, at any N >= 1 (C a multiple of 32 in [32, 512]), whatever the precision
  * mode: for comparing it with the tiled core on the same shape. */
 int sr3_op_attention_stream(sr3_ctx *ctx, const float *qkv_dev, int B, int N, int C, float *out_dev);

@@ -131,24 +131,118 @@ def test_groupnorm_affine(eng, shape):
     np.testing.assert_allclose(got, want, atol=2e-5, rtol=0)
 
 
+def _attention64(qkv):
+    """softmax(q k^T / sqrt(C)) v per image in float64."""
+    C = qkv.shape[-1] // 3
+    q, k, v = (qkv[..., i * C:(i + 1) * C].astype(np.float64) for i in range(3))
+    s = np.einsum("bpc,bqc->bpq", q, k) / np.sqrt(C)
+    s = np.exp(s - s.max(-1, keepdims=True))
+    return np.einsum("bpq,bqc->bpc", s / s.sum(-1, keepdims=True), v)
+
+
+def _attn_images(B):
+    """large batches repeat three distinct images (first, middle and last differ): the float64 reference runs on three"""
+    idx = np.arange(B) % 3
+    idx[0], idx[B // 2], idx[-1] = 0, 1, 2
+    return idx
+
+
+# Which attention_split_kernel<NTW, NTC, MTQ, NWAVES, CH, KS> launch_attention_split picks in f16x3 (Np = N rounded up to
+# 32; big = Np % 64 == 0 and B * Np/64 >= 256 and ceil(Np/16 / 8) <= 2 and ceil(C/16 / 8) <= 4: 64 queries x 8 waves;
+# else 32 queries x 4 waves with ntw = ceil(Np/16 / 4) key tiles and ntc = ceil(C/16 / 4) channel tiles per wave):
+#   (2, 400, 64):   Np 416 (odd multiple of 32: not big), ntw 7, ntc 1 -> <8,8,2,4>, 7 key tiles per wave
+#   (3, 288, 96):   Np 288 (not big), ntw 5, ntc 2                     -> <8,8,2,4>, 5 key tiles per wave
+#   (1, 512, 512):  Np 512, 8 blocks of 64 (not big), ntw 8, ntc 8     -> <8,8,2,4>, 8 key tiles per wave
+#   (64, 256, 512): Np 256, 256 blocks of 64, 2 and 4 tiles per wave: big, C == 512 and Np == 256
+#                                                                      -> <2,4,4,8,16,8>, the unrolled config-3 form
+ATTN_REPEATED = [(64, 256, 512)]
+
+
 @pytest.mark.parametrize("prec", ["f32", "f16x3"])
 @pytest.mark.parametrize("B,N,C", [(2, 64, 512), (1, 256, 512), (3, 1, 64), (2, 4, 32), (2, 100, 64), (1, 16, 512),
-                                   (3, 256, 64), (1, 1024, 32), (64, 256, 64), (128, 128, 96)])
+                                   (3, 256, 64), (1, 1024, 32), (64, 256, 64), (128, 128, 96),
+                                   (2, 400, 64), (3, 288, 96), (1, 512, 512)] + ATTN_REPEATED)
 def test_attention(eng, B, N, C, prec):
-    """f32: f32-MFMA core; f16x3: the split-f16 core (q, k, v and the probabilities as hi + lo halfs); the last two
-    shapes have 256+ blocks of 64 queries: the 64-query x 8-wave form of the split core (BASELINE config 3 at B = 64)."""
+    """f32: f32-MFMA core; f16x3: the split-f16 core (q, k, v and the probabilities as hi + lo halfs); (64, 256, 64) and
+    (128, 128, 96) have 256+ blocks of 64 queries: the 64-query x 8-wave form of the split core (BASELINE config 3 at
+    B = 64). The last four shapes: see the table above."""
     rs = np.random.RandomState(B * 1000 + N + C)
-    qkv = _rand(rs, B, N, 3 * C)
+    if (B, N, C) in ATTN_REPEATED:
+        idx = _attn_images(B)
+        qd = _rand(rs, 3, N, 3 * C)
+        qkv = qd[idx]
+    else:
+        idx, qd = np.arange(B), None
+        qkv = _rand(rs, B, N, 3 * C)
     eng.set_precision(prec)
     try:
         got = eng.op_attention(qkv)
     finally:
         eng.set_precision("f32")
-    q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-    s = np.einsum("bpc,bqc->bpq", q, k).astype(np.float64) / np.sqrt(C)
-    s = np.exp(s - s.max(-1, keepdims=True))
-    want = np.einsum("bpq,bqc->bpc", s / s.sum(-1, keepdims=True), v)
+    if qd is not None:
+        want = _attention64(qd)[idx]
+    else:
+        q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+        s = np.einsum("bpc,bqc->bpq", q, k).astype(np.float64) / np.sqrt(C)
+        s = np.exp(s - s.max(-1, keepdims=True))
+        want = np.einsum("bpq,bqc->bpc", s / s.sum(-1, keepdims=True), v)
+    print(f"attention {prec} {(B, N, C)}: err {np.abs(got - want).max():.2e} (bar 2e-05)")
     np.testing.assert_allclose(got, want, atol=2e-5, rtol=0)
+
+
+# the instantiations of the split core by shape: <2,2,2,4>, <8,8,2,4>, <2,4,4,8,0,0> (big), <2,4,4,8,16,8> (config 3)
+ATTN_TWIN = [(2, 100, 64), (2, 400, 64), (64, 256, 64), (64, 256, 512)]
+
+
+@pytest.mark.parametrize("B,N,C", ATTN_TWIN)
+def test_attention_twin(eng, B, N, C):
+    """The out_split store of the split core, which the forward always uses (sr3_op_attention_twin): the twin is, bit for
+    bit, hi = fp16(out), lo = fp16(out - hi) of the call's own fp32 result, which is sr3_op_attention's; the twin-only
+    call writes the same twin."""
+    import gn_stats_ref as gn
+    rs = np.random.RandomState(B * 1000 + N + C + 1)
+    idx = _attn_images(B) if B > 3 else np.arange(B)
+    qkv = _rand(rs, int(idx.max()) + 1, N, 3 * C)[idx]
+    eng.set_precision("f16x3")
+    try:
+        plain = eng.op_attention(qkv)
+        out, twin = eng.op_attention(qkv, twin=True)
+        none, only = eng.op_attention(qkv, twin=True, f32_out=False)
+    finally:
+        eng.set_precision("f32")
+    assert np.array_equal(out.view(np.uint32), plain.view(np.uint32))
+    assert np.array_equal(twin, gn.pack_format(out, 1)), "the twin is not hi = fp16(out), lo = fp16(out - hi)"
+    assert none is None and np.array_equal(only, twin)
+
+
+def test_attention_twin_range(eng):
+    """A v scaled so that ONE output exceeds 65504 (checked on the CPU) is the "range" error, with and without the fp32
+    output. (An output is a convex combination of v rows, so such a v is itself beyond the range of the split operand
+    format: the pass that writes q, k, v raises the flag as well, and the plain call fails the same way.) Outside the
+    split core the twin is refused."""
+    Sr3Error = pkg("_lib").Sr3Error
+    B, N, C = 2, 100, 64
+    rs = np.random.RandomState(17)
+    qkv = _rand(rs, B, N, 3 * C)
+    qkv[1, 37, :C] = qkv[1, 11, C:2 * C] * 4           # query 37 of image 1 looks at key 11 ...
+    qkv[1, 11, 2 * C + 9] = 2e5                        # ... whose v is huge in channel 9
+    want = _attention64(qkv)
+    over = np.abs(want) > 65504
+    assert over[1, 37, 9] and over.sum() == 1 and np.abs(want[~over]).max() < 6e4, (over.sum(), np.abs(want[~over]).max())
+    with pytest.raises(Sr3Error, match="split-f16 core"):
+        eng.op_attention(qkv, twin=True)               # f32 mode
+    eng.set_precision("f16x3")
+    try:
+        for kw in ({"twin": True}, {"twin": True, "f32_out": False}, {}):
+            with pytest.raises(Sr3Error, match="range"):
+                eng.op_attention(qkv, **kw)
+        with pytest.raises(Sr3Error, match="split-f16 core"):
+            eng.op_attention(_rand(rs, 1, 600, 3 * 32), twin=True)      # N > 512: the f32 tile core
+        qkv[1, 11, 2 * C + 9] = 1.0                    # (the flag does not outlive the failed calls)
+        out, twin = eng.op_attention(qkv, twin=True)
+    finally:
+        eng.set_precision("f32")
+    np.testing.assert_allclose(out, _attention64(qkv), atol=2e-5, rtol=0)
 
 
 def test_attention_peaked_softmax(eng):
