@@ -98,6 +98,10 @@ PROTOTYPES = {
     "sr3_wino_gemm_out_launches": (_I, [_P]),
     "sr3_up2_wino_launches": (_I, [_P]),
     "sr3_wino_fused_rows_launches": (_I, [_P]),
+    "sr3_gn_res1x1_launches": (_I, [_P]),
+    "sr3_gn_res1x1_gate": (_I, [_I] * 9),
+    "sr3_op_gn_res1x1": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _I, C.c_float, _F, _F, _F]),
+    "sr3_bench_gn_res1x1": (_I, [_P] + [_I] * 8 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_I)]),
     "sr3_step_graph_captures": (_I, [_P]),
     "sr3_test_flag_address": (_P, [_P]),
     "sr3_last_warning": (C.c_char_p, []),
@@ -163,7 +167,8 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_read_packed_state", "sr3_set_dynamic_threshold", "sr3_op_abs_quantile", "sr3_op_dynamic_threshold",
                   "sr3_dynamic_threshold_launches", "sr3_set_feature_cache", "sr3_feature_cache_steps", "sr3_unet_forward_cached", "sr3_step_graph_captures",
                   "sr3_rows_begin", "sr3_rows_admit", "sr3_rows_step", "sr3_rows_position", "sr3_rows_retire", "sr3_rows_drop",
-                  "sr3_rows_end", "sr3_op_conv2d_fused", "sr3_op_attention_twin")
+                  "sr3_rows_end", "sr3_op_conv2d_fused", "sr3_op_attention_twin", "sr3_gn_res1x1_launches", "sr3_gn_res1x1_gate",
+                  "sr3_op_gn_res1x1", "sr3_bench_gn_res1x1")
 
 _lib = None
 

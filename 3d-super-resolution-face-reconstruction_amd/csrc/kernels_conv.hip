@@ -2029,6 +2029,7 @@ void launch_conv(const ConvParams &p_in, hipStream_t s) {
     const ConvPlan plan = conv_plan(p_in);
     if (plan.error) { g_conv_error = plan.error; return; }
     if (plan.kernel == CK_WINO_ONE_PASS || plan.kernel == CK_WINO_THREE_PASS) { launch_conv_wino(p_in, plan, s); return; }
+    if (p_in.res_ready) { g_conv_error = "internal: the 1x1 term was announced in the output of a conv whose plan multiplies it itself"; return; }
     if (plan.up2_wino) { launch_conv_up2_wino(p_in, plan, s); return; }
     ConvParams p = phase_form(p_in);     // up2: the weights must be in phase form (make_up2_phase_weights)
     const int HWo = p.Hout * p.Wout;

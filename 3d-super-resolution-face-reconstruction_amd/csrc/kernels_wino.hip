@@ -1055,7 +1055,10 @@ void launch_conv_wino(const ConvParams &p, const ConvPlan &plan, hipStream_t s) 
     const int H = p.Hout, W = p.Wout, Cout = p.out.C;
     const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
     ConvParams o = p;
-    if (p.in2.p) {
+    if (p.in2.p && p.res_ready) {
+        // (block1's GroupNorm pass left the 1x1 term in the output: launch_gn_res1x1)
+        o.resid = p.out;
+    } else if (p.in2.p) {
         // fused 1x1 term: a 1x1 conv over in2 || in2b (+ the residual) into the output, added back as the residual
         ConvParams r;
         r.in0 = p.in2; r.in1 = p.in2b;

@@ -199,6 +199,7 @@ struct sr3_ctx {
     int up2_wino_launches = 0;          // Upsample convs launched on wino_up2_kernel (ConvPlan::up2_wino) since sr3_create
     int wino_fused_rows_launches = 0;   // three-pass Winograd convs launched on the one-pass kernel's tile-row form (ConvPlan::wino_fused_rows) since sr3_create
     int wino_gemm_out_launches = 0;     // three-pass Winograd convs launched in the one-kernel form (ConvPlan::wino_gemm_out) since sr3_create
+    int gn_res1x1_launches = 0;         // block1 apply passes launched together with the block's 1x1 res_conv (launch_gn_res1x1) since sr3_create
     float *ckpt = nullptr;              // sr3_sample: NCHW copy of the sampler state at the last clean checkpoint
     size_t ckpt_floats = 0;
     double *metrics_ws = nullptr;       // sr3_metrics_psnr_ssim / sr3_denoise_loss: per-block fp64 partial sums (grows on demand)
@@ -852,17 +853,26 @@ GnRoute gn_route(const TDesc &a, const TDesc &b, int B, const StatsRef &sa, cons
 // scratch of an apply pass: scale / shift [B][C] of the finalize launch, partials of the statistics kernel (gn_workspace_floats)
 struct GnScratch { float *scale = nullptr, *shift = nullptr, *part = nullptr; };
 
+// the second output of an apply pass that also multiplies the block's 1x1 res_conv (launch_gn_res1x1)
+struct GnRes1x1 { const float *w2 = nullptr; TDesc out; };
+
 // the launches of one apply pass on `route`; statistics the producers did not fuse come from the streaming statistics
 // kernel over the (fp32) tensors, whose partials describe the virtual concatenation as one source of a.C + b.C channels
 void launch_gn_act(GnRoute route, const TDesc &a, const TDesc &b, int B, int groups, const float *gamma, const float *beta, int mode,
                    int fmt, const TDesc &act, const StatsRef &sa, const StatsRef &sb, const GnScratch &ws, const TDesc &raw, int in_split,
-                   float *U, int *ovf, const DropLayer &drop, hipStream_t s) {
+                   float *U, int *ovf, const DropLayer &drop, hipStream_t s, const GnRes1x1 *res = nullptr) {
     StatsRef s0 = sa, s1 = sb;
     int C0 = a.C, C1 = b.p ? b.C : 0;
     if (!gn_stats_fused(b, sa, sb)) {
         s0 = launch_groupnorm_partials(a, b, B, ws.part, s);
         s1 = StatsRef();
         C0 += C1; C1 = 0;
+    }
+    if (res) {
+        // block1's pass together with the block's 1x1 res_conv (gn_res1x1_gate said so): always behind a finalize launch
+        launch_groupnorm_finalize(s0, C0, s1, C1, B, a.H * a.W, groups, gamma, beta, 1e-5f, ws.scale, ws.shift, s);
+        launch_gn_res1x1(a, b, B, ws.scale, ws.shift, act, res->w2, res->out, s);
+        return;
     }
     if (route == GN_FINALIZE_ROWS) {
         launch_groupnorm_finalize(s0, C0, s1, C1, B, a.H * a.W, groups, gamma, beta, 1e-5f, ws.scale, ws.shift, s);
@@ -882,15 +892,19 @@ void launch_gn_act(GnRoute route, const TDesc &a, const TDesc &b, int B, int gro
 // finalize + streaming form is the same either way, so no pass gains or loses a finalize launch
 void run_gn_act(sr3_ctx *c, const TDesc &a, const TDesc &b, const GNRef &g, int B, int mode, const TDesc &act,
                 const StatsRef &sa, const StatsRef &sb, const TDesc &raw = TDesc(), int in_split = 0, bool f8 = false,
-                float *U = nullptr, const DropLayer &drop = DropLayer()) {
+                float *U = nullptr, const DropLayer &drop = DropLayer(), const GnRes1x1 *res = nullptr) {
     const int fmt = c->act_format(f8);
     if (U) ++c->gn_wino_passes;
-    c->pbegin(F_GN);
+    if (res) ++c->gn_res1x1_launches;
+    // (with `res` the pass is bracketed in the conv family: most of its time is the 1x1 product, whose FLOPs conv2's
+    // record counts as before)
+    c->pbegin(res ? F_CONV : F_GN);
     GnScratch ws;
     ws.scale = c->gscale; ws.shift = c->gshift; ws.part = c->gpart;
     launch_gn_act(gn_route(a, b, B, sa, sb), a, b, B, c->cfg.norm_groups, c->params[g.gamma].dev, c->params[g.beta].dev, mode, fmt,
-                  act, sa, sb, ws, raw, in_split, U, c->d_ovf, drop, c->stream);
-    c->pend();
+                  act, sa, sb, ws, raw, in_split, U, c->d_ovf, drop, c->stream, res);
+    if (res && c->prof) c->pend(0.0, "gn_res1x1");
+    else c->pend();
 }
 
 // One conv of the engine, by name (defaults = what most convs want)
@@ -913,6 +927,7 @@ struct ConvCall {
     const ConvRef *fused1x1 = nullptr;
     const float *ident_w = nullptr;
     bool u_ready = false;               // the GroupNorm pass wrote the Winograd input transform (gn_writes_u), `in` holds nothing
+    bool res_ready = false;             // block1's GroupNorm pass left the fused 1x1 term in `out` (gn_res1x1_gate)
 };
 
 // the ConvParams of a ConvCall: what run_conv launches and what conv_plan is asked about before the conv's input exists
@@ -950,6 +965,7 @@ ConvParams conv_params(const sr3_ctx *c, const ConvCall &k) {
         p.w2 = k.ident_w;
     }
     p.u_ready = k.u_ready ? 1 : 0;
+    p.res_ready = k.res_ready ? 1 : 0;
     return p;
 }
 
@@ -967,6 +983,40 @@ bool gn_writes_u(const sr3_ctx *c, const ConvCall &k, bool raw_wanted, int in_sp
     if (gn_wino_off() || c->split() || raw_wanted || in_split) return false;
     const ConvPlan pl = conv_plan(conv_params(c, k));
     return pl.kernel == CK_WINO_THREE_PASS && !pl.wino_fused_rows;
+}
+
+// SR3_NO_GN_RES1X1=1 / SR3_GN_RES1X1_FORCE=1 (product switches, read once)
+bool gn_res1x1_off() {
+    static const bool off = env_int("SR3_NO_GN_RES1X1", 0) != 0;
+    return off;
+}
+bool gn_res1x1_force() {
+    static const bool force = env_int("SR3_GN_RES1X1_FORCE", 0) != 0;
+    return force;
+}
+
+// Does block1's GroupNorm + Swish pass also multiply the block's 1x1 res_conv (launch_gn_res1x1 in place of the apply pass
+// and of the side launch of conv2's Winograd plan)? Decided HERE, before block1's pass runs, for the engine (run_res),
+// sr3_op_gn_res1x1 and sr3_gn_res1x1_gate.
+//   valid: exact f32 and a res_conv whose operands are x / skip themselves, unsplit (`direct`, in_split 0, no raw copy
+//          wanted); mode 2; conv1 reads the plain activated tensor (its pass does not write U); conv2's plan is a Winograd
+//          plan, so that today's 1x1 is a side launch; the kernel's shapes (gn_res1x1_shape_ok).
+//   tuned: the levels where every shape of the B = 64 step measured at or under 0.9 of the pair (profiles/README.md,
+//          finding 99), from GN_RES1X1_MIN_BLOCKS blocks on (the smallest count timed).
+struct GnResGate { bool valid = false, tuned = false; bool takes() const { return valid && (tuned || gn_res1x1_force()) && !gn_res1x1_off(); } };
+constexpr int GN_RES1X1_MIN_HW = 32 * 32;       // pixels of one image: the 32x32 level and above
+constexpr long GN_RES1X1_MIN_BLOCKS = 1024;
+GnResGate gn_res1x1_gate(int prec, bool has_res, bool direct, bool raw_wanted, int in_split, int mode, bool conv1_reads_u,
+                         const ConvPlan &pl2, int B, int H, int W, int C0, int C1, int Cout) {
+    GnResGate g;
+    const bool wino2 = pl2.kernel == CK_WINO_ONE_PASS || pl2.kernel == CK_WINO_THREE_PASS;
+    g.valid = prec == 0 && has_res && direct && !raw_wanted && !in_split && mode == 2 && !conv1_reads_u && wino2 &&
+              gn_res1x1_shape_ok(H, W, C0, C1, Cout);
+    if (g.valid) {
+        const long blocks = ((long)B * H * W / 128) * (Cout / gn_res1x1_bn(B, H, W, Cout));
+        g.tuned = (long)H * W >= GN_RES1X1_MIN_HW && blocks >= GN_RES1X1_MIN_BLOCKS;
+    }
+    return g;
 }
 
 // launch_conv on the context's stream; counts the convs whose plan takes the one-kernel form of the three-pass Winograd
@@ -1028,8 +1078,17 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     const bool raw1 = rb.has_res && !direct;
     const int in_split1 = (x_so ? 1 : 0) | (skip.p && sk_so ? 2 : 0);
     k1.u_ready = gn_writes_u(c, k1, raw1, in_split1);
+    // the same pass multiplies the res_conv into the block's output where conv2 would run it as a side launch
+    ConvCall q2;                         // (what conv2's plan depends on)
+    q2.in = m.act2; q2.conv = &rb.c2; q2.B = B; q2.activated = true; q2.f8 = f8b; q2.out = m.rb_out; q2.stats = m.st_rb;
+    GnRes1x1 res1;
+    ConvPlan pl2;                        // (asked only where the rest of the gate can say yes)
+    if (!c->split() && rb.has_res && direct) pl2 = conv_plan(conv_params(c, q2));
+    const bool res_pass = gn_res1x1_gate(c->split() ? 1 : 0, rb.has_res, direct, raw1, in_split1, 2, k1.u_ready, pl2, B, h, w,
+                                         x.C, skip.p ? skip.C : 0, rb.cout).takes();
+    if (res_pass) { res1.w2 = c->params[rb.res.w].dev; res1.out = m.rb_out; }
     run_gn_act(c, x_so ? xr : x, (skip.p && sk_so) ? skr : skip, rb.gn1, B, 2, m.act1, sx, ss, raw1 ? m.raw1 : kNone, in_split1,
-               f8a, k1.u_ready ? c->wino_ws : nullptr);
+               f8a, k1.u_ready ? c->wino_ws : nullptr, DropLayer(), res_pass ? &res1 : nullptr);
     // block1's conv + FeatureWiseAffine bias writes the fp32 h1, then block2's GroupNorm + Swish as the apply pass over it
     run_conv(c, k1);
     // block2 + skip path in one launch: conv3x3(act2) [+ res_conv 1x1 (raw x ‖ skip) as extra
@@ -1041,6 +1100,7 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     if (rb.has_res) {
         k2.in2 = direct ? xr : m.raw1; k2.in2b = direct && skip.p ? skr : kNone;
         k2.fused1x1 = &rb.res; k2.bias_override = rb.fused_bias;
+        k2.res_ready = res_pass;
     } else if (c->split() && rb.ident_w && xr.p) {
         k2.in2 = xr; k2.ident_w = rb.ident_w;
     } else {
@@ -3163,6 +3223,7 @@ int sr3_step_graph_captures(sr3_ctx *c) { return c ? c->step_graph_captures : fa
 int sr3_up2_wino_launches(sr3_ctx *c) { return c ? c->up2_wino_launches : fail("null context"); }
 int sr3_dynamic_threshold_launches(sr3_ctx *c) { return c ? c->dyn_steps : fail("null context"); }
 int sr3_wino_fused_rows_launches(sr3_ctx *c) { return c ? c->wino_fused_rows_launches : fail("null context"); }
+int sr3_gn_res1x1_launches(sr3_ctx *c) { return c ? c->gn_res1x1_launches : fail("null context"); }
 int sr3_replay_calls(sr3_ctx *c) { return c ? c->replay_calls : fail("null context"); }
 void *sr3_test_flag_address(sr3_ctx *c) { return c ? c->d_ovf : nullptr; }
 const char *sr3_last_warning(void) { return g_warn.c_str(); }
@@ -3583,6 +3644,76 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     return 0;
 }
 
+// Per-shape timing of block1's pass + the res_conv (tools/conv_bench.py --set gnres): pair_ms = what the engine launches
+// without gn_res1x1_kernel — the apply pass on the route gn_route names (with its finalize launch where that route has
+// one) and the 1x1 side launch of conv2's Winograd plan; one_ms = finalize launch + gn_res1x1_kernel. Random inputs, the
+// statistics as two conv epilogues would have left them (x and skip separately), `iters` back-to-back repetitions each.
+int sr3_bench_gn_res1x1(sr3_ctx *c, int B, int H, int W, int C0, int C1, int Cout, int groups, int iters, float *pair_ms, float *one_ms,
+                        int *route_out) {
+    const char *what = "sr3_bench_gn_res1x1";
+    if (!c || !pair_ms || !one_ms || iters < 1) return fail("%s: bad argument", what);
+    const int C = C0 + C1;
+    ConvPlan wino;
+    wino.kernel = CK_WINO_ONE_PASS;
+    if (B < 1 || groups <= 0 || C % groups || !gn_res1x1_gate(c->split() ? 1 : 0, true, true, false, 0, 2, false, wino, B, H, W, C0, C1, Cout).valid)
+        return fail("%s: shape refused by the gate", what);
+    HIP_OK(hipSetDevice(c->device));
+    TDesc x, sk, act, out;
+    x.C = C0; sk.C = C1; act.C = C; out.C = Cout;
+    for (TDesc *d : {&x, &sk, &act, &out}) { d->H = H; d->W = W; d->pad = 1; }
+    DevBuf bx, bsk, bact, bout, dg, db, scale, shift, p0, p1, w2;
+    if (bx.alloc(x.floats(B)) || (C1 && bsk.alloc(sk.floats(B))) || bact.alloc(act.floats(B)) || bout.alloc(out.floats(B)) ||
+        dg.alloc((size_t)C) || db.alloc((size_t)C) || scale.alloc((size_t)B * C) || shift.alloc((size_t)B * C) ||
+        p0.alloc(gn_workspace_floats(B, C)) || p1.alloc(gn_workspace_floats(B, C)) || w2.alloc((size_t)Cout * C))
+        return -1;
+    x.p = bx.p; sk.p = bsk.p; act.p = bact.p; out.p = bout.p;
+    HIP_OK(hipMemsetAsync(act.p, 0, act.floats(B) * sizeof(float), c->stream));
+    HIP_OK(hipMemsetAsync(out.p, 0, out.floats(B) * sizeof(float), c->stream));
+    fill_random(c, x.p, x.floats(B), 21);
+    if (C1) fill_random(c, sk.p, sk.floats(B), 22);
+    fill_random(c, dg.p, (size_t)C, 23); fill_random(c, db.p, (size_t)C, 24); fill_random(c, w2.p, (size_t)Cout * C, 25);
+    const TDesc b = C1 ? sk : kNone;
+    const StatsRef sa = launch_groupnorm_partials(x, kNone, B, p0.p, c->stream);
+    const StatsRef sb = C1 ? launch_groupnorm_partials(sk, kNone, B, p1.p, c->stream) : StatsRef();
+    const GnRoute route = gn_route(x, b, B, sa, sb);
+    if (route_out) *route_out = (int)route;
+    GnScratch ws;
+    ws.scale = scale.p; ws.shift = shift.p;
+    GnRes1x1 res;
+    res.w2 = w2.p; res.out = out;
+    ConvParams r;                       // the side launch, as launch_conv_wino builds it
+    r.in0 = x; r.in1 = b;
+    r.B = B; r.Hout = H; r.Wout = W;
+    r.ks = 1; r.prec = 0;
+    r.w = w2.p;
+    r.out = out;
+    auto pair = [&] {
+        launch_gn_act(route, x, b, B, groups, dg.p, db.p, 2, 0, act, sa, sb, ws, TDesc(), 0, nullptr, nullptr, DropLayer(), c->stream);
+        launch_conv(r, c->stream);
+    };
+    auto one = [&] {
+        launch_gn_act(route, x, b, B, groups, dg.p, db.p, 2, 0, act, sa, sb, ws, TDesc(), 0, nullptr, nullptr, DropLayer(), c->stream, &res);
+    };
+    hipEvent_t e0, e1, e2;
+    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1)); HIP_OK(hipEventCreate(&e2));
+    for (int i = 0; i < 2; ++i) { pair(); one(); }
+    HIP_OK(hipEventRecord(e0, c->stream));
+    for (int i = 0; i < iters; ++i) pair();
+    HIP_OK(hipEventRecord(e1, c->stream));
+    for (int i = 0; i < iters; ++i) one();
+    HIP_OK(hipEventRecord(e2, c->stream));
+    HIP_OK(hipEventSynchronize(e2));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    *pair_ms = ms / iters;
+    HIP_OK(hipEventElapsedTime(&ms, e1, e2));
+    *one_ms = ms / iters;
+    HIP_OK(hipEventDestroy(e0)); HIP_OK(hipEventDestroy(e1)); HIP_OK(hipEventDestroy(e2));
+    if (const char *e = conv_take_error()) return fail("%s: %s", what, e);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 int sr3_op_groupnorm_affine(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B,
                             int H, int W, int groups, const float *gamma_host, const float *beta_host,
                             float *scale_dev, float *shift_dev) {
@@ -3650,6 +3781,76 @@ int sr3_op_groupnorm_apply(sr3_ctx *c, const float *in0_dev, int C0, const float
     HIP_OK(hipGetLastError());
     if (route_out) *route_out = (int)r;
     if (range_out) *range_out = flag ? 1 : 0;
+    return 0;
+}
+
+int sr3_gn_res1x1_gate(int B, int H, int W, int C0, int C1, int Cout, int precision, int flags, int mode) {
+    if (B <= 0 || H <= 0 || W <= 0 || C0 <= 0 || C1 < 0 || Cout <= 0 || precision < 0 || precision > 2 || (flags & ~15))
+        return fail("sr3_gn_res1x1_gate: bad argument");
+    const bool has_res = flags & 1, direct = flags & 2, raw_wanted = flags & 4, in_split = flags & 8;
+    ConvPlan pl1, pl2;
+    bool reads_u = false;
+    if (((C0 + C1) % 32) == 0 && (Cout % 32) == 0) {
+        // the engine's convs: fused statistics offered, every buffer offered
+        pl1 = conv_plan_offered(B, H, W, C0 + C1, Cout, 3, 1, 0, precision ? 1 : 0, false, true);
+        pl2 = conv_plan_offered(B, H, W, Cout, Cout, 3, 1, 0, precision ? 1 : 0, false, true);
+        reads_u = !gn_wino_off() && !precision && !raw_wanted && !in_split && pl1.kernel == CK_WINO_THREE_PASS && !pl1.wino_fused_rows;
+    }
+    const GnResGate g = gn_res1x1_gate(precision ? 1 : 0, has_res, direct, raw_wanted, in_split ? 1 : 0, mode, reads_u, pl2, B, H, W, C0, C1, Cout);
+    return (g.valid ? 1 : 0) | (g.tuned ? 2 : 0) | (g.takes() ? 4 : 0);
+}
+
+int sr3_op_gn_res1x1(sr3_ctx *c, const float *x_dev, int C0, const float *skip_dev, int C1, int B, int H, int W, int groups,
+                     const float *gamma_host, const float *beta_host, const float *w2_host, int Cout, float sentinel,
+                     float *act_dev, float *res_dev, float *res_pair_dev) {
+    const char *what = "sr3_op_gn_res1x1";
+    if (!c || !x_dev || !gamma_host || !beta_host || !w2_host || !act_dev || !res_dev) return fail("%s: null argument", what);
+    if (!skip_dev) C1 = 0;
+    const int C = C0 + C1;
+    if (B < 1 || H < 1 || W < 1 || C0 <= 0 || C1 < 0 || Cout <= 0) return fail("%s: bad size B=%d H=%d W=%d C0=%d C1=%d Cout=%d", what, B, H, W, C0, C1, Cout);
+    if (groups <= 0 || C % groups) return fail("%s: groups=%d does not divide C=%d", what, groups, C);
+    // the engine's gate with everything that is not a property of this call granted: a res_conv over unsplit x / skip, mode
+    // 2, conv1 reading the plain activated tensor and a Winograd plan for conv2 (a single op has no convs around it)
+    ConvPlan wino;
+    wino.kernel = CK_WINO_ONE_PASS;
+    if (!gn_res1x1_gate(c->split() ? 1 : 0, true, true, false, 0, 2, false, wino, B, H, W, C0, C1, Cout).valid)
+        return fail("%s: refused by the gate (exact f32 only; C0=%d, C1=%d in multiples of 32, at most %d together; Cout=%d a multiple of "
+                    "64; H*W=%d a multiple of 128)", what, C0, C1, GN_RES1X1_MAX_CIN, Cout, H * W);
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf dg, db, scale, shift, part, w2;
+    std::vector<float> packed((size_t)Cout * C);
+    pack_conv_weight(w2_host, Cout, C, 1, C, packed.data());
+    if (dg.upload(gamma_host, (size_t)C) || db.upload(beta_host, (size_t)C) || scale.alloc((size_t)B * C) || shift.alloc((size_t)B * C) ||
+        part.alloc(gn_workspace_floats(B, C)) || w2.upload(packed.data(), packed.size()))
+        return -1;
+    const TDesc a = unpadded(const_cast<float *>(x_dev), C0, H, W);
+    const TDesc b = skip_dev ? unpadded(const_cast<float *>(skip_dev), C1, H, W) : kNone;
+    TDesc act = unpadded(act_dev, C, H, W);
+    act.pad = 1;
+    GnRes1x1 res;
+    res.w2 = w2.p; res.out = unpadded(res_dev, Cout, H, W);
+    const unsigned bits = __builtin_bit_cast(unsigned, sentinel);
+    HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(act_dev), (int)bits, act.floats(B), c->stream));
+    HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(res_dev), (int)bits, res.out.floats(B), c->stream));
+    GnScratch ws;
+    ws.scale = scale.p; ws.shift = shift.p; ws.part = part.p;
+    // statistics as sr3_op_groupnorm_apply gets them without partials: the streaming statistics kernel, then finalize
+    launch_gn_act(GN_FINALIZE_ROWS, a, b, B, groups, dg.p, db.p, 2, 0, act, StatsRef(), StatsRef(), ws, TDesc(), 0, nullptr, nullptr,
+                  DropLayer(), c->stream, &res);
+    ++c->gn_res1x1_launches;
+    if (res_pair_dev) {
+        // the launch the kernel replaces, as launch_conv_wino builds it: the unsplit 1x1 conv without bias
+        ConvParams r;
+        r.in0 = a; r.in1 = b;
+        r.B = B; r.Hout = H; r.Wout = W;
+        r.ks = 1; r.prec = 0;
+        r.w = w2.p;
+        r.out = unpadded(res_pair_dev, Cout, H, W);
+        HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(res_pair_dev), (int)bits, r.out.floats(B), c->stream));
+        launch_conv(r, c->stream);
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("%s: launch failed", what);
+    if (const char *e = conv_take_error()) return fail("%s: %s", what, e);
     return 0;
 }
 

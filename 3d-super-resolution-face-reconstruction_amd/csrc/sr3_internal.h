@@ -8,7 +8,7 @@
 namespace sr3 {
 
 // ---- environment switches ---------------------------------------------------------------------------
-// Everything the library reads from the environment (INTEGRATION.md lists the same twelve; each is read once per process
+// Everything the library reads from the environment (INTEGRATION.md lists the same fourteen; each is read once per process
 // and then baked into captured graphs):
 //   SR3_NO_GRAPH=1          every kernel launched individually, no hipGraph replay (hosts that cannot capture)
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
@@ -28,6 +28,10 @@ namespace sr3 {
 //   SR3_NO_WINO_FUSED_ROWS=1  three-pass Winograd convs never on the one-pass kernel's tile-row instantiations
 //                           (ConvPlan::wino_fused_rows): the launches of the library before them, same bits
 //   SR3_WINO_FUSED_ROWS_FORCE=1  that form wherever its preconditions hold, whatever the block count and Cin (tests,
+//                           per-shape timing)
+//   SR3_NO_GN_RES1X1=1      block1's GroupNorm apply pass and the 1x1 res_conv side launch of a Winograd conv2 always as
+//                           two launches (the library before gn_res1x1_kernel; same bits)
+//   SR3_GN_RES1X1_FORCE=1   that kernel wherever its preconditions hold, whatever the level and block count (tests,
 //                           per-shape timing)
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
@@ -135,6 +139,10 @@ struct ConvParams {
     // 1 (CK_WINO_THREE_PASS only): U of in0 || in1 is already at the head of wino_ws (launch_gn_wino_input wrote it);
     // launch_conv_wino then skips wino_input_kernel and does nothing else differently. No input of conv_plan.
     int u_ready = 0;
+    // 1 (Winograd plans with the fused 1x1 term only): out already holds w2 . (in2 || in2b) — launch_gn_res1x1 wrote it in
+    // block1's GroupNorm pass (sr3_api.hip: gn_res1x1_gate) — so launch_conv_wino skips its 1x1 side launch and takes out
+    // as the residual, and does nothing else differently. No input of conv_plan.
+    int res_ready = 0;
     // GEMM batch (launch_wino_gemm only): blockIdx.z = z multiplies in0.p + z * batch_in_stride by
     // w + z * phase_w_stride into out.p + z * batch_out_stride
     int zbatch = 1;
@@ -361,6 +369,18 @@ void launch_gn_wino_input(const TDesc &in0, const TDesc &in1, int B, const float
 void launch_gn_fold_wino_input(const TDesc &in0, const TDesc &in1, int B, const StatsRef &s0, const StatsRef &s1, int groups,
                                const float *gamma, const float *beta, float eps, int mode, float *U, hipStream_t s);
 StatsRef launch_groupnorm_partials(const TDesc &in0, const TDesc &in1, int B, float *part, hipStream_t s);
+// ---- block1's apply pass + the block's 1x1 res_conv in one pass over the raw x || skip (kernels_gn_res.hip) -------------
+// act (zero-bordered, C0 + C1 channels; interior only) = swish_fast(fmaf(in0 || in1, scale, shift)), bit for bit what
+// launch_gn_apply* write in mode 2 / format 0; out (C = Cout) = w2 . (in0 || in1), bit for bit what launch_conv writes for
+// the unsplit 1x1 conv without bias (the side launch of launch_conv_wino). scale / shift [B][C0 + C1] from
+// launch_groupnorm_finalize. Shapes: gn_res1x1_shape_ok — channels in 32s on both sides of the concatenation, Cout in
+// 64s (a whole number of gn_res1x1_bn column tiles), H * W a multiple of the 128-pixel tile, at most GN_RES1X1_MAX_CIN
+// input channels (the scale / shift table of a block lives in LDS).
+constexpr int GN_RES1X1_MAX_CIN = 1024;
+bool gn_res1x1_shape_ok(int H, int W, int C0, int C1, int Cout);
+int gn_res1x1_bn(int B, int H, int W, int Cout);
+void launch_gn_res1x1(const TDesc &in0, const TDesc &in1, int B, const float *scale, const float *shift, const TDesc &act,
+                      const float *w2, const TDesc &out, hipStream_t s);
 // common power-of-two scale for several weight tensors: returns k with max|w| * 2^k in [1024, 2048)
 int split_scale_exponent(const float *packed, size_t n);
 float split_conv_weight_k(const float *packed, size_t rows, int CinPad, int k, float *dst);

@@ -85,6 +85,18 @@ def conv_plan(B: int, H: int, W: int, Cin: int, Cout: int, ks: int = 3, stride: 
             "wino_ws_floats": v[9], "needs_wino_frag": bool(v[10]), "f8": bool(v[11])}
 
 
+def gn_res1x1_gate(B: int, H: int, W: int, C0: int, C1: int, Cout: int, precision: str = "f32", has_res: bool = True,
+                   direct: bool = True, raw_wanted: bool = False, in_split: bool = False, mode: int = 2) -> dict:
+    """The library's decision for one ResnetBlock at H x W pixels: does block1's GroupNorm + Swish pass over x (C0) ‖ skip
+    (C1) also multiply the block's 1x1 res_conv (sr3_gn_res1x1_gate)? valid: the rules hold; tuned: the level and block
+    count are adopted; takes: what this process launches (the two environment switches included). Host only: needs no GPU
+    and no context."""
+    flags = (1 if has_res else 0) | (2 if direct else 0) | (4 if raw_wanted else 0) | (8 if in_split else 0)
+    r = int(_lib.load().sr3_gn_res1x1_gate(B, H, W, C0, C1, Cout, PRECISIONS[precision], flags, mode))
+    _lib.check(min(r, 0))
+    return {"valid": bool(r & 1), "tuned": bool(r & 2), "takes": bool(r & 4)}
+
+
 def lr_operators(l: int, r: int) -> Tuple[np.ndarray, np.ndarray]:
     """(A [l,r], P [r,l]) in float64 for one axis of the r -> l bicubic resample: A the real weights of Pillow's
     precompute_coeffs with rows normalised, P = A^T (A A^T)^-1 (sr3_lr_operators_host). Host only: needs
@@ -170,6 +182,11 @@ class Engine:
         """Three-pass Winograd convs this engine launched (or captured into a graph) on the one-pass kernel with 2 | 4 tile rows
         per block (the 32x32 and 16x16 levels); 0 under SR3_NO_WINO_FUSED_ROWS=1 and outside the f32 mode."""
         return int(self.lib.sr3_wino_fused_rows_launches(self.ctx))
+
+    def gn_res1x1_launches(self) -> int:
+        """block1 GroupNorm apply passes this engine launched (or captured into a graph) together with the block's 1x1
+        res_conv, op_gn_res1x1 calls included; 0 under SR3_NO_GN_RES1X1=1 and outside the f32 mode."""
+        return int(self.lib.sr3_gn_res1x1_launches(self.ctx))
 
     def step_graph_captures(self) -> int:
         """Sampler steps this engine captured into a graph since it was created: a step whose form and baked-in values
@@ -907,6 +924,40 @@ class Engine:
             r = raw.download((B, H, W, Cc))
             res["raw"] = r.view(np.uint32) if fmt else r
         return res
+
+    def bench_gn_res1x1(self, B, H, W, C0, C1, Cout, iters=20, groups=32):
+        """(ms of the apply pass + 1x1 conv pair, ms of finalize + gn_res1x1_kernel, route of the pair's apply pass) for one
+        block shape on random data (sr3_bench_gn_res1x1)."""
+        pair, one, route = C.c_float(0), C.c_float(0), C.c_int(0)
+        _lib.check(self.lib.sr3_bench_gn_res1x1(self.ctx, B, H, W, C0, C1, Cout, groups, iters, C.byref(pair), C.byref(one),
+                                                C.byref(route)))
+        return pair.value, one.value, route.value
+
+    def op_gn_res1x1(self, x, gamma, beta, w2, groups=32, skip=None, sentinel=-12345.0, want_pair=False):
+        """block1's GroupNorm + Swish pass and the block's 1x1 res_conv in one kernel (f32 mode) over NHWC x ‖ skip; w2
+        [Cout, C0 + C1]. Returns a dict: act [B, H+2, W+2, C] (border = sentinel), res [B, H, W, Cout] and, with
+        want_pair, res_pair: the same product from the 1x1 side launch the kernel replaces in the engine."""
+        x = _host_f32(x)
+        B, H, W, C0 = x.shape
+        C1 = 0 if skip is None else skip.shape[-1]
+        Cc = C0 + C1
+        w2 = _host_f32(w2)
+        Cout = w2.shape[0]
+        assert w2.size == Cout * Cc
+        g, b = _host_f32(gamma), _host_f32(beta)
+        assert g.size == Cc and b.size == Cc
+        d0 = self.to_device(x)
+        d1 = self.to_device(_host_f32(skip)) if skip is not None else None
+        act = self.buffer(B * (H + 2) * (W + 2) * Cc)
+        res = self.buffer(B * H * W * Cout)
+        pair = self.buffer(B * H * W * Cout) if want_pair else None
+        _lib.check(self.lib.sr3_op_gn_res1x1(
+            self.ctx, d0.ptr, C0, d1.ptr if d1 else None, C1, B, H, W, groups, g.ctypes.data, b.ctypes.data, w2.ctypes.data,
+            Cout, float(sentinel), act.ptr, res.ptr, pair.ptr if pair else None))
+        out = {"act": act.download((B, H + 2, W + 2, Cc)), "res": res.download((B, H, W, Cout))}
+        if want_pair:
+            out["res_pair"] = pair.download((B, H, W, Cout))
+        return out
 
     def op_groupnorm_affine(self, x0, gamma, beta, groups=32, x1=None):
         x0 = _host_f32(x0)

@@ -315,6 +315,17 @@ int sr3_up2_wino_launches(sr3_ctx *ctx);
  * 2 | 4 tile rows per block (the 32x32 and 16x16 levels; exact f32 only; 0 under SR3_NO_WINO_FUSED_ROWS=1): tells a test
  * which form ran. */
 int sr3_wino_fused_rows_launches(sr3_ctx *ctx);
+/* block1 GroupNorm apply passes this context launched (or captured into a graph) since sr3_create together with the
+ * block's 1x1 res_conv (gn_res1x1_kernel; exact f32 only; 0 under SR3_NO_GN_RES1X1=1), sr3_op_gn_res1x1 calls included:
+ * tells a test which form ran. */
+int sr3_gn_res1x1_launches(sr3_ctx *ctx);
+/* The engine's decision for one ResnetBlock (host only, no context): does block1's GroupNorm + Swish pass over x (C0
+ * channels) || skip (C1) also multiply the block's 1x1 res_conv into Cout channels? The two 3x3 convs' plans are those of
+ * sr3_conv_plan with statistics. flags: 1 = the block has a res_conv, 2 = its operands are x / skip themselves, 4 = a raw
+ * copy of the concatenation is wanted, 8 = an input is stored in the split format; mode as sr3_op_groupnorm_apply.
+ * Returns bit 0 = valid, bit 1 = tuned (the level and block count are adopted), bit 2 = taken in this process (valid,
+ * not SR3_NO_GN_RES1X1=1, and tuned or SR3_GN_RES1X1_FORCE=1); < 0: bad argument. */
+int sr3_gn_res1x1_gate(int B, int H, int W, int C0, int C1, int Cout, int precision, int flags, int mode);
 /* Sampler steps this context captured into a graph since sr3_create (successful instantiations; 0 under SR3_NO_GRAPH=1
  * and while profiling): tells a test that a step was replayed from its graph, or captured anew because a value the graph
  * holds had changed. */
@@ -478,6 +489,23 @@ int sr3_op_final_conv(sr3_ctx *ctx, const float *in_dev, int B, int H, int W, in
  * number of padded pixels B*(H+2)*(W+2); 0: this shape keeps no packed state (conv_in_supported), nothing is copied;
  * < 0: error (no workspace yet). Synchronises the context's stream. (tests) */
 int64_t sr3_read_packed_state(sr3_ctx *ctx, float *state_host, void *packed_host, int *dims3);
+/* block1's GroupNorm + Swish pass and the block's 1x1 res_conv in one kernel (exact f32), on unpadded NHWC x (C0
+ * channels) || skip (C1; skip_dev NULL: none): act_dev [B][H+2][W+2][C0+C1] receives swish(group_norm(x || skip)) at its
+ * interior pixels — the bits of sr3_op_groupnorm_apply (mode 2, format 0) — and res_dev [B][H][W][Cout] receives
+ * w2 . (x || skip) without bias (w2_host [Cout][C0+C1]) — the bits of the unsplit 1x1 conv. The statistics come from the
+ * streaming statistics kernel and a finalize launch. Both outputs are filled with `sentinel` first, so the border of
+ * act_dev still holds it afterwards. res_pair_dev (optional, [B][H][W][Cout]): additionally receives the same product from
+ * the launch the kernel replaces in the engine (the 1x1 side launch of a Winograd conv2). Fails for a shape the engine's
+ * gate refuses: C0, C1 multiples of 32, C0+C1 <= 1024, Cout a multiple of 64, H*W a multiple of 128; f32 mode. (tests) */
+int sr3_op_gn_res1x1(sr3_ctx *ctx, const float *x_dev, int C0, const float *skip_dev, int C1, int B, int H, int W, int groups,
+                     const float *gamma_host, const float *beta_host, const float *w2_host, int Cout, float sentinel,
+                     float *act_dev, float *res_dev, float *res_pair_dev);
+/* Per-shape timing of that kernel against the two launches it replaces, on random data with the statistics of x and skip
+ * given as conv epilogues leave them: *pair_ms = the GroupNorm apply pass on the engine's route (*route_out, as
+ * sr3_op_groupnorm_apply's; with its finalize launch on route 2) + the 1x1 conv; *one_ms = finalize launch + the kernel;
+ * each the average of `iters` back-to-back repetitions. (tools/conv_bench.py --set gnres) */
+int sr3_bench_gn_res1x1(sr3_ctx *ctx, int B, int H, int W, int C0, int C1, int Cout, int groups, int iters, float *pair_ms,
+                        float *one_ms, int *route_out);
 /* GroupNorm statistics folded with the affine: scale[b,c] = rstd*gamma[c],
  * shift[b,c] = beta[c] - mean*rstd*gamma[c]  (torch GroupNorm, eps 1e-5; unet.py:84,119). */
 int sr3_op_groupnorm_affine(sr3_ctx *ctx, const float *in0_dev, int C0, const float *in1_dev,

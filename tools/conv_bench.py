@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark for the implicit-GEMM conv (development tool; run on the GPU box):
-    python tools/conv_bench.py [--iters N] [--set main|wino3|up2|rows] [--only i,j,...] [--repeat R]
+    python tools/conv_bench.py [--iters N] [--set main|wino3|up2|rows|gnres] [--only i,j,...] [--repeat R]
 Prints ms and TFLOP/s per shape of the B=64, 128x128 SR3 step (--set wino3: every distinct shape of its three-pass
 Winograd convs, timed from U on: the position GEMMs + output transform, in whichever form the plan takes).
 --set up2: the four Upsample convs of the step, and the 64 -> 128 one at B = 4 and 16, in the form the plan takes, as
@@ -8,7 +8,11 @@ four phase convs (SR3_NO_UP2_WINO=1) and as sub-pixel Winograd wherever its prec
 one child process per form (the switches are read once per process), the forms alternating, --repeat rounds.
 --set rows: every distinct 3x3 shape of the step's 32x32 and 16x16 levels from the RAW input on (GroupNorm apply pass + conv),
 in the parent's three-pass forms (SR3_NO_WINO_FUSED_ROWS=1) and on the one-pass kernel with 2 | 4 tile rows per block
-(SR3_WINO_FUSED_ROWS_FORCE=1), alternating in the same way: the table that sets WINO_FUSED_ROWS_MIN_BLOCKS."""
+(SR3_WINO_FUSED_ROWS_FORCE=1), alternating in the same way: the table that sets WINO_FUSED_ROWS_MIN_BLOCKS.
+--set gnres: the eleven ResnetBlocks of the step whose block1 GroupNorm pass also multiplies the 1x1 res_conv
+(gn_res1x1_kernel): the pair it replaces (apply pass on the engine's route, with its finalize launch where that route has
+one, + the 1x1 side launch) against finalize + the kernel, alternating in ONE process, --repeat rounds: the table that
+sets the level gate of gn_res1x1_gate (a level is adopted where every shape is at or under 0.9 of the pair)."""
 import argparse
 import importlib
 import os
@@ -58,6 +62,21 @@ ROWS = WINO3[:9]
 ROWS_FORMS = [("three-pass", {"SR3_NO_WINO_FUSED_ROWS": "1"}), ("rows", {"SR3_WINO_FUSED_ROWS_FORCE": "1"})]
 FORMS = {"up2": UP2_FORMS, "rows": ROWS_FORMS}
 
+# B, H = W, C0, C1, Cout of the blocks gn_res1x1_gate takes at B = 64: the 128x128, 64x64 and 32x32 levels
+GNRES = [(64, 128, 128, 64, 64), (64, 128, 64, 64, 64), (64, 64, 64, 0, 128), (64, 64, 256, 128, 128), (64, 64, 128, 128, 128),
+         (64, 64, 128, 64, 128), (64, 32, 128, 0, 256), (64, 32, 512, 256, 256), (64, 32, 256, 256, 256), (64, 32, 256, 128, 256)]
+
+
+def gnres_main(e, args):
+    shapes = GNRES if not args.only else [GNRES[int(i)] for i in args.only.split(",")]
+    for rnd in range(args.repeat):
+        for (B, hw, C0, C1, Cout) in shapes:
+            pair, one, route = e.bench_gn_res1x1(B, hw, hw, C0, C1, Cout, args.iters)
+            fl = 2.0 * B * hw * hw * Cout * (C0 + C1)
+            gb = 4.0 * B * hw * hw * (2 * (C0 + C1) + Cout) / 1e9
+            print(f"round {rnd + 1} B{B} {hw}x{hw} cin{C0}+{C1} cout{Cout}: pair {pair:7.4f} ms (apply route {route})  one {one:7.4f} ms  "
+                  f"ratio {one / pair:5.3f}   [one: {fl / one / 1e9:6.1f} TFLOP/s, {gb / one:5.2f} TB/s]", flush=True)
+
 
 def forms_parent(args):
     """one child per form and round; nothing here touches the GPU"""
@@ -78,8 +97,8 @@ def forms_parent(args):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--set", type=str, default="main", choices=["main", "wino3", "up2", "rows"])
-    ap.add_argument("--repeat", type=int, default=2, help="--set up2 | rows: rounds over the forms")
+    ap.add_argument("--set", type=str, default="main", choices=["main", "wino3", "up2", "rows", "gnres"])
+    ap.add_argument("--repeat", type=int, default=2, help="--set up2 | rows | gnres: rounds over the forms")
     ap.add_argument("--child", type=str, default="", help=argparse.SUPPRESS)
     ap.add_argument("--only", type=str, default="", help="comma list of shape indices")
     ap.add_argument("--precision", type=str, default="f32", choices=["f32", "f16x3", "f16f8"])
@@ -93,6 +112,10 @@ if __name__ == "__main__":
     Engine = importlib.import_module(PKG + ".engine").Engine
     e = Engine(synth.tiny_unet_config(), 0)
     e.set_precision(args.precision)
+    if args.set == "gnres":
+        gnres_main(e, args)
+        e.close()
+        sys.exit(0)
     table = {"wino3": WINO3, "up2": UP2, "rows": ROWS}.get(args.set, MAIN)
     shapes = table if not args.only else [table[int(i)] for i in args.only.split(",")]
     for (B, H, W, C0, C1, Cout, ks, st, up, mode, rs, cb) in shapes:
