@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsr3hip.so")
-SOURCES = ["sr3_api.hip", "kernels_conv.hip", "kernels_wino.hip", "kernels_misc.hip", "kernels_edge.hip", "kernels_pre.hip", "kernels_post.hip", "kernels_metrics.hip", "kernels_loss.hip", "kernels_weights.hip", "kernels_consist.hip", "kernels_threshold.hip", "kernels_rows.hip", "kernels_gn_res.hip"]
+SOURCES = ["sr3_api.hip", "conv_plan.hip", "kernels_conv.hip", "kernels_wino.hip", "kernels_misc.hip", "kernels_edge.hip", "kernels_pre.hip", "kernels_post.hip", "kernels_metrics.hip", "kernels_loss.hip", "kernels_weights.hip", "kernels_consist.hip", "kernels_threshold.hip", "kernels_rows.hip", "kernels_gn_res.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-source flags: the fp32 VALU contraction of kernels_edge.hip must stay scalar v_fma_f32 (the SLP
 # vectoriser packs it into v_pk_fma_f32 pairs: register-pair shuffles, 2 KB of scratch per lane)
@@ -37,8 +37,8 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "sr3_internal.h"),
-               os.path.join(HERE, "..", "include", "sr3hip.h")]
+    headers = [os.path.join(CSRC, h) for h in ("sr3_internal.h", "conv_plan.h")]
+    headers.append(os.path.join(HERE, "..", "include", "sr3hip.h"))
     jobs = []
     objs = []
     for src in SOURCES:

@@ -30,6 +30,7 @@
 // Each lane reads 4 consecutive k per ds_read_b128 and feeds 4 MFMAs; lane half h supplies
 // k = 8kk + 4h + j to MFMA j of group kk for both operands.
 #include "sr3_internal.h"
+#include "conv_plan.h"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1678,329 +1679,6 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvParam
             o[0] = sa; o[1] = sb;
         }
     }
-}
-
-// pixels per block of the split-K reduce (at most 64 statistics slices per image and phase)
-static int splitk_reduce_tp(int HWo) { const int tp = HWo / 64; return tp < 1 ? 1 : tp; }
-// a split conv's fused GroupNorm statistics come out of its reduce pass: slices per image (and per sub-pixel phase)
-// for an output of HWo pixels; 0: the reduce pass cannot produce the statistics of this shape
-static int splitk_stats_slices(int HWo, int Cout) {
-    const int tp = splitk_reduce_tp(HWo);
-    return ((HWo % tp) == 0 && Cout <= 1024 && (Cout & 3) == 0) ? HWo / tp : 0;
-}
-
-// ---- the dispatch plan ---------------------------------------------------------------------------------------------
-// tile of the generic kernel (and of the x-halo kernel that replaces it where its preconditions hold)
-struct Tile { ConvKernel generic; int bm, bn; };
-static Tile conv_tile_choice(long M, int Cout) {
-    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((Cout + bn - 1) / bn); };
-    const long want = 512;  // 256 CUs x 2 resident blocks
-    const Tile t32 = {CK_GENERIC_128x32, 128, 32}, t64 = {CK_GENERIC_128x64, 128, 64}, t6464 = {CK_GENERIC_64x64, 64, 64};
-    if (Cout <= 32) return t32;
-    if (Cout <= 64 || (Cout % 128) != 0) return blocks(128, 64) >= want ? t64 : t6464;
-    if (blocks(128, 128) >= want) return Tile{CK_GENERIC_128x128, 128, 128};
-    return blocks(128, 64) >= want ? t64 : t6464;
-}
-static long tile_count(const Tile &t, long M, int Cout) { return ((M + t.bm - 1) / t.bm) * ((Cout + t.bn - 1) / t.bn); }
-
-// K-splits of the generic kernel for small problems (1 = none); Cin per tap, multiple of 32
-static int conv_splits(long M, int Cout, int Cin) {
-    if (Cout & 3) return 1;
-    const long tiles = tile_count(conv_tile_choice(M, Cout), M, Cout);
-    const int nchunk = Cin / BK;
-    // (tuned on B = 1 at 128x128 and config 1, with the in-place fix-up: profiles/README.md finding 42)
-    constexpr int tmin = 256, target = 256, chmin = 2;
-    if (tiles >= tmin || nchunk < 2 * chmin) return 1;
-    int s = 2;
-    while (s * 2 <= nchunk / chmin && tiles * s * 2 <= target && s < 16) s *= 2;
-    return s;
-}
-
-// SR3_NO_HALO=1 (product safety switch): no x-halo kernel anywhere — and therefore no F8C path and no halo split-K
-static bool halo_off() {
-    static const int off = env_int("SR3_NO_HALO", 0);
-    return off != 0;
-}
-
-// Deep-K 3x3 / stride-1 split-f16 convs over FEW output tiles (the 8x8 level at B = 64: M = 4096 pixels, 512 channels):
-// instead of 64x64 tiles of the generic kernel (LDS traffic per MFMA twice that of a 128x128 tile) they run on the
-// 128x128 x-halo tile with the K range split over `return value` blocks per tile, added IN PLACE by the block that
-// arrives last (conv3x3_halo_h3, end of the consumer path) — no reduce pass, statistics in the unsplit layout (one
-// slice per 128-row tile, or one per image where a tile covers several whole images). 0 or 1: not for this shape.
-// Assumes ks 3, stride 1, prec 1, pad 1 (conv_plan checks them).
-static int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
-    static const int force = env_int("SR3_HALO_SPLITS", -1);    // product switch: 0 off, 2 | 4 forced
-    if (force == 0 || halo_off()) return 0;
-    const int HWo = H * W;
-    if (W < 8 || (M % 128) || (Cout % 128) || (Cin % 32)) return 0;
-    const int seg = W < 128 ? W : 128;
-    if ((W % seg) || (128 % seg)) return 0;
-    if (HWo >= 128 ? (HWo % 128) != 0 : ((128 % HWo) != 0 || (HWo % 32) != 0)) return 0;
-    if (conv_tile_choice(M, Cout).generic != CK_GENERIC_64x64) return 0;   // enough 128-row tiles already: no split needed
-    const long tiles = (M / 128) * (Cout / 128);
-    const int nchunk = Cin / 32;
-    if (tiles < 64 || tiles > CONV_TILE_COUNTERS || nchunk < 8) return 0;
-    int sp = 2;
-    while (sp * 2 <= nchunk / 4 && tiles * sp * 2 <= 512 && sp < 4) sp *= 2;      // (the reduce-scatter tail handles 2 or 4 splits)
-    if (force == 2 || force == 4) sp = force;
-    return sp;
-}
-
-// preconditions of the x-halo kernel for tile height BM: p after the phase transform, splits = the plan's
-static bool halo_ok(const ConvParams &p, int splits, int BM, int segmin, int bn, bool split_ok = false) {
-    if (halo_off() || p.prec != 1 || (p.ks != 3 && p.ks != 2) || p.stride != 1 || p.up2 || (splits > 1 && !split_ok) || p.in0.pad != 1) return false;
-    const int W = p.Wout;
-    if (p.in0.W != W || p.in0.H != p.Hout) return false;
-    const int seg = W < BM ? W : BM;
-    if (seg < segmin || (W % seg) || (BM % seg)) return false;
-    const long M = (long)p.B * p.Hout * W;
-    // no masking anywhere in the halo kernels: whole tiles in M and (for the tile width bn the caller picks) in N
-    return (M % BM) == 0 && (p.out.C % bn) == 0 && (!p.in2.p || (p.in2.C % 32) == 0) && (!p.in2b.p || (p.in2b.C % 32) == 0);
-}
-
-// ---- Winograd gates (the kernels are in kernels_wino.hip) ----
-// one-pass kernel: 64x64 pixels and up, whole strips per tile row, whole channel blocks, and enough blocks to fill the
-// chip (fewer: the direct kernel, whose smaller tiles spread further)
-static bool wino_fused_shape(int B, int H, int W, int Cin, int Cout) {
-    if (H * W < 4096 || (H & 1) || (W % (2 * WINO_FUSED_TILES)) || Cin < WINO_FUSED_CIN || (Cin % 32) || (Cout % WINO_FUSED_BN)) return false;
-    const uint64_t blocks = (uint64_t)B * (H / 2) * (W / (2 * WINO_FUSED_TILES)) * (Cout / WINO_FUSED_BN);
-    return blocks >= WINO_FUSED_MIN_BLOCKS;
-}
-
-// shape rule (3x3 / stride 1 / prec 0 convs): false also under SR3_NO_WINOGRAD=1
-static bool wino_shape(int B, int H, int W, int Cin, int Cout) {
-    static const bool off = env_int("SR3_NO_WINOGRAD", 0) != 0;    // product switch (read once)
-    if (off || B <= 0) return false;
-    if (wino_fused_shape(B, H, W, Cin, Cout)) return true;
-    if ((H & 1) || (W & 1) || H * W > 1024 || Cin < WINO_MIN_CIN || (Cin % 32) || (Cout % 64)) return false;
-    // few tiles (a single 128x128 image: 256 at its 32x32 level): the three dependent passes cost more latency than the
-    // MACs they save (B = 1 step 1.99 -> 2.27 ms with every level in Winograd form); B = 64 at 8x8 is 1024 tiles and gains
-    const uint64_t tiles = (uint64_t)B * (H / 2) * (W / 2);
-    if (tiles < WINO_MIN_TILES) return false;
-    // the LDS-DMA and epilogue addressing of the position GEMMs uses 32-bit byte offsets inside one position's plane
-    return tiles * (uint64_t)(Cin > Cout ? Cin : Cout) * 4 < (1ull << 32);
-}
-
-// the Winograd form this conv runs in, CK_COUNT: none (the direct kernels)
-static ConvKernel wino_form(const ConvParams &p) {
-    if (p.prec != 0 || p.ks != 3 || p.stride != 1 || p.up2 || p.phases != 1 || p.f8) return CK_COUNT;
-    if (p.out_split.p || !p.out_f32 || p.resid_split) return CK_COUNT;
-    if (p.in0.pad != 1 || p.in0.H != p.Hout || p.in0.W != p.Wout) return CK_COUNT;
-    if (p.in1.p && (p.in1.pad != 1 || p.in1.H != p.Hout || p.in1.W != p.Wout)) return CK_COUNT;
-    if (p.in2.p && !p.w2) return CK_COUNT;
-    const int Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
-    if (!wino_shape(p.B, p.Hout, p.Wout, Cin, p.out.C)) return CK_COUNT;
-    if (wino_fused_shape(p.B, p.Hout, p.Wout, Cin, p.out.C)) {
-        // one input tensor: the engine concatenates x || skip in the GroupNorm apply pass that writes the conv's input,
-        // so no caller hands these convs a second tensor (one that does gets the direct kernel)
-        if (!p.w_wino_f || p.in1.p) return CK_COUNT;
-        // the statistics slices must be whole strips or 2 | 4 equal parts of one
-        const int spi = (p.Hout / 2) * (p.Wout / (2 * WINO_FUSED_TILES));
-        if (p.stats == nullptr) return CK_WINO_ONE_PASS;
-        if (p.stats_slices <= 0 || (p.stats_slices % spi)) return CK_COUNT;
-        const int spb = p.stats_slices / spi;
-        return (spb == 1 || spb == 2 || spb == 4) ? CK_WINO_ONE_PASS : CK_COUNT;
-    }
-    if (!p.w_wino || !p.wino_ws) return CK_COUNT;
-    const int tiles = (p.Hout >> 1) * (p.Wout >> 1);
-    return (p.stats == nullptr || (p.stats_slices > 0 && (tiles % p.stats_slices) == 0)) ? CK_WINO_THREE_PASS : CK_COUNT;
-}
-
-// second form of the three-pass plan (kernels_wino.hip, wino_gemm_out_kernel): output channels per block, 0 = the
-// position GEMMs + wino_output_kernel. Preconditions: whole channel blocks (wino_shape: Cout % 64 == 0), statistics
-// slices of 16 | 32 tiles (what a block's waves hold whole). Tuning (profiles/README.md finding 86): enough blocks of
-// 64 tiles to fill the chip, as each runs all 16 positions, and Cin small enough for M's traffic to matter
-static int wino_gemm_out_bn(const ConvParams &p, int Cin) {
-    static const bool off = env_int("SR3_NO_WINO_GEMM_OUT", 0) != 0;         // product switches (read once)
-    static const bool force = env_int("SR3_WINO_GEMM_OUT_FORCE", 0) != 0;
-    if (off) return 0;
-    const int tpi = (p.Hout >> 1) * (p.Wout >> 1), Cout = p.out.C;
-    if (p.stats) {
-        const int tps = tpi / p.stats_slices;
-        if (tps != 16 && tps != 32) return 0;
-    }
-    // the epilogue addresses the zero-bordered output (and the residual, same geometry) with 32-bit byte offsets
-    if ((uint64_t)p.out.floats(p.B) * 4 >= (1ull << 32)) return 0;
-    const int bn = (Cout % 128) == 0 ? 128 : 64;
-    if (force) return bn;
-    const long blocks = (((long)p.B * tpi + WINO_GEMM_OUT_TILES - 1) / WINO_GEMM_OUT_TILES) * (Cout / bn);
-    return (blocks >= WINO_GEMM_OUT_MIN_BLOCKS && Cin <= WINO_GEMM_OUT_MAX_CIN) ? bn : 0;
-}
-
-// third form of the three-pass plan: the one-pass kernel with R = 2 | 4 tile rows per block (kernels_wino.hip,
-// wino_fused_kernel<R>), 0 = not taken. Preconditions: one input tensor (the engine's GroupNorm pass concatenates) and
-// the fragment-major weights; a width of 32 | 16 (R = 2 | 4: a block's 32 tiles are R whole tile rows) and whole blocks
-// (H % 2R == 0); whole 32-channel K-steps and 64-channel blocks; statistics slices that are a whole block or 2 | 4
-// equal parts of one; 32-bit offsets of the input DMA (bit 31 of a lane's offset switches an instruction off) and of
-// the weight loads (the four planes of a wave). Tuning: WINO_FUSED_ROWS_MIN_BLOCKS (per level).
-static int wino_fused_rows(const ConvParams &p, int Cin) {
-    static const bool off = env_int("SR3_NO_WINO_FUSED_ROWS", 0) != 0;       // product switches (read once)
-    static const bool force = env_int("SR3_WINO_FUSED_ROWS_FORCE", 0) != 0;
-    if (off || p.in1.p || !p.w_wino_f) return 0;
-    const int H = p.Hout, W = p.Wout, Cout = p.out.C;
-    const int R = W == 32 ? 2 : W == 16 ? 4 : 0;
-    if (R == 0 || (H % (2 * R)) || (Cin % 32) || (Cout % WINO_FUSED_BN)) return 0;
-    const int bpi = (H / 2) * (W / 2) / WINO_FUSED_TILES;                    // blocks per image
-    if (p.stats) {
-        if (p.stats_slices <= 0 || (p.stats_slices % bpi)) return 0;
-        const int spb = p.stats_slices / bpi;
-        if (spb != 1 && spb != 2 && spb != 4) return 0;
-    }
-    if (((uint64_t)(2 * R + 1) * (W + 2) + W + 1) * (uint64_t)Cin * 4 + 128 >= (1ull << 31) || (uint64_t)4 * Cout * Cin * 4 >= (1ull << 31)) return 0;
-    if (force) return R;
-    const int min_blocks = R == 2 ? WINO_FUSED_ROWS_MIN_BLOCKS : WINO_FUSED_ROWS_MIN_BLOCKS_16;
-    const uint64_t blocks = (uint64_t)p.B * bpi * (Cout / WINO_FUSED_BN);
-    return (min_blocks > 0 && blocks >= (uint64_t)min_blocks) ? R : 0;
-}
-
-// p as the kernels see it: an upsample conv becomes its four sub-pixel phases over the low-resolution pixels (one
-// launch: blockIdx.z picks (py, px)); splits / phase_slices / phase_part_stride are the plan's to fill
-static ConvParams phase_form(const ConvParams &p_in) {
-    ConvParams p = p_in;
-    if (!p.up2) return p;
-    p.ks = 2; p.stride = 1; p.up2 = 0;
-    p.Hout = p_in.Hout / 2; p.Wout = p_in.Wout / 2;
-    p.out_step = 2;
-    p.phases = 4;
-    p.phase_w_stride = (size_t)4 * p.out.C * (p.in0.C + (p.in1.p ? p.in1.C : 0));
-    return p;
-}
-
-const char *conv_kernel_name(ConvKernel k) {
-    static const char *const names[CK_COUNT] = {"wino_one_pass", "wino_three_pass", "halo_f8c", "halo_128x128_seg32", "halo_128x128_seg8",
-                                                "halo_128x64", "generic_128x32", "generic_128x64", "generic_64x64", "generic_128x128"};
-    return (unsigned)k < (unsigned)CK_COUNT ? names[k] : "?";
-}
-
-// Upsample convs (prec 0): tile rows per block of wino_up2_kernel (kernels_wino.hip), 0 = the four phase convs of `direct`.
-// Preconditions: one f32 input with its zero border, f32 output only, nothing fused but the biases; whole 32-channel
-// blocks on both sides; a low-resolution width of 16, 32 or a multiple of 64 and whole blocks of 32 tiles; an unsplit
-// direct plan; statistics absent or in the direct plan's slices of 128 pixels (one phase of a block: widths 16, 32, 64; two
-// strips of a tile row, run by one block: multiples of 128) or of 64 (half of that; few-tile shapes); 32-bit offsets of the input DMA (as wino_fused_kernel: bit
-// 31 of a lane's offset switches an instruction off) and of the weight loads (the nine planes of a phase).
-// Tuning: UP2_WINO_MIN_BLOCKS.
-static int up2_wino_rows(const ConvParams &p, const ConvPlan &direct) {
-    static const bool off = env_int("SR3_NO_UP2_WINO", 0) != 0;             // product switches (read once)
-    static const bool force = env_int("SR3_UP2_WINO_FORCE", 0) != 0;
-    if (off || !p.up2 || p.prec != 0 || p.f8 || p.ks != 3 || p.stride != 1 || !p.w_up_wino) return 0;
-    if (p.in1.p || p.in2.p || p.resid.p || p.out_split.p || !p.out_f32 || p.in0.pad != 1) return 0;
-    const int Hl = p.in0.H, Wl = p.in0.W, Cin = p.in0.C, Cout = p.out.C;
-    if (p.B <= 0 || 2 * Hl != p.Hout || 2 * Wl != p.Wout || (Cin % 32) || (Cout % UP2_WINO_BN)) return 0;
-    const int R = Wl == 16 ? 4 : Wl == 32 ? 2 : (Wl % 64) == 0 ? 1 : 0;
-    if (R == 0 || (Hl % (2 * R))) return 0;
-    if (direct.split != CS_NONE || direct.error) return 0;
-    if (p.stats) {
-        if ((direct.tile_m != 128 && direct.tile_m != 64) || p.stats_slices != 4 * (Hl * Wl / direct.tile_m)) return 0;
-        if (direct.tile_m == 128 && Wl > 64 && (Wl % 128)) return 0;
-    }
-    if (((uint64_t)10 * (Wl + 2) + 70) * (uint64_t)Cin * 4 >= (1ull << 31) || (uint64_t)9 * Cout * Cin * 4 >= (1ull << 31)) return 0;
-    const uint64_t blocks = (uint64_t)p.B * ((uint64_t)Hl * Wl / (4 * UP2_WINO_TILES)) * (Cout / UP2_WINO_BN);
-    return (force || blocks >= (uint64_t)UP2_WINO_MIN_BLOCKS) ? R : 0;
-}
-
-static ConvPlan conv_plan_direct(const ConvParams &p_in);
-ConvPlan conv_plan(const ConvParams &p_in) {
-    ConvPlan plan = conv_plan_direct(p_in);
-    plan.up2_wino = up2_wino_rows(p_in, plan);
-    return plan;
-}
-
-static ConvPlan conv_plan_direct(const ConvParams &p_in) {
-    const ConvParams p = phase_form(p_in);
-    const int Cout = p.out.C, Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
-    const int HWo = p.Hout * p.Wout;                 // pixels of one image (and phase)
-    const long M = (long)p.B * HWo;
-    const Tile t = conv_tile_choice(M, Cout);
-    ConvPlan plan;
-    plan.phases = p.phases;
-    plan.tile_m = t.bm; plan.tile_n = t.bn;
-    // split-K of the generic kernel: in place on the 64x64 tile where every tile has a counter, whole tiles per image (the
-    // statistics slices are per M-tile of an image) and in N (nothing is masked in the fix-up); else conv + reduce kernel
-    static const int no_inplace = env_int("SR3_NO_INPLACE_SPLIT", 0);
-    const int gs = p.part ? conv_splits(M, Cout, Cin) : 1;
-    const bool inplace = gs > 1 && p.tile_cnt && !no_inplace && t.generic == CK_GENERIC_64x64 && (HWo % t.bm) == 0 && (Cout % t.bn) == 0 &&
-                         tile_count(t, M, Cout) * p.phases <= CONV_TILE_COUNTERS;
-    // fused statistics: one slice per M-tile of an image (an in-place split conv leaves the same slices as an unsplit
-    // one; every kernel of one output shape uses the same tile height), a two-kernel split one slice per reduce block
-    plan.stats_slices = p.phases * ((gs > 1 && !inplace) ? splitk_stats_slices(HWo, Cout) : (HWo % t.bm) == 0 ? HWo / t.bm : 0);
-
-    const ConvKernel wino = wino_form(p);
-    if (wino != CK_COUNT) {
-        plan.kernel = wino;
-        plan.needs_wino_frag = wino == CK_WINO_ONE_PASS;       // (U and M never leave the CU)
-        if (wino == CK_WINO_THREE_PASS) {
-            plan.wino_ws_floats = (size_t)16 * p.B * (p.Hout / 2) * (p.Wout / 2) * (Cin + Cout);
-            plan.wino_fused_rows = wino_fused_rows(p, Cin);
-            plan.wino_gemm_out = plan.wino_fused_rows ? 0 : wino_gemm_out_bn(p, Cin);
-        }
-        return plan;
-    }
-    auto split = [&](ConvSplit kind, int splits) {
-        plan.split = kind; plan.splits = splits;
-        plan.part_floats = (size_t)p.phases * splits * M * Cout;
-        plan.needs_counters = kind != CS_REDUCE;
-    };
-    if (p.prec == 1 && p.ks == 3 && p.stride == 1 && p.phases == 1 && p.part != nullptr && p.tile_cnt != nullptr && p.in0.pad == 1 &&
-        p.in0.W == p.Wout && p.in0.H == p.Hout && !p.no_halo_split) {
-        const int hs = conv_halo_splits(M, p.Hout, p.Wout, Cout, Cin);
-        const bool stats_ok = p.stats == nullptr || p.stats_slices == (HWo >= 128 ? HWo / 128 : 1);
-        const bool seg32 = halo_ok(p, hs, 128, 32, 128, true);
-        if (hs > 1 && stats_ok && (seg32 || halo_ok(p, hs, 128, 8, 128, true))) {
-            plan.kernel = seg32 ? CK_HALO_128x128_SEG32 : CK_HALO_128x128_SEG8;
-            plan.tile_m = plan.tile_n = 128;
-            split(CS_INPLACE_HALO, hs);
-            return plan;
-        }
-    }
-    if (gs > 1) split(inplace ? CS_INPLACE : CS_REDUCE, gs);
-    if (p.f8) {
-        // the caller asked conv_f8_supported() first and wrote the input / passes the weights in the F8C format
-        // (conv_f8_supported is this plan's answer; a mismatch is a library bug, reported through the API's error
-        // path — nothing is launched, the process is never aborted)
-        if (!(p.prec == 1 && p.ks == 3 && p.phases == 1 && gs <= 1 && halo_ok(p, gs, 128, 8, 128)))
-            plan.error = "internal: fp8 correction products requested for a conv the F8C kernel does not support";
-        plan.kernel = CK_HALO_F8C;
-        plan.tile_m = plan.tile_n = 128;
-        return plan;
-    }
-    plan.kernel = t.generic;
-    if (t.generic == CK_GENERIC_128x64 && halo_ok(p, gs, 128, 32, 64)) plan.kernel = CK_HALO_128x64;
-    else if (t.generic == CK_GENERIC_128x128 && halo_ok(p, gs, 128, 32, 128)) plan.kernel = CK_HALO_128x128_SEG32;   // rows of 32+ pixels: one row segment per wave (ONESEG)
-    else if (t.generic == CK_GENERIC_128x128 && halo_ok(p, gs, 128, 8, 128)) plan.kernel = CK_HALO_128x128_SEG8;
-    return plan;
-}
-
-ConvPlan conv_plan_offered(int B, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int prec, bool f8, bool stats) {
-    static float buf;                    // (never dereferenced: a plan only asks whether a buffer is offered)
-    static unsigned cnt;
-    static double st;
-    const int pad = ks / 2, Hv = H << up2, Wv = W << up2;
-    ConvParams p;
-    p.in0.p = &buf; p.in0.C = Cin; p.in0.H = H; p.in0.W = W; p.in0.pad = 1;
-    p.B = B; p.ks = ks; p.stride = stride; p.up2 = up2; p.prec = prec; p.f8 = f8 ? 1 : 0;
-    p.Hout = (Hv + 2 * pad - ks) / stride + 1; p.Wout = (Wv + 2 * pad - ks) / stride + 1;
-    p.out.p = &buf; p.out.C = Cout; p.out.H = p.Hout; p.out.W = p.Wout;
-    p.w = p.w_wino = p.w_wino_f = p.w_up_wino = &buf;
-    p.part = p.wino_ws = &buf;
-    p.tile_cnt = &cnt;
-    if (stats) {
-        p.stats_slices = conv_plan(p).stats_slices;       // (the layout does not depend on what is offered beyond part / tile_cnt)
-        if (p.stats_slices) p.stats = &st;
-    }
-    return conv_plan(p);
-}
-
-// F8C ("f16f8" mode): 3x3 / stride-1 split-f16 convs that run on the 128x128 x-halo tile without split-K at the 32x32- and
-// 16x16-pixel levels — the MFMA-bound shapes, where the 32x32 consumers with the corrections on the fp8 path measured
-// 14-20 % faster than the f16x3 kernel (profiles/README.md finding 64); the 64x64- and 128x128-pixel levels are bound by
-// operand movement and gain nothing. Callers format the conv's input accordingly.
-bool conv_f8_supported(int B, int H, int W, int Cout, int Cin) {
-    constexpr int maxhw = 1024;         // pixels of one image: the 32x32 level and below
-    const int HWo = H * W;
-    if ((Cin % 32) || HWo > maxhw || HWo < 128 || (HWo % 128)) return false;
-    // where the f16x3 plan runs the conv unsplit on a 128x128 x-halo tile, the F8C kernel can take its place
-    const ConvPlan f16 = conv_plan_offered(B, H, W, Cin, Cout, 3, 1, 0, 1, false, false);
-    return f16.split == CS_NONE && (f16.kernel == CK_HALO_128x128_SEG32 || f16.kernel == CK_HALO_128x128_SEG8);
 }
 
 // first launch request of this thread that could not be honoured (nothing was launched for it); the API entry points

@@ -5,6 +5,7 @@
 // and ResnetBlock/SelfAttention.forward (:105-110, :123-142) as a sequence of HIP launches.
 #include "../../include/sr3hip.h"
 #include "sr3_internal.h"
+#include "conv_plan.h"
 
 #include <limits.h>
 #include <math.h>
@@ -832,24 +833,6 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
 // ---------------------------------------------------------------------------------------------
 const TDesc kNone{};
 
-// The form an apply pass takes: decided HERE for the engine (run_gn_act) and for sr3_op_groupnorm_apply's route 0
-enum GnRoute { GN_FOLDED = 1, GN_FINALIZE_ROWS = 2 };   // finalize folded into the apply launch | finalize launch + streaming rows
-// do the producers' epilogues cover the pass? (else the streaming statistics kernel runs first: launch_groupnorm_partials)
-bool gn_stats_fused(const TDesc &b, const StatsRef &sa, const StatsRef &sb) { return sa.p && (!b.p || sb.p); }
-GnRoute gn_route(const TDesc &a, const TDesc &b, int B, const StatsRef &sa, const StatsRef &sb) {
-    if (!gn_stats_fused(b, sa, sb)) return GN_FOLDED;
-    // bytes the pass moves (read + write, 4 B per element each way): above ~200 MB the one-item-per-thread
-    // streaming kernel behind a separate finalize launch is faster than the folded form (A/B on one box,
-    // profiles/README.md); below it the launch saved and the shorter critical path win
-    const double pass_bytes = 8.0 * B * a.H * a.W * (a.C + (b.p ? b.C : 0));
-    constexpr double fold_max = 200.0 * 1e6;
-    // few images with many statistics slices (a single 128x128 image on 64x64 tiles leaves 256): the folded form's
-    // prologue walks them in 12-16 dependent round trips in EVERY block (12-23 us per apply at B = 1); the
-    // per-(image, group) finalize launch takes one round trip
-    const bool many_slices = (long)B * 4 < 128 && std::max(sa.slices, b.p ? sb.slices : 0) >= 64;
-    return (pass_bytes > fold_max || many_slices) ? GN_FINALIZE_ROWS : GN_FOLDED;
-}
-
 // scratch of an apply pass: scale / shift [B][C] of the finalize launch, partials of the statistics kernel (gn_workspace_floats)
 struct GnScratch { float *scale = nullptr, *shift = nullptr, *part = nullptr; };
 
@@ -969,54 +952,10 @@ ConvParams conv_params(const sr3_ctx *c, const ConvCall &k) {
     return p;
 }
 
-// SR3_NO_GN_WINO=1 (product switch, read once): the parent's two passes in front of every three-pass Winograd conv
-bool gn_wino_off() {
-    static const bool off = env_int("SR3_NO_GN_WINO", 0) != 0;
-    return off;
-}
-
 // Does the GroupNorm apply pass in front of conv k write the conv's Winograd input transform (into c->wino_ws) instead
-// of k.in? Where the conv's plan is the three-pass form (not its wino_fused_rows form, which reads the zero-bordered
-// activated tensor like the one-pass plan), in f32 with unsplit inputs and no raw side output wanted
-// (raw_wanted also stands for "the pass applies a Dropout mask": only launch_gn_apply* know one).
+// of k.in? gn_pass_writes_u's answer for the conv's plan, asked before the conv's input exists
 bool gn_writes_u(const sr3_ctx *c, const ConvCall &k, bool raw_wanted, int in_split) {
-    if (gn_wino_off() || c->split() || raw_wanted || in_split) return false;
-    const ConvPlan pl = conv_plan(conv_params(c, k));
-    return pl.kernel == CK_WINO_THREE_PASS && !pl.wino_fused_rows;
-}
-
-// SR3_NO_GN_RES1X1=1 / SR3_GN_RES1X1_FORCE=1 (product switches, read once)
-bool gn_res1x1_off() {
-    static const bool off = env_int("SR3_NO_GN_RES1X1", 0) != 0;
-    return off;
-}
-bool gn_res1x1_force() {
-    static const bool force = env_int("SR3_GN_RES1X1_FORCE", 0) != 0;
-    return force;
-}
-
-// Does block1's GroupNorm + Swish pass also multiply the block's 1x1 res_conv (launch_gn_res1x1 in place of the apply pass
-// and of the side launch of conv2's Winograd plan)? Decided HERE, before block1's pass runs, for the engine (run_res),
-// sr3_op_gn_res1x1 and sr3_gn_res1x1_gate.
-//   valid: exact f32 and a res_conv whose operands are x / skip themselves, unsplit (`direct`, in_split 0, no raw copy
-//          wanted); mode 2; conv1 reads the plain activated tensor (its pass does not write U); conv2's plan is a Winograd
-//          plan, so that today's 1x1 is a side launch; the kernel's shapes (gn_res1x1_shape_ok).
-//   tuned: the levels where every shape of the B = 64 step measured at or under 0.9 of the pair (profiles/README.md,
-//          finding 99), from GN_RES1X1_MIN_BLOCKS blocks on (the smallest count timed).
-struct GnResGate { bool valid = false, tuned = false; bool takes() const { return valid && (tuned || gn_res1x1_force()) && !gn_res1x1_off(); } };
-constexpr int GN_RES1X1_MIN_HW = 32 * 32;       // pixels of one image: the 32x32 level and above
-constexpr long GN_RES1X1_MIN_BLOCKS = 1024;
-GnResGate gn_res1x1_gate(int prec, bool has_res, bool direct, bool raw_wanted, int in_split, int mode, bool conv1_reads_u,
-                         const ConvPlan &pl2, int B, int H, int W, int C0, int C1, int Cout) {
-    GnResGate g;
-    const bool wino2 = pl2.kernel == CK_WINO_ONE_PASS || pl2.kernel == CK_WINO_THREE_PASS;
-    g.valid = prec == 0 && has_res && direct && !raw_wanted && !in_split && mode == 2 && !conv1_reads_u && wino2 &&
-              gn_res1x1_shape_ok(H, W, C0, C1, Cout);
-    if (g.valid) {
-        const long blocks = ((long)B * H * W / 128) * (Cout / gn_res1x1_bn(B, H, W, Cout));
-        g.tuned = (long)H * W >= GN_RES1X1_MIN_HW && blocks >= GN_RES1X1_MIN_BLOCKS;
-    }
-    return g;
+    return gn_pass_writes_u(c->split(), conv_plan(conv_params(c, k)), raw_wanted, in_split);
 }
 
 // launch_conv on the context's stream; counts the convs whose plan takes the one-kernel form of the three-pass Winograd
@@ -1904,6 +1843,30 @@ void fill_random(sr3_ctx *c, float *q, size_t n, int seed) {
     launch_philox_normal(seed, 0, 0, (int)std::min<size_t>(n, 1u << 30), q, c->stream);
 }
 
+// The timing tail of the per-shape benchmarks: `iters` back-to-back repetitions of `first`, then of `second`, on the
+// context's stream between three events (the caller warms up); the average of each phase in ms. The events are
+// destroyed on every return.
+template <class First, class Second>
+int time_two_phases(sr3_ctx *c, int iters, First &&first, Second &&second, float *first_ms, float *second_ms) {
+    struct Events {
+        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+        ~Events() { for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev); }
+    } ev;
+    for (hipEvent_t &e : ev.e) HIP_OK(hipEventCreate(&e));
+    HIP_OK(hipEventRecord(ev.e[0], c->stream));
+    for (int i = 0; i < iters; ++i) first();
+    HIP_OK(hipEventRecord(ev.e[1], c->stream));
+    for (int i = 0; i < iters; ++i) second();
+    HIP_OK(hipEventRecord(ev.e[2], c->stream));
+    HIP_OK(hipEventSynchronize(ev.e[2]));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    *first_ms = ms / iters;
+    HIP_OK(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+    *second_ms = ms / iters;
+    return 0;
+}
+
 // the weights of conv2's fused 1x1 term as run_res hands them over: a res_conv (w2_host: [Cout][C2], OIHW of a 1x1
 // conv), or — split-f16 arithmetics — the identity skip as extra K-steps (ident: ResBlock::ident_w)
 struct FusedTerm {
@@ -2031,10 +1994,8 @@ struct ScratchConv {
         p.ovf = c->d_ovf;            // (range bits of twin stores and the 'wait gave up' bit of the in-place split-K)
         return 0;
     }
-    // the engine's rule (gn_writes_u of the UNet's convs): the apply pass in front of this conv writes U into wino_ws
-    bool gn_writes_u(const sr3_ctx *c) const {
-        return !gn_wino_off() && !c->split() && plan.kernel == CK_WINO_THREE_PASS && !plan.wino_fused_rows;
-    }
+    // the engine's rule (gn_pass_writes_u): the apply pass in front of this conv writes U into wino_ws
+    bool gn_writes_u(const sr3_ctx *c) const { return gn_pass_writes_u(c->split(), plan, false, 0); }
 };
 
 } // namespace
@@ -2066,7 +2027,7 @@ int sr3_create(const sr3_unet_cfg *cfg, int device, sr3_ctx **out) {
     sr3_ctx *c = new sr3_ctx();
     c->cfg = *cfg;
     c->device = device;
-    c->no_graph = env_int("SR3_NO_GRAPH", 0) != 0;                  // product switch
+    c->no_graph = env_switch_now(SW_NO_GRAPH) != 0;                 // product switch, read per context
     if (build_graph(c)) { delete c; return -1; }
     if (alloc_weights(c)) { sr3_destroy(c); return -1; }
     if (hipStreamCreate(&c->own_stream) != hipSuccess) { sr3_destroy(c); return fail("hipStreamCreate failed"); }
@@ -3619,27 +3580,18 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
     p.chan_bias = with_chan_bias ? cb.p : nullptr; p.chan_bias_stride = Cout;
     if (with_resid) p.resid = res;
     p.out = out;
-    hipEvent_t e0, e1, e2;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1)); HIP_OK(hipEventCreate(&e2));
     // as the engine runs the shape: behind the fused pass the conv starts from U (random contents like every input here)
     const bool to_u = sc.gn_writes_u(c);
     if (to_u) { fill_random(c, p.wino_ws, (size_t)16 * B * (Hin / 2) * (Win / 2) * Cin, 11); p.u_ready = 1; }
-    for (int i = 0; i < 2; ++i) ctx_launch_conv(c, p);       // (the counters tell a tool which form it timed)
-    HIP_OK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < iters; ++i) ctx_launch_conv(c, p);
-    HIP_OK(hipEventRecord(e1, c->stream));
-    for (int i = 0; i < iters; ++i) {
+    auto conv = [&] { ctx_launch_conv(c, p); };              // (the counters tell a tool which form it timed)
+    auto apply = [&] {
         if (to_u) launch_gn_wino_input(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, p.wino_ws, c->stream);
         else launch_gn_apply(i0, C1 ? i1 : kNone, B, scale.p, shift.p, mode, c->act_format(sc.f8), p.in0, c->stream);
-    }
-    HIP_OK(hipEventRecord(e2, c->stream));
-    HIP_OK(hipEventSynchronize(e2));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / iters;
-    HIP_OK(hipEventElapsedTime(&ms, e1, e2));
-    if (apply_ms) *apply_ms = ms / iters;
-    HIP_OK(hipEventDestroy(e0)); HIP_OK(hipEventDestroy(e1)); HIP_OK(hipEventDestroy(e2));
+    };
+    float ms_apply = 0.f;
+    for (int i = 0; i < 2; ++i) conv();
+    if (time_two_phases(c, iters, conv, apply, avg_ms, &ms_apply)) return -1;
+    if (apply_ms) *apply_ms = ms_apply;
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -3653,9 +3605,7 @@ int sr3_bench_gn_res1x1(sr3_ctx *c, int B, int H, int W, int C0, int C1, int Cou
     const char *what = "sr3_bench_gn_res1x1";
     if (!c || !pair_ms || !one_ms || iters < 1) return fail("%s: bad argument", what);
     const int C = C0 + C1;
-    ConvPlan wino;
-    wino.kernel = CK_WINO_ONE_PASS;
-    if (B < 1 || groups <= 0 || C % groups || !gn_res1x1_gate(c->split() ? 1 : 0, true, true, false, 0, 2, false, wino, B, H, W, C0, C1, Cout).valid)
+    if (B < 1 || groups <= 0 || C % groups || !gn_res1x1_gate_op(c->split() ? 1 : 0, B, H, W, C0, C1, Cout).valid)
         return fail("%s: shape refused by the gate", what);
     HIP_OK(hipSetDevice(c->device));
     TDesc x, sk, act, out;
@@ -3694,21 +3644,8 @@ int sr3_bench_gn_res1x1(sr3_ctx *c, int B, int H, int W, int C0, int C1, int Cou
     auto one = [&] {
         launch_gn_act(route, x, b, B, groups, dg.p, db.p, 2, 0, act, sa, sb, ws, TDesc(), 0, nullptr, nullptr, DropLayer(), c->stream, &res);
     };
-    hipEvent_t e0, e1, e2;
-    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1)); HIP_OK(hipEventCreate(&e2));
     for (int i = 0; i < 2; ++i) { pair(); one(); }
-    HIP_OK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < iters; ++i) pair();
-    HIP_OK(hipEventRecord(e1, c->stream));
-    for (int i = 0; i < iters; ++i) one();
-    HIP_OK(hipEventRecord(e2, c->stream));
-    HIP_OK(hipEventSynchronize(e2));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-    *pair_ms = ms / iters;
-    HIP_OK(hipEventElapsedTime(&ms, e1, e2));
-    *one_ms = ms / iters;
-    HIP_OK(hipEventDestroy(e0)); HIP_OK(hipEventDestroy(e1)); HIP_OK(hipEventDestroy(e2));
+    if (time_two_phases(c, iters, pair, one, pair_ms, one_ms)) return -1;
     if (const char *e = conv_take_error()) return fail("%s: %s", what, e);
     HIP_OK(hipGetLastError());
     return 0;
@@ -3722,17 +3659,12 @@ int sr3_op_groupnorm_affine(sr3_ctx *c, const float *in0_dev, int C0, const floa
     const int C = C0 + C1;
     if (groups <= 0 || C % groups) return fail("groups=%d does not divide C=%d", groups, C);
     HIP_OK(hipSetDevice(c->device));
-    float *dg = nullptr, *db = nullptr, *part = nullptr;
-    HIP_OK(hipMalloc(&dg, (size_t)C * sizeof(float)));
-    HIP_OK(hipMalloc(&db, (size_t)C * sizeof(float)));
-    HIP_OK(hipMalloc(&part, gn_workspace_floats(B, C) * sizeof(float)));
-    HIP_OK(hipMemcpy(dg, gamma_host, (size_t)C * sizeof(float), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(db, beta_host, (size_t)C * sizeof(float), hipMemcpyHostToDevice));
+    DevBuf dg, db, part;
+    if (dg.upload(gamma_host, (size_t)C) || db.upload(beta_host, (size_t)C) || part.alloc(gn_workspace_floats(B, C))) return -1;
     launch_groupnorm_affine(unpadded(const_cast<float *>(in0_dev), C0, H, W),
-                            in1_dev ? unpadded(const_cast<float *>(in1_dev), C1, H, W) : kNone, B, groups, dg, db,
-                            1e-5f, part, scale_dev, shift_dev, c->stream);
+                            in1_dev ? unpadded(const_cast<float *>(in1_dev), C1, H, W) : kNone, B, groups, dg.p, db.p,
+                            1e-5f, part.p, scale_dev, shift_dev, c->stream);
     HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipFree(dg)); HIP_OK(hipFree(db)); HIP_OK(hipFree(part));
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -3794,7 +3726,7 @@ int sr3_gn_res1x1_gate(int B, int H, int W, int C0, int C1, int Cout, int precis
         // the engine's convs: fused statistics offered, every buffer offered
         pl1 = conv_plan_offered(B, H, W, C0 + C1, Cout, 3, 1, 0, precision ? 1 : 0, false, true);
         pl2 = conv_plan_offered(B, H, W, Cout, Cout, 3, 1, 0, precision ? 1 : 0, false, true);
-        reads_u = !gn_wino_off() && !precision && !raw_wanted && !in_split && pl1.kernel == CK_WINO_THREE_PASS && !pl1.wino_fused_rows;
+        reads_u = gn_pass_writes_u(precision != 0, pl1, raw_wanted, in_split ? 1 : 0);
     }
     const GnResGate g = gn_res1x1_gate(precision ? 1 : 0, has_res, direct, raw_wanted, in_split ? 1 : 0, mode, reads_u, pl2, B, H, W, C0, C1, Cout);
     return (g.valid ? 1 : 0) | (g.tuned ? 2 : 0) | (g.takes() ? 4 : 0);
@@ -3809,11 +3741,7 @@ int sr3_op_gn_res1x1(sr3_ctx *c, const float *x_dev, int C0, const float *skip_d
     const int C = C0 + C1;
     if (B < 1 || H < 1 || W < 1 || C0 <= 0 || C1 < 0 || Cout <= 0) return fail("%s: bad size B=%d H=%d W=%d C0=%d C1=%d Cout=%d", what, B, H, W, C0, C1, Cout);
     if (groups <= 0 || C % groups) return fail("%s: groups=%d does not divide C=%d", what, groups, C);
-    // the engine's gate with everything that is not a property of this call granted: a res_conv over unsplit x / skip, mode
-    // 2, conv1 reading the plain activated tensor and a Winograd plan for conv2 (a single op has no convs around it)
-    ConvPlan wino;
-    wino.kernel = CK_WINO_ONE_PASS;
-    if (!gn_res1x1_gate(c->split() ? 1 : 0, true, true, false, 0, 2, false, wino, B, H, W, C0, C1, Cout).valid)
+    if (!gn_res1x1_gate_op(c->split() ? 1 : 0, B, H, W, C0, C1, Cout).valid)
         return fail("%s: refused by the gate (exact f32 only; C0=%d, C1=%d in multiples of 32, at most %d together; Cout=%d a multiple of "
                     "64; H*W=%d a multiple of 128)", what, C0, C1, GN_RES1X1_MAX_CIN, Cout, H * W);
     HIP_OK(hipSetDevice(c->device));

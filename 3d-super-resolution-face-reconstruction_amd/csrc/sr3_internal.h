@@ -8,9 +8,11 @@
 namespace sr3 {
 
 // ---- environment switches ---------------------------------------------------------------------------
-// Everything the library reads from the environment (INTEGRATION.md lists the same fourteen; each is read once per process
-// and then baked into captured graphs):
-//   SR3_NO_GRAPH=1          every kernel launched individually, no hipGraph replay (hosts that cannot capture)
+// Everything the library reads from the environment (INTEGRATION.md lists the same names, tests/test_switches_host.py
+// compares; each is read on its first use in a process and then baked into captured graphs). All but the last are
+// entries of ONE table, read through env_switch / form_switch (conv_plan.h):
+//   SR3_NO_GRAPH=1          every kernel launched individually, no hipGraph replay (hosts that cannot capture); the one
+//                           switch read again by every sr3_create
 //   SR3_NO_HALO=1           generic implicit-GEMM kernel instead of the x-halo kernels (safety switch; slower)
 //   SR3_HALO_SPLITS=0|2|4   in-place split-K of deep-K convs on 128x128 x-halo tiles: off / forced
 //   SR3_NO_INPLACE_SPLIT=1  split-K always as conv + reduce kernel
@@ -33,6 +35,8 @@ namespace sr3 {
 //                           two launches (the library before gn_res1x1_kernel; same bits)
 //   SR3_GN_RES1X1_FORCE=1   that kernel wherever its preconditions hold, whatever the level and block count (tests,
 //                           per-shape timing)
+//   SR3_THRESHOLD_BLOCKS=N  blocks that share one image in the selection of the dynamic threshold instead of one per
+//                           16384 keys (per-shape timing; same bits); read where kernels_threshold.hip plans a selection
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Activation tensor: NHWC fp32 with an optional 1-pixel zero border ("pad") stored around every
@@ -140,7 +144,7 @@ struct ConvParams {
     // launch_conv_wino then skips wino_input_kernel and does nothing else differently. No input of conv_plan.
     int u_ready = 0;
     // 1 (Winograd plans with the fused 1x1 term only): out already holds w2 . (in2 || in2b) — launch_gn_res1x1 wrote it in
-    // block1's GroupNorm pass (sr3_api.hip: gn_res1x1_gate) — so launch_conv_wino skips its 1x1 side launch and takes out
+    // block1's GroupNorm pass (conv_plan.hip: gn_res1x1_gate) — so launch_conv_wino skips its 1x1 side launch and takes out
     // as the residual, and does nothing else differently. No input of conv_plan.
     int res_ready = 0;
     // GEMM batch (launch_wino_gemm only): blockIdx.z = z multiplies in0.p + z * batch_in_stride by

@@ -1,5 +1,5 @@
 """The gate that decides whether block1's GroupNorm + Swish pass also multiplies the block's 1x1 res_conv
-(csrc/sr3_api.hip: gn_res1x1_gate), asked through the host-only export sr3_gn_res1x1_gate — no GPU.
+(csrc/conv_plan.hip: gn_res1x1_gate), asked through the host-only export sr3_gn_res1x1_gate — no GPU.
 
 valid  exact f32; a res_conv whose operands are x / skip themselves, unsplit, no raw copy wanted; mode 2; conv1 reads the
        plain activated tensor (its GroupNorm pass does not write the Winograd U); conv2's plan is a Winograd plan;
@@ -22,7 +22,7 @@ synth = pkg("synth")
 
 SWITCHES = ("SR3_NO_GN_RES1X1", "SR3_GN_RES1X1_FORCE", "SR3_NO_GN_WINO", "SR3_NO_WINOGRAD", "SR3_NO_WINO_FUSED_ROWS",
             "SR3_WINO_FUSED_ROWS_FORCE")
-MAX_CIN, MIN_HW, MIN_BLOCKS = 1024, 32 * 32, 1024         # csrc/sr3_internal.h, csrc/sr3_api.hip
+MAX_CIN, MIN_HW, MIN_BLOCKS = 1024, 32 * 32, 1024         # csrc/sr3_internal.h, csrc/conv_plan.hip
 
 
 @pytest.fixture(autouse=True)
