@@ -85,6 +85,9 @@ PROTOTYPES = {
     "sr3_num_frames_from": (_I, [_P, _I]),
     "sr3_rows_begin": (_I, [_P, _I, _I, _I, _U64]),
     "sr3_rows_admit": (_I, [_P, _I, _F, _F, _I, _I, _F, _U64]),
+    "sr3_rows_lr_consistency": (_I, [_P, _I, _I]),
+    "sr3_rows_admit_lr": (_I, [_P, _I, _F, _F, _I, _I, _F, _U64, _F, C.c_float]),
+    "sr3_rows_frames": (_I, [_P, _I, _F, _I]),
     "sr3_rows_step": (_I, [_P, C.POINTER(_F)]),
     "sr3_rows_position": (_I, [_P, _I]),
     "sr3_rows_retire": (_I, [_P, _I, _F]),
@@ -144,6 +147,7 @@ PROTOTYPES = {
     "sr3_lr_operators_host": (_I, [_I, _I, _P, _P]),
     "sr3_set_lr_consistency": (_I, [_P, _F, _I, _I, _I, _U64, C.c_float]),
     "sr3_op_lr_project": (_I, [_P, _F, _I, _I, _I, _I, _F, _I, _I, _I, _U64, C.c_float, _I]),
+    "sr3_op_lr_project_rows": (_I, [_P, _F, _I, _I, _I, _I, _F, _I, _I, _P, _P, _I]),
     "sr3_lr_residual": (_I, [_P, _F, _I, _I, _I, _I, _F, _I, _I, _I, _U64, _P, _P]),
     "sr3_set_dynamic_threshold": (_I, [_P, C.c_float, C.c_float]),
     "sr3_op_abs_quantile": (_I, [_P, _F, _I, C.c_int64, C.c_float, C.c_float, _F, _F, _F]),
@@ -168,7 +172,8 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_dynamic_threshold_launches", "sr3_set_feature_cache", "sr3_feature_cache_steps", "sr3_unet_forward_cached", "sr3_step_graph_captures",
                   "sr3_rows_begin", "sr3_rows_admit", "sr3_rows_step", "sr3_rows_position", "sr3_rows_retire", "sr3_rows_drop",
                   "sr3_rows_end", "sr3_op_conv2d_fused", "sr3_op_attention_twin", "sr3_gn_res1x1_launches", "sr3_gn_res1x1_gate",
-                  "sr3_op_gn_res1x1", "sr3_bench_gn_res1x1")
+                  "sr3_op_gn_res1x1", "sr3_bench_gn_res1x1", "sr3_rows_lr_consistency", "sr3_rows_admit_lr", "sr3_rows_frames",
+                  "sr3_op_lr_project_rows")
 
 _lib = None
 

@@ -132,14 +132,10 @@ __device__ __forceinline__ const float *lr_plane(const LrArgs &a, const LrOps &o
 // one block per plane; LDS: T [H][lw] (reused for U) | R [lh][lw]. B*C planes are fewer blocks than the device has compute
 // units at the sampler's batch sizes, so a plane of 64 x 64 or more takes 1024 threads (the stages are latency-bound
 // chains of loads and fmaf: at B = 64, 16 -> 128, 82 us with 256 threads, 67 us with 1024; profiles/README.md finding 87).
-__global__ void __launch_bounds__(1024) lr_project_lds_kernel(float *__restrict__ X, int C, const LrOps o, const LrArgs val,
-                                                             const LrArgs *dyn) {
-    extern __shared__ float lds[];
+// the four stages of one plane xp [H][W] against Y [lh][lw], by the whole block (both LDS kernels: the same statements)
+__device__ __forceinline__ void lr_project_plane_lds(float *__restrict__ xp, const float *__restrict__ Y, const LrOps &o,
+                                                     float strength, float *lds) {
     float *T = lds, *R = lds + (size_t)o.H * o.lw;
-    const LrArgs a = dyn ? *dyn : val;
-    const int plane = blockIdx.x;
-    float *xp = X + (size_t)plane * o.H * o.W;
-    const float *Y = lr_plane(a, o, plane, C);
     const int nT = o.H * o.lw, nR = o.lh * o.lw, nX = o.H * o.W;
     for (int e = threadIdx.x; e < nT; e += blockDim.x) {
         const int y = e / o.lw, j = e - y * o.lw;
@@ -158,8 +154,73 @@ __global__ void __launch_bounds__(1024) lr_project_lds_kernel(float *__restrict_
     __syncthreads();
     for (int e = threadIdx.x; e < nX; e += blockDim.x) {
         const int y = e / o.W, x = e - y * o.W;
-        xp[e] = stage_x(xp[e], T + (size_t)y * o.lw, o, x, a.strength);
+        xp[e] = stage_x(xp[e], T + (size_t)y * o.lw, o, x, strength);
     }
+}
+
+__global__ void __launch_bounds__(1024) lr_project_lds_kernel(float *__restrict__ X, int C, const LrOps o, const LrArgs val,
+                                                             const LrArgs *dyn) {
+    extern __shared__ float lds[];
+    const LrArgs a = dyn ? *dyn : val;
+    const int plane = blockIdx.x;
+    lr_project_plane_lds(X + (size_t)plane * o.H * o.W, lr_plane(a, o, plane, C), o, a.strength, lds);
+}
+
+// ---- the rows form (rolling batch): the LR image and the strength of a plane come from its row's slot ---------------
+// strength of the row a plane belongs to; 0: the plane is not touched (idle slot, or a row admitted without an LR image)
+__device__ __forceinline__ float row_strength(const RowArgs *__restrict__ rows, int b) {
+    return rows[b].live ? rows[b].lr_strength : 0.f;
+}
+
+// (the test is uniform over the block: all of it leaves before the first barrier, or none)
+__global__ void __launch_bounds__(1024) lr_project_lds_rows_kernel(float *__restrict__ X, int C, const LrOps o,
+                                                                  const float *__restrict__ lr_rows,
+                                                                  const RowArgs *__restrict__ rows) {
+    extern __shared__ float lds[];
+    const int plane = blockIdx.x;
+    const float strength = row_strength(rows, plane / C);
+    if (strength == 0.f) return;
+    lr_project_plane_lds(X + (size_t)plane * o.H * o.W, lr_rows + (size_t)plane * o.lh * o.lw, o, strength, lds);
+}
+
+__global__ void lr_rows_stage_t_kernel(const float *__restrict__ X, int C, const LrOps o, const RowArgs *__restrict__ rows,
+                                       float *__restrict__ T, size_t total) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // over planes*H*lw
+    if (e >= total) return;
+    const int j = (int)(e % o.lw);
+    const size_t row = e / o.lw;                                        // plane*H + y
+    if (row_strength(rows, (int)(row / o.H / C)) == 0.f) return;
+    T[e] = stage_t(X + row * o.W, o, j);
+}
+__global__ void lr_rows_stage_r_kernel(const float *__restrict__ T, int C, const LrOps o, const float *__restrict__ lr_rows,
+                                       const RowArgs *__restrict__ rows, float *__restrict__ R, size_t total) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // over planes*lh*lw
+    if (e >= total) return;
+    const int nR = o.lh * o.lw;
+    const int plane = (int)(e / nR), r = (int)(e - (size_t)plane * nR);
+    if (row_strength(rows, plane / C) == 0.f) return;
+    const int i = r / o.lw, j = r - i * o.lw;
+    R[e] = stage_r(T + (size_t)plane * o.H * o.lw, lr_rows[e], o, i, j);
+}
+__global__ void lr_rows_stage_u_kernel(const float *__restrict__ R, int C, const LrOps o, const RowArgs *__restrict__ rows,
+                                       float *__restrict__ U, size_t total) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // over planes*H*lw
+    if (e >= total) return;
+    const int j = (int)(e % o.lw);
+    const size_t row = e / o.lw;
+    const size_t plane = row / o.H;
+    if (row_strength(rows, (int)(plane / C)) == 0.f) return;
+    U[e] = stage_u(R + plane * o.lh * o.lw, o, (int)(row - plane * o.H), j);
+}
+__global__ void lr_rows_stage_x_kernel(float *__restrict__ X, const float *__restrict__ U, int C, const LrOps o,
+                                       const RowArgs *__restrict__ rows, size_t total) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // over planes*H*W
+    if (e >= total) return;
+    const int x = (int)(e % o.W);
+    const size_t row = e / o.W;
+    const float lambda = row_strength(rows, (int)(row / o.H / C));
+    if (lambda == 0.f) return;
+    X[e] = stage_x(X[e], U + row * o.lw, o, x, lambda);
 }
 
 // the same stages as four launches over global scratch: T [planes][H][lw] | U [planes][H][lw] | R [planes][lh][lw]
@@ -247,6 +308,23 @@ void launch_lr_project(float *x, int planes, int C, const LrOps &o, const LrArgs
     hipLaunchKernelGGL(lr_stage_r_kernel, dim3(nblk(nR)), dim3(256), 0, s, T, C, o, val, dyn, R, nR);
     hipLaunchKernelGGL(lr_stage_u_kernel, dim3(nblk(nT)), dim3(256), 0, s, R, o, U, nT);
     hipLaunchKernelGGL(lr_stage_x_kernel, dim3(nblk(nX)), dim3(256), 0, s, x, U, o, val, dyn, nX);
+}
+
+void launch_lr_project_rows(float *x, int B, int C, const LrOps &o, const float *lr_rows, const RowArgs *rows, bool lds_form,
+                            float *scratch, hipStream_t s) {
+    const int planes = B * C;
+    if (planes <= 0) return;
+    if (lds_form) {
+        const int threads = (size_t)o.H * o.W >= 4096 ? 1024 : 256;
+        hipLaunchKernelGGL(lr_project_lds_rows_kernel, dim3(planes), dim3(threads), lr_lds_bytes(o), s, x, C, o, lr_rows, rows);
+        return;
+    }
+    const size_t nT = (size_t)planes * o.H * o.lw, nR = (size_t)planes * o.lh * o.lw, nX = (size_t)planes * o.H * o.W;
+    float *T = scratch, *U = scratch + nT, *R = scratch + 2 * nT;
+    hipLaunchKernelGGL(lr_rows_stage_t_kernel, dim3(nblk(nT)), dim3(256), 0, s, x, C, o, rows, T, nT);
+    hipLaunchKernelGGL(lr_rows_stage_r_kernel, dim3(nblk(nR)), dim3(256), 0, s, T, C, o, lr_rows, rows, R, nR);
+    hipLaunchKernelGGL(lr_rows_stage_u_kernel, dim3(nblk(nT)), dim3(256), 0, s, R, C, o, rows, U, nT);
+    hipLaunchKernelGGL(lr_rows_stage_x_kernel, dim3(nblk(nX)), dim3(256), 0, s, x, U, C, o, rows, nX);
 }
 
 void launch_lr_residual(const float *img, int B, int C, const LrOps &o, const LrArgs &val, float *scratch, double *sumsq,

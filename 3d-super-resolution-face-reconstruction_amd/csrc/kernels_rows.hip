@@ -50,6 +50,7 @@ __device__ __forceinline__ void finish_update(const RowsUpdateParams &u, const R
         pk[8] = (_Float16)(v - (float)hi);
         if (u.ovf != nullptr && ((unsigned)__builtin_bit_cast(unsigned short, hi) & 0x7C00u) == 0x7C00u) *u.ovf = 1;
     }
+    if (ra.frame) ra.frame[(size_t)e.c * e.HW + e.pp] = v;     // (the row's own [C][HW] frame of this step)
 }
 
 __global__ void rows_update_kernel(const RowsUpdateParams u, size_t total) {

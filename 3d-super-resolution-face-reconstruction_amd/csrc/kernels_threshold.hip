@@ -126,6 +126,14 @@ __global__ __launch_bounds__(THR_THREADS) void thr_final_kernel(const unsigned *
     if (s_out) s_out[blockIdx.x] = fminf(fmaxf(s_raw, 1.0f), max_value);
 }
 
+// the counts back to zero, as a kernel. A workaround: with a hipMemsetAsync here (a memset node of the captured step) a
+// thresholded rows step with the projection gave other images replayed from its graph than run eagerly, and with this
+// kernel it does not; why is not explained
+__global__ void thr_zero_kernel(unsigned *__restrict__ bins, size_t total) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) bins[i] = 0u;
+}
+
 __global__ void thr_apply_kernel(float *__restrict__ x, long n, size_t total, const float *__restrict__ s_all) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
@@ -156,7 +164,8 @@ ThrPlan threshold_plan(float ratio, int64_t n) {
 
 void launch_abs_quantile(const float *x, int B, int64_t n, const ThrPlan &p, float max_value, unsigned *bins, float *lo, float *hi,
                          float *s, hipStream_t st) {
-    (void)hipMemsetAsync(bins, 0, threshold_bins_bytes(B), st);
+    const size_t total = (size_t)B * THR_BINS_PER_IMAGE;
+    hipLaunchKernelGGL(thr_zero_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, bins, total);
     for (int pass = 0; pass < THR_PASSES; ++pass)
         hipLaunchKernelGGL(thr_count_kernel, dim3(p.blocks, B), dim3(THR_THREADS), 0, st, x, (long)n, bins, pass, p.k, p.k2);
     hipLaunchKernelGGL(thr_final_kernel, dim3(B), dim3(THR_THREADS), 0, st, (const unsigned *)bins, p.k, p.k2, p.frac, max_value, lo, hi, s);

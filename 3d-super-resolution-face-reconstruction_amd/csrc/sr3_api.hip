@@ -137,14 +137,16 @@ struct StepKey {
     float *dyn_s = nullptr;
     unsigned *dyn_bins = nullptr;
     RowArgs *rows = nullptr;        // rolling batch (sr3_rows_step): the per-row argument table; null: the uniform step
+    const float *rows_lr = nullptr; // rows && lr (a session armed by sr3_rows_lr_consistency): the per-slot LR images
 
     // one graph is kept per (arithmetic, whole | shallow, form): 24 at the most, and per (arithmetic, plain | dynamic
-    // threshold) of the rows form (always whole, never projected): 6 more. A rows step and a uniform one never share a slot.
+    // threshold, unarmed | armed for the projection) of the rows form (always whole): 12 more. A rows step and a uniform
+    // one never share a slot, nor do the steps of an armed and of an unarmed session.
     bool same_slot(const StepKey &o) const {
         return mode == o.mode && (depth > 0) == (o.depth > 0) && lr == o.lr && dyn == o.dyn && (rows != nullptr) == (o.rows != nullptr);
     }
     auto tie() const {
-        return std::tie(mode, depth, lr, dyn, rows, x0hat, lr_ops.Av, lr_ops.Ah, lr_ops.Pv, lr_ops.PhT, lr_ops.bv, lr_ops.bh, lr_ops.lh,
+        return std::tie(mode, depth, lr, dyn, rows, rows_lr, x0hat, lr_ops.Av, lr_ops.Ah, lr_ops.Pv, lr_ops.PhT, lr_ops.bv, lr_ops.bh, lr_ops.lh,
                         lr_ops.lw, lr_ops.H, lr_ops.W, lr_lds, lr_scratch, dyn_n, dyn_plan.k, dyn_plan.k2, dyn_plan.frac,
                         dyn_plan.blocks, dyn_max, dyn_s, dyn_bins);
     }
@@ -314,8 +316,25 @@ struct sr3_ctx {
     // is authoritative: rows[r].pos steps are left for slot r (its next step is t = pos - 1). d_rows: the table the
     // kernels read, rows_cap entries (grown on demand: its address is a member of the StepKey); h_rows: the pinned ring
     // it is refreshed from, kRowRing slots of rows_cap entries.
-    struct RowState { bool live = false, hist_valid = false, fold = false; int pos = 0; uint64_t image = 0; };
+    // Per row as well: lr_strength (0: not held to an LR image) and frames (null, or where the row writes the frames of
+    // a uniform call from `start`; frames_n of them written so far).
+    struct RowState {
+        bool live = false, hist_valid = false, fold = false;
+        int pos = 0, start = 0;
+        uint64_t image = 0;
+        float lr_strength = 0.f;
+        float *frames = nullptr;
+        int frames_n = 0, frames_cap = 0;   // (frames_cap: the count sr3_rows_frames checked; never written past)
+    };
     bool rows_on = false;
+    // sr3_rows_lr_consistency: the session is armed — its steps run the projection's rows form between the halves of the
+    // update. rows_lr_ops / rows_lr_lds: operators and form, launch arguments of the captured steps (StepKey) like
+    // rows_lr_buf, the LR image of every slot [rows_lr_slots][out_channel][lh][lw] (grown on demand, kept between sessions).
+    bool rows_lr = false, rows_lr_lds = false;
+    bool rows_admitted = false;         // a row was admitted since sr3_rows_begin
+    LrOps rows_lr_ops;
+    float *rows_lr_buf = nullptr;
+    size_t rows_lr_floats = 0;
     std::vector<RowState> rows;
     RowArgs *d_rows = nullptr, *h_rows = nullptr;
     int rows_cap = 0;
@@ -1678,13 +1697,18 @@ void enqueue_rows_update(sr3_ctx *c, const StepKey &k) {
     u.ovf = k.mode != A_F32 ? c->d_ovf : nullptr;
     u.hist = c->xhist;
     c->pbegin(F_MISC);
-    if (!k.dyn) {
+    if (!k.dyn && !k.lr) {
         launch_rows_update(u, B, c->stream);
     } else {
-        // (the threshold kernels run over all B rows: an idle row's slab of x0hat is zeros, s = 1, and is never used)
-        launch_rows_x0_predict(u, k.x0hat, B, c->stream, false);
-        launch_abs_quantile(k.x0hat, B, k.dyn_n, k.dyn_plan, k.dyn_max, k.dyn_bins, nullptr, nullptr, k.dyn_s, c->stream);
-        launch_threshold_apply(k.x0hat, B, k.dyn_n, k.dyn_s, c->stream);
+        // as enqueue_update: prediction | threshold | projection | the rest of the update, each in its rows form
+        launch_rows_x0_predict(u, k.x0hat, B, c->stream, !k.dyn);
+        if (k.dyn) {
+            // (the threshold kernels run over all B rows: an idle row's slab of x0hat is zeros, s = 1, and is never used)
+            launch_abs_quantile(k.x0hat, B, k.dyn_n, k.dyn_plan, k.dyn_max, k.dyn_bins, nullptr, nullptr, k.dyn_s, c->stream);
+            launch_threshold_apply(k.x0hat, B, k.dyn_n, k.dyn_s, c->stream);
+        }
+        // (only the planes of live rows admitted with an LR image: the others keep the prediction as it is)
+        if (k.lr) launch_lr_project_rows(k.x0hat, B, u.C, k.lr_ops, k.rows_lr, k.rows, k.lr_lds, k.lr_scratch, c->stream);
         launch_rows_update_from_x0(u, k.x0hat, B, c->stream);
     }
     c->pend();
@@ -2081,6 +2105,7 @@ void sr3_destroy(sr3_ctx *c) {
     if (c->h_rows) (void)hipHostFree(c->h_rows);
     if (c->d_rows) (void)hipFree(c->d_rows);
     if (c->d_row_start) (void)hipFree(c->d_row_start);
+    if (c->rows_lr_buf) (void)hipFree(c->rows_lr_buf);
     for (auto &kv : c->lr_ops) { (void)hipFree(kv.second.buf); (void)hipFree(kv.second.bounds); }
     if (c->d_lr) (void)hipFree(c->d_lr);
     if (c->h_lr) (void)hipHostFree(c->h_lr);
@@ -2896,6 +2921,7 @@ int sr3_rows_begin(sr3_ctx *c, int B, int H, int W, uint64_t seed) {
     c->hist_valid = false;
     c->fc_invalidate();
     c->rows.assign((size_t)B, sr3_ctx::RowState());
+    c->rows_lr = false; c->rows_admitted = false;
     if (range_reset(c)) return -1;
     // every slot idle and zero: an idle row still runs through the UNet, and must never carry a NaN or Inf into it
     // (the borders and pad channels of the state are zero already and stay so)
@@ -2906,21 +2932,51 @@ int sr3_rows_begin(sr3_ctx *c, int B, int H, int W, uint64_t seed) {
     return 0;
 }
 
-int sr3_rows_admit(sr3_ctx *c, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
-                   const float *noise0_dev, uint64_t image_id) {
-    if (rows_check(c, "sr3_rows_admit", row)) return -1;
+int sr3_rows_lr_consistency(sr3_ctx *c, int lh, int lw) {
+    if (rows_check(c, "sr3_rows_lr_consistency", 0)) return -1;
     HIP_OK(hipSetDevice(c->device));
-    if (!cond_dev) return fail("sr3_rows_admit: cond_dev is null");
+    if (c->rows_admitted)
+        return fail("sr3_rows_lr_consistency: a row was admitted already; arm the session right after sr3_rows_begin");
+    const int B = c->wB, C = c->cfg.out_channel, H = c->wH, W = c->wW;
+    if (check_lr_shape("sr3_rows_lr_consistency", C, H, W, B, lh, lw)) return -1;
+    LrOps o;
+    if (get_lr_ops(c, lh, lw, H, W, &o)) return -1;
+    const bool lds = lr_lds_fits(o);
+    if (ensure_x0hat(c, (size_t)B * C * H * W)) return -1;
+    if (!lds && ensure_lr_scratch(c, lr_scratch_floats(B * C, o))) return -1;
+    const size_t need = (size_t)B * C * lh * lw;
+    if (c->rows_lr_floats < need) {
+        HIP_OK(hipStreamSynchronize(c->stream));
+        if (c->rows_lr_buf) HIP_OK(hipFree(c->rows_lr_buf));
+        c->rows_lr_buf = nullptr; c->rows_lr_floats = 0;
+        HIP_OK(hipMalloc(&c->rows_lr_buf, need * sizeof(float)));
+        c->rows_lr_floats = need;
+    }
+    c->rows_lr_ops = o; c->rows_lr_lds = lds;
+    c->rows_lr = true;
+    return 0;
+}
+
+namespace {
+int rows_admit_impl(sr3_ctx *c, const char *what, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
+                    const float *noise0_dev, uint64_t image_id, const float *lr_dev, float strength) {
+    if (rows_check(c, what, row)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    if (!cond_dev) return fail("%s: cond_dev is null", what);
     sr3_ctx::RowState &r = c->rows[row];
-    if (r.live) return fail("sr3_rows_admit: slot %d is live (%d steps left); retire or drop it first", row, r.pos);
+    if (r.live) return fail("%s: slot %d is live (%d steps left); retire or drop it first", what, row, r.pos);
     const int C = c->cfg.out_channel, nc = c->cfg.in_channel - C;
     if (init_dev ? (start_step < 1 || start_step > c->T) : start_step != c->T)
-        return fail("sr3_rows_admit: start_step %d outside [1, %d] (%d without init_dev)", start_step, c->T, c->T);
+        return fail("%s: start_step %d outside [1, %d] (%d without init_dev)", what, start_step, c->T, c->T);
     if (init_dev && init_dev == cond_dev && nc != C)
-        return fail("sr3_rows_admit: the conditioning image has %d channels and cannot start a state of %d", nc, C);
+        return fail("%s: the conditioning image has %d channels and cannot start a state of %d", what, nc, C);
     const bool q = init_dev && noised;
     if (q && c->cfg.in_channel > 8)
-        return fail("sr3_rows_admit: in_channel = %d, the state kernel builds at most 8 input channels", c->cfg.in_channel);
+        return fail("%s: in_channel = %d, the state kernel builds at most 8 input channels", what, c->cfg.in_channel);
+    if (!(strength >= 0.f) || strength > 1.f) return fail("%s: strength must lie in [0, 1], got %g", what, (double)strength);
+    const bool held = lr_dev != nullptr && strength != 0.f;
+    if (held && !c->rows_lr)
+        return fail("%s: an LR image for a session that is not armed; call sr3_rows_lr_consistency after sr3_rows_begin", what);
     const TDesc x0r = row_desc(c->x0, row);
     float *xpr = row_packed(c, row);
     c->pbegin(F_MISC);
@@ -2939,9 +2995,42 @@ int sr3_rows_admit(sr3_ctx *c, int row, const float *cond_dev, const float *init
     }
     c->pend();
     HIP_OK(hipGetLastError());
-    r = sr3_ctx::RowState();
-    r.live = true; r.pos = start_step; r.image = image_id;
+    // the slot's own copy of the LR image, behind the steps enqueued so far (they read the previous occupant's, if any)
+    if (held) {
+        const size_t n = (size_t)C * c->rows_lr_ops.lh * c->rows_lr_ops.lw;
+        HIP_OK(hipMemcpyAsync(c->rows_lr_buf + (size_t)row * n, lr_dev, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    }
+    r = sr3_ctx::RowState();            // (not held, no frames: nothing of the previous occupant is left)
+    r.live = true; r.pos = r.start = start_step; r.image = image_id;
     r.fold = init_dev != nullptr;       // (as sr3_sample_begin_from: the first step of a multistep sampler is first order)
+    r.lr_strength = held ? strength : 0.f;
+    c->rows_admitted = true;
+    return 0;
+}
+}
+
+int sr3_rows_admit(sr3_ctx *c, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
+                   const float *noise0_dev, uint64_t image_id) {
+    return rows_admit_impl(c, "sr3_rows_admit", row, cond_dev, init_dev, start_step, noised, noise0_dev, image_id, nullptr, 0.f);
+}
+
+int sr3_rows_admit_lr(sr3_ctx *c, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
+                      const float *noise0_dev, uint64_t image_id, const float *lr_dev, float strength) {
+    return rows_admit_impl(c, "sr3_rows_admit_lr", row, cond_dev, init_dev, start_step, noised, noise0_dev, image_id, lr_dev,
+                           strength);
+}
+
+int sr3_rows_frames(sr3_ctx *c, int row, float *frames_dev, int capacity) {
+    if (rows_check(c, "sr3_rows_frames", row)) return -1;
+    if (!frames_dev) return fail("sr3_rows_frames: frames_dev is null");
+    sr3_ctx::RowState &r = c->rows[row];
+    if (!r.live || r.pos != r.start)
+        return fail("sr3_rows_frames: slot %d is %s; call it after sr3_rows_admit and before the row's first step", row,
+                    r.live ? "past its first step" : "idle");
+    const int n = sr3_num_frames_from(c, r.start);
+    if (n < 0) return -1;
+    if (capacity < n) return fail("sr3_rows_frames: a row begun at step %d writes %d frames, capacity is %d", r.start, n, capacity);
+    r.frames = frames_dev; r.frames_n = 0; r.frames_cap = n;
     return 0;
 }
 
@@ -2964,6 +3053,10 @@ int sr3_rows_step(sr3_ctx *c, const float *const *noise_rows) {
         if (c->dyn_n != n || c->dyn_rows < B || c->x0hat_floats < (size_t)B * n || c->dyn_plan.k != threshold_plan(c->dyn_ratio, n).k)
             return fail("sr3_rows_step: the dynamic threshold was turned on or changed after sr3_rows_begin; set it before");
     }
+    if (c->rows_lr && (c->x0hat_floats < (size_t)B * c->cfg.out_channel * c->wH * c->wW ||
+                       (!c->rows_lr_lds && c->lr_scratch_n < lr_scratch_floats(B * c->cfg.out_channel, c->rows_lr_ops))))
+        return fail("sr3_rows_step: the buffers of the armed session are gone; arm it again after sr3_rows_begin");
+    const int frame_every = 1 | (c->T / 10);        // (sr3_sample's rule: a frame after every step t with t % (1 | T/10) == 0)
     // the host may run ahead of the GPU: never reuse a ring slot that may still be pending
     if (c->rows_count && (c->rows_count % (sr3_ctx::kRowRing / 2)) == 0) HIP_OK(hipStreamSynchronize(c->stream));
     RowArgs *slot = c->h_rows + (size_t)(c->rows_count % sr3_ctx::kRowRing) * c->rows_cap;
@@ -2987,6 +3080,9 @@ int sr3_rows_step(sr3_ctx *c, const float *const *noise_rows) {
             if (c->uses_hist) r.hist_valid = true;
             ra.image = r.image; ra.seed = c->seed;
             ra.noise = (noise_rows && t > 0) ? noise_rows[n] : nullptr;
+            ra.lr_strength = c->rows_lr ? r.lr_strength : 0.f;
+            if (r.frames && t % frame_every == 0 && r.frames_n < r.frames_cap)
+                ra.frame = r.frames + (size_t)(r.frames_n++) * c->cfg.out_channel * c->wH * c->wW;
             --r.pos;
         }
         slot[n] = ra;
@@ -2995,6 +3091,12 @@ int sr3_rows_step(sr3_ctx *c, const float *const *noise_rows) {
     c->fc_invalidate();
     StepKey key = step_key(c, 0);
     key.rows = c->d_rows;
+    if (c->rows_lr) {       // (the members step_key fills for the per-call projection, from the session's own)
+        key.lr = true; key.x0hat = c->x0hat;
+        key.lr_ops = c->rows_lr_ops; key.lr_lds = c->rows_lr_lds;
+        if (!key.lr_lds) key.lr_scratch = c->lr_scratch;
+        key.rows_lr = c->rows_lr_buf;
+    }
     if (launch_step(c, key)) return -1;
     if (const char *e = conv_take_error()) return fail("sr3_rows_step: %s", e);
     if (c->prof) c->pflush();           // bound the number of live events
@@ -3045,6 +3147,7 @@ int sr3_rows_end(sr3_ctx *c) {
     if (!c) return fail("null context");
     if (!c->rows_on) return fail("sr3_rows_end outside a row session (sr3_rows_begin)");
     c->rows_on = false;
+    c->rows_lr = false;     // (the LR buffer stays for the next session, as the table and the ring do)
     c->rows.clear();
     return 0;
 }
@@ -4017,6 +4120,39 @@ int sr3_op_lr_project(sr3_ctx *c, float *x_dev, int B, int C, int H, int W, cons
     launch_lr_project(x_dev, B * C, C, o, a, nullptr, lds, c->lr_scratch, c->stream);
     c->pend();
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int sr3_op_lr_project_rows(sr3_ctx *c, float *x_dev, int B, int C, int H, int W, const float *lr_rows_dev, int lh, int lw,
+                           const float *strength_host, const int *live_host, int form) {
+    if (!c || !x_dev || !lr_rows_dev || !strength_host || !live_host) return fail("sr3_op_lr_project_rows: null argument");
+    if (B <= 0 || form < 0 || form > 2) return fail("sr3_op_lr_project_rows: needs B > 0 and form 0 (auto) | 1 (LDS) | 2 (scratch)");
+    if (check_lr_shape("sr3_op_lr_project_rows", C, H, W, B, lh, lw)) return -1;
+    for (int b = 0; b < B; ++b)
+        if (!(strength_host[b] >= 0.f) || strength_host[b] > 1.f)
+            return fail("sr3_op_lr_project_rows: strength must lie in [0, 1], got %g for row %d", (double)strength_host[b], b);
+    HIP_OK(hipSetDevice(c->device));
+    LrOps o;
+    if (get_lr_ops(c, lh, lw, H, W, &o)) return -1;
+    if (form == 1 && !lr_lds_fits(o))
+        return fail("sr3_op_lr_project_rows: the LDS form needs %zu bytes per plane, above its %zu", lr_lds_bytes(o), LR_LDS_MAX_BYTES);
+    const bool lds = form == 1 || (form == 0 && lr_lds_fits(o));
+    if (!lds && ensure_lr_scratch(c, lr_scratch_floats(B * C, o))) return -1;
+    // a table of its own, as the session's steps read theirs (only live and lr_strength matter to the projection)
+    std::vector<RowArgs> tab((size_t)B, RowArgs());
+    for (int b = 0; b < B; ++b) { tab[b].live = live_host[b] ? 1u : 0u; tab[b].lr_strength = strength_host[b]; }
+    RowArgs *d_tab = nullptr;
+    HIP_OK(hipMalloc(&d_tab, sizeof(RowArgs) * B));
+    hipError_t e = hipMemcpy(d_tab, tab.data(), sizeof(RowArgs) * B, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        c->pbegin(F_MISC);
+        launch_lr_project_rows(x_dev, B, C, o, lr_rows_dev, d_tab, lds, c->lr_scratch, c->stream);
+        c->pend();
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    (void)hipFree(d_tab);
+    if (e != hipSuccess) return fail("sr3_op_lr_project_rows: %s", hipGetErrorString(e));
     return 0;
 }
 

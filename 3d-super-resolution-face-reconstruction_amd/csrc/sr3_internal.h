@@ -479,6 +479,9 @@ struct RowArgs {
     uint64_t image;             // global image id of the Philox key
     uint64_t seed;
     const float *noise;         // this row's [C][HW] slab of the step, or null -> Philox
+    float *frame;               // this row's [C][HW] copy of the updated image for this step, or null (as StepArgs::frame)
+    float lr_strength;          // low-resolution consistency of this row (launch_lr_project_rows); 0: the row is not held
+    uint32_t pad_;
 };
 static_assert(sizeof(RowArgs) % sizeof(float) == 0, "RowArgs::nl is read with a stride in floats");
 struct RowsUpdateParams {
@@ -532,6 +535,12 @@ bool lr_lds_fits(const LrOps &o);
 size_t lr_scratch_floats(int planes, const LrOps &o);
 void launch_lr_project(float *x, int planes, int C, const LrOps &o, const LrArgs &val, const LrArgs *dyn, bool lds_form,
                        float *scratch, hipStream_t s);
+// The rows form (rolling batch): the same stages on the planes of x [B][C][H][W] whose row is live and held
+// (rows[b].live && rows[b].lr_strength != 0), row b against lr_rows[b] ([B slots][C][lh][lw]) at rows[b].lr_strength. A plane
+// of any other row is neither read nor written: its block returns before the first barrier (LDS form), every stage skips
+// it (scratch form). A held plane carries the bits launch_lr_project gives it.
+void launch_lr_project_rows(float *x, int B, int C, const LrOps &o, const float *lr_rows, const RowArgs *rows, bool lds_form,
+                            float *scratch, hipStream_t s);
 // per image b: sumsq[b] = sum over its C planes of (A img - y)^2 (fp32 residuals, fp64 sum), maxabs[b] = max |A img - y|;
 // scratch as for the projection
 void launch_lr_residual(const float *img, int B, int C, const LrOps &o, const LrArgs &val, float *scratch, double *sumsq,

@@ -499,7 +499,7 @@ class GaussianDiffusion(nn.Module):
                 frames[:, a:b] = fc[:, : b - a]
         return (out, frames) if continous else out
 
-    def rolling(self, slots: Optional[int] = None, seed: Optional[int] = None, shape=None):
+    def rolling(self, slots: Optional[int] = None, seed: Optional[int] = None, shape=None, lr_size=None):
         """A `rolling.RollingSampler` on this model: single-image requests served through `slots` batch
         rows, each at its own position of the schedule, so a request takes a free slot while the others are mid-trajectory.
         It uses the model's sampler (set_sampler), arithmetic, range policy and dynamic threshold as they stand now. Every
@@ -508,8 +508,13 @@ class GaussianDiffusion(nn.Module):
         strength — whatever shared the batch and wherever it sat. Against a call at ANOTHER batch size (the B = 1 call, say)
         it differs as any two batch sizes differ: the conv dispatch depends on the batch (fp32 round-off in f32 / f16x3,
         1e-5 in f16f8, whose fp8 path runs only from 32 or 64 images on). slots None: min(64, the per-call limit at `shape` = (H, W), default
-        image_size). LR consistency, the feature cache and Dropout sampling do not follow single rows: the session
-        refuses them, naming the setting. Use as a context manager, or close() it."""
+        image_size). LR consistency is per request here: submit(..., lr=image) holds that request to its LR image (fp32
+        [C,l,l] or uint8 [l,l,3], lr_to_tensor) as set_lr_consistency holds a batch, a request without one is not held; the
+        session is armed for the LR size when it begins — by lr_size=(lh, lw), or by the first request carrying an lr.
+        submit(..., continous=True) makes poll return what super_resolution(x, continous=True) returns for one image:
+        the conditioning image followed by the request's frames. The per-call set_lr_consistency, the feature cache and
+        Dropout sampling do not follow single rows: the session refuses them, naming the setting. Use as a context
+        manager, or close() it."""
         from .rolling import RollingSampler
         if not self.conditional:
             raise Sr3Error("rolling() needs a conditional model: the unconditional one has no per-request input")
@@ -533,10 +538,25 @@ class GaussianDiffusion(nn.Module):
         def alloc(r):
             return torch.empty((C,) + tuple(r.cond.shape[-2:]), dtype=torch.float32, device=r.cond.device)
 
+        def alloc_frames(r, n):
+            return torch.empty((n, C) + tuple(r.cond.shape[-2:]), dtype=torch.float32, device=r.cond.device)
+
+        def to_lr(lr):
+            t = torch.as_tensor(lr)
+            t = lr_to_tensor(t if t.dim() == 4 else t[None])
+            if t.shape[0] != 1 or t.shape[1] != C:
+                raise RuntimeError(f"one LR image of {C} channels per request, got {tuple(t.shape)}")
+            return t[0].to(dev).contiguous()
+
+        def deliver(r):
+            # p_sample_loop's ret_img for one image: the conditioning image, then its frames
+            return torch.cat([r.cond.to(torch.float32)[None], r.frames], dim=0) if r.continous else r.out
+
         return RollingSampler(eng, int(slots), self.num_sampling_steps, self._draw_seed() if seed is None else int(seed),
                               precision=getattr(eng, "precision", "f32"), strict=self.denoise_fn.strict_range,
                               start_steps=lambda S, strength: self.start_steps(S, strength=strength), alloc=alloc,
-                              ready=self.denoise_fn.ready, finish=self.denoise_fn.finish)
+                              ready=self.denoise_fn.ready, finish=self.denoise_fn.finish, lr_size=lr_size, to_lr=to_lr,
+                              alloc_frames=alloc_frames, deliver=deliver)
 
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, noise=None, seed=None):

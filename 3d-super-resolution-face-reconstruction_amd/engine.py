@@ -400,21 +400,39 @@ class Engine:
     # ---- rolling batch: every row at its own position ---------------------------
     def rows_begin(self, B: int, H: int, W: int, seed: int = 0) -> None:
         """Opens a row session of B slots at H x W, all idle (sr3_rows_begin). Uses the sampler, arithmetic and dynamic
-        threshold set on the engine; refuses LR consistency, the feature cache and Dropout sampling. Every step runs at
-        batch B whatever is live: a row's result is that of its row in a uniform call of B images."""
+        threshold set on the engine; refuses the per-call LR consistency (set_lr_consistency: a session holds single rows,
+        rows_lr_consistency), the feature cache and Dropout sampling. Every step runs at batch B whatever is live: a
+        row's result is that of its row in a uniform call of B images."""
         _lib.check(self.lib.sr3_rows_begin(self.ctx, int(B), int(H), int(W), int(seed) & (2 ** 64 - 1)))
         self._rows_slots = int(B)
 
+    def rows_lr_consistency(self, lh: int, lw: int) -> None:
+        """Arms the open session for LR images of lh x lw (sr3_rows_lr_consistency): right after rows_begin, before the
+        first rows_admit. The rows admitted with an `lr` are then held to it, the others are not."""
+        _lib.check(self.lib.sr3_rows_lr_consistency(self.ctx, int(lh), int(lw)))
+
     def rows_admit(self, row: int, cond_ptr: int, image_id: int, init_ptr: Optional[int] = None,
-                   start_step: Optional[int] = None, noised: bool = True, noise0_ptr: Optional[int] = None) -> None:
+                   start_step: Optional[int] = None, noised: bool = True, noise0_ptr: Optional[int] = None,
+                   lr: Optional[int] = None, lr_strength: float = 1.0) -> None:
         """One request into idle slot `row` (sr3_rows_admit): cond [Cc,H,W]; init_ptr None: from the start noise at the
         top; init [C,H,W] with start_step (None: S): the warm start, noised to noise_level[start_step] unless noised is
-        False. noise0: the start noise / the z of q_sample, [C,H,W] (None: Philox draw 0 of image_id)."""
+        False. noise0: the start noise / the z of q_sample, [C,H,W] (None: Philox draw 0 of image_id). lr: the device
+        address of the row's LR image, fp32 [C,lh,lw] in [-1,1], in an armed session (sr3_rows_admit_lr; the library
+        copies it), held at lr_strength in [0, 1]; None: the row is not held."""
         if init_ptr is None and start_step is not None and int(start_step) != self.T:
             raise ValueError("start_step needs init_ptr: the image the row starts from")
         s0 = self.T if start_step is None else int(start_step)
-        _lib.check(self.lib.sr3_rows_admit(self.ctx, int(row), cond_ptr, init_ptr or None, s0, 1 if noised else 0,
-                                           noise0_ptr or None, int(image_id) & (2 ** 64 - 1)))
+        if lr is None:
+            _lib.check(self.lib.sr3_rows_admit(self.ctx, int(row), cond_ptr, init_ptr or None, s0, 1 if noised else 0,
+                                               noise0_ptr or None, int(image_id) & (2 ** 64 - 1)))
+            return
+        _lib.check(self.lib.sr3_rows_admit_lr(self.ctx, int(row), cond_ptr, init_ptr or None, s0, 1 if noised else 0,
+                                              noise0_ptr or None, int(image_id) & (2 ** 64 - 1), lr, float(lr_strength)))
+
+    def rows_frames(self, row: int, frames_ptr: int, capacity: int) -> None:
+        """After rows_admit, before the row's first step: the row writes its frames, [n,C,H,W] with n = num_frames(its
+        start_step), to frames_ptr (sr3_rows_frames) — those of its row in the uniform call with frames."""
+        _lib.check(self.lib.sr3_rows_frames(self.ctx, int(row), frames_ptr, int(capacity)))
 
     def rows_step(self, noise_ptrs: Optional[Sequence[Optional[int]]] = None) -> int:
         """One step of every live row at its own position (sr3_rows_step); noise_ptrs: one device address (or None)
@@ -473,6 +491,28 @@ class Engine:
         stream-ordered). form: 'auto' | 'lds' (one block per plane) | 'scratch' (one launch per stage)."""
         _lib.check(self.lib.sr3_op_lr_project(self.ctx, x_ptr, B, C_, H, W, lr_ptr, N, lh, lw, int(row_offset), float(strength),
                                               self.LR_FORMS[form]))
+
+    def lr_project_rows(self, x_ptr: int, B: int, C_: int, H: int, W: int, lr_ptr: int, lh: int, lw: int,
+                        strengths: Sequence[float], live: Sequence[int], form: str = "auto") -> None:
+        """The rows form of the projection (sr3_op_lr_project_rows): row b of x [B,C,H,W] against lr [B,C,lh,lw] at
+        strengths[b] where live[b] and strengths[b] != 0; every other row is left alone."""
+        st = np.ascontiguousarray(strengths, dtype=np.float32)
+        lv = np.ascontiguousarray(live, dtype=np.int32)
+        if st.shape != (B,) or lv.shape != (B,):
+            raise ValueError(f"strengths and live need one entry per row ({B})")
+        _lib.check(self.lib.sr3_op_lr_project_rows(self.ctx, x_ptr, B, C_, H, W, lr_ptr, lh, lw, st.ctypes.data,
+                                                   lv.ctypes.data, self.LR_FORMS[form]))
+
+    def lr_project_rows_np(self, x, lr, strengths, live, form: str = "auto") -> np.ndarray:
+        """numpy convenience: x [B,C,H,W], lr [B,C,lh,lw] -> x with its live, held rows projected."""
+        x, lr = _host_f32(x), _host_f32(lr)
+        B, C_, H, W = x.shape
+        _, _, lh, lw = lr.shape
+        dx, dl = self.to_device(x), self.to_device(lr)
+        self.lr_project_rows(dx.ptr, B, C_, H, W, dl.ptr, lh, lw, strengths, live, form)
+        out = dx.download(x.shape)
+        dx.free(); dl.free()
+        return out
 
     def lr_residual(self, img_ptr: int, B: int, C_: int, H: int, W: int, lr_ptr: int, N: int, lh: int, lw: int,
                     row_offset: int, sumsq_ptr: int, maxabs_ptr: int) -> None:
@@ -1048,12 +1088,17 @@ class Engine:
         """numpy convenience (tests): a whole row session. requests: dicts with cond [Cc,H,W], image_id, and optionally
         at (the earliest session step the request may be admitted at, default 0), init [C,H,W] with start_step and
         noised, noise [s0,C,H,W] (slab 0 the start noise / the z of q_sample, slab k the draw of step t = s0 - k) and
-        slot (a slot of its own; default: the lowest free one). A request enters once `at` steps have run and a slot is
+        slot (a slot of its own; default: the lowest free one), lr [C,lh,lw] with lr_strength (the row is held to it: the
+        session is armed for the size of the first lr among the requests) and frames True (the row's frames come back with
+        its image). A request enters once `at` steps have run and a slot is
         free; finished rows retire after every step. on_step(k) runs after step k, with the session open (read-backs).
-        Returns (images in request order, trace): trace[k] = the request index per slot (None: idle) during step k."""
+        Returns (images in request order, trace): trace[k] = the request index per slot (None: idle) during step k; the
+        entry of a request with frames is (image, frames [n,C,H,W])."""
         C_ = self.cfg.out_channel
         H, W = np.asarray(requests[0]["cond"]).shape[-2:]
         self.rows_begin(slots, H, W, seed)
+        lrs = [np.asarray(rq["lr"]).shape[-2:] for rq in requests if rq.get("lr") is not None]
+        fbufs = [None] * slots
         keep, held = [], [None] * slots         # device buffers of the live rows; request index per slot
         pos0 = [0] * slots
         out = [None] * len(requests)
@@ -1061,6 +1106,8 @@ class Engine:
         waiting = list(range(len(requests)))
         trace, k = [], 0
         try:
+            if lrs:
+                self.rows_lr_consistency(*lrs[0])
             while waiting or any(h is not None for h in held):
                 for i in list(waiting):
                     rq = requests[i]
@@ -1075,8 +1122,16 @@ class Engine:
                     nz = _host_f32(rq["noise"]) if rq.get("noise") is not None else None
                     dn = [self.to_device(z) for z in nz] if nz is not None else None
                     s0 = int(rq.get("start_step", self.T)) if di is not None else self.T
+                    dl = self.to_device(rq["lr"]) if rq.get("lr") is not None else None
                     self.rows_admit(s, dc.ptr, rq["image_id"], di.ptr if di else None, s0 if di else None,
-                                    bool(rq.get("noised", True)), dn[0].ptr if dn else None)
+                                    bool(rq.get("noised", True)), dn[0].ptr if dn else None,
+                                    lr=dl.ptr if dl else None, lr_strength=float(rq.get("lr_strength", 1.0)))
+                    if dl is not None:
+                        dl.free()               # (the library holds its own copy)
+                    if rq.get("frames"):
+                        nf = self.num_frames(s0)
+                        fbufs[s] = (self.buffer(nf * C_ * H * W), nf)
+                        self.rows_frames(s, fbufs[s][0].ptr, nf)
                     keep.append((dc, di, dn))
                     held[s], pos0[s] = (i, dn), s0
                     waiting.remove(i)
@@ -1102,6 +1157,11 @@ class Engine:
                     if held[s] is not None and self.rows_position(s) == 0:
                         self.rows_retire(s, obuf.ptr)
                         out[held[s][0]] = obuf.download((C_, H, W)).copy()
+                        if fbufs[s] is not None:
+                            fb, nf = fbufs[s]
+                            out[held[s][0]] = (out[held[s][0]], fb.download((nf, C_, H, W)).copy())
+                            fb.free()
+                            fbufs[s] = None
                         held[s] = None
         finally:
             self.rows_end()

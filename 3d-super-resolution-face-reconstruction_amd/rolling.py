@@ -24,18 +24,20 @@ LADDER = {"f16f8": "f16x3", "f16x3": "f32"}       # one arithmetic down (the lib
 
 
 class _Request:
-    __slots__ = ("ticket", "cond", "init", "start_step", "noised", "image_id", "out")
+    __slots__ = ("ticket", "cond", "init", "start_step", "noised", "image_id", "out", "lr", "lr_strength", "continous",
+                 "frames")
 
-    def __init__(self, ticket, cond, init, start_step, noised, image_id):
+    def __init__(self, ticket, cond, init, start_step, noised, image_id, lr=None, lr_strength=1.0, continous=False):
         self.ticket, self.cond, self.init = ticket, cond, init
         self.start_step, self.noised, self.image_id = start_step, noised, image_id
-        self.out = None
+        self.lr, self.lr_strength, self.continous = lr, lr_strength, continous
+        self.out = self.frames = None
 
 
 class RollingSampler:
     """Serves single-image requests through `slots` batch rows.
 
-      submit(x_in_row, init=None, strength=None, image_id=None) -> ticket
+      submit(x_in_row, init=None, strength=None, image_id=None, lr=None, lr_strength=1.0, continous=False) -> ticket
       step()              one step of every live row; finished rows retire, queued requests take the free slots
       poll()              [(ticket, image)] of the rows finished since the last poll, in completion order
       drain()             steps until nothing is queued or in flight; returns what poll would
@@ -50,12 +52,19 @@ class RollingSampler:
     switched conv paths, everything since the last check is invalid), restarts the same requests in the same arithmetic
     under either policy and is counted in `replays`, as p_sample repeats its step.
 
+    LR consistency is per request: a request submitted with an `lr` image is held to it, one without is
+    not, in the same session. The session must be armed for the LR size when it begins — it begins with the first
+    submit — either by `lr_size` or by that first request carrying an `lr`. A restart re-admits a request with its LR
+    image and writes its frames again from the first.
+
     `trace` records one entry per step: (live rows, requests still queued, whether the stream's source is exhausted).
     """
 
     def __init__(self, engine, slots: int, steps: int, seed: int = 0, precision: str = "f32", strict: bool = False,
                  start_steps: Optional[Callable] = None, alloc: Optional[Callable] = None,
-                 ready: Optional[Callable] = None, finish: Optional[Callable] = None):
+                 ready: Optional[Callable] = None, finish: Optional[Callable] = None,
+                 lr_size: Optional[Tuple[int, int]] = None, to_lr: Optional[Callable] = None,
+                 alloc_frames: Optional[Callable] = None, deliver: Optional[Callable] = None):
         if int(slots) < 1:
             raise ValueError(f"slots must be >= 1, got {slots}")
         self.eng, self.slots, self.S, self.seed = engine, int(slots), int(steps), int(seed)
@@ -63,6 +72,14 @@ class RollingSampler:
         self._start_steps = start_steps or (lambda S, strength: max(1, min(S, int(round(float(strength) * S)))))
         self._alloc = alloc
         self._ready, self._finish = ready or (lambda: None), finish or (lambda: None)
+        # to_lr(lr) -> the LR image as the engine takes it (fp32 [C,lh,lw] with a data_ptr); alloc_frames(request, n) ->
+        # the buffer of its n frames; deliver(request) -> what poll hands back for it (default: its image, or
+        # (image, frames) for a request with continous)
+        self._to_lr = to_lr or self._row
+        self._alloc_frames = alloc_frames
+        self._deliver = deliver or (lambda r: (r.out, r.frames) if r.continous else r.out)
+        self._lr_size0 = self._lr_size = None if lr_size is None else (int(lr_size[0]), int(lr_size[1]))
+        self._armed = False
         self._queue: Deque[_Request] = deque()
         self._rows: List[Optional[_Request]] = [None] * self.slots
         self._left: List[int] = [0] * self.slots         # steps left per slot (the library keeps the same count)
@@ -77,25 +94,46 @@ class RollingSampler:
         self.trace: List[Tuple[int, int, bool]] = []
 
     # ---- requests ---------------------------------------------------------------------------------------
-    def submit(self, x_in_row, init=None, strength=None, image_id: Optional[int] = None) -> int:
+    def submit(self, x_in_row, init=None, strength=None, image_id: Optional[int] = None, lr=None, lr_strength: float = 1.0,
+               continous: bool = False) -> int:
         """Queues one request and returns its ticket. x_in_row: the conditioning image [Cc,H,W] (or [1,Cc,H,W]).
         strength in (0, 1]: a warm start over the last max(1, round(strength * S)) steps from `init` [C,H,W], or from the
         conditioning image itself without one; init without a strength starts at the top level. image_id keys the
-        request's Philox streams (default: the ticket)."""
+        request's Philox streams (default: the ticket). lr: the request's LR image ([C,l,l] fp32 in [-1,1], or what the
+        sampler's to_lr converts), to which every step holds the row at lr_strength in [0, 1] (0, or no lr: not held).
+        continous: poll hands back the frames of the request as well."""
         cond = self._row(x_in_row)
+        # every check first: a refused request leaves the sampler as it was (image size, LR size, arming)
+        if not 0.0 <= float(lr_strength) <= 1.0:
+            raise ValueError(f"lr_strength must lie in [0, 1], got {lr_strength}")
+        if continous and self._alloc_frames is None:
+            raise ValueError("continous=True needs a sampler built with alloc_frames: the buffer the row writes its frames to")
         shape = tuple(cond.shape[-2:])
-        if self._shape is None:
-            self._shape = shape
-        elif shape != self._shape:
+        if self._shape is not None and shape != self._shape:
             raise ValueError(f"a rolling session serves one image size: got {shape}, the session runs {self._shape}")
+        lr_size = self._lr_size
+        if lr is not None and float(lr_strength) != 0.0:
+            lr = self._to_lr(lr)
+            size = tuple(int(v) for v in lr.shape[-2:])
+            if self._open and not self._armed:
+                raise ValueError("this session was begun without LR consistency: a request with an lr needs a session armed "
+                                 "from its start — pass lr_size=(lh, lw) to rolling(), or submit an lr with the first request")
+            if lr_size is None:
+                lr_size = size
+            elif size != lr_size:
+                raise ValueError(f"a rolling session holds rows to one LR size: got {size}, the session runs {lr_size}")
+        else:
+            lr = None
         if init is not None:
             init = self._row(init)
         elif strength is not None:
             init = cond
         start = self.S if strength is None else int(self._start_steps(self.S, strength))
+        self._shape, self._lr_size = shape, lr_size
         ticket = self._next_ticket
         self._next_ticket += 1
-        self._queue.append(_Request(ticket, cond, init, start, True, ticket if image_id is None else int(image_id)))
+        self._queue.append(_Request(ticket, cond, init, start, True, ticket if image_id is None else int(image_id), lr,
+                                    float(lr_strength), bool(continous)))
         self._fill()
         return ticket
 
@@ -115,6 +153,11 @@ class RollingSampler:
             H, W = self._shape
             self.eng.rows_begin(self.slots, H, W, self.seed)
             self._open = True
+            # armed by lr_size, or by the LR image of the request whose submit begins the session: the session begins
+            # with the first submit, so no later request can arm it (submit refuses their lr, naming lr_size)
+            if self._lr_size is not None:
+                self.eng.rows_lr_consistency(*self._lr_size)
+                self._armed = True
 
     def _fill(self):
         """queued requests into free slots, lowest slot first"""
@@ -127,9 +170,15 @@ class RollingSampler:
                 continue
             self._begin()
             r = self._queue.popleft()
+            n_frames = self.eng.num_frames(r.start_step) if r.continous else 0
+            if r.continous:
+                r.frames = self._alloc_frames(r, n_frames)
             self._ready()
+            held = {} if r.lr is None else {"lr": r.lr.data_ptr(), "lr_strength": r.lr_strength}
             self.eng.rows_admit(s, r.cond.data_ptr(), r.image_id, r.init.data_ptr() if r.init is not None else None,
-                                r.start_step if r.init is not None else None, r.noised)
+                                r.start_step if r.init is not None else None, r.noised, **held)
+            if r.continous:
+                self.eng.rows_frames(s, r.frames.data_ptr(), n_frames)
             self._rows[s], self._left[s] = r, r.start_step
 
     @property
@@ -177,7 +226,7 @@ class RollingSampler:
                 self._restart(e, lower=not replay)
                 return []
         self._finish()
-        out = [(r.ticket, r.out) for r in self._done]
+        out = [(r.ticket, self._deliver(r)) for r in self._done]
         self._done = []
         return out
 
@@ -192,7 +241,7 @@ class RollingSampler:
                 self._rows[s] = None
         self._done = []
         for r in sorted(hit, key=lambda r: r.ticket, reverse=True):
-            r.out = None
+            r.out = r.frames = None     # (the LR image stays with the request: it is re-admitted held, its frames restart)
             self._queue.appendleft(r)
         if lower:
             self.set_precision(nxt)
@@ -250,6 +299,7 @@ class RollingSampler:
         if self._open:
             self.eng.rows_end()
             self._open = False
+        self._armed, self._lr_size = False, self._lr_size0
         self._rows = [None] * self.slots
         if self.precision != self._precision0:
             self.set_precision(self._precision0)

@@ -242,7 +242,8 @@ int sr3_num_frames_from(sr3_ctx *ctx, int start_step);
  * only from 32 or 64 images on, the split-K forms): against a call at another batch size a row differs as any two batch
  * sizes do, by fp32 round-off in modes 0 / 1 and at the 1e-5 level in mode 2. The update half of
  * a step reads a per-row argument table (RowArgs, csrc/kernels_rows.hip); one captured graph serves every step of every
- * session of a size. Sampler, schedule, arithmetic and dynamic threshold are the context's; there are no frames.
+ * session of a size. Sampler, schedule, arithmetic and dynamic threshold are the context's; low-resolution consistency
+ * and frames are per ROW (sr3_rows_lr_consistency / sr3_rows_admit_lr, sr3_rows_frames).
  *   sr3_rows_begin     opens a session of B slots at H x W, all idle, the state zeroed (an idle row still runs through the
  *                      UNet and is never written by the update). Fails, naming the setting, while low-resolution
  *                      consistency, the feature cache or Dropout sampling is on, and for the unconditional model.
@@ -253,6 +254,20 @@ int sr3_num_frames_from(sr3_ctx *ctx, int start_step);
  *                      what sr3_sample_begin_from writes for that row; noised == 0: init itself. With a sampler that
  *                      keeps an x0 history such a row's first step takes c1 + c3 as its c1, as there, per row; a slot's
  *                      new occupant never reads the history of the previous one. Fails if the slot is live.
+ *   sr3_rows_lr_consistency  arms the session for low-resolution consistency at the LR size (lh, lw): after sr3_rows_begin
+ *                      and before the first admit. Builds or reuses the operators of (lh, lw) -> (H, W) and picks the
+ *                      form as sr3_set_lr_consistency does; fails as it does when the size cannot constrain H x W. Every
+ *                      step of an armed session runs x0 prediction | (dynamic threshold) | projection | update, the
+ *                      projection on the planes of the rows admitted with an LR image only; one more captured graph.
+ *   sr3_rows_admit_lr  sr3_rows_admit with the row's LR image: lr_dev [C, lh, lw] fp32 in [-1, 1], copied into the
+ *                      session's own buffer (stream-ordered: the caller may free it once the call returns), and its
+ *                      strength in [0, 1] (outside: an error). NULL or 0: the row is not held, as after sr3_rows_admit —
+ *                      it is then the bytes of its row in the uniform call WITHOUT low-resolution consistency, a held row
+ *                      those of the call with sr3_set_lr_consistency at that strength. An LR image for a session that is
+ *                      not armed is an error. A slot's new occupant never reads the LR image of the previous one.
+ *   sr3_rows_frames    after the admit and before the row's first step: the row writes into frames_dev, [n][C, H, W] in
+ *                      order, the frames a sr3_sample / sr3_sample_from call begun at the same start_step returns for it
+ *                      (n = sr3_num_frames_from(start_step); capacity < n is an error and changes nothing).
  *   sr3_rows_step      one step of every live row at its own position (t = position - 1, Philox draw S - t), then those
  *                      positions go down by one. noise_rows: NULL (Philox), or B host-side entries of device pointers,
  *                      entry r the [C, H, W] draw of row r's step (read for live rows with t > 0 only). Returns the number
@@ -270,6 +285,10 @@ int sr3_num_frames_from(sr3_ctx *ctx, int start_step);
 int sr3_rows_begin(sr3_ctx *ctx, int B, int H, int W, uint64_t seed);
 int sr3_rows_admit(sr3_ctx *ctx, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
                    const float *noise0_dev, uint64_t image_id);
+int sr3_rows_lr_consistency(sr3_ctx *ctx, int lh, int lw);
+int sr3_rows_admit_lr(sr3_ctx *ctx, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
+                      const float *noise0_dev, uint64_t image_id, const float *lr_dev, float strength);
+int sr3_rows_frames(sr3_ctx *ctx, int row, float *frames_dev, int capacity);
 int sr3_rows_step(sr3_ctx *ctx, const float *const *noise_rows);
 int sr3_rows_position(sr3_ctx *ctx, int row);
 int sr3_rows_retire(sr3_ctx *ctx, int row, float *out_dev);
@@ -673,6 +692,12 @@ int sr3_set_lr_consistency(sr3_ctx *ctx, const float *lr_dev, int N, int lh, int
  * scratch; form 0: form 1 where it fits, as the sampler chooses. Both forms return the same bits. Asynchronous. */
 int sr3_op_lr_project(sr3_ctx *ctx, float *x_dev, int B, int C, int H, int W, const float *lr_dev, int N, int lh,
                       int lw, uint64_t row_offset, float strength, int form);
+/* The rows form of the projection (the one an armed row session runs), alone: row b of x_dev is held to
+ * lr_rows_dev[b] ([B, C, lh, lw]) at strength_host[b] when live_host[b] != 0 and strength_host[b] != 0 (host arrays of B
+ * entries, strengths in [0, 1]); the planes of every other row are neither read nor written. form as above. A held plane
+ * gets the bits sr3_op_lr_project gives it. Synchronous. */
+int sr3_op_lr_project_rows(sr3_ctx *ctx, float *x_dev, int B, int C, int H, int W, const float *lr_rows_dev, int lh, int lw,
+                           const float *strength_host, const int *live_host, int form);
 /* The consistency score, which needs no HR image: per batch row b over its C planes,
  *   sumsq_dev[b]  = sum (A_v X A_h^T - Y)^2   (fp32 residuals, fp64 sum; mse = sumsq / (C lh lw))
  *   maxabs_dev[b] = max |A_v X A_h^T - Y|

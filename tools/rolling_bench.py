@@ -10,9 +10,14 @@
   mixed     64 requests whose strengths are drawn from {0.25, 0.5, 1.0}: one rolling session against one uniform
             warm-start call per strength (each at the batch of its own group)
 
+--lr holds EVERY request to an LR image (LR consistency per row: sr3_rows_lr_consistency / sr3_rows_admit_lr) and
+compares with the uniform forms under sr3_set_lr_consistency: the like-for-like pair of the armed rolling step.
+SR3_LIB=<another build of the library> (read by _lib.py) runs the tool on that build (without --lr: an A/B of the
+unarmed step against the build of an earlier commit).
+
 Synthetic weights: times only. One JSON object on the last line.
 
-    python tools/rolling_bench.py [--precision f16f8] [--T 100] [--requests 256] [--rounds 5] [--block 20] [--skip stream,mixed]
+    python tools/rolling_bench.py [--precision f16f8] [--T 100] [--requests 256] [--rounds 5] [--block 20] [--skip stream,mixed] [--lr]
 """
 import argparse
 import importlib
@@ -36,6 +41,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--block", type=int, default=20)
     ap.add_argument("--skip", default="", help="comma list of step, stream, mixed")
+    ap.add_argument("--lr", action="store_true", help="hold every request to an LR image (both the rolling and the uniform forms)")
     a = ap.parse_args()
     skip = set(x for x in a.skip.split(",") if x)
     import numpy as np
@@ -50,7 +56,23 @@ def main():
     seed = 5
     cond = torch.from_numpy(synth.synth_cond(SLOTS, R, L, 0)).cuda()
     out = torch.empty((SLOTS, 3, R, R), device="cuda")
+    lr = torch.from_numpy(np.random.RandomState(1).uniform(-1, 1, (SLOTS, 3, L, L)).astype(np.float32)).cuda() if a.lr else None
     torch.cuda.synchronize()
+
+    def hold_uniform(on, offset=0):
+        """the per-call setting of the uniform forms (row b of a call at image offset k is held to lr[(k + b) % SLOTS]);
+        off before every row session, which refuses it"""
+        if lr is not None:
+            eng.set_lr_consistency(lr.data_ptr() if on else None, SLOTS, L, L, offset, 1.0)
+
+    def rows_begin():
+        hold_uniform(False)
+        eng.rows_begin(SLOTS, R, R, seed)
+        if lr is not None:
+            eng.rows_lr_consistency(L, L)
+
+    def lr_kw(i):
+        return {} if lr is None else {"lr": lr[i % SLOTS].data_ptr()}
 
     def set_T(T):
         eng.set_schedule(schedule.schedule_buffers({"schedule": "linear", "n_timestep": T, "linear_start": 1e-6, "linear_end": 1e-2}))
@@ -59,11 +81,12 @@ def main():
         for s in range(B):
             i = s if ids is None else ids[s]
             if start is None:
-                eng.rows_admit(s, cond[i % SLOTS].data_ptr(), i)
+                eng.rows_admit(s, cond[i % SLOTS].data_ptr(), i, **lr_kw(i))
             else:
-                eng.rows_admit(s, cond[i % SLOTS].data_ptr(), i, init_ptr=cond[i % SLOTS].data_ptr(), start_step=start)
+                eng.rows_admit(s, cond[i % SLOTS].data_ptr(), i, init_ptr=cond[i % SLOTS].data_ptr(), start_step=start, **lr_kw(i))
 
-    res = {"tool": "rolling_bench", "device": torch.cuda.get_device_name(0),
+    res = {"tool": "rolling_bench", "device": torch.cuda.get_device_name(0), "lr_consistency": bool(a.lr),
+           "library": os.environ.get("SR3_LIB") or "in-tree",
            "shape": {"slots": SLOTS, "lres": L, "res": R, "unet": "yml image_size=224"}}
 
     # ---- step: rolling against uniform, all rows live --------------------------------------------------------------
@@ -76,6 +99,7 @@ def main():
             n = a.block
 
             def uniform_block():
+                hold_uniform(True)
                 eng.sample_begin(cond.data_ptr(), SLOTS, R, R, None, seed, 0)
                 for t in range(T - 1, T - 4, -1):       # eager step, capture, one replay
                     eng.sample_step(t)
@@ -87,7 +111,7 @@ def main():
                 return (time.perf_counter() - t0) / n * 1e3
 
             def rolling_block():
-                eng.rows_begin(SLOTS, R, R, seed)
+                rows_begin()
                 admit_all(SLOTS)
                 for _ in range(3):
                     eng.rows_step()
@@ -131,14 +155,14 @@ def main():
         # warm-up of the three workspaces' graphs happens inside each timing's first steps; the workspace changes between
         # the forms (B = 64 | 1), so each form is timed after a short run of its own
         def rolling_stream():
-            eng.rows_begin(SLOTS, R, R, seed)
+            rows_begin()
             nxt, done, first = 0, 0, None
             held = [None] * SLOTS
             t0 = time.perf_counter()
             while done < N:
                 for s in range(SLOTS):
                     if held[s] is None and nxt < N:
-                        eng.rows_admit(s, cond[nxt % SLOTS].data_ptr(), nxt)
+                        eng.rows_admit(s, cond[nxt % SLOTS].data_ptr(), nxt, **lr_kw(nxt))
                         held[s] = nxt
                         nxt += 1
                 eng.rows_step()
@@ -162,6 +186,7 @@ def main():
         def uniform_batches():
             t0, first = time.perf_counter(), None
             for k in range(0, N, SLOTS):
+                hold_uniform(True, k)
                 eng.sample(cond.data_ptr(), SLOTS, R, R, out.data_ptr(), None, seed, k)
                 if first is None:
                     eng.synchronize()
@@ -172,6 +197,7 @@ def main():
         def one_by_one():
             t0, first = time.perf_counter(), None
             for k in range(N):
+                hold_uniform(True, k)
                 eng.sample(cond[k % SLOTS].data_ptr(), 1, R, R, one.data_ptr(), None, seed, k)
                 if first is None:
                     eng.synchronize()
@@ -180,8 +206,9 @@ def main():
             return time.perf_counter() - t0, first
 
         res["stream"] = {"precision": a.precision, "T": T, "requests": N, "arrival": "all waiting at time zero"}
+        hold_uniform(True)
         eng.sample(cond.data_ptr(), SLOTS, R, R, out.data_ptr(), None, seed, 0)     # warm-up at B = 64 (both graphs below)
-        eng.rows_begin(SLOTS, R, R, seed); admit_all(SLOTS)
+        rows_begin(); admit_all(SLOTS)
         for _ in range(3):
             eng.rows_step()
         eng.rows_end()
@@ -189,6 +216,7 @@ def main():
         for name, fn in (("rolling_64_slots", rolling_stream), ("uniform_batches_of_64", uniform_batches)):
             sec, first = fn()
             res["stream"][name] = {"s": round(sec, 3), "images_per_s": round(N / sec, 2), "first_result_s": round(first, 3)}
+        hold_uniform(True)
         eng.sample(cond.data_ptr(), 1, R, R, one.data_ptr(), None, seed, 0)         # warm-up at B = 1
         eng.synchronize()
         sec, first = one_by_one()
@@ -201,10 +229,10 @@ def main():
         starts = [max(1, int(round(float(s) * T))) for s in strengths]
 
         def rolling_mixed():
-            eng.rows_begin(SLOTS, R, R, seed)
+            rows_begin()
             t0 = time.perf_counter()
             for s in range(SLOTS):
-                eng.rows_admit(s, cond[s].data_ptr(), s, init_ptr=cond[s].data_ptr(), start_step=starts[s])
+                eng.rows_admit(s, cond[s].data_ptr(), s, init_ptr=cond[s].data_ptr(), start_step=starts[s], **lr_kw(s))
             steps = 0
             while eng.rows_step():
                 steps += 1
@@ -220,6 +248,9 @@ def main():
             for s0 in sorted(set(starts)):
                 rows = [i for i in range(SLOTS) if starts[i] == s0]
                 c = cond[rows].contiguous()
+                if lr is not None:      # (the group's own LR rows, in its order)
+                    y = lr[rows].contiguous()
+                    eng.set_lr_consistency(y.data_ptr(), len(rows), L, L, 0, 1.0)
                 eng.sample(c.data_ptr(), len(rows), R, R, out.data_ptr(), None, seed, 0, init_ptr=c.data_ptr(), start_step=s0)
             eng.synchronize()
             return time.perf_counter() - t0
