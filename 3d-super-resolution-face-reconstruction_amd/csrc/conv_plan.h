@@ -55,8 +55,10 @@ bool gn_pass_writes_u(bool split_arith, const ConvPlan &pl, bool raw_wanted, int
 // and of the side launch of conv2's Winograd plan)? Decided HERE, before block1's pass runs, for the engine (run_res),
 // sr3_op_gn_res1x1 and sr3_gn_res1x1_gate.
 //   valid: exact f32 and a res_conv whose operands are x / skip themselves, unsplit (`direct`, in_split 0, no raw copy
-//          wanted); mode 2; conv1 reads the plain activated tensor (its pass does not write U); conv2's plan is a Winograd
-//          plan, so that today's 1x1 is a side launch; the kernel's shapes (gn_res1x1_shape_ok).
+//          wanted); mode 2; conv1 reads the plain activated tensor (its pass does not write U) and does not run
+//          wino_fused_kernel<4> (conv1_fused_rows, its plan's wino_fused_rows: the kernel has not been run behind that
+//          form); conv2's plan is a Winograd plan, so that today's 1x1 is a side launch; the kernel's shapes
+//          (gn_res1x1_shape_ok).
 //   tuned: the levels where every shape of the B = 64 step measured at or under 0.9 of the pair (profiles/README.md,
 //          finding 99), from GN_RES1X1_MIN_BLOCKS blocks on (the smallest count timed).
 struct GnResGate {
@@ -64,7 +66,7 @@ struct GnResGate {
     bool takes() const;     // valid, and tuned or forced, and not switched off
 };
 GnResGate gn_res1x1_gate(int prec, bool has_res, bool direct, bool raw_wanted, int in_split, int mode, bool conv1_reads_u,
-                         const ConvPlan &pl2, int B, int H, int W, int C0, int C1, int Cout);
+                         int conv1_fused_rows, const ConvPlan &pl2, int B, int H, int W, int C0, int C1, int Cout);
 // the gate of a single op (sr3_op_gn_res1x1, sr3_bench_gn_res1x1), which has no convs around it
 GnResGate gn_res1x1_gate_op(int prec, int B, int H, int W, int C0, int C1, int Cout);
 

@@ -187,7 +187,8 @@ static int wino_gemm_out_bn(const ConvParams &p, int Cin) {
 // the fragment-major weights; a width of 32 | 16 (R = 2 | 4: a block's 32 tiles are R whole tile rows) and whole blocks
 // (H % 2R == 0); whole 32-channel K-steps and 64-channel blocks; statistics slices that are a whole block or 2 | 4
 // equal parts of one; 32-bit offsets of the input DMA (bit 31 of a lane's offset switches an instruction off) and of
-// the weight loads (the four planes of a wave). Tuning: WINO_FUSED_ROWS_MIN_BLOCKS (per level).
+// the weight loads (the four planes of a wave). Tuning: WINO_FUSED_ROWS_MIN_BLOCKS (per level) and, at a width of 16,
+// WINO_FUSED_ROWS_MAX_CIN_16.
 static int wino_fused_rows(const ConvParams &p, int Cin) {
     const FormSwitch sw = form_switch(FORM_WINO_FUSED_ROWS);
     if (sw.off || p.in1.p || !p.w_wino_f) return 0;
@@ -203,6 +204,7 @@ static int wino_fused_rows(const ConvParams &p, int Cin) {
     if (((uint64_t)(2 * R + 1) * (W + 2) + W + 1) * (uint64_t)Cin * 4 + 128 >= (1ull << 31) || (uint64_t)4 * Cout * Cin * 4 >= (1ull << 31)) return 0;
     if (sw.force) return R;
     const int min_blocks = R == 2 ? WINO_FUSED_ROWS_MIN_BLOCKS : WINO_FUSED_ROWS_MIN_BLOCKS_16;
+    if (R == 4 && Cin > WINO_FUSED_ROWS_MAX_CIN_16) return 0;       // (deeper K: the position GEMMs are within 0.9)
     const uint64_t blocks = (uint64_t)p.B * bpi * (Cout / WINO_FUSED_BN);
     return (min_blocks > 0 && blocks >= (uint64_t)min_blocks) ? R : 0;
 }
@@ -382,11 +384,12 @@ bool GnResGate::takes() const {
 constexpr int GN_RES1X1_MIN_HW = 32 * 32;      // pixels of one image: the 32x32 level and above
 constexpr long GN_RES1X1_MIN_BLOCKS = 1024;
 GnResGate gn_res1x1_gate(int prec, bool has_res, bool direct, bool raw_wanted, int in_split, int mode, bool conv1_reads_u,
-                         const ConvPlan &pl2, int B, int H, int W, int C0, int C1, int Cout) {
+                         int conv1_fused_rows, const ConvPlan &pl2, int B, int H, int W, int C0, int C1, int Cout) {
     GnResGate g;
     const bool wino2 = pl2.kernel == CK_WINO_ONE_PASS || pl2.kernel == CK_WINO_THREE_PASS;
-    g.valid = prec == 0 && has_res && direct && !raw_wanted && !in_split && mode == 2 && !conv1_reads_u && wino2 &&
-              gn_res1x1_shape_ok(H, W, C0, C1, Cout);
+    // (conv1 on wino_fused_kernel<4>: the kernel has not been run behind that form)
+    g.valid = prec == 0 && has_res && direct && !raw_wanted && !in_split && mode == 2 && !conv1_reads_u && conv1_fused_rows != 4 &&
+              wino2 && gn_res1x1_shape_ok(H, W, C0, C1, Cout);
     if (g.valid) {
         const long blocks = ((long)B * H * W / 128) * (Cout / gn_res1x1_bn(B, H, W, Cout));
         g.tuned = (long)H * W >= GN_RES1X1_MIN_HW && blocks >= GN_RES1X1_MIN_BLOCKS;
@@ -399,7 +402,7 @@ GnResGate gn_res1x1_gate(int prec, bool has_res, bool direct, bool raw_wanted, i
 GnResGate gn_res1x1_gate_op(int prec, int B, int H, int W, int C0, int C1, int Cout) {
     ConvPlan wino;
     wino.kernel = CK_WINO_ONE_PASS;
-    return gn_res1x1_gate(prec, true, true, false, 0, 2, false, wino, B, H, W, C0, C1, Cout);
+    return gn_res1x1_gate(prec, true, true, false, 0, 2, false, 0, wino, B, H, W, C0, C1, Cout);
 }
 
 } // namespace sr3

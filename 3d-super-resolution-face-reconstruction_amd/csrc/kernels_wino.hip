@@ -158,10 +158,15 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const ConvParams p, co
 // Tile rows (R, as wino_up2_kernel): the block's 32 tiles are R tile rows of TPR = 32 / R tiles, R = 1 | 2 | 4 for widths
 // 64k | 32 | 16 (R > 1: ConvPlan::wino_fused_rows, a form of the three-pass plan at the 32x32 and 16x16 levels). Lane li
 // holds tile (li / TPR, li % TPR), which is tile li of the block in the image's row-major tile order, so the K loop, the
-// fragment ring, the exchange and the statistics slices are R = 1's. A stage holds, per tile row, the 4 window rows of
-// 2 TPR + 2 padded columns (padded rows 2 (ty + tr) + 0..3: the two rows that neighbouring tile rows share are staged
-// twice): 264 | 272 | 288 pixel rows of 32 floats, 33 | 34 | 36 LDS-DMA instructions; two stages are at most 73728 B, so
-// two blocks still fit in a CU's LDS.
+// fragment ring, the exchange and the statistics slices are R = 1's. A stage holds the block's 2R + 2 distinct padded
+// input rows (2 ty + 0 .. 2R + 1) of 2 TPR + 2 padded columns, each once: tile row tr reads its 4 window rows from stage
+// row 2 tr on, so the two rows that neighbouring tile rows share are fetched and stored once (staged per tile row they
+// were 25 % | 37.5 % of the input DMA at R = 2 | 4). 264 | 204 | 180 live pixel rows of 32 floats, rounded up to whole
+// LDS-DMA instructions: 264 | 208 | 184 rows, 33 | 26 | 23 instructions; the lanes of the last instruction past the
+// live rows are switched off through bit 31 of their offset. At R > 1 every wave issues 7 | 6 instructions per stage,
+// the 2 | 1 slots past the last instruction switched off the same way (they point behind the rows, still inside the
+// stage). A stage is at least the 32 KiB that half of the epilogue exchange needs (R > 1: exactly; 28 | 24 slots of
+// 1 KiB fit), two stages are at most 67584 B, so two blocks still fit in a CU's LDS.
 constexpr int WF_T = 32;                    // 2x2 output tiles per block (R = 1: one strip of a tile row)
 constexpr int WF_BN = 64;                   // output channels per block
 template <int R>
@@ -169,13 +174,18 @@ struct WfGeom {
     static_assert(R == 1 || R == 2 || R == 4, "tile rows per block");
     static constexpr int TPR = WF_T / R;            // tiles per tile row of the block
     static constexpr int WX = 2 * TPR + 2;          // padded input columns of a tile row's windows
-    static constexpr int ROWS = R * 4 * WX;         // pixel rows of 32 floats per LDS stage
-    static constexpr int STAGE = ROWS * 32;         // floats per stage
-    static constexpr int DMA = ROWS / 8;            // LDS-DMA instructions per stage (64 lanes x 16 B each)
+    static constexpr int SROWS = R == 1 ? 4 : 2 * R + 2;        // distinct padded input rows of the block's windows
+    static constexpr int PIX = SROWS * WX;          // live pixel rows of 32 floats per LDS stage
+    static constexpr int DMA = (PIX + 7) / 8;       // LDS-DMA instructions per stage (64 lanes x 16 B each)
+    static constexpr int ROWS = DMA * 8;            // pixel rows they write (rows PIX .. ROWS - 1: lanes switched off)
+    static constexpr int PER_WAVE = (DMA + 3) / 4;  // R > 1: instructions every wave issues per stage (R = 1: 8, and wave 0's 33rd)
+    static constexpr int SLOTS = R == 1 ? DMA : 4 * PER_WAVE;   // 1-KiB destinations a stage needs room for
+    static constexpr int XCHG = 4 * WF_T * WF_BN;   // floats of half the epilogue exchange
+    static constexpr int STAGE = SLOTS * 256 > XCHG ? SLOTS * 256 : XCHG;       // floats per stage
     static constexpr size_t LDS = (size_t)2 * STAGE * sizeof(float);
-    static_assert(ROWS % 8 == 0, "whole DMA instructions per stage");
-    static_assert(DMA > 32 && DMA <= 36, "eight instructions per wave and one more for the first DMA - 32 waves");
+    static_assert(R == 1 ? DMA == 33 && ROWS == PIX : PER_WAVE <= 8, "R = 1: eight instructions per wave and one more for wave 0");
     static_assert(LDS >= (size_t)4 * 2 * WF_T * WF_BN * sizeof(float), "epilogue exchange fits in the stages");
+    static_assert(2 * LDS <= 160 * 1024, "two blocks per CU");
 };
 
 template <int N, class F>
@@ -218,12 +228,19 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     const int Wp = p.in0.Wp();
     const size_t pix0 = ((size_t)n * p.in0.Hp() + 2 * ty) * Wp + 2 * tx0;     // window origin of the strip
     const char *src0 = reinterpret_cast<const char *>(p.in0.p + pix0 * Cin);
+    if constexpr (R > 1) {
+        // (block-uniform, but computed with vector multiplies: without this the compiler keeps the DMA descriptors in
+        // vector registers and wraps every DMA instruction in a loop over their distinct values)
+        const uint64_t s = reinterpret_cast<uint64_t>(src0);
+        src0 = reinterpret_cast<const char *>((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)s) |
+                                              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(s >> 32)) << 32));
+    }
 
-    // LDS-DMA: wave a issues instructions i = a + 4m; lane -> pixel row 8i + (lane >> 3) of the stage (tile row, window
-    // row, column x: padded input row 2 * tile row + window row), stored chunk lane & 7.
+    // LDS-DMA: wave a issues instructions i = a + 4m; lane -> pixel row 8i + (lane >> 3) of the stage (stage row r,
+    // column x: padded input row 2 ty + r), stored chunk lane & 7.
     // The lane's byte offset of an instruction depends on lane, i, Wp and Cin only (the channel step c0 goes into the
     // descriptor's base), so the nine offsets of the wave are computed once here and held across the K loop: dvoff[m] for
-    // i = a + 4m, dvoff[8] for the one from 32 on. Recomputed per K-step they cost 13 vector instructions each (a
+    // i = a + 4m, dvoff[8] for the one from 32 on (R = 1; R > 1: the first 7 | 6). Recomputed per K-step they cost 13 vector instructions each (a
     // division by WF_WX, three 64-bit multiply-adds, the swizzle) beside the MFMAs, and the registers were held anyway
     // (for the row index the arithmetic started from). one() pins the offset itself, so the compiler neither
     // rematerialises it in the loop nor moves the arithmetic back in: a K-step issues its DMAs with no vector
@@ -232,23 +249,32 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
     // s_waitcnt vmcnt(N) it inserts assume the fewest loads in flight, so a skipped DMA makes every later wait one
     // instruction stricter. A step with no next stage (on == false) is wave-uniform and switches its instructions off
     // in the descriptor: num_records = 0 puts every offset past its end (no memory request; the free stage may receive
-    // zeros, which nobody reads); only the instructions from 32 on (m = 8; wave 0 alone at R = 1, waves 0 and 1 at
-    // R = 2, every wave at R = 4) sit behind a wave-uniform branch, one per wave, and they go first.
+    // zeros, which nobody reads); only R = 1's instruction 32 (m = 8, wave 0 alone) sits behind a wave-uniform branch,
+    // and it goes first. At R > 1 nothing does: every wave issues PER_WAVE instructions, and a lane past the live rows
+    // (the tail of the last instruction, the whole of a slot past it; fixed per wave, m and lane) holds an offset with
+    // bit 31 set, which no live descriptor reaches.
     // A live descriptor ends at 2^31 - 1 bytes, so a live offset must stay below it:
     // (3 Wp + 65) * Cin * 4 + 128 < 2^31, i.e. Wp * Cin < 1.7e8 (the widest row of the UNet: 130 * 384 = 5e4);
-    // R > 1: ((2R + 1) Wp + 2 TPR + 1) * Cin * 4 + 128, with Wp = 2 TPR + 2 <= 34 (conv_plan checks it).
+    // R > 1: ((2R + 1) Wp + 2 TPR + 1) * Cin * 4 + 128 (stage row 2R + 1 is the last), with Wp = 2 TPR + 2 <= 34
+    // (conv_plan checks it).
     unsigned dvoff[9];
     {
         const unsigned cs4 = (unsigned)Cin * 4u;
         auto lane_off = [&](int i) {
             const int q = 8 * i + (lane >> 3);
-            const int wr = q / WF_WX, x = q - wr * WF_WX;
-            const int r = R == 1 ? wr : 2 * (wr >> 2) + (wr & 3);
-            return (unsigned)(r * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16);
+            const int r = q / WF_WX, x = q - r * WF_WX;
+            const unsigned voff = (unsigned)(r * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16);
+            if constexpr (R == 1) return voff;
+            else return q < G::PIX ? voff : 0x80000000u;
         };
+        if constexpr (R == 1) {
 #pragma unroll
-        for (int m = 0; m < 8; ++m) dvoff[m] = lane_off(a + 4 * m);
-        dvoff[8] = lane_off(R == 1 ? 32 : 32 + a);       // (R > 1, a >= WF_DMA - 32: never issued)
+            for (int m = 0; m < 8; ++m) dvoff[m] = lane_off(a + 4 * m);
+            dvoff[8] = lane_off(32);
+        } else {
+#pragma unroll
+            for (int m = 0; m < G::PER_WAVE; ++m) dvoff[m] = lane_off(a + 4 * m);
+        }
     }
     auto issue = [&](int c0, int stage, bool on) {
         const __amdgpu_buffer_rsrc_t rsrc =
@@ -261,10 +287,8 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
         };
         if constexpr (R == 1) {
             if (a == 0 && on) one(32, dvoff[8]);
-        } else {
-            if (a < WF_DMA - 32 && on) one(32 + a, dvoff[8]);
         }
-        wf_static_for<8>([&](auto mc) { constexpr int m = decltype(mc)::value; one(a + 4 * m, dvoff[m]); });
+        wf_static_for<(R == 1 ? 8 : G::PER_WAVE)>([&](auto mc) { constexpr int m = decltype(mc)::value; one(a + 4 * m, dvoff[m]); });
     };
 
     // B fragments: lane (li, h) loads channels c0 + 8kk + 4h .. +3 of output channel n0 + 32ni + li, position 4a + b,
@@ -297,8 +321,8 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
             aoff[1][x] = (rb * WF_WX + 2 * li + x) * 32;
             asw[x] = (li + (x >> 1)) & 7;
         } else {
-            aoff[0][x] = ((4 * ltr + ra) * WF_WX + 2 * ltc + x) * 32;
-            aoff[1][x] = ((4 * ltr + rb) * WF_WX + 2 * ltc + x) * 32;
+            aoff[0][x] = ((2 * ltr + ra) * WF_WX + 2 * ltc + x) * 32;   // (tile row ltr: stage rows 2 ltr + 0..3)
+            aoff[1][x] = ((2 * ltr + rb) * WF_WX + 2 * ltc + x) * 32;
             asw[x] = (ltc + (x >> 1)) & 7;
         }
     }
@@ -472,11 +496,12 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
 // (transforms and indexing: sr3_internal.h at make_up2_wino_weights.) One pass, modelled on wino_fused_kernel:
 //   * block = 32 tiles of the phase images (R tile rows x TPR = 32 / R tiles) x WU_BN = 32 output channels x the four
 //     phases; wave a owns phase (py, px) = (a >> 1, a & 1). The 3x3 windows of all four phases lie inside the 4x4
-//     low-resolution window (padded rows 2ti .. 2ti + 3) of the tile, so a stage is wino_fused_kernel's: per tile row 4
-//     rows of WX = 2 TPR + 2 padded pixels x 32 channels, by LDS-DMA with the same swizzle (264 | 272 | 288 pixel rows
-//     for R = 1 | 2 | 4: 33 | 34 | 36 instructions). Every wave issues nine instructions per stage, whatever R: the ones
-//     past the stage's last (and all nine of a step that has no next stage) go past the end of the descriptor, so no
-//     vector memory instruction of the K loop sits behind a branch; a stage has room for all 36.
+//     low-resolution window (padded rows 2ti .. 2ti + 3) of the tile, so a stage is wino_fused_kernel's: the block's
+//     2R + 2 distinct padded rows (R = 1: 4), each once, of WX = 2 TPR + 2 padded pixels x 32 channels, by LDS-DMA with
+//     the same swizzle (264 | 204 | 180 live pixel rows for R = 1 | 2 | 4: 33 | 26 | 23 instructions, the tail of the
+//     last one switched off). Every wave issues 9 | 7 | 6 instructions per stage: the lanes past the live rows (and every
+//     lane of a step that has no next stage) go past the end of the descriptor, so no vector memory instruction of the K
+//     loop sits behind a branch; a stage has room for all 36 | 28 | 24 slots.
 //   * per 8-channel group a lane reads the nine window pixels of its tile (4 channels each), forms B^T d B with
 //     differences only, and runs 9 positions x 4 MFMAs against B fragments loaded straight from the fragment-major
 //     weights [phase][position][CinPad/8][Cout][8]; each position's fragment is reloaded for the next group right
@@ -490,7 +515,7 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(const ConvParams p, 
 //     pair one after the other and the second adds to what the first stored. No LDS, no atomics, no inter-block waits.
 // Registers: 9 positions x 16 accumulators = 144, a ring of six B fragments (24), nine transformed values (36).
 constexpr int WU_BN = 32;
-constexpr int WU_DMA = 36;                  // LDS-DMA slots per stage (nine per wave)
+constexpr int WU_DMA = 36;                  // LDS-DMA slots per stage (R = 1: nine per wave; R = 2 | 4 use 28 | 24)
 constexpr int WU_STAGE = WU_DMA * 256;      // floats per stage
 constexpr size_t WU_LDS = (size_t)2 * WU_STAGE * sizeof(float);
 static_assert(WU_BN == UP2_WINO_BN && UP2_WINO_TILES == 32, "conv_plan gates wino_up2_kernel on its block shape");
@@ -498,8 +523,9 @@ static_assert(WU_BN == UP2_WINO_BN && UP2_WINO_TILES == 32, "conv_plan gates win
 template <int R>
 __global__ __launch_bounds__(256, 2) void wino_up2_kernel(const ConvParams p, int smode) {
     const int nst = smode == 1 ? 2 : 1;
-    constexpr int TPR = 32 / R, WX = 2 * TPR + 2, ROWS = R * 4 * WX, NDMA = ROWS / 8;
-    static_assert(ROWS % 8 == 0 && NDMA <= WU_DMA, "whole DMA instructions, inside a stage");
+    constexpr int TPR = 32 / R, WX = 2 * TPR + 2, PIX = (R == 1 ? 4 : 2 * R + 2) * WX;     // live pixel rows of a stage
+    constexpr int NDMA = (PIX + 7) / 8, NPW = (NDMA + 3) / 4;                              // instructions per stage / per wave
+    static_assert(4 * NPW <= WU_DMA, "every slot inside a stage");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Cin = p.in0.C, Cout = p.out.C;
     const int Hl = p.in0.H, Wl = p.in0.W, th = Hl >> 1, tw = Wl >> 1;     // tiles of a phase image
@@ -538,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void wino_up2_kernel(const ConvParams p, in
     // the lane's tile and its window: pixel (py + i, px + j) of the tile's 4x4 window, i, j = 0..2
     // (float offset wbase + (i WX + j) * 32 in a stage, 16-B chunk c of column j at c ^ wsw[j])
     const int ltr = li / TPR, ltc = li - ltr * TPR;
-    const int wbase = ((ltr * 4 + py) * WX + 2 * ltc + px) * 32;
+    const int wbase = ((ltr * 2 + py) * WX + 2 * ltc + px) * 32;       // (tile row ltr: stage rows 2 ltr + 0..3)
     int wsw[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) wsw[j] = (ltc + ((px + j) >> 1)) & 7;
@@ -547,25 +573,25 @@ __global__ __launch_bounds__(256, 2) void wino_up2_kernel(const ConvParams p, in
     float add = p.bias ? p.bias[co] : 0.f;               // (the direct kernel's epilogue order: bias, FeatureWiseAffine bias)
     if (p.chan_bias) add += p.chan_bias[(size_t)n * p.chan_bias_stride + co];
 
-    // LDS-DMA: wave a issues instructions i = a + 4m, m = 0..8; lane -> pixel row 8i + (lane >> 3) of the stage
-    // (tile row, window row r, column x), stored chunk lane & 7. The lane's byte offsets depend on lane, i, Wp and Cin
+    // LDS-DMA: wave a issues instructions i = a + 4m, m = 0..NPW - 1; lane -> pixel row 8i + (lane >> 3) of the stage
+    // (stage row, column x: padded row 2 ti0 + stage row), stored chunk lane & 7. The lane's byte offsets depend on lane, i, Wp and Cin
     // only (strip and channel step go into the descriptor's base), so they are computed once for all strips and K-steps
     // and held (dvoff, pinned in issue() as in wino_fused_kernel). A live descriptor ends at 2^31 - 1 bytes and a live
-    // offset stays below it (conv_plan: (10 Wp + 70) * Cin * 4 < 2^31); an instruction past the stage's last
-    // (i >= NDMA, fixed per wave and m) holds an offset with bit 31 set, and a step with no next stage (on == false,
+    // offset stays below it (conv_plan: (10 Wp + 70) * Cin * 4 < 2^31; stage row 2R + 1 <= 9 is the last); a lane past
+    // the live rows (q >= PIX, fixed per wave, m and lane) holds an offset with bit 31 set, and a step with no next stage (on == false,
     // wave-uniform) takes a descriptor with num_records = 0: either way the load is out of range and makes no memory
     // request.
-    unsigned dvoff[9];
+    unsigned dvoff[NPW];
     {
         const unsigned cs4 = (unsigned)Cin * 4u;
 #pragma unroll
-        for (int m = 0; m < 9; ++m) {
+        for (int m = 0; m < NPW; ++m) {
             const int i = a + 4 * m;
             const int q = 8 * i + (lane >> 3);
             const int wr = q / WX, x = q - wr * WX;
-            const int row = 2 * (wr >> 2) + (wr & 3);
+            const int row = R == 1 ? 2 * (wr >> 2) + (wr & 3) : wr;      // (R = 1: wr itself in every live lane)
             const unsigned voff = (unsigned)(row * Wp + x) * cs4 + (unsigned)(((lane & 7) ^ ((x >> 1) & 7)) * 16);
-            dvoff[m] = i < NDMA ? voff : 0x80000000u;
+            dvoff[m] = (R == 1 ? i < NDMA : q < PIX) ? voff : 0x80000000u;
         }
     }
 
@@ -579,7 +605,7 @@ __global__ __launch_bounds__(256, 2) void wino_up2_kernel(const ConvParams p, in
             const __amdgpu_buffer_rsrc_t rsrc =
                 __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(src0 + (size_t)c0 * 4), 0, on ? 0x7fffffff : 0, 0x00020000);
             float *dst = smem + stage * WU_STAGE;
-            wf_static_for<9>([&](auto mc) {
+            wf_static_for<NPW>([&](auto mc) {
                 constexpr int m = decltype(mc)::value;
                 asm volatile("" : "+v"(dvoff[m]));   // (held, not recomputed: as in wino_fused_kernel)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst + (a + 4 * m) * 256),

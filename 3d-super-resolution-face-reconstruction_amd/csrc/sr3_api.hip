@@ -1035,15 +1035,16 @@ void run_res(sr3_ctx *c, Module &m, const TDesc &x, const StatsRef &sx, const TD
     k1.out = m.h1; k1.stats = m.st_h1;
     const bool raw1 = rb.has_res && !direct;
     const int in_split1 = (x_so ? 1 : 0) | (skip.p && sk_so ? 2 : 0);
-    k1.u_ready = gn_writes_u(c, k1, raw1, in_split1);
+    const ConvPlan pl1 = conv_plan(conv_params(c, k1));
+    k1.u_ready = gn_pass_writes_u(c->split(), pl1, raw1, in_split1);
     // the same pass multiplies the res_conv into the block's output where conv2 would run it as a side launch
     ConvCall q2;                         // (what conv2's plan depends on)
     q2.in = m.act2; q2.conv = &rb.c2; q2.B = B; q2.activated = true; q2.f8 = f8b; q2.out = m.rb_out; q2.stats = m.st_rb;
     GnRes1x1 res1;
     ConvPlan pl2;                        // (asked only where the rest of the gate can say yes)
     if (!c->split() && rb.has_res && direct) pl2 = conv_plan(conv_params(c, q2));
-    const bool res_pass = gn_res1x1_gate(c->split() ? 1 : 0, rb.has_res, direct, raw1, in_split1, 2, k1.u_ready, pl2, B, h, w,
-                                         x.C, skip.p ? skip.C : 0, rb.cout).takes();
+    const bool res_pass = gn_res1x1_gate(c->split() ? 1 : 0, rb.has_res, direct, raw1, in_split1, 2, k1.u_ready, pl1.wino_fused_rows,
+                                         pl2, B, h, w, x.C, skip.p ? skip.C : 0, rb.cout).takes();
     if (res_pass) { res1.w2 = c->params[rb.res.w].dev; res1.out = m.rb_out; }
     run_gn_act(c, x_so ? xr : x, (skip.p && sk_so) ? skr : skip, rb.gn1, B, 2, m.act1, sx, ss, raw1 ? m.raw1 : kNone, in_split1,
                f8a, k1.u_ready ? c->wino_ws : nullptr, DropLayer(), res_pass ? &res1 : nullptr);
@@ -3831,7 +3832,8 @@ int sr3_gn_res1x1_gate(int B, int H, int W, int C0, int C1, int Cout, int precis
         pl2 = conv_plan_offered(B, H, W, Cout, Cout, 3, 1, 0, precision ? 1 : 0, false, true);
         reads_u = gn_pass_writes_u(precision != 0, pl1, raw_wanted, in_split ? 1 : 0);
     }
-    const GnResGate g = gn_res1x1_gate(precision ? 1 : 0, has_res, direct, raw_wanted, in_split ? 1 : 0, mode, reads_u, pl2, B, H, W, C0, C1, Cout);
+    const GnResGate g = gn_res1x1_gate(precision ? 1 : 0, has_res, direct, raw_wanted, in_split ? 1 : 0, mode, reads_u, pl1.wino_fused_rows,
+                                       pl2, B, H, W, C0, C1, Cout);
     return (g.valid ? 1 : 0) | (g.tuned ? 2 : 0) | (g.takes() ? 4 : 0);
 }
 

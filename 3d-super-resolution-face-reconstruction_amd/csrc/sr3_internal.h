@@ -279,10 +279,15 @@ constexpr int WINO_FUSED_TILES = 32, WINO_FUSED_BN = 64;
 // tiles are R = 2 | 4 tile rows of 16 | 8 tiles, i.e. 32 consecutive tiles of the image. What it saves over the three
 // passes is U's trip through memory (four times the activated input, written by the GroupNorm pass and read by the
 // GEMMs) and, beyond WINO_GEMM_OUT_MAX_CIN, M's. Taken from WINO_FUSED_ROWS_MIN_BLOCKS blocks on at a width of 32 (the
-// smallest count timed: the B = 64 step's 32x32 convs; profiles/README.md finding 91); the 16x16 level did not pass
-// the 0.9 rule there and is reached only under SR3_WINO_FUSED_ROWS_FORCE=1 (0: never by default).
+// smallest count timed: the B = 64 step's 32x32 convs; profiles/README.md finding 91). At a width of 16, from
+// WINO_FUSED_ROWS_MIN_BLOCKS_16 blocks on (B = 64, Cout = 512: the only count timed) and up to
+// WINO_FUSED_ROWS_MAX_CIN_16 input channels: with each window row staged once, Cin = 256 and 512 run at 0.88 and
+// 0.85-0.88 of the three-pass form in both rounds, Cin = 768 and 1024 at 0.92-0.96, over the 0.9 rule (finding 102);
+// those stay on the position GEMMs and are reached only under SR3_WINO_FUSED_ROWS_FORCE=1.
+// (tests/test_wino_rows16_host.py restates the gate with all three constants: retune them there too)
 constexpr int WINO_FUSED_ROWS_MIN_BLOCKS = 2048;
-constexpr int WINO_FUSED_ROWS_MIN_BLOCKS_16 = 0;
+constexpr int WINO_FUSED_ROWS_MIN_BLOCKS_16 = 1024;
+constexpr int WINO_FUSED_ROWS_MAX_CIN_16 = 512;
 // host helper: packed [9][Cout][CinPad] -> G g G^T as [16][Cout][CinPad] (fp64, rounded once to fp32)
 void make_wino_weights(const float *packed9, int Cout, int CinPad, float *dst);
 // host helper: [16][Cout][CinPad] (make_wino_weights) -> [16][CinPad/8][Cout][8]; launch_wino_frag: the same on the device
