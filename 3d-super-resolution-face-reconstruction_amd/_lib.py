@@ -64,6 +64,10 @@ PROTOTYPES = {
     "sr3_set_precision": (_I, [_P, _I]),
     "sr3_conv_f8_supported": (_I, [_I, _I, _I, _I, _I]),
     "sr3_conv_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int64), C.c_char_p, _I]),
+    "sr3_set_batch_invariant": (_I, [_P, _I]),
+    "sr3_get_batch_invariant": (_I, [_P]),
+    "sr3_conv_plan_invariant": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int64), C.c_char_p, _I]),
+    "sr3_conv_plan_invariant_max_batch": (C.c_int64, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "sr3_num_params": (_I, [_P]),
     "sr3_param_info": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(C.c_int64), C.POINTER(_I)]),
     "sr3_load_weight": (_I, [_P, C.c_char_p, _F, C.POINTER(C.c_int64), _I]),

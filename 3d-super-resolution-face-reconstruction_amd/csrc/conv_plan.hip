@@ -45,6 +45,14 @@ FormSwitch form_switch(Form f) {
     return {env_switch(pair[f][0]) != 0, env_switch(pair[f][1]) != 0};
 }
 
+// ---- batch-invariant mode: the planning batch of the calling thread ----------------------------------
+// Every decision below that asks "is there enough work for this form?" reads plan_b(B) in place of B; every rule that
+// says "the kernel can run this shape" is evaluated on one image, so that what holds at B = 1 holds at every B; a limit
+// on the real B (tile counters, 32-bit offsets) becomes ConvPlan::batch_limit, the mode's maximum batch.
+namespace { thread_local int g_plan_batch = 0; }
+int plan_batch() { return g_plan_batch; }
+int set_plan_batch(int P) { const int prev = g_plan_batch; g_plan_batch = P > 0 ? P : 0; return prev; }
+
 int splitk_reduce_tp(int HWo) { const int tp = HWo / 64; return tp < 1 ? 1 : tp; }
 int splitk_stats_slices(int HWo, int Cout) {
     const int tp = splitk_reduce_tp(HWo);
@@ -85,6 +93,7 @@ static bool halo_off() { return env_switch(SW_NO_HALO) != 0; }
 // arrives last (conv3x3_halo_h3, end of the consumer path) — no reduce pass, statistics in the unsplit layout (one
 // slice per 128-row tile, or one per image where a tile covers several whole images). 0 or 1: not for this shape.
 // Assumes ks 3, stride 1, prec 1, pad 1 (conv_plan checks them).
+// M: the pixels the gates count (the planning batch's in the batch-invariant mode, where whole tiles per IMAGE are asked for)
 static int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
     const int force = env_switch(SW_HALO_SPLITS);               // product switch: 0 off, 2 | 4 forced
     if (force == 0 || halo_off()) return 0;
@@ -93,6 +102,7 @@ static int conv_halo_splits(long M, int H, int W, int Cout, int Cin) {
     const int seg = W < 128 ? W : 128;
     if ((W % seg) || (128 % seg)) return 0;
     if (HWo >= 128 ? (HWo % 128) != 0 : ((128 % HWo) != 0 || (HWo % 32) != 0)) return 0;
+    if (plan_batch() > 0 && HWo < 128) return 0;        // (a tile over several whole images does not exist at B = 1)
     if (conv_tile_choice(M, Cout).generic != CK_GENERIC_64x64) return 0;   // enough 128-row tiles already: no split needed
     const long tiles = (M / 128) * (Cout / 128);
     const int nchunk = Cin / 32;
@@ -110,8 +120,9 @@ static bool halo_ok(const ConvParams &p, int splits, int BM, int segmin, int bn,
     if (p.in0.W != W || p.in0.H != p.Hout) return false;
     const int seg = W < BM ? W : BM;
     if (seg < segmin || (W % seg) || (BM % seg)) return false;
-    const long M = (long)p.B * p.Hout * W;
-    // no masking anywhere in the halo kernels: whole tiles in M and (for the tile width bn the caller picks) in N
+    // no masking anywhere in the halo kernels: whole tiles in M (batch-invariant mode: in every image, so that the answer
+    // at B = 1 is the answer) and (for the tile width bn the caller picks) in N
+    const long M = (long)(plan_batch() > 0 ? 1 : p.B) * p.Hout * W;
     return (M % BM) == 0 && (p.out.C % bn) == 0 && (!p.in2.p || (p.in2.C % 32) == 0) && (!p.in2b.p || (p.in2b.C % 32) == 0);
 }
 
@@ -120,7 +131,7 @@ static bool halo_ok(const ConvParams &p, int splits, int BM, int segmin, int bn,
 // chip (fewer: the direct kernel, whose smaller tiles spread further)
 static bool wino_fused_shape(int B, int H, int W, int Cin, int Cout) {
     if (H * W < 4096 || (H & 1) || (W % (2 * WINO_FUSED_TILES)) || Cin < WINO_FUSED_CIN || (Cin % 32) || (Cout % WINO_FUSED_BN)) return false;
-    const uint64_t blocks = (uint64_t)B * (H / 2) * (W / (2 * WINO_FUSED_TILES)) * (Cout / WINO_FUSED_BN);
+    const uint64_t blocks = (uint64_t)plan_b(B) * (H / 2) * (W / (2 * WINO_FUSED_TILES)) * (Cout / WINO_FUSED_BN);
     return blocks >= WINO_FUSED_MIN_BLOCKS;
 }
 
@@ -131,10 +142,11 @@ static bool wino_shape(int B, int H, int W, int Cin, int Cout) {
     if ((H & 1) || (W & 1) || H * W > 1024 || Cin < WINO_MIN_CIN || (Cin % 32) || (Cout % 64)) return false;
     // few tiles (a single 128x128 image: 256 at its 32x32 level): the three dependent passes cost more latency than the
     // MACs they save (B = 1 step 1.99 -> 2.27 ms with every level in Winograd form); B = 64 at 8x8 is 1024 tiles and gains
-    const uint64_t tiles = (uint64_t)B * (H / 2) * (W / 2);
-    if (tiles < WINO_MIN_TILES) return false;
+    const uint64_t tpi = (uint64_t)(H / 2) * (W / 2);
+    if ((uint64_t)plan_b(B) * tpi < WINO_MIN_TILES) return false;
     // the LDS-DMA and epilogue addressing of the position GEMMs uses 32-bit byte offsets inside one position's plane
-    return tiles * (uint64_t)(Cin > Cout ? Cin : Cout) * 4 < (1ull << 32);
+    // (batch-invariant mode: asked of one image; the real batch's bound is ConvPlan::batch_limit)
+    return (plan_batch() > 0 ? 1 : (uint64_t)B) * tpi * (uint64_t)(Cin > Cout ? Cin : Cout) * 4 < (1ull << 32);
 }
 
 // the Winograd form this conv runs in, CK_COUNT: none (the direct kernels)
@@ -175,10 +187,11 @@ static int wino_gemm_out_bn(const ConvParams &p, int Cin) {
         if (tps != 16 && tps != 32) return 0;
     }
     // the epilogue addresses the zero-bordered output (and the residual, same geometry) with 32-bit byte offsets
-    if ((uint64_t)p.out.floats(p.B) * 4 >= (1ull << 32)) return 0;
+    // (batch-invariant mode: every activation tensor of a call within the mode's maximum batch is below 4 GiB)
+    if ((uint64_t)p.out.floats(plan_batch() > 0 ? 1 : p.B) * 4 >= (1ull << 32)) return 0;
     const int bn = (Cout % 128) == 0 ? 128 : 64;
     if (sw.force) return bn;
-    const long blocks = (((long)p.B * tpi + WINO_GEMM_OUT_TILES - 1) / WINO_GEMM_OUT_TILES) * (Cout / bn);
+    const long blocks = ((plan_b(p.B) * tpi + WINO_GEMM_OUT_TILES - 1) / WINO_GEMM_OUT_TILES) * (Cout / bn);
     return (blocks >= WINO_GEMM_OUT_MIN_BLOCKS && Cin <= WINO_GEMM_OUT_MAX_CIN) ? bn : 0;
 }
 
@@ -205,7 +218,7 @@ static int wino_fused_rows(const ConvParams &p, int Cin) {
     if (sw.force) return R;
     const int min_blocks = R == 2 ? WINO_FUSED_ROWS_MIN_BLOCKS : WINO_FUSED_ROWS_MIN_BLOCKS_16;
     if (R == 4 && Cin > WINO_FUSED_ROWS_MAX_CIN_16) return 0;       // (deeper K: the position GEMMs are within 0.9)
-    const uint64_t blocks = (uint64_t)p.B * bpi * (Cout / WINO_FUSED_BN);
+    const uint64_t blocks = (uint64_t)plan_b(p.B) * bpi * (Cout / WINO_FUSED_BN);
     return (min_blocks > 0 && blocks >= (uint64_t)min_blocks) ? R : 0;
 }
 
@@ -247,7 +260,7 @@ static int up2_wino_rows(const ConvParams &p, const ConvPlan &direct) {
         if (direct.tile_m == 128 && Wl > 64 && (Wl % 128)) return 0;
     }
     if (((uint64_t)10 * (Wl + 2) + 70) * (uint64_t)Cin * 4 >= (1ull << 31) || (uint64_t)9 * Cout * Cin * 4 >= (1ull << 31)) return 0;
-    const uint64_t blocks = (uint64_t)p.B * ((uint64_t)Hl * Wl / (4 * UP2_WINO_TILES)) * (Cout / UP2_WINO_BN);
+    const uint64_t blocks = (uint64_t)plan_b(p.B) * ((uint64_t)Hl * Wl / (4 * UP2_WINO_TILES)) * (Cout / UP2_WINO_BN);
     return (sw.force || blocks >= (uint64_t)UP2_WINO_MIN_BLOCKS) ? R : 0;
 }
 
@@ -263,16 +276,26 @@ static ConvPlan conv_plan_direct(const ConvParams &p_in) {
     const int Cout = p.out.C, Cin = p.in0.C + (p.in1.p ? p.in1.C : 0);
     const int HWo = p.Hout * p.Wout;                 // pixels of one image (and phase)
     const long M = (long)p.B * HWo;
-    const Tile t = conv_tile_choice(M, Cout);
+    // what the performance gates count: the planning batch's pixels in the batch-invariant mode, else the call's
+    const bool inv = plan_batch() > 0;
+    const long Mp = plan_b(p.B) * HWo;
+    const Tile t = conv_tile_choice(Mp, Cout);
     ConvPlan plan;
+    // batch-invariant mode: a limit on the real batch never changes the form, it bounds the batch (and fails a launch past it)
+    auto limit = [&](uint64_t b) {
+        if (!inv) return;
+        const long l = (long)std::min<uint64_t>(b, 1u << 30);
+        if (plan.batch_limit == 0 || l < plan.batch_limit) plan.batch_limit = l;
+        if (p.B > l) plan.error = "batch-invariant mode: the batch exceeds the mode's maximum (sr3_max_batch)";
+    };
     plan.phases = p.phases;
     plan.tile_m = t.bm; plan.tile_n = t.bn;
     // split-K of the generic kernel: in place on the 64x64 tile where every tile has a counter, whole tiles per image (the
     // statistics slices are per M-tile of an image) and in N (nothing is masked in the fix-up); else conv + reduce kernel
     const int no_inplace = env_switch(SW_NO_INPLACE_SPLIT);
-    const int gs = p.part ? conv_splits(M, Cout, Cin) : 1;
+    const int gs = p.part ? conv_splits(Mp, Cout, Cin) : 1;
     const bool inplace = gs > 1 && p.tile_cnt && !no_inplace && t.generic == CK_GENERIC_64x64 && (HWo % t.bm) == 0 && (Cout % t.bn) == 0 &&
-                         tile_count(t, M, Cout) * p.phases <= CONV_TILE_COUNTERS;
+                         tile_count(t, inv ? Mp : M, Cout) * p.phases <= CONV_TILE_COUNTERS;
     // fused statistics: one slice per M-tile of an image (an in-place split conv leaves the same slices as an unsplit
     // one; every kernel of one output shape uses the same tile height), a two-kernel split one slice per reduce block
     plan.stats_slices = p.phases * ((gs > 1 && !inplace) ? splitk_stats_slices(HWo, Cout) : (HWo % t.bm) == 0 ? HWo / t.bm : 0);
@@ -280,6 +303,8 @@ static ConvPlan conv_plan_direct(const ConvParams &p_in) {
     const ConvKernel wino = wino_form(p);
     if (wino != CK_COUNT) {
         plan.kernel = wino;
+        if (wino == CK_WINO_THREE_PASS)
+            limit(((1ull << 32) - 1) / ((uint64_t)(p.Hout / 2) * (p.Wout / 2) * (uint64_t)std::max(Cin, Cout) * 4));
         plan.needs_wino_frag = wino == CK_WINO_ONE_PASS;       // (U and M never leave the CU)
         if (wino == CK_WINO_THREE_PASS) {
             plan.wino_ws_floats = (size_t)16 * p.B * (p.Hout / 2) * (p.Wout / 2) * (Cin + Cout);
@@ -295,17 +320,19 @@ static ConvPlan conv_plan_direct(const ConvParams &p_in) {
     };
     if (p.prec == 1 && p.ks == 3 && p.stride == 1 && p.phases == 1 && p.part != nullptr && p.tile_cnt != nullptr && p.in0.pad == 1 &&
         p.in0.W == p.Wout && p.in0.H == p.Hout && !p.no_halo_split) {
-        const int hs = conv_halo_splits(M, p.Hout, p.Wout, Cout, Cin);
+        const int hs = conv_halo_splits(Mp, p.Hout, p.Wout, Cout, Cin);
         const bool stats_ok = p.stats == nullptr || p.stats_slices == (HWo >= 128 ? HWo / 128 : 1);
         const bool seg32 = halo_ok(p, hs, 128, 32, 128, true);
         if (hs > 1 && stats_ok && (seg32 || halo_ok(p, hs, 128, 8, 128, true))) {
             plan.kernel = seg32 ? CK_HALO_128x128_SEG32 : CK_HALO_128x128_SEG8;
             plan.tile_m = plan.tile_n = 128;
             split(CS_INPLACE_HALO, hs);
+            if (inv) limit((uint64_t)CONV_TILE_COUNTERS / ((uint64_t)(HWo / 128) * (Cout / 128)));     // (HWo >= 128 there)
             return plan;
         }
     }
     if (gs > 1) split(inplace ? CS_INPLACE : CS_REDUCE, gs);
+    if (gs > 1 && inplace) limit((uint64_t)CONV_TILE_COUNTERS / ((uint64_t)tile_count(t, HWo, Cout) * p.phases));
     if (p.f8) {
         // the caller asked conv_f8_supported() first and wrote the input / passes the weights in the F8C format
         // (conv_f8_supported is this plan's answer; a mismatch is a library bug, reported through the API's error
@@ -362,12 +389,13 @@ GnRoute gn_route(const TDesc &a, const TDesc &b, int B, const StatsRef &sa, cons
     // bytes the pass moves (read + write, 4 B per element each way): above ~200 MB the one-item-per-thread
     // streaming kernel behind a separate finalize launch is faster than the folded form (A/B on one box,
     // profiles/README.md); below it the launch saved and the shorter critical path win
-    const double pass_bytes = 8.0 * B * a.H * a.W * (a.C + (b.p ? b.C : 0));
+    const long Bp = plan_b(B);           // (batch-invariant mode: the planning batch's pass)
+    const double pass_bytes = 8.0 * Bp * a.H * a.W * (a.C + (b.p ? b.C : 0));
     constexpr double fold_max = 200.0 * 1e6;
     // few images with many statistics slices (a single 128x128 image on 64x64 tiles leaves 256): the folded form's
     // prologue walks them in 12-16 dependent round trips in EVERY block (12-23 us per apply at B = 1); the
     // per-(image, group) finalize launch takes one round trip
-    const bool many_slices = (long)B * 4 < 128 && std::max(sa.slices, b.p ? sb.slices : 0) >= 64;
+    const bool many_slices = Bp * 4 < 128 && std::max(sa.slices, b.p ? sb.slices : 0) >= 64;
     return (pass_bytes > fold_max || many_slices) ? GN_FINALIZE_ROWS : GN_FOLDED;
 }
 
@@ -391,7 +419,7 @@ GnResGate gn_res1x1_gate(int prec, bool has_res, bool direct, bool raw_wanted, i
     g.valid = prec == 0 && has_res && direct && !raw_wanted && !in_split && mode == 2 && !conv1_reads_u && conv1_fused_rows != 4 &&
               wino2 && gn_res1x1_shape_ok(H, W, C0, C1, Cout);
     if (g.valid) {
-        const long blocks = ((long)B * H * W / 128) * (Cout / gn_res1x1_bn(B, H, W, Cout));
+        const long blocks = (plan_b(B) * H * W / 128) * (Cout / gn_res1x1_bn(B, H, W, Cout));
         g.tuned = (long)H * W >= GN_RES1X1_MIN_HW && blocks >= GN_RES1X1_MIN_BLOCKS;
     }
     return g;

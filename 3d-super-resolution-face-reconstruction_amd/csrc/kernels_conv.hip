@@ -1690,12 +1690,12 @@ static int log2_exact(int v) { int s = 0; while ((1 << s) < v) ++s; return (1 <<
 
 void launch_wino_gemm(const ConvParams &p_in, hipStream_t s) {
     ConvParams p = p_in;
-    const long M = (long)p.B * p.Hout * p.Wout;
     p.hw_shift = log2_exact(p.Hout * p.Wout);
     p.w_shift = log2_exact(p.Wout);
     p.splits = 1; p.part = nullptr; p.tile_cnt = nullptr; p.stats = nullptr; p.phases = 1;
     // the zbatch GEMMs fill the chip together: the tile is chosen for their combined rows
-    switch (conv_tile_choice(M * p.zbatch, p.out.C).generic) {
+    // (batch-invariant mode: for the planning batch's)
+    switch (conv_tile_choice(plan_b(p.B) * p.Hout * p.Wout * p.zbatch, p.out.C).generic) {
     case CK_GENERIC_128x32: launch_inst2<128, 32, 4, 1, 1, 0, 2, true>(p, s); break;
     case CK_GENERIC_128x64: launch_inst2<128, 64, 2, 2, 1, 0, 2, true>(p, s); break;
     case CK_GENERIC_64x64: launch_inst2<64, 64, 2, 2, 1, 0, 4, true>(p, s); break;

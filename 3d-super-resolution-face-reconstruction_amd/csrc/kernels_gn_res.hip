@@ -314,7 +314,7 @@ bool gn_res1x1_shape_ok(int H, int W, int C0, int C1, int Cout) {
 
 // output channels per block: 128 where that still leaves two resident blocks per CU on 256 CUs (conv_tile_choice's rule)
 int gn_res1x1_bn(int B, int H, int W, int Cout) {
-    const long M = (long)B * H * W;
+    const long M = plan_b(B) * H * W;
     return ((Cout % 128) == 0 && (M / GR_BM) * (Cout / 128) >= 512) ? 128 : 64;
 }
 

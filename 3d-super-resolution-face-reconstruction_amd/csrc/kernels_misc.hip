@@ -205,7 +205,9 @@ __global__ __launch_bounds__(256) void gn_finalize_group_kernel(const double *__
 
 } // namespace
 
+// (B: the planning batch in the batch-invariant mode — the slice count fixes the order of the fp64 sums)
 static int gn_slices(int B, int HW) {
+    B = (int)plan_b(B);
     int s = 2048 / (B > 0 ? B : 1);
     if (s < 1) s = 1;
     int cap = HW / 64;
@@ -234,7 +236,7 @@ void launch_groupnorm_finalize(const StatsRef &s0, int C0, const StatsRef &s1, i
                                const float *gamma, const float *beta, float eps, float *scale, float *shift,
                                hipStream_t s) {
     // few images, many slices: one block per (image, group) instead of B x 4 blocks
-    if ((long)B * GN_FIN_GQ < 128 && std::max(s0.slices, s1.slices) >= 16 && (C0 + C1) / groups <= 64 && ((C0 + C1) % groups) == 0) {
+    if (plan_b(B) * GN_FIN_GQ < 128 && std::max(s0.slices, s1.slices) >= 16 && (C0 + C1) / groups <= 64 && ((C0 + C1) % groups) == 0) {
         hipLaunchKernelGGL(gn_finalize_group_kernel, dim3(B, groups), dim3(256), 0, s, s0.p, C0, s0.slices, s1.p, C1, s1.slices,
                            HW, groups, gamma, beta, eps, scale, shift);
         return;
@@ -719,6 +721,7 @@ void launch_gn_apply_rows(const TDesc &in0, const TDesc &in1, int B, const float
 // the whole grid), at least two items per thread
 static int ga_pixels_per_block(int B, int HW, int C8) {
     constexpr int total = 1024;                         // blocks of the whole grid wanted
+    B = (int)plan_b(B);
     int P = (total + B - 1) / B;                        // blocks per image wanted
     const int maxP = (HW * C8 + 2 * GA_T - 1) / (2 * GA_T);
     if (P > maxP) P = maxP;
@@ -808,7 +811,7 @@ static void launch_gn_wino_impl(const TDesc &in0, const TDesc &in1, int B, const
     // blocks per image: one item per thread where the prologue only copies scale / shift; where it folds the
     // statistics, as few blocks as keep every CU busy (gn_apply_kernel's ~1024 blocks of the whole grid)
     unsigned gx = (unsigned)((items + GA_T - 1) / GA_T);
-    if (mode != 0 && !scale) gx = std::min(gx, (unsigned)std::max(1, (1024 + B - 1) / B));
+    if (mode != 0 && !scale) gx = std::min(gx, (unsigned)std::max(1L, (1024 + plan_b(B) - 1) / plan_b(B)));
     const size_t lds = ga_lds_bytes(mode, C, scale != nullptr, st.groups);
 #define SR3_GW(M)                                                                                                  \
     {                                                                                                              \
@@ -1343,7 +1346,7 @@ double launch_attention_split(const float *qkv_split, float *vt, int B, int N, i
     hipLaunchKernelGGL(attention_vt_kernel, dim3(Np / 32, (C + 127) / 128, B), dim3(256), 0, s, qkv_split, N, C, vt);
     // 64 queries x 8 waves per block where that still leaves a block for every CU (config 3: B = 64, 256 tokens);
     // else 32 queries x 4 waves
-    const bool big = (Np % 64) == 0 && (long)B * (Np / 64) >= 256 && (Np / 16 + 7) / 8 <= 2 && (C / 16 + 7) / 8 <= 4;
+    const bool big = (Np % 64) == 0 && plan_b(B) * (Np / 64) >= 256 && (Np / 16 + 7) / 8 <= 2 && (C / 16 + 7) / 8 <= 4;
     const int QB = big ? 64 : 32, NW = big ? 8 : 4;
     const size_t lds = std::max((size_t)QB * (Np + 8) * sizeof(float), big ? (size_t)QB * (C * 4 + 32) : (size_t)0);
     const int ntw = (Np / 16 + NW - 1) / NW, ntc = (C / 16 + NW - 1) / NW;

@@ -181,6 +181,9 @@ struct sr3_ctx {
     // The arithmetic of the 3x3 / activated-input convs (sr3_set_precision). Assigned by sr3_set_precision, step_down
     // and ModeScope only; everything else asks the three questions below (step_key and the feature cache record it).
     Arith mode = A_F32;
+    // Batch-invariant mode (sr3_set_batch_invariant): the planning batch every dispatch decision of this
+    // context counts in place of the call's B, 0 = off. Installed for the calling thread by PlanScope in every entry point that plans or launches.
+    int plan_batch = 0;
     bool split() const { return mode != A_F32; }        // split-f16 operands (f16x3 or f16f8)
     // "f16f8": the two correction products of eligible convs run on the fp8 matrix path (ConvParams::f8, conv_f8_supported)
     bool f8() const { return mode == A_F16F8; }
@@ -654,8 +657,22 @@ struct ShapePool {
 void drop_graphs(sr3_ctx *c);
 int prepare_f8(sr3_ctx *c);
 
+// installs the context's planning batch (batch-invariant mode; 0 = off) for the decisions of one entry point. The rule:
+// every extern "C" function that reaches conv_plan / conv_plan_offered / gn_route / gn_res1x1_gate / max_batch or a
+// launcher that reads plan_b (launch_conv, launch_wino_gemm, the GroupNorm launchers, launch_gn_res1x1,
+// launch_attention_split) opens one first. ensure_workspace refuses to size a workspace for a context in the mode
+// without one, so an entry point of the UNet that forgets it fails instead of planning by B.
+struct PlanScope {
+    const int was;
+    explicit PlanScope(const sr3_ctx *c) : was(set_plan_batch(c ? c->plan_batch : 0)) {}
+    PlanScope(const PlanScope &) = delete;
+    ~PlanScope() { set_plan_batch(was); }
+};
+
 // largest batch one call can take at H x W: every activation tensor must stay below 4 GiB (32-bit byte offsets of the
-// conv's LDS-DMA addressing) and the padded pixel count below 2^31
+// conv's LDS-DMA addressing) and the padded pixel count below 2^31. Batch-invariant mode: also what the plans of the
+// UNet's convs hold for (ConvPlan::batch_limit, either arithmetic, with and without fused statistics) and 65535, the
+// grid rows of the launches that take one image per row — past the bound a call fails, it never changes its arithmetic.
 int max_batch(const sr3_ctx *c, int H, int W) {
     const int div = 1 << (c->cfg.n_mults - 1);
     if (H <= 0 || W <= 0 || (H % div) || (W % div)) return 0;
@@ -672,10 +689,35 @@ int max_batch(const sr3_ctx *c, int H, int W) {
     }
     const uint64_t by_bytes = ((1ull << 32) - 1) / (per * sizeof(float));
     const uint64_t by_pix = ((1ull << 31) - 1) / ((uint64_t)(H + 2) * (W + 2));
-    return (int)std::min<uint64_t>(std::min(by_bytes, by_pix), 1u << 20);
+    uint64_t bound = std::min<uint64_t>(std::min(by_bytes, by_pix), 1u << 20);
+    if (c->plan_batch > 0) {
+        PlanScope plan(c);
+        bound = std::min<uint64_t>(bound, 65535);
+        auto conv = [&](const ConvRef &cr, int ih, int iw, int stride, int up2) {
+            for (int v = 0; v < 4; ++v) {
+                const ConvPlan pl = conv_plan_offered(1, ih, iw, cr.cin_pad, cr.cout, cr.ks, stride, up2, v & 1, false, (v & 2) != 0);
+                if (pl.batch_limit > 0) bound = std::min<uint64_t>(bound, (uint64_t)pl.batch_limit);
+            }
+        };
+        h = H; w = W;
+        for (const Module &m : c->mods) {
+            const int ih = h, iw = w;
+            if (m.kind == M_DOWN) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+            else if (m.kind == M_UP) { h *= 2; w *= 2; }
+            if (m.kind == M_RES) {
+                conv(m.rb.c1, h, w, 1, 0);
+                conv(m.rb.c2, h, w, 1, 0);
+                if (m.rb.attn) { conv(m.rb.qkv, h, w, 1, 0); conv(m.rb.aout, h, w, 1, 0); }
+            } else {
+                conv(m.conv, ih, iw, m.kind == M_DOWN ? 2 : 1, m.kind == M_UP ? 1 : 0);
+            }
+        }
+    }
+    return (int)bound;
 }
 
 int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
+    if (plan_batch() != c->plan_batch) return fail("internal: an entry point reached the workspace without the context's planning batch (PlanScope)");
     if (c->arena && c->wB == B && c->wH == H && c->wW == W) return 0;
     const sr3_unet_cfg &g = c->cfg;
     const int div = 1 << (g.n_mults - 1);
@@ -2176,6 +2218,57 @@ int sr3_conv_plan(int B, int H, int W, int Cin, int Cout, int ks, int stride, in
     return 0;
 }
 
+// Batch-invariant mode. Everything that bakes a plan in goes: the workspace (its statistics slices and
+// buffer sizes follow the plans), the feature cache it holds and the captured steps. No weight layout depends on the mode
+// (the F8C copies exist for every 3x3 conv; which of them a call reads is the plan's answer).
+int sr3_set_batch_invariant(sr3_ctx *c, int plan_batch) {
+    if (!c) return fail("null context");
+    if (plan_batch < 0 || plan_batch > (1 << 20)) return fail("sr3_set_batch_invariant: planning batch %d outside [0, 2^20] (0 = off)", plan_batch);
+    if (plan_batch == c->plan_batch) return 0;
+    if (c->rows_on)
+        return fail("sr3_set_batch_invariant: a row session is open (its steps were planned under the current setting; sr3_rows_end first)");
+    c->sampling = false;        // (the state of a step session goes with the workspace: sr3_sample_begin again)
+    HIP_OK(hipSetDevice(c->device));
+    if (c->arena) {
+        HIP_OK(hipStreamSynchronize(c->stream));
+        HIP_OK(hipFree(c->arena));
+        c->arena = nullptr;
+        c->arena_bytes = 0;
+        c->wB = c->wH = c->wW = 0;
+    }
+    drop_graphs(c);
+    c->fc_invalidate();
+    c->plan_batch = plan_batch;
+    return 0;
+}
+
+int sr3_get_batch_invariant(sr3_ctx *c) { return c ? c->plan_batch : fail("null context"); }
+
+int sr3_conv_plan_invariant(int plan_batch, int B, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int precision,
+                            int with_stats, int64_t *out12, char *kernel_name, int name_cap) {
+    if (plan_batch <= 0) return fail("sr3_conv_plan_invariant: the planning batch must be positive");
+    const int was = set_plan_batch(plan_batch);
+    const int r = sr3_conv_plan(B, H, W, Cin, Cout, ks, stride, up2, precision, with_stats, out12, kernel_name, name_cap);
+    set_plan_batch(was);
+    return r;
+}
+
+int64_t sr3_conv_plan_invariant_max_batch(int plan_batch, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int precision,
+                                          int with_stats) {
+    int64_t out12[12];
+    if (plan_batch <= 0) return fail("sr3_conv_plan_invariant_max_batch: the planning batch must be positive");
+    if (sr3_conv_plan_invariant(plan_batch, 1, H, W, Cin, Cout, ks, stride, up2, precision, with_stats, out12, nullptr, 0)) return -1;
+    const int was = set_plan_batch(plan_batch);
+    const ConvPlan pl = conv_plan_offered(1, H, W, Cin, Cout, ks, stride, up2, precision ? 1 : 0, out12[11] != 0, with_stats != 0);
+    set_plan_batch(was);
+    // the tensors of the conv itself stay below 4 GiB (what sr3_max_batch asks of every activation tensor of a UNet)
+    const int pad = ks / 2, Ho = ((H << up2) + 2 * pad - ks) / stride + 1, Wo = ((W << up2) + 2 * pad - ks) / stride + 1;
+    const uint64_t per = std::max((uint64_t)(H + 2) * (W + 2) * Cin, (uint64_t)(Ho + 2) * (Wo + 2) * Cout) * sizeof(float);
+    uint64_t bound = std::min<uint64_t>(((1ull << 32) - 1) / per, 65535);
+    if (pl.batch_limit > 0) bound = std::min<uint64_t>(bound, (uint64_t)pl.batch_limit);
+    return (int64_t)bound;
+}
+
 int sr3_wino_weights_host(const float *packed_host, int Cout, int CinPad, int frag, float *dst_host) {
     if (!packed_host || !dst_host || Cout <= 0 || CinPad <= 0 || (CinPad % 8))
         return fail("sr3_wino_weights_host: Cout > 0 and CinPad a positive multiple of 8");
@@ -2544,6 +2637,7 @@ static int unet_forward_once(sr3_ctx *c, const float *x_dev, const float *noise_
 
 int sr3_unet_forward(sr3_ctx *c, const float *x_dev, const float *noise_level_dev, int B, int H, int W,
                      float *out_dev) {
+    PlanScope plan_scope(c);
     if (check_ready(c)) return -1;
     if (!x_dev || !noise_level_dev || !out_dev) return fail("sr3_unet_forward: null pointer");
     if (ensure_workspace(c, B, H, W)) return -1;
@@ -2570,6 +2664,7 @@ static int check_cache_depth(sr3_ctx *c, const char *what, int depth) {
 
 int sr3_unet_forward_cached(sr3_ctx *c, const float *x_dev, const float *noise_level_dev, int B, int H, int W, int depth,
                             float *out_dev) {
+    PlanScope plan_scope(c);
     if (check_ready(c)) return -1;
     if (!x_dev || !noise_level_dev || !out_dev) return fail("sr3_unet_forward_cached: null pointer");
     if (check_cache_depth(c, "sr3_unet_forward_cached", depth)) return -1;
@@ -2640,6 +2735,7 @@ static int denoise_loss_once(sr3_ctx *c, const LossCall &k) {
 int sr3_denoise_loss(sr3_ctx *c, const float *hr_dev, const float *cond_dev, int N, int row_offset, const float *level_dev,
                      const float *s_dev, const float *noise_dev, int noise_per_source, uint64_t seed, uint64_t image_offset,
                      int B, int H, int W, int loss_type, double *per_image_dev, float *x_noisy_out, float *eps_out) {
+    PlanScope plan_scope(c);
     if (check_ready(c)) return -1;
     if (!hr_dev || !level_dev || !s_dev || !per_image_dev) return fail("sr3_denoise_loss: null pointer");
     if (loss_type != 0 && loss_type != 1) return fail("sr3_denoise_loss: loss_type %d is neither 0 (l1) nor 1 (l2)", loss_type);
@@ -2724,6 +2820,7 @@ int sr3_set_sampler_schedule(sr3_ctx *c, int S, const float *noise_level, const 
 }
 
 int sr3_max_batch(sr3_ctx *c, int H, int W) {
+    PlanScope plan_scope(c);
     if (!c) return fail("null context");
     const int b = max_batch(c, H, W);
     if (b < 0) return fail("unsupported shape H=%d W=%d: attention over more than 1024 tokens at more than 512 channels", H, W);
@@ -2809,6 +2906,7 @@ int begin_impl(sr3_ctx *c, const char *what, const float *cond_dev, int B, int H
 
 int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_noise_dev,
                      uint64_t seed, uint64_t image_offset) {
+    PlanScope plan_scope(c);
     if (check_ready(c)) return -1;
     if (c->T < 1) return fail("sr3_sample_begin: no schedule set (sr3_set_schedule)");
     if (begin_impl(c, "sr3_sample_begin", cond_dev, B, H, W, nullptr, c->T, false, init_noise_dev, seed, image_offset)) return -1;
@@ -2818,6 +2916,7 @@ int sr3_sample_begin(sr3_ctx *c, const float *cond_dev, int B, int H, int W, con
 
 int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_dev, int start_step,
                           int noised, const float *noise0_dev, uint64_t seed, uint64_t image_offset) {
+    PlanScope plan_scope(c);
     if (check_ready(c)) return -1;
     if (c->T < 1) return fail("sr3_sample_begin_from: no schedule set (sr3_set_schedule)");
     if (!init_dev) return fail("sr3_sample_begin_from: init_dev is null");
@@ -2831,6 +2930,7 @@ int sr3_sample_begin_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W
 }
 
 int sr3_sample_step(sr3_ctx *c, int t, const float *noise_slab_dev) {
+    PlanScope plan_scope(c);
     if (!c) return fail("null context");
     HIP_OK(hipSetDevice(c->device));
     if (step_checked(c, t, noise_slab_dev, nullptr)) return -1;
@@ -2849,6 +2949,7 @@ static int sample_copy_out(sr3_ctx *c, float *out_dev) {
 }
 
 int sr3_sample_end(sr3_ctx *c, float *out_dev) {
+    PlanScope plan_scope(c);
     if (!c || !out_dev) return fail("sr3_sample_end: null argument");
     if (!c->sampling) return fail("sr3_sample_end before sr3_sample_begin");
     if (sample_copy_out(c, out_dev)) return -1;
@@ -2899,6 +3000,7 @@ int rows_reserve(sr3_ctx *c, int B) {
 }
 
 int sr3_rows_begin(sr3_ctx *c, int B, int H, int W, uint64_t seed) {
+    PlanScope plan_scope(c);
     if (check_ready(c)) return -1;
     if (c->T < 1) return fail("sr3_rows_begin: no schedule set (sr3_set_schedule)");
     if (B < 1) return fail("sr3_rows_begin: bad slot count B=%d", B);
@@ -2934,6 +3036,7 @@ int sr3_rows_begin(sr3_ctx *c, int B, int H, int W, uint64_t seed) {
 }
 
 int sr3_rows_lr_consistency(sr3_ctx *c, int lh, int lw) {
+    PlanScope plan_scope(c);
     if (rows_check(c, "sr3_rows_lr_consistency", 0)) return -1;
     HIP_OK(hipSetDevice(c->device));
     if (c->rows_admitted)
@@ -3012,11 +3115,13 @@ int rows_admit_impl(sr3_ctx *c, const char *what, int row, const float *cond_dev
 
 int sr3_rows_admit(sr3_ctx *c, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
                    const float *noise0_dev, uint64_t image_id) {
+    PlanScope plan_scope(c);
     return rows_admit_impl(c, "sr3_rows_admit", row, cond_dev, init_dev, start_step, noised, noise0_dev, image_id, nullptr, 0.f);
 }
 
 int sr3_rows_admit_lr(sr3_ctx *c, int row, const float *cond_dev, const float *init_dev, int start_step, int noised,
                       const float *noise0_dev, uint64_t image_id, const float *lr_dev, float strength) {
+    PlanScope plan_scope(c);
     return rows_admit_impl(c, "sr3_rows_admit_lr", row, cond_dev, init_dev, start_step, noised, noise0_dev, image_id, lr_dev,
                            strength);
 }
@@ -3036,6 +3141,7 @@ int sr3_rows_frames(sr3_ctx *c, int row, float *frames_dev, int capacity) {
 }
 
 int sr3_rows_step(sr3_ctx *c, const float *const *noise_rows) {
+    PlanScope plan_scope(c);
     if (rows_check(c, "sr3_rows_step", 0)) return -1;
     HIP_OK(hipSetDevice(c->device));
     const int B = c->wB;
@@ -3113,6 +3219,7 @@ int sr3_rows_position(sr3_ctx *c, int row) {
 }
 
 int sr3_rows_retire(sr3_ctx *c, int row, float *out_dev) {
+    PlanScope plan_scope(c);
     if (rows_check(c, "sr3_rows_retire", row)) return -1;
     HIP_OK(hipSetDevice(c->device));
     if (!out_dev) return fail("sr3_rows_retire: out_dev is null");
@@ -3266,11 +3373,13 @@ int sample_impl(sr3_ctx *c, const char *what, const float *cond_dev, int B, int 
 
 int sr3_sample(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *noise_dev, uint64_t seed,
                uint64_t image_offset, float *out_dev, float *frames_dev) {
+    PlanScope plan_scope(c);
     return sample_impl(c, "sr3_sample", cond_dev, B, H, W, nullptr, 0, 0, noise_dev, seed, image_offset, out_dev, frames_dev);
 }
 
 int sr3_sample_from(sr3_ctx *c, const float *cond_dev, int B, int H, int W, const float *init_dev, int start_step, int noised,
                     const float *noise_dev, uint64_t seed, uint64_t image_offset, float *out_dev, float *frames_dev) {
+    PlanScope plan_scope(c);
     if (!init_dev) return fail("sr3_sample_from: init_dev is null");
     return sample_impl(c, "sr3_sample_from", cond_dev, B, H, W, init_dev, start_step, noised, noise_dev, seed, image_offset,
                        out_dev, frames_dev);
@@ -3330,6 +3439,7 @@ int sr3_set_dropout_masks(sr3_ctx *c, const uint8_t *dev, uint64_t bytes) {
 }
 
 int sr3_dropout_layers(sr3_ctx *c, int H, int W, int *n, int *chw) {
+    PlanScope plan_scope(c);
     if (!c || !n) return fail("sr3_dropout_layers: null argument");
     const int b = max_batch(c, H, W);
     if (b <= 0) return fail("sr3_dropout_layers: unsupported shape H=%d W=%d", H, W);
@@ -3339,6 +3449,7 @@ int sr3_dropout_layers(sr3_ctx *c, int H, int W, int *n, int *chw) {
 }
 
 int64_t sr3_dropout_mask_bytes(sr3_ctx *c, int B, int H, int W) {
+    PlanScope plan_scope(c);
     if (!c) return fail("null context");
     if (B < 1 || max_batch(c, H, W) <= 0) return fail("sr3_dropout_mask_bytes: unsupported shape B=%d H=%d W=%d", B, H, W);
     return (int64_t)((uint64_t)B * dropout_layers(c, H, W, nullptr));
@@ -3523,6 +3634,7 @@ int sr3_op_conv2d(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev
                   int Win, const float *weight_host, const float *bias_host, int Cout, int ks, int stride,
                   int up2, const float *gn_scale_dev, const float *gn_shift_dev, int swish,
                   const float *chan_bias_dev, const float *resid_dev, float *out_dev) {
+    PlanScope plan_scope(c);
     return op_conv2d_impl("sr3_op_conv2d", c, in0_dev, C0, in1_dev, C1, B, Hin, Win, weight_host, bias_host, Cout, ks, stride, up2,
                           gn_scale_dev, gn_shift_dev, swish, chan_bias_dev, resid_dev, out_dev, nullptr, 0, nullptr);
 }
@@ -3532,6 +3644,7 @@ int sr3_op_conv2d_stats(sr3_ctx *c, const float *in0_dev, int C0, const float *i
                         int up2, const float *gn_scale_dev, const float *gn_shift_dev, int swish,
                         const float *chan_bias_dev, const float *resid_dev, float *out_dev, double *stats_dev,
                         uint64_t stats_capacity_doubles, int *slices_out) {
+    PlanScope plan_scope(c);
     if (!stats_dev || !slices_out) return fail("sr3_op_conv2d_stats: null argument");
     return op_conv2d_impl("sr3_op_conv2d_stats", c, in0_dev, C0, in1_dev, C1, B, Hin, Win, weight_host, bias_host, Cout, ks, stride,
                           up2, gn_scale_dev, gn_shift_dev, swish, chan_bias_dev, resid_dev, out_dev, stats_dev,
@@ -3544,6 +3657,7 @@ int sr3_op_conv2d_fused(sr3_ctx *c, const float *in0_dev, int C0, const float *i
                         const float *in2_dev, int C2a, const float *in2b_dev, int C2b, const float *w2_host,
                         const float *b2_host, int flags, float *out_dev, float *out_split_dev, double *stats_dev,
                         uint64_t stats_capacity_doubles, int *slices_out) {
+    PlanScope plan_scope(c);
     if (!stats_dev || !slices_out) return fail("sr3_op_conv2d_fused: null argument");
     FusedArgs fa;
     fa.in2_dev = in2_dev; fa.C2a = C2a; fa.in2b_dev = in2b_dev; fa.C2b = C2b;
@@ -3557,6 +3671,7 @@ int sr3_op_conv2d_fused(sr3_ctx *c, const float *in0_dev, int C0, const float *i
 int sr3_op_conv_in(sr3_ctx *c, const float *state_nchw_dev, int B, int H, int W, int Cin, const float *weight_host,
                    const float *bias_host, int Cout, float *out_dev, float *twin_dev, double *stats_dev,
                    uint64_t stats_capacity_doubles, int *slices_out, void *packed_host) {
+    PlanScope plan_scope(c);
     const char *what = "sr3_op_conv_in";
     if (!c || !state_nchw_dev || !weight_host) return fail("%s: null argument", what);
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return fail("%s: bad shape", what);
@@ -3605,6 +3720,7 @@ int sr3_op_conv_in(sr3_ctx *c, const float *state_nchw_dev, int B, int H, int W,
 int sr3_op_final_conv(sr3_ctx *c, const float *in_dev, int B, int H, int W, int C, const float *gn_scale_dev,
                       const float *gn_shift_dev, const float *weight_host, const float *bias_host, int Cout,
                       float *out_dev, int *form_out) {
+    PlanScope plan_scope(c);
     const char *what = "sr3_op_final_conv";
     if (!c || !in_dev || !gn_scale_dev || !gn_shift_dev || !weight_host || !bias_host || !out_dev) return fail("%s: null argument", what);
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0) return fail("%s: bad shape", what);
@@ -3660,6 +3776,7 @@ int64_t sr3_read_packed_state(sr3_ctx *c, float *state_host, void *packed_host, 
 // conv in the engine (1 affine, 2 affine + Swish) and reports it in *apply_ms.
 int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout, int ks, int stride, int up2,
                    int mode, int with_resid, int with_chan_bias, int iters, float *avg_ms, float *apply_ms) {
+    PlanScope plan_scope(c);
     if (!c || !avg_ms) return fail("null argument");
     if ((C0 % 32) || (C1 % 32) || C0 <= 0) return fail("sr3_bench_conv: channels must be multiples of 32");
     HIP_OK(hipSetDevice(c->device));
@@ -3706,6 +3823,7 @@ int sr3_bench_conv(sr3_ctx *c, int B, int Hin, int Win, int C0, int C1, int Cout
 // statistics as two conv epilogues would have left them (x and skip separately), `iters` back-to-back repetitions each.
 int sr3_bench_gn_res1x1(sr3_ctx *c, int B, int H, int W, int C0, int C1, int Cout, int groups, int iters, float *pair_ms, float *one_ms,
                         int *route_out) {
+    PlanScope plan_scope(c);
     const char *what = "sr3_bench_gn_res1x1";
     if (!c || !pair_ms || !one_ms || iters < 1) return fail("%s: bad argument", what);
     const int C = C0 + C1;
@@ -3758,6 +3876,7 @@ int sr3_bench_gn_res1x1(sr3_ctx *c, int B, int H, int W, int C0, int C1, int Cou
 int sr3_op_groupnorm_affine(sr3_ctx *c, const float *in0_dev, int C0, const float *in1_dev, int C1, int B,
                             int H, int W, int groups, const float *gamma_host, const float *beta_host,
                             float *scale_dev, float *shift_dev) {
+    PlanScope plan_scope(c);
     if (!c || !in0_dev || !gamma_host || !beta_host || !scale_dev || !shift_dev) return fail("sr3_op_groupnorm_affine: null argument");
     if (!in1_dev) C1 = 0;
     const int C = C0 + C1;
@@ -3777,6 +3896,7 @@ int sr3_op_groupnorm_apply(sr3_ctx *c, const float *in0_dev, int C0, const float
                            int groups, const float *gamma_host, const float *beta_host, const double *stats0_dev, int slices0,
                            const double *stats1_dev, int slices1, int mode, int format, int in_split, int route,
                            float *out_dev, float *raw_out_dev, int *route_out, int *range_out) {
+    PlanScope plan_scope(c);
     if (!c || !in0_dev || !gamma_host || !beta_host || !out_dev) return fail("sr3_op_groupnorm_apply: null argument");
     if (!in1_dev) C1 = 0;
     const int C = C0 + C1;
@@ -3840,6 +3960,7 @@ int sr3_gn_res1x1_gate(int B, int H, int W, int C0, int C1, int Cout, int precis
 int sr3_op_gn_res1x1(sr3_ctx *c, const float *x_dev, int C0, const float *skip_dev, int C1, int B, int H, int W, int groups,
                      const float *gamma_host, const float *beta_host, const float *w2_host, int Cout, float sentinel,
                      float *act_dev, float *res_dev, float *res_pair_dev) {
+    PlanScope plan_scope(c);
     const char *what = "sr3_op_gn_res1x1";
     if (!c || !x_dev || !gamma_host || !beta_host || !w2_host || !act_dev || !res_dev) return fail("%s: null argument", what);
     if (!skip_dev) C1 = 0;
@@ -3917,12 +4038,14 @@ static int op_attention_impl(const char *what, sr3_ctx *c, const float *qkv_dev,
 }
 
 int sr3_op_attention(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev) {
+    PlanScope plan_scope(c);
     if (!c || !qkv_dev || !out_dev) return fail("sr3_op_attention: null argument");
     return op_attention_impl("sr3_op_attention", c, qkv_dev, B, N, C, out_dev, nullptr, false);
 }
 
 int sr3_op_attention_twin(sr3_ctx *c, const float *qkv_dev, int B, int N, int C, float *out_dev, float *out_split_dev,
                           int fp32_off) {
+    PlanScope plan_scope(c);
     if (!c || !qkv_dev || !out_split_dev || (!out_dev && !fp32_off)) return fail("sr3_op_attention_twin: null argument");
     return op_attention_impl("sr3_op_attention_twin", c, qkv_dev, B, N, C, fp32_off ? nullptr : out_dev, out_split_dev, true);
 }

@@ -39,6 +39,15 @@ namespace sr3 {
 //                           16384 keys (per-shape timing; same bits); read where kernels_threshold.hip plans a selection
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
+// ---- batch-invariant mode (sr3_set_batch_invariant) ---------------------------------------------------
+// The planning batch P of the calling thread, 0 = off (conv_plan.hip). While it is set, every host decision that picks
+// an arithmetic from the amount of work (a tile, a split-K count, a Winograd form, the statistics slices, the attention
+// block) counts P images instead of the call's B, so the bytes of one image do not depend on its batch. The C-ABI entry
+// points set it from their context for the time of the call (sr3_api.hip: PlanScope); set_plan_batch returns the old value.
+int plan_batch();
+int set_plan_batch(int P);
+inline long plan_b(long B) { const int P = plan_batch(); return P > 0 ? (long)P : B; }
+
 // Activation tensor: NHWC fp32 with an optional 1-pixel zero border ("pad") stored around every
 // image, so a 3x3 window never needs a bounds check: pixel (n, y, x) lives at
 //   p + (((n * (H + 2*pad)) + y + pad) * (W + 2*pad) + x + pad) * C.
@@ -227,7 +236,10 @@ struct ConvPlan {
     // many tile rows per block, reading ConvParams::w_up_wino instead of w. Not part of the exported plan: kernel, phases,
     // split and stats_slices stay the direct plan's, and the statistics come in the same slices.
     int up2_wino = 0;
-    const char *error = nullptr;       // a request no kernel honours (ConvParams::f8 on a shape outside the F8C kernel)
+    // Batch-invariant mode only: the largest batch this plan holds for (a limit on the real batch — arrival counters,
+    // 32-bit offsets inside one Winograd plane — never changes the form there; a launch past it fails), 0 = none.
+    long batch_limit = 0;
+    const char *error = nullptr;      // a request no kernel honours (ConvParams::f8 on a shape outside the F8C kernel)
 };
 // reads p as launch_conv does: a null part / tile_cnt / w_wino / w_wino_f / wino_ws / stats means "not offered", and the
 // plan degrades (no split-K, two-kernel split, direct kernel); p.up2: p describes the conv at the OUTPUT resolution

@@ -293,6 +293,13 @@ class GaussianDiffusion(nn.Module):
             eng.set_feature_cache(*(want if want is not None else (None, 1)))
             eng._fc_set = want
 
+    def set_batch_invariant(self, on: bool = True, plan_batch: int = 64) -> None:
+        """Batch-invariant mode (UNet.set_batch_invariant): an image's bytes no longer depend on the batch
+        it ran in. Honoured by sample_batch, super_resolution_batch, refine, p_losses, validate_batch, rolling() — a
+        session inherits the setting, changing it inside one is refused — and dist.sharded_super_resolution: the same
+        request gives the same bytes served alone, in a chunk, in a slot or on another rank. Off by default."""
+        self.denoise_fn.set_batch_invariant(on, plan_batch)
+
     def set_dropout_sampling(self, on: bool, seed: Optional[int] = None) -> None:
         """Opt in to sampling the UNet's Dropout as the reference does under .train() (unet.py:81-91; model 3 samples
         with the SR model in train mode, model/sr3d/model.py:234-249). While on, in train() mode and with cfg.dropout >
@@ -396,7 +403,10 @@ class GaussianDiffusion(nn.Module):
         Batches above the library's per-call limit (4 GiB per activation tensor: ~250 images at 128x128) — the
         reference's validation loop is 15 samples x N images (lib/trainer_temp.py:441-446), BASELINE configs[3] is 512
         images — run as equal chunks, one sr3_sample call each; Philox streams stay keyed by the GLOBAL image index
-        (image_offset + row), so the result does not depend on the chunking. max_chunk lowers the limit (tests).
+        (image_offset + row), so the noise does not depend on the chunking. max_chunk lowers the limit (tests). The
+        arithmetic does, by default: the library plans every launch from the batch of the call, so the chunk size moves
+        an image by fp32 round-off in f32 / f16x3 and by up to about 1e-4 in f16f8, where it also decides which convs take
+        the fp8 products. Under set_batch_invariant() the result is bit-equal whatever the chunking, in every arithmetic.
 
         Warm start: init [B,C,H,W] is an explicit start image and overrides set_start; it is chunked,
         and its last chunk padded, like x_in. start: a strength in (0, 1] (float) or s0 itself (int); None takes
@@ -506,9 +516,12 @@ class GaussianDiffusion(nn.Module):
         step runs at batch `slots`, so a request is byte for byte its row of a uniform call of `slots` images —
         super_resolution_batch(x, seed=seed, image_offset=image_id)[0] with x of `slots` rows, or refine(...) with a
         strength — whatever shared the batch and wherever it sat. Against a call at ANOTHER batch size (the B = 1 call, say)
-        it differs as any two batch sizes differ: the conv dispatch depends on the batch (fp32 round-off in f32 / f16x3,
-        1e-5 in f16f8, whose fp8 path runs only from 32 or 64 images on). slots None: min(64, the per-call limit at `shape` = (H, W), default
-        image_size). LR consistency is per request here: submit(..., lr=image) holds that request to its LR image (fp32
+        it differs, by default, as any two batch sizes differ: the conv dispatch depends on the batch (fp32 round-off in
+        f32 / f16x3, 1e-5 in f16f8, whose fp8 path runs only from 32 or 64 images on). Under
+        set_batch_invariant() a request is its B = 1 call byte for byte; a session inherits that setting and holds it
+        (changing it inside one is refused), and `slots` must lie within the mode's maximum batch (planned for one image,
+        plan_batch=1, that is 16 images at 128x128 with the yml UNet: a 64-slot session is refused there). slots None:
+        min(64, the per-call limit at `shape` = (H, W), default image_size). LR consistency is per request here: submit(..., lr=image) holds that request to its LR image (fp32
         [C,l,l] or uint8 [l,l,3], lr_to_tensor) as set_lr_consistency holds a batch, a request without one is not held; the
         session is armed for the LR size when it begins — by lr_size=(lh, lw), or by the first request carrying an lr.
         submit(..., continous=True) makes poll return what super_resolution(x, continous=True) returns for one image:

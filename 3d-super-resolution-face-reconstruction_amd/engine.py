@@ -72,17 +72,34 @@ SPLIT_KINDS = ("none", "reduce", "inplace", "inplace_halo")
 
 
 def conv_plan(B: int, H: int, W: int, Cin: int, Cout: int, ks: int = 3, stride: int = 1, up2: int = 0,
-              precision: str = "f32", stats: bool = False) -> dict:
+              precision: str = "f32", stats: bool = False, plan_batch: Optional[int] = None) -> dict:
     """The library's dispatch plan for one conv shape (H x W input pixels, Cin a multiple of 32) with every scratch buffer
-    offered; stats: the conv also produces fused GroupNorm statistics (the UNet's convs do, op_conv2d does not). Host
-    only: needs no GPU and no context."""
+    offered; stats: the conv also produces fused GroupNorm statistics (the UNet's convs do, op_conv2d does not).
+    plan_batch (a positive int): the plan of an engine in the batch-invariant mode with that planning batch
+    (sr3_conv_plan_invariant) — the same for every B but for the two buffer sizes. Host only: needs no GPU
+    and no context."""
     v = (C.c_int64 * 12)()
     name = C.create_string_buffer(32)
-    _lib.check(_lib.load().sr3_conv_plan(B, H, W, Cin, Cout, ks, stride, up2, PRECISIONS[precision], int(bool(stats)),
-                                         v, name, len(name)))
+    if plan_batch:
+        _lib.check(_lib.load().sr3_conv_plan_invariant(int(plan_batch), B, H, W, Cin, Cout, ks, stride, up2, PRECISIONS[precision],
+                                                       int(bool(stats)), v, name, len(name)))
+    else:
+        _lib.check(_lib.load().sr3_conv_plan(B, H, W, Cin, Cout, ks, stride, up2, PRECISIONS[precision], int(bool(stats)),
+                                             v, name, len(name)))
     return {"kernel": name.value.decode(), "kernel_id": v[0], "tile": [v[1], v[2]], "split": SPLIT_KINDS[v[3]], "splits": v[4],
             "phases": v[5], "part_floats": v[6], "needs_counters": bool(v[7]), "stats_slices": v[8],
             "wino_ws_floats": v[9], "needs_wino_frag": bool(v[10]), "f8": bool(v[11])}
+
+
+def conv_plan_invariant_max_batch(plan_batch: int, H: int, W: int, Cin: int, Cout: int, ks: int = 3, stride: int = 1,
+                                  up2: int = 0, precision: str = "f32", stats: bool = False) -> int:
+    """The largest batch the batch-invariant plan of this conv holds for under `plan_batch` (the arrival counters of an
+    in-place split-K, 32-bit offsets, tensors below 4 GiB; at most 65535): Engine.max_batch is the smallest over a UNet's
+    convs while the mode is on. Host only."""
+    n = int(_lib.load().sr3_conv_plan_invariant_max_batch(int(plan_batch), H, W, Cin, Cout, ks, stride, up2, PRECISIONS[precision],
+                                                          int(bool(stats))))
+    _lib.check(min(n, 0))
+    return n
 
 
 def gn_res1x1_gate(B: int, H: int, W: int, C0: int, C1: int, Cout: int, precision: str = "f32", has_res: bool = True,
@@ -90,7 +107,8 @@ def gn_res1x1_gate(B: int, H: int, W: int, C0: int, C1: int, Cout: int, precisio
     """The library's decision for one ResnetBlock at H x W pixels: does block1's GroupNorm + Swish pass over x (C0) ‖ skip
     (C1) also multiply the block's 1x1 res_conv (sr3_gn_res1x1_gate)? valid: the rules hold; tuned: the level and block
     count are adopted; takes: what this process launches (the two environment switches included). Host only: needs no GPU
-    and no context."""
+    and no context — and therefore the DEFAULT plan's answer: an engine in the batch-invariant mode counts its planning
+    batch in place of B."""
     flags = (1 if has_res else 0) | (2 if direct else 0) | (4 if raw_wanted else 0) | (8 if in_split else 0)
     r = int(_lib.load().sr3_gn_res1x1_gate(B, H, W, C0, C1, Cout, PRECISIONS[precision], flags, mode))
     _lib.check(min(r, 0))
@@ -141,12 +159,36 @@ class Engine:
     PRECISIONS = PRECISIONS
 
     def conv_plan(self, B: int, H: int, W: int, Cin: int, Cout: int, ks: int = 3, stride: int = 1, up2: int = 0,
-                  precision: Optional[str] = None, stats: bool = False) -> dict:
-        """conv_plan() in this engine's precision (or the one named)."""
-        return conv_plan(B, H, W, Cin, Cout, ks, stride, up2, precision or getattr(self, "precision", "f32"), stats)
+                  precision: Optional[str] = None, stats: bool = False, plan_batch: Optional[int] = None) -> dict:
+        """conv_plan() in this engine's precision (or the one named) and under its batch-invariant setting (or the planning
+        batch named)."""
+        return conv_plan(B, H, W, Cin, Cout, ks, stride, up2, precision or getattr(self, "precision", "f32"), stats,
+                         self.batch_invariant() if plan_batch is None else plan_batch)
+
+    def set_batch_invariant(self, plan_batch: int = 64):
+        """Batch-invariant mode. plan_batch > 0: every dispatch decision counts `plan_batch` images in
+        place of the call's batch, so the bytes of one image depend on its own inputs and on plan_batch alone — not on the
+        batch size, the row, the other rows, the chunking or the rank split. 0 / False: off (the default); True: 64, the
+        facade's default planning batch. Changing the
+        value frees the workspace and the captured steps; refused while a row session is open. max_batch()
+        reports the mode's maximum batch while it is on."""
+        if isinstance(plan_batch, bool) or plan_batch is None:
+            plan_batch = 64 if plan_batch else 0
+        _lib.check(self.lib.sr3_set_batch_invariant(self.ctx, int(plan_batch)))
+
+    def batch_invariant(self) -> int:
+        """The planning batch of the batch-invariant mode, 0 = off."""
+        n = int(self.lib.sr3_get_batch_invariant(self.ctx))
+        _lib.check(min(n, 0))
+        return n
 
     def conv_f8_supported(self, B: int, H: int, W: int, Cout: int, Cin: int) -> bool:
-        """Does the 'f16f8' mode run a 3x3 / stride-1 conv of this shape with fp8 correction products?"""
+        """Does the 'f16f8' mode run a 3x3 / stride-1 conv of this shape with fp8 correction products on THIS engine —
+        under its planning batch while the batch-invariant mode is on (sr3_conv_f8_supported itself describes the
+        default plan)?"""
+        P = self.batch_invariant()
+        if P:
+            return bool(conv_plan(B, H, W, Cin, Cout, 3, 1, 0, "f16f8", False, P)["f8"])
         return bool(self.lib.sr3_conv_f8_supported(B, H, W, Cout, Cin))
 
     def set_precision(self, name: str):

@@ -99,6 +99,8 @@ class UNet(nn.Module):
         self.dropout_sampling = False
         self.dropout_seed: Optional[int] = None
         self._dropout_masks: Optional[torch.Tensor] = None
+        # batch-invariant mode: the planning batch, 0 = off (set_batch_invariant)
+        self.batch_invariant = 0
 
     # ---- engine management -------------------------------------------------------------------
     def _device_index(self) -> int:
@@ -126,6 +128,8 @@ class UNet(nn.Module):
         cur = torch.cuda.current_stream(idx)
         self._own_stream = cur.cuda_stream == 0
         self._engine.set_stream(cur.cuda_stream)
+        if self._engine.batch_invariant() != self.batch_invariant:
+            self._engine.set_batch_invariant(self.batch_invariant)
         if getattr(self._engine, "_strict", None) != self.strict_range:
             self._engine.set_range_policy(self.strict_range)
             self._engine._strict = self.strict_range
@@ -144,6 +148,24 @@ class UNet(nn.Module):
         (including `.cpu()` and collectives enqueued from torch's current stream) without a host synchronisation."""
         if self._engine is not None and getattr(self, "_own_stream", True):
             self._engine.stream_wait_for_engine(0)
+
+    def set_batch_invariant(self, on: bool = True, plan_batch: int = 64) -> None:
+        """Batch-invariant mode, off by default. On: every launch of this model is planned for
+        `plan_batch` images whatever the batch of the call, so the bytes the library writes for one image — a forward, a
+        sampling call, a rolling request, a loss term — depend only on that image's own inputs (conditioning row, state or
+        noise, noise level, image id, seed), the weights, the arithmetic, the sampler options and plan_batch: not on the
+        batch size, the row, the other rows, the chunking (max_chunk), the rank split or the slots of a rolling session.
+        Two values of plan_batch may give different bytes. One exception: the range policy acts on whole calls, so a call
+        that steps its arithmetic down changes every row of that call (the warning says so, as without the mode).
+        The mode has a maximum batch of its own (engine().max_batch), which the chunking honours. It costs speed away from
+        plan_batch (README, profiles/README.md). Changing the setting frees the engine's workspace and captured steps; it is
+        refused while a rolling session is open."""
+        want = int(plan_batch) if on else 0
+        if on and want < 1:
+            raise ValueError(f"plan_batch must be a positive integer, got {plan_batch!r}")
+        if self._engine is not None:
+            self._engine.set_batch_invariant(want)      # (refused while a rolling session is open)
+        self.batch_invariant = want
 
     def set_weight_sync(self, route: str) -> None:
         """How changed parameters reach the library. "host" (default): each one through a CPU copy and the host packers

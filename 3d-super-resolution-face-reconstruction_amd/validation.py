@@ -147,7 +147,9 @@ def validate_batch(netG, sr: "torch.Tensor", hr: "torch.Tensor", samples: int = 
 
     sr, hr: [N,3,r,r] in [-1,1] (the dataset's 'SR' and 'HR' entries, datasets/LRHR_dataset.py:93-99).
     N * samples may exceed what one library call takes (~250 images at 128x128): `sample_batch` runs equal chunks
-    with the Philox streams keyed by the global row, so the scores do not depend on the chunking.
+    with the Philox streams keyed by the global row, so the noise does not depend on the chunking. By default the images
+    do, within fp32 round-off in f32 / f16x3 and up to about 1e-4 in f16f8 (the chunk size decides which convs take the
+    fp8 products); under netG.set_batch_invariant() images and scores are bit-equal whatever the chunking.
     The chains use netG's sampler setting (GaussianDiffusion.set_sampler: the reference's DDPM loop by default).
     Under a warm start (GaussianDiffusion.set_start) every chain starts from its own row of `sr`, noised with its own
     Philox stream, and runs netG.num_steps_run steps.

@@ -92,7 +92,8 @@ int sr3_stream_wait_for_ctx(sr3_ctx *ctx, void *other_stream);
  * policy then repeats the work in mode 1 first, in f32 if that overflows too. No reference counterpart (unet.py
  * computes in fp32). */
 int sr3_set_precision(sr3_ctx *ctx, int prec);
-/* 1 when mode 2 runs a 3x3 / stride-1 conv of this shape with fp8 correction products, else 0 (tests, tools) */
+/* 1 when mode 2 runs a 3x3 / stride-1 conv of this shape with fp8 correction products, else 0 (tests, tools). The DEFAULT
+ * plan's answer: for a context in the batch-invariant mode read field 11 of sr3_conv_plan_invariant. */
 int sr3_conv_f8_supported(int B, int H, int W, int Cout, int Cin);
 /* The dispatch plan of one conv shape (H x W input pixels, Cin a multiple of 32) as the engine runs it in `precision`
  * (sr3_set_precision values), with every scratch buffer offered; with_stats: the conv also produces the fused GroupNorm
@@ -105,6 +106,30 @@ int sr3_conv_f8_supported(int B, int H, int W, int Cout, int Cin);
  * "generic_128x32" | "generic_128x64" | "generic_64x64" | "generic_128x128". (tests, tools) */
 int sr3_conv_plan(int B, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int precision, int with_stats,
                   int64_t *out12, char *kernel_name, int name_cap);
+
+/* ---- batch-invariant mode ------------------------------------------------
+ * By default the library picks every launch's form (conv tile, split-K, Winograd form, fp8 layer set, statistics slices,
+ * attention block) from the work of the call at hand, so the bytes of one image depend on the batch it ran in. With a
+ * planning batch P > 0 every such decision counts P images instead of the call's B and every shape rule is asked of one
+ * image: the bytes sr3_unet_forward(_cached), sr3_sample(_from), sr3_sample_begin/step/end, sr3_rows_* and
+ * sr3_denoise_loss write for an image then depend on that image's own inputs (conditioning row, state or injected
+ * noise, noise level, image id, seed), the weights, the precision, the sampler options and P — not on B, the row, the
+ * other rows, the chunking or which batch sizes ran before. Two values of P may give different bytes. Exception: the
+ * range policy acts on whole calls, so a call that steps an arithmetic down (SR3_OK_F32_FALLBACK) changes every row.
+ * Limits on the real batch (arrival counters of the in-place split-K, 32-bit offsets) become the mode's maximum batch:
+ * sr3_max_batch reports it and a larger call fails; the arithmetic never changes at the upper end.
+ * plan_batch 0 = off (the default: every launch is today's). Changing the value frees the workspace and drops the
+ * captured steps (the state sr3_sample_begin loaded goes with them); refused while a row session (sr3_rows_begin) is
+ * open. No reference counterpart. */
+int sr3_set_batch_invariant(sr3_ctx *ctx, int plan_batch);
+int sr3_get_batch_invariant(sr3_ctx *ctx);
+/* sr3_conv_plan as a context in the mode plans the conv at batch B (host only, no GPU call). Every field but the two
+ * buffer sizes (which scale with B) is the same for every B up to sr3_conv_plan_invariant_max_batch: the largest batch
+ * this conv's plan and tensors hold for under plan_batch (at most 65535); past it sr3_conv_plan_invariant fails. */
+int sr3_conv_plan_invariant(int plan_batch, int B, int H, int W, int Cin, int Cout, int ks, int stride, int up2, int precision,
+                            int with_stats, int64_t *out12, char *kernel_name, int name_cap);
+int64_t sr3_conv_plan_invariant_max_batch(int plan_batch, int H, int W, int Cin, int Cout, int ks, int stride, int up2,
+                                          int precision, int with_stats);
 
 /* ---- weights: reference state_dict names and layouts ------------------------------------- */
 
@@ -343,7 +368,8 @@ int sr3_gn_res1x1_launches(sr3_ctx *ctx);
  * sr3_conv_plan with statistics. flags: 1 = the block has a res_conv, 2 = its operands are x / skip themselves, 4 = a raw
  * copy of the concatenation is wanted, 8 = an input is stored in the split format; mode as sr3_op_groupnorm_apply.
  * Returns bit 0 = valid, bit 1 = tuned (the level and block count are adopted), bit 2 = taken in this process (valid,
- * not SR3_NO_GN_RES1X1=1, and tuned or SR3_GN_RES1X1_FORCE=1); < 0: bad argument. */
+ * not SR3_NO_GN_RES1X1=1, and tuned or SR3_GN_RES1X1_FORCE=1); < 0: bad argument. Like sr3_conv_plan it describes the
+ * DEFAULT plan: a context in the batch-invariant mode counts its planning batch in place of B. */
 int sr3_gn_res1x1_gate(int B, int H, int W, int C0, int C1, int Cout, int precision, int flags, int mode);
 /* Sampler steps this context captured into a graph since sr3_create (successful instantiations; 0 under SR3_NO_GRAPH=1
  * and while profiling): tells a test that a step was replayed from its graph, or captured anew because a value the graph

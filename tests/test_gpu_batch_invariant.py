@@ -1,0 +1,486 @@
+"""Batch-invariant mode on the GPU (sr3_set_batch_invariant): with a planning batch P the bytes the
+library writes for one image depend on that image's own inputs, the weights, the arithmetic, the sampler options and P —
+not on the batch size, the row, the other rows, the chunking, the rank split or the slots of a rolling session.
+
+Every comparison is np.array_equal on the raw values, P = 64 unless a test says otherwise, and every batch size runs on an
+engine of its own (as tests/test_gpu_rows.py does: DESIGN.md §8 records an unexplained difference of thresholded calls
+after a larger workspace on the same engine, which is not what these tests are about).
+
+Without the mode the same comparisons fail: the default plans of every configuration here change with B
+(tests/test_batch_invariant_host.py counts them), so a setter that is accepted but ignored does not pass.
+"""
+import functools
+import os
+import socket
+
+import numpy as np
+import pytest
+
+from conftest import pkg
+
+import test_conv_plan_host as plans
+import test_gpu_config_sweep as sweep
+
+pytestmark = pytest.mark.gpu
+synth = pkg("synth")
+schedule = pkg("schedule")
+samplers = pkg("samplers")
+engine_mod = pkg("engine")
+UNetConfig = pkg("graph").UNetConfig
+F32 = np.float32
+
+P = 64
+PRECISIONS = ["f32", "f16x3", "f16f8"]
+SCHED = {"schedule": "linear", "n_timestep": 6, "linear_start": 1e-4, "linear_end": 2e-2}
+KINDS = [("ddpm", None), ("ddim", 4), ("dpmpp_2m", 4)]
+KIND_IDS = ["ddpm_T6", "ddim_S4", "dpmpp_2m_S4"]
+SEED = 4242
+
+
+def _cfg(name):
+    if name == "tiny":
+        return synth.tiny_unet_config()
+    if name == "F8":
+        # two levels of 128 / 256 channels, no attention: at 32x32 the default plan of a single image runs every 3x3 conv
+        # on 64x64 tiles (no fp8 operands), the plan for 64 images puts the 32x32 level on the 128x128 x-halo tile
+        return UNetConfig(in_channel=6, out_channel=3, inner_channel=128, norm_groups=32, channel_mults=(1, 2), attn_res=(),
+                          res_blocks=1, dropout=0.0, image_size=32)
+    return sweep._cfg(name)
+
+
+@functools.lru_cache(maxsize=None)
+def _weights(name):
+    return synth.synth_state_dict(_cfg(name), 600 + sum(map(ord, name)))
+
+
+def _new_engine(name, plan_batch=P):
+    e = engine_mod.Engine(_cfg(name), 0)
+    e.load_state_dict(_weights(name))
+    assert e.weights_missing() == 0
+    e.set_batch_invariant(plan_batch)
+    assert e.batch_invariant() == plan_batch
+    return e
+
+
+@functools.lru_cache(maxsize=None)
+def _engine(name, B):
+    """one engine per (configuration, batch size), kept for the module: the tests set its arithmetic and planning batch"""
+    return _new_engine(name)
+
+
+def _arm(e, prec, plan_batch=P):
+    e.set_batch_invariant(plan_batch)
+    e.set_precision(prec)
+    return e
+
+
+@functools.lru_cache(maxsize=None)
+def _input(name, n, size):
+    """n images, every one with its own input and noise level"""
+    x, nl = synth.synth_unet_input(_cfg(name), n, size, size, SEED + n)
+    return x, nl.reshape(-1)
+
+
+def _same(got, want, what):
+    assert got.shape == want.shape and got.dtype == want.dtype
+    assert np.array_equal(got, want), f"{what}: max abs difference {np.abs(got.astype(np.float64) - want).max():.3e}"
+
+
+def _forward_rows_alone(name, size, prec, rows, n, plan_batch=P):
+    x, nl = _input(name, n, size)
+    e1 = _arm(_engine(name, 1), prec, plan_batch)
+    return {r: e1.unet_forward_np(x[r:r + 1], nl[r:r + 1])[0] for r in rows}
+
+
+def _form_counters(e):
+    """launches of the forms a plan does not export: the tile-row and one-kernel forms of the three-pass Winograd plan,
+    the sub-pixel Winograd Upsample conv, the GroupNorm passes that write U and those that multiply the 1x1 res_conv"""
+    return np.array([e.wino_fused_rows_launches(), e.wino_gemm_out_launches(), e.up2_wino_launches(), e.gn_wino_passes(),
+                     e.gn_res1x1_launches()])
+
+
+def _check_forward(name, size, prec, B, rows=None, plan_batch=P, n=None):
+    n = n or B
+    x, nl = _input(name, n, size)
+    rows = list(range(B)) if rows is None else rows
+    e1 = _engine(name, 1)
+    c1 = _form_counters(e1)
+    alone = _forward_rows_alone(name, size, prec, tuple(rows), n, plan_batch)
+    c1 = (_form_counters(e1) - c1) // len(rows)
+    eb = _arm(_engine(name, B), prec, plan_batch)
+    cb = _form_counters(eb)
+    got = eb.unet_forward_np(x[:B], nl[:B])
+    assert np.array_equal(_form_counters(eb) - cb, c1), "the B = 1 forward and the batched one launched other forms"
+    assert eb.fallback_calls() == 0 and _engine(name, 1).fallback_calls() == 0     # (the calls kept their arithmetic)
+    for r in rows:
+        _same(got[r], alone[r], f"{name} {size}x{size} {prec} P={plan_batch}: row {r} of B={B} against its B=1 forward")
+
+
+# ---- forward ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("prec", PRECISIONS)
+def test_forward_config_d(prec):
+    """128 / 256 / 512 channels at 32x32, 16x16 and 8x8 pixels, unconditional: B = 5 and B = 2 against five B = 1 forwards"""
+    _check_forward("D", 32, prec, 5)
+    _check_forward("D", 32, prec, 2, n=5)
+
+
+def test_forward_config_d_planned_for_one_image():
+    _check_forward("D", 32, "f32", 5, plan_batch=1)
+    _check_forward("D", 32, "f16f8", 5, plan_batch=1)
+
+
+def test_the_default_mode_does_depend_on_the_batch():
+    """teeth of everything above: the same comparison with the mode off fails in at least one row"""
+    x, nl = _input("D", 5, 32)
+    e1, e5 = _new_engine("D", 0), _new_engine("D", 0)
+    try:
+        for e in (e1, e5):
+            e.set_precision("f16f8")
+        got = e5.unet_forward_np(x, nl)
+        alone = np.concatenate([e1.unet_forward_np(x[r:r + 1], nl[r:r + 1]) for r in range(5)])
+        assert not np.array_equal(got, alone)
+    finally:
+        e1.close(); e5.close()
+
+
+@pytest.mark.parametrize("prec", ["f32", "f16x3"])
+@pytest.mark.parametrize("name,size,B", [("B", 32, 8), ("A", 48, 3)])
+def test_forward_configs_a_and_b(name, size, B, prec):
+    """B: the default statistics slices move at B = 8. A: a size that is no power of two, groups that straddle the concat,
+    attention at 576 and 144 tokens"""
+    _check_forward(name, size, prec, B)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f16x3"])
+def test_forward_config_c_rows_of_16(prec):
+    """five levels at 64x64; the default tile changes at B = 16"""
+    _check_forward("C", 64, prec, 16, rows=[0, 7, 15])
+
+
+# ---- a slot of 64 against the single image: the gates whose default threshold lies at 32 - 64 images -----------------------
+@pytest.mark.parametrize("prec", PRECISIONS)
+def test_forward_tiny_rows_of_64(prec):
+    _check_forward("tiny", 16, prec, 64, rows=[0, 29, 63])
+
+
+@pytest.mark.parametrize("name,prec", [("F8", "f16f8"), ("F8", "f32"), ("B", "f16x3"), ("B", "f32")])
+def test_forward_rows_of_64(name, prec):
+    """F8: the fp8 layer set and the Winograd forms that the default takes only from 32 - 64 images on. B: attention over 256
+    tokens (the split-f16 core's 64-query form from 64 images on), the per-(image, group) finalize launch and the
+    finalize-rows route of the apply pass below 32 images"""
+    _check_forward(name, 32, prec, 64, rows=[0, 37, 63])
+
+
+def test_attention_form_of_64_images_runs_at_3():
+    """The split-f16 attention core over 256 tokens of 192 channels (config B's): its 64-query form asks for
+    B * (tokens / 64) >= 256 blocks (launch_attention_split), which 64 images have and 3 do not. A default engine takes
+    it at B = 64; the mode (P = 64) must take it at B = 3: rows 0..2 of the two calls are byte-equal, and so is the B = 1 call.
+    The default B = 3 call runs the 32-query form. Measured here: it gives the SAME bytes as the 64-query form (each
+    query row walks the key tiles in the same order in both), so this site is one of those that DESIGN.md 3.5h lists as
+    shown not to matter; it reads the planning batch all the same. The last assertion holds that claim: if the two forms
+    ever part, it fails, and the first two assertions are then what keeps the mode right."""
+    rs = np.random.RandomState(SEED)
+    qkv = rs.standard_normal((64, 256, 3 * 192)).astype(F32)
+    out = {}
+    for what, plan_batch, B in [("default64", 0, 64), ("mode3", P, 3), ("default3", 0, 3), ("mode1", P, 1)]:
+        e = _new_engine("tiny", plan_batch)         # (the op takes its shape from the data, not from the UNet)
+        try:
+            e.set_precision("f16x3")
+            out[what] = e.op_attention(qkv[:B])
+        finally:
+            e.close()
+    _same(out["mode3"], out["default64"][:3], "mode on at B = 3 against the default B = 64 call")
+    _same(out["mode1"], out["default64"][:1], "mode on at B = 1 against the default B = 64 call")
+    _same(out["default3"], out["default64"][:3], "the 32-query form against the 64-query form (DESIGN.md 3.5h: does not matter)")
+
+
+# ---- the fp8 layer set ------------------------------------------------------------------------------------------------
+def _f8_convs(name, size, B, plan_batch):
+    convs = dict.fromkeys(c[1:] for c in plans.unet_convs(_cfg(name), 1, size, size))
+    return [c for c in convs if engine_mod.conv_plan(B, *c, precision="f16f8", stats=True, plan_batch=plan_batch)["f8"]]
+
+
+def test_fp8_layer_set_follows_the_planning_batch():
+    assert _f8_convs("F8", 32, 1, None) == [] and _f8_convs("F8", 32, 2, None) == []      # default plans: no fp8 operands
+    on = _f8_convs("F8", 32, 1, P)
+    assert on and on == _f8_convs("F8", 32, 2, P)
+    _check_forward("F8", 32, "f16f8", 2)
+    # (and the fp8 operands are live: the same forward in f16x3 gives other bytes)
+    x, nl = _input("F8", 2, 32)
+    a = _arm(_engine("F8", 2), "f16f8").unet_forward_np(x, nl)
+    b = _arm(_engine("F8", 2), "f16x3").unet_forward_np(x, nl)
+    assert not np.array_equal(a, b)
+
+
+# ---- samplers ---------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _bufs():
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return schedule.schedule_buffers(SCHED)
+
+
+def _set_sampler(e, kind, steps):
+    if kind == "ddpm":
+        e.set_schedule(_bufs())
+    else:
+        e.set_sampler_schedule(samplers.sampler_tables(_bufs(), kind, steps, 0.5 if kind == "ddim" else 0.0))
+    return steps or SCHED["n_timestep"]
+
+
+def _sampler_inputs(name, n):
+    cfg = _cfg(name)
+    size = 32 if name == "D" else 16
+    if cfg.in_channel == cfg.out_channel:
+        return None, (n, cfg.out_channel, size, size)
+    return synth.synth_cond(n, size, size // 2, SEED), None
+
+
+def _sample(e, cond, shape, rows, offset, **kw):
+    if cond is None:
+        return e.sample_np(None, shape=(len(rows),) + tuple(shape[1:]), seed=SEED, image_offset=offset, **kw)
+    return e.sample_np(cond[rows], seed=SEED, image_offset=offset, **kw)
+
+
+def _check_sampler(name, kind, steps, prec, setup=lambda e, row0, n: {}):
+    """one B = 4 call with image_offset 0 against four B = 1 calls with image_offset = row. setup(engine, first row, rows)
+    arms the options of a call and returns extra sample_np arguments."""
+    cond, shape = _sampler_inputs(name, 4)
+    e4, e1 = _arm(_engine(name, 4), prec), _arm(_engine(name, 1), prec)
+    for e in (e4, e1):
+        _set_sampler(e, kind, steps)
+    try:
+        got = _sample(e4, cond, shape, list(range(4)), 0, **setup(e4, 0, 4))
+        for r in range(4):
+            want = _sample(e1, cond, shape, [r], r, **setup(e1, r, 1))
+            _same(got[r:r + 1], want, f"{name} {kind} {prec}: row {r} of B=4 against its B=1 call")
+        assert e4.fallback_calls() == 0 and e1.fallback_calls() == 0
+    finally:
+        for e in (e4, e1):
+            e.set_lr_consistency(None)
+            e.set_dynamic_threshold(None)
+            e.set_feature_cache(None)
+
+
+@pytest.mark.parametrize("prec", PRECISIONS)
+@pytest.mark.parametrize("kind,steps", KINDS, ids=KIND_IDS)
+@pytest.mark.parametrize("name", ["tiny", "D"])
+def test_sampler_rows_are_their_single_image_calls(name, kind, steps, prec):
+    _check_sampler(name, kind, steps, prec)
+
+
+def test_sampler_warm_start():
+    init = synth.synth_cond(4, 16, 8, SEED + 1)
+
+    def setup(e, row0, n):
+        return {"init": init[row0:row0 + n], "start_step": 3}
+    _check_sampler("tiny", "dpmpp_2m", 4, "f16f8", setup)
+
+
+def test_sampler_lr_consistency():
+    lr = np.random.RandomState(SEED).uniform(-1, 1, (4, 3, 8, 8)).astype(F32)
+    keep = []
+
+    def setup(e, row0, n):
+        keep.append(e.to_device(lr))
+        e.set_lr_consistency(keep[-1].ptr, 4, 8, 8, row_offset=row0, strength=1.0)
+        return {}
+    _check_sampler("tiny", "ddim", 4, "f16x3", setup)
+
+
+def test_sampler_dynamic_threshold():
+    def setup(e, row0, n):
+        e.set_dynamic_threshold(0.995, 1.25)
+        return {}
+    _check_sampler("tiny", "ddim", 4, "f32", setup)
+
+
+def test_sampler_feature_cache():
+    def setup(e, row0, n):
+        e.set_feature_cache(2, 1)
+        return {}
+    _check_sampler("tiny", "ddpm", None, "f16f8", setup)
+    assert _engine("tiny", 4).feature_cache_steps()[1] > 0       # (shallow steps did run)
+
+
+# ---- rolling ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("prec", ["f32", "f16f8"])
+def test_rolling_requests_are_their_single_image_calls(prec):
+    """three slots, five requests admitted at steps 0, 0, 2, 3 and once a slot is free: every request returns the bytes
+    of its B = 1 uniform call"""
+    cond = synth.synth_cond(5, 16, 8, SEED)
+    e3, e1 = _arm(_engine("tiny", 3), prec), _arm(_engine("tiny", 1), prec)
+    for e in (e3, e1):
+        S = _set_sampler(e, "dpmpp_2m", 4)
+    reqs = [{"cond": cond[i], "image_id": 100 + i, "at": at} for i, at in enumerate([0, 0, 2, 3, S])]
+    got, trace = e3.rows_np(reqs, 3, seed=SEED)
+    assert any(sum(h is not None for h in t) == 3 for t in trace) and trace[2][2] == 2      # staggered, and full at times
+    for i in range(5):
+        want = e1.sample_np(cond[i:i + 1], seed=SEED, image_offset=100 + i)
+        _same(np.asarray(got[i])[None], want, f"rolling {prec}: request {i}")
+
+
+# ---- the facade: chunking, ranks, loss ---------------------------------------------------------------------------------
+def _opt(cfg):
+    return {"phase": "val", "sr": {"model": {
+        "which_model_G": "sr3",
+        "unet": {"in_channel": cfg.in_channel, "out_channel": cfg.out_channel, "inner_channel": cfg.inner_channel,
+                 "channel_multiplier": list(cfg.channel_mults), "attn_res": list(cfg.attn_res),
+                 "res_blocks": cfg.res_blocks, "dropout": 0.0},
+        "beta_schedule": {"train": SCHED, "val": SCHED},
+        "diffusion": {"image_size": cfg.image_size, "channels": 3, "conditional": True}}}}
+
+
+def _model(name, on=True):
+    import torch
+    cfg = _cfg(name)
+    netG = pkg("networks").define_G(_opt(cfg)).cuda()
+    netG.load_state_dict({"denoise_fn." + k: torch.from_numpy(v) for k, v in _weights(name).items()}, strict=False)
+    netG.set_new_noise_schedule(SCHED, [0])
+    if on:
+        netG.set_batch_invariant(True, P)
+    return netG
+
+
+def test_chunking_in_the_default_arithmetic():
+    """five images through super_resolution_batch in chunks of 2 (the last one padded) and in one call of 5, in the
+    facade's default f16f8 — on the configuration whose fp8 layer set the planning batch switches on"""
+    import torch
+    x = torch.from_numpy(synth.synth_cond(5, 32, 16, SEED)).cuda()
+    a, b = _model("F8"), _model("F8")
+    assert a.denoise_fn.precision == "f16f8"
+    by2 = a.super_resolution_batch(x, seed=SEED, max_chunk=2).cpu().numpy()
+    by5 = b.super_resolution_batch(x, seed=SEED, max_chunk=5).cpu().numpy()
+    assert a.denoise_fn.engine().batch_invariant() == P
+    _same(by2, by5, "chunks of 2 against one call of 5")
+
+
+def test_loss_terms_are_their_single_image_evaluations():
+    """p_losses: the fp64 per-image sums of one B = 4 evaluation against four B = 1 evaluations (chunks of one image;
+    the levels come from the reference's np.random draws, so the same seed gives both calls the same levels)"""
+    import torch
+    hr = torch.from_numpy(synth.synth_cond(4, 16, 8, SEED + 2)).cuda()
+    sr = torch.from_numpy(synth.synth_cond(4, 16, 8, SEED + 3)).cuda()
+    res = []
+    for chunk in (None, 1):
+        m = _model("tiny")
+        m.set_loss("cuda")
+        np.random.seed(SEED)
+        m.p_losses({"HR": hr, "SR": sr}, seed=SEED, max_chunk=chunk)
+        res.append(m.last_loss_per_image.cpu().numpy())
+    assert res[0].dtype == np.float64 and res[0].shape == (4,)
+    _same(res[0], res[1], "per-image loss sums")
+
+
+def test_a_rolling_session_inherits_the_setting_and_refuses_a_change():
+    import torch
+    m = _model("tiny")
+    x = torch.from_numpy(synth.synth_cond(2, 16, 8, SEED)).cuda()
+    alone = m.super_resolution_batch(x[:1], seed=SEED, image_offset=7).cpu().numpy()       # B = 1
+    other = _model("tiny")
+    with other.rolling(slots=3, seed=SEED) as roll:
+        t = roll.submit(x[0], image_id=7)
+        roll.submit(x[1], image_id=8)
+        with pytest.raises(pkg("_lib").Sr3Error):
+            other.set_batch_invariant(False)
+        with pytest.raises(pkg("_lib").Sr3Error):
+            other.set_batch_invariant(True, 8)
+        done = dict(roll.drain())
+    assert other.denoise_fn.batch_invariant == P
+    _same(done[t].cpu().numpy()[None], alone, "a request of a three-slot session against its B = 1 call")
+
+
+def _free_port():
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close()
+    return p
+
+
+def _worker(rank, world, port, n, q):
+    import importlib
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, repo)
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
+                      MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import torch
+    import torch.distributed as dist
+    name = "3d-super-resolution-face-reconstruction_amd"
+    pk = importlib.import_module(name)
+    d = importlib.import_module(name + ".dist")
+    sy = importlib.import_module(name + ".synth")
+    d.init_from_env("gloo")
+    torch.cuda.set_device(0)                     # every rank on the box's single GPU
+    cfg = sy.tiny_unet_config()
+    netG = pk.define_G(_opt(cfg)).cuda()
+    netG.load_state_dict({"denoise_fn." + k: torch.from_numpy(v) for k, v in sy.synth_state_dict(cfg, 515).items()},
+                         strict=False)
+    netG.set_new_noise_schedule(SCHED, [0])
+    netG.set_batch_invariant(True, P)
+    x_full = torch.from_numpy(sy.synth_cond(n, 16, 8, 99))
+    out = d.sharded_super_resolution(
+        lambda x, off: netG.super_resolution_batch(x.cuda(), seed=SEED, image_offset=off).cpu(), x_full)
+    q.put((rank, out.numpy(), d.shard_bounds(n, world, rank), netG.denoise_fn.precision))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_two_ranks_gather_the_single_process_batch():
+    """two real ranks over gloo on the one GPU, a ragged 3 + 2 split: the gathered batch is the single-process B = 5 call,
+    byte for byte (without the mode: to 2e-5, tests/test_gpu_dist.py)"""
+    import torch.multiprocessing as mp
+    n, world = 5, 2
+    cfg = synth.tiny_unet_config()
+    e = engine_mod.Engine(cfg, 0)
+    e.load_state_dict(synth.synth_state_dict(cfg, 515))
+    e.set_precision("f16f8")
+    e.set_batch_invariant(P)
+    e.set_schedule(_bufs())
+    want = e.sample_np(synth.synth_cond(n, 16, 8, 99), seed=SEED)
+    e.close()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, n, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=600) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    sizes = []
+    for rank, out, (a, b), prec in res:
+        assert prec == "f16f8"
+        _same(out, want, f"rank {rank}: the gathered batch")
+        sizes.append(b - a)
+    assert sorted(sizes) == [2, 3]
+
+
+# ---- switching --------------------------------------------------------------------------------------------------------
+def test_switching_the_mode_rebuilds_what_bakes_the_plan_in():
+    """mode on, a call, mode off, a call: the last call is a fresh default engine's, and the steps were captured again"""
+    cond = synth.synth_cond(2, 16, 8, SEED)
+    e = _new_engine("tiny", P)
+    fresh = _new_engine("tiny", 0)
+    try:
+        for x in (e, fresh):
+            x.set_precision("f16x3")
+            _set_sampler(x, "ddpm", None)
+        on = e.sample_np(cond, seed=SEED)
+        n_on = e.step_graph_captures()
+        e.set_batch_invariant(0)
+        assert e.batch_invariant() == 0
+        off = e.sample_np(cond, seed=SEED)
+        n_off = e.step_graph_captures()
+        _same(off, fresh.sample_np(cond, seed=SEED), "mode switched off against a fresh default engine")
+        if os.environ.get("SR3_NO_GRAPH", "0") in ("", "0"):    # (a host that cannot capture counts nothing)
+            assert n_on > 0, "no step was captured"
+            assert n_off > n_on, "the captured steps of the mode were replayed after it was switched off"
+        e.set_batch_invariant(True)                 # (True: the facade's default planning batch, not a batch of one)
+        assert e.batch_invariant() == P == 64
+        _same(e.sample_np(cond, seed=SEED), on, "mode switched back on")
+        e.set_batch_invariant(False)
+        assert e.batch_invariant() == 0
+        e.set_batch_invariant(P)
+        with pytest.raises(pkg("_lib").Sr3Error):
+            e.set_batch_invariant(-1)
+    finally:
+        e.close(); fresh.close()
