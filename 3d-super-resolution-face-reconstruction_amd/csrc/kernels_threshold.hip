@@ -126,9 +126,10 @@ __global__ __launch_bounds__(THR_THREADS) void thr_final_kernel(const unsigned *
     if (s_out) s_out[blockIdx.x] = fminf(fmaxf(s_raw, 1.0f), max_value);
 }
 
-// the counts back to zero, as a kernel. A workaround: with a hipMemsetAsync here (a memset node of the captured step) a
-// thresholded rows step with the projection gave other images replayed from its graph than run eagerly, and with this
-// kernel it does not; why is not explained
+// the counts back to zero, as a kernel: a captured step holds kernel nodes only. With a hipMemsetAsync here (a memset node
+// of the captured step) a thresholded call repeated on a workspace that replaced an older one ran with s = 1 in every step
+// when replayed from its graph, and an armed thresholded rows step gave other images replayed than run eagerly
+// (tests/test_gpu_engine_history.py fails on such a build)
 __global__ void thr_zero_kernel(unsigned *__restrict__ bins, size_t total) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < total) bins[i] = 0u;

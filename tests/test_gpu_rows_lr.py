@@ -179,8 +179,9 @@ def test_strength_is_per_row():
 
 # ---- 5. with the dynamic threshold ----------------------------------------------------------------------------------------
 def test_staggered_held_rows_with_the_dynamic_threshold():
-    """every engine runs one batch size and the oracle's second chunk an engine of its own, as
-    test_gpu_rows.py::test_staggered_rows_with_the_dynamic_threshold does (the open defect of DESIGN.md §8)"""
+    """one engine runs both chunks of the oracle, a thresholded call of 6 (a larger workspace), the session and the first
+    chunk again, as test_gpu_rows.py::test_staggered_rows_with_the_dynamic_threshold does (DESIGN.md §8: the replay
+    difference that kept these apart went with the memset node of the select)"""
     kind, S = "dpmpp_2m", 4
     cond, lr = _cond(6), _lr(6)
     e = _engine(kind, S)
@@ -188,16 +189,15 @@ def test_staggered_held_rows_with_the_dynamic_threshold():
     e.set_dynamic_threshold(RATIO, CAP)
     want = [_uniform(e, cond[:SLOTS], OFFSET, lr[:SLOTS])]
     assert np.abs(want[0] - only_lr).max() > 1e-3           # (the threshold is live on these inputs)
-    other = _engine(kind, S)
-    other.set_dynamic_threshold(RATIO, CAP)
-    want.append(_uniform(other, cond[SLOTS:], OFFSET + SLOTS, lr[SLOTS:]))
-    other.close()
+    want.append(_uniform(e, cond[SLOTS:], OFFSET + SLOTS, lr[SLOTS:]))
     want = np.concatenate(want)
+    e.sample_np(cond, seed=SEED, image_offset=OFFSET)       # (B = 6: the session's workspace replaces a larger one)
     reqs = [{"cond": cond[i], "image_id": OFFSET + i, "at": at, "lr": lr[i]} for i, at in enumerate(_staggered(S))]
     n0 = e.dynamic_threshold_launches()
     got, trace = e.rows_np(reqs, SLOTS, seed=SEED)
     assert trace[S] == [4, 5, 2, 3] and e.dynamic_threshold_launches() - n0 == 2 * S
     _same(np.stack(got), want, "thresholded and held")
+    _same(_uniform(e, cond[:SLOTS], OFFSET, lr[:SLOTS]), want[:SLOTS], "the first chunk again, after the session")
     e.close()
 
 
