@@ -97,6 +97,10 @@ PROTOTYPES = {
     "sr3_rows_retire": (_I, [_P, _I, _F]),
     "sr3_rows_drop": (_I, [_P, _I]),
     "sr3_rows_end": (_I, [_P]),
+    "sr3_rows_step_batch": (_I, [_P, C.POINTER(_F), _I]),
+    "sr3_rows_move": (_I, [_P, _I, _I]),
+    "sr3_rows_rows_run": (_U64, [_P]),
+    "sr3_read_history": (C.c_int64, [_P, _P]),
     "sr3_range_check": (_I, [_P]),
     "sr3_set_range_policy": (_I, [_P, _I]),
     "sr3_fallback_calls": (_I, [_P]),
@@ -177,7 +181,7 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_rows_begin", "sr3_rows_admit", "sr3_rows_step", "sr3_rows_position", "sr3_rows_retire", "sr3_rows_drop",
                   "sr3_rows_end", "sr3_op_conv2d_fused", "sr3_op_attention_twin", "sr3_gn_res1x1_launches", "sr3_gn_res1x1_gate",
                   "sr3_op_gn_res1x1", "sr3_bench_gn_res1x1", "sr3_rows_lr_consistency", "sr3_rows_admit_lr", "sr3_rows_frames",
-                  "sr3_op_lr_project_rows")
+                  "sr3_op_lr_project_rows", "sr3_rows_step_batch", "sr3_rows_move", "sr3_rows_rows_run", "sr3_read_history")
 
 _lib = None
 

@@ -8,6 +8,8 @@
 // Element-wise, no matrix work: bound by the Philox / Box-Muller arithmetic like the kernels they mirror.
 #include "sr3_internal.h"
 
+#include <algorithm>
+
 namespace sr3 {
 
 namespace {
@@ -94,7 +96,41 @@ __global__ void rows_update_from_x0_kernel(const RowsUpdateParams u, const float
     finish_update(u, ra, e, i, pix, si, u.state.p[si], x0hat[i]);
 }
 
+// sr3_rows_move (live rows only): a pure copy, bound by memory traffic (about 3 MB at 128x128: the
+// 2.2 MB state slab read, written and zeroed dominates). blockIdx.y picks the segment, blockIdx.x strides over its
+// 16-byte units (VEC) or its floats; each element is read, stored to the destination and, for the state and the packed
+// copy, overwritten with zero at the source by the same thread.
+__global__ void rows_move_kernel(const RowsMoveParams p) {
+    const RowsMoveSeg sg = p.seg[blockIdx.y];
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool vec = (sg.n % 4) == 0 && ((reinterpret_cast<uintptr_t>(sg.src) | reinterpret_cast<uintptr_t>(sg.dst)) & 15) == 0;
+    if (vec) {
+        float4 *src = reinterpret_cast<float4 *>(sg.src);
+        float4 *dst = reinterpret_cast<float4 *>(sg.dst);
+        const size_t n4 = sg.n / 4;
+        for (size_t i = i0; i < n4; i += stride) {
+            dst[i] = src[i];
+            if (sg.zero) src[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    } else {
+        for (size_t i = i0; i < sg.n; i += stride) {
+            sg.dst[i] = sg.src[i];
+            if (sg.zero) sg.src[i] = 0.f;
+        }
+    }
+}
+
 } // namespace
+
+void launch_rows_move(const RowsMoveParams &p, hipStream_t s) {
+    if (p.nseg < 1) return;
+    size_t most = 0;
+    for (int i = 0; i < p.nseg; ++i) most = std::max(most, (p.seg[i].n + 3) / 4);
+    // memory-bound: one 16-byte unit per thread up to 2048 blocks, the rest in the grid-stride loop
+    const unsigned gx = (unsigned)std::min<size_t>(std::max<size_t>(nblk(most), 1), 2048);
+    hipLaunchKernelGGL(rows_move_kernel, dim3(gx, (unsigned)p.nseg), dim3(256), 0, s, p);
+}
 
 void launch_rows_update(const RowsUpdateParams &p, int B, hipStream_t s) {
     const size_t total = (size_t)B * p.C * p.state.H * p.state.W;

@@ -138,22 +138,27 @@ struct StepKey {
     unsigned *dyn_bins = nullptr;
     RowArgs *rows = nullptr;        // rolling batch (sr3_rows_step): the per-row argument table; null: the uniform step
     const float *rows_lr = nullptr; // rows && lr (a session armed by sr3_rows_lr_consistency): the per-slot LR images
+    int batch = 0;                  // rows: the slots [0, batch) the step covers (sr3_rows_step_batch); 0: the whole workspace
 
     // one graph is kept per (arithmetic, whole | shallow, form): 24 at the most, and per (arithmetic, plain | dynamic
-    // threshold, unarmed | armed for the projection) of the rows form (always whole): 12 more. A rows step and a uniform
-    // one never share a slot, nor do the steps of an armed and of an unarmed session.
-    bool same_slot(const StepKey &o) const {
+    // threshold, unarmed | armed for the projection) of the rows form (always whole): 12 more, 36 in all while no step is
+    // elastic. Each of the 12 rows forms keeps up to kRowsBatchGraphs (16) more, one per batch value below the slot count
+    // (launch_step evicts the least recently used): 12 * 17 + 24 = 228 at the most. A rows step and a uniform one never
+    // share a slot, nor do the steps of an armed and of an unarmed session, nor those of two batch values.
+    bool same_form(const StepKey &o) const {
         return mode == o.mode && (depth > 0) == (o.depth > 0) && lr == o.lr && dyn == o.dyn && (rows != nullptr) == (o.rows != nullptr);
     }
+    bool same_slot(const StepKey &o) const { return same_form(o) && batch == o.batch; }
     auto tie() const {
-        return std::tie(mode, depth, lr, dyn, rows, rows_lr, x0hat, lr_ops.Av, lr_ops.Ah, lr_ops.Pv, lr_ops.PhT, lr_ops.bv, lr_ops.bh, lr_ops.lh,
+        return std::tie(mode, depth, lr, dyn, rows, rows_lr, batch, x0hat, lr_ops.Av, lr_ops.Ah, lr_ops.Pv, lr_ops.PhT, lr_ops.bv, lr_ops.bh, lr_ops.lh,
                         lr_ops.lw, lr_ops.H, lr_ops.W, lr_lds, lr_scratch, dyn_n, dyn_plan.k, dyn_plan.k2, dyn_plan.frac,
                         dyn_plan.blocks, dyn_max, dyn_s, dyn_bins);
     }
     bool operator==(const StepKey &o) const { return tie() == o.tie(); }
 };
 // warm: steps run eagerly under this key (the first sets one-time function attributes; the second is captured)
-struct StepGraph { StepKey key; hipGraphExec_t exec = nullptr; int warm = 0; };
+// used: launch_step's clock at the last launch (the eviction order of the elastic rows graphs)
+struct StepGraph { StepKey key; hipGraphExec_t exec = nullptr; int warm = 0; uint64_t used = 0; };
 
 } // namespace
 
@@ -284,6 +289,10 @@ struct sr3_ctx {
     // workspace for one (B, H, W)
     int wB = 0, wH = 0, wW = 0;
     char *arena = nullptr;
+    // what ensure_workspace carved of the buffers every conv / attention / GroupNorm shares, in floats, and the statistics
+    // slices per image of every conv in the order it asked (rows_batch_fits holds a smaller batch against them)
+    uint64_t cap_part = 0, cap_wino = 0, cap_vt = 0, cap_gpart = 0;
+    std::vector<int> conv_slices;
     uint64_t arena_bytes = 0;
     TDesc x0;                   // [B][H+2][W+2][in_pad]: cond ‖ x ‖ zero pad (UNet input = sampler state)
     TDesc x0s;                  // split-f16 copy of x0 for the first conv (prec 1)
@@ -343,6 +352,13 @@ struct sr3_ctx {
     int rows_cap = 0;
     static constexpr int kRowRing = 256;        // as kRing: the host synchronises every 128 steps
     uint64_t rows_count = 0;
+    // Elastic steps (sr3_rows_step_batch): rows_run sums the batch of every row-session step launched; rows_batch_ok holds
+    // the batch values below wB whose plans were checked against what ensure_workspace carved (rows_batch_fits; emptied
+    // with every new workspace and every change of the planning batch).
+    uint64_t rows_run = 0;
+    std::vector<int> rows_batch_ok;
+    static constexpr int kRowsBatchGraphs = 16;
+    uint64_t graph_clock = 0;
     float *d_row_start = nullptr;       // a[rows_cap] | s[rows_cap]: q_sample coefficients of the rows admitted noised
     // per-step arguments: pinned host ring -> device struct (async copy before every step)
     static constexpr int kRing = 256;
@@ -754,6 +770,8 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     // repeat of the range check runs on the same workspace) and with or without fused statistics (a shape that has none
     // runs without). Returns the statistics slices per image of its output (the same in all four plans).
     bool frag_ok = true;
+    c->conv_slices.clear();
+    c->rows_batch_ok.clear();
     auto want = [&](const ConvRef &cr, int ih, int iw, int stride, int up2) {
         int slices = 0;
         for (int v = 0; v < 4; ++v) {
@@ -764,6 +782,7 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
             max_wino = std::max<uint64_t>(max_wino, pl.wino_ws_floats);
             if ((pl.needs_wino_frag || pl.wino_fused_rows) && ensure_wino_frag(c, c->params[cr.w])) frag_ok = false;
         }
+        c->conv_slices.push_back(slices);
         return slices;
     };
     for (size_t i = 0; i < nm; ++i) {
@@ -885,8 +904,62 @@ int ensure_workspace(sr3_ctx *c, int B, int H, int W) {
     c->gscale = at(o_gs); c->gshift = at(o_gh); c->gpart = at(o_gp);
     c->temb = at(o_te); c->cbias = at(o_cb);
     c->all_fused = all_fused;
+    c->cap_part = max_part; c->cap_wino = max_wino; c->cap_vt = max_vt; c->cap_gpart = gn_workspace_floats(B, c->c_max);
     c->wB = B; c->wH = H; c->wW = W;
     return 0;
+}
+
+// Elastic row steps (sr3_rows_step_batch): does a step over `b` < wB images fit the workspace carved for wB? The same
+// questions ensure_workspace asked at wB, asked at b: split-K partials, Winograd workspace, v^T scratch and GroupNorm
+// partials must not exceed what was carved, the statistics slices per image must be the ones the buffers were laid out
+// for, and a plan must not want a weight layout nobody made. In batch-invariant mode all of it follows from the plans
+// being those of the planning batch (part_floats = phases * splits * M * Cout with splits a function of P: monotone in
+// the batch); this check is what keeps a later change of a plan from launching past a buffer. 0, or -1 with the error set.
+int rows_batch_fits(sr3_ctx *c, int b) {
+    size_t at = 0;
+    int bad = 0;
+    auto ask = [&](const ConvRef &cr, int ih, int iw, int stride, int up2) {
+        const int slices = at < c->conv_slices.size() ? c->conv_slices[at] : -1;
+        ++at;
+        for (int v = 0; v < 4 && !bad; ++v) {
+            const ConvPlan pl = conv_plan_offered(b, ih, iw, cr.cin_pad, cr.cout, cr.ks, stride, up2, v & 1, false, (v & 2) != 0);
+            if (pl.part_floats > c->cap_part)
+                bad = fail("internal: a step over %d of %d rows wants %llu floats of split-K partials (conv %d -> %d at %dx%d), the workspace holds %llu",
+                           b, c->wB, (unsigned long long)pl.part_floats, cr.cin, cr.cout, ih, iw, (unsigned long long)c->cap_part);
+            else if (pl.stats_slices != slices)
+                bad = fail("internal: a step over %d of %d rows leaves %d statistics slices per image (conv %d -> %d at %dx%d), the workspace was laid out for %d",
+                           b, c->wB, pl.stats_slices, cr.cin, cr.cout, ih, iw, slices);
+            else if (wino_weights(c->params[cr.w])) {
+                if (pl.wino_ws_floats > c->cap_wino)
+                    bad = fail("internal: a step over %d of %d rows wants %llu floats of Winograd workspace (conv %d -> %d at %dx%d), the workspace holds %llu",
+                               b, c->wB, (unsigned long long)pl.wino_ws_floats, cr.cin, cr.cout, ih, iw, (unsigned long long)c->cap_wino);
+                else if ((pl.needs_wino_frag || pl.wino_fused_rows) && !c->params[cr.w].dev_wino_f)
+                    bad = fail("internal: a step over %d of %d rows wants fragment-major Winograd weights (conv %d -> %d at %dx%d) that the plans of the workspace never asked for",
+                               b, c->wB, cr.cin, cr.cout, ih, iw);
+            }
+        }
+    };
+    for (const Module &m : c->mods) {
+        if (bad) break;
+        if (m.kind == M_RES) {
+            ask(m.rb.c1, m.oh, m.ow, 1, 0);
+            ask(m.rb.c2, m.oh, m.ow, 1, 0);
+            if (m.rb.attn) {
+                ask(m.rb.qkv, m.oh, m.ow, 1, 0);
+                ask(m.rb.aout, m.oh, m.ow, 1, 0);
+                for (const bool split : {false, true})
+                    if (!bad && attention_core(split, (long)m.oh * m.ow, m.oc) == ATTN_SPLIT &&
+                        attention_vt_floats(b, m.oh * m.ow, m.oc) > c->cap_vt)
+                        bad = fail("internal: a step over %d of %d rows wants more attention scratch than the workspace holds", b, c->wB);
+            }
+        } else {
+            ask(m.conv, m.ih, m.iw, m.kind == M_DOWN ? 2 : 1, m.kind == M_UP ? 1 : 0);
+        }
+    }
+    if (!bad && at != c->conv_slices.size()) bad = fail("internal: the workspace recorded %zu convs, its modules hold %zu", c->conv_slices.size(), at);
+    if (!bad && gn_workspace_floats(b, c->c_max) > c->cap_gpart)
+        bad = fail("internal: a step over %d of %d rows wants more GroupNorm partials than the workspace holds", b, c->wB);
+    return bad;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1730,7 +1803,7 @@ StepKey step_key(const sr3_ctx *c, int depth) {
 // key, NOT from the live context: what a capture bakes in is then what its key says. (c->lr travels as launch_lr_project's
 // `val`, which no kernel reads when `dyn` is given.)
 void enqueue_rows_update(sr3_ctx *c, const StepKey &k) {
-    const int B = c->wB;
+    const int B = k.batch ? k.batch : c->wB;        // (every launch below covers rows [0, B) and no other)
     RowsUpdateParams u;
     u.state = c->x0; u.C = c->cfg.out_channel;
     u.packed = c->x0p;
@@ -1746,7 +1819,7 @@ void enqueue_rows_update(sr3_ctx *c, const StepKey &k) {
         // as enqueue_update: prediction | threshold | projection | the rest of the update, each in its rows form
         launch_rows_x0_predict(u, k.x0hat, B, c->stream, !k.dyn);
         if (k.dyn) {
-            // (the threshold kernels run over all B rows: an idle row's slab of x0hat is zeros, s = 1, and is never used)
+            // (the threshold kernels run over all B rows of the step: an idle row's slab of x0hat is zeros, s = 1, and is never used)
             launch_abs_quantile(k.x0hat, B, k.dyn_n, k.dyn_plan, k.dyn_max, k.dyn_bins, nullptr, nullptr, k.dyn_s, c->stream);
             launch_threshold_apply(k.x0hat, B, k.dyn_n, k.dyn_s, c->stream);
         }
@@ -1791,8 +1864,9 @@ void enqueue_update(sr3_ctx *c, const StepKey &k) {
 void enqueue_step(sr3_ctx *c, const StepKey &k) {
     if (k.rows) {
         // every row's own level: the embedding over B rows, each conv reading its row of the FeatureWiseAffine biases
-        run_embed(c, &k.rows->nl, (int)(sizeof(RowArgs) / sizeof(float)), c->wB);
-        run_unet_body(c, c->wB, c->wH, c->wW, 0);
+        const int B = k.batch ? k.batch : c->wB;
+        run_embed(c, &k.rows->nl, (int)(sizeof(RowArgs) / sizeof(float)), B);
+        run_unet_body(c, B, c->wH, c->wW, 0);
         enqueue_update(c, k);
         return;
     }
@@ -1860,12 +1934,28 @@ int launch_step(sr3_ctx *c, const StepKey &key) {
     for (StepGraph &e : c->step_graphs)
         if (e.key.same_slot(key)) { g = &e; break; }
     if (!g) {
+        if (key.batch) {
+            // an elastic rows step at a batch value without a graph: its form keeps kRowsBatchGraphs of them, the least
+            // recently used one goes
+            int n = 0;
+            size_t lru = 0;
+            for (size_t i = 0; i < c->step_graphs.size(); ++i) {
+                const StepGraph &e = c->step_graphs[i];
+                if (!e.key.batch || !e.key.same_form(key)) continue;
+                if (!n++ || e.used < c->step_graphs[lru].used) lru = i;
+            }
+            if (n >= sr3_ctx::kRowsBatchGraphs) {
+                if (c->step_graphs[lru].exec) (void)hipGraphExecDestroy(c->step_graphs[lru].exec);
+                c->step_graphs.erase(c->step_graphs.begin() + (long)lru);
+            }
+        }
         c->step_graphs.push_back(StepGraph{key});
         g = &c->step_graphs.back();
     } else if (!(g->key == key)) {      // a baked-in value changed: as for a new key, one eager step and one capture
         if (g->exec) (void)hipGraphExecDestroy(g->exec);
         *g = StepGraph{key};
     }
+    g->used = ++c->graph_clock;
     if (!g->exec) {
         if (g->warm < 1) {          // first step runs eagerly (one-time function attributes)
             ++g->warm;
@@ -3141,17 +3231,36 @@ int sr3_rows_frames(sr3_ctx *c, int row, float *frames_dev, int capacity) {
 }
 
 int sr3_rows_step(sr3_ctx *c, const float *const *noise_rows) {
+    if (rows_check(c, "sr3_rows_step", 0)) return -1;
+    return sr3_rows_step_batch(c, noise_rows, c->wB);
+}
+
+// (B below is the step's batch: every loop and every launch covers slots [0, B); with B == wB the key carries batch 0 and
+// the step is the one sr3_rows_step always launched)
+int sr3_rows_step_batch(sr3_ctx *c, const float *const *noise_rows, int batch) {
     PlanScope plan_scope(c);
     if (rows_check(c, "sr3_rows_step", 0)) return -1;
     HIP_OK(hipSetDevice(c->device));
-    const int B = c->wB;
+    if (batch < 1 || batch > c->wB) return fail("sr3_rows_step_batch: batch %d outside [1, %d], the session's slots", batch, c->wB);
+    if (batch < c->wB && c->plan_batch <= 0)
+        return fail("sr3_rows_step_batch: batch %d below the session's %d slots needs the batch-invariant mode (sr3_set_batch_invariant "
+                    "before sr3_rows_begin): the workspace was sized by plans that follow the batch, and a smaller batch may "
+                    "ask more of it", batch, c->wB);
+    const int B = batch;
     int live = 0;
-    for (const auto &r : c->rows) {
+    for (int n = 0; n < c->wB; ++n) {
+        const auto &r = c->rows[n];
         // (positions index the step tables: a schedule set after a row was admitted may be shorter)
         if (r.live && r.pos > c->T) return fail("sr3_rows_step: a row has %d steps left and the schedule %d: the schedule was changed after sr3_rows_admit", r.pos, c->T);
+        if (r.live && r.pos > 0 && n >= B)
+            return fail("sr3_rows_step_batch: slot %d is live with %d steps left and lies outside batch %d (sr3_rows_move it below the batch, or step a larger one)", n, r.pos, B);
         live += (r.live && r.pos > 0) ? 1 : 0;
     }
     if (!live) return 0;
+    if (B < c->wB && std::find(c->rows_batch_ok.begin(), c->rows_batch_ok.end(), B) == c->rows_batch_ok.end()) {
+        if (rows_batch_fits(c, B)) return -1;
+        c->rows_batch_ok.push_back(B);
+    }
     if (prepare_f8(c)) return -1;
     if (c->lr_on() || c->fc_on() || c->drop_live())
         return fail("sr3_rows_step: low-resolution consistency, the feature cache or Dropout sampling was turned on after sr3_rows_begin");
@@ -3198,6 +3307,7 @@ int sr3_rows_step(sr3_ctx *c, const float *const *noise_rows) {
     c->fc_invalidate();
     StepKey key = step_key(c, 0);
     key.rows = c->d_rows;
+    key.batch = B < c->wB ? B : 0;
     if (c->rows_lr) {       // (the members step_key fills for the per-call projection, from the session's own)
         key.lr = true; key.x0hat = c->x0hat;
         key.lr_ops = c->rows_lr_ops; key.lr_lds = c->rows_lr_lds;
@@ -3209,8 +3319,52 @@ int sr3_rows_step(sr3_ctx *c, const float *const *noise_rows) {
     if (c->prof) c->pflush();           // bound the number of live events
     HIP_OK(hipGetLastError());
     c->rows.swap(next);
+    c->rows_run += (uint64_t)B;
     if (c->dyn_on()) ++c->dyn_steps;
     return live;
+}
+
+uint64_t sr3_rows_rows_run(sr3_ctx *c) { return c ? c->rows_run : 0; }
+
+int sr3_rows_move(sr3_ctx *c, int src, int dst) {
+    if (rows_check(c, "sr3_rows_move", src) || rows_check(c, "sr3_rows_move", dst)) return -1;
+    HIP_OK(hipSetDevice(c->device));
+    if (!c->rows[src].live) return fail("sr3_rows_move: source slot %d is idle", src);
+    if (c->rows[dst].live) return fail("sr3_rows_move: destination slot %d is live (%d steps left); retire or drop it first", dst, c->rows[dst].pos);
+    // (src != dst follows: one slot cannot be both)
+    const int C = c->cfg.out_channel;
+    const TDesc xs = row_desc(c->x0, src), xd = row_desc(c->x0, dst);
+    RowsMoveParams mv;
+    auto seg = [&](float *from, float *to, size_t n, int zero) {
+        RowsMoveSeg &g = mv.seg[mv.nseg++];
+        g.src = from; g.dst = to; g.n = n; g.zero = zero;
+    };
+    seg(xs.p, xd.p, xs.floats(1), 1);
+    if (c->x0p) seg(row_packed(c, src), row_packed(c, dst), (size_t)(c->wH + 2) * (c->wW + 2) * 8, 1);
+    const size_t nh = (size_t)C * c->wH * c->wW;
+    seg(c->xhist + (size_t)src * nh, c->xhist + (size_t)dst * nh, nh, 0);
+    if (c->rows_lr) {       // (every slot of an armed session has its slab, held or not)
+        const size_t nl = (size_t)C * c->rows_lr_ops.lh * c->rows_lr_ops.lw;
+        seg(c->rows_lr_buf + (size_t)src * nl, c->rows_lr_buf + (size_t)dst * nl, nl, 0);
+    }
+    c->pbegin(F_MISC);
+    launch_rows_move(mv, c->stream);
+    c->pend();
+    HIP_OK(hipGetLastError());
+    c->rows[dst] = c->rows[src];
+    c->rows[src] = sr3_ctx::RowState();
+    return 0;
+}
+
+int64_t sr3_read_history(sr3_ctx *c, float *hist_host) {
+    if (!c) return fail("null context");
+    if (!c->arena || c->wB <= 0) return fail("sr3_read_history: no call has set up a workspace yet");
+    if (!hist_host) return fail("sr3_read_history: hist_host is null");
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)c->wB * c->cfg.out_channel * c->wH * c->wW;
+    HIP_OK(hipMemcpy(hist_host, c->xhist, n * sizeof(float), hipMemcpyDeviceToHost));
+    return (int64_t)n;
 }
 
 int sr3_rows_position(sr3_ctx *c, int row) {

@@ -515,6 +515,13 @@ struct RowsUpdateParams {
 void launch_rows_update(const RowsUpdateParams &p, int B, hipStream_t s);
 void launch_rows_x0_predict(const RowsUpdateParams &p, float *x0hat, int B, hipStream_t s, bool clamp = true);
 void launch_rows_update_from_x0(const RowsUpdateParams &p, const float *x0hat, int B, hipStream_t s);
+// sr3_rows_move: one row's slabs into another slot in ONE launch. Each segment is a contiguous run of n floats (the state
+// slab, the packed slab, the history slab, the LR image); zero: the source is left as zeros (state and packed copy, as
+// sr3_rows_drop leaves them). Source and destination are different rows and never overlap. A segment whose addresses
+// and length allow it moves in 16-byte units.
+struct RowsMoveSeg { float *src = nullptr; float *dst = nullptr; size_t n = 0; int zero = 0; };
+struct RowsMoveParams { RowsMoveSeg seg[4]; int nseg = 0; };
+void launch_rows_move(const RowsMoveParams &p, hipStream_t s);
 // x <- noise (NCHW buffer or Philox draw 0) into state channels
 void launch_init_state(const TDesc &state, int xoff, int C, const float *noise, uint64_t seed,
                        uint64_t image_offset, int B, hipStream_t s);

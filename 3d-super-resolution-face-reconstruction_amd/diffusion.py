@@ -509,7 +509,8 @@ class GaussianDiffusion(nn.Module):
                 frames[:, a:b] = fc[:, : b - a]
         return (out, frames) if continous else out
 
-    def rolling(self, slots: Optional[int] = None, seed: Optional[int] = None, shape=None, lr_size=None):
+    def rolling(self, slots: Optional[int] = None, seed: Optional[int] = None, shape=None, lr_size=None,
+                elastic: bool = False, ladder=None):
         """A `rolling.RollingSampler` on this model: single-image requests served through `slots` batch
         rows, each at its own position of the schedule, so a request takes a free slot while the others are mid-trajectory.
         It uses the model's sampler (set_sampler), arithmetic, range policy and dynamic threshold as they stand now. Every
@@ -526,8 +527,11 @@ class GaussianDiffusion(nn.Module):
         session is armed for the LR size when it begins — by lr_size=(lh, lw), or by the first request carrying an lr.
         submit(..., continous=True) makes poll return what super_resolution(x, continous=True) returns for one image:
         the conditioning image followed by the request's frames. The per-call set_lr_consistency, the feature cache and
-        Dropout sampling do not follow single rows: the session refuses them, naming the setting. Use as a context
-        manager, or close() it."""
+        Dropout sampling do not follow single rows: the session refuses them, naming the setting. elastic=True (needs
+        set_batch_invariant(): ValueError otherwise): a step runs over the live rows only, at the smallest batch of
+        `ladder` (default rolling.default_ladder(slots)) that covers them, the rows compacted by one-launch moves where
+        that lowers the batch; a lightly loaded session then pays for the rows it holds, not for its slots, and every
+        request is still its B = 1 call byte for byte (`batch_trace`, `moves`). Use as a context manager, or close() it."""
         from .rolling import RollingSampler
         if not self.conditional:
             raise Sr3Error("rolling() needs a conditional model: the unconditional one has no per-request input")
@@ -537,6 +541,8 @@ class GaussianDiffusion(nn.Module):
             raise Sr3Error("rolling(): set_feature_cache is on and counts whole and shallow steps per call; turn it off")
         if self.denoise_fn.dropout_live():
             raise Sr3Error("rolling(): Dropout sampling (set_dropout_sampling) is on and keys its masks per call; turn it off")
+        if elastic and not self.denoise_fn.batch_invariant:
+            raise ValueError("rolling(elastic=True) needs the batch-invariant mode: call set_batch_invariant() first")
         eng = self._engine()
         self.denoise_fn.arm_dropout(eng)
         dev = next(self.denoise_fn.parameters()).device
@@ -569,7 +575,7 @@ class GaussianDiffusion(nn.Module):
                               precision=getattr(eng, "precision", "f32"), strict=self.denoise_fn.strict_range,
                               start_steps=lambda S, strength: self.start_steps(S, strength=strength), alloc=alloc,
                               ready=self.denoise_fn.ready, finish=self.denoise_fn.finish, lr_size=lr_size, to_lr=to_lr,
-                              alloc_frames=alloc_frames, deliver=deliver)
+                              alloc_frames=alloc_frames, deliver=deliver, elastic=elastic, ladder=ladder)
 
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, noise=None, seed=None):

@@ -444,7 +444,8 @@ class Engine:
         """Opens a row session of B slots at H x W, all idle (sr3_rows_begin). Uses the sampler, arithmetic and dynamic
         threshold set on the engine; refuses the per-call LR consistency (set_lr_consistency: a session holds single rows,
         rows_lr_consistency), the feature cache and Dropout sampling. Every step runs at batch B whatever is live: a
-        row's result is that of its row in a uniform call of B images."""
+        row's result is that of its row in a uniform call of B images. (In the batch-invariant mode rows_step takes a
+        `batch` below B and rows_move compacts the live rows: the step then costs what `batch` images cost.)"""
         _lib.check(self.lib.sr3_rows_begin(self.ctx, int(B), int(H), int(W), int(seed) & (2 ** 64 - 1)))
         self._rows_slots = int(B)
 
@@ -476,9 +477,11 @@ class Engine:
         start_step), to frames_ptr (sr3_rows_frames) — those of its row in the uniform call with frames."""
         _lib.check(self.lib.sr3_rows_frames(self.ctx, int(row), frames_ptr, int(capacity)))
 
-    def rows_step(self, noise_ptrs: Optional[Sequence[Optional[int]]] = None) -> int:
+    def rows_step(self, noise_ptrs: Optional[Sequence[Optional[int]]] = None, batch: Optional[int] = None) -> int:
         """One step of every live row at its own position (sr3_rows_step); noise_ptrs: one device address (or None)
-        per slot, the [C,H,W] draw of that row's step. Returns the number of rows stepped (0: nothing was launched)."""
+        per slot, the [C,H,W] draw of that row's step. Returns the number of rows stepped (0: nothing was launched).
+        batch (batch-invariant mode only): the step runs over slots [0, batch) alone (sr3_rows_step_batch) and costs
+        what `batch` images cost; every live row must sit below it (rows_move). None: the whole session."""
         arr = None
         if noise_ptrs is not None:
             # (the library reads one entry per slot of the session)
@@ -486,9 +489,29 @@ class Engine:
                 raise ValueError(f"noise_ptrs needs one entry per slot of the session ({getattr(self, '_rows_slots', 0)}), "
                                  f"got {len(noise_ptrs)}")
             arr = (C.c_void_p * len(noise_ptrs))(*[p or None for p in noise_ptrs])
-        n = int(self.lib.sr3_rows_step(self.ctx, arr))
+        if batch is None:
+            n = int(self.lib.sr3_rows_step(self.ctx, arr))
+        else:
+            n = int(self.lib.sr3_rows_step_batch(self.ctx, arr, int(batch)))
         _lib.check(min(n, 0))
         return n
+
+    def rows_move(self, src: int, dst: int) -> None:
+        """Moves live slot `src` into idle slot `dst` (sr3_rows_move): state, packed copy, x0 history, LR image and the
+        row's position, image id, strength and frames; `src` is left idle and zero. One launch, stream-ordered."""
+        _lib.check(self.lib.sr3_rows_move(self.ctx, int(src), int(dst)))
+
+    def rows_rows_run(self) -> int:
+        """The sum of the batch over every row-session step this engine has launched (sr3_rows_rows_run)."""
+        return int(self.lib.sr3_rows_rows_run(self.ctx))
+
+    def read_history(self, B: int, H: int, W: int) -> np.ndarray:
+        """The x0 history of the current workspace, float32 [B, C, H, W] (sr3_read_history). For tests."""
+        a = np.empty((B, self.cfg.out_channel, H, W), dtype=np.float32)
+        n = int(self.lib.sr3_read_history(self.ctx, a.ctypes.data))
+        _lib.check(min(n, 0))
+        assert n == a.size, (n, a.shape)
+        return a
 
     def rows_position(self, row: int) -> int:
         """Steps left for the slot, -1 for an idle one (sr3_rows_position)."""
@@ -1126,7 +1149,7 @@ class Engine:
             return o, fr.download((nf, B, C_, H, W))
         return o
 
-    def rows_np(self, requests, slots: int, seed: int = 0, on_step=None):
+    def rows_np(self, requests, slots: int, seed: int = 0, on_step=None, elastic: bool = False, ladder=None):
         """numpy convenience (tests): a whole row session. requests: dicts with cond [Cc,H,W], image_id, and optionally
         at (the earliest session step the request may be admitted at, default 0), init [C,H,W] with start_step and
         noised, noise [s0,C,H,W] (slab 0 the start noise / the z of q_sample, slab k the draw of step t = s0 - k) and
@@ -1135,7 +1158,16 @@ class Engine:
         its image). A request enters once `at` steps have run and a slot is
         free; finished rows retire after every step. on_step(k) runs after step k, with the session open (read-backs).
         Returns (images in request order, trace): trace[k] = the request index per slot (None: idle) during step k; the
-        entry of a request with frames is (image, frames [n,C,H,W])."""
+        entry of a request with frames is (image, frames [n,C,H,W]). elastic (batch-invariant mode): before each step
+        the live rows are compacted by rolling.elastic_plan over `ladder` (default rolling.default_ladder(slots)) and the
+        step runs at the batch it names; returns (images, trace, batches) with the batch of every step (0 for an empty
+        one), the trace taken after the moves."""
+        from .rolling import check_ladder, elastic_plan
+        if elastic:
+            if not self.batch_invariant():
+                raise ValueError("elastic=True needs the batch-invariant mode: call set_batch_invariant first")
+            ladder = check_ladder(ladder, slots)
+        batches = []
         C_ = self.cfg.out_channel
         H, W = np.asarray(requests[0]["cond"]).shape[-2:]
         self.rows_begin(slots, H, W, seed)
@@ -1180,8 +1212,17 @@ class Engine:
                 if all(h is None for h in held):    # nothing admissible yet: an empty step of the session clock
                     assert self.rows_step() == 0
                     trace.append([None] * slots)
+                    batches.append(0)
                     k += 1
                     continue
+                batch = None
+                if elastic:
+                    moves, batch = elastic_plan([h is not None for h in held], ladder)
+                    for a, b in moves:
+                        self.rows_move(a, b)
+                        held[b], pos0[b], fbufs[b] = held[a], pos0[a], fbufs[a]
+                        held[a], fbufs[a] = None, None
+                batches.append(slots if batch is None else batch)
                 ptrs = None
                 if any(h is not None and h[1] is not None for h in held):
                     ptrs = []
@@ -1190,7 +1231,7 @@ class Engine:
                         p = self.rows_position(s)
                         # slab index of step t = p - 1 in a run of pos0 steps: pos0 - t (none for t == 0)
                         ptrs.append(dn[pos0[s] - (p - 1)].ptr if dn is not None and p > 1 else None)
-                self.rows_step(ptrs)
+                self.rows_step(ptrs, batch)
                 trace.append([h[0] if h is not None else None for h in held])
                 if on_step is not None:
                     on_step(k)
@@ -1212,4 +1253,4 @@ class Engine:
                     if b is not None:
                         b.free()
             obuf.free()
-        return out, trace
+        return (out, trace, batches) if elastic else (out, trace)

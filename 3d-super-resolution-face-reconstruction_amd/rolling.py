@@ -7,7 +7,9 @@ id, conditioning, start image, start step) and of the session's slot count: its 
 uniform call of `slots` images with the same image id and seed, whatever else shared the batch and wherever it sat. The
 slot count matters because every step runs at batch `slots`, and the library's conv dispatch depends on the batch
 (against a call at another batch size an image moves by fp32 round-off in f32 / f16x3 and at the 1e-5
-level in f16f8, whose fp8 path runs only from 32 or 64 images on).
+level in f16f8, whose fp8 path runs only from 32 or 64 images on). In the batch-invariant mode that dependence is gone,
+and a session may be elastic (elastic=True): each step then runs over the slots of its live rows alone, compacted by
+one-launch moves, and an idle slot costs nothing (elastic_plan; DESIGN.md §3.5g, "live rows only").
 
 The scheduler itself touches no torch and no GPU: it drives an engine object (`Engine`'s rows_* methods, or a recording
 fake in the host tests) with device addresses it gets from `data_ptr()` of whatever the caller submits.
@@ -16,11 +18,58 @@ from __future__ import annotations
 
 import warnings
 from collections import deque
-from typing import Callable, Deque, Dict, Iterable, Iterator, List, Optional, Tuple
+from typing import Callable, Deque, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 from ._lib import Sr3Error, Sr3RangeWarning, Sr3ReplayWarning
 
 LADDER = {"f16f8": "f16x3", "f16x3": "f32"}       # one arithmetic down (the library's range policy, f32 at the bottom)
+
+# Elastic sessions (batch-invariant mode; DESIGN.md §3.5g "live rows only"): a step runs at the smallest batch of a ladder
+# that covers the live rows. The library keeps one captured graph per batch value and at most MAX_LADDER of them per form.
+BATCH_LADDER = (1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64)
+MAX_LADDER = 16
+
+
+def default_ladder(slots: int) -> Tuple[int, ...]:
+    """BATCH_LADDER within [1, slots], and slots itself"""
+    return tuple(sorted({b for b in BATCH_LADDER if b <= int(slots)} | {int(slots)}))
+
+
+def check_ladder(ladder, slots: int) -> Tuple[int, ...]:
+    """The ladder of an elastic session as a tuple (None: default_ladder): positive, increasing, ending at `slots`, at
+    most MAX_LADDER entries — anything else is a ValueError."""
+    if ladder is None:
+        return default_ladder(slots)
+    lad = tuple(int(b) for b in ladder)
+    if not lad or lad[0] < 1 or any(b <= a for a, b in zip(lad, lad[1:])):
+        raise ValueError(f"ladder must be a non-empty increasing sequence of positive batch sizes, got {list(ladder)}")
+    if lad[-1] != int(slots):
+        raise ValueError(f"ladder must end at the session's slot count {slots}, got {list(ladder)}")
+    if len(lad) > MAX_LADDER:
+        raise ValueError(f"ladder may hold at most {MAX_LADDER} batch sizes (one captured graph each), got {len(lad)}")
+    return lad
+
+
+def elastic_plan(occupied: Sequence[bool], ladder: Sequence[int]) -> Tuple[List[Tuple[int, int]], int]:
+    """The policy of an elastic step. occupied[s]: slot s holds a live row. With L live rows and b the smallest ladder
+    entry >= L: while a live row sits at a slot >= b, the highest live row moves to the lowest free slot. Returns
+    (moves as (src, dst) in order, the batch of the step: the smallest ladder entry >= highest live slot + 1 after the
+    moves). Moves happen only where they lower the batch: every one takes a row from at or above b to below it, and a
+    session whose rows already sit below b — a full one among them — records none."""
+    occ = [bool(o) for o in occupied]
+    live = sum(occ)
+    if not live:
+        return [], ladder[0]
+    b = next(x for x in ladder if x >= live)
+    moves = []
+    while True:
+        hi = max(s for s, o in enumerate(occ) if o)
+        if hi < b:
+            break
+        lo = occ.index(False)       # (below b: fewer than b rows are live below it while one sits at or above it)
+        moves.append((hi, lo))
+        occ[hi], occ[lo] = False, True
+    return moves, next(x for x in ladder if x >= hi + 1)
 
 
 class _Request:
@@ -58,15 +107,34 @@ class RollingSampler:
     image and writes its frames again from the first.
 
     `trace` records one entry per step: (live rows, requests still queued, whether the stream's source is exhausted).
+
+    elastic=True (a model in batch-invariant mode only: ValueError otherwise): a step runs over the live rows' slots
+    alone. After retiring and filling, before each step, elastic_plan compacts the live rows below the smallest entry of
+    `ladder` (default default_ladder(slots)) that holds them — Engine.rows_move, one launch each, only where it lowers
+    the batch — and the step runs at the smallest entry that covers the highest live slot. In that mode a row's bytes do
+    not depend on the batch of the launch, so every request is still its B = 1 call. `batch_trace` records the batch
+    of every step, `moves` counts the moves. elastic=False: every step runs all slots, as it always did.
     """
 
     def __init__(self, engine, slots: int, steps: int, seed: int = 0, precision: str = "f32", strict: bool = False,
                  start_steps: Optional[Callable] = None, alloc: Optional[Callable] = None,
                  ready: Optional[Callable] = None, finish: Optional[Callable] = None,
                  lr_size: Optional[Tuple[int, int]] = None, to_lr: Optional[Callable] = None,
-                 alloc_frames: Optional[Callable] = None, deliver: Optional[Callable] = None):
+                 alloc_frames: Optional[Callable] = None, deliver: Optional[Callable] = None,
+                 elastic: bool = False, ladder: Optional[Sequence[int]] = None):
         if int(slots) < 1:
             raise ValueError(f"slots must be >= 1, got {slots}")
+        self.elastic = bool(elastic)
+        if self.elastic:
+            mode = getattr(engine, "batch_invariant", None)
+            if not (mode() if callable(mode) else mode):
+                raise ValueError("elastic=True needs the batch-invariant mode: a step over fewer rows than the session has "
+                                 "slots keeps a row's bytes only there — call set_batch_invariant() on the model first")
+            self.ladder = check_ladder(ladder, slots)
+        elif ladder is not None:
+            raise ValueError("a ladder belongs to an elastic session: pass elastic=True")
+        else:
+            self.ladder = (int(slots),)
         self.eng, self.slots, self.S, self.seed = engine, int(slots), int(steps), int(seed)
         self.precision, self._precision0, self.strict = precision, precision, bool(strict)
         self._start_steps = start_steps or (lambda S, strength: max(1, min(S, int(round(float(strength) * S)))))
@@ -92,6 +160,8 @@ class RollingSampler:
         self.replays = 0
         self.steps_run = 0
         self.trace: List[Tuple[int, int, bool]] = []
+        self.batch_trace: List[int] = []
+        self.moves = 0
 
     # ---- requests ---------------------------------------------------------------------------------------
     def submit(self, x_in_row, init=None, strength=None, image_id: Optional[int] = None, lr=None, lr_strength: float = 1.0,
@@ -196,7 +266,18 @@ class RollingSampler:
         if not self.in_flight:
             return 0
         self.trace.append((self.in_flight, len(self._queue), self._source_done))
-        n = self.eng.rows_step()
+        if self.elastic:
+            moves, batch = elastic_plan([r is not None for r in self._rows], self.ladder)
+            for a, b in moves:
+                self.eng.rows_move(a, b)
+                self._rows[b], self._left[b] = self._rows[a], self._left[a]
+                self._rows[a], self._left[a] = None, 0
+            self.moves += len(moves)
+            n = self.eng.rows_step(None, batch)
+        else:
+            batch = self.slots
+            n = self.eng.rows_step()
+        self.batch_trace.append(batch)
         self.steps_run += 1
         for s, r in enumerate(self._rows):
             if r is None:

@@ -303,6 +303,29 @@ int sr3_num_frames_from(sr3_ctx *ctx, int start_step);
  *   sr3_rows_drop      frees a slot at any point, nothing copied; the state of a live row goes back to zeros (it may hold
  *                      anything mid-trajectory, and an idle row still runs through the UNet).
  *   sr3_rows_end       closes the session.
+ * Elastic steps (batch-invariant mode only, sr3_set_batch_invariant; DESIGN.md 3.5g "live rows only"): in that mode a
+ * row's bytes do not depend on how many rows a launch covers, nor does what the workspace holds per image, so a step may
+ * run over rows [0, batch) of the session's workspace alone and cost what `batch` images cost.
+ *   sr3_rows_step_batch  sr3_rows_step over slots [0, batch): embedding, UNet and every launch of the update run for
+ *                      `batch` rows; slots at or above `batch` are neither read nor written (state, packed copy, history,
+ *                      their slab of the x0 prediction, LR image, frames). batch == B is sr3_rows_step itself: the same
+ *                      key, graph and launches. Fails, launching nothing and leaving every position where it was, when
+ *                      batch lies outside [1, B], when a live row with steps left sits at a slot >= batch (named), and
+ *                      when batch < B with the batch-invariant mode off (the workspace was sized by plans that follow B: a
+ *                      smaller batch may take more split-K partials than it holds; the message names
+ *                      sr3_set_batch_invariant). Before the first launch at a new `batch` the host checks that what the
+ *                      plans at `batch` ask of the shared buffers fits what was carved for B (an "internal:" error
+ *                      otherwise; cached per value). One captured graph per (rows form, batch value), at most 16 batch
+ *                      values per form (the least recently used one is evicted). noise_rows has B entries as before.
+ *   sr3_rows_move      moves live slot `src` into idle slot `dst` (anything else is an error): state slab with borders and
+ *                      pad channels, packed split-f16 slab, x0 history slab, in an armed session the slot's LR image, and
+ *                      the host's record of the row (position, start, image id, history flags, strength, frames). `src`
+ *                      is left as sr3_rows_drop leaves it (zero state, zero packed copy, idle). One kernel launch behind
+ *                      the steps already enqueued, no host synchronisation. The row's Philox streams are keyed by its
+ *                      image id and do not change; injected noise must follow the row (entry `dst` of noise_rows).
+ *   sr3_rows_rows_run  the sum of `batch` over the row-session steps this context has launched (sr3_rows_step counts B).
+ *   sr3_read_history   the x0 history of the current workspace, B * out_channel * H * W floats NCHW, to host memory;
+ *                      returns that count, < 0 on error. Synchronises the context's stream. (tests)
  * Range contract: the step API's. Nothing is replayed inside the library; sr3_range_check reports an activation beyond
  * the operand range since the last check (the caller re-admits what was in flight, its requests being pure functions of
  * seed, image id and init), and sr3_set_precision is allowed between steps. sr3_sample* and sr3_unet_forward during a
@@ -319,6 +342,10 @@ int sr3_rows_position(sr3_ctx *ctx, int row);
 int sr3_rows_retire(sr3_ctx *ctx, int row, float *out_dev);
 int sr3_rows_drop(sr3_ctx *ctx, int row);
 int sr3_rows_end(sr3_ctx *ctx);
+int sr3_rows_step_batch(sr3_ctx *ctx, const float *const *noise_rows, int batch);
+int sr3_rows_move(sr3_ctx *ctx, int src, int dst);
+uint64_t sr3_rows_rows_run(sr3_ctx *ctx);
+int64_t sr3_read_history(sr3_ctx *ctx, float *hist_host);
 /* Range check of the split-f16 arithmetic (sr3_set_precision(ctx, 1)): the reference computes in
  * fp32 (diffusion.py:164-180, unet.py:235-265) and has no such limit, so a value that does not fit
  * the hi + lo fp16 operand format (|v| > 65504, or a NaN) must never pass silently. Every kernel that stores
