@@ -134,6 +134,9 @@ PROTOTYPES = {
     "sr3_op_conv2d_fused": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _I, _F, _F, _F, _I, _F, _I, _F, _F, _I, _F, _F,
                                 _F, _U64, C.POINTER(_I)]),
     "sr3_op_conv_in": (_I, [_P, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _F, _U64, C.POINTER(_I), _P]),
+    "sr3_op_conv_in_f32": (_I, [_P, _F, _I, _I, _I, _I, _F, _F, _I, _F, _F, _U64, C.POINTER(_I)]),
+    "sr3_conv_in_f32_gate": (_I, [_I] * 5),
+    "sr3_conv_in_f32_launches": (_I, [_P]),
     "sr3_op_final_conv": (_I, [_P, _F, _I, _I, _I, _I, _F, _F, _F, _F, _I, _F, C.POINTER(_I)]),
     "sr3_read_packed_state": (C.c_int64, [_P, _F, _P, C.POINTER(_I)]),
     "sr3_op_groupnorm_affine": (_I, [_P, _F, _I, _F, _I, _I, _I, _I, _I, _F, _F, _F, _F]),
@@ -181,7 +184,8 @@ NEWER_COUNTERS = ("sr3_gn_wino_passes", "sr3_wino_gemm_out_launches", "sr3_up2_w
                   "sr3_rows_begin", "sr3_rows_admit", "sr3_rows_step", "sr3_rows_position", "sr3_rows_retire", "sr3_rows_drop",
                   "sr3_rows_end", "sr3_op_conv2d_fused", "sr3_op_attention_twin", "sr3_gn_res1x1_launches", "sr3_gn_res1x1_gate",
                   "sr3_op_gn_res1x1", "sr3_bench_gn_res1x1", "sr3_rows_lr_consistency", "sr3_rows_admit_lr", "sr3_rows_frames",
-                  "sr3_op_lr_project_rows", "sr3_rows_step_batch", "sr3_rows_move", "sr3_rows_rows_run", "sr3_read_history")
+                  "sr3_op_lr_project_rows", "sr3_rows_step_batch", "sr3_rows_move", "sr3_rows_rows_run", "sr3_read_history",
+                  "sr3_op_conv_in_f32", "sr3_conv_in_f32_gate", "sr3_conv_in_f32_launches")
 
 _lib = None
 

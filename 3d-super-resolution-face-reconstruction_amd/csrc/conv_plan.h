@@ -10,7 +10,7 @@ namespace sr3 {
 enum Switch {
     SW_NO_GRAPH, SW_NO_HALO, SW_HALO_SPLITS, SW_NO_INPLACE_SPLIT, SW_NO_WINOGRAD, SW_NO_GN_WINO,
     SW_NO_WINO_GEMM_OUT, SW_WINO_GEMM_OUT_FORCE, SW_NO_WINO_FUSED_ROWS, SW_WINO_FUSED_ROWS_FORCE,
-    SW_NO_UP2_WINO, SW_UP2_WINO_FORCE, SW_NO_GN_RES1X1, SW_GN_RES1X1_FORCE,
+    SW_NO_UP2_WINO, SW_UP2_WINO_FORCE, SW_NO_GN_RES1X1, SW_GN_RES1X1_FORCE, SW_NO_CONV_IN_F32,
     SW_COUNT
 };
 // the variable's value (its default when unset): read from the environment on the FIRST call for this switch, then kept
@@ -21,6 +21,9 @@ int env_switch_now(Switch s);
 enum Form { FORM_WINO_GEMM_OUT, FORM_WINO_FUSED_ROWS, FORM_UP2_WINO, FORM_GN_RES1X1 };
 struct FormSwitch { bool off, force; };
 FormSwitch form_switch(Form f);
+// the first conv of the exact-f32 UNet on its own kernel (run_unet_body's M_CONV_IN, sr3_op_conv_in_f32, sr3_conv_in_f32_gate):
+// a form without a tuned gate, so SR3_NO_CONV_IN_F32 has no _FORCE twin
+bool conv_in_f32_gate(bool split_arith, int Cin, int Cout, int H, int W);
 inline bool gn_wino_off() { return env_switch(SW_NO_GN_WINO) != 0; }
 
 // ---- what launch_conv / launch_wino_gemm share with the plan --------------------------------------------------------

@@ -9,7 +9,7 @@
 namespace sr3 {
 
 // ---- environment switches: ONE table ----------------------------------------------------------------------------------
-// (SR3_THRESHOLD_BLOCKS, the fifteenth, is read by kernels_threshold.hip where it plans a selection)
+// (SR3_THRESHOLD_BLOCKS, the sixteenth, is read by kernels_threshold.hip where it plans a selection)
 namespace {
 struct SwitchDef { const char *name; int dflt; };
 const SwitchDef kSwitches[SW_COUNT] = {
@@ -27,6 +27,7 @@ const SwitchDef kSwitches[SW_COUNT] = {
     /* SW_UP2_WINO_FORCE */ {"SR3_UP2_WINO_FORCE", 0},
     /* SW_NO_GN_RES1X1 */ {"SR3_NO_GN_RES1X1", 0},
     /* SW_GN_RES1X1_FORCE */ {"SR3_GN_RES1X1_FORCE", 0},
+    /* SW_NO_CONV_IN_F32 */ {"SR3_NO_CONV_IN_F32", 0},
 };
 } // namespace
 
@@ -43,6 +44,12 @@ FormSwitch form_switch(Form f) {
     static const Switch pair[][2] = {{SW_NO_WINO_GEMM_OUT, SW_WINO_GEMM_OUT_FORCE}, {SW_NO_WINO_FUSED_ROWS, SW_WINO_FUSED_ROWS_FORCE},
                                      {SW_NO_UP2_WINO, SW_UP2_WINO_FORCE}, {SW_NO_GN_RES1X1, SW_GN_RES1X1_FORCE}};
     return {env_switch(pair[f][0]) != 0, env_switch(pair[f][1]) != 0};
+}
+
+// downs.0 on conv_in_f32_kernel (kernels_edge.hip) instead of the generic kernel: the exact-f32 arithmetic, a shape of
+// conv_in_supported, SR3_NO_CONV_IN_F32 unset. Asks nothing of B (the same answer in the batch-invariant mode)
+bool conv_in_f32_gate(bool split_arith, int Cin, int Cout, int H, int W) {
+    return !split_arith && conv_in_supported(Cin, Cout, H, W) && env_switch(SW_NO_CONV_IN_F32) == 0;
 }
 
 // ---- batch-invariant mode: the planning batch of the calling thread ----------------------------------

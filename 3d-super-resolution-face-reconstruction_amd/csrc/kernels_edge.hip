@@ -558,6 +558,147 @@ __global__ void pack_state_kernel(const TDesc x, _Float16 *__restrict__ xp, int 
     if (ovf != nullptr && absmax > SPLIT_F16_MAX) *ovf = 1;
 }
 
+// -------------------------------------------------------------------------------------------------
+// downs.0 in the exact-f32 arithmetic, on the fp32 state tensor itself.
+//   x    [B][H+2][W+2][x.C] fp32, zero border, channels >= in_channel zero: channels 0..7 of a pixel are read
+//        (32 contiguous bytes), nothing else of it
+//   w    the parameter's packed copy [tap 9][Cout][wld] (pack_conv_weight; input channels >= Cin zero)
+// v_mfma_f32_16x16x4_f32 (A[row l16][k q], B[k q][col l16]): k-step (tap t = 3 dy + dx, j in {0, 1}) takes input
+// channel 2q + j from lane quarter q, so a lane loads ONE float2 (channels 2q, 2q + 1) per tap and M-tile and per
+// tap and N-tile. K = 72 in 18 k-steps; an output adds its products in the FIXED order
+//   dy 0..2 > dx 0..2 > j 0..1 > q 0..3 (inside one MFMA), i.e. per tap the channels 0 2 4 6 1 3 5 7,
+// whatever B and the grid are (no atomics, no split of K).
+// Block = 4 waves x 64 consecutive pixels (4 M-tiles of 16) = 256 pixels of one image, persistent; the B fragments
+// (18 x NT floats per lane) are fetched once per wave. A fragments are direct global loads, pixel
+// x0 + l16 + dx - 1 of row y + dy - 1: 36 8-byte loads per lane against 72 NT MFMAs of 32 cycles per 64 pixels,
+// and the nine taps of a pixel hit the same 32 bytes (L1 / L2), so an LDS stage of the window rows has no
+// load time to save here.
+// Epilogue in the direct kernel's order: bias, fp32 store (through a per-wave LDS transpose: 16 bytes per
+// lane, 256-byte runs per pixel), fused GroupNorm statistics of the stored values (one slice per block).
+// -------------------------------------------------------------------------------------------------
+template <int NT>
+__global__ __launch_bounds__(256, 2) void conv_in_f32_kernel(const TDesc x, const float *__restrict__ w, const int wld,
+                                                             const float *__restrict__ bias, const TDesc out,
+                                                             double *__restrict__ stats, const int stats_slices,
+                                                             const int nblocks) {
+    constexpr int MT = 4;
+    constexpr int Cout = NT * 16;
+    constexpr int TLD = Cout + 4;                        // floats per staged pixel row (+4: bank spread, 16-B aligned)
+    __shared__ double2 red[16][Cout];
+    __shared__ __attribute__((aligned(16))) float tstage[4 * 16 * TLD];
+    const int H = out.H, W = out.W, Hp = H + 2, Wp = W + 2, HW = H * W, C = x.C;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l16 = lane & 15, q = lane >> 4;
+    // resident weight fragments: (tap, N-tile) -> input channels 2q, 2q + 1 of output channel nt*16 + l16
+    float2 bw[9][NT];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+            bw[t][nt] = *reinterpret_cast<const float2 *>(w + ((size_t)t * Cout + nt * 16 + l16) * wld + 2 * q);
+    float bs[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) bs[nt] = bias ? bias[nt * 16 + l16] : 0.f;
+    for (int blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+    const int pix0 = blk * 256 + wave * 64;                 // first pixel (n*HW + y*W + x) of this wave
+    const int n = pix0 / HW;
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[mt][nt][r] = 0.f;
+    int ty[MT], tx[MT];                                      // tile origin (row, first column)
+    const float *ap[MT];                                     // this lane's float2 of padded pixel (ty, tx + l16)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int rem = pix0 + mt * 16 - n * HW;
+        ty[mt] = rem / W;
+        tx[mt] = rem - ty[mt] * W;
+        ap[mt] = x.p + (((size_t)n * Hp + ty[mt]) * Wp + tx[mt] + l16) * C + 2 * q;
+    }
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        // padded coordinates of pixel (ty - 1 + dy, tx + l16 - 1 + dx) are (ty + dy, tx + l16 + dx)
+        float2 a[3][MT];
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+                a[dx][mt] = *reinterpret_cast<const float2 *>(ap[mt] + ((size_t)dy * Wp + dx) * C);
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[dx][mt].x, bw[dy * 3 + dx][nt].x, acc[mt][nt], 0, 0, 0);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[dx][mt].y, bw[dy * 3 + dx][nt].y, acc[mt][nt], 0, 0, 0);
+        }
+    }
+    // ---- epilogue: C/D map col = l16 (+ 16 nt), row = 4 q + j ----
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[mt][nt][j] += bs[nt];
+    {
+        // the accumulator layout gives a lane 4 pixels x 1 channel; staged as [pixel][channel] a lane owns 4 consecutive
+        // channels of a pixel and 16 lanes store the pixel's whole channel run
+        float *T = tstage + wave * (16 * TLD);
+        constexpr int QPP = NT * 4;               // 16-byte pieces per pixel
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {         // one 16-pixel M-tile at a time
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) T[(4 * q + j) * TLD + nt * 16 + l16] = acc[mt][nt][j];
+            // a wave only reads what it wrote itself: no block barrier, just its own LDS writes completed
+            __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
+            float *orow = out.p + out.pix(n, ty[mt], tx[mt]) * Cout;
+#pragma unroll
+            for (int k = 0; k < NT; ++k) {        // 16 * QPP pieces over 64 lanes
+                const int item = lane + 64 * k;
+                const int px = item / QPP, pc = item - px * QPP;
+                *reinterpret_cast<f32x4 *>(orow + (size_t)px * Cout + pc * 4) = *reinterpret_cast<const f32x4 *>(T + px * TLD + pc * 4);
+            }
+            __builtin_amdgcn_s_waitcnt(0xc07f);   // the reads are done before the next M-tile overwrites T
+        }
+    }
+    if (stats != nullptr) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            double st1 = 0.0, st2 = 0.0;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double v = (double)acc[mt][nt][j];
+                    st1 += v;
+                    st2 = fma(v, v, st2);
+                }
+            red[wave * 4 + q][nt * 16 + l16] = make_double2(st1, st2);
+        }
+        __syncthreads();
+        if (threadIdx.x < Cout) {
+            double a = 0, b = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { const double2 v = red[i][threadIdx.x]; a += v.x; b += v.y; }
+            const int slice = (blk * 256 - n * HW) / 256;
+            double *o = stats + (((size_t)n * stats_slices + slice) * Cout + threadIdx.x) * 2;
+            o[0] = a; o[1] = b;
+        }
+        __syncthreads();        // red[] is reused by the next block of pixels
+    }
+    }
+}
+
 } // namespace
 
 bool conv_in_supported(int Cin, int Cout, int H, int W) {
@@ -607,6 +748,16 @@ void launch_conv_in(const float *xp, const float *wci, const float *bias, float 
     default: SR3_CI(4); break;
     }
 #undef SR3_CI
+}
+
+void launch_conv_in_f32(const TDesc &x, const float *w, int w_cin_pad, const float *bias, int B, const TDesc &out,
+                        double *stats, int stats_slices, hipStream_t s) {
+    const int blocks = B * out.H * out.W / 256;
+    const int grid = blocks < CONV_IN_F32_GRID ? blocks : CONV_IN_F32_GRID;
+    if (out.C == 32)
+        hipLaunchKernelGGL(conv_in_f32_kernel<2>, dim3(grid), dim3(256), 0, s, x, w, w_cin_pad, bias, out, stats, stats_slices, blocks);
+    else
+        hipLaunchKernelGGL(conv_in_f32_kernel<4>, dim3(grid), dim3(256), 0, s, x, w, w_cin_pad, bias, out, stats, stats_slices, blocks);
 }
 
 } // namespace sr3

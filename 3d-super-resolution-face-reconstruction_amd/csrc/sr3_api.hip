@@ -209,7 +209,8 @@ struct sr3_ctx {
     int gn_wino_passes = 0;             // GroupNorm apply passes launched as launch_gn_wino_input / _fold_ since sr3_create
     int up2_wino_launches = 0;          // Upsample convs launched on wino_up2_kernel (ConvPlan::up2_wino) since sr3_create
     int wino_fused_rows_launches = 0;   // three-pass Winograd convs launched on the one-pass kernel's tile-row form (ConvPlan::wino_fused_rows) since sr3_create
-    int wino_gemm_out_launches = 0;     // three-pass Winograd convs launched in the one-kernel form (ConvPlan::wino_gemm_out) since sr3_create
+    int conv_in_f32_launches = 0;       // forwards whose first conv ran on conv_in_f32_kernel (conv_in_f32_gate) since sr3_create
+    int wino_gemm_out_launches = 0;    // three-pass Winograd convs launched in the one-kernel form (ConvPlan::wino_gemm_out) since sr3_create
     int gn_res1x1_launches = 0;         // block1 apply passes launched together with the block's 1x1 res_conv (launch_gn_res1x1) since sr3_create
     float *ckpt = nullptr;              // sr3_sample: NCHW copy of the sampler state at the last clean checkpoint
     size_t ckpt_floats = 0;
@@ -1293,6 +1294,20 @@ void run_unet_body(sr3_ctx *c, int B, int H, int W, int depth = 0) {
                 c->pend();
                 k.in = c->x0s; k.activated = true; k.out_f32 = !(so_mode && m.out_s.p);
                 run_conv(c, k);
+            } else if (conv_in_f32_gate(c->split(), c->cfg.in_channel, m.conv.cout, H, W) && cur.pad == 1 && cur.C >= 8 &&
+                       (!m.st_out.p || H * W / 256 <= m.slices_default)) {
+                // downs.0 in exact f32 on the state tensor itself (kernels_edge.hip): 72 k-values per output instead of
+                // the generic kernel's 9 K-steps of 32 mostly-zero channels; weights: the parameter's packed copy
+                if (m.st_out.p) m.st_out.slices = H * W / 256;       // one statistics slice per 256-pixel block
+                c->pbegin(F_CONV);
+                launch_conv_in_f32(cur, c->params[m.conv.w].dev, m.conv.cin_pad, m.conv.b >= 0 ? c->params[m.conv.b].dev : nullptr,
+                                   B, m.out, const_cast<double *>(m.st_out.p), m.st_out.slices, c->stream);
+                ++c->conv_in_f32_launches;
+                if (c->prof) {
+                    char tag[160];
+                    snprintf(tag, sizeof tag, "conv_in k3 %dx%d cin%d cout%d f32 mfma", H, W, m.conv.cin, m.conv.cout);
+                    c->pend(2.0 * (double)B * H * W * m.conv.cout * 9.0 * m.conv.cin, tag);
+                }
             } else {
                 k.in = cur;
                 run_conv(c, k);
@@ -3547,6 +3562,10 @@ int sr3_set_range_policy(sr3_ctx *c, int strict) {
 int sr3_fallback_calls(sr3_ctx *c) { return c ? c->fallback_calls : fail("null context"); }
 int sr3_gn_wino_passes(sr3_ctx *c) { return c ? c->gn_wino_passes : fail("null context"); }
 int sr3_wino_gemm_out_launches(sr3_ctx *c) { return c ? c->wino_gemm_out_launches : fail("null context"); }
+int sr3_conv_in_f32_launches(sr3_ctx *c) { return c ? c->conv_in_f32_launches : fail("null context"); }
+int sr3_conv_in_f32_gate(int Cin, int Cout, int H, int W, int precision) {
+    return conv_in_f32_gate(precision != 0, Cin, Cout, H, W) ? 1 : 0;
+}
 int sr3_step_graph_captures(sr3_ctx *c) { return c ? c->step_graph_captures : fail("null context"); }
 int sr3_up2_wino_launches(sr3_ctx *c) { return c ? c->up2_wino_launches : fail("null context"); }
 int sr3_dynamic_threshold_launches(sr3_ctx *c) { return c ? c->dyn_steps : fail("null context"); }
@@ -3869,6 +3888,53 @@ int sr3_op_conv_in(sr3_ctx *c, const float *state_nchw_dev, int B, int H, int W,
     if (rc < 0) return rc;
     if (packed_host) HIP_OK(hipMemcpy(packed_host, xp.p, npix * 16 * sizeof(_Float16), hipMemcpyDeviceToHost));
     return rc;
+}
+
+int sr3_op_conv_in_f32(sr3_ctx *c, const float *state_nchw_dev, int B, int H, int W, int Cin, const float *weight_host,
+                       const float *bias_host, int Cout, float *out_dev, double *stats_dev, uint64_t stats_capacity_doubles,
+                       int *slices_out) {
+    PlanScope plan_scope(c);
+    const char *what = "sr3_op_conv_in_f32";
+    if (!c || !state_nchw_dev || !weight_host || !out_dev) return fail("%s: null argument", what);
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return fail("%s: bad shape", what);
+    // run_unet_body's gate (M_CONV_IN): conv_in_f32_gate, its three terms named one by one
+    if (c->split())
+        return fail("%s: the f32 first-conv kernel runs in the exact-f32 arithmetic only (sr3_set_precision 0)", what);
+    if (!conv_in_supported(Cin, Cout, H, W))
+        return fail("%s: Cin=%d Cout=%d H=%d W=%d is no shape of the f32 first-conv kernel (Cin <= 8, Cout 32 | 64, W %% 16 == 0, "
+                    "H*W %% 256 == 0)", what, Cin, Cout, H, W);
+    if (!conv_in_f32_gate(false, Cin, Cout, H, W)) return fail("%s: switched off (SR3_NO_CONV_IN_F32=1)", what);
+    if ((uint64_t)B * H * W >= (1ull << 31)) return fail("%s: B*H*W must stay under 2^31 pixels", what);
+    const int slices = H * W / 256;
+    if (stats_dev) {
+        const uint64_t need = (uint64_t)B * slices * Cout * 2;
+        if (stats_capacity_doubles < need)
+            return fail("%s: the statistics take %llu doubles ([B][%d slices][Cout][2]), the buffer holds %llu", what,
+                        (unsigned long long)need, slices, (unsigned long long)stats_capacity_doubles);
+    }
+    if (slices_out) *slices_out = slices;
+    HIP_OK(hipSetDevice(c->device));
+    // the workspace's x0 (ensure_workspace): zero-bordered fp32 state of in_pad channels; the weights as alloc_weights
+    // keeps them ([tap][Cout][cin_pad], pack_conv_weight)
+    const int cin_pad = round_up(Cin, 32);
+    TDesc x0; x0.C = cin_pad; x0.H = H; x0.W = W; x0.pad = 1;
+    DevBuf state, wdev, bias;
+    if (state.alloc(x0.floats(B))) return -1;
+    x0.p = state.p;
+    std::vector<float> wf((size_t)9 * Cout * cin_pad);
+    pack_conv_weight(weight_host, Cout, Cin, 3, cin_pad, wf.data());
+    if (wdev.upload(wf.data(), wf.size())) return -1;
+    if (bias_host && bias.upload(bias_host, (size_t)Cout)) return -1;
+    const TDesc out = unpadded(out_dev, Cout, H, W);
+    return guarded_eval(c, what, "the conv", false, [&]() -> int {
+        HIP_OK(hipMemsetAsync(state.p, 0, x0.floats(B) * sizeof(float), c->stream));
+        if (stats_dev) HIP_OK(hipMemsetAsync(stats_dev, 0xFF, stats_capacity_doubles * sizeof(double), c->stream));
+        launch_nchw_to_nhwc(state_nchw_dev, B, Cin, x0, 0, c->stream);
+        launch_conv_in_f32(x0, wdev.p, cin_pad, bias.p, B, out, stats_dev, slices, c->stream);
+        ++c->conv_in_f32_launches;
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail("%s: launch failed", what);
+        return 0;
+    });
 }
 
 int sr3_op_final_conv(sr3_ctx *c, const float *in_dev, int B, int H, int W, int C, const float *gn_scale_dev,

@@ -35,6 +35,9 @@ namespace sr3 {
 //                           two launches (the library before gn_res1x1_kernel; same bits)
 //   SR3_GN_RES1X1_FORCE=1   that kernel wherever its preconditions hold, whatever the level and block count (tests,
 //                           per-shape timing)
+//   SR3_NO_CONV_IN_F32=1    the exact-f32 first conv always on the generic implicit-GEMM kernel over the 32 padded input
+//                           channels (the launch of the library before conv_in_f32_kernel; another summation order,
+//                           so not the same bits). No _FORCE twin: the form has no tuned gate
 //   SR3_THRESHOLD_BLOCKS=N  blocks that share one image in the selection of the dynamic threshold instead of one per
 //                           16384 keys (per-shape timing; same bits); read where kernels_threshold.hip plans a selection
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
@@ -695,6 +698,13 @@ size_t conv_in_weight_floats(int Cout);
 void launch_pack_state(const TDesc &x, int B, float *xp, hipStream_t s, int *ovf);
 void launch_conv_in(const float *xp, const float *wci, const float *bias, float w_unscale, int B, const TDesc &out,
                     const TDesc &out_split, int out_f32, double *stats, int stats_slices, int *ovf, hipStream_t s);
+// downs.0 in the exact-f32 arithmetic (conv_in_f32_kernel; the shapes of conv_in_supported): x = the fp32 state tensor
+// itself (zero border of 1 pixel, x.C >= 8 channels per pixel, those >= Cin zero), w = the parameter's packed copy
+// [tap][Cout][w_cin_pad] (pack_conv_weight), out.C = Cout; stats (optional): one slice per 256 pixels, stats_slices = H*W/256.
+// A persistent grid of at most CONV_IN_F32_GRID blocks (2 resident blocks of 4 waves per CU)
+constexpr int CONV_IN_F32_GRID = 512;
+void launch_conv_in_f32(const TDesc &x, const float *w, int w_cin_pad, const float *bias, int B, const TDesc &out,
+                        double *stats, int stats_slices, hipStream_t s);
 
 // ---- pre-processing: PIL-exact 8-bit bicubic resize -> sampler input tensor (kernels_pre.hip) ----
 } // namespace sr3

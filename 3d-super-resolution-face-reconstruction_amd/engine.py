@@ -215,6 +215,11 @@ class Engine:
         and the output transform in one kernel; 0 under SR3_NO_WINO_GEMM_OUT=1 and outside the f32 mode."""
         return int(self.lib.sr3_wino_gemm_out_launches(self.ctx))
 
+    def conv_in_f32_launches(self) -> int:
+        """Forwards this engine launched (or captured into a graph; op_conv_in_f32 calls included) whose first conv ran on
+        conv_in_f32_kernel; 0 under SR3_NO_CONV_IN_F32=1 and outside the f32 mode."""
+        return int(self.lib.sr3_conv_in_f32_launches(self.ctx))
+
     def up2_wino_launches(self) -> int:
         """Upsample convs this engine launched (or captured into a graph) as sub-pixel Winograd F(2x2, 2x2); 0 under
         SR3_NO_UP2_WINO=1 and outside the f32 mode."""
@@ -951,6 +956,33 @@ class Engine:
                 "twin": twin.download().view(np.uint16).reshape(B, H, W, Cout // 32, 2, 32) if twin else None,
                 "stats": st.download().view(np.float64).reshape(B, got.value, Cout, 2) if st else None,
                 "packed": packed}
+
+    def op_conv_in_f32(self, state, weight, bias=None, want_stats=True, stats_slots=None) -> dict:
+        """The UNet's first conv as the exact-f32 forward runs it (sr3_op_conv_in_f32, conv_in_f32_kernel): state
+        [B, H, W, Cin <= 8] fp32, weight OIHW [Cout, Cin, 3, 3]. Returns a dict: out (float32 [B, H, W, Cout]), stats
+        (float64 [B, H*W // 256, Cout, 2]; None when switched off), slices (H*W // 256) and stats_raw (the whole statistics
+        buffer as float64, stats_slots >= B * slices * Cout * 2 doubles when given: what lies behind the slices keeps the
+        0xFF fill, NaN)."""
+        state = _host_f32(state)
+        B, H, W, Cin = state.shape
+        weight = _host_f32(weight)
+        Cout = weight.shape[0]
+        assert weight.shape == (Cout, Cin, 3, 3), weight.shape
+        d = self.to_device(state.transpose(0, 3, 1, 2))
+        bh = _host_f32(bias) if bias is not None else None
+        out = self.buffer(B * H * W * Cout)
+        need = B * max(1, H * W // 256) * Cout * 2
+        cap = need if stats_slots is None else int(stats_slots)
+        st = self.buffer(cap * 2) if want_stats else None
+        got = C.c_int(-1)
+        _lib.check(self.lib.sr3_op_conv_in_f32(
+            self.ctx, d.ptr, B, H, W, Cin, weight.ctypes.data, bh.ctypes.data if bh is not None else None, Cout,
+            out.ptr, st.ptr if st else None, cap, C.byref(got)))
+        assert got.value == H * W // 256, got.value
+        raw = st.download().view(np.float64) if st else None
+        return {"out": out.download((B, H, W, Cout)),
+                "stats": raw[:B * got.value * Cout * 2].reshape(B, got.value, Cout, 2) if st else None,
+                "slices": got.value, "stats_raw": raw}
 
     def op_final_conv(self, x, gn_scale, gn_shift, weight, bias, return_form=False):
         """The UNet's last layer as the forward runs it (sr3_op_final_conv): swish(x * gn_scale + gn_shift), zero padding,

@@ -379,6 +379,9 @@ int sr3_gn_wino_passes(sr3_ctx *ctx);
 /* Three-pass Winograd convs this context launched (or captured into a graph) since sr3_create in the form that runs the position GEMMs
  * and the output transform in one kernel (0 under SR3_NO_WINO_GEMM_OUT=1): tells a test which form ran. */
 int sr3_wino_gemm_out_launches(sr3_ctx *ctx);
+/* Forwards of this context (launched or captured into a graph, sr3_op_conv_in_f32 calls included) since sr3_create whose
+ * first conv ran on conv_in_f32_kernel (exact f32 only; 0 under SR3_NO_CONV_IN_F32=1): tells a test which kernel ran. */
+int sr3_conv_in_f32_launches(sr3_ctx *ctx);
 /* Upsample convs this context launched (or captured into a graph) since sr3_create as sub-pixel Winograd F(2x2, 2x2)
  * (wino_up2_kernel; exact f32 only; 0 under SR3_NO_UP2_WINO=1): tells a test which form ran. */
 int sr3_up2_wino_launches(sr3_ctx *ctx);
@@ -544,6 +547,22 @@ int sr3_op_conv2d_fused(sr3_ctx *ctx, const float *in0_dev, int C0, const float 
 int sr3_op_conv_in(sr3_ctx *ctx, const float *state_nchw_dev, int B, int H, int W, int Cin, const float *weight_host,
                    const float *bias_host, int Cout, float *out_dev, float *twin_dev, double *stats_dev,
                    uint64_t stats_capacity_doubles, int *slices_out, void *packed_host);
+/* The same conv as the exact-f32 forward runs it: the zero-bordered fp32 state of 32 channels per pixel is built from
+ * state_nchw_dev [B, Cin, H, W] as sr3_unet_forward builds it and convolved by conv_in_f32_kernel (fp32 operands on
+ * v_mfma_f32_16x16x4_f32, 72 k-values per output) with weight_host (OIHW [Cout, Cin, 3, 3]) in the packed layout the engine
+ * keeps ([tap][Cout][32]), bias_host NULL or [Cout].
+ *   out_dev     fp32 NHWC [B, H, W, Cout]
+ *   stats_dev   NULL, or fp64 {sum, sum of squares} of the stored values per (image, 256-pixel block, channel),
+ *               [B][H*W/256][Cout][2]; the whole buffer (stats_capacity_doubles) is first filled with 0xFF bytes;
+ *               *slices_out = H*W/256
+ * Fails where the forward would not take this path: a split-f16 arithmetic, a shape conv_in_supported refuses (Cin > 8,
+ * Cout not 32 | 64, W % 16, H*W % 256), SR3_NO_CONV_IN_F32=1; nothing is launched then. (tests) */
+int sr3_op_conv_in_f32(sr3_ctx *ctx, const float *state_nchw_dev, int B, int H, int W, int Cin, const float *weight_host,
+                       const float *bias_host, int Cout, float *out_dev, double *stats_dev, uint64_t stats_capacity_doubles,
+                       int *slices_out);
+/* Does an exact-f32 forward (precision 0; 1 | 2: never) run its first conv Cin -> Cout at H x W on conv_in_f32_kernel?
+ * 1 | 0: conv_in_supported's shape rule and SR3_NO_CONV_IN_F32 (host arithmetic only; needs no context and no GPU). */
+int sr3_conv_in_f32_gate(int Cin, int Cout, int H, int W, int precision);
 /* The UNet's last layer as the forward runs it (unet.py:229,263 final_conv = Block: GroupNorm -> Swish -> Conv3x3) behind
  * the folded GroupNorm affine: in_dev fp32 NHWC [B, H, W, C], gn_scale_dev / gn_shift_dev [B, C]
  * (sr3_op_groupnorm_affine), weight_host OIHW [Cout, C, 3, 3], bias_host [Cout], out_dev fp32 NHWC [B, H, W, Cout];
