@@ -13,6 +13,11 @@ and the candidates price the two CORRECTION terms at a cheaper MFMA rate:
     bf8c    xh·wh + b8(xl)·b8(wh) + b8(xh)·b8(wl)      b8 = OCP e5m2 = the rounded top byte of the fp16 value
     fp8c    xh·wh + s8(xl)·s8(wh) + s8(xh)·s8(wl)      s8 = OCP e4m3 with one power-of-two scale per 32 channels
                                                         (the block scale of v_mfma_scale_f32_16x16x128_f8f6f4)
+    fp8f<A> fixed activation scales, one weight scale per output column (a candidate; NOT the shipped format)
+    f8c     the SHIPPED format of the 'f16f8' arithmetic (tests/f8c_ref.py: fixed power-of-two scales SR3_F8_*, the
+            weights pre-scaled by one 2^k per tensor), in float64, for exactly the convs a predicate names — the ones
+            engine.conv_plan(...)["f8"] sends to the halo_f8c kernel; every other conv stays plain fp32
+            (ConvProxy("f8c", f8c_convs=...); tests/test_gpu_f8c_model.py runs a forward through it)
 
 The partial products themselves are accumulated by torch's CPU conv in fp32 (the MFMAs accumulate in fp32
 too); only the operand formats are emulated. Runs the reference-made sampler fixtures of tests/golden/ through
@@ -85,15 +90,34 @@ def s8_col(w):
 class ConvProxy:
     """Stands in for torch.nn.functional inside the oracle module: conv2d with emulated operand formats."""
 
-    def __init__(self, mode):
+    def __init__(self, mode, f8c_convs=None):
+        """f8c_convs(H, W, Cin, Cout, ks, stride, up2) -> bool (mode "f8c"): whether the conv of an H x W input takes the
+        fp8-correction kernel; up2: the conv reads the output of F.interpolate (an Upsample conv; H, W are the upsampled
+        sizes). Default: every 3x3 / stride 1 / padding 1 conv on channels in multiples of 32 that is no Upsample conv."""
         self.mode = mode
+        self.f8c_convs = f8c_convs or (lambda H, W, Cin, Cout, ks, stride, up2: not up2)
+        self._up = False
 
     def __getattr__(self, name):
         return getattr(F, name)
 
+    def interpolate(self, *a, **kw):
+        self._up = True
+        return F.interpolate(*a, **kw)
+
     def conv2d(self, x, w, b=None, stride=1, padding=0):
         m = self.mode
+        up2, self._up = self._up, False
         if m == "f32":
+            return F.conv2d(x, w, b, stride=stride, padding=padding)
+        if m == "f8c":
+            import f8c_ref
+            Cout, Cin, ks, _ = w.shape
+            if (ks, stride, padding) == (3, 1, 1) and Cin % 32 == 0 and Cout % 32 == 0 and \
+                    self.f8c_convs(x.shape[2], x.shape[3], Cin, Cout, ks, stride, up2):
+                g = np.ascontiguousarray(x.permute(0, 2, 3, 1).numpy(), np.float32)
+                y = f8c_ref.conv_f8c_model(g, w.numpy(), None if b is None else b.numpy())
+                return torch.from_numpy(np.ascontiguousarray(y.transpose(0, 3, 1, 2))).to(x.dtype)
             return F.conv2d(x, w, b, stride=stride, padding=padding)
         xh, xl = split16(x)
         wh, wl = split16(w)
@@ -109,7 +133,8 @@ class ConvProxy:
             y = y + F.conv2d(s8(xl, 1), s8(wh, 1), None, stride=stride, padding=padding) + \
                 F.conv2d(s8(xh, 1), s8(wl, 1), None, stride=stride, padding=padding)
         elif m.startswith("fp8f"):
-            # fixed activation scales: xh * 2^A, xl * 2^(A + 11); per-output-channel weight scales
+            # fixed activation scales: xh * 2^A, xl * 2^(A + 11); per-output-channel weight scales. A candidate that was
+            # not shipped: the library scales a weight tensor by ONE 2^k (mode "f8c" above restates that format)
             A = int(m[4:] or 4)
             y = y + F.conv2d(s8_fixed(xl, A + 11), s8_col(wh), None, stride=stride, padding=padding) + \
                 F.conv2d(s8_fixed(xh, A), s8_col(wl), None, stride=stride, padding=padding)

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 SR3_F8_XH, SR3_F8_XL = 0, 11        # csrc/sr3_internal.h
+SR3_F8_WH, SR3_F8_WL = -3, 9        # csrc/sr3_internal.h (the weights' side: tests/f8c_ref.py)
 
 
 def e4m3_bytes(v):

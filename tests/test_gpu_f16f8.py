@@ -6,7 +6,10 @@ fixtures (B = 1 or 2) are replicated along the batch and every replica is held t
 Bars: single conv 2e-4 absolute on O(1) outputs (observed 5.5e-5..6.1e-5; the CPU emulation of the same operand
 formats, tests/emulate_operand_formats.py, predicts 5.1e-5); UNet forward 5e-4 (observed 1e-5); samplers the north-star
 1e-3 (observed 9e-6 over T = 100, 1.9e-5 over the headline T = 1000 run).
-The reference computes in plain fp32 (model/sr/sr3_modules/unet.py:235-265, diffusion.py:189-215)."""
+The reference computes in plain fp32 (model/sr/sr3_modules/unet.py:235-265, diffusion.py:189-215).
+
+These bars are against the plain conv, ~5e-5 of which is the operand formats' own; tests/test_gpu_f8c_model.py holds the
+same kernel to a float64 model of its quantised operands (tests/f8c_ref.py) at a few 1e-6."""
 import numpy as np
 import pytest
 
